@@ -27,6 +27,11 @@ labels of the full-depth model on the committed golden inputs, tests/golden/vitb
 (the north-star's own target: image-tower forward at bs 256) and ``cfg5`` (a short ViT-L/14 fp16-mode leg).
 In the timed region the text tower runs on a side HIP stream next to the image tower (they are independent
 until the logits); the instrumented roofline step serialises them so each GEMM's duration is its own.
+
+``--dump-outputs DIR`` writes what the LAST timed step handed its caller -- loss_sum, correct, logits (rank 0's rows) and
+the flat LoRA + prompt parameters after AdamW with the gradient it applied (``features`` under --forward-only) -- as
+DIR/<name>.npy.  Inputs and weights come from fixed seeds, so two builds run with the same arguments can be compared
+output for output.
 """
 from __future__ import annotations
 
@@ -110,7 +115,37 @@ def parse():
     ap.add_argument("--no-extras", action="store_true", help="skip the forward_only / cfg5 legs after the timed region")
     ap.add_argument("--cfg5-budget-s", type=float, default=150.0,
                     help="skip the cfg-5 leg when the run has already taken this many seconds")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (rank 0)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """Writes ``arrays`` ({name: tensor}) as ``out_dir/<name>.npy`` in float32 (float64 where the tensor is float64).
+    Each array gets an equal share of 64 MB; an array over its share is replaced by a fixed, seeded sample of its
+    flattened elements (sorted indices, saved beside it as ``<name>_index.npy``), so two runs sample the same elements."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_MAX_BYTES // (2 * len(arrays))  # room for a sample and its index per array
+    written = []
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        a = a.astype(np.float64 if a.dtype == np.float64 else np.float32)
+        if a.nbytes > share:
+            n = share // 8  # a float64 index per sampled element
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=n, replace=False))
+            np.save(os.path.join(out_dir, f"{name}_index.npy"), idx.astype(np.float64))
+            written.append(f"{name}_index")
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+        written.append(name)
+    return written
 
 
 def self_launch(args) -> int:
@@ -360,13 +395,16 @@ def main():
     captions = synth.synth_captions(args.classes, 77, cfg.vocab_size, seed=1).to(dev)
     # caption rows 1..4 are the learnable prompt slots; keep EOT after them (synthetic captions have len >= 6)
 
+    last = {}  # what the most recent step() returned to its caller (--dump-outputs)
+
     def step():
         if args.forward_only:
             with torch.no_grad():
-                model.engine.vit_forward(images, False)
+                last["features"], _ = model.engine.vit_forward(images, False)
             return
         tr.flat.zero_grad()
-        tr.forward_backward(images, captions, labels, 1, gb, row_offset=lo)
+        last["loss_sum"], last["correct"], last["logits"] = tr.forward_backward(images, captions, labels, 1, gb,
+                                                                                 row_offset=lo)
         tr.optimizer_step()
 
     def barrier():
@@ -392,6 +430,15 @@ def main():
         dt = tmax.item()
     ms = dt / args.steps * 1e3
     value = gb * args.steps / dt
+
+    # ---- the last timed step's results, before any later leg steps the trainer again ----
+    if args.dump_outputs and rank == 0:
+        arrays = dict(last)
+        if not args.forward_only:  # the optimiser's result: flat LoRA + prompt parameters and the gradient it applied
+            arrays.update(params=tr.flat.params, grads=tr.flat.grads)
+        names = dump_outputs(args.dump_outputs, arrays)
+        print(f"[bench] outputs of the last timed step written to {args.dump_outputs}: {', '.join(names)}",
+              file=sys.stderr, flush=True)
 
     # ---- collectives: three more steps with every collective bracketed by HIP events on its launch stream ----
     coll = None
