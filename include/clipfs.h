@@ -329,6 +329,16 @@ int clipfs_logit_normalize(const float* z, float* out, float* work, int rows, in
 int clipfs_logit_normalize_bwd(const float* z, const float* dzn, float* dz, int rows, int classes, void* stream);
 /* out[c] = sum_r x[r,c] * (y ? y[r,c] : 1): bias / per-channel scale gradients of the head (fixed row order) */
 int clipfs_colsum(const float* x, const float* y, float* out, int rows, int cols, void* stream);
+/* Bias gradients: out_s[j] += sum_r x[r, s * seg_width + j] for the segments s = 0, 1, 2 of the `cols` columns
+ * (cols <= 3 seg_width; seg_width <= 0 means one segment of `cols`).  x has leading dimension ldx >= cols, so a slice is
+ * summed in place.  A NULL out_s is skipped (a frozen q / k / v segment of the packed in-projection bias); with every
+ * segment NULL nothing is launched.  The result is ACCUMULATED into the slots, like the LoRA gradient slots.
+ * Bitwise deterministic: a partial slab per row chunk, then a fixed-order pass (no float atomics).  work: >=
+ * clipfs_bias_grad_work_floats(rows, cols) floats, 16-byte aligned (may be NULL when that is 0).  float4 loads when
+ * cols, ldx and the base allow; the scalar form adds in the same order. */
+size_t clipfs_bias_grad_work_floats(int rows, int cols);
+int clipfs_bias_grad(const float* x, size_t ldx, int rows, int cols, int seg_width, float* out0, float* out1,
+                     float* out2, float* work, void* stream);
 /* Stage-2 self-consistency losses (slow_pace.py:1653-1658).
  * l1_loss: loss[0] = mean |a - b| (jittor nn.l1_loss); da (may be NULL) = sign(a - b) * grad_scale / n.
  * kl_logits: kl_div(log_softmax(logits), log_softmax(target_logits)) of slow_pace.py:1170-1177 per row:
@@ -384,6 +394,10 @@ typedef struct clipfs_block {
    * clipfs_convert_f16, format in clipfs_tower.weight_format); when present the tower's GEMMs use the
    * bf16 x 3 or f16 MFMA kernel, otherwise the exact fp32 MFMA kernel */
   const void *w_qkv_p, *w_o_p, *w_fc_p, *w_pr_p, *w_qkv_t_p, *w_o_t_p, *w_fc_t_p, *w_pr_t_p;
+  /* bias gradient slots (accumulated into by clipfs_tower_bwd / _bwd_sparse; NULL = frozen, nothing launched for it):
+   * LayerNorm biases, the q / k / v segments of the packed in-projection bias, out projection, c_fc, c_proj.
+   * Refused in the fp16 storage mode (weight_format 2), which keeps dqkv and the MLP gradient as f16 images only. */
+  float *g_ln1_b, *g_ln2_b, *g_b_q, *g_b_k, *g_b_v, *g_b_o, *g_b_fc, *g_b_pr;
 } clipfs_block;
 
 typedef struct clipfs_tower {

@@ -53,7 +53,8 @@ class Block(C.Structure):
         "w_pr", "b_pr", "w_pr_t",
         "lora_a_qkv", "lora_b_qkv", "lora_a_o", "lora_b_o",
         "g_lora_a_qkv", "g_lora_b_qkv", "g_lora_a_o", "g_lora_b_o")] + [("lora_mask", C.c_uint)] + [
-        (n, C.c_void_p) for n in ("w_qkv_p", "w_o_p", "w_fc_p", "w_pr_p", "w_qkv_t_p", "w_o_t_p", "w_fc_t_p", "w_pr_t_p")]
+        (n, C.c_void_p) for n in ("w_qkv_p", "w_o_p", "w_fc_p", "w_pr_p", "w_qkv_t_p", "w_o_t_p", "w_fc_t_p", "w_pr_t_p",
+                                  "g_ln1_b", "g_ln2_b", "g_b_q", "g_b_k", "g_b_v", "g_b_o", "g_b_fc", "g_b_pr")]
 
 
 class Tower(C.Structure):
@@ -125,6 +126,8 @@ SIGNATURES = {
     "clipfs_logit_normalize": (_i, [_p, _p, _p, _i, _i, _p]),
     "clipfs_logit_normalize_bwd": (_i, [_p, _p, _p, _i, _i, _p]),
     "clipfs_colsum": (_i, [_p, _p, _p, _i, _i, _p]),
+    "clipfs_bias_grad_work_floats": (_sz, [_i, _i]),
+    "clipfs_bias_grad": (_i, [_p, _sz, _i, _i, _i, _p, _p, _p, _p, _p]),
     "clipfs_l1_loss": (_i, [_p, _p, _sz, _p, _p, _f, _p]),
     "clipfs_kl_logits": (_i, [_p, _p, _p, _p, _i, _i, _f, _p]),
     "clipfs_adamw": (_i, [_p, _p, _p, _p, _sz, _i, _f, _f, _f, _f, _f, _f, _p]),

@@ -21,6 +21,14 @@ def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
     return None if t is None else t.data_ptr()
 
 
+def _bias_slot(p: Optional[torch.nn.Parameter]) -> Optional[torch.Tensor]:
+    """Gradient slot of a trainable bias (``grad_slot``, attached by FlatTrainables or the autograd route), else None:
+    a frozen bias gets no slot, and the backward launches nothing for it."""
+    if p is None or not p.requires_grad:
+        return None
+    return getattr(p, "grad_slot", None)
+
+
 def _mix_seed(base: int, step: int) -> int:
     """64-bit non-zero dropout seed for (base, step) -- splitmix64 finaliser."""
     z = (base * 0x9E3779B97F4A7C15 + step * 0xBF58476D1CE4E5B9 + 0x94D049BB133111EB) & 0xFFFFFFFFFFFFFFFF
@@ -88,6 +96,18 @@ class _TowerRT:
             b.w_o, b.b_o = _ptr(w_o), _ptr(b_o)
             b.w_fc, b.b_fc = _ptr(blk.mlp.c_fc.weight), _ptr(blk.mlp.c_fc.bias)
             b.w_pr, b.b_pr = _ptr(blk.mlp.c_proj.weight), _ptr(blk.mlp.c_proj.bias)
+            # bias gradient slots (NULL = frozen): the q / k / v segments of the packed in-projection bias separately
+            if lora:
+                gq, gk, gv = (_bias_slot(getattr(a, n).bias) for n in ("q_proj", "k_proj", "v_proj"))
+                go = _bias_slot(a.proj.bias)
+            else:
+                g = _bias_slot(a.in_proj_bias)
+                d = self.width
+                gq, gk, gv = (None, None, None) if g is None else (g[:d], g[d:2 * d], g[2 * d:])
+                go = _bias_slot(a.out_proj.bias)
+            b.g_b_q, b.g_b_k, b.g_b_v, b.g_b_o = _ptr(gq), _ptr(gk), _ptr(gv), _ptr(go)
+            b.g_ln1_b, b.g_ln2_b = _ptr(_bias_slot(blk.ln_1.bias)), _ptr(_bias_slot(blk.ln_2.bias))
+            b.g_b_fc, b.g_b_pr = _ptr(_bias_slot(blk.mlp.c_fc.bias)), _ptr(_bias_slot(blk.mlp.c_proj.bias))
             if train:
                 wt = self._transposed(i, blk)
                 b.w_qkv_t, b.w_o_t, b.w_fc_t, b.w_pr_t = _ptr(wt["qkv"]), _ptr(wt["o"]), _ptr(wt["fc"]), _ptr(wt["pr"])
@@ -295,21 +315,29 @@ class Engine:
         return feat, ctx
 
     def vit_backward(self, ctx: dict, dfeat: torch.Tensor) -> None:
-        """Accumulates into the LoRA gradient slots (and VPT.grad_slot)."""
+        """Accumulates into the LoRA gradient slots (and VPT.grad_slot, and the slots of trainable biases)."""
         v = self.model.visual
         B, L, d = ctx["B"], v.tokens, v.width
         dy = ops.gemm_nt(dfeat.contiguous(), v.proj.data)  # [B, width] = dfeat @ proj^T
+        g_post = _bias_slot(v.ln_post.bias)
+        if g_post is not None:
+            ops.bias_grad(dy, g_post)
+        # ln_pre's bias gradient is the column sum of the gradient wrt the tower input: block 0 then runs to the end
+        g_pre = _bias_slot(v.ln_pre.bias)
         mean1, rstd1 = ctx["stats"]
         # only the class-token row of each image carries gradient (jclip/model.py:121-124): it stays compact [B, width]
         # and the tower's last block works on B rows (clipfs_tower_bwd_sparse) -- no zero-filled [B*L, width] tensor
         dcls = ops.layernorm_bwd(dy, ctx["x_final"], v.ln_post.weight.data, mean1, rstd1, ldx=L * d)
         has_vpt = v.VPT is not None
+        stop = not (has_vpt or g_pre is not None)
         if ctx["one_row"]:  # the forward that produced ``saved`` decides (its last block kept one row per image)
             dx = self.vis.backward_sparse(dcls, self._class_rows(B, dfeat.device), B, ctx["saved"], ctx["seed"],
-                                          stop_at_input=not has_vpt, row0=ctx["row0"])
+                                          stop_at_input=stop, row0=ctx["row0"])
         else:
             dx = ops.scatter_rows(dcls, self._class_rows(B, dfeat.device), L)
-            self.vis.backward(dx, B, ctx["saved"], ctx["seed"], stop_at_input=not has_vpt, row0=ctx["row0"])
+            self.vis.backward(dx, B, ctx["saved"], ctx["seed"], stop_at_input=stop, row0=ctx["row0"])
+        if g_pre is not None:
+            ops.bias_grad(dx, g_pre)
         if has_vpt:
             x0, mean0, rstd0 = ctx["pre"]
             dx0 = ops.layernorm_bwd(dx, x0, v.ln_pre.weight.data, mean0, rstd0)
@@ -367,6 +395,9 @@ class Engine:
         m = self.model
         n, seq = ctx["n"], ctx["seq"]
         dy = ops.gemm_nt(dfeat.contiguous(), m.text_projection.data)
+        g_final = _bias_slot(m.ln_final.bias)
+        if g_final is not None:
+            ops.bias_grad(dy, g_final)
         mean, rstd = ctx["stats"]
         drows = ops.layernorm_bwd(dy, ctx["rows"], m.ln_final.weight.data, mean, rstd)
         # only the EOT row of each caption carries gradient (jclip/model.py:213-214)
@@ -395,6 +426,46 @@ def _tower_trainables(tower_mod) -> List[Tuple[torch.nn.Parameter, torch.Tensor]
     return out
 
 
+def _block_biases(tower_mod) -> List[torch.nn.Parameter]:
+    """Every bias parameter of a tower's blocks (LoRA blocks: the q / k / v views of the packed in-projection bias)."""
+    out = []
+    for blk in tower_mod.resblocks:
+        a = blk.attn
+        if getattr(a, "is_lora_mha", False):
+            out += [a.q_proj.bias, a.k_proj.bias, a.v_proj.bias, a.proj.bias]
+        else:
+            out += [a.in_proj_bias, a.out_proj.bias]
+        out += [blk.ln_1.bias, blk.ln_2.bias, blk.mlp.c_fc.bias, blk.mlp.c_proj.bias]
+    return out
+
+
+def image_biases(model) -> List[torch.nn.Parameter]:
+    v = model.visual
+    return [v.ln_pre.bias] + _block_biases(v.transformer) + [v.ln_post.bias]
+
+
+def text_biases(model) -> List[torch.nn.Parameter]:
+    return _block_biases(model.transformer) + [model.ln_final.bias]
+
+
+def _bias_pairs(biases) -> List[Tuple[torch.nn.Parameter, torch.Tensor]]:
+    """(bias, gradient slot) of the trainable ones; a slot is attached where none is yet (autograd route)."""
+    out = []
+    for p in biases:
+        if p is not None and p.requires_grad:
+            _ensure_slot(p)
+            out.append((p, p.grad_slot))
+    return out
+
+
+def _image_trainables(model):
+    return _tower_trainables(model.visual.transformer) + _bias_pairs(image_biases(model))
+
+
+def _text_trainables(model):
+    return _tower_trainables(model.transformer) + _bias_pairs(text_biases(model))
+
+
 def _zero_slots(pairs):
     for _, g in pairs:
         g.zero_()
@@ -413,7 +484,7 @@ class _EncodeImage(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dfeat):
         model = ctx.model
-        pairs = _tower_trainables(model.visual.transformer)
+        pairs = _image_trainables(model)
         _zero_slots(pairs)
         v = model.visual
         if v.VPT is not None:
@@ -437,7 +508,7 @@ class _EncodeText(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dfeat):
         model = ctx.model
-        pairs = _tower_trainables(model.transformer)
+        pairs = _text_trainables(model)
         _zero_slots(pairs)
         slot = None
         if ctx.prompt is not None:
@@ -448,7 +519,7 @@ class _EncodeText(torch.autograd.Function):
 
 def encode_image(model, images: torch.Tensor) -> torch.Tensor:
     images = images.to(device=model.device, dtype=torch.float32)
-    pairs = _tower_trainables(model.visual.transformer)
+    pairs = _image_trainables(model)
     params = [p for p, _ in pairs]
     if model.visual.VPT is not None:
         _ensure_slot(model.visual.VPT)
@@ -462,7 +533,7 @@ def encode_image(model, images: torch.Tensor) -> torch.Tensor:
 
 
 def encode_text(model, ids: torch.Tensor, prompt_ctx: Optional[torch.Tensor] = None) -> torch.Tensor:
-    pairs = _tower_trainables(model.transformer)
+    pairs = _text_trainables(model)
     params = [p for p, _ in pairs]
     needs = any(p.requires_grad for p in params) or (prompt_ctx is not None and prompt_ctx.requires_grad)
     if torch.is_grad_enabled() and needs:

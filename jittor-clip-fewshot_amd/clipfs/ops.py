@@ -395,6 +395,27 @@ def colsum(x, y=None):
     return out
 
 
+def bias_grad(x, out, seg_width: int = 0, rows: Optional[int] = None, work: Optional[torch.Tensor] = None):
+    """Accumulate column sums of ``x`` [rows, cols] (row stride ``x.stride(0)``, unit column stride) into bias gradient
+    slots: ``out`` is one tensor, or a sequence of up to three (None = frozen segment, skipped) receiving the columns
+    ``[s * seg_width, (s + 1) * seg_width)``.  ``rows`` (default ``x.shape[0]``) sums a leading part only.  Bitwise
+    deterministic (clipfs_bias_grad)."""
+    assert x.dtype == torch.float32 and x.dim() == 2 and x.stride(1) == 1
+    outs = list(out) if isinstance(out, (list, tuple)) else [out]
+    assert 1 <= len(outs) <= 3
+    for o in outs:
+        assert o is None or (o.dtype == torch.float32 and o.is_contiguous() and o.device == x.device)
+    outs += [None] * (3 - len(outs))
+    n = x.shape[0] if rows is None else rows
+    cols = x.shape[1]
+    lib = _lib.load()
+    need = lib.clipfs_bias_grad_work_floats(n, cols)
+    if need and (work is None or work.numel() < need):
+        work = torch.empty(need, device=x.device, dtype=torch.float32)
+    check(lib.clipfs_bias_grad(_p(x), x.stride(0), n, cols, seg_width, _p(outs[0]), _p(outs[1]), _p(outs[2]),
+                               _p(work) if need else None, _stream()), "bias_grad")
+
+
 def adamw(p, g, m, v, step, lr=2e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, grad_scale=1.0):
     check(_lib.load().clipfs_adamw(_p(p), _p(g), _p(m), _p(v), p.numel(), step, lr, betas[0], betas[1], eps,
                                    weight_decay, grad_scale, _stream()), "adamw")

@@ -55,8 +55,20 @@ static SavedLayout saved_layout(const clipfs_tower* t, size_t M) {
   return L;
 }
 
+// bias gradient slots (clipfs_block.g_*): NULL everywhere = bias='none', and then the backward launches exactly what it
+// launched before they existed
+static inline bool block_has_bias_slots(const clipfs_block& b) {
+  return b.g_ln1_b || b.g_ln2_b || b.g_b_q || b.g_b_k || b.g_b_v || b.g_b_o || b.g_b_fc || b.g_b_pr;
+}
+static bool tower_has_bias_slots(const clipfs_tower* t) {
+  if (!t->blocks || t->block_size != sizeof(clipfs_block)) return false;
+  for (int l = 0; l < t->layers; ++l)
+    if (block_has_bias_slots(t->blocks[l])) return true;
+  return false;
+}
+
 struct ScratchLayout {
-  size_t h, big, b3, b1, dt, work, gemm_ws, gemm_ws_floats, a16, c16, total;
+  size_t h, big, b3, b1, dt, work, gemm_ws, gemm_ws_floats, a16, c16, bwork, total;
   size_t counter_ints;  // stream-K arrival counters the tower's largest GEMM needs (a separate, caller-zeroed buffer)
 };
 
@@ -90,6 +102,18 @@ static ScratchLayout scratch_layout(const clipfs_tower* t, size_t M) {
   // fp16 storage mode (weight_format 2): f16 images of the GEMM operands, M x 4d halves each
   S.a16 = o; o += t->weight_format == 2 ? al4(M * 2 * d) : 0;
   S.c16 = o; o += t->weight_format == 2 ? al4(M * 2 * d) : 0;
+  // partial slab of the bias-gradient column sums (clipfs_bias_grad), only when some block has a bias slot
+  size_t bw = 0;
+  if (tower_has_bias_slots(t)) {
+    const int widths[3] = {(int)d, 3 * (int)d, 4 * (int)d};
+    for (int k = 0; k < 2; ++k)
+      for (int i = 0; i < 3; ++i) {
+        if (!row_counts[k]) continue;
+        const size_t w = clipfs_bias_grad_work_floats((int)row_counts[k], widths[i]);
+        bw = w > bw ? w : bw;
+      }
+  }
+  S.bwork = o; o += al4(bw);
   S.total = o;
   return S;
 }
@@ -106,6 +130,9 @@ static int check_tower(const clipfs_tower* t, int batch) {
     for (int l = 0; l < t->layers; ++l) {
       const clipfs_block& b = t->blocks[l];
       CLIPFS_REQUIRE(b.w_qkv_p && b.w_o_p && b.w_fc_p && b.w_pr_p, "tower: block %d lacks f16 weight copies", l);
+      // dqkv and the MLP gradient exist only as f16 images there: nothing to take the bias column sums of
+      CLIPFS_REQUIRE(!block_has_bias_slots(b), "tower: bias gradients are not supported in the fp16 storage mode (block %d)",
+                     l);
     }
   return CLIPFS_OK;
 }
@@ -177,6 +204,13 @@ static int gemm(const TowerCtx& cx, const float* A, const float* B, const void* 
     CLIPFS_REQUIRE(!c16_only, "tower: the f16 x f16 GEMM is required for an f16-only result");
   }
   return clipfs_gemm_nt(&a, st);
+}
+
+// accumulate the column sums of a dense [rows, cols] tensor into up to three bias slots (nothing when all are NULL)
+static int bias_sum(const float* x, int rows, int cols, int segw, float* o0, float* o1, float* o2, float* work,
+                    hipStream_t st) {
+  if (!o0 && !o1 && !o2) return CLIPFS_OK;
+  return clipfs_bias_grad(x, (size_t)cols, rows, cols, segw, o0, o1, o2, work, st);
 }
 
 }  // namespace clipfs
@@ -375,17 +409,24 @@ static int tower_bwd_range(const clipfs_tower* t, float* dx, int batch, const fl
     float* dqkv = scratch + SC.b3;
     float* dt = scratch + SC.dt;
     float* work = scratch + SC.work;
+    float* bwork = scratch + SC.bwork;
+    // bias gradients: column sums of the tensors below, each taken right after it is written (c_proj: the residual
+    // gradient entering the block; c_fc: du; ln_2: dh2; out projection: dx after LN2'; q/k/v: dqkv; ln_1: dh1)
+    CLIPFS_CHECK(bias_sum(dx, M, d, d, b.g_b_pr, nullptr, nullptr, bwork, st));
     // MLP: du = (dx Wpr) * gelu'(u) ; dh2 = du Wfc ; dx += LN2'(dh2)
     CLIPFS_CHECK(gemm(cx, dx, b.w_pr_t, b.w_pr_t_p, du, M, 4 * d, d, nullptr, nullptr, 2, nullptr, sv + SL.u, nullptr, nullptr, 0, 0, 0,
                       0.f, st, CHAIN_OUT16, h16));
+    CLIPFS_CHECK(bias_sum(du, M, 4 * d, 4 * d, b.g_b_fc, nullptr, nullptr, bwork, st));
     CLIPFS_CHECK(gemm(cx, du, b.w_fc_t, b.w_fc_t_p, dh, M, d, 4 * d, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 0.f,
                       st, CHAIN_IN16));
+    CLIPFS_CHECK(bias_sum(dh, M, d, d, b.g_ln2_b, nullptr, nullptr, bwork, st));
     if (h16)
       CLIPFS_CHECK(clipfs_layernorm_bwd_f16(dh, sv + SL.x_mid, d, b.ln2_g, sv + SL.stat2, sv + SL.stat2 + M, dx, dx, h16, d,
                                             M, d, st));
     else
       CLIPFS_CHECK(clipfs_layernorm_bwd(dh, sv + SL.x_mid, d, b.ln2_g, sv + SL.stat2, sv + SL.stat2 + M, dx, dx, d, M, d,
                                         st));
+    CLIPFS_CHECK(bias_sum(dx, M, d, d, b.g_b_o, nullptr, nullptr, bwork, st));
     // attention output projection.  fp16 storage mode without an o-projection adapter: its only consumer is the f16
     // attention backward, which rounds dO to f16 for its MFMA operands anyway -- the GEMM writes the f16 image alone (into
     // the same scratch slot): a quarter of the epilogue bytes of an fp32 result, half the bytes the attention kernels stage
@@ -409,21 +450,25 @@ static int tower_bwd_range(const clipfs_tower* t, float* dx, int batch, const fl
     } else
       CLIPFS_CHECK(clipfs_attention_bwd(sv + SL.qkv, datt, sv + SL.att, sv + SL.lse, dqkv, dh, batch, t->seq, t->heads,
                                         t->causal, st));
+    CLIPFS_CHECK(bias_sum(dqkv, M, 3 * d, d, b.g_b_q, b.g_b_k, b.g_b_v, bwork, st));
     const bool need_dx = !(l == 0 && stop_at_input);
-    if (need_dx)
+    // dh1 (the gradient wrt LayerNorm 1's output) is also needed for ln_1's bias gradient, even where dx is not
+    const bool need_dh = need_dx || b.g_ln1_b;
+    if (need_dh)
       CLIPFS_CHECK(gemm(cx, dqkv, b.w_qkv_t, b.w_qkv_t_p, dh, M, d, 3 * d, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, 0, 0, 0,
                         0.f, st, CHAIN_NONE, dqkv16_ready));
     if (qkv_mask) {
       CLIPFS_REQUIRE(b.g_lora_a_qkv && b.g_lora_b_qkv, "tower_bwd: block %d LoRA gradient slots missing", l);
       if (dy16)
         CLIPFS_CHECK(clipfs_lora_bwd_f16dy(dqkv16, sv + SL.h1, sv + SL.t_qkv, b.lora_a_qkv, b.lora_b_qkv, dt, b.g_lora_a_qkv,
-                                           b.g_lora_b_qkv, need_dx ? dh : nullptr, M, d, d, r, 3, qkv_mask, t->lora_scale,
+                                           b.g_lora_b_qkv, need_dh ? dh : nullptr, M, d, d, r, 3, qkv_mask, t->lora_scale,
                                            t->lora_dropout, seed, ds, t->dropout_row0, keep_bits_saved(t) ? (const void*)(sv + SL.keep) : nullptr, work, st));
       else
         CLIPFS_CHECK(clipfs_lora_bwd(dqkv, sv + SL.h1, sv + SL.t_qkv, b.lora_a_qkv, b.lora_b_qkv, dt, b.g_lora_a_qkv,
-                                     b.g_lora_b_qkv, need_dx ? dh : nullptr, M, d, d, r, 3, qkv_mask, t->lora_scale,
+                                     b.g_lora_b_qkv, need_dh ? dh : nullptr, M, d, d, r, 3, qkv_mask, t->lora_scale,
                                      t->lora_dropout, seed, ds, t->dropout_row0, keep_bits_saved(t) ? (const void*)(sv + SL.keep) : nullptr, work, st));
     }
+    CLIPFS_CHECK(bias_sum(dh, M, d, d, b.g_ln1_b, nullptr, nullptr, bwork, st));
     if (need_dx) {
       if (h16)
         CLIPFS_CHECK(clipfs_layernorm_bwd_f16(dh, sv + SL.x_in, d, b.ln1_g, sv + SL.stat1, sv + SL.stat1 + M, dx, dx, h16, d,
@@ -476,7 +521,10 @@ extern "C" int clipfs_tower_bwd_sparse(const clipfs_tower* t, const float* dxs, 
   float* datt_s = dxm_s + (size_t)Ms * d;
   float* mean_s = datt_s + (size_t)Ms * d;
   float* rstd_s = mean_s + al4((size_t)Ms);
+  float* bwork = scratch + SC.bwork;
   // ---- MLP and output projection on the `batch` rows that carry gradient ----
+  // (their bias gradients are column sums over those rows: the other rows' gradients are exact zeros)
+  CLIPFS_CHECK(bias_sum(dxs, Ms, d, d, b.g_b_pr, nullptr, nullptr, bwork, st));
   // fp16 storage mode: the `batch`-row products use the fp32 master weights (plane argument NULL); the saved pre-GELU
   // activation is an f16 tensor there
   const bool f16m = t->weight_format == 2;
@@ -489,9 +537,12 @@ extern "C" int clipfs_tower_bwd_sparse(const clipfs_tower* t, const float* dxs, 
   CLIPFS_CHECK(clipfs_gather_seq_rows(sv + SL.stat2 + M, 1, rows, rstd_s, Ms, seq, 1, st));
   CLIPFS_CHECK(gemm(cx, dxs, b.w_pr_t, f16m ? nullptr : b.w_pr_t_p, du_s, Ms, 4 * d, d, nullptr, nullptr, 2, nullptr, u_s, nullptr, nullptr,
                     0, 0, 0, 0.f, st));
+  CLIPFS_CHECK(bias_sum(du_s, Ms, 4 * d, 4 * d, b.g_b_fc, nullptr, nullptr, bwork, st));
   CLIPFS_CHECK(gemm(cx, du_s, b.w_fc_t, f16m ? nullptr : b.w_fc_t_p, dh_s, Ms, d, 4 * d, nullptr, nullptr, 0, nullptr, nullptr, nullptr,
                     nullptr, 0, 0, 0, 0.f, st));
+  CLIPFS_CHECK(bias_sum(dh_s, Ms, d, d, b.g_ln2_b, nullptr, nullptr, bwork, st));
   CLIPFS_CHECK(clipfs_layernorm_bwd(dh_s, xmid_s, d, b.ln2_g, mean_s, rstd_s, dxs, dxm_s, d, Ms, d, st));
+  CLIPFS_CHECK(bias_sum(dxm_s, Ms, d, d, b.g_b_o, nullptr, nullptr, bwork, st));
   CLIPFS_CHECK(gemm(cx, dxm_s, b.w_o_t, f16m ? nullptr : b.w_o_t_p, datt_s, Ms, d, d, nullptr, nullptr, 0, nullptr, nullptr, nullptr,
                     nullptr, 0, 0, 0, 0.f, st));
   // ---- attention and the QKV projection see every row again ----
@@ -511,23 +562,26 @@ extern "C" int clipfs_tower_bwd_sparse(const clipfs_tower* t, const float* dxs, 
     dqkv16_ready = dqkv16;
   } else
     CLIPFS_CHECK(clipfs_attention_bwd(sv + SL.qkv, datt, sv + SL.att, sv + SL.lse, dqkv, dh, batch, seq, t->heads, t->causal, st));
+  CLIPFS_CHECK(bias_sum(dqkv, M, 3 * d, d, b.g_b_q, b.g_b_k, b.g_b_v, bwork, st));
   const uint32_t ds = t->dropout_stream0 + 4u * (uint32_t)l;
   const bool need_dx = !(l == 0 && stop_at_input);
-  if (need_dx)
+  const bool need_dh = need_dx || b.g_ln1_b;  // as in tower_bwd_range
+  if (need_dh)
     CLIPFS_CHECK(gemm(cx, dqkv, b.w_qkv_t, b.w_qkv_t_p, dh, M, d, 3 * d, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, 0, 0,
                       0, 0.f, st, CHAIN_NONE, dqkv16_ready));
   if (qkv_mask) {
     CLIPFS_REQUIRE(b.g_lora_a_qkv && b.g_lora_b_qkv, "tower_bwd: block %d LoRA gradient slots missing", l);
     if (dy16)
       CLIPFS_CHECK(clipfs_lora_bwd_f16dy(dqkv16, sv + SL.h1, sv + SL.t_qkv, b.lora_a_qkv, b.lora_b_qkv, dt, b.g_lora_a_qkv,
-                                         b.g_lora_b_qkv, need_dx ? dh : nullptr, M, d, d, r, 3, qkv_mask, t->lora_scale,
+                                         b.g_lora_b_qkv, need_dh ? dh : nullptr, M, d, d, r, 3, qkv_mask, t->lora_scale,
                                          t->lora_dropout, t->dropout_seed, ds, t->dropout_row0, keep_bits_saved(t) ? (const void*)(sv + SL.keep) : nullptr,
                                          work, st));
     else
       CLIPFS_CHECK(clipfs_lora_bwd(dqkv, sv + SL.h1, sv + SL.t_qkv, b.lora_a_qkv, b.lora_b_qkv, dt, b.g_lora_a_qkv, b.g_lora_b_qkv,
-                                   need_dx ? dh : nullptr, M, d, d, r, 3, qkv_mask, t->lora_scale, t->lora_dropout,
+                                   need_dh ? dh : nullptr, M, d, d, r, 3, qkv_mask, t->lora_scale, t->lora_dropout,
                                    t->dropout_seed, ds, t->dropout_row0, keep_bits_saved(t) ? (const void*)(sv + SL.keep) : nullptr, work, st));
   }
+  CLIPFS_CHECK(bias_sum(dh, M, d, d, b.g_ln1_b, nullptr, nullptr, bwork, st));
   if (!need_dx) return CLIPFS_OK;
   CLIPFS_CHECK(clipfs_layernorm_bwd(dh, sv + SL.x_in, d, b.ln1_g, sv + SL.stat1, sv + SL.stat1 + M, nullptr, dx, d, M, d, st));
   CLIPFS_CHECK(clipfs_add_seq_rows(dxm_s, rows, dx, batch, seq, d, st));  // the residual branch around the attention

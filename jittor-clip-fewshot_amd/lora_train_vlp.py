@@ -17,7 +17,7 @@ from __future__ import annotations
 import math
 import os
 import pickle
-from typing import Dict, Optional, Sequence
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -75,11 +75,11 @@ def mark_only_lora_as_trainable(model, bias: str = 'none') -> None:
     """lora_train_vlp.py:143-160: freeze everything whose name has no ``lora_``; ``bias='all'`` re-enables every
     parameter named ``*bias*``, ``'lora_only'`` the bias of each LoRA-wrapped linear, anything else raises
     NotImplementedError.  The flags are set exactly as the reference sets them (so ``get_lora_parameters`` /
-    optimiser parameter lists come out the same).  NOTE: the reference's own training loop never uses a mode other than
-    'none' (its optimiser is built from ``get_lora_parameters(model)``, lora_train_vlp.py:946); the fused HIP backward
-    computes adapter / prompt gradients only, so a bias enabled here receives no gradient from ``LoRATrainer`` -- which is
-    also what the reference does with it, since ``p.requires_grad_ = True`` (:151,:157) assigns an attribute instead of
-    calling the method."""
+    optimiser parameter lists come out the same).  ``LoRATrainer`` trains exactly the biases flagged here (see
+    ``trainable_biases``): the fused backward writes their gradients into the flat buffer next to the adapters', and the
+    autograd route (``encode_image`` / ``encode_text``) returns them in ``param.grad``.  (The reference's own loop
+    never trains a bias: its optimiser is built from ``get_lora_parameters(model)``, lora_train_vlp.py:946, and
+    ``p.requires_grad_ = True`` at :151,:157 assigns an attribute instead of calling the method.)"""
     for n, p in model.named_parameters():
         if 'lora_' not in n:
             p.requires_grad_(False)
@@ -95,9 +95,6 @@ def mark_only_lora_as_trainable(model, bias: str = 'none') -> None:
                 m.bias.requires_grad_(True)
     else:
         raise NotImplementedError
-    import warnings
-    warnings.warn(f"mark_only_lora_as_trainable(bias={bias!r}): the flags are set as the reference sets them, but the fused "
-                  "backward (LoRATrainer) produces adapter / prompt gradients only -- these biases will NOT be trained")
 
 
 def lora_state_dict(model, bias: str = 'none'):
@@ -241,6 +238,8 @@ class PlainMultiheadAttentionLoRA(nn.Module, LoRALayer):
             if isinstance(old, LinearLoRA) and isinstance(m, LinearLoRA):
                 m.w_lora_A.requires_grad_(old.w_lora_A.requires_grad)
                 m.w_lora_B.requires_grad_(old.w_lora_B.requires_grad)
+            if old is not None and old.bias is not None and m.bias is not None:
+                m.bias.requires_grad_(old.bias.requires_grad)  # a bias flagged trainable stays flagged
             setattr(self, k, m)
 
     # -- engine hooks -------------------------------------------------------------------------------
@@ -494,13 +493,53 @@ def evaluate_lora(args, clip_model, loader, templates=None, textual_features=Non
 # flat trainable buffer + stage-1 step (lora_train_vlp.py:946,956-1002)
 # ----------------------------------------------------------------------------------------------
 
+def trainable_biases(model) -> List[Tuple[str, nn.Parameter]]:
+    """(name, parameter) of the biases ``LoRATrainer`` trains: exactly those with ``requires_grad=True``, in
+    ``model.named_parameters()`` order.  The flags come from ``mark_only_lora_as_trainable(model, bias)``:
+
+    - 'none': no bias;
+    - 'all': every bias of both towers (block LayerNorms, packed in-projection or its q / k / v views, out projection,
+      c_fc, c_proj) plus ``visual.ln_pre`` / ``visual.ln_post`` / ``ln_final``;
+    - 'lora_only': the biases of the LoRA-wrapped linears (``q_proj.bias`` ... ``proj.bias`` of the enabled projections).
+
+    The 'lora_only' rule deliberately follows the FLAGS, not ``get_lora_parameters(model, 'lora_only')``: the reference's
+    filter builds the bias name as ``name.split('lora_')[0] + 'bias'`` = ``...q_proj.w_bias`` (the adapter is called
+    ``w_lora_A``), finds no such parameter and so hands the optimiser no bias at all -- kept as it is in
+    ``get_lora_parameters`` (reference-faithful), not repeated here.
+
+    Any other CLIP parameter flagged trainable (a weight, an embedding, a LayerNorm gain) has no gradient in the fused
+    backward: ValueError naming it, instead of silently leaving it untouched."""
+    from clipfs.engine import image_biases, text_biases
+    known = {id(p) for p in image_biases(model) + text_biases(model) if p is not None}
+    out, bad = [], []
+    for n, p in model.named_parameters():
+        if not p.requires_grad or 'lora_' in n:
+            continue
+        if id(p) in known:
+            out.append((n, p))
+        elif n != 'visual.VPT':  # the VPT tokens are trained as an extra tensor (LoRATrainer)
+            bad.append(n)
+    if bad:
+        raise ValueError("the fused backward computes gradients for LoRA adapters, prompt / VPT tokens and biases only; "
+                         f"these parameters are flagged trainable but would never be updated: {', '.join(bad)}")
+    return out
+
+
 class FlatTrainables:
-    """Re-homes every stacked LoRA tensor (text blocks, then vision blocks: apply_lora order) plus the
-    optional prompt / VPT tokens into ONE contiguous fp32 buffer with matching gradient and AdamW
-    moment buffers: a single RCCL all-reduce and a single optimiser launch per step."""
+    """Re-homes every stacked LoRA tensor (text blocks, then vision blocks: apply_lora order), the
+    optional prompt / VPT tokens and the trainable biases (``trainable_biases``) into ONE contiguous fp32 buffer
+    with matching gradient and AdamW moment buffers: a single RCCL all-reduce and a single optimiser launch per step.
+
+    Biases go last, so with none flagged the buffer is exactly what it was without them.  Each trainable bias parameter
+    becomes a view of the buffer (``state_dict`` returns the trained values) with ``grad_slot`` the matching view of the
+    gradient buffer.  The packed in-projection bias the QKV GEMM reads: when all three q / k / v views of a LoRA block
+    train, their slices are adjacent and the packed tensor IS that 3d slice; when only some do (``lora_only`` with
+    ``params=['q', 'v']``), the trained segments get their own slices and ``sync_packed`` copies them into the packed
+    tensor (3d floats per block) -- a frozen segment is never in the buffer, so AdamW's weight decay cannot touch it."""
 
     def __init__(self, model, extra: Sequence[nn.Parameter] = ()):
         self.model = model
+        bias_names = [n for n, _ in trainable_biases(model)]
         entries = []
         for tower in (model.transformer, model.visual.transformer):
             for blk in tower.resblocks:
@@ -508,7 +547,8 @@ class FlatTrainables:
                 if getattr(a, "is_lora_mha", False):
                     for name, p, _ in a.stacked():
                         entries.append((a, name, p))
-        n = sum(p.numel() for _, _, p in entries) + sum(p.numel() for p in extra)
+        n_bias = sum(p.numel() for _, p in trainable_biases(model))
+        n = sum(p.numel() for _, _, p in entries) + sum(p.numel() for p in extra) + n_bias
         if n == 0:
             raise ValueError("model has no trainable adapter parameters (call apply_lora first)")
         dev = model.device
@@ -530,8 +570,55 @@ class FlatTrainables:
             p.grad_slot = self.grads[off:off + k].view_as(p)
             self.extra.append(p)
             off += k
+        # biases (after the LoRA rebinds above: those rebuild the q / k / v / proj modules, flags carried over)
+        named = dict(model.named_parameters())
+        self.bias_names = bias_names
+        self.bias_offset = off
+        self._packed_dst, self._packed_src = [], []
+        owner = {}  # id(q/k/v_proj.bias) -> (attention block, segment)
+        for tower in (model.transformer, model.visual.transformer):
+            for blk in tower.resblocks:
+                a = blk.attn
+                if getattr(a, "is_lora_mha", False):
+                    for s, nm in enumerate(("q_proj", "k_proj", "v_proj")):
+                        owner[id(getattr(a, nm).bias)] = (a, s)
+        seg_off = {}  # attention block -> {segment: offset of its slice}
+        for name in bias_names:
+            p = named[name]
+            k = p.numel()
+            view = self.params[off:off + k].view_as(p)
+            view.copy_(p.data)
+            p.data = view
+            p.grad_slot = self.grads[off:off + k].view_as(p)
+            if id(p) in owner:
+                a, s = owner[id(p)]
+                seg_off.setdefault(a, {})[s] = off
+            off += k
+        for tower in (model.transformer, model.visual.transformer):
+            for blk in tower.resblocks:
+                a = blk.attn
+                if getattr(a, "is_lora_mha", False) and a.proj.bias.requires_grad:
+                    a._o_b = a.proj.bias.data  # the direct (single-block) forward reads the same storage
+        for a, segs in seg_off.items():
+            d = a.embed_dim
+            if len(segs) == 3 and segs[1] == segs[0] + d and segs[2] == segs[0] + 2 * d:
+                # adjacent in the buffer (named_parameters order q, k, v): the packed bias becomes that slice
+                a.qkv_bias = self.params[segs[0]:segs[0] + 3 * d]
+            else:
+                for s, o in segs.items():
+                    self._packed_dst.append(a.qkv_bias[s * d:(s + 1) * d])
+                    self._packed_src.append(self.params[o:o + d])
+        assert off == n
         self.numel = n
+        self.sync_packed()
         model.invalidate_engine()
+
+    def sync_packed(self):
+        """Copy the trained q / k / v bias segments into the packed in-projection biases of the blocks where only some of
+        the three train (nothing to do otherwise)."""
+        if self._packed_dst:
+            with torch.no_grad():
+                torch._foreach_copy_(self._packed_dst, self._packed_src)
 
     def zero_grad(self):
         self.grads.zero_()
@@ -559,6 +646,9 @@ class LoRATrainer:
         if model.visual.VPT is not None and model.visual.VPT.requires_grad:
             extra.append(model.visual.VPT)
         self.flat = FlatTrainables(model, extra)
+        if self.flat.bias_names and model.engine.precision == "fp16":
+            raise ValueError("bias training is not supported in the fp16 storage mode (dqkv and the MLP gradient exist "
+                             "only as f16 images there): use precision 'fp32' or 'bf16x3'")
         self.prompt_ctx = prompt_ctx
         self.lr, self.wd, self.betas, self.eps = lr, weight_decay, betas, eps
         self.logit_scale = logit_scale
@@ -616,6 +706,7 @@ class LoRATrainer:
         from clipfs import dist as D
         m = self.model
         eng = m.engine
+        self.flat.sync_packed()  # packed q/k/v biases of partially trained blocks (no-op otherwise)
         seed = eng.next_seed() if m.training else 0
         B = images.shape[0]
         gb = global_batch or B * self.world
@@ -683,6 +774,7 @@ class LoRATrainer:
         self.t += 1
         ops.adamw(self.flat.params, self.flat.grads, self.flat.m, self.flat.v, self.t, self.lr, self.betas, self.eps,
                   self.wd, grad_scale)
+        self.flat.sync_packed()
 
     def step(self, images, captions, target, templates_per_class: int = 1, global_batch: Optional[int] = None,
              row_offset: int = 0):
