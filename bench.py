@@ -17,14 +17,18 @@ in HBM before the timed region.  One step = one such pass over one global batch 
 N > 1 is STRONG scaling (global batch fixed at 256, 256/N images per rank); the
 text tower is class-sharded (ceil(403/N) captions per rank); collectives per step over RCCL: ONE
 all_gather_into_tensor of the class-feature blocks, ONE reduce_scatter_tensor of their gradient and ONE all-reduce
-of the flat 1.5 MB LoRA+prompt gradient buffer (clipfs/dist.py); their per-step time is measured with HIP events
-and reported (``collective_ms_per_step``).  ``--weak`` keeps 256 images per rank instead.
+of the flat 1.5 MB LoRA+prompt gradient buffer (clipfs/dist.py); under --full their per-step time is measured with HIP
+events and reported (``collective_ms_per_step``).  ``--weak`` keeps 256 images per rank instead.
 
-Rank 0 prints ONE JSON line.  Extra objects: ``roofline`` (dominant kernel = the fp32-MFMA GEMM; every
-GEMM launch of one extra, instrumented step is bracketed by HIP events on its launch stream) and
-``cpu_baseline`` (the CPU oracle timed on the host cores on a bounded sample; N = 1 only), ``top5_match`` (top-5
-labels of the full-depth model on the committed golden inputs, tests/golden/vitb32_full_step.npz), ``forward_only``
-(the north-star's own target: image-tower forward at bs 256) and ``cfg5`` (a short ViT-L/14 fp16-mode leg).
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps, writes ``--dump-outputs`` and prints
+the headline fields; it runs nothing else.  ``--full`` adds every other measurement and check, each after the timed
+region except the golden check (it needs the pristine adapters): ``top5_match`` (top-5 labels of the full-depth model
+on the committed golden inputs, tests/golden/vitb32_full_step.npz), ``collective_ms_per_step`` (N > 1 or
+--rccl-one-rank), ``roofline`` (dominant kernel = the fp32-MFMA GEMM; every GEMM launch of one extra, instrumented
+step is bracketed by HIP events on its launch stream), ``variants`` (opt-in modes), ``forward_only`` (the
+north-star's own target: image-tower forward at bs 256), ``cfg4`` (MTA test-time augmentation), ``cfg5`` (a short
+ViT-L/14 fp16-mode leg) and ``cpu_baseline`` (the CPU oracle timed on the host cores on a bounded sample; N = 1
+only).  The --no-* flags drop single legs of a --full run.
 In the timed region the text tower runs on a side HIP stream next to the image tower (they are independent
 until the logits); the instrumented roofline step serialises them so each GEMM's duration is its own.
 
@@ -96,13 +100,16 @@ def parse():
     ap.add_argument("--weak", action="store_true", help="keep --batch images PER RANK (weak scaling)")
     ap.add_argument("--no-shard-text", action="store_true", help="replicate the text tower on every rank")
     ap.add_argument("--dropout", type=float, default=0.25, help="LoRA input dropout (reference default 0.25)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, run every other measurement and check: golden top-5, collective timing, "
+                         "roofline step, opt-in variants, forward_only / cfg4 / cfg5 legs, CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="--full without the roofline step")
     ap.add_argument("--serial-towers", action="store_true",
                     help="run the text and image towers back to back on one stream (default: text tower on a side stream)")
     ap.add_argument("--model", choices=["b32", "l14"], default="b32",
                     help="b32: the headline ViT-B/32 cfg-2; l14: cfg-5 shapes (ViT-L/14, LoRA r=16, synthetic adapters)")
-    ap.add_argument("--no-variants", action="store_true", help="skip the opt-in-mode measurements after the timed region")
+    ap.add_argument("--no-variants", action="store_true", help="--full without the opt-in-mode measurements")
     ap.add_argument("--precision", choices=["fp32", "bf16x3", "fp16"], default="fp32",
                     help="GEMM arithmetic of the towers: exact fp32 MFMA (default) or split-bf16 x3 (opt-in fast mode)")
     ap.add_argument("--trim-text", action="store_true",
@@ -112,9 +119,9 @@ def parse():
     ap.add_argument("--rccl-one-rank", action="store_true",
                     help="diagnostic at --gpus 1: an RCCL process group of ONE rank with the step's three collectives "
                          "issued anyway (their launch / stream cost on one card; no bytes cross xGMI)")
-    ap.add_argument("--no-extras", action="store_true", help="skip the forward_only / cfg5 legs after the timed region")
+    ap.add_argument("--no-extras", action="store_true", help="--full without the forward_only / cfg4 / cfg5 legs")
     ap.add_argument("--cfg5-budget-s", type=float, default=150.0,
-                    help="skip the cfg-5 leg when the run has already taken this many seconds")
+                    help="--full: skip the cfg-5 leg when the run has already taken this many seconds")
     ap.add_argument("--dump-outputs", metavar="DIR",
                     help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
@@ -387,7 +394,8 @@ def main():
         D.FORCE_COLLECTIVES = True
     lib = _lib.load()
     model, tr, cfg = build_trainer(dev, args)
-    top5 = golden_top5(model, tr, dev) if (args.model == "b32" and rank == 0) else None
+    # eval mode draws no dropout seed, so the timed steps see the same seeds with or without this check
+    top5 = golden_top5(model, tr, dev) if (args.full and args.model == "b32" and rank == 0) else None
     gb = args.batch * world if args.weak else args.batch
     lo, hi = D.shard_bounds(gb, rank, world)
     images = synth.synth_images(gb, 224, seed=0)[lo:hi].contiguous().to(dev)
@@ -412,12 +420,16 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
+    t_setup = time.time() - t_start
     for i in range(args.warmup):
         step()
         if rank == 0:
             torch.cuda.synchronize()
             print(f"[bench] warmup step {i} done", file=sys.stderr, flush=True)
     barrier()
+    if rank == 0:
+        print(f"[bench] set up in {t_setup:.1f} s, {args.warmup} warm-up steps in {time.time() - t_start - t_setup:.1f} s",
+              file=sys.stderr, flush=True)
     t0 = time.perf_counter()
     for _ in range(args.steps):
         step()
@@ -442,7 +454,7 @@ def main():
 
     # ---- collectives: three more steps with every collective bracketed by HIP events on its launch stream ----
     coll = None
-    if (world > 1 or args.rccl_one_rank) and not args.forward_only:
+    if args.full and (world > 1 or args.rccl_one_rank) and not args.forward_only:
         tr.time_collectives = True
         for _ in range(3):
             step()
@@ -458,7 +470,7 @@ def main():
 
     # ---- roofline leg: one more step with every GEMM launch bracketed by HIP events on its stream ----
     roof = None
-    if not args.no_roofline:
+    if args.full and not args.no_roofline:
         overlap = tr.overlap_towers
         tr.overlap_towers = False  # per-kernel durations are only meaningful when nothing else shares the GPU
         lib.clipfs_gemm_timing(1)
@@ -471,7 +483,7 @@ def main():
 
     # ---- opt-in modes next to the headline (same step, same inputs; never the headline `value`) ----
     variants = None
-    if world == 1 and not args.no_variants and not args.forward_only and args.model == "b32" and \
+    if args.full and world == 1 and not args.no_variants and not args.forward_only and args.model == "b32" and \
             args.precision == "fp32" and not args.trim_text:
         variants = {}
         # the same step with every block dense in both directions (the one-row-per-sequence gradient scattered into zeros)
@@ -508,7 +520,7 @@ def main():
 
     # ---- the north-star's own target: image-tower forward at bs 256 (>= 40 % of the MFMA roofline) ----
     fwd_only = None
-    extras = world == 1 and not args.no_extras and not args.forward_only and args.model == "b32" and \
+    extras = args.full and world == 1 and not args.no_extras and not args.forward_only and args.model == "b32" and \
         args.precision == "fp32" and not args.trim_text
     if extras:
         with torch.no_grad():
@@ -574,7 +586,7 @@ def main():
                        "global_batch": gb, "images_per_rank": n_img_local, "captions": args.classes,
                        "last_block": "dense (CLIPFS_DENSE_BWD=1)" if os.environ.get("CLIPFS_DENSE_BWD", "0") not in ("", "0")
                        else "after its attention, forward and backward on one row per sequence (the class / EOT row: the only "
-                            "row read, the only row with gradient; exact -- `variants.dense_last_block` is the all-rows step)",
+                            "row read, the only row with gradient; exact -- `variants.dense_last_block` of --full is the all-rows step)",
                        "lora_dropout": args.dropout, "tower_streams": 1 if args.serial_towers else 2, "text_positions": "trimmed-to-last-EOT" if args.trim_text else 77, "parallelism": f"dp{world}" + ("" if args.no_shard_text or world == 1 else "+class-sharded-text")},
             "algorithmic_tflop_per_step": round(step_tflop, 3),
             "step_tflops": round(step_tflop / (ms * 1e-3), 2),
@@ -599,7 +611,7 @@ def main():
             out["cfg5"] = cfg5
         if variants:
             out["variants"] = variants
-        if world == 1 and not args.no_cpu_baseline and not args.forward_only:
+        if args.full and world == 1 and not args.no_cpu_baseline and not args.forward_only:
             out["cpu_baseline"] = cpu_baseline()
         if knobs:
             out["env_overrides"] = knobs
