@@ -221,7 +221,10 @@ int clipfs_lora_keep_bits_ok(int width, int segw, int r, int nseg);
  *   dB[s*segw+n,j] += scale * sum_m dy[m, s*segw+n] * t[m, s*r+j]
  *   dA[s*r+j, k]  += sum_m dt[m, s*r+j] * drop_s(x)[m,k]
  *   dx[m,k]       += sum_{s,j} dt[m, s*r+j] * A[s*r+j,k] * dropscale_s(m,k)   (if dx != NULL)
- * work: caller scratch, >= clipfs_lora_bwd_work_floats(...) floats. */
+ * work: caller scratch, >= clipfs_lora_bwd_work_floats(...) floats.
+ * Frozen adapter: dA == dB == NULL computes dt and the dx contribution only -- no dB / dA partial products or slice
+ * reductions are launched, and dt / dx are bitwise those of the call with slots.  With dx NULL as well only dt is
+ * computed.  Exactly one of dA / dB NULL is CLIPFS_EINVAL.  The same holds for clipfs_lora_bwd_f16dy. */
 size_t clipfs_lora_bwd_work_floats(int rows, int width, int r, int nseg);
 int clipfs_lora_bwd(const float* dy, const float* x, const float* t, const float* A, const float* B,
                     float* dt, float* dA, float* dB, float* dx, int rows, int width, int segw, int r,
@@ -414,9 +417,15 @@ typedef struct clipfs_tower {
   int* gemm_counters;       /* optional: >= clipfs_tower_counter_ints(t, batch) ints, zeroed ONCE by the caller (every
                                GEMM leaves them zero) -- enables the stream-K GEMM schedule; one buffer per stream */
   size_t gemm_counters_ints;
+  int grad_lo;              /* gradient floor: the lowest block whose parameters train.  0 = every block (today's
+                               behaviour).  Blocks below it keep no activations in the forward (same kernels, same
+                               dropout masks, same block outputs) and get no backward; their gradient slots must be
+                               NULL.  0 <= grad_lo < layers; grad_lo > 0 needs stop_at_input != 0 in the backward
+                               (the gradient wrt the tower input runs through every block). */
 } clipfs_tower;
 
-/* floats needed per tower call for saved activations / scratch */
+/* floats needed per tower call for saved activations / scratch (saved: one record per block grad_lo ... layers-1;
+ * 0 for a descriptor the library rejects) */
 size_t clipfs_tower_saved_floats(const clipfs_tower* t, int batch);
 size_t clipfs_tower_scratch_floats(const clipfs_tower* t, int batch);
 size_t clipfs_tower_counter_ints(const clipfs_tower* t, int batch);

@@ -65,6 +65,7 @@ class Tower(C.Structure):
         ("dropout_seed", C.c_uint64), ("dropout_stream0", C.c_uint32), ("dropout_row0", C.c_uint32),
         ("blocks", C.POINTER(Block)), ("weight_format", C.c_int),
         ("gemm_counters", C.c_void_p), ("gemm_counters_ints", C.c_size_t),
+        ("grad_lo", C.c_int),  # 0 = every block (today's behaviour)
     ]
 
 

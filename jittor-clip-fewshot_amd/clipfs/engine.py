@@ -29,6 +29,26 @@ def _bias_slot(p: Optional[torch.nn.Parameter]) -> Optional[torch.Tensor]:
     return getattr(p, "grad_slot", None)
 
 
+def _lora_trains(a, where: str) -> bool:
+    """Whether the LoRA adapters of one attention block train (``requires_grad`` of their A / B).  All or nothing per
+    block: a block with some adapters frozen and others trainable is refused rather than training the frozen half."""
+    flags = {p.requires_grad for p, _ in a.trainable_pairs()}
+    if len(flags) > 1:
+        raise ValueError(f"{where}: some of its LoRA adapters are frozen and others trainable; freeze or train the "
+                         "q / k / v / o adapters of a block together")
+    return flags == {True}
+
+
+def _blk_biases(blk) -> List[torch.nn.Parameter]:
+    """The bias parameters of one block (LoRA blocks: the q / k / v views of the packed in-projection bias)."""
+    a = blk.attn
+    if getattr(a, "is_lora_mha", False):
+        out = [a.q_proj.bias, a.k_proj.bias, a.v_proj.bias, a.proj.bias]
+    else:
+        out = [a.in_proj_bias, a.out_proj.bias]
+    return out + [blk.ln_1.bias, blk.ln_2.bias, blk.mlp.c_fc.bias, blk.mlp.c_proj.bias]
+
+
 def _mix_seed(base: int, step: int) -> int:
     """64-bit non-zero dropout seed for (base, step) -- splitmix64 finaliser."""
     z = (base * 0x9E3779B97F4A7C15 + step * 0xBF58476D1CE4E5B9 + 0x94D049BB133111EB) & 0xFFFFFFFFFFFFFFFF
@@ -43,8 +63,9 @@ def _mix_seed(base: int, step: int) -> int:
 class _TowerRT:
     """One transformer tower: pointer collection + workspace cache."""
 
-    def __init__(self, transformer, seq: int, stream0: int):
+    def __init__(self, transformer, seq: int, stream0: int, name: str = "tower"):
         self.mod = transformer
+        self.name = name
         self.seq = seq
         self.width = transformer.width
         self.heads = transformer.heads
@@ -79,7 +100,26 @@ class _TowerRT:
             self._planes[key] = pl
         return pl
 
-    def descriptor(self, train: bool, seed: int, seq: Optional[int] = None, row0: int = 0) -> Tower:
+    def _block_trains(self, i: int, blk) -> bool:
+        """Whether block i gets any gradient slot in ``descriptor`` (a trainable adapter or bias)."""
+        a = blk.attn
+        if getattr(a, "is_lora_mha", False) and a.r > 0 and _lora_trains(a, f"{self.name} block {i}"):
+            return True
+        return any(_bias_slot(p) is not None for p in _blk_biases(blk))
+
+    def grad_floor(self, needs_input_grad: bool, head_trains: bool = False) -> Optional[int]:
+        """The tower's gradient floor (clipfs_tower.grad_lo): the lowest block with a gradient slot; 0 when the tower
+        input needs a gradient (prompt ctx, VPT, ln_pre's bias: that gradient runs through every block); None when
+        nothing in the tower or its head trains (no backward at all).  A head-only layout (ln_post / ln_final bias
+        trained, every block frozen) keeps the top block: the head's input is that block's output."""
+        if needs_input_grad:
+            return 0
+        for i, blk in enumerate(self.mod.resblocks):
+            if self._block_trains(i, blk):
+                return i
+        return self.layers - 1 if head_trains else None
+
+    def descriptor(self, train: bool, seed: int, seq: Optional[int] = None, row0: int = 0, grad_lo: int = 0) -> Tower:
         blocks = (Block * self.layers)()
         r, scale, p = 0, 0.0, 0.0
         for i, blk in enumerate(self.mod.resblocks):
@@ -127,11 +167,16 @@ class _TowerRT:
                     raise ValueError("all LoRA layers of one tower must share r / alpha / dropout")
                 r, scale, p = a.r, float(a.scaling), float(a.dropout_rate)
                 b.lora_mask = a.lora_mask
+                # gradient slots only for trainable adapters: NULL slots = frozen, the tower computes the adapter's
+                # input-gradient contribution only and AdamW never sees it
+                trains = _lora_trains(a, f"{self.name} block {i}")
                 b.lora_a_qkv, b.lora_b_qkv = _ptr(a.lora_A_qkv), _ptr(a.lora_B_qkv)
-                b.g_lora_a_qkv, b.g_lora_b_qkv = _ptr(a.grad_A_qkv), _ptr(a.grad_B_qkv)
+                if trains:
+                    b.g_lora_a_qkv, b.g_lora_b_qkv = _ptr(a.grad_A_qkv), _ptr(a.grad_B_qkv)
                 if a.lora_mask & 8:
                     b.lora_a_o, b.lora_b_o = _ptr(a.lora_A_o), _ptr(a.lora_B_o)
-                    b.g_lora_a_o, b.g_lora_b_o = _ptr(a.grad_A_o), _ptr(a.grad_B_o)
+                    if trains:
+                        b.g_lora_a_o, b.g_lora_b_o = _ptr(a.grad_A_o), _ptr(a.grad_B_o)
         t = _lib.new_tower()
         t.width, t.heads, t.layers, t.seq, t.causal = (self.width, self.heads, self.layers, seq or self.seq,
                                                        int(self.causal))
@@ -142,6 +187,7 @@ class _TowerRT:
         t.dropout_stream0 = self.stream0
         t.dropout_row0 = row0 * (seq or self.seq)  # first TOKEN row of this call in the global batch
         t.weight_format = {"fp32": 0, "bf16x3": 1, "fp16": 2}[self.precision]
+        t.grad_lo = grad_lo
         t.blocks = C.cast(blocks, C.POINTER(Block))
         t._blocks_keepalive = blocks  # ctypes array must outlive the call
         self.lora_r, self.lora_scale, self.lora_dropout = r, scale, p
@@ -179,13 +225,14 @@ class _TowerRT:
         t.gemm_counters, t.gemm_counters_ints = buf.data_ptr(), buf.numel()
 
     def forward(self, x: torch.Tensor, batch: int, train: bool, seed: int, seq: Optional[int] = None,
-                own_saved: bool = False, row0: int = 0, rows: Optional[torch.Tensor] = None):
+                own_saved: bool = False, row0: int = 0, rows: Optional[torch.Tensor] = None, grad_lo: int = 0):
         """``train`` = keep the activations the backward needs.  ``own_saved``: give this call its OWN saved-activation
         tensor (the autograd route: several grad-enabled forwards of one tower may precede one backward, e.g. the 13
         caption chunks of encode_text_in_batches, lora_train_vlp.py:905-912); otherwise the per-tower cached buffer
-        is reused (LoRATrainer: exactly one forward per backward)."""
+        is reused (LoRATrainer: exactly one forward per backward).  ``grad_lo``: the gradient floor (``grad_floor``);
+        only blocks grad_lo ... top keep activations, and the backward must be given the same floor."""
         lib = _lib.load()
-        t = self.descriptor(train, seed, seq, row0)
+        t = self.descriptor(train, seed, seq, row0, grad_lo if train else 0)
         self._attach_counters(t, batch, x.device)
         scratch = self.buffer("scratch", lib.clipfs_tower_scratch_floats(C.byref(t), batch), x.device)
         saved = None
@@ -205,9 +252,9 @@ class _TowerRT:
         return saved
 
     def backward(self, dx: torch.Tensor, batch: int, saved: torch.Tensor, seed: int, stop_at_input: bool,
-                 seq: Optional[int] = None, row0: int = 0):
+                 seq: Optional[int] = None, row0: int = 0, grad_lo: int = 0):
         lib = _lib.load()
-        t = self.descriptor(True, seed, seq, row0)
+        t = self.descriptor(True, seed, seq, row0, grad_lo)
         self._attach_counters(t, batch, dx.device)
         scratch = self.buffer("scratch", lib.clipfs_tower_scratch_floats(C.byref(t), batch), dx.device)
         check(lib.clipfs_tower_bwd(C.byref(t), dx.data_ptr(), batch, saved.data_ptr(), scratch.data_ptr(),
@@ -215,12 +262,12 @@ class _TowerRT:
 
 
     def backward_sparse(self, dxs: torch.Tensor, rows: torch.Tensor, batch: int, saved: torch.Tensor, seed: int,
-                        stop_at_input: bool, seq: Optional[int] = None, row0: int = 0) -> torch.Tensor:
+                        stop_at_input: bool, seq: Optional[int] = None, row0: int = 0, grad_lo: int = 0) -> torch.Tensor:
         """Backward from a gradient that is non-zero in ONE row per sequence (``dxs`` [batch, width] at token ``rows``
         [batch] int32): the class token of the image head, the EOT token of the text head.  Returns the dense gradient
         wrt the tower input (uninitialised when ``stop_at_input``)."""
         lib = _lib.load()
-        t = self.descriptor(True, seed, seq, row0)
+        t = self.descriptor(True, seed, seq, row0, grad_lo)
         self._attach_counters(t, batch, dxs.device)
         scratch = self.buffer("scratch", lib.clipfs_tower_scratch_floats(C.byref(t), batch), dxs.device)
         dx = torch.empty(batch * (seq or self.seq), self.width, device=dxs.device, dtype=torch.float32)
@@ -234,8 +281,8 @@ class Engine:
     def __init__(self, model):
         self.model = model
         v = model.visual
-        self.vis = _TowerRT(v.transformer, v.tokens, stream0=1000)
-        self.txt = _TowerRT(model.transformer, model.context_length, stream0=0)
+        self.vis = _TowerRT(v.transformer, v.tokens, stream0=1000, name="vision")
+        self.txt = _TowerRT(model.transformer, model.context_length, stream0=0, name="text")
         self.vproj_t = v.proj.data.t().contiguous()                  # [E, width]  (NT form of x @ proj)
         self.tproj_t = model.text_projection.data.t().contiguous()   # [E, width]
         self.seed_base = 0x5EED
@@ -253,6 +300,11 @@ class Engine:
         # gradient rows scattered into a zero-filled tensor (identical features and gradients; kept as the A/B
         # reference, bench.py reports it as a variant).  The name predates the forward half.
         self.sparse_backward = True
+        # Gradient floor per tower (_TowerRT.grad_floor): blocks below the lowest one that trains keep no activations and
+        # get no backward, and a tower with nothing to train gets no backward at all (LoRATrainer).  Features and
+        # gradients are bitwise those of the full-depth path.  False = every tower saves and back-propagates every block
+        # (the A/B reference; frozen adapters are still never trained).
+        self.prune_backward = True
 
     @property
     def precision(self) -> str:
@@ -270,6 +322,21 @@ class Engine:
         self.vis.precision = mode
         self.txt.precision = mode
 
+    # -- backward plan --------------------------------------------------------------------------------
+    def image_plan(self) -> Optional[int]:
+        """Gradient floor of the image tower (None: nothing of it trains).  0 with a VPT or a trainable ln_pre bias."""
+        if not self.prune_backward:
+            return 0
+        v = self.model.visual
+        return self.vis.grad_floor(v.VPT is not None or _bias_slot(v.ln_pre.bias) is not None,
+                                   _bias_slot(v.ln_post.bias) is not None)
+
+    def text_plan(self, has_ctx: bool) -> Optional[int]:
+        """Gradient floor of the text tower (None: nothing of it trains).  0 with prompt ctx tokens."""
+        if not self.prune_backward:
+            return 0
+        return self.txt.grad_floor(has_ctx, _bias_slot(self.model.ln_final.bias) is not None)
+
     # -- seeds ------------------------------------------------------------------------------------
     def next_seed(self) -> int:
         self.step += 1
@@ -277,7 +344,12 @@ class Engine:
 
     # -- image tower --------------------------------------------------------------------------------
     def vit_forward(self, images: torch.Tensor, train: bool, seed: int = 0, own_saved: bool = False, row0: int = 0):
-        """``row0``: index of images[0] in the GLOBAL batch (data-parallel shard) -- only the dropout masks see it."""
+        """``row0``: index of images[0] in the GLOBAL batch (data-parallel shard) -- only the dropout masks see it.
+        ``train``: keep what the backward needs; with nothing of the image side to train (``image_plan`` None) the pass
+        is the no-grad one and the returned ctx is None."""
+        lo = self.image_plan() if train else 0
+        if lo is None:
+            train = False
         m = self.model
         v = m.visual
         assert images.is_cuda and images.dtype == torch.float32, "images: fp32 device tensor [B,3,R,R]"
@@ -300,7 +372,7 @@ class Engine:
         # only the class-token row of each image is read below (jclip/model.py:121-124)
         one_row = bool(self.sparse_backward)
         saved = self.vis.forward(x, B, train, seed, own_saved=own_saved, row0=row0,
-                                 rows=self._class_rows(B, images.device) if one_row else None)
+                                 rows=self._class_rows(B, images.device) if one_row else None, grad_lo=lo)
         if train:
             y, mean1, rstd1 = ops.layernorm_fwd(x, v.ln_post.weight.data, v.ln_post.bias.data, ldx=L * d, rows=B,
                                                 save_stats=True)
@@ -311,7 +383,7 @@ class Engine:
         ctx = None
         if train:
             ctx = dict(B=B, x_final=x, saved=saved, stats=(mean1, rstd1), seed=seed, row0=row0, one_row=one_row,
-                       pre=(x0, mean0, rstd0) if need_pre else None)
+                       pre=(x0, mean0, rstd0) if need_pre else None, lo=lo)
         return feat, ctx
 
     def vit_backward(self, ctx: dict, dfeat: torch.Tensor) -> None:
@@ -332,10 +404,10 @@ class Engine:
         stop = not (has_vpt or g_pre is not None)
         if ctx["one_row"]:  # the forward that produced ``saved`` decides (its last block kept one row per image)
             dx = self.vis.backward_sparse(dcls, self._class_rows(B, dfeat.device), B, ctx["saved"], ctx["seed"],
-                                          stop_at_input=stop, row0=ctx["row0"])
+                                          stop_at_input=stop, row0=ctx["row0"], grad_lo=ctx["lo"])
         else:
             dx = ops.scatter_rows(dcls, self._class_rows(B, dfeat.device), L)
-            self.vis.backward(dx, B, ctx["saved"], ctx["seed"], stop_at_input=stop, row0=ctx["row0"])
+            self.vis.backward(dx, B, ctx["saved"], ctx["seed"], stop_at_input=stop, row0=ctx["row0"], grad_lo=ctx["lo"])
         if g_pre is not None:
             ops.bias_grad(dx, g_pre)
         if has_vpt:
@@ -366,6 +438,11 @@ class Engine:
 
     def text_forward(self, ids: torch.Tensor, prompt_ctx: Optional[torch.Tensor], train: bool, seed: int = 0,
                      own_saved: bool = False, row0: int = 0):
+        """As ``vit_forward``: with nothing of the text side to train (``text_plan`` None) the pass is the no-grad one
+        and the returned ctx is None."""
+        lo = self.text_plan(prompt_ctx is not None) if train else 0
+        if lo is None:
+            train = False
         m = self.model
         ids = ids.to(device=m.device, dtype=torch.int64).contiguous()
         n, seq = ids.shape
@@ -377,7 +454,7 @@ class Engine:
         # only the EOT row of each caption is read below (jclip/model.py:213-214)
         one_row = bool(self.sparse_backward)
         saved = self.txt.forward(x, n, train, seed, seq, own_saved=own_saved, row0=row0,
-                                 rows=ops.eot_index(ids) if one_row else None)
+                                 rows=ops.eot_index(ids) if one_row else None, grad_lo=lo)
         rows, idx = ops.gather_eot(x, ids)
         if train:
             y, mean, rstd = ops.layernorm_fwd(rows, m.ln_final.weight.data, m.ln_final.bias.data, save_stats=True)
@@ -388,7 +465,7 @@ class Engine:
         ctx = None
         if train:
             ctx = dict(n=n, seq=seq, rows=rows, idx=idx, stats=(mean, rstd), saved=saved, seed=seed, row0=row0,
-                       one_row=one_row, has_ctx=prompt_ctx is not None)
+                       one_row=one_row, has_ctx=prompt_ctx is not None, lo=lo)
         return feat, ctx
 
     def text_backward(self, ctx: dict, dfeat: torch.Tensor, dctx_slot: Optional[torch.Tensor] = None) -> None:
@@ -403,10 +480,11 @@ class Engine:
         # only the EOT row of each caption carries gradient (jclip/model.py:213-214)
         if ctx["one_row"]:
             dx = self.txt.backward_sparse(drows, ctx["idx"], n, ctx["saved"], ctx["seed"], stop_at_input=not ctx["has_ctx"],
-                                          seq=seq, row0=ctx["row0"])
+                                          seq=seq, row0=ctx["row0"], grad_lo=ctx["lo"])
         else:
             dx = ops.scatter_rows(drows, ctx["idx"], seq)
-            self.txt.backward(dx, n, ctx["saved"], ctx["seed"], stop_at_input=not ctx["has_ctx"], seq=seq, row0=ctx["row0"])
+            self.txt.backward(dx, n, ctx["saved"], ctx["seed"], stop_at_input=not ctx["has_ctx"], seq=seq, row0=ctx["row0"],
+                              grad_lo=ctx["lo"])
         if ctx["has_ctx"]:
             assert dctx_slot is not None
             ops.token_rows_grad(dx, dctx_slot, n, seq, 1)
@@ -428,15 +506,7 @@ def _tower_trainables(tower_mod) -> List[Tuple[torch.nn.Parameter, torch.Tensor]
 
 def _block_biases(tower_mod) -> List[torch.nn.Parameter]:
     """Every bias parameter of a tower's blocks (LoRA blocks: the q / k / v views of the packed in-projection bias)."""
-    out = []
-    for blk in tower_mod.resblocks:
-        a = blk.attn
-        if getattr(a, "is_lora_mha", False):
-            out += [a.q_proj.bias, a.k_proj.bias, a.v_proj.bias, a.proj.bias]
-        else:
-            out += [a.in_proj_bias, a.out_proj.bias]
-        out += [blk.ln_1.bias, blk.ln_2.bias, blk.mlp.c_fc.bias, blk.mlp.c_proj.bias]
-    return out
+    return [p for blk in tower_mod.resblocks for p in _blk_biases(blk)]
 
 
 def image_biases(model) -> List[torch.nn.Parameter]:

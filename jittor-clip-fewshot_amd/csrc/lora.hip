@@ -344,36 +344,31 @@ static int lora_bwd_r(const float* dy, const float* x, const float* t, const flo
   hipLaunchKernelGGL((lora_dt_kernel<R>), dim3((rows + 3) / 4), dim3(256), 0, st, dy, B, dt, rows, segw, nseg, seg_mask,
                      scale);
   CLIPFS_CHECK(launch_status());
-  // dB
-  float* part_b = work;
-  hipLaunchKernelGGL((lora_db_partial_kernel<R>), dim3((cols + 255) / 256, slices), dim3(256), 0, st, dy, t, part_b,
-                     rows, cols, segw, nseg, sr);
-  CLIPFS_CHECK(launch_status());
-  const size_t nb = (size_t)cols * R;
-  hipLaunchKernelGGL(reduce_slices_kernel, dim3((unsigned)((nb + 63) / 64)), dim3(1024), 0, st, part_b, dB, nb, slices,
-                     scale);
-  CLIPFS_CHECK(launch_status());
-  // dA
-  float* part_a = work + (size_t)slices * nb;
-  const dim3 ga((width / 4 + 63) / 64, slices);
-  switch (nseg) {
-    case 1:
+  if (dA) {  // dA == dB == NULL: frozen adapter, dt and dx only
+    // dB
+    float* part_b = work;
+    hipLaunchKernelGGL((lora_db_partial_kernel<R>), dim3((cols + 255) / 256, slices), dim3(256), 0, st, dy, t, part_b,
+                       rows, cols, segw, nseg, sr);
+    CLIPFS_CHECK(launch_status());
+    const size_t nb = (size_t)cols * R;
+    hipLaunchKernelGGL(reduce_slices_kernel, dim3((unsigned)((nb + 63) / 64)), dim3(1024), 0, st, part_b, dB, nb, slices,
+                       scale);
+    CLIPFS_CHECK(launch_status());
+    // dA
+    float* part_a = work + (size_t)slices * nb;
+    const dim3 ga((width / 4 + 63) / 64, slices);
+    if (nseg == 1)
       hipLaunchKernelGGL((lora_da_partial_kernel<R, 1>), ga, dim3(64), 0, st, x, dt, part_a, rows, width, seg_mask, p,
                          seed, stream_base, drow0, sr);
-      break;
-    case 3:
+    else
       hipLaunchKernelGGL((lora_da_partial_kernel<R, 3>), ga, dim3(64), 0, st, x, dt, part_a, rows, width, seg_mask, p,
                          seed, stream_base, drow0, sr);
-      break;
-    default:
-      set_error("lora_bwd: nseg %d unsupported (1 or 3)", nseg);
-      return CLIPFS_EINVAL;
+    CLIPFS_CHECK(launch_status());
+    const size_t na = (size_t)nseg * R * width;
+    hipLaunchKernelGGL(reduce_slices_kernel, dim3((unsigned)((na + 63) / 64)), dim3(1024), 0, st, part_a, dA, na, slices,
+                       1.0f);
+    CLIPFS_CHECK(launch_status());
   }
-  CLIPFS_CHECK(launch_status());
-  const size_t na = (size_t)nseg * R * width;
-  hipLaunchKernelGGL(reduce_slices_kernel, dim3((unsigned)((na + 63) / 64)), dim3(1024), 0, st, part_a, dA, na, slices,
-                     1.0f);
-  CLIPFS_CHECK(launch_status());
   if (dx) {
     hipLaunchKernelGGL(lora_dx_kernel, dim3((rows + 3) / 4), dim3(256), 0, st, dt, A, dx, rows, width, R, nseg, seg_mask,
                        p, seed, stream_base, drow0);
@@ -386,7 +381,9 @@ extern "C" int clipfs_lora_bwd(const float* dy, const float* x, const float* t, 
                                float* dt, float* dA, float* dB, float* dx, int rows, int width, int segw, int r,
                                int nseg, unsigned seg_mask, float scale, float p, uint64_t seed, uint32_t stream_base, uint32_t drow0,
                                const void* keep_bits, float* work, void* stream) {
-  CLIPFS_REQUIRE(dy && x && t && A && B && dt && dA && dB && work, "lora_bwd: null pointer");
+  CLIPFS_REQUIRE((dA == nullptr) == (dB == nullptr), "lora_bwd: dA and dB must both be given or both NULL (frozen adapter)");
+  CLIPFS_REQUIRE(dy && x && t && A && B && dt && work, "lora_bwd: null pointer");
+  CLIPFS_REQUIRE(nseg == 1 || nseg == 3, "lora_bwd: nseg %d unsupported (1 or 3)", nseg);
   CLIPFS_REQUIRE(!keep_bits || (clipfs_lora_keep_bits_ok(width, segw, r, nseg) && aligned16(dy) && aligned16(dx ? dx : x)),
                  "lora_bwd: keep bits are read by the matrix-core kernels only (width %d r %d nseg %d)", width, r, nseg);
   CLIPFS_REQUIRE(rows > 0 && width > 0 && (width & 3) == 0 && segw == width, "lora_bwd: width %d segw %d unsupported (segw must equal width)", width, segw);
@@ -424,7 +421,9 @@ extern "C" int clipfs_lora_bwd_f16dy(const void* dy16, const float* x, const flo
                                      float* dt, float* dA, float* dB, float* dx, int rows, int width, int segw, int r,
                                      int nseg, unsigned seg_mask, float scale, float p, uint64_t seed, uint32_t stream_base,
                                      uint32_t drow0, const void* keep_bits, float* work, void* stream) {
-  CLIPFS_REQUIRE(dy16 && x && t && A && B && dt && dA && dB && work, "lora_bwd_f16dy: null pointer");
+  CLIPFS_REQUIRE((dA == nullptr) == (dB == nullptr),
+                 "lora_bwd_f16dy: dA and dB must both be given or both NULL (frozen adapter)");
+  CLIPFS_REQUIRE(dy16 && x && t && A && B && dt && work, "lora_bwd_f16dy: null pointer");
   CLIPFS_REQUIRE(rows > 0 && clipfs_lora_bwd_f16dy_ok(width, segw, r, nseg),
                  "lora_bwd_f16dy: width %d segw %d r %d nseg %d is outside the matrix-core kernels", width, segw, r, nseg);
   CLIPFS_REQUIRE(p >= 0.f && p < 1.f, "lora_bwd_f16dy: dropout p out of range");

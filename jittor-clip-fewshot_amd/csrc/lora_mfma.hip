@@ -433,6 +433,7 @@ static void launch_da_dx(const float* x, const float* dt, const float* A, float*
                          const uint16_t* keep_bits, hipStream_t st) {
   const int gx_a = (width + 255) / 256, n_da = gx_a * slices_a;
   const int n_dx = dx ? (rows + 15) / 16 : 0;
+  if (n_da + n_dx == 0) return;
   hipLaunchKernelGGL((lora_da_dx_mfma_kernel<NSEG, RQ>), dim3(n_da + n_dx), dim3(256), 0, st, x, dt, A, part_a, dx, rows, width,
                      r, seg_mask, p, seed, stream_base, drow0, sr_a, gx_a, n_da, keep_bits);
 }
@@ -446,8 +447,10 @@ static int lora_bwd_mfma_n(const TY* dy, const float* x, const float* t, const f
                            float scale, float p, uint64_t seed, uint32_t stream_base, uint32_t drow0, const uint16_t* keep_bits,
                            float* work, hipStream_t st, lora_reduce2_fn reduce2) {
   const int cols = NSEG * segw;
-  const int sr_b = lora_mfma_slice_rows(rows, cols / 64), slices_b = (rows + sr_b - 1) / sr_b;
-  const int sr_a = lora_mfma_slice_rows(rows, width / 64), slices_a = (rows + sr_a - 1) / sr_a;
+  // dA == dB == NULL: frozen adapter -- no dB / dA workgroups, no slice sums (dt and dx come out bitwise the same)
+  const bool grads = dA != nullptr;
+  const int sr_b = lora_mfma_slice_rows(rows, cols / 64), slices_b = grads ? (rows + sr_b - 1) / sr_b : 0;
+  const int sr_a = lora_mfma_slice_rows(rows, width / 64), slices_a = grads ? (rows + sr_a - 1) / sr_a : 0;
   const int n_rows16 = (rows + 15) / 16;
   const size_t nb = (size_t)cols * r, na = (size_t)NSEG * r * width;
   float* part_b = work;
@@ -474,7 +477,7 @@ static int lora_bwd_mfma_n(const TY* dy, const float* x, const float* t, const f
   }
   CLIPFS_CHECK(launch_status());
   // 3: both slice sums
-  reduce2(part_b, dB, nb, slices_b, scale, part_a, dA, na, slices_a, 1.0f, st);
+  if (grads) reduce2(part_b, dB, nb, slices_b, scale, part_a, dA, na, slices_a, 1.0f, st);
   return launch_status();
 }
 

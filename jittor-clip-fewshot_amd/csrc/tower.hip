@@ -126,6 +126,14 @@ static int check_tower(const clipfs_tower* t, int batch) {
   CLIPFS_REQUIRE(batch > 0 && t->layers > 0 && t->seq > 0 && t->heads > 0 && t->width == t->heads * 64,
                  "tower: width %d must be heads %d * 64", t->width, t->heads);
   CLIPFS_REQUIRE(t->lora_r >= 0 && t->lora_r <= 16, "tower: lora rank %d unsupported", t->lora_r);
+  CLIPFS_REQUIRE(t->grad_lo >= 0 && t->grad_lo < t->layers, "tower: grad_lo %d outside [0, layers %d)", t->grad_lo,
+                 t->layers);
+  // blocks below the floor get no backward: a gradient slot there would silently stay untouched
+  for (int l = 0; l < t->grad_lo; ++l) {
+    const clipfs_block& b = t->blocks[l];
+    CLIPFS_REQUIRE(!b.g_lora_a_qkv && !b.g_lora_b_qkv && !b.g_lora_a_o && !b.g_lora_b_o && !block_has_bias_slots(b),
+                   "tower: block %d below grad_lo %d has gradient slots", l, t->grad_lo);
+  }
   if (t->weight_format == 2)  // fp16 storage mode chains f16 results between GEMMs: every block needs all its f16 weights
     for (int l = 0; l < t->layers; ++l) {
       const clipfs_block& b = t->blocks[l];
@@ -219,7 +227,8 @@ using namespace clipfs;
 
 extern "C" size_t clipfs_tower_saved_floats(const clipfs_tower* t, int batch) {
   if (!t || batch <= 0 || t->struct_size != sizeof(clipfs_tower)) return 0;
-  return saved_layout(t, (size_t)batch * t->seq).total * (size_t)t->layers;
+  if (t->grad_lo < 0 || t->grad_lo >= t->layers) return 0;
+  return saved_layout(t, (size_t)batch * t->seq).total * (size_t)(t->layers - t->grad_lo);  // blocks grad_lo ... top
 }
 
 extern "C" size_t clipfs_tower_scratch_floats(const clipfs_tower* t, int batch) {
@@ -258,21 +267,28 @@ static int tower_fwd_impl(const clipfs_tower* t, float* x, const int32_t* rows, 
   // dropout follows the caller's train MODE (is_training(), lora_train_vlp.py:297-298), carried by a non-zero seed;
   // `saved` only decides whether activations are kept (a no-grad forward in train mode still drops)
   const uint64_t seed = t->dropout_seed;
-  if (train) {
-    hipError_t e = hipMemcpyAsync(saved + SL.x_in, x, (size_t)M * d * sizeof(float), hipMemcpyDeviceToDevice, st);
-    CLIPFS_REQUIRE(e == hipSuccess, "tower_fwd: memcpy failed: %s", hipGetErrorString(e));
-  }
+  // gradient floor: blocks below it run the no-save path (nothing of theirs is back-propagated); saved record l - lo
+  const int lo = t->grad_lo;
   for (int l = 0; l < t->layers; ++l) {
     const clipfs_block& b = t->blocks[l];
-    float* sv = train ? saved + (size_t)l * SL.total : nullptr;
-    const float* x_in = train ? sv + SL.x_in : x;
-    float* h1 = train ? sv + SL.h1 : scratch + SC.h;
-    float* qkv = train ? sv + SL.qkv : scratch + SC.b3;
-    float* att = train ? sv + SL.att : scratch + SC.b1;
-    float* x_mid = train ? sv + SL.x_mid : x;
-    float* t_qkv = train ? sv + SL.t_qkv : scratch + SC.dt;
-    float* t_o = train ? sv + SL.t_o : scratch + SC.dt + al4((size_t)M * 3 * r);
-    float* x_next = train ? (l + 1 < t->layers ? saved + (size_t)(l + 1) * SL.total + SL.x_in : x) : x;
+    const bool keep_l = train && l >= lo;  // this block's activations are kept for the backward
+    if (train && l == lo) {
+      hipError_t e = hipMemcpyAsync(saved + SL.x_in, x, (size_t)M * d * sizeof(float), hipMemcpyDeviceToDevice, st);
+      CLIPFS_REQUIRE(e == hipSuccess, "tower_fwd: memcpy failed: %s", hipGetErrorString(e));
+    }
+    float* sv = keep_l ? saved + (size_t)(l - lo) * SL.total : nullptr;
+    const float* x_in = keep_l ? sv + SL.x_in : x;
+    float* h1 = keep_l ? sv + SL.h1 : scratch + SC.h;
+    float* qkv = keep_l ? sv + SL.qkv : scratch + SC.b3;
+    float* att = keep_l ? sv + SL.att : scratch + SC.b1;
+    float* x_mid = keep_l ? sv + SL.x_mid : x;
+    float* t_qkv = keep_l ? sv + SL.t_qkv : scratch + SC.dt;
+    float* t_o = keep_l ? sv + SL.t_o : scratch + SC.dt + al4((size_t)M * 3 * r);
+    float* x_next = keep_l ? (l + 1 < t->layers ? saved + (size_t)(l + 1 - lo) * SL.total + SL.x_in : x) : x;
+    // attention statistics: kept (saved record), or -- below the floor of a saving forward -- written to the MLP scratch
+    // (dead until the c_fc GEMM): the attention kernels are picked by whether lse is requested, and a block below the floor
+    // must produce bitwise the block output of the saving forward
+    float* lse = keep_l ? sv + SL.lse : (train ? scratch + SC.big : nullptr);
     const unsigned qkv_mask = b.lora_a_qkv ? (b.lora_mask & 7u) : 0u;
     const bool lora_o = b.lora_a_o && (b.lora_mask & 8u);
     const uint32_t ds = t->dropout_stream0 + 4u * (uint32_t)l;
@@ -281,19 +297,19 @@ static int tower_fwd_impl(const clipfs_tower* t, float* x, const int32_t* rows, 
     void* h16 = cx.a16;                                                        // [M, d] halves: ln1 / attention / ln2 / dx
     void* dqkv16 = cx.a16 ? (void*)((char*)cx.a16 + (size_t)M * d * 2) : nullptr;  // [M, 3d] halves
     (void)dqkv16;
-    void* keep = (train && qkv_mask && keep_bits_saved(t)) ? (void*)(sv + SL.keep) : nullptr;
+    void* keep = (keep_l && qkv_mask && keep_bits_saved(t)) ? (void*)(sv + SL.keep) : nullptr;
     if (qkv_mask && clipfs_layernorm_fwd_lora_ok(d, r, 3)) {
       // small ranks: the adapter's down-projection rides on the LayerNorm pass (the row is in registers there)
-      CLIPFS_CHECK(clipfs_layernorm_fwd_lora(x_in, d, b.ln1_g, b.ln1_b, h1, h16, train ? sv + SL.stat1 : nullptr,
-                                             train ? sv + SL.stat1 + M : nullptr, M, d, 1e-5f, b.lora_a_qkv, t_qkv, r, 3, qkv_mask,
+      CLIPFS_CHECK(clipfs_layernorm_fwd_lora(x_in, d, b.ln1_g, b.ln1_b, h1, h16, keep_l ? sv + SL.stat1 : nullptr,
+                                             keep_l ? sv + SL.stat1 + M : nullptr, M, d, 1e-5f, b.lora_a_qkv, t_qkv, r, 3, qkv_mask,
                                              t->lora_dropout, seed, ds, t->dropout_row0, keep, st));
     } else {
       if (h16)
-        CLIPFS_CHECK(clipfs_layernorm_fwd_f16(x_in, d, b.ln1_g, b.ln1_b, h1, h16, train ? sv + SL.stat1 : nullptr,
-                                              train ? sv + SL.stat1 + M : nullptr, M, d, 1e-5f, st));
+        CLIPFS_CHECK(clipfs_layernorm_fwd_f16(x_in, d, b.ln1_g, b.ln1_b, h1, h16, keep_l ? sv + SL.stat1 : nullptr,
+                                              keep_l ? sv + SL.stat1 + M : nullptr, M, d, 1e-5f, st));
       else
-        CLIPFS_CHECK(clipfs_layernorm_fwd(x_in, d, b.ln1_g, b.ln1_b, h1, train ? sv + SL.stat1 : nullptr,
-                                          train ? sv + SL.stat1 + M : nullptr, M, d, 1e-5f, st));
+        CLIPFS_CHECK(clipfs_layernorm_fwd(x_in, d, b.ln1_g, b.ln1_b, h1, keep_l ? sv + SL.stat1 : nullptr,
+                                          keep_l ? sv + SL.stat1 + M : nullptr, M, d, 1e-5f, st));
       if (qkv_mask)
         CLIPFS_CHECK(clipfs_lora_down(h1, b.lora_a_qkv, t_qkv, M, d, r, 3, qkv_mask, t->lora_dropout, seed, ds, t->dropout_row0,
                                       keep, st));
@@ -303,11 +319,10 @@ static int tower_fwd_impl(const clipfs_tower* t, float* x, const int32_t* rows, 
                       b.lora_b_qkv, r, 3, d, t->lora_scale, st, CHAIN_NONE, h16, q16 ? (void*)qkv : nullptr));
     const void* att16 = nullptr;
     if (f16_attention(t)) {
-      CLIPFS_CHECK(clipfs_attention_f16_fwd(qkv, q16, att, h16, train ? sv + SL.lse : nullptr, batch, t->seq, t->heads,
-                                            t->causal, st));
+      CLIPFS_CHECK(clipfs_attention_f16_fwd(qkv, q16, att, h16, lse, batch, t->seq, t->heads, t->causal, st));
       att16 = h16;
     } else
-      CLIPFS_CHECK(clipfs_attention_fwd(qkv, att, train ? sv + SL.lse : nullptr, batch, t->seq, t->heads, t->causal, st));
+      CLIPFS_CHECK(clipfs_attention_fwd(qkv, att, lse, batch, t->seq, t->heads, t->causal, st));
     if (rows && l == t->layers - 1) {
       // ---- the rest of the LAST block on one row per sequence: the head reads nothing else (jclip/model.py:121-124,
       // :213-214) and every remaining operation is row-wise.  Compact buffers live in the MLP scratch (Ms (13 d + 2)
@@ -330,14 +345,14 @@ static int tower_fwd_impl(const clipfs_tower* t, float* x, const int32_t* rows, 
       const bool f16m = t->weight_format == 2;
       CLIPFS_CHECK(gemm(cx, att_s, b.w_o, f16m ? nullptr : b.w_o_p, xmid_s, Ms, d, d, b.b_o, xin_s, 0, nullptr, nullptr, nullptr, nullptr,
                         0, 0, 0, 0.f, st));
-      CLIPFS_CHECK(clipfs_layernorm_fwd(xmid_s, d, b.ln2_g, b.ln2_b, h2_s, train ? mean_s : nullptr, train ? rstd_s : nullptr, Ms,
+      CLIPFS_CHECK(clipfs_layernorm_fwd(xmid_s, d, b.ln2_g, b.ln2_b, h2_s, keep_l ? mean_s : nullptr, keep_l ? rstd_s : nullptr, Ms,
                                         d, 1e-5f, st));
-      CLIPFS_CHECK(gemm(cx, h2_s, b.w_fc, f16m ? nullptr : b.w_fc_p, g_s, Ms, 4 * d, d, b.b_fc, nullptr, 1, train ? u_s : nullptr,
+      CLIPFS_CHECK(gemm(cx, h2_s, b.w_fc, f16m ? nullptr : b.w_fc_p, g_s, Ms, 4 * d, d, b.b_fc, nullptr, 1, keep_l ? u_s : nullptr,
                         nullptr, nullptr, nullptr, 0, 0, 0, 0.f, st));
       CLIPFS_CHECK(gemm(cx, g_s, b.w_pr, f16m ? nullptr : b.w_pr_p, xout_s, Ms, d, 4 * d, b.b_pr, xmid_s, 0, nullptr, nullptr, nullptr,
                         nullptr, 0, 0, 0, 0.f, st));
       CLIPFS_CHECK(clipfs_put_seq_rows(xout_s, rows, x, (size_t)d, Ms, seq, d, st));
-      if (train) {
+      if (keep_l) {
         CLIPFS_CHECK(clipfs_put_seq_rows(xmid_s, rows, sv + SL.x_mid, (size_t)d, Ms, seq, d, st));
         if (f16m)
           CLIPFS_CHECK(clipfs_put_seq_rows_f16(u_s, rows, sv + SL.u, (size_t)4 * d, Ms, seq, 4 * d, st));
@@ -354,13 +369,13 @@ static int tower_fwd_impl(const clipfs_tower* t, float* x, const int32_t* rows, 
                       1, d, t->lora_scale, st, CHAIN_NONE, att16));
     float* h2 = scratch + SC.h;
     if (h16)  // only the f16 image is consumed (by the c_fc GEMM)
-      CLIPFS_CHECK(clipfs_layernorm_fwd_f16(x_mid, d, b.ln2_g, b.ln2_b, nullptr, h16, train ? sv + SL.stat2 : nullptr,
-                                            train ? sv + SL.stat2 + M : nullptr, M, d, 1e-5f, st));
+      CLIPFS_CHECK(clipfs_layernorm_fwd_f16(x_mid, d, b.ln2_g, b.ln2_b, nullptr, h16, keep_l ? sv + SL.stat2 : nullptr,
+                                            keep_l ? sv + SL.stat2 + M : nullptr, M, d, 1e-5f, st));
     else
-      CLIPFS_CHECK(clipfs_layernorm_fwd(x_mid, d, b.ln2_g, b.ln2_b, h2, train ? sv + SL.stat2 : nullptr,
-                                        train ? sv + SL.stat2 + M : nullptr, M, d, 1e-5f, st));
+      CLIPFS_CHECK(clipfs_layernorm_fwd(x_mid, d, b.ln2_g, b.ln2_b, h2, keep_l ? sv + SL.stat2 : nullptr,
+                                        keep_l ? sv + SL.stat2 + M : nullptr, M, d, 1e-5f, st));
     float* gbuf = scratch + SC.big;
-    CLIPFS_CHECK(gemm(cx, h2, b.w_fc, b.w_fc_p, gbuf, M, 4 * d, d, b.b_fc, nullptr, 1, train ? sv + SL.u : nullptr, nullptr, nullptr,
+    CLIPFS_CHECK(gemm(cx, h2, b.w_fc, b.w_fc_p, gbuf, M, 4 * d, d, b.b_fc, nullptr, 1, keep_l ? sv + SL.u : nullptr, nullptr, nullptr,
                       nullptr, 0, 0, 0, 0.f, st, CHAIN_OUT16, h16));
     CLIPFS_CHECK(gemm(cx, gbuf, b.w_pr, b.w_pr_p, x_next, M, d, 4 * d, b.b_pr, x_mid, 0, nullptr, nullptr, nullptr, nullptr, 0, 0, 0,
                       0.f, st, CHAIN_IN16));
@@ -383,20 +398,35 @@ extern "C" int clipfs_tower_rows_mode(const clipfs_tower* t) {
   return (t && t->blocks && t->layers > 0 && last_block_rows_ok(t)) ? 1 : 0;
 }
 
-// blocks l_hi ... 0 of the backward; dx [batch*seq, width] in/out
+// Adapter backward of one block.  Gradient slots NULL = the adapter is frozen: only its dx contribution (when wanted) is
+// computed, and with nothing wanted nothing is launched.
+static int lora_bwd_block(const clipfs_tower* t, bool dy16, const float* dy, const void* dy16p, const float* x,
+                          const float* tt, const float* A, const float* B, float* dt, float* gA, float* gB, float* dx,
+                          int M, int nseg, unsigned mask, uint32_t ds, const void* keep, float* work, hipStream_t st, int l) {
+  CLIPFS_REQUIRE((gA == nullptr) == (gB == nullptr), "tower_bwd: block %d has only one of the LoRA gradient slots", l);
+  if (!gA && !dx) return CLIPFS_OK;  // frozen and nothing below needs its input gradient
+  const int d = t->width, r = t->lora_r;
+  if (dy16)
+    return clipfs_lora_bwd_f16dy(dy16p, x, tt, A, B, dt, gA, gB, dx, M, d, d, r, nseg, mask, t->lora_scale, t->lora_dropout,
+                                 t->dropout_seed, ds, t->dropout_row0, keep, work, st);
+  return clipfs_lora_bwd(dy, x, tt, A, B, dt, gA, gB, dx, M, d, d, r, nseg, mask, t->lora_scale, t->lora_dropout,
+                         t->dropout_seed, ds, t->dropout_row0, keep, work, st);
+}
+
+// blocks l_hi ... grad_lo of the backward; dx [batch*seq, width] in/out
 static int tower_bwd_range(const clipfs_tower* t, float* dx, int batch, const float* saved, float* scratch,
                            int stop_at_input, hipStream_t st, int l_hi) {
   const int M = batch * t->seq, d = t->width, r = t->lora_r;
   const SavedLayout SL = saved_layout(t, (size_t)M);
   const ScratchLayout SC = scratch_layout(t, (size_t)M);
   const TowerCtx cx = make_ctx(t, scratch, SC);
-  const uint64_t seed = t->dropout_seed;
   void* h16 = cx.a16;                                                           // f16 image of dx (then of d ln-out ...)
   void* dqkv16 = cx.a16 ? (void*)((char*)cx.a16 + (size_t)M * d * 2) : nullptr;  // [M, 3d] halves
   if (h16) CLIPFS_CHECK(clipfs_convert_f16(dx, h16, (size_t)M * d, st));       // later images come from LayerNorm backward
-  for (int l = l_hi; l >= 0; --l) {
+  const int lo = t->grad_lo;
+  for (int l = l_hi; l >= lo; --l) {
     const clipfs_block& b = t->blocks[l];
-    const float* sv = saved + (size_t)l * SL.total;
+    const float* sv = saved + (size_t)(l - lo) * SL.total;
     CLIPFS_REQUIRE(b.w_pr_t && b.w_fc_t && b.w_o_t && b.w_qkv_t, "tower_bwd: block %d lacks transposed weights", l);
     CLIPFS_REQUIRE(t->weight_format != 2 || (b.w_pr_t_p && b.w_fc_t_p && b.w_o_t_p && b.w_qkv_t_p),
                    "tower_bwd: block %d lacks f16 copies of the transposed weights", l);
@@ -433,11 +463,9 @@ static int tower_bwd_range(const clipfs_tower* t, float* dx, int batch, const fl
     const bool datt16 = f16_attention(t) && !lora_o && h16 != nullptr;
     CLIPFS_CHECK(gemm(cx, dx, b.w_o_t, b.w_o_t_p, datt, M, d, d, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 0.f,
                       st, CHAIN_NONE, h16, datt16 ? (void*)datt : nullptr));
-    if (lora_o) {
-      CLIPFS_REQUIRE(b.g_lora_a_o && b.g_lora_b_o, "tower_bwd: block %d o-LoRA gradient slots missing", l);
-      CLIPFS_CHECK(clipfs_lora_bwd(dx, sv + SL.att, sv + SL.t_o, b.lora_a_o, b.lora_b_o, dt, b.g_lora_a_o, b.g_lora_b_o,
-                                   datt, M, d, d, r, 1, 1u, t->lora_scale, t->lora_dropout, seed, ds + 3, t->dropout_row0, nullptr, work, st));
-    }
+    if (lora_o)
+      CLIPFS_CHECK(lora_bwd_block(t, false, dx, nullptr, sv + SL.att, sv + SL.t_o, b.lora_a_o, b.lora_b_o, dt, b.g_lora_a_o,
+                                  b.g_lora_b_o, datt, M, 1, 1u, ds + 3, nullptr, work, st, l));
     // (the D_i work vector of the long-sequence kernels lives in the dt scratch slot's neighbour: reuse `dh`, dead here)
     const void* dqkv16_ready = nullptr;
     // fp16 storage mode: the dgrad GEMM and (matrix-core shapes) the adapter backward read the f16 image of dqkv, so the
@@ -451,23 +479,16 @@ static int tower_bwd_range(const clipfs_tower* t, float* dx, int batch, const fl
       CLIPFS_CHECK(clipfs_attention_bwd(sv + SL.qkv, datt, sv + SL.att, sv + SL.lse, dqkv, dh, batch, t->seq, t->heads,
                                         t->causal, st));
     CLIPFS_CHECK(bias_sum(dqkv, M, 3 * d, d, b.g_b_q, b.g_b_k, b.g_b_v, bwork, st));
-    const bool need_dx = !(l == 0 && stop_at_input);
+    const bool need_dx = !(l == lo && stop_at_input);
     // dh1 (the gradient wrt LayerNorm 1's output) is also needed for ln_1's bias gradient, even where dx is not
     const bool need_dh = need_dx || b.g_ln1_b;
     if (need_dh)
       CLIPFS_CHECK(gemm(cx, dqkv, b.w_qkv_t, b.w_qkv_t_p, dh, M, d, 3 * d, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, 0, 0, 0,
                         0.f, st, CHAIN_NONE, dqkv16_ready));
-    if (qkv_mask) {
-      CLIPFS_REQUIRE(b.g_lora_a_qkv && b.g_lora_b_qkv, "tower_bwd: block %d LoRA gradient slots missing", l);
-      if (dy16)
-        CLIPFS_CHECK(clipfs_lora_bwd_f16dy(dqkv16, sv + SL.h1, sv + SL.t_qkv, b.lora_a_qkv, b.lora_b_qkv, dt, b.g_lora_a_qkv,
-                                           b.g_lora_b_qkv, need_dh ? dh : nullptr, M, d, d, r, 3, qkv_mask, t->lora_scale,
-                                           t->lora_dropout, seed, ds, t->dropout_row0, keep_bits_saved(t) ? (const void*)(sv + SL.keep) : nullptr, work, st));
-      else
-        CLIPFS_CHECK(clipfs_lora_bwd(dqkv, sv + SL.h1, sv + SL.t_qkv, b.lora_a_qkv, b.lora_b_qkv, dt, b.g_lora_a_qkv,
-                                     b.g_lora_b_qkv, need_dh ? dh : nullptr, M, d, d, r, 3, qkv_mask, t->lora_scale,
-                                     t->lora_dropout, seed, ds, t->dropout_row0, keep_bits_saved(t) ? (const void*)(sv + SL.keep) : nullptr, work, st));
-    }
+    if (qkv_mask)
+      CLIPFS_CHECK(lora_bwd_block(t, dy16, dqkv, dqkv16, sv + SL.h1, sv + SL.t_qkv, b.lora_a_qkv, b.lora_b_qkv, dt,
+                                  b.g_lora_a_qkv, b.g_lora_b_qkv, need_dh ? dh : nullptr, M, 3, qkv_mask, ds,
+                                  keep_bits_saved(t) ? (const void*)(sv + SL.keep) : nullptr, work, st, l));
     CLIPFS_CHECK(bias_sum(dh, M, d, d, b.g_ln1_b, nullptr, nullptr, bwork, st));
     if (need_dx) {
       if (h16)
@@ -485,6 +506,8 @@ static int tower_bwd_range(const clipfs_tower* t, float* dx, int batch, const fl
 extern "C" int clipfs_tower_bwd(const clipfs_tower* t, float* dx, int batch, const float* saved, float* scratch,
                                 int stop_at_input, void* stream) {
   CLIPFS_CHECK(check_tower(t, batch));
+  CLIPFS_REQUIRE(t->grad_lo == 0 || stop_at_input,
+                 "tower_bwd: grad_lo %d > 0 needs stop_at_input (the input gradient runs through every block)", t->grad_lo);
   CLIPFS_REQUIRE(dx && saved && scratch, "tower_bwd: null buffer");
   const ScratchLayout SC = scratch_layout(t, (size_t)batch * t->seq);
   CLIPFS_REQUIRE(!t->gemm_counters || t->gemm_counters_ints >= SC.counter_ints,
@@ -495,6 +518,9 @@ extern "C" int clipfs_tower_bwd(const clipfs_tower* t, float* dx, int batch, con
 extern "C" int clipfs_tower_bwd_sparse(const clipfs_tower* t, const float* dxs, const int32_t* rows, float* dx, int batch,
                                        const float* saved, float* scratch, int stop_at_input, void* stream) {
   CLIPFS_CHECK(check_tower(t, batch));
+  CLIPFS_REQUIRE(t->grad_lo == 0 || stop_at_input,
+                 "tower_bwd_sparse: grad_lo %d > 0 needs stop_at_input (the input gradient runs through every block)",
+                 t->grad_lo);
   CLIPFS_REQUIRE(dxs && rows && dx && saved && scratch, "tower_bwd_sparse: null buffer");
   hipStream_t st = (hipStream_t)stream;
   const int seq = t->seq, M = batch * seq, d = t->width, r = t->lora_r, Ms = batch;
@@ -510,7 +536,7 @@ extern "C" int clipfs_tower_bwd_sparse(const clipfs_tower* t, const float* dxs, 
   }
   CLIPFS_REQUIRE(b.w_pr_t && b.w_fc_t && b.w_o_t && b.w_qkv_t, "tower_bwd: block %d lacks transposed weights", l);
   const TowerCtx cx = make_ctx(t, scratch, SC);
-  const float* sv = saved + (size_t)l * SL.total;
+  const float* sv = saved + (size_t)(l - t->grad_lo) * SL.total;
   // compact (one row per sequence) buffers live in the MLP scratch, which this block does not otherwise use:
   // Ms (8 d + 4 d + 2) floats <= M 4 d for seq >= 3
   float* u_s = scratch + SC.big;
@@ -564,23 +590,15 @@ extern "C" int clipfs_tower_bwd_sparse(const clipfs_tower* t, const float* dxs, 
     CLIPFS_CHECK(clipfs_attention_bwd(sv + SL.qkv, datt, sv + SL.att, sv + SL.lse, dqkv, dh, batch, seq, t->heads, t->causal, st));
   CLIPFS_CHECK(bias_sum(dqkv, M, 3 * d, d, b.g_b_q, b.g_b_k, b.g_b_v, bwork, st));
   const uint32_t ds = t->dropout_stream0 + 4u * (uint32_t)l;
-  const bool need_dx = !(l == 0 && stop_at_input);
+  const bool need_dx = !(l == t->grad_lo && stop_at_input);
   const bool need_dh = need_dx || b.g_ln1_b;  // as in tower_bwd_range
   if (need_dh)
     CLIPFS_CHECK(gemm(cx, dqkv, b.w_qkv_t, b.w_qkv_t_p, dh, M, d, 3 * d, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, 0, 0,
                       0, 0.f, st, CHAIN_NONE, dqkv16_ready));
-  if (qkv_mask) {
-    CLIPFS_REQUIRE(b.g_lora_a_qkv && b.g_lora_b_qkv, "tower_bwd: block %d LoRA gradient slots missing", l);
-    if (dy16)
-      CLIPFS_CHECK(clipfs_lora_bwd_f16dy(dqkv16, sv + SL.h1, sv + SL.t_qkv, b.lora_a_qkv, b.lora_b_qkv, dt, b.g_lora_a_qkv,
-                                         b.g_lora_b_qkv, need_dh ? dh : nullptr, M, d, d, r, 3, qkv_mask, t->lora_scale,
-                                         t->lora_dropout, t->dropout_seed, ds, t->dropout_row0, keep_bits_saved(t) ? (const void*)(sv + SL.keep) : nullptr,
-                                         work, st));
-    else
-      CLIPFS_CHECK(clipfs_lora_bwd(dqkv, sv + SL.h1, sv + SL.t_qkv, b.lora_a_qkv, b.lora_b_qkv, dt, b.g_lora_a_qkv, b.g_lora_b_qkv,
-                                   need_dh ? dh : nullptr, M, d, d, r, 3, qkv_mask, t->lora_scale, t->lora_dropout,
-                                   t->dropout_seed, ds, t->dropout_row0, keep_bits_saved(t) ? (const void*)(sv + SL.keep) : nullptr, work, st));
-  }
+  if (qkv_mask)
+    CLIPFS_CHECK(lora_bwd_block(t, dy16, dqkv, dqkv16, sv + SL.h1, sv + SL.t_qkv, b.lora_a_qkv, b.lora_b_qkv, dt,
+                                b.g_lora_a_qkv, b.g_lora_b_qkv, need_dh ? dh : nullptr, M, 3, qkv_mask, ds,
+                                keep_bits_saved(t) ? (const void*)(sv + SL.keep) : nullptr, work, st, l));
   CLIPFS_CHECK(bias_sum(dh, M, d, d, b.g_ln1_b, nullptr, nullptr, bwork, st));
   if (!need_dx) return CLIPFS_OK;
   CLIPFS_CHECK(clipfs_layernorm_bwd(dh, sv + SL.x_in, d, b.ln1_g, sv + SL.stat1, sv + SL.stat1 + M, nullptr, dx, d, M, d, st));

@@ -535,22 +535,27 @@ class FlatTrainables:
     gradient buffer.  The packed in-projection bias the QKV GEMM reads: when all three q / k / v views of a LoRA block
     train, their slices are adjacent and the packed tensor IS that 3d slice; when only some do (``lora_only`` with
     ``params=['q', 'v']``), the trained segments get their own slices and ``sync_packed`` copies them into the packed
-    tensor (3d floats per block) -- a frozen segment is never in the buffer, so AdamW's weight decay cannot touch it."""
+    tensor (3d floats per block) -- a frozen segment is never in the buffer, so AdamW's weight decay cannot touch it.
+
+    Adapters frozen with ``requires_grad_(False)`` are left out the same way (all or nothing per block, as the fused
+    backward sees them: ``clipfs.engine._lora_trains``): they keep their own storage, get no gradient slot and are never
+    moved by AdamW (the stage-2 layout, slow_pace.py:1556-1564: LoRA applied but frozen)."""
 
     def __init__(self, model, extra: Sequence[nn.Parameter] = ()):
+        from clipfs.engine import _lora_trains
         self.model = model
         bias_names = [n for n, _ in trainable_biases(model)]
         entries = []
-        for tower in (model.transformer, model.visual.transformer):
-            for blk in tower.resblocks:
+        for tname, tower in (("text", model.transformer), ("vision", model.visual.transformer)):
+            for i, blk in enumerate(tower.resblocks):
                 a = blk.attn
-                if getattr(a, "is_lora_mha", False):
+                if getattr(a, "is_lora_mha", False) and _lora_trains(a, f"{tname} block {i}"):
                     for name, p, _ in a.stacked():
                         entries.append((a, name, p))
         n_bias = sum(p.numel() for _, p in trainable_biases(model))
         n = sum(p.numel() for _, _, p in entries) + sum(p.numel() for p in extra) + n_bias
         if n == 0:
-            raise ValueError("model has no trainable adapter parameters (call apply_lora first)")
+            raise ValueError("model has nothing to train: no trainable adapter, bias or extra tensor (call apply_lora first)")
         dev = model.device
         self.params = torch.zeros(n, device=dev)
         self.grads = torch.zeros(n, device=dev)
@@ -661,6 +666,7 @@ class LoRATrainer:
         # the send block / the gradient table are written by nobody and stay zero)
         self._xbuf = {}
         self.collectives_per_step = (3 if self.shard_text else 1) if (self.world > 1 or D.FORCE_COLLECTIVES) else 0
+        self.last_plan = None  # gradient floors of the last forward_backward: {"text": lo or None, "vision": lo or None}
         self.time_collectives = False      # bench: bracket every collective with HIP events on the launch stream
         self._coll_events = []
 
@@ -702,7 +708,12 @@ class LoRATrainer:
         returns (loss_sum_local [1], correct_local [1], logits_local [B_local, C]).
 
         Collectives (world > 1, class-sharded text): all_gather of the class-feature block, reduce_scatter of its
-        gradient (here), all_reduce of the flat gradient (optimizer_step) -- clipfs/dist.py."""
+        gradient (here), all_reduce of the flat gradient (optimizer_step) -- clipfs/dist.py.
+
+        A tower with nothing to train (gradient floor None, ``Engine.image_plan`` / ``text_plan``) runs its no-grad
+        forward and gets no backward; its side of the logits gradient is not formed, and a frozen class-sharded text
+        tower skips the reduce_scatter (every rank holds the same flags, so the ranks agree).  ``last_plan`` records the
+        floors."""
         from clipfs import dist as D
         m = self.model
         eng = m.engine
@@ -720,6 +731,11 @@ class LoRATrainer:
             raise ValueError("trim_text cannot be combined with a class-sharded text tower and LoRA dropout > 0: the "
                              "Philox rows would depend on each rank's trimmed length (use trim_text=False or shard_text=False)")
         xb = self._exchange_buffers(classes, d) if self.shard_text else None
+        text_lo = eng.text_plan(self.prompt_ctx is not None)
+        vis_lo = eng.image_plan()
+        self.last_plan = {"text": text_lo, "vision": vis_lo}
+        if self.world > 1 or D.FORCE_COLLECTIVES:
+            self.collectives_per_step = (3 if text_lo is not None else 2) if self.shard_text else 1
         # The two towers are independent until the logits: the text tower runs on a side HIP stream so that
         # its kernels fill the CUs the image tower's launches leave idle (small per-rank batches) and vice versa.
         main = torch.cuda.current_stream()
@@ -740,21 +756,24 @@ class LoRATrainer:
         logits = ops.gemm_nt(img_n, txt, alpha=self.logit_scale)
         self.last_features = (img_n, txt)  # unit image features of this rank's shard, unit class features [C, d] (tests)
         loss_sum, dl, correct = ops.cross_entropy(logits, target, True, grad_scale=B / gb)
-        d_img_n = ops.matmul_small(dl, txt, B, d, classes, classes, 1, d, 1, self.logit_scale)
-        d_txt = ops.matmul_small(dl, img_n, classes, d, B, 1, classes, d, 1, self.logit_scale,
-                                 out=None if xb is None else xb["dfull"][:classes])
-        if self.shard_text:  # every rank needs the batch-total gradient of ITS classes only
-            mine = self._timed("reduce_scatter", lambda: D.reduce_scatter_blocks(xb["dfull"], xb["dmine"], self.pg))
-            d_txt_local = mine[:c_hi - c_lo]
-        else:
-            d_txt_local = d_txt
-        side.wait_stream(main)
-        with torch.cuda.stream(side):
-            if c_hi > c_lo:
-                d_emb = ops.class_mean_bwd(emb, d_txt_local, c_hi - c_lo, t)
-                slot = None if self.prompt_ctx is None else self.prompt_ctx.grad_slot
-                eng.text_backward(tctx, d_emb, slot)
-        eng.vit_backward(ictx, ops.l2norm_bwd(d_img_n, img_n, inv))
+        if vis_lo is not None:
+            d_img_n = ops.matmul_small(dl, txt, B, d, classes, classes, 1, d, 1, self.logit_scale)
+        if text_lo is not None:
+            d_txt = ops.matmul_small(dl, img_n, classes, d, B, 1, classes, d, 1, self.logit_scale,
+                                     out=None if xb is None else xb["dfull"][:classes])
+            if self.shard_text:  # every rank needs the batch-total gradient of ITS classes only
+                mine = self._timed("reduce_scatter", lambda: D.reduce_scatter_blocks(xb["dfull"], xb["dmine"], self.pg))
+                d_txt_local = mine[:c_hi - c_lo]
+            else:
+                d_txt_local = d_txt
+            side.wait_stream(main)
+            with torch.cuda.stream(side):
+                if c_hi > c_lo:
+                    d_emb = ops.class_mean_bwd(emb, d_txt_local, c_hi - c_lo, t)
+                    slot = None if self.prompt_ctx is None else self.prompt_ctx.grad_slot
+                    eng.text_backward(tctx, d_emb, slot)
+        if vis_lo is not None:
+            eng.vit_backward(ictx, ops.l2norm_bwd(d_img_n, img_n, inv))
         main.wait_stream(side)
         return loss_sum, correct, logits
 
