@@ -150,6 +150,11 @@ int clipfs_layernorm_fwd(const float* x, int ldx, const float* gamma, const floa
 int clipfs_layernorm_bwd(const float* dy, const float* x, int ldx, const float* gamma, const float* mean,
                          const float* rstd, const float* dres, float* dx, int lddx, int rows, int width,
                          void* stream);
+/* The same backward with x, mean and rstd read at row xmap[r] for output row r (dy, dres, dx stay dense [rows, ...]):
+ * the packed text backward reads the forward's full-layout tensors in place.  Arithmetic identical per row. */
+int clipfs_layernorm_bwd_rows(const float* dy, const float* x, int ldx, const float* gamma, const float* mean,
+                              const float* rstd, const int32_t* xmap, const float* dres, float* dx, int lddx, int rows,
+                              int width, void* stream);
 /* fp16 storage mode: the same kernels writing an f16 copy of the result [rows, width] for the GEMM that consumes it
  * (y16 / dx16 may be NULL; in the forward y may be NULL when only the f16 operand is needed). */
 int clipfs_layernorm_fwd_f16(const float* x, int ldx, const float* gamma, const float* beta, float* y, void* y16,
@@ -187,6 +192,15 @@ int clipfs_attention_fwd(const float* qkv, float* out, float* lse, int batch, in
 int clipfs_attention_bwd(const float* qkv, const float* dout, const float* out, const float* lse, float* dqkv,
                          float* work, int batch, int seq, int heads, int causal, void* stream);
 size_t clipfs_attention_lse_floats(int batch, int seq, int heads);
+/* Packed (live-row) causal backward of the text tower, seq <= 96 on the exact-fp32 16-token-tile kernels
+ * (clipfs_attention_bwd_packed_ok(seq, causal) != 0; needs causal and the MFMA kernels).  Sequence b is live on tokens
+ * 0 .. Lb - 1, Lb = off[b + 1] - off[b] in [1, seq] (off: int32 [batch + 1], device, off[0] = 0): qkv, out and lse are the
+ * forward's full-layout tensors (row b * seq + tok), dout and dqkv are packed [off[batch], d] / [off[batch], 3 d] (row
+ * off[b] + tok).  Each live row gets exactly the values the full-layout call computes when every dead row of dout is 0;
+ * tiles past Lb do no work. */
+int clipfs_attention_bwd_packed_ok(int seq, int causal);
+int clipfs_attention_bwd_packed(const float* qkv, const float* dout, const float* out, const float* lse, float* dqkv,
+                                const int32_t* off, int batch, int seq, int heads, void* stream);
 /* fp16 storage mode (cfg-5), seq <= 288: the same function with both contractions on
  * v_mfma_f32_32x32x16_f16 (operands rounded to f16 in the staging path; softmax statistics, accumulators and
  * outputs fp32).  lse as above (may be NULL when no backward follows). */
@@ -271,6 +285,10 @@ int clipfs_add_seq_rows(const float* src, const int32_t* idx, float* dx, int n, 
 int clipfs_put_seq_rows(const float* src, const int32_t* idx, float* dst, size_t ld, int n, int seq, int width,
                         void* stream);
 int clipfs_eot_index(const int64_t* ids, int32_t* idx, int n, int seq, void* stream);
+/* rows through a map (the packed text backward): gather  out[i, :] = src[map[i] * ld + 0..width)   (i < n)
+ *                                                 put     dst[map[i] * ld + 0..width) = src[i, :] (other rows untouched) */
+int clipfs_gather_rows_map(const float* src, size_t ld, const int32_t* map, float* out, int n, int width, void* stream);
+int clipfs_put_rows_map(const float* src, const int32_t* map, float* dst, size_t ld, int n, int width, void* stream);
 /* gather / put for a tensor kept as f16 (the saved pre-GELU activation of the fp16 storage mode); ld in halves, the
  * compact side [n, width] is fp32 */
 int clipfs_gather_seq_rows_f16(const void* src_f16, size_t ld, const int32_t* idx, float* out, int n, int seq, int width,
@@ -458,6 +476,22 @@ int clipfs_tower_bwd(const clipfs_tower* t, float* dx, int batch, const float* s
  * (scatter + clipfs_tower_bwd) for o-projection adapters in the last block and seq < 8 (clipfs_tower_rows_mode). */
 int clipfs_tower_bwd_sparse(const clipfs_tower* t, const float* dxs, const int32_t* rows, float* dx, int batch,
                             const float* saved, float* scratch, int stop_at_input, void* stream);
+/* The same backward on the LIVE rows of a causal tower (the text tower): below the last block's compact part, the gradient
+ * of sequence c is non-zero only on its rows c*seq + 0 .. rows[c] (nothing before the EOT attends to a later row), so
+ * every block from the last block's attention down to grad_lo runs its dgrad GEMMs, attention, LayerNorm, LoRA and bias
+ * backward on the R = sum (rows[c] + 1) live rows, packed caption after caption (the saved per-row tensors are gathered).
+ * plan: int32 device [2 batch + 1 + R] = off[0 .. batch] (exclusive prefix sum of rows[c] + 1, off[batch] = R) |
+ * eotp[0 .. batch) (= off[c + 1] - 1) | map[0 .. R) (packed row i -> full-layout row c*seq + i - off[c]); built by the
+ * caller from the same rows.  The forward is clipfs_tower_fwd_rows with these rows; dx is written in the full layout
+ * (dead rows exact zeros) unless stop_at_input.  Results equal clipfs_tower_bwd_sparse's up to the summation order of the
+ * parameter gradients (fewer exact-zero terms).  Runs the dense rows (clipfs_tower_bwd_sparse) when
+ * clipfs_tower_pack_mode(t, batch, R) == 0: not causal, the fp16 storage mode, clipfs_tower_rows_mode() == 0, no packed
+ * attention kernel for seq, R > batch*seq / 2 (the packed buffers live in the scratch slots of the dense rows: no extra
+ * memory), batch*seq < 2048 (launch-bound: nothing to gain), LoRA dropout whose masks are not saved as keep bits (or
+ * on an o-projection adapter), or a LoRA / bias workspace the R-row launch would outgrow.  CLIPFS_EINVAL for NULL buffers or R outside [batch, batch*seq]. */
+int clipfs_tower_pack_mode(const clipfs_tower* t, int batch, int R);
+int clipfs_tower_bwd_packed(const clipfs_tower* t, const float* dxs, const int32_t* rows, const int32_t* plan, int R,
+                            float* dx, int batch, const float* saved, float* scratch, int stop_at_input, void* stream);
 
 #ifdef __cplusplus
 }

@@ -150,6 +150,13 @@ SIGNATURES = {
     "clipfs_tower_rows_mode": (_i, [C.POINTER(Tower)]),
     "clipfs_tower_bwd": (_i, [C.POINTER(Tower), _p, _i, _p, _p, _i, _p]),
     "clipfs_tower_bwd_sparse": (_i, [C.POINTER(Tower), _p, _p, _p, _i, _p, _p, _i, _p]),
+    "clipfs_attention_bwd_packed_ok": (_i, [_i, _i]),
+    "clipfs_attention_bwd_packed": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _p]),
+    "clipfs_gather_rows_map": (_i, [_p, _sz, _p, _p, _i, _i, _p]),
+    "clipfs_put_rows_map": (_i, [_p, _p, _p, _sz, _i, _i, _p]),
+    "clipfs_layernorm_bwd_rows": (_i, [_p, _p, _i, _p, _p, _p, _p, _p, _p, _i, _i, _i, _p]),
+    "clipfs_tower_pack_mode": (_i, [C.POINTER(Tower), _i, _i]),
+    "clipfs_tower_bwd_packed": (_i, [C.POINTER(Tower), _p, _p, _p, _i, _p, _i, _p, _p, _i, _p]),
 }
 
 def new_gemm_args() -> GemmArgs:

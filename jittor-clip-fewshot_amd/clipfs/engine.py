@@ -276,6 +276,26 @@ class _TowerRT:
               "tower_bwd_sparse")
         return dx
 
+    def backward_packed(self, dxs: torch.Tensor, rows: torch.Tensor, plan: torch.Tensor, R: int, batch: int,
+                        saved: torch.Tensor, seed: int, stop_at_input: bool, seq: Optional[int] = None, row0: int = 0,
+                        grad_lo: int = 0) -> torch.Tensor:
+        """``backward_sparse`` of a causal tower on its live rows only (clipfs_tower_bwd_packed; ``plan`` / ``R`` from
+        ``Engine._pack_plan``).  Same return value; runs the dense rows where the library does not pack."""
+        lib = _lib.load()
+        t = self.descriptor(True, seed, seq, row0, grad_lo)
+        self._attach_counters(t, batch, dxs.device)
+        scratch = self.buffer("scratch", lib.clipfs_tower_scratch_floats(C.byref(t), batch), dxs.device)
+        dx = torch.empty(batch * (seq or self.seq), self.width, device=dxs.device, dtype=torch.float32)
+        check(lib.clipfs_tower_bwd_packed(C.byref(t), dxs.data_ptr(), rows.data_ptr(), plan.data_ptr(), R, dx.data_ptr(), batch,
+                                          saved.data_ptr(), scratch.data_ptr(), int(stop_at_input),
+                                          torch.cuda.current_stream().cuda_stream), "tower_bwd_packed")
+        return dx
+
+    def pack_mode(self, batch: int, R: int, seed: int, seq: Optional[int] = None, grad_lo: int = 0) -> bool:
+        """Whether ``backward_packed`` runs packed for this geometry (clipfs_tower_pack_mode)."""
+        t = self.descriptor(True, seed, seq, 0, grad_lo)
+        return bool(_lib.load().clipfs_tower_pack_mode(C.byref(t), batch, R))
+
 
 class Engine:
     def __init__(self, model):
@@ -305,6 +325,13 @@ class Engine:
         # gradients are bitwise those of the full-depth path.  False = every tower saves and back-propagates every block
         # (the A/B reference; frozen adapters are still never trained).
         self.prune_backward = True
+        # Text backward on live rows only (clipfs_tower_bwd_packed): under the causal mask a caption's gradient is zero
+        # on every row after its EOT, so below the last block's compact part the text tower back-propagates the
+        # R = sum (eot + 1) rows 0 .. eot of each caption (31 % of the rows for the bench's captions).  Applies on the
+        # one-row path only (``sparse_backward``).  Loss and logits are unchanged; parameter gradients differ only in
+        # summation order.  False = every row of every block (the A/B reference).
+        self.pack_text_backward = True
+        self._pack_cache = {}
 
     @property
     def precision(self) -> str:
@@ -436,6 +463,30 @@ class Engine:
             self._trim_cache = {key: hit}
         return hit
 
+    def _pack_plan(self, ids: torch.Tensor, ids_host: Optional[torch.Tensor] = None):
+        """(plan, R) of clipfs_tower_bwd_packed for a caption table ``ids`` [n, seq]: off [n + 1] | eotp [n] | map [R], int32
+        on the device.  Built once per distinct table, cached like ``_effective_ids``; the entry holds ``ids`` so that its
+        storage cannot be reused under the same key.  ``ids_host``: the same table still on the host (the drop-in route
+        uploads its ids every call): the plan is then built there and uploaded with them, with no device-to-host sync."""
+        key = (ids.data_ptr(), tuple(ids.shape), ids._version)
+        hit = self._pack_cache.get(key)
+        if hit is None:
+            n, seq = ids.shape
+            src = ids if ids_host is None else ids_host[:, :seq]
+            if ids_host is None:
+                lens = ops.eot_index(ids).to(torch.int64) + 1
+            else:  # first maximum, as clipfs_eot_index
+                lens = src.to(torch.int64).argmax(dim=-1) + 1
+            off = torch.zeros(n + 1, device=src.device, dtype=torch.int64)
+            off[1:] = torch.cumsum(lens, 0)
+            R = int(off[-1].item())  # device tables: one host sync per distinct caption table
+            cap = torch.repeat_interleave(torch.arange(n, device=src.device), lens, output_size=R)
+            rows = cap * seq + torch.arange(R, device=src.device) - off[cap]
+            plan = torch.cat([off, off[1:] - 1, rows]).to(device=ids.device, dtype=torch.int32)
+            hit = (plan, R, ids)
+            self._pack_cache = {key: hit}
+        return hit[0], hit[1]
+
     def text_forward(self, ids: torch.Tensor, prompt_ctx: Optional[torch.Tensor], train: bool, seed: int = 0,
                      own_saved: bool = False, row0: int = 0):
         """As ``vit_forward``: with nothing of the text side to train (``text_plan`` None) the pass is the no-grad one
@@ -444,6 +495,7 @@ class Engine:
         if lo is None:
             train = False
         m = self.model
+        ids_host = ids if not ids.is_cuda else None
         ids = ids.to(device=m.device, dtype=torch.int64).contiguous()
         n, seq = ids.shape
         if seq != m.context_length:
@@ -465,7 +517,9 @@ class Engine:
         ctx = None
         if train:
             ctx = dict(n=n, seq=seq, rows=rows, idx=idx, stats=(mean, rstd), saved=saved, seed=seed, row0=row0,
-                       one_row=one_row, has_ctx=prompt_ctx is not None, lo=lo)
+                       one_row=one_row, has_ctx=prompt_ctx is not None, lo=lo,
+                       pack=self._pack_plan(ids, ids_host) if one_row and self.pack_text_backward and
+                       self.txt.pack_mode(n, n, seed, seq, lo) else None)
         return feat, ctx
 
     def text_backward(self, ctx: dict, dfeat: torch.Tensor, dctx_slot: Optional[torch.Tensor] = None) -> None:
@@ -478,7 +532,11 @@ class Engine:
         mean, rstd = ctx["stats"]
         drows = ops.layernorm_bwd(dy, ctx["rows"], m.ln_final.weight.data, mean, rstd)
         # only the EOT row of each caption carries gradient (jclip/model.py:213-214)
-        if ctx["one_row"]:
+        if ctx.get("pack") is not None:
+            plan, R = ctx["pack"]
+            dx = self.txt.backward_packed(drows, ctx["idx"], plan, R, n, ctx["saved"], ctx["seed"],
+                                          stop_at_input=not ctx["has_ctx"], seq=seq, row0=ctx["row0"], grad_lo=ctx["lo"])
+        elif ctx["one_row"]:
             dx = self.txt.backward_sparse(drows, ctx["idx"], n, ctx["saved"], ctx["seed"], stop_at_input=not ctx["has_ctx"],
                                           seq=seq, row0=ctx["row0"], grad_lo=ctx["lo"])
         else:

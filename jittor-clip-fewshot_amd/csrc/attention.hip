@@ -652,6 +652,10 @@ int attention_mfma_fwd(const float* qkv, float* out, float* lse, int batch, int 
 int attention_mfma_bwd(const float* qkv, const float* dout, const float* out, const float* lse, float* dqkv, float* work,
                        int batch, int seq, int heads, int causal, hipStream_t st);
 constexpr int ATTN_MFMA_MAX = 288;
+// attention_mfma16.hip: the 16-token-tile kernels (seq <= 96) and their packed (live-row) backward
+bool attention16_enabled(int seq);
+int attention16_bwd_packed(const float* qkv, const float* dout, const float* out, const float* lse, float* dqkv,
+                           const int32_t* off, int batch, int seq, int heads, hipStream_t st);
 
 static int check_attn(const char* what, int batch, int seq, int heads, int max_seq) {
   CLIPFS_REQUIRE(batch > 0 && heads > 0 && seq > 0 && seq <= max_seq, "%s: batch %d seq %d heads %d unsupported (seq <= %d)",
@@ -772,6 +776,20 @@ extern "C" int clipfs_attention_bwd(const float* qkv, const float* dout, const f
   else
     hipLaunchKernelGGL((attention_bwd_kernel<96>), grid, block, lds, st, qkv, dout, dqkv, seq, heads, causal, lp);
   return launch_status();
+}
+
+extern "C" int clipfs_attention_bwd_packed_ok(int seq, int causal) {
+  return (causal && seq > 0 && seq <= ATTN_MFMA_MAX && attention_mfma_enabled() && attention16_enabled(seq)) ? 1 : 0;
+}
+
+extern "C" int clipfs_attention_bwd_packed(const float* qkv, const float* dout, const float* out, const float* lse,
+                                           float* dqkv, const int32_t* off, int batch, int seq, int heads, void* stream) {
+  CLIPFS_CHECK(check_attn("attention_bwd_packed", batch, seq, heads, ATTN_MAX_SEQ));
+  CLIPFS_REQUIRE(clipfs_attention_bwd_packed_ok(seq, 1), "attention_bwd_packed: seq %d has no packed kernel", seq);
+  CLIPFS_REQUIRE(qkv && dout && out && lse && dqkv && off, "attention_bwd_packed: null pointer");
+  CLIPFS_REQUIRE(aligned16(qkv) && aligned16(dout) && aligned16(out) && aligned16(dqkv),
+                 "attention_bwd_packed: misaligned pointer");
+  return attention16_bwd_packed(qkv, dout, out, lse, dqkv, off, batch, seq, heads, (hipStream_t)stream);
 }
 
 extern "C" size_t clipfs_attention_lse_floats(int batch, int seq, int heads) {

@@ -202,11 +202,16 @@ __global__ __launch_bounds__(64 * NT) void attention16_fwd_kernel(const float* _
 
 // dQ pass (own = 16 queries).  S^T = K Q^T ; P^T = exp2(S^T c - lse) ; dP^T = V dO^T ; dS^T = P^T (dP^T - D) / 8 ;
 // dQ^T = K^T dS^T.  D_i = dO_i . O_i from the own rows in registers.
-template <int NT>
+//
+// PACKED (the text tower's live-row backward): sequence b is live on tokens 0 .. Lb - 1 only, Lb = off[b + 1] - off[b]
+// (its EOT and what precedes it).  qkv, out and lse keep the forward's full layout (row b * L + tok); dout and dqkv are
+// packed (row off[b] + tok).  Tokens Lb .. L - 1 are staged as zeros and masked like the padding past L, and waves whose
+// own tile starts at or past Lb leave after the last barrier: under the causal mask a live row never sees a dead one.
+template <int NT, bool PACKED>
 __device__ __forceinline__ void attention16_bwd_q_body(const float* __restrict__ qkv, const float* __restrict__ dout,
                                                        const float* __restrict__ out, const float* __restrict__ lse,
                                                        float* __restrict__ dqkv, int L, int H, int causal, int item,
-                                                       float* a16_smem) {
+                                                       const int32_t* __restrict__ off, float* a16_smem) {
   constexpr int TP = 16 * NT + 8;
   float* sKt = a16_smem;
   float* sVt = sKt + 64 * TP;
@@ -215,18 +220,20 @@ __device__ __forceinline__ void attention16_bwd_q_body(const float* __restrict__
   const int d = H * A16_HD;
   const size_t ld = (size_t)3 * d;
   const int g = lane >> 4;
-  const int q_tok = 16 * qt + (lane & 15), q_cl = min(q_tok, L - 1);
+  const int b = item / H, h = item % H;
+  const size_t prow = PACKED ? (size_t)off[b] : (size_t)b * L;  // row of token 0 in dout / dqkv
+  const int Lb = PACKED ? (int)(off[b + 1] - prow) : L;
+  const int q_tok = 16 * qt + (lane & 15), q_cl = min(q_tok, Lb - 1);
   const float c = 0.125f * A16_LOG2E;
-  const int klim = causal ? q_tok : L - 1;
-  const int na = causal ? qt + 1 : NT;
+  const int klim = causal ? q_tok : Lb - 1;
+  const int na = causal ? qt + 1 : (Lb + 15) / 16;
   auto head = [&](int item) { return qkv + (size_t)(item / H) * L * ld + (size_t)(item % H) * A16_HD; };
   f32x4 kst[4], vst[4];
-  a16_fetch<NT>(head(item) + d, ld, L, kst);
-  a16_fetch<NT>(head(item) + 2 * d, ld, L, vst);
-  const int b = item / H, h = item % H;
+  a16_fetch<NT>(head(item) + d, ld, Lb, kst);
+  a16_fetch<NT>(head(item) + 2 * d, ld, Lb, vst);
   float qf[16], gf[16];
   a16_load_own(head(item), ld, q_cl, lane, qf);
-  a16_load_own(dout + (size_t)b * L * d + (size_t)h * A16_HD, (size_t)d, q_cl, lane, gf);
+  a16_load_own(dout + prow * d + (size_t)h * A16_HD, (size_t)d, q_cl, lane, gf);
   float Di = 0.f;
   {
     const float* op = out + ((size_t)b * L + q_cl) * d + h * A16_HD + 16 * g;
@@ -238,10 +245,11 @@ __device__ __forceinline__ void attention16_bwd_q_body(const float* __restrict__
     }
   }
   const float lse2 = lse[((size_t)b * H + h) * L + q_cl] * A16_LOG2E;
-  a16_put<NT>(sKt, kst, L);
-  a16_put<NT>(sVt, vst, L);
+  a16_put<NT>(sKt, kst, Lb);
+  a16_put<NT>(sVt, vst, Lb);
   Di = a16_allreduce_sum(Di);
   __syncthreads();
+  if (PACKED && 16 * qt >= Lb) return;  // no live query in this wave's tile (wave-uniform; no barrier follows)
   f32x4 s[A16_MAX_TILES], dp[A16_MAX_TILES];
   A16_SWITCH_SCORES(na, sKt, qf, s)
   A16_SWITCH_SCORES(na, sVt, gf, dp)
@@ -255,22 +263,22 @@ __device__ __forceinline__ void attention16_bwd_q_body(const float* __restrict__
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int key = 16 * t + 4 * g + r;
-        const float p = (key < L && key <= klim) ? __builtin_amdgcn_exp2f(s[t][r] * c - lse2) : 0.f;
+        const float p = (key < Lb && key <= klim) ? __builtin_amdgcn_exp2f(s[t][r] * c - lse2) : 0.f;
         ds[r] = p * (dp[t][r] - Di) * 0.125f;
       }
       a16_accum<TP>(sKt, lane, t, ds, acc);
     }
-  if (q_tok < L) a16_store(dqkv + ((size_t)b * L + q_tok) * ld + h * A16_HD, acc, 1.f, lane);
+  if (q_tok < Lb) a16_store(dqkv + (prow + q_tok) * ld + h * A16_HD, acc, 1.f, lane);
 }
 
 // dK/dV pass (own = 16 keys).  S = Q K^T ; P = exp2(S c - lse) ; dP = dO V^T ; dS = P (dP - D) / 8 ;
 // dV^T = dO^T P ; dK^T = Q^T dS.  lse and D vary with the register index (rows = queries): 4-float groups from LDS;
 // D is recomputed here from the staged dO rows and the matching O rows.
-template <int NT>
+template <int NT, bool PACKED>
 __device__ __forceinline__ void attention16_bwd_kv_body(const float* __restrict__ qkv, const float* __restrict__ dout,
                                                         const float* __restrict__ out, const float* __restrict__ lse,
                                                         float* __restrict__ dqkv, int L, int H, int causal, int item,
-                                                        float* a16_smem) {
+                                                        const int32_t* __restrict__ off, float* a16_smem) {
   constexpr int Lp = 16 * NT, TP = Lp + 8;
   float* sQt = a16_smem;
   float* sGt = sQt + 64 * TP;
@@ -282,27 +290,28 @@ __device__ __forceinline__ void attention16_bwd_kv_body(const float* __restrict_
   const int d = H * A16_HD;
   const size_t ld = (size_t)3 * d;
   const int g = lane >> 4;
-  const int k_tok = 16 * kt + (lane & 15), k_cl = min(k_tok, L - 1);
+  const int b = item / H, h = item % H;
+  const size_t prow = PACKED ? (size_t)off[b] : (size_t)b * L;  // row of token 0 in dout / dqkv
+  const int Lb = PACKED ? (int)(off[b + 1] - prow) : L;
+  const int k_tok = 16 * kt + (lane & 15), k_cl = min(k_tok, Lb - 1);
   const float c = 0.125f * A16_LOG2E;
   // query tiles with work: t >= kt under the causal mask (wave-uniform); they run as tiles 0 .. na-1 of a shifted image
   const int t_first = causal ? kt : 0;
-  const int na = NT - t_first;
+  const int na = (PACKED ? (Lb + 15) / 16 : NT) - t_first;
   const float* sQ1 = sQt + 16 * t_first;
   const float* sG1 = sGt + 16 * t_first;
   auto qhead = [&](int item) { return qkv + (size_t)(item / H) * L * ld + (size_t)(item % H) * A16_HD; };
-  auto ghead = [&](int item) { return dout + (size_t)(item / H) * L * d + (size_t)(item % H) * A16_HD; };
-  const int vtok = min((int)threadIdx.x, L - 1);  // thread i < 16 NT carries element i of the head's lse / D vectors
+  const int vtok = min((int)threadIdx.x, Lb - 1);  // thread i < 16 NT carries element i of the head's lse / D vectors
   f32x4 qst[4], gst[4], ost[4];
-  a16_fetch<NT>(qhead(item), ld, L, qst);
-  a16_fetch<NT>(ghead(item), (size_t)d, L, gst);
-  a16_fetch<NT>(out + (size_t)(item / H) * L * d + (size_t)(item % H) * A16_HD, (size_t)d, L, ost);
-  const int b = item / H, h = item % H;
+  a16_fetch<NT>(qhead(item), ld, Lb, qst);
+  a16_fetch<NT>(dout + prow * d + (size_t)h * A16_HD, (size_t)d, Lb, gst);
+  a16_fetch<NT>(out + (size_t)(item / H) * L * d + (size_t)(item % H) * A16_HD, (size_t)d, Lb, ost);
   float kf[16], vf[16];
   a16_load_own(qhead(item) + d, ld, k_cl, lane, kf);
   a16_load_own(qhead(item) + 2 * d, ld, k_cl, lane, vf);
   const float lse_i = lse[(size_t)item * L + vtok];  // item = b * H + h
-  a16_put<NT>(sQt, qst, L);
-  a16_put<NT>(sGt, gst, L);
+  a16_put<NT>(sQt, qst, Lb);
+  a16_put<NT>(sGt, gst, Lb);
   // D_i = dO_i . O_i from the rows this pass stages anyway (the dQ pass computes its own copy in registers, so the two
   // passes do not depend on each other and run as ONE launch): each staging thread holds 4 features of 4 (chunk, token)
   // pairs; the 16 chunk sums of a token are added in chunk order by the thread that owns the token => reproducible
@@ -317,10 +326,11 @@ __device__ __forceinline__ void attention16_bwd_kv_body(const float* __restrict_
     float d_i = 0.f;
 #pragma unroll
     for (int c = 0; c < 16; ++c) d_i += sPart[c * Lp + threadIdx.x];
-    sLse[threadIdx.x] = (int)threadIdx.x < L ? lse_i * A16_LOG2E : 0.f;
-    sD[threadIdx.x] = (int)threadIdx.x < L ? d_i : 0.f;
+    sLse[threadIdx.x] = (int)threadIdx.x < Lb ? lse_i * A16_LOG2E : 0.f;
+    sD[threadIdx.x] = (int)threadIdx.x < Lb ? d_i : 0.f;
   }
   __syncthreads();
+  if (PACKED && na <= 0) return;  // no live key in this wave's tile (wave-uniform; no barrier follows)
   f32x4 s[A16_MAX_TILES], dp[A16_MAX_TILES];
   A16_SWITCH_SCORES(na, sQ1, kf, s)
   A16_SWITCH_SCORES(na, sG1, vf, dp)
@@ -340,14 +350,14 @@ __device__ __forceinline__ void attention16_bwd_kv_body(const float* __restrict_
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int qi = 16 * t + 4 * g + r;
-        p[r] = (qi < L && (!causal || qi >= k_tok)) ? __builtin_amdgcn_exp2f(s[u][r] * c - l4[r]) : 0.f;
+        p[r] = (qi < Lb && (!causal || qi >= k_tok)) ? __builtin_amdgcn_exp2f(s[u][r] * c - l4[r]) : 0.f;
         ds[r] = p[r] * (dp[u][r] - d4[r]) * 0.125f;
       }
       a16_accum<TP>(sGt, lane, t, p, av);
       a16_accum<TP>(sQt, lane, t, ds, ak);
     }
-  if (k_tok < L) {
-    float* kp = dqkv + ((size_t)b * L + k_tok) * ld + d + h * A16_HD;
+  if (k_tok < Lb) {
+    float* kp = dqkv + (prow + k_tok) * ld + d + h * A16_HD;
     a16_store(kp, ak, 1.f, lane);
     a16_store(kp + d, av, 1.f, lane);
   }
@@ -357,16 +367,17 @@ __device__ __forceinline__ void attention16_bwd_kv_body(const float* __restrict_
 // dispatch order, so the head's q, k, v, dO rows are fetched from HBM once and found in L2 by the other).  Round 2 ran
 // them as two launches with D handed through memory; at the per-rank sizes of the 8-GPU step each was ~15 us of work
 // behind its own launch.
-template <int NT>
+template <int NT, bool PACKED = false>
 __global__ __launch_bounds__(64 * NT) void attention16_bwd_kernel(const float* __restrict__ qkv, const float* __restrict__ dout,
                                                                   const float* __restrict__ out, const float* __restrict__ lse,
-                                                                  float* __restrict__ dqkv, int L, int H, int causal) {
+                                                                  float* __restrict__ dqkv, int L, int H, int causal,
+                                                                  const int32_t* __restrict__ off) {
   extern __shared__ __attribute__((aligned(16))) float a16_smem[];
   const int item = blockIdx.x >> 1;  // = b * H + h
   if (blockIdx.x & 1)
-    attention16_bwd_kv_body<NT>(qkv, dout, out, lse, dqkv, L, H, causal, item, a16_smem);
+    attention16_bwd_kv_body<NT, PACKED>(qkv, dout, out, lse, dqkv, L, H, causal, item, off, a16_smem);
   else
-    attention16_bwd_q_body<NT>(qkv, dout, out, lse, dqkv, L, H, causal, item, a16_smem);
+    attention16_bwd_q_body<NT, PACKED>(qkv, dout, out, lse, dqkv, L, H, causal, item, off, a16_smem);
 }
 
 // ---- host side (called from attention_mfma.hip) -------------------------------------------------------------
@@ -393,18 +404,18 @@ static int a16_fwd(const float* qkv, float* out, float* lse, int batch, int seq,
   return launch_status();
 }
 
-template <int NT>
+template <int NT, bool PACKED = false>
 static int a16_bwd(const float* qkv, const float* dout, const float* out, const float* lse, float* dqkv, float* work,
-                   int batch, int seq, int heads, int causal, hipStream_t st) {
+                   int batch, int seq, int heads, int causal, hipStream_t st, const int32_t* off = nullptr) {
   (void)work;  // D_i no longer travels through memory
   static bool attr = false;
   if (!attr && a16_lds(NT, true) > 48 * 1024) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attention16_bwd_kernel<NT>),
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attention16_bwd_kernel<NT, PACKED>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)a16_lds(NT, true));
     attr = true;
   }
-  hipLaunchKernelGGL(attention16_bwd_kernel<NT>, dim3(2 * batch * heads), dim3(64 * NT), a16_lds(NT, true), st, qkv, dout, out,
-                     lse, dqkv, seq, heads, causal);
+  hipLaunchKernelGGL((attention16_bwd_kernel<NT, PACKED>), dim3(2 * batch * heads), dim3(64 * NT), a16_lds(NT, true), st, qkv,
+                     dout, out, lse, dqkv, seq, heads, causal, off);
   return launch_status();
 }
 
@@ -428,6 +439,19 @@ int attention16_bwd(const float* qkv, const float* dout, const float* out, const
     case 4: return a16_bwd<4>(qkv, dout, out, lse, dqkv, work, batch, seq, heads, causal, st);
     case 5: return a16_bwd<5>(qkv, dout, out, lse, dqkv, work, batch, seq, heads, causal, st);
     default: return a16_bwd<6>(qkv, dout, out, lse, dqkv, work, batch, seq, heads, causal, st);
+  }
+}
+
+// packed (live-row) backward: runtime tile bounds from off[], the launch sized by the full sequence
+int attention16_bwd_packed(const float* qkv, const float* dout, const float* out, const float* lse, float* dqkv,
+                           const int32_t* off, int batch, int seq, int heads, hipStream_t st) {
+  switch ((seq + 15) / 16) {
+    case 1: return a16_bwd<1, true>(qkv, dout, out, lse, dqkv, nullptr, batch, seq, heads, 1, st, off);
+    case 2: return a16_bwd<2, true>(qkv, dout, out, lse, dqkv, nullptr, batch, seq, heads, 1, st, off);
+    case 3: return a16_bwd<3, true>(qkv, dout, out, lse, dqkv, nullptr, batch, seq, heads, 1, st, off);
+    case 4: return a16_bwd<4, true>(qkv, dout, out, lse, dqkv, nullptr, batch, seq, heads, 1, st, off);
+    case 5: return a16_bwd<5, true>(qkv, dout, out, lse, dqkv, nullptr, batch, seq, heads, 1, st, off);
+    default: return a16_bwd<6, true>(qkv, dout, out, lse, dqkv, nullptr, batch, seq, heads, 1, st, off);
   }
 }
 

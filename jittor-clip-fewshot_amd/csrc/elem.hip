@@ -123,6 +123,31 @@ __global__ __launch_bounds__(256) void put_seq_rows_kernel(const float* __restri
   }
 }
 
+// packed rows (the text tower's live-row backward): out[i, :] = src[map[i] * ld + 0..width) and its inverse
+// dst[map[i] * ld + 0..width) = src[i, :]; V = 4 moves float4 (width, ld and both bases 16-byte multiples)
+template <int V>
+__global__ __launch_bounds__(256) void gather_rows_map_kernel(const float* __restrict__ src, size_t ld, const int32_t* __restrict__ map,
+                                                              float* __restrict__ out, int n, int width) {
+  typedef float vec __attribute__((ext_vector_type(V)));
+  const int wv = width / V;
+  const size_t total = (size_t)n * wv;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+    const int k = (int)(i % wv), r = (int)(i / wv);
+    reinterpret_cast<vec*>(out)[i] = *reinterpret_cast<const vec*>(src + (size_t)map[r] * ld + (size_t)k * V);
+  }
+}
+template <int V>
+__global__ __launch_bounds__(256) void put_rows_map_kernel(const float* __restrict__ src, const int32_t* __restrict__ map,
+                                                           float* __restrict__ dst, size_t ld, int n, int width) {
+  typedef float vec __attribute__((ext_vector_type(V)));
+  const int wv = width / V;
+  const size_t total = (size_t)n * wv;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+    const int k = (int)(i % wv), r = (int)(i / wv);
+    *reinterpret_cast<vec*>(dst + (size_t)map[r] * ld + (size_t)k * V) = reinterpret_cast<const vec*>(src)[i];
+  }
+}
+
 // the same two for a tensor stored as f16 (fp16 storage mode: the saved pre-GELU activation); the compact side stays fp32
 __global__ __launch_bounds__(256) void gather_seq_rows_f16_kernel(const _Float16* __restrict__ src, size_t ld,
                                                                   const int32_t* __restrict__ idx, float* __restrict__ out,
@@ -662,6 +687,34 @@ extern "C" int clipfs_put_seq_rows(const float* src, const int32_t* idx, float* 
   CLIPFS_REQUIRE(src && idx && dst && n > 0 && seq > 0 && width > 0 && ld >= (size_t)width, "put_seq_rows: bad args");
   hipLaunchKernelGGL(put_seq_rows_kernel, dim3(grid_for((size_t)n * width)), dim3(256), 0, (hipStream_t)stream, src, idx, dst,
                      ld, n, seq, width);
+  return launch_status();
+}
+
+static inline bool rows_map_vec(const void* a, const void* b, size_t ld, int width) {
+  return (width % 4) == 0 && (ld % 4) == 0 && aligned16(a) && aligned16(b);
+}
+
+extern "C" int clipfs_gather_rows_map(const float* src, size_t ld, const int32_t* map, float* out, int n, int width,
+                                      void* stream) {
+  CLIPFS_REQUIRE(src && map && out && n > 0 && width > 0 && ld >= (size_t)width, "gather_rows_map: bad args");
+  if (rows_map_vec(src, out, ld, width))
+    hipLaunchKernelGGL(gather_rows_map_kernel<4>, dim3(grid_for((size_t)n * width / 4)), dim3(256), 0, (hipStream_t)stream,
+                       src, ld, map, out, n, width);
+  else
+    hipLaunchKernelGGL(gather_rows_map_kernel<1>, dim3(grid_for((size_t)n * width)), dim3(256), 0, (hipStream_t)stream, src,
+                       ld, map, out, n, width);
+  return launch_status();
+}
+
+extern "C" int clipfs_put_rows_map(const float* src, const int32_t* map, float* dst, size_t ld, int n, int width,
+                                   void* stream) {
+  CLIPFS_REQUIRE(src && map && dst && n > 0 && width > 0 && ld >= (size_t)width, "put_rows_map: bad args");
+  if (rows_map_vec(src, dst, ld, width))
+    hipLaunchKernelGGL(put_rows_map_kernel<4>, dim3(grid_for((size_t)n * width / 4)), dim3(256), 0, (hipStream_t)stream, src,
+                       map, dst, ld, n, width);
+  else
+    hipLaunchKernelGGL(put_rows_map_kernel<1>, dim3(grid_for((size_t)n * width)), dim3(256), 0, (hipStream_t)stream, src, map,
+                       dst, ld, n, width);
   return launch_status();
 }
 

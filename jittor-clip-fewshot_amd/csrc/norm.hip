@@ -168,19 +168,23 @@ __global__ __launch_bounds__(256) void layernorm_fwd_lora_kernel(const float* x,
   }
 }
 
+// MAP: x, mean and rstd are read at row xmap[row] (the packed text backward reads the saved full-layout tensors in place)
+template <bool MAP = false>
 __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ x,
                                                             int ldx, const float* __restrict__ gamma,
                                                             const float* __restrict__ mean_in,
                                                             const float* __restrict__ rstd_in,
                                                             const float* dres, float* dx,  // may alias (in-place residual add)
                                                             int lddx, int rows, int width,
-                                                            _Float16* __restrict__ dx16 = nullptr) {  // optional f16 copy [rows, width]
+                                                            _Float16* __restrict__ dx16 = nullptr,  // optional f16 copy [rows, width]
+                                                            const int32_t* __restrict__ xmap = nullptr) {
   const int lane = threadIdx.x & 63;
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= rows) return;
   const int nch = width >> 2;
-  const float mean = mean_in[row], rstd = rstd_in[row];
-  const float4* xr = reinterpret_cast<const float4*>(x + (size_t)row * ldx);
+  const size_t xrow = MAP ? (size_t)xmap[row] : (size_t)row;
+  const float mean = mean_in[xrow], rstd = rstd_in[xrow];
+  const float4* xr = reinterpret_cast<const float4*>(x + xrow * ldx);
   const float4* dyr = reinterpret_cast<const float4*>(dy + (size_t)row * width);
   const float4* g4 = reinterpret_cast<const float4*>(gamma);
   float4 xh[LN_MAX_CHUNKS], gd[LN_MAX_CHUNKS];
@@ -313,8 +317,21 @@ extern "C" int clipfs_layernorm_bwd(const float* dy, const float* x, int ldx, co
   CLIPFS_REQUIRE(ldx >= width && (ldx & 3) == 0 && lddx >= width && (lddx & 3) == 0 && aligned16(x) && aligned16(dy) &&
                      aligned16(dx) && aligned16(gamma) && (!dres || aligned16(dres)),
                  "layernorm_bwd: alignment");
-  hipLaunchKernelGGL(layernorm_bwd_kernel, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, dy, x, ldx, gamma,
+  hipLaunchKernelGGL(layernorm_bwd_kernel<false>, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, dy, x, ldx, gamma,
                      mean, rstd, dres, dx, lddx, rows, width);
+  return launch_status();
+}
+
+extern "C" int clipfs_layernorm_bwd_rows(const float* dy, const float* x, int ldx, const float* gamma, const float* mean,
+                                         const float* rstd, const int32_t* xmap, const float* dres, float* dx, int lddx,
+                                         int rows, int width, void* stream) {
+  CLIPFS_CHECK(check_rows("layernorm_bwd_rows", rows, width));
+  CLIPFS_REQUIRE(dy && x && gamma && mean && rstd && xmap && dx, "layernorm_bwd_rows: null pointer");
+  CLIPFS_REQUIRE(ldx >= width && (ldx & 3) == 0 && lddx >= width && (lddx & 3) == 0 && aligned16(x) && aligned16(dy) &&
+                     aligned16(dx) && aligned16(gamma) && (!dres || aligned16(dres)),
+                 "layernorm_bwd_rows: alignment");
+  hipLaunchKernelGGL(layernorm_bwd_kernel<true>, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, dy, x, ldx, gamma,
+                     mean, rstd, dres, dx, lddx, rows, width, nullptr, xmap);
   return launch_status();
 }
 
@@ -358,7 +375,7 @@ extern "C" int clipfs_layernorm_bwd_f16(const float* dy, const float* x, int ldx
   CLIPFS_REQUIRE(ldx >= width && (ldx & 3) == 0 && lddx >= width && (lddx & 3) == 0 && aligned16(x) && aligned16(dy) &&
                      aligned16(dx) && aligned16(gamma) && (!dres || aligned16(dres)) && (!dx16 || aligned16(dx16)),
                  "layernorm_bwd_f16: alignment");
-  hipLaunchKernelGGL(layernorm_bwd_kernel, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, dy, x, ldx, gamma,
+  hipLaunchKernelGGL(layernorm_bwd_kernel<false>, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, dy, x, ldx, gamma,
                      mean, rstd, dres, dx, lddx, rows, width, reinterpret_cast<_Float16*>(dx16));
   return launch_status();
 }

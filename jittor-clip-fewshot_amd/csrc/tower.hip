@@ -515,14 +515,150 @@ extern "C" int clipfs_tower_bwd(const clipfs_tower* t, float* dx, int batch, con
   return tower_bwd_range(t, dx, batch, saved, scratch, stop_at_input, (hipStream_t)stream, t->layers - 1);
 }
 
-extern "C" int clipfs_tower_bwd_sparse(const clipfs_tower* t, const float* dxs, const int32_t* rows, float* dx, int batch,
-                                       const float* saved, float* scratch, int stop_at_input, void* stream) {
-  CLIPFS_CHECK(check_tower(t, batch));
-  CLIPFS_REQUIRE(t->grad_lo == 0 || stop_at_input,
-                 "tower_bwd_sparse: grad_lo %d > 0 needs stop_at_input (the input gradient runs through every block)",
-                 t->grad_lo);
-  CLIPFS_REQUIRE(dxs && rows && dx && saved && scratch, "tower_bwd_sparse: null buffer");
-  hipStream_t st = (hipStream_t)stream;
+// ---- packed (live-row) backward of a causal tower ------------------------------------------------------------------
+// Sequence c carries gradient on its rows c*seq + 0 .. eot_c only (the head reads its EOT row and a row never attends to a
+// later one): below the last block's compact part every operation runs on the R = sum (eot_c + 1) live rows, packed
+// caption after caption.  plan (int32, device): off[0 .. batch] (exclusive prefix sum of eot_c + 1, off[batch] = R),
+// eotp[0 .. batch) = off[c + 1] - 1 (packed row of each EOT), map[0 .. R) = c * seq + p (full-layout row of packed row i).
+// The saved per-row tensors a block's GEMM epilogue and adapter backward read (u, h1, t_qkv, keep bits; att / t_o for an
+// o-projection adapter) are gathered into packed scratch; the LayerNorm backward reads x and its statistics in place
+// through the row map (clipfs_layernorm_bwd_rows).
+struct PackPlan {
+  const int32_t* off;
+  const int32_t* eotp;
+  const int32_t* map;
+  int R;
+};
+
+static bool pack_dropout_ok(const clipfs_tower* t) {
+  // the adapter backward must not evaluate Philox on packed rows (it would index the masks by the packed row): with
+  // dropout active the q/k/v masks come from the saved keep bits, and the o-projection adapter has none
+  const bool drop = t->lora_r > 0 && t->lora_dropout > 0.f && t->dropout_seed != 0;
+  if (!drop) return true;
+  for (int l = t->grad_lo; l < t->layers; ++l) {
+    const clipfs_block& b = t->blocks[l];
+    if (b.lora_a_o && (b.lora_mask & 8u)) return false;
+    if (b.lora_a_qkv && (b.lora_mask & 7u) && !keep_bits_saved(t)) return false;
+  }
+  return true;
+}
+
+// Packing runs only where its buffers fit the existing scratch slots (R <= M / 2, see tower_bwd_packed_range), its
+// kernels exist and the tower is large enough to gain; everything else takes the dense path of clipfs_tower_bwd_sparse, so the scratch size does not change.
+// Below kPackMinRows dense rows the text backward is launch-bound (a few captions: tens of microseconds per block) and
+// the per-block gathers would cost what the smaller products save; such towers keep the dense rows and their arithmetic.
+constexpr int kPackMinRows = 2048;
+
+static bool pack_ok(const clipfs_tower* t, int batch, int R) {
+  const int M = batch * t->seq, d = t->width, r = t->lora_r;
+  if (M < kPackMinRows) return false;
+  if (!t->causal || t->weight_format == 2 || !last_block_rows_ok(t)) return false;
+  if (!clipfs_attention_bwd_packed_ok(t->seq, 1)) return false;
+  if (R < batch || 2 * (size_t)R > (size_t)M || (d % 8) != 0) return false;
+  if (!pack_dropout_ok(t)) return false;
+  const ScratchLayout SC = scratch_layout(t, (size_t)M);
+  if (r > 0) {
+    const size_t need = al4(clipfs_lora_bwd_work_floats(R, d, r, 3));
+    if (need > SC.gemm_ws - SC.work) return false;  // the slice count is not monotone in the rows
+  }
+  if (tower_has_bias_slots(t)) {
+    const int widths[3] = {d, 3 * d, 4 * d};
+    for (int i = 0; i < 3; ++i)
+      if (clipfs_bias_grad_work_floats(R, widths[i]) > SC.total - SC.bwork) return false;
+  }
+  return true;
+}
+
+// blocks l_hi ... grad_lo on the packed rows.  On entry dx_p (scratch b1, second half) holds the packed gradient wrt
+// block l_hi's output -- or, with attn_only_top, wrt its attention residual, datt_p (b1, first half) the gradient wrt its
+// attention output.  Slots (R <= M / 2): b1 = datt_p | dx_p; big = du_p | u_p in the MLP part, then the gathered
+// h1 / t_qkv / keep bits (/ att / t_o); b3 = dqkv_p; h = dh_p.
+static int tower_bwd_packed_range(const clipfs_tower* t, float* dx, int batch, const PackPlan& P, const float* saved,
+                                  float* scratch, int stop_at_input, hipStream_t st, int l_hi, bool attn_only_top) {
+  const int M = batch * t->seq, d = t->width, r = t->lora_r, R = P.R;
+  const SavedLayout SL = saved_layout(t, (size_t)M);
+  const ScratchLayout SC = scratch_layout(t, (size_t)M);
+  const TowerCtx cx = make_ctx(t, scratch, SC);
+  const size_t Rd = (size_t)R * d;
+  float* datt_p = scratch + SC.b1;
+  float* dx_p = datt_p + al4(Rd);
+  float* dh_p = scratch + SC.h;
+  float* du_p = scratch + SC.big;
+  float* u_p = du_p + 4 * Rd;
+  float* dqkv_p = scratch + SC.b3;
+  float* h1_p = scratch + SC.big;
+  float* tq_p = h1_p + al4(Rd);
+  float* keep_p = tq_p + al4((size_t)R * 3 * r);
+  float* att_p = keep_p + al4((size_t)R * d / 8);
+  float* to_p = att_p + al4(Rd);
+  float* dt = scratch + SC.dt;
+  float* work = scratch + SC.work;
+  float* bwork = scratch + SC.bwork;
+  const int lo = t->grad_lo;
+  for (int l = l_hi; l >= lo; --l) {
+    const clipfs_block& b = t->blocks[l];
+    const float* sv = saved + (size_t)(l - lo) * SL.total;
+    CLIPFS_REQUIRE(b.w_pr_t && b.w_fc_t && b.w_o_t && b.w_qkv_t, "tower_bwd: block %d lacks transposed weights", l);
+    const unsigned qkv_mask = b.lora_a_qkv ? (b.lora_mask & 7u) : 0u;
+    const bool lora_o = b.lora_a_o && (b.lora_mask & 8u);
+    const uint32_t ds = t->dropout_stream0 + 4u * (uint32_t)l;
+    if (!(attn_only_top && l == l_hi)) {
+      // MLP and output projection, as in tower_bwd_range
+      CLIPFS_CHECK(bias_sum(dx_p, R, d, d, b.g_b_pr, nullptr, nullptr, bwork, st));
+      CLIPFS_CHECK(clipfs_gather_rows_map(sv + SL.u, (size_t)4 * d, P.map, u_p, R, 4 * d, st));
+      CLIPFS_CHECK(gemm(cx, dx_p, b.w_pr_t, b.w_pr_t_p, du_p, R, 4 * d, d, nullptr, nullptr, 2, nullptr, u_p, nullptr, nullptr, 0, 0,
+                        0, 0.f, st));
+      CLIPFS_CHECK(bias_sum(du_p, R, 4 * d, 4 * d, b.g_b_fc, nullptr, nullptr, bwork, st));
+      CLIPFS_CHECK(gemm(cx, du_p, b.w_fc_t, b.w_fc_t_p, dh_p, R, d, 4 * d, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, 0,
+                        0, 0, 0.f, st));
+      CLIPFS_CHECK(bias_sum(dh_p, R, d, d, b.g_ln2_b, nullptr, nullptr, bwork, st));
+      CLIPFS_CHECK(clipfs_layernorm_bwd_rows(dh_p, sv + SL.x_mid, d, b.ln2_g, sv + SL.stat2, sv + SL.stat2 + M, P.map, dx_p,
+                                             dx_p, d, R, d, st));
+      CLIPFS_CHECK(bias_sum(dx_p, R, d, d, b.g_b_o, nullptr, nullptr, bwork, st));
+      CLIPFS_CHECK(gemm(cx, dx_p, b.w_o_t, b.w_o_t_p, datt_p, R, d, d, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, 0, 0,
+                        0, 0.f, st));
+      if (lora_o) {  // no dropout here (pack_dropout_ok): the adapter backward evaluates no mask
+        CLIPFS_CHECK(clipfs_gather_rows_map(sv + SL.att, (size_t)d, P.map, att_p, R, d, st));
+        CLIPFS_CHECK(clipfs_gather_rows_map(sv + SL.t_o, (size_t)r, P.map, to_p, R, r, st));
+        CLIPFS_CHECK(lora_bwd_block(t, false, dx_p, nullptr, att_p, to_p, b.lora_a_o, b.lora_b_o, dt, b.g_lora_a_o,
+                                    b.g_lora_b_o, datt_p, R, 1, 1u, ds + 3, nullptr, work, st, l));
+      }
+    }
+    // attention (full-layout q/k/v, O, lse; packed dO and dqkv) and the QKV projection
+    CLIPFS_CHECK(clipfs_attention_bwd_packed(sv + SL.qkv, datt_p, sv + SL.att, sv + SL.lse, dqkv_p, P.off, batch, t->seq,
+                                             t->heads, st));
+    CLIPFS_CHECK(bias_sum(dqkv_p, R, 3 * d, d, b.g_b_q, b.g_b_k, b.g_b_v, bwork, st));
+    const bool need_dx = !(l == lo && stop_at_input);
+    const bool need_dh = need_dx || b.g_ln1_b;
+    if (need_dh)
+      CLIPFS_CHECK(gemm(cx, dqkv_p, b.w_qkv_t, b.w_qkv_t_p, dh_p, R, d, 3 * d, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr,
+                        0, 0, 0, 0.f, st));
+    if (qkv_mask && (b.g_lora_a_qkv || need_dh)) {
+      const bool keep = keep_bits_saved(t);
+      CLIPFS_CHECK(clipfs_gather_rows_map(sv + SL.h1, (size_t)d, P.map, h1_p, R, d, st));
+      CLIPFS_CHECK(clipfs_gather_rows_map(sv + SL.t_qkv, (size_t)3 * r, P.map, tq_p, R, 3 * r, st));
+      if (keep)  // uint16 per float4 of h1: d / 8 floats per row
+        CLIPFS_CHECK(clipfs_gather_rows_map(sv + SL.keep, (size_t)d / 8, P.map, keep_p, R, d / 8, st));
+      CLIPFS_CHECK(lora_bwd_block(t, false, dqkv_p, nullptr, h1_p, tq_p, b.lora_a_qkv, b.lora_b_qkv, dt, b.g_lora_a_qkv,
+                                  b.g_lora_b_qkv, need_dh ? dh_p : nullptr, R, 3, qkv_mask, ds,
+                                  keep ? (const void*)keep_p : nullptr, work, st, l));
+    }
+    CLIPFS_CHECK(bias_sum(dh_p, R, d, d, b.g_ln1_b, nullptr, nullptr, bwork, st));
+    if (need_dx) {
+      CLIPFS_CHECK(clipfs_layernorm_bwd_rows(dh_p, sv + SL.x_in, d, b.ln1_g, sv + SL.stat1, sv + SL.stat1 + M, P.map, dx_p,
+                                             dx_p, d, R, d, st));
+    }
+  }
+  if (stop_at_input) return CLIPFS_OK;
+  // the gradient wrt the tower input in the full layout: the dead rows are exact zeros
+  hipError_t e = hipMemsetAsync(dx, 0, (size_t)M * d * sizeof(float), st);
+  CLIPFS_REQUIRE(e == hipSuccess, "tower_bwd_packed: memset failed: %s", hipGetErrorString(e));
+  return clipfs_put_rows_map(dx_p, P.map, dx, (size_t)d, R, d, st);
+}
+
+// the last block's compact part, then (P != NULL) the packed or (P == NULL) the dense rows below it
+static int tower_bwd_sparse_impl(const clipfs_tower* t, const float* dxs, const int32_t* rows, float* dx, int batch,
+                                 const float* saved, float* scratch, int stop_at_input, hipStream_t st, const PackPlan* P) {
   const int seq = t->seq, M = batch * seq, d = t->width, r = t->lora_r, Ms = batch;
   const SavedLayout SL = saved_layout(t, (size_t)M);
   const ScratchLayout SC = scratch_layout(t, (size_t)M);
@@ -571,6 +707,17 @@ extern "C" int clipfs_tower_bwd_sparse(const clipfs_tower* t, const float* dxs, 
   CLIPFS_CHECK(bias_sum(dxm_s, Ms, d, d, b.g_b_o, nullptr, nullptr, bwork, st));
   CLIPFS_CHECK(gemm(cx, dxm_s, b.w_o_t, f16m ? nullptr : b.w_o_t_p, datt_s, Ms, d, d, nullptr, nullptr, 0, nullptr, nullptr, nullptr,
                     nullptr, 0, 0, 0, 0.f, st));
+  if (P) {
+    // packed: datt_p and dx_p (the residual around the attention) are zero except at the EOT rows.  Put before the
+    // packed range gathers anything into the MLP scratch that holds datt_s / dxm_s.
+    float* datt_p = scratch + SC.b1;
+    const size_t Rd = (size_t)P->R * d;
+    hipError_t e = hipMemsetAsync(datt_p, 0, (al4(Rd) + Rd) * sizeof(float), st);
+    CLIPFS_REQUIRE(e == hipSuccess, "tower_bwd_packed: memset failed: %s", hipGetErrorString(e));
+    CLIPFS_CHECK(clipfs_put_rows_map(datt_s, P->eotp, datt_p, (size_t)d, Ms, d, st));
+    CLIPFS_CHECK(clipfs_put_rows_map(dxm_s, P->eotp, datt_p + al4(Rd), (size_t)d, Ms, d, st));
+    return tower_bwd_packed_range(t, dx, batch, *P, saved, scratch, stop_at_input, st, l, true);
+  }
   // ---- attention and the QKV projection see every row again ----
   float* dh = scratch + SC.h;
   float* datt = scratch + SC.b1;
@@ -604,4 +751,37 @@ extern "C" int clipfs_tower_bwd_sparse(const clipfs_tower* t, const float* dxs, 
   CLIPFS_CHECK(clipfs_layernorm_bwd(dh, sv + SL.x_in, d, b.ln1_g, sv + SL.stat1, sv + SL.stat1 + M, nullptr, dx, d, M, d, st));
   CLIPFS_CHECK(clipfs_add_seq_rows(dxm_s, rows, dx, batch, seq, d, st));  // the residual branch around the attention
   return tower_bwd_range(t, dx, batch, saved, scratch, stop_at_input, st, l - 1);
+}
+
+extern "C" int clipfs_tower_bwd_sparse(const clipfs_tower* t, const float* dxs, const int32_t* rows, float* dx, int batch,
+                                       const float* saved, float* scratch, int stop_at_input, void* stream) {
+  CLIPFS_CHECK(check_tower(t, batch));
+  CLIPFS_REQUIRE(t->grad_lo == 0 || stop_at_input,
+                 "tower_bwd_sparse: grad_lo %d > 0 needs stop_at_input (the input gradient runs through every block)",
+                 t->grad_lo);
+  CLIPFS_REQUIRE(dxs && rows && dx && saved && scratch, "tower_bwd_sparse: null buffer");
+  return tower_bwd_sparse_impl(t, dxs, rows, dx, batch, saved, scratch, stop_at_input, (hipStream_t)stream, nullptr);
+}
+
+extern "C" int clipfs_tower_pack_mode(const clipfs_tower* t, int batch, int R) {
+  if (!t || !t->blocks || t->struct_size != sizeof(clipfs_tower) || t->block_size != sizeof(clipfs_block)) return 0;
+  if (batch <= 0 || t->layers <= 0 || t->seq <= 0 || t->grad_lo < 0 || t->grad_lo >= t->layers) return 0;
+  return pack_ok(t, batch, R) ? 1 : 0;
+}
+
+extern "C" int clipfs_tower_bwd_packed(const clipfs_tower* t, const float* dxs, const int32_t* rows, const int32_t* plan,
+                                       int R, float* dx, int batch, const float* saved, float* scratch, int stop_at_input,
+                                       void* stream) {
+  CLIPFS_CHECK(check_tower(t, batch));
+  CLIPFS_REQUIRE(t->grad_lo == 0 || stop_at_input,
+                 "tower_bwd_packed: grad_lo %d > 0 needs stop_at_input (the input gradient runs through every block)",
+                 t->grad_lo);
+  CLIPFS_REQUIRE(dxs && rows && plan && dx && saved && scratch, "tower_bwd_packed: null buffer");
+  CLIPFS_REQUIRE(R >= batch && (size_t)R <= (size_t)batch * t->seq, "tower_bwd_packed: R %d outside [batch %d, batch*seq %zu]",
+                 R, batch, (size_t)batch * t->seq);
+  hipStream_t st = (hipStream_t)stream;
+  if (!pack_ok(t, batch, R))  // the dense rows (clipfs_tower_pack_mode says which)
+    return tower_bwd_sparse_impl(t, dxs, rows, dx, batch, saved, scratch, stop_at_input, st, nullptr);
+  const PackPlan P = {plan, plan + batch + 1, plan + 2 * (size_t)batch + 1, R};
+  return tower_bwd_sparse_impl(t, dxs, rows, dx, batch, saved, scratch, stop_at_input, st, &P);
 }
