@@ -173,6 +173,12 @@ int clipfs_layernorm_fwd_lora(const float* x, int ldx, const float* gamma, const
                               float* mean, float* rstd, int rows, int width, float eps, const float* A, float* t, int r,
                               int nseg, unsigned seg_mask, float p, uint64_t seed, uint32_t stream_base, uint32_t drow0,
                               void* keep_bits, void* stream);
+/* The same with the dropout masks of row i drawn at row drow0 + drow_map[i] (int32, device, [rows]): the live-row text
+ * forward runs packed rows and draws the masks (and records the keep bits) of their full-layout rows. */
+int clipfs_layernorm_fwd_lora_map(const float* x, int ldx, const float* gamma, const float* beta, float* y, void* y16,
+                                  float* mean, float* rstd, int rows, int width, float eps, const float* A, float* t, int r,
+                                  int nseg, unsigned seg_mask, float p, uint64_t seed, uint32_t stream_base, uint32_t drow0,
+                                  const int32_t* drow_map, void* keep_bits, void* stream);
 
 /* ------------------------------------------------------------- attention --
  * qkv [B*L, 3*d] (q | k | v, head h at columns h*64..), out [B*L, d] heads merged.
@@ -201,6 +207,14 @@ size_t clipfs_attention_lse_floats(int batch, int seq, int heads);
 int clipfs_attention_bwd_packed_ok(int seq, int causal);
 int clipfs_attention_bwd_packed(const float* qkv, const float* dout, const float* out, const float* lse, float* dqkv,
                                 const int32_t* off, int batch, int seq, int heads, void* stream);
+/* The live-row causal forward on the same kernels (clipfs_attention_bwd_packed_ok): qkv [off[batch], 3 d] and out
+ * [off[batch], d] packed, lse (may be NULL) in its [batch * heads][seq] layout with entries past Lb left unwritten.  Each
+ * live row gets bitwise the values of the full-layout clipfs_attention_fwd (a dead key gets weight 0 from a live query).
+ * The backward over what it wrote: clipfs_attention_bwd_packed_io, which also reads qkv and out packed. */
+int clipfs_attention_fwd_packed(const float* qkv, float* out, float* lse, const int32_t* off, int batch, int seq, int heads,
+                                void* stream);
+int clipfs_attention_bwd_packed_io(const float* qkv, const float* dout, const float* out, const float* lse, float* dqkv,
+                                   const int32_t* off, int batch, int seq, int heads, void* stream);
 /* fp16 storage mode (cfg-5), seq <= 288: the same function with both contractions on
  * v_mfma_f32_32x32x16_f16 (operands rounded to f16 in the staging path; softmax statistics, accumulators and
  * outputs fp32).  lse as above (may be NULL when no backward follows). */
@@ -492,6 +506,22 @@ int clipfs_tower_bwd_sparse(const clipfs_tower* t, const float* dxs, const int32
 int clipfs_tower_pack_mode(const clipfs_tower* t, int batch, int R);
 int clipfs_tower_bwd_packed(const clipfs_tower* t, const float* dxs, const int32_t* rows, const int32_t* plan, int R,
                             float* dx, int batch, const float* saved, float* scratch, int stop_at_input, void* stream);
+/* The FORWARD on the live rows (same plan and rows): every block runs its LayerNorms, adapters, GEMMs and attention on the
+ * R packed rows, the last block's compact part on the EOT rows; on return x holds the tower output at the rows
+ * c*seq + rows[c] (as clipfs_tower_fwd_rows; the other rows of x are unspecified).  Live rows get bitwise the dense
+ * forward's values, dropout masks and keep bits included.  `saved` (NULL: no-grad) keeps R rows per block inside the
+ * clipfs_tower_saved_floats buffer; its backward is clipfs_tower_bwd_packed_saved.  Runs clipfs_tower_fwd_rows instead
+ * (and the backward is then clipfs_tower_bwd_packed) when clipfs_tower_pack_fwd_mode(t, batch, R) == 0: whenever
+ * clipfs_tower_pack_mode is 0, outside the exact fp32 mode, where a dense GEMM of the tower's shapes would run split-K or
+ * stream-K at batch*seq rows (an unsplit R-row launch would sum in another order), or with LoRA dropout on an
+ * o-projection adapter or on a rank the fused LayerNorm + down-projection does not cover. */
+int clipfs_tower_pack_fwd_mode(const clipfs_tower* t, int batch, int R);
+int clipfs_tower_fwd_packed(const clipfs_tower* t, float* x, const int32_t* rows, const int32_t* plan, int R, int batch,
+                            float* saved, float* scratch, void* stream);
+/* clipfs_tower_bwd_packed over the saved tensors of clipfs_tower_fwd_packed (read in place: no gathers).  Same results
+ * as clipfs_tower_bwd_packed after clipfs_tower_fwd_rows; CLIPFS_EINVAL where clipfs_tower_pack_fwd_mode is 0. */
+int clipfs_tower_bwd_packed_saved(const clipfs_tower* t, const float* dxs, const int32_t* rows, const int32_t* plan, int R,
+                                  float* dx, int batch, const float* saved, float* scratch, int stop_at_input, void* stream);
 
 #ifdef __cplusplus
 }

@@ -157,6 +157,13 @@ SIGNATURES = {
     "clipfs_layernorm_bwd_rows": (_i, [_p, _p, _i, _p, _p, _p, _p, _p, _p, _i, _i, _i, _p]),
     "clipfs_tower_pack_mode": (_i, [C.POINTER(Tower), _i, _i]),
     "clipfs_tower_bwd_packed": (_i, [C.POINTER(Tower), _p, _p, _p, _i, _p, _i, _p, _p, _i, _p]),
+    "clipfs_layernorm_fwd_lora_map": (_i, [_p, _i, _p, _p, _p, _p, _p, _p, _i, _i, _f, _p, _p, _i, _i, _u, _f, _u64, _u32, _u32, _p,
+                                           _p, _p]),
+    "clipfs_attention_fwd_packed": (_i, [_p, _p, _p, _p, _i, _i, _i, _p]),
+    "clipfs_attention_bwd_packed_io": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _p]),
+    "clipfs_tower_pack_fwd_mode": (_i, [C.POINTER(Tower), _i, _i]),
+    "clipfs_tower_fwd_packed": (_i, [C.POINTER(Tower), _p, _p, _p, _i, _i, _p, _p, _p]),
+    "clipfs_tower_bwd_packed_saved": (_i, [C.POINTER(Tower), _p, _p, _p, _i, _p, _i, _p, _p, _i, _p]),
 }
 
 def new_gemm_args() -> GemmArgs:

@@ -225,14 +225,18 @@ class _TowerRT:
         t.gemm_counters, t.gemm_counters_ints = buf.data_ptr(), buf.numel()
 
     def forward(self, x: torch.Tensor, batch: int, train: bool, seed: int, seq: Optional[int] = None,
-                own_saved: bool = False, row0: int = 0, rows: Optional[torch.Tensor] = None, grad_lo: int = 0):
+                own_saved: bool = False, row0: int = 0, rows: Optional[torch.Tensor] = None, grad_lo: int = 0,
+                pack: Optional[Tuple[torch.Tensor, int]] = None, desc: Optional[Tower] = None):
         """``train`` = keep the activations the backward needs.  ``own_saved``: give this call its OWN saved-activation
         tensor (the autograd route: several grad-enabled forwards of one tower may precede one backward, e.g. the 13
         caption chunks of encode_text_in_batches, lora_train_vlp.py:905-912); otherwise the per-tower cached buffer
         is reused (LoRATrainer: exactly one forward per backward).  ``grad_lo``: the gradient floor (``grad_floor``);
-        only blocks grad_lo ... top keep activations, and the backward must be given the same floor."""
+        only blocks grad_lo ... top keep activations, and the backward must be given the same floor.  ``pack``: (plan, R)
+        of ``Engine._pack_plan`` with ``rows``: every block runs on the live rows (clipfs_tower_fwd_packed; the caller
+        checked ``pack_fwd_mode``), and the backward is ``backward_packed(..., saved_packed=True)``.  ``desc``: this
+        call's descriptor when the caller already built it (the same arguments)."""
         lib = _lib.load()
-        t = self.descriptor(train, seed, seq, row0, grad_lo if train else 0)
+        t = desc if desc is not None else self.descriptor(train, seed, seq, row0, grad_lo if train else 0)
         self._attach_counters(t, batch, x.device)
         scratch = self.buffer("scratch", lib.clipfs_tower_scratch_floats(C.byref(t), batch), x.device)
         saved = None
@@ -244,6 +248,12 @@ class _TowerRT:
             # the caller reads one row per sequence (``rows`` [batch] int32): the last block's output projection and MLP
             # run on those rows only; the matching backward is ``backward_sparse`` with the same rows
             assert rows.dtype == torch.int32 and rows.is_cuda and rows.numel() >= batch
+        if pack is not None:
+            assert rows is not None
+            plan, R = pack
+            check(lib.clipfs_tower_fwd_packed(C.byref(t), x.data_ptr(), rows.data_ptr(), plan.data_ptr(), R, batch, _ptr(saved),
+                                              scratch.data_ptr(), torch.cuda.current_stream().cuda_stream), "tower_fwd_packed")
+        elif rows is not None:
             check(lib.clipfs_tower_fwd_rows(C.byref(t), x.data_ptr(), rows.data_ptr(), batch, _ptr(saved), scratch.data_ptr(),
                                             torch.cuda.current_stream().cuda_stream), "tower_fwd_rows")
         else:
@@ -278,23 +288,38 @@ class _TowerRT:
 
     def backward_packed(self, dxs: torch.Tensor, rows: torch.Tensor, plan: torch.Tensor, R: int, batch: int,
                         saved: torch.Tensor, seed: int, stop_at_input: bool, seq: Optional[int] = None, row0: int = 0,
-                        grad_lo: int = 0) -> torch.Tensor:
+                        grad_lo: int = 0, saved_packed: bool = False) -> torch.Tensor:
         """``backward_sparse`` of a causal tower on its live rows only (clipfs_tower_bwd_packed; ``plan`` / ``R`` from
-        ``Engine._pack_plan``).  Same return value; runs the dense rows where the library does not pack."""
+        ``Engine._pack_plan``).  Same return value; runs the dense rows where the library does not pack.
+        ``saved_packed``: ``saved`` is the live-row forward's (clipfs_tower_bwd_packed_saved)."""
         lib = _lib.load()
         t = self.descriptor(True, seed, seq, row0, grad_lo)
         self._attach_counters(t, batch, dxs.device)
         scratch = self.buffer("scratch", lib.clipfs_tower_scratch_floats(C.byref(t), batch), dxs.device)
         dx = torch.empty(batch * (seq or self.seq), self.width, device=dxs.device, dtype=torch.float32)
-        check(lib.clipfs_tower_bwd_packed(C.byref(t), dxs.data_ptr(), rows.data_ptr(), plan.data_ptr(), R, dx.data_ptr(), batch,
-                                          saved.data_ptr(), scratch.data_ptr(), int(stop_at_input),
-                                          torch.cuda.current_stream().cuda_stream), "tower_bwd_packed")
+        fn = lib.clipfs_tower_bwd_packed_saved if saved_packed else lib.clipfs_tower_bwd_packed
+        check(fn(C.byref(t), dxs.data_ptr(), rows.data_ptr(), plan.data_ptr(), R, dx.data_ptr(), batch, saved.data_ptr(),
+                 scratch.data_ptr(), int(stop_at_input), torch.cuda.current_stream().cuda_stream),
+              "tower_bwd_packed_saved" if saved_packed else "tower_bwd_packed")
         return dx
 
-    def pack_mode(self, batch: int, R: int, seed: int, seq: Optional[int] = None, grad_lo: int = 0) -> bool:
+    def pack_mode(self, batch: int, R: int, seed: int, seq: Optional[int] = None, grad_lo: int = 0,
+                  train: bool = True) -> bool:
         """Whether ``backward_packed`` runs packed for this geometry (clipfs_tower_pack_mode)."""
-        t = self.descriptor(True, seed, seq, 0, grad_lo)
+        t = self.descriptor(train, seed, seq, 0, grad_lo)
         return bool(_lib.load().clipfs_tower_pack_mode(C.byref(t), batch, R))
+
+    @staticmethod
+    def pack_modes(desc: Tower, batch: int, R: int) -> Tuple[bool, bool]:
+        """(clipfs_tower_pack_mode, clipfs_tower_pack_fwd_mode) for an already built descriptor."""
+        lib = _lib.load()
+        return bool(lib.clipfs_tower_pack_mode(C.byref(desc), batch, R)), bool(lib.clipfs_tower_pack_fwd_mode(C.byref(desc), batch, R))
+
+    def pack_fwd_mode(self, batch: int, R: int, seed: int, seq: Optional[int] = None, grad_lo: int = 0,
+                      train: bool = True) -> bool:
+        """Whether ``forward(..., pack=...)`` runs on the live rows for this geometry (clipfs_tower_pack_fwd_mode)."""
+        t = self.descriptor(train, seed, seq, 0, grad_lo)
+        return bool(_lib.load().clipfs_tower_pack_fwd_mode(C.byref(t), batch, R))
 
 
 class Engine:
@@ -331,6 +356,12 @@ class Engine:
         # one-row path only (``sparse_backward``).  Loss and logits are unchanged; parameter gradients differ only in
         # summation order.  False = every row of every block (the A/B reference).
         self.pack_text_backward = True
+        # Text FORWARD on the same live rows (clipfs_tower_fwd_packed): row i of a causal block reads rows <= i only, so
+        # every block runs on the R packed rows and the last block's compact part on the EOT rows; the backward then reads
+        # the packed saved tensors in place.  Applies where the backward packs (needs ``pack_text_backward``) and the
+        # library's clipfs_tower_pack_fwd_mode agrees, in training and in no-grad forwards alike.  Every feature, dropout
+        # mask and gradient is bitwise that of the dense forward.  False = the dense forward (the A/B reference).
+        self.pack_text_forward = True
         self._pack_cache = {}
 
     @property
@@ -484,7 +515,9 @@ class Engine:
             rows = cap * seq + torch.arange(R, device=src.device) - off[cap]
             plan = torch.cat([off, off[1:] - 1, rows]).to(device=ids.device, dtype=torch.int32)
             hit = (plan, R, ids)
-            self._pack_cache = {key: hit}
+            if len(self._pack_cache) >= 4:  # a few tables (training captions, eval captions) without rebuilding
+                self._pack_cache.pop(next(iter(self._pack_cache)))
+            self._pack_cache[key] = hit
         return hit[0], hit[1]
 
     def text_forward(self, ids: torch.Tensor, prompt_ctx: Optional[torch.Tensor], train: bool, seed: int = 0,
@@ -505,8 +538,20 @@ class Engine:
                            None if prompt_ctx is None else prompt_ctx.data)
         # only the EOT row of each caption is read below (jclip/model.py:213-214)
         one_row = bool(self.sparse_backward)
+        # live rows (clipfs_tower_bwd_packed / clipfs_tower_fwd_packed): the plan is cached per caption table, so a
+        # steady-state step builds nothing; the first check at R = n skips the plan for geometries that never pack
+        # (one descriptor serves the checks and the forward)
+        desc = self.txt.descriptor(train, seed, seq, row0, lo if train else 0)
+        pack, pack_fwd = None, False
+        if one_row and self.pack_text_backward and self.txt.pack_modes(desc, n, n)[0]:
+            plan, R = self._pack_plan(ids, ids_host)
+            bwd, fwd = self.txt.pack_modes(desc, n, R)
+            if bwd:
+                pack = (plan, R)
+                pack_fwd = self.pack_text_forward and fwd
         saved = self.txt.forward(x, n, train, seed, seq, own_saved=own_saved, row0=row0,
-                                 rows=ops.eot_index(ids) if one_row else None, grad_lo=lo)
+                                 rows=ops.eot_index(ids) if one_row else None, grad_lo=lo,
+                                 pack=pack if pack_fwd else None, desc=desc)
         rows, idx = ops.gather_eot(x, ids)
         if train:
             y, mean, rstd = ops.layernorm_fwd(rows, m.ln_final.weight.data, m.ln_final.bias.data, save_stats=True)
@@ -517,9 +562,7 @@ class Engine:
         ctx = None
         if train:
             ctx = dict(n=n, seq=seq, rows=rows, idx=idx, stats=(mean, rstd), saved=saved, seed=seed, row0=row0,
-                       one_row=one_row, has_ctx=prompt_ctx is not None, lo=lo,
-                       pack=self._pack_plan(ids, ids_host) if one_row and self.pack_text_backward and
-                       self.txt.pack_mode(n, n, seed, seq, lo) else None)
+                       one_row=one_row, has_ctx=prompt_ctx is not None, lo=lo, pack=pack, pack_fwd=pack_fwd)
         return feat, ctx
 
     def text_backward(self, ctx: dict, dfeat: torch.Tensor, dctx_slot: Optional[torch.Tensor] = None) -> None:
@@ -535,7 +578,8 @@ class Engine:
         if ctx.get("pack") is not None:
             plan, R = ctx["pack"]
             dx = self.txt.backward_packed(drows, ctx["idx"], plan, R, n, ctx["saved"], ctx["seed"],
-                                          stop_at_input=not ctx["has_ctx"], seq=seq, row0=ctx["row0"], grad_lo=ctx["lo"])
+                                          stop_at_input=not ctx["has_ctx"], seq=seq, row0=ctx["row0"], grad_lo=ctx["lo"],
+                                          saved_packed=ctx["pack_fwd"])
         elif ctx["one_row"]:
             dx = self.txt.backward_sparse(drows, ctx["idx"], n, ctx["saved"], ctx["seed"], stop_at_input=not ctx["has_ctx"],
                                           seq=seq, row0=ctx["row0"], grad_lo=ctx["lo"])

@@ -655,7 +655,9 @@ constexpr int ATTN_MFMA_MAX = 288;
 // attention_mfma16.hip: the 16-token-tile kernels (seq <= 96) and their packed (live-row) backward
 bool attention16_enabled(int seq);
 int attention16_bwd_packed(const float* qkv, const float* dout, const float* out, const float* lse, float* dqkv,
-                           const int32_t* off, int batch, int seq, int heads, hipStream_t st);
+                           const int32_t* off, int batch, int seq, int heads, bool pin, hipStream_t st);
+int attention16_fwd_packed(const float* qkv, float* out, float* lse, const int32_t* off, int batch, int seq, int heads,
+                           hipStream_t st);
 
 static int check_attn(const char* what, int batch, int seq, int heads, int max_seq) {
   CLIPFS_REQUIRE(batch > 0 && heads > 0 && seq > 0 && seq <= max_seq, "%s: batch %d seq %d heads %d unsupported (seq <= %d)",
@@ -789,7 +791,26 @@ extern "C" int clipfs_attention_bwd_packed(const float* qkv, const float* dout, 
   CLIPFS_REQUIRE(qkv && dout && out && lse && dqkv && off, "attention_bwd_packed: null pointer");
   CLIPFS_REQUIRE(aligned16(qkv) && aligned16(dout) && aligned16(out) && aligned16(dqkv),
                  "attention_bwd_packed: misaligned pointer");
-  return attention16_bwd_packed(qkv, dout, out, lse, dqkv, off, batch, seq, heads, (hipStream_t)stream);
+  return attention16_bwd_packed(qkv, dout, out, lse, dqkv, off, batch, seq, heads, false, (hipStream_t)stream);
+}
+
+extern "C" int clipfs_attention_fwd_packed(const float* qkv, float* out, float* lse, const int32_t* off, int batch, int seq,
+                                           int heads, void* stream) {
+  CLIPFS_CHECK(check_attn("attention_fwd_packed", batch, seq, heads, ATTN_MAX_SEQ));
+  CLIPFS_REQUIRE(clipfs_attention_bwd_packed_ok(seq, 1), "attention_fwd_packed: seq %d has no packed kernel", seq);
+  CLIPFS_REQUIRE(qkv && out && off, "attention_fwd_packed: null pointer");
+  CLIPFS_REQUIRE(aligned16(qkv) && aligned16(out), "attention_fwd_packed: misaligned pointer");
+  return attention16_fwd_packed(qkv, out, lse, off, batch, seq, heads, (hipStream_t)stream);
+}
+
+extern "C" int clipfs_attention_bwd_packed_io(const float* qkv, const float* dout, const float* out, const float* lse,
+                                              float* dqkv, const int32_t* off, int batch, int seq, int heads, void* stream) {
+  CLIPFS_CHECK(check_attn("attention_bwd_packed_io", batch, seq, heads, ATTN_MAX_SEQ));
+  CLIPFS_REQUIRE(clipfs_attention_bwd_packed_ok(seq, 1), "attention_bwd_packed_io: seq %d has no packed kernel", seq);
+  CLIPFS_REQUIRE(qkv && dout && out && lse && dqkv && off, "attention_bwd_packed_io: null pointer");
+  CLIPFS_REQUIRE(aligned16(qkv) && aligned16(dout) && aligned16(out) && aligned16(dqkv),
+                 "attention_bwd_packed_io: misaligned pointer");
+  return attention16_bwd_packed(qkv, dout, out, lse, dqkv, off, batch, seq, heads, true, (hipStream_t)stream);
 }
 
 extern "C" size_t clipfs_attention_lse_floats(int batch, int seq, int heads) {

@@ -136,9 +136,16 @@ __device__ __forceinline__ float a16_allreduce_sum(float v) {
 
 // forward: own = 16 queries per wave.  S^T = K Q^T (lane = query, registers = keys), exact softmax over the
 // registers, O^T = V^T P^T.
-template <int NT>
+//
+// PACKED (the text tower's live-row forward): sequence b is live on tokens 0 .. Lb - 1, Lb = off[b + 1] - off[b]; qkv
+// and out are packed (row off[b] + tok), lse keeps its [b * H + h][L] layout (entries past Lb are not written).  Tokens
+// Lb .. L - 1 are staged as zeros and masked like the padding past L, and waves whose tile starts at or past Lb leave
+// after the barrier.  Under the causal mask a live query gives every dead key the weight exp2(-inf) = 0, so each live
+// row gets bitwise the values of the full-layout launch.
+template <int NT, bool PACKED = false>
 __global__ __launch_bounds__(64 * NT) void attention16_fwd_kernel(const float* __restrict__ qkv, float* __restrict__ out,
-                                                                  float* __restrict__ lse, int L, int H, int causal) {
+                                                                  float* __restrict__ lse, int L, int H, int causal,
+                                                                  const int32_t* __restrict__ off) {
   extern __shared__ __attribute__((aligned(16))) float a16_smem[];
   constexpr int TP = 16 * NT + 8;
   float* sKt = a16_smem;
@@ -150,19 +157,23 @@ __global__ __launch_bounds__(64 * NT) void attention16_fwd_kernel(const float* _
   const int g = lane >> 4;
   const int q_tok = 16 * qt + (lane & 15);
   const float c = 0.125f * A16_LOG2E;
-  const int klim = causal ? q_tok : L - 1;
-  const int na = causal ? qt + 1 : NT;  // key tiles with work (wave-uniform)
-  auto head = [&](int item) { return qkv + (size_t)(item / H) * L * ld + (size_t)(item % H) * A16_HD; };
-  f32x4 kst[4], vst[4];
   const int item = blockIdx.x;  // = b * H + h
-  a16_fetch<NT>(head(item) + d, ld, L, kst);
-  a16_fetch<NT>(head(item) + 2 * d, ld, L, vst);
   const int b = item / H, h = item % H;
+  const size_t prow = PACKED ? (size_t)off[b] : (size_t)b * L;  // row of token 0 in qkv / out
+  const int Lb = PACKED ? (int)(off[b + 1] - prow) : L;
+  if (PACKED && (Lb <= 0 || Lb > L)) return;  // not a valid plan entry (workgroup-uniform): read nothing
+  const int klim = causal ? q_tok : Lb - 1;
+  const int na = causal ? qt + 1 : NT;  // key tiles with work (wave-uniform)
+  const float* hq = qkv + prow * ld + (size_t)h * A16_HD;
+  f32x4 kst[4], vst[4];
+  a16_fetch<NT>(hq + d, ld, Lb, kst);
+  a16_fetch<NT>(hq + 2 * d, ld, Lb, vst);
   float qf[16];
-  a16_load_own(head(item), ld, min(q_tok, L - 1), lane, qf);
-  a16_put<NT>(sKt, kst, L);
-  a16_put<NT>(sVt, vst, L);
+  a16_load_own(hq, ld, min(q_tok, Lb - 1), lane, qf);
+  a16_put<NT>(sKt, kst, Lb);
+  a16_put<NT>(sVt, vst, Lb);
   __syncthreads();
+  if (PACKED && 16 * qt >= Lb) return;  // no live query in this wave's tile (wave-uniform; no barrier follows)
   f32x4 s[A16_MAX_TILES];
   A16_SWITCH_SCORES(na, sKt, qf, s)
   float m = -INFINITY;
@@ -172,7 +183,7 @@ __global__ __launch_bounds__(64 * NT) void attention16_fwd_kernel(const float* _
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int key = 16 * t + 4 * g + r;
-        s[t][r] = (key < L && key <= klim) ? s[t][r] * c : -INFINITY;
+        s[t][r] = (key < Lb && key <= klim) ? s[t][r] * c : -INFINITY;
         m = fmaxf(m, s[t][r]);
       }
     }
@@ -194,8 +205,8 @@ __global__ __launch_bounds__(64 * NT) void attention16_fwd_kernel(const float* _
 #pragma unroll
   for (int t = 0; t < NT; ++t)
     if (t < na) a16_accum<TP>(sVt, lane, t, s[t], o);
-  if (q_tok < L) {
-    a16_store(out + ((size_t)b * L + q_tok) * d + h * A16_HD, o, 1.f / l, lane);
+  if (q_tok < Lb) {
+    a16_store(out + (prow + q_tok) * d + h * A16_HD, o, 1.f / l, lane);
     if (lse && g == 0) lse[((size_t)b * H + h) * L + q_tok] = (m + log2f(l)) * (1.f / A16_LOG2E);
   }
 }
@@ -207,7 +218,8 @@ __global__ __launch_bounds__(64 * NT) void attention16_fwd_kernel(const float* _
 // (its EOT and what precedes it).  qkv, out and lse keep the forward's full layout (row b * L + tok); dout and dqkv are
 // packed (row off[b] + tok).  Tokens Lb .. L - 1 are staged as zeros and masked like the padding past L, and waves whose
 // own tile starts at or past Lb leave after the last barrier: under the causal mask a live row never sees a dead one.
-template <int NT, bool PACKED>
+// PIN (with PACKED): qkv and out are packed as well (the live-row forward saved them so); lse keeps its layout.
+template <int NT, bool PACKED, bool PIN>
 __device__ __forceinline__ void attention16_bwd_q_body(const float* __restrict__ qkv, const float* __restrict__ dout,
                                                        const float* __restrict__ out, const float* __restrict__ lse,
                                                        float* __restrict__ dqkv, int L, int H, int causal, int item,
@@ -222,21 +234,22 @@ __device__ __forceinline__ void attention16_bwd_q_body(const float* __restrict__
   const int g = lane >> 4;
   const int b = item / H, h = item % H;
   const size_t prow = PACKED ? (size_t)off[b] : (size_t)b * L;  // row of token 0 in dout / dqkv
+  const size_t irow = PIN ? prow : (size_t)b * L;                 // ... and in qkv / out
   const int Lb = PACKED ? (int)(off[b + 1] - prow) : L;
   const int q_tok = 16 * qt + (lane & 15), q_cl = min(q_tok, Lb - 1);
   const float c = 0.125f * A16_LOG2E;
   const int klim = causal ? q_tok : Lb - 1;
   const int na = causal ? qt + 1 : (Lb + 15) / 16;
-  auto head = [&](int item) { return qkv + (size_t)(item / H) * L * ld + (size_t)(item % H) * A16_HD; };
+  const float* hq = qkv + irow * ld + (size_t)h * A16_HD;
   f32x4 kst[4], vst[4];
-  a16_fetch<NT>(head(item) + d, ld, Lb, kst);
-  a16_fetch<NT>(head(item) + 2 * d, ld, Lb, vst);
+  a16_fetch<NT>(hq + d, ld, Lb, kst);
+  a16_fetch<NT>(hq + 2 * d, ld, Lb, vst);
   float qf[16], gf[16];
-  a16_load_own(head(item), ld, q_cl, lane, qf);
+  a16_load_own(hq, ld, q_cl, lane, qf);
   a16_load_own(dout + prow * d + (size_t)h * A16_HD, (size_t)d, q_cl, lane, gf);
   float Di = 0.f;
   {
-    const float* op = out + ((size_t)b * L + q_cl) * d + h * A16_HD + 16 * g;
+    const float* op = out + (irow + q_cl) * d + h * A16_HD + 16 * g;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const f32x4 ov = *reinterpret_cast<const f32x4*>(op + 4 * j);
@@ -274,7 +287,7 @@ __device__ __forceinline__ void attention16_bwd_q_body(const float* __restrict__
 // dK/dV pass (own = 16 keys).  S = Q K^T ; P = exp2(S c - lse) ; dP = dO V^T ; dS = P (dP - D) / 8 ;
 // dV^T = dO^T P ; dK^T = Q^T dS.  lse and D vary with the register index (rows = queries): 4-float groups from LDS;
 // D is recomputed here from the staged dO rows and the matching O rows.
-template <int NT, bool PACKED>
+template <int NT, bool PACKED, bool PIN>
 __device__ __forceinline__ void attention16_bwd_kv_body(const float* __restrict__ qkv, const float* __restrict__ dout,
                                                         const float* __restrict__ out, const float* __restrict__ lse,
                                                         float* __restrict__ dqkv, int L, int H, int causal, int item,
@@ -292,6 +305,7 @@ __device__ __forceinline__ void attention16_bwd_kv_body(const float* __restrict_
   const int g = lane >> 4;
   const int b = item / H, h = item % H;
   const size_t prow = PACKED ? (size_t)off[b] : (size_t)b * L;  // row of token 0 in dout / dqkv
+  const size_t irow = PIN ? prow : (size_t)b * L;                 // ... and in qkv / out
   const int Lb = PACKED ? (int)(off[b + 1] - prow) : L;
   const int k_tok = 16 * kt + (lane & 15), k_cl = min(k_tok, Lb - 1);
   const float c = 0.125f * A16_LOG2E;
@@ -300,15 +314,15 @@ __device__ __forceinline__ void attention16_bwd_kv_body(const float* __restrict_
   const int na = (PACKED ? (Lb + 15) / 16 : NT) - t_first;
   const float* sQ1 = sQt + 16 * t_first;
   const float* sG1 = sGt + 16 * t_first;
-  auto qhead = [&](int item) { return qkv + (size_t)(item / H) * L * ld + (size_t)(item % H) * A16_HD; };
+  const float* hq = qkv + irow * ld + (size_t)h * A16_HD;
   const int vtok = min((int)threadIdx.x, Lb - 1);  // thread i < 16 NT carries element i of the head's lse / D vectors
   f32x4 qst[4], gst[4], ost[4];
-  a16_fetch<NT>(qhead(item), ld, Lb, qst);
+  a16_fetch<NT>(hq, ld, Lb, qst);
   a16_fetch<NT>(dout + prow * d + (size_t)h * A16_HD, (size_t)d, Lb, gst);
-  a16_fetch<NT>(out + (size_t)(item / H) * L * d + (size_t)(item % H) * A16_HD, (size_t)d, Lb, ost);
+  a16_fetch<NT>(out + irow * d + (size_t)h * A16_HD, (size_t)d, Lb, ost);
   float kf[16], vf[16];
-  a16_load_own(qhead(item) + d, ld, k_cl, lane, kf);
-  a16_load_own(qhead(item) + 2 * d, ld, k_cl, lane, vf);
+  a16_load_own(hq + d, ld, k_cl, lane, kf);
+  a16_load_own(hq + 2 * d, ld, k_cl, lane, vf);
   const float lse_i = lse[(size_t)item * L + vtok];  // item = b * H + h
   a16_put<NT>(sQt, qst, Lb);
   a16_put<NT>(sGt, gst, Lb);
@@ -367,7 +381,7 @@ __device__ __forceinline__ void attention16_bwd_kv_body(const float* __restrict_
 // dispatch order, so the head's q, k, v, dO rows are fetched from HBM once and found in L2 by the other).  Round 2 ran
 // them as two launches with D handed through memory; at the per-rank sizes of the 8-GPU step each was ~15 us of work
 // behind its own launch.
-template <int NT, bool PACKED = false>
+template <int NT, bool PACKED = false, bool PIN = false>
 __global__ __launch_bounds__(64 * NT) void attention16_bwd_kernel(const float* __restrict__ qkv, const float* __restrict__ dout,
                                                                   const float* __restrict__ out, const float* __restrict__ lse,
                                                                   float* __restrict__ dqkv, int L, int H, int causal,
@@ -375,9 +389,9 @@ __global__ __launch_bounds__(64 * NT) void attention16_bwd_kernel(const float* _
   extern __shared__ __attribute__((aligned(16))) float a16_smem[];
   const int item = blockIdx.x >> 1;  // = b * H + h
   if (blockIdx.x & 1)
-    attention16_bwd_kv_body<NT, PACKED>(qkv, dout, out, lse, dqkv, L, H, causal, item, off, a16_smem);
+    attention16_bwd_kv_body<NT, PACKED, PIN>(qkv, dout, out, lse, dqkv, L, H, causal, item, off, a16_smem);
   else
-    attention16_bwd_q_body<NT, PACKED>(qkv, dout, out, lse, dqkv, L, H, causal, item, off, a16_smem);
+    attention16_bwd_q_body<NT, PACKED, PIN>(qkv, dout, out, lse, dqkv, L, H, causal, item, off, a16_smem);
 }
 
 // ---- host side (called from attention_mfma.hip) -------------------------------------------------------------
@@ -391,31 +405,32 @@ static size_t a16_lds(int nt, bool vectors) {  // vectors: lse, D and the 16 par
   return ((size_t)2 * 64 * (16 * nt + 8) + (vectors ? 18 * (size_t)16 * nt : 0)) * sizeof(float);
 }
 
-template <int NT>
-static int a16_fwd(const float* qkv, float* out, float* lse, int batch, int seq, int heads, int causal, hipStream_t st) {
+template <int NT, bool PACKED = false>
+static int a16_fwd(const float* qkv, float* out, float* lse, int batch, int seq, int heads, int causal, hipStream_t st,
+                   const int32_t* off = nullptr) {
   static bool attr = false;
   if (!attr && a16_lds(NT, false) > 48 * 1024) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attention16_fwd_kernel<NT>),
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attention16_fwd_kernel<NT, PACKED>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)a16_lds(NT, false));
     attr = true;
   }
-  hipLaunchKernelGGL(attention16_fwd_kernel<NT>, dim3(batch * heads), dim3(64 * NT), a16_lds(NT, false), st, qkv, out, lse, seq,
-                     heads, causal);
+  hipLaunchKernelGGL((attention16_fwd_kernel<NT, PACKED>), dim3(batch * heads), dim3(64 * NT), a16_lds(NT, false), st, qkv, out,
+                     lse, seq, heads, causal, off);
   return launch_status();
 }
 
-template <int NT, bool PACKED = false>
+template <int NT, bool PACKED = false, bool PIN = false>
 static int a16_bwd(const float* qkv, const float* dout, const float* out, const float* lse, float* dqkv, float* work,
                    int batch, int seq, int heads, int causal, hipStream_t st, const int32_t* off = nullptr) {
   (void)work;  // D_i no longer travels through memory
   static bool attr = false;
   if (!attr && a16_lds(NT, true) > 48 * 1024) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attention16_bwd_kernel<NT, PACKED>),
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attention16_bwd_kernel<NT, PACKED, PIN>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)a16_lds(NT, true));
     attr = true;
   }
-  hipLaunchKernelGGL((attention16_bwd_kernel<NT, PACKED>), dim3(2 * batch * heads), dim3(64 * NT), a16_lds(NT, true), st, qkv,
-                     dout, out, lse, dqkv, seq, heads, causal, off);
+  hipLaunchKernelGGL((attention16_bwd_kernel<NT, PACKED, PIN>), dim3(2 * batch * heads), dim3(64 * NT), a16_lds(NT, true), st,
+                     qkv, dout, out, lse, dqkv, seq, heads, causal, off);
   return launch_status();
 }
 
@@ -442,16 +457,34 @@ int attention16_bwd(const float* qkv, const float* dout, const float* out, const
   }
 }
 
-// packed (live-row) backward: runtime tile bounds from off[], the launch sized by the full sequence
+// packed (live-row) backward: runtime tile bounds from off[], the launch sized by the full sequence.  pin: q/k/v and O
+// are packed too (saved by the live-row forward), otherwise they keep the full layout
 int attention16_bwd_packed(const float* qkv, const float* dout, const float* out, const float* lse, float* dqkv,
-                           const int32_t* off, int batch, int seq, int heads, hipStream_t st) {
+                           const int32_t* off, int batch, int seq, int heads, bool pin, hipStream_t st) {
+#define A16_BWD_PACKED(nt)                                                                              \
+  return pin ? a16_bwd<nt, true, true>(qkv, dout, out, lse, dqkv, nullptr, batch, seq, heads, 1, st, off) \
+             : a16_bwd<nt, true, false>(qkv, dout, out, lse, dqkv, nullptr, batch, seq, heads, 1, st, off)
   switch ((seq + 15) / 16) {
-    case 1: return a16_bwd<1, true>(qkv, dout, out, lse, dqkv, nullptr, batch, seq, heads, 1, st, off);
-    case 2: return a16_bwd<2, true>(qkv, dout, out, lse, dqkv, nullptr, batch, seq, heads, 1, st, off);
-    case 3: return a16_bwd<3, true>(qkv, dout, out, lse, dqkv, nullptr, batch, seq, heads, 1, st, off);
-    case 4: return a16_bwd<4, true>(qkv, dout, out, lse, dqkv, nullptr, batch, seq, heads, 1, st, off);
-    case 5: return a16_bwd<5, true>(qkv, dout, out, lse, dqkv, nullptr, batch, seq, heads, 1, st, off);
-    default: return a16_bwd<6, true>(qkv, dout, out, lse, dqkv, nullptr, batch, seq, heads, 1, st, off);
+    case 1: A16_BWD_PACKED(1);
+    case 2: A16_BWD_PACKED(2);
+    case 3: A16_BWD_PACKED(3);
+    case 4: A16_BWD_PACKED(4);
+    case 5: A16_BWD_PACKED(5);
+    default: A16_BWD_PACKED(6);
+  }
+#undef A16_BWD_PACKED
+}
+
+// packed (live-row) causal forward: qkv and out packed, lse in its [b * H + h][seq] layout
+int attention16_fwd_packed(const float* qkv, float* out, float* lse, const int32_t* off, int batch, int seq, int heads,
+                           hipStream_t st) {
+  switch ((seq + 15) / 16) {
+    case 1: return a16_fwd<1, true>(qkv, out, lse, batch, seq, heads, 1, st, off);
+    case 2: return a16_fwd<2, true>(qkv, out, lse, batch, seq, heads, 1, st, off);
+    case 3: return a16_fwd<3, true>(qkv, out, lse, batch, seq, heads, 1, st, off);
+    case 4: return a16_fwd<4, true>(qkv, out, lse, batch, seq, heads, 1, st, off);
+    case 5: return a16_fwd<5, true>(qkv, out, lse, batch, seq, heads, 1, st, off);
+    default: return a16_fwd<6, true>(qkv, out, lse, batch, seq, heads, 1, st, off);
   }
 }
 

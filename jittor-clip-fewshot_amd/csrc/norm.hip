@@ -73,7 +73,9 @@ __global__ __launch_bounds__(256) void layernorm_fwd_kernel(const float* x, int 
 // read of y plus, at the per-rank sizes of the 8-GPU step, ~10 us of launch for ~2 us of work) is folded in: per float4
 // of y one Philox call per adapted segment (the same (stream, row, column group) counter as the stand-alone kernel, so
 // the backward's masks agree), NSEG * R dot products against A (12 rows of <= 8 KiB: cache resident), NSEG * R wave sums.
-template <int NSEG, int R>
+// MAP: the dropout masks of row `row` are those of row drow0 + drow_map[row] (the text tower's
+// live-row forward runs packed rows and draws the masks of their full-layout rows).
+template <int NSEG, int R, bool MAP = false>
 __global__ __launch_bounds__(256) void layernorm_fwd_lora_kernel(const float* x, int ldx, const float* __restrict__ gamma,
                                                                  const float* __restrict__ beta, float* y,
                                                                  float* __restrict__ mean_out, float* __restrict__ rstd_out,
@@ -81,7 +83,8 @@ __global__ __launch_bounds__(256) void layernorm_fwd_lora_kernel(const float* x,
                                                                  const float* __restrict__ A, float* __restrict__ t,
                                                                  unsigned seg_mask, float p, uint64_t seed,
                                                                  uint32_t stream_base, uint32_t drow0,
-                                                                 uint16_t* __restrict__ keep_bits) {
+                                                                 uint16_t* __restrict__ keep_bits,
+                                                                 const int32_t* __restrict__ drow_map) {
   const int lane = threadIdx.x & 63;
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= rows) return;
@@ -139,7 +142,8 @@ __global__ __launch_bounds__(256) void layernorm_fwd_lora_kernel(const float* x,
         if (!((seg_mask >> sg) & 1u)) continue;
         float4 xs = o;
         if (drop) {
-          const float4 mk = dropout_scale4(seed, stream_base + sg, drow0 + (uint32_t)row, (uint32_t)c, thr, inv_keep);
+          const float4 mk = dropout_scale4(seed, stream_base + sg, drow0 + (uint32_t)(MAP ? drow_map[row] : row),
+                                           (uint32_t)c, thr, inv_keep);
           xs.x *= mk.x;
           xs.y *= mk.y;
           xs.z *= mk.z;
@@ -386,10 +390,10 @@ extern "C" int clipfs_layernorm_fwd_lora_ok(int width, int r, int nseg) {
   return (cfg != 0 && nseg == 3 && (r == 1 || r == 2 || r == 4) && width > 0 && (width & 3) == 0 && width <= 256 * LN_MAX_CHUNKS) ? 1 : 0;
 }
 
-extern "C" int clipfs_layernorm_fwd_lora(const float* x, int ldx, const float* gamma, const float* beta, float* y, void* y16,
+static int layernorm_fwd_lora_impl(const float* x, int ldx, const float* gamma, const float* beta, float* y, void* y16,
                                          float* mean, float* rstd, int rows, int width, float eps, const float* A, float* t,
                                          int r, int nseg, unsigned seg_mask, float p, uint64_t seed, uint32_t stream_base,
-                                         uint32_t drow0, void* keep_bits, void* stream) {
+                                         uint32_t drow0, void* keep_bits, const int32_t* drow_map, void* stream) {
   CLIPFS_CHECK(check_rows("layernorm_fwd_lora", rows, width));
   CLIPFS_REQUIRE(x && gamma && beta && (y || y16) && A && t, "layernorm_fwd_lora: null pointer");
   CLIPFS_REQUIRE((mean == nullptr) == (rstd == nullptr), "layernorm_fwd_lora: mean and rstd must both be given or both NULL");
@@ -403,17 +407,47 @@ extern "C" int clipfs_layernorm_fwd_lora(const float* x, int ldx, const float* g
   uint16_t* kb = reinterpret_cast<uint16_t*>(keep_bits);
   switch (r) {
     case 1:
-      hipLaunchKernelGGL((layernorm_fwd_lora_kernel<3, 1>), grid, dim3(256), 0, st, x, ldx, gamma, beta, y, mean, rstd, rows, width,
-                         eps, h, A, t, seg_mask, p, seed, stream_base, drow0, kb);
+      if (drow_map)
+        hipLaunchKernelGGL((layernorm_fwd_lora_kernel<3, 1, true>), grid, dim3(256), 0, st, x, ldx, gamma, beta, y, mean, rstd, rows,
+                           width, eps, h, A, t, seg_mask, p, seed, stream_base, drow0, kb, drow_map);
+      else
+        hipLaunchKernelGGL((layernorm_fwd_lora_kernel<3, 1>), grid, dim3(256), 0, st, x, ldx, gamma, beta, y, mean, rstd, rows,
+                           width, eps, h, A, t, seg_mask, p, seed, stream_base, drow0, kb, nullptr);
       break;
     case 2:
-      hipLaunchKernelGGL((layernorm_fwd_lora_kernel<3, 2>), grid, dim3(256), 0, st, x, ldx, gamma, beta, y, mean, rstd, rows, width,
-                         eps, h, A, t, seg_mask, p, seed, stream_base, drow0, kb);
+      if (drow_map)
+        hipLaunchKernelGGL((layernorm_fwd_lora_kernel<3, 2, true>), grid, dim3(256), 0, st, x, ldx, gamma, beta, y, mean, rstd, rows,
+                           width, eps, h, A, t, seg_mask, p, seed, stream_base, drow0, kb, drow_map);
+      else
+        hipLaunchKernelGGL((layernorm_fwd_lora_kernel<3, 2>), grid, dim3(256), 0, st, x, ldx, gamma, beta, y, mean, rstd, rows,
+                           width, eps, h, A, t, seg_mask, p, seed, stream_base, drow0, kb, nullptr);
       break;
     default:
-      hipLaunchKernelGGL((layernorm_fwd_lora_kernel<3, 4>), grid, dim3(256), 0, st, x, ldx, gamma, beta, y, mean, rstd, rows, width,
-                         eps, h, A, t, seg_mask, p, seed, stream_base, drow0, kb);
+      if (drow_map)
+        hipLaunchKernelGGL((layernorm_fwd_lora_kernel<3, 4, true>), grid, dim3(256), 0, st, x, ldx, gamma, beta, y, mean, rstd, rows,
+                           width, eps, h, A, t, seg_mask, p, seed, stream_base, drow0, kb, drow_map);
+      else
+        hipLaunchKernelGGL((layernorm_fwd_lora_kernel<3, 4>), grid, dim3(256), 0, st, x, ldx, gamma, beta, y, mean, rstd, rows,
+                           width, eps, h, A, t, seg_mask, p, seed, stream_base, drow0, kb, nullptr);
       break;
   }
   return launch_status();
+}
+
+extern "C" int clipfs_layernorm_fwd_lora(const float* x, int ldx, const float* gamma, const float* beta, float* y, void* y16,
+                                         float* mean, float* rstd, int rows, int width, float eps, const float* A, float* t,
+                                         int r, int nseg, unsigned seg_mask, float p, uint64_t seed, uint32_t stream_base,
+                                         uint32_t drow0, void* keep_bits, void* stream) {
+  return layernorm_fwd_lora_impl(x, ldx, gamma, beta, y, y16, mean, rstd, rows, width, eps, A, t, r, nseg, seg_mask, p, seed,
+                                 stream_base, drow0, keep_bits, nullptr, stream);
+}
+
+extern "C" int clipfs_layernorm_fwd_lora_map(const float* x, int ldx, const float* gamma, const float* beta, float* y,
+                                             void* y16, float* mean, float* rstd, int rows, int width, float eps, const float* A,
+                                             float* t, int r, int nseg, unsigned seg_mask, float p, uint64_t seed,
+                                             uint32_t stream_base, uint32_t drow0, const int32_t* drow_map, void* keep_bits,
+                                             void* stream) {
+  CLIPFS_REQUIRE(drow_map, "layernorm_fwd_lora_map: null row map");
+  return layernorm_fwd_lora_impl(x, ldx, gamma, beta, y, y16, mean, rstd, rows, width, eps, A, t, r, nseg, seg_mask, p, seed,
+                                 stream_base, drow0, keep_bits, drow_map, stream);
 }

@@ -33,7 +33,8 @@ static inline bool keep_bits_slot(const clipfs_tower* t) {  // the slot exists (
 }
 static inline bool keep_bits_saved(const clipfs_tower* t) { return keep_bits_slot(t) && t->dropout_seed != 0; }
 
-static SavedLayout saved_layout(const clipfs_tower* t, size_t M) {
+// M per-row records; the lse slot keeps its [sequence * heads + head][seq] layout whatever the row count
+static SavedLayout saved_layout_rows(const clipfs_tower* t, size_t M, size_t batch) {
   const size_t d = t->width, r = t->lora_r > 0 ? t->lora_r : 0;
   SavedLayout L;
   size_t o = 0;
@@ -44,8 +45,8 @@ static SavedLayout saved_layout(const clipfs_tower* t, size_t M) {
   L.qkv = o;   o += al4(qkv_f16(t) ? (M * 3 * d + 1) / 2 : M * 3 * d);  // fp16 mode: q | k | v saved as f16
   L.att = o;   o += al4(M * d);
   // log-sum-exp rows: the long-sequence fp32 kernels (0 floats for seq <= 96) and every f16 MFMA attention need them
-  L.lse = o;   o += al4(t->weight_format == 2 ? (M / t->seq) * t->seq * (size_t)t->heads
-                                              : clipfs_attention_lse_floats((int)(M / t->seq), t->seq, t->heads));
+  L.lse = o;   o += al4(t->weight_format == 2 ? batch * t->seq * (size_t)t->heads
+                                              : clipfs_attention_lse_floats((int)batch, t->seq, t->heads));
   L.t_o = o;   o += al4(M * r);
   L.x_mid = o; o += al4(M * d);
   L.stat2 = o; o += al4(2 * M);
@@ -53,6 +54,12 @@ static SavedLayout saved_layout(const clipfs_tower* t, size_t M) {
   L.keep = o;  o += keep_bits_slot(t) ? al4((M * (d / 4) + 1) / 2) : 0;    // uint16 per float4 of h1
   L.total = o;
   return L;
+}
+
+static SavedLayout saved_layout(const clipfs_tower* t, size_t M) { return saved_layout_rows(t, M, M / t->seq); }
+// the live-row forward (clipfs_tower_fwd_packed) keeps R packed rows per block: no larger than the dense record for R <= M
+static SavedLayout saved_layout_packed(const clipfs_tower* t, size_t R, size_t batch) {
+  return saved_layout_rows(t, R, batch);
 }
 
 // bias gradient slots (clipfs_block.g_*): NULL everywhere = bias='none', and then the backward launches exactly what it
@@ -573,10 +580,14 @@ static bool pack_ok(const clipfs_tower* t, int batch, int R) {
 // block l_hi's output -- or, with attn_only_top, wrt its attention residual, datt_p (b1, first half) the gradient wrt its
 // attention output.  Slots (R <= M / 2): b1 = datt_p | dx_p; big = du_p | u_p in the MLP part, then the gathered
 // h1 / t_qkv / keep bits (/ att / t_o); b3 = dqkv_p; h = dh_p.
+// saved_packed: the saved tensors are the live-row forward's (clipfs_tower_fwd_packed: R packed rows per record), read
+// in place -- no gathers, the plain LayerNorm backward, the attention backward on packed q/k/v and O.
 static int tower_bwd_packed_range(const clipfs_tower* t, float* dx, int batch, const PackPlan& P, const float* saved,
-                                  float* scratch, int stop_at_input, hipStream_t st, int l_hi, bool attn_only_top) {
+                                  float* scratch, int stop_at_input, hipStream_t st, int l_hi, bool attn_only_top,
+                                  bool saved_packed) {
   const int M = batch * t->seq, d = t->width, r = t->lora_r, R = P.R;
-  const SavedLayout SL = saved_layout(t, (size_t)M);
+  const SavedLayout SL = saved_packed ? saved_layout_packed(t, (size_t)R, (size_t)batch) : saved_layout(t, (size_t)M);
+  const int srows = saved_packed ? R : M;  // rows of a saved record (offset of the rstd half of a statistics slot)
   const ScratchLayout SC = scratch_layout(t, (size_t)M);
   const TowerCtx cx = make_ctx(t, scratch, SC);
   const size_t Rd = (size_t)R * d;
@@ -605,28 +616,39 @@ static int tower_bwd_packed_range(const clipfs_tower* t, float* dx, int batch, c
     if (!(attn_only_top && l == l_hi)) {
       // MLP and output projection, as in tower_bwd_range
       CLIPFS_CHECK(bias_sum(dx_p, R, d, d, b.g_b_pr, nullptr, nullptr, bwork, st));
-      CLIPFS_CHECK(clipfs_gather_rows_map(sv + SL.u, (size_t)4 * d, P.map, u_p, R, 4 * d, st));
-      CLIPFS_CHECK(gemm(cx, dx_p, b.w_pr_t, b.w_pr_t_p, du_p, R, 4 * d, d, nullptr, nullptr, 2, nullptr, u_p, nullptr, nullptr, 0, 0,
-                        0, 0.f, st));
+      if (!saved_packed) CLIPFS_CHECK(clipfs_gather_rows_map(sv + SL.u, (size_t)4 * d, P.map, u_p, R, 4 * d, st));
+      CLIPFS_CHECK(gemm(cx, dx_p, b.w_pr_t, b.w_pr_t_p, du_p, R, 4 * d, d, nullptr, nullptr, 2, nullptr,
+                        saved_packed ? sv + SL.u : u_p, nullptr, nullptr, 0, 0, 0, 0.f, st));
       CLIPFS_CHECK(bias_sum(du_p, R, 4 * d, 4 * d, b.g_b_fc, nullptr, nullptr, bwork, st));
       CLIPFS_CHECK(gemm(cx, du_p, b.w_fc_t, b.w_fc_t_p, dh_p, R, d, 4 * d, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, 0,
                         0, 0, 0.f, st));
       CLIPFS_CHECK(bias_sum(dh_p, R, d, d, b.g_ln2_b, nullptr, nullptr, bwork, st));
-      CLIPFS_CHECK(clipfs_layernorm_bwd_rows(dh_p, sv + SL.x_mid, d, b.ln2_g, sv + SL.stat2, sv + SL.stat2 + M, P.map, dx_p,
-                                             dx_p, d, R, d, st));
+      if (saved_packed)
+        CLIPFS_CHECK(clipfs_layernorm_bwd(dh_p, sv + SL.x_mid, d, b.ln2_g, sv + SL.stat2, sv + SL.stat2 + srows, dx_p, dx_p, d,
+                                          R, d, st));
+      else
+        CLIPFS_CHECK(clipfs_layernorm_bwd_rows(dh_p, sv + SL.x_mid, d, b.ln2_g, sv + SL.stat2, sv + SL.stat2 + srows, P.map,
+                                               dx_p, dx_p, d, R, d, st));
       CLIPFS_CHECK(bias_sum(dx_p, R, d, d, b.g_b_o, nullptr, nullptr, bwork, st));
       CLIPFS_CHECK(gemm(cx, dx_p, b.w_o_t, b.w_o_t_p, datt_p, R, d, d, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, 0, 0,
                         0, 0.f, st));
       if (lora_o) {  // no dropout here (pack_dropout_ok): the adapter backward evaluates no mask
-        CLIPFS_CHECK(clipfs_gather_rows_map(sv + SL.att, (size_t)d, P.map, att_p, R, d, st));
-        CLIPFS_CHECK(clipfs_gather_rows_map(sv + SL.t_o, (size_t)r, P.map, to_p, R, r, st));
-        CLIPFS_CHECK(lora_bwd_block(t, false, dx_p, nullptr, att_p, to_p, b.lora_a_o, b.lora_b_o, dt, b.g_lora_a_o,
-                                    b.g_lora_b_o, datt_p, R, 1, 1u, ds + 3, nullptr, work, st, l));
+        if (!saved_packed) {
+          CLIPFS_CHECK(clipfs_gather_rows_map(sv + SL.att, (size_t)d, P.map, att_p, R, d, st));
+          CLIPFS_CHECK(clipfs_gather_rows_map(sv + SL.t_o, (size_t)r, P.map, to_p, R, r, st));
+        }
+        CLIPFS_CHECK(lora_bwd_block(t, false, dx_p, nullptr, saved_packed ? sv + SL.att : att_p, saved_packed ? sv + SL.t_o : to_p,
+                                    b.lora_a_o, b.lora_b_o, dt, b.g_lora_a_o, b.g_lora_b_o, datt_p, R, 1, 1u, ds + 3, nullptr,
+                                    work, st, l));
       }
     }
-    // attention (full-layout q/k/v, O, lse; packed dO and dqkv) and the QKV projection
-    CLIPFS_CHECK(clipfs_attention_bwd_packed(sv + SL.qkv, datt_p, sv + SL.att, sv + SL.lse, dqkv_p, P.off, batch, t->seq,
-                                             t->heads, st));
+    // attention (full-layout or packed q/k/v and O, lse; packed dO and dqkv) and the QKV projection
+    if (saved_packed)
+      CLIPFS_CHECK(clipfs_attention_bwd_packed_io(sv + SL.qkv, datt_p, sv + SL.att, sv + SL.lse, dqkv_p, P.off, batch, t->seq,
+                                                  t->heads, st));
+    else
+      CLIPFS_CHECK(clipfs_attention_bwd_packed(sv + SL.qkv, datt_p, sv + SL.att, sv + SL.lse, dqkv_p, P.off, batch, t->seq,
+                                               t->heads, st));
     CLIPFS_CHECK(bias_sum(dqkv_p, R, 3 * d, d, b.g_b_q, b.g_b_k, b.g_b_v, bwork, st));
     const bool need_dx = !(l == lo && stop_at_input);
     const bool need_dh = need_dx || b.g_ln1_b;
@@ -635,18 +657,25 @@ static int tower_bwd_packed_range(const clipfs_tower* t, float* dx, int batch, c
                         0, 0, 0, 0.f, st));
     if (qkv_mask && (b.g_lora_a_qkv || need_dh)) {
       const bool keep = keep_bits_saved(t);
-      CLIPFS_CHECK(clipfs_gather_rows_map(sv + SL.h1, (size_t)d, P.map, h1_p, R, d, st));
-      CLIPFS_CHECK(clipfs_gather_rows_map(sv + SL.t_qkv, (size_t)3 * r, P.map, tq_p, R, 3 * r, st));
-      if (keep)  // uint16 per float4 of h1: d / 8 floats per row
-        CLIPFS_CHECK(clipfs_gather_rows_map(sv + SL.keep, (size_t)d / 8, P.map, keep_p, R, d / 8, st));
-      CLIPFS_CHECK(lora_bwd_block(t, false, dqkv_p, nullptr, h1_p, tq_p, b.lora_a_qkv, b.lora_b_qkv, dt, b.g_lora_a_qkv,
-                                  b.g_lora_b_qkv, need_dh ? dh_p : nullptr, R, 3, qkv_mask, ds,
-                                  keep ? (const void*)keep_p : nullptr, work, st, l));
+      if (!saved_packed) {
+        CLIPFS_CHECK(clipfs_gather_rows_map(sv + SL.h1, (size_t)d, P.map, h1_p, R, d, st));
+        CLIPFS_CHECK(clipfs_gather_rows_map(sv + SL.t_qkv, (size_t)3 * r, P.map, tq_p, R, 3 * r, st));
+        if (keep)  // uint16 per float4 of h1: d / 8 floats per row
+          CLIPFS_CHECK(clipfs_gather_rows_map(sv + SL.keep, (size_t)d / 8, P.map, keep_p, R, d / 8, st));
+      }
+      CLIPFS_CHECK(lora_bwd_block(t, false, dqkv_p, nullptr, saved_packed ? sv + SL.h1 : h1_p, saved_packed ? sv + SL.t_qkv : tq_p,
+                                  b.lora_a_qkv, b.lora_b_qkv, dt, b.g_lora_a_qkv, b.g_lora_b_qkv, need_dh ? dh_p : nullptr, R, 3,
+                                  qkv_mask, ds, keep ? (saved_packed ? (const void*)(sv + SL.keep) : (const void*)keep_p) : nullptr,
+                                  work, st, l));
     }
     CLIPFS_CHECK(bias_sum(dh_p, R, d, d, b.g_ln1_b, nullptr, nullptr, bwork, st));
     if (need_dx) {
-      CLIPFS_CHECK(clipfs_layernorm_bwd_rows(dh_p, sv + SL.x_in, d, b.ln1_g, sv + SL.stat1, sv + SL.stat1 + M, P.map, dx_p,
-                                             dx_p, d, R, d, st));
+      if (saved_packed)
+        CLIPFS_CHECK(clipfs_layernorm_bwd(dh_p, sv + SL.x_in, d, b.ln1_g, sv + SL.stat1, sv + SL.stat1 + srows, dx_p, dx_p, d, R,
+                                          d, st));
+      else
+        CLIPFS_CHECK(clipfs_layernorm_bwd_rows(dh_p, sv + SL.x_in, d, b.ln1_g, sv + SL.stat1, sv + SL.stat1 + srows, P.map,
+                                               dx_p, dx_p, d, R, d, st));
     }
   }
   if (stop_at_input) return CLIPFS_OK;
@@ -657,10 +686,12 @@ static int tower_bwd_packed_range(const clipfs_tower* t, float* dx, int batch, c
 }
 
 // the last block's compact part, then (P != NULL) the packed or (P == NULL) the dense rows below it
+// (saved_packed: the saved tensors are clipfs_tower_fwd_packed's, P != NULL)
 static int tower_bwd_sparse_impl(const clipfs_tower* t, const float* dxs, const int32_t* rows, float* dx, int batch,
-                                 const float* saved, float* scratch, int stop_at_input, hipStream_t st, const PackPlan* P) {
+                                 const float* saved, float* scratch, int stop_at_input, hipStream_t st, const PackPlan* P,
+                                 bool saved_packed = false) {
   const int seq = t->seq, M = batch * seq, d = t->width, r = t->lora_r, Ms = batch;
-  const SavedLayout SL = saved_layout(t, (size_t)M);
+  const SavedLayout SL = saved_packed ? saved_layout_packed(t, (size_t)P->R, (size_t)batch) : saved_layout(t, (size_t)M);
   const ScratchLayout SC = scratch_layout(t, (size_t)M);
   CLIPFS_REQUIRE(!t->gemm_counters || t->gemm_counters_ints >= SC.counter_ints,
                  "tower: gemm_counters holds %zu ints, %zu needed", t->gemm_counters_ints, SC.counter_ints);
@@ -690,13 +721,20 @@ static int tower_bwd_sparse_impl(const clipfs_tower* t, const float* dxs, const 
   // fp16 storage mode: the `batch`-row products use the fp32 master weights (plane argument NULL); the saved pre-GELU
   // activation is an f16 tensor there
   const bool f16m = t->weight_format == 2;
-  if (f16m)
-    CLIPFS_CHECK(clipfs_gather_seq_rows_f16(sv + SL.u, (size_t)4 * d, rows, u_s, Ms, seq, 4 * d, st));
-  else
-    CLIPFS_CHECK(clipfs_gather_seq_rows(sv + SL.u, (size_t)4 * d, rows, u_s, Ms, seq, 4 * d, st));
-  CLIPFS_CHECK(clipfs_gather_seq_rows(sv + SL.x_mid, (size_t)d, rows, xmid_s, Ms, seq, d, st));
-  CLIPFS_CHECK(clipfs_gather_seq_rows(sv + SL.stat2, 1, rows, mean_s, Ms, seq, 1, st));
-  CLIPFS_CHECK(clipfs_gather_seq_rows(sv + SL.stat2 + M, 1, rows, rstd_s, Ms, seq, 1, st));
+  if (saved_packed) {  // the compact forward put these rows at the packed EOT rows
+    CLIPFS_CHECK(clipfs_gather_rows_map(sv + SL.u, (size_t)4 * d, P->eotp, u_s, Ms, 4 * d, st));
+    CLIPFS_CHECK(clipfs_gather_rows_map(sv + SL.x_mid, (size_t)d, P->eotp, xmid_s, Ms, d, st));
+    CLIPFS_CHECK(clipfs_gather_rows_map(sv + SL.stat2, 1, P->eotp, mean_s, Ms, 1, st));
+    CLIPFS_CHECK(clipfs_gather_rows_map(sv + SL.stat2 + P->R, 1, P->eotp, rstd_s, Ms, 1, st));
+  } else {
+    if (f16m)
+      CLIPFS_CHECK(clipfs_gather_seq_rows_f16(sv + SL.u, (size_t)4 * d, rows, u_s, Ms, seq, 4 * d, st));
+    else
+      CLIPFS_CHECK(clipfs_gather_seq_rows(sv + SL.u, (size_t)4 * d, rows, u_s, Ms, seq, 4 * d, st));
+    CLIPFS_CHECK(clipfs_gather_seq_rows(sv + SL.x_mid, (size_t)d, rows, xmid_s, Ms, seq, d, st));
+    CLIPFS_CHECK(clipfs_gather_seq_rows(sv + SL.stat2, 1, rows, mean_s, Ms, seq, 1, st));
+    CLIPFS_CHECK(clipfs_gather_seq_rows(sv + SL.stat2 + M, 1, rows, rstd_s, Ms, seq, 1, st));
+  }
   CLIPFS_CHECK(gemm(cx, dxs, b.w_pr_t, f16m ? nullptr : b.w_pr_t_p, du_s, Ms, 4 * d, d, nullptr, nullptr, 2, nullptr, u_s, nullptr, nullptr,
                     0, 0, 0, 0.f, st));
   CLIPFS_CHECK(bias_sum(du_s, Ms, 4 * d, 4 * d, b.g_b_fc, nullptr, nullptr, bwork, st));
@@ -716,7 +754,7 @@ static int tower_bwd_sparse_impl(const clipfs_tower* t, const float* dxs, const 
     CLIPFS_REQUIRE(e == hipSuccess, "tower_bwd_packed: memset failed: %s", hipGetErrorString(e));
     CLIPFS_CHECK(clipfs_put_rows_map(datt_s, P->eotp, datt_p, (size_t)d, Ms, d, st));
     CLIPFS_CHECK(clipfs_put_rows_map(dxm_s, P->eotp, datt_p + al4(Rd), (size_t)d, Ms, d, st));
-    return tower_bwd_packed_range(t, dx, batch, *P, saved, scratch, stop_at_input, st, l, true);
+    return tower_bwd_packed_range(t, dx, batch, *P, saved, scratch, stop_at_input, st, l, true, saved_packed);
   }
   // ---- attention and the QKV projection see every row again ----
   float* dh = scratch + SC.h;
@@ -784,4 +822,171 @@ extern "C" int clipfs_tower_bwd_packed(const clipfs_tower* t, const float* dxs, 
     return tower_bwd_sparse_impl(t, dxs, rows, dx, batch, saved, scratch, stop_at_input, st, nullptr);
   const PackPlan P = {plan, plan + batch + 1, plan + 2 * (size_t)batch + 1, R};
   return tower_bwd_sparse_impl(t, dxs, rows, dx, batch, saved, scratch, stop_at_input, st, &P);
+}
+
+// ---- packed (live-row) forward of a causal tower ---------------------------------------------------------------------
+// The same argument forward: row i of every block reads rows <= i of its caption only, and the head reads the EOT row,
+// so every block runs on the R live rows of the plan, packed caption after caption; the last block's compact part reads
+// its rows at the packed EOT rows (eotp).  Saved records hold R rows each (saved_layout_packed; the lse slot keeps its
+// [sequence * heads + head][seq] layout) and only clipfs_tower_bwd_packed_saved reads them.
+//
+// Every value of a live row equals the dense forward's bitwise: LayerNorm, the adapters and the GEMM epilogues are
+// row-wise, the attention masks a dead key exactly as the padding, the dropout masks are drawn at the full-layout row
+// (drow0 + map[i]), and each R-row GEMM is launched unsplit -- the K order of one output element depends on the split
+// factor only, never on the tile height -- which is why packing requires the dense launches to be unsplit too.
+static bool pack_fwd_ok(const clipfs_tower* t, int batch, int R) {
+  if (!pack_ok(t, batch, R) || t->weight_format != 0) return false;  // exact fp32 only
+  const int M = batch * t->seq, d = t->width, r = t->lora_r;
+  const int shapes[4][2] = {{3 * d, d}, {d, d}, {4 * d, d}, {d, 4 * d}};  // (N, K) of QKV, out-projection, c_fc, c_proj
+  for (int i = 0; i < 4; ++i)
+    if (clipfs_gemm_workspace_floats(M, shapes[i][0], shapes[i][1]) != 0) return false;  // split-K or stream-K at M
+  // dropout on the packed rows: only the fused LayerNorm + down-projection draws its masks through the row map, and the
+  // blocks below grad_lo draw them too
+  if (r > 0 && t->lora_dropout > 0.f && t->dropout_seed != 0)
+    for (int l = 0; l < t->layers; ++l) {
+      const clipfs_block& b = t->blocks[l];
+      if (b.lora_a_o && (b.lora_mask & 8u)) return false;
+      if (b.lora_a_qkv && (b.lora_mask & 7u) && !clipfs_layernorm_fwd_lora_ok(d, r, 3)) return false;
+    }
+  return true;
+}
+
+// Slots (R <= M / 2): the residual of the blocks that save nothing lives in b1's second half (x_p), their attention
+// output in its first half; h1 / qkv / t_qkv / t_o / the MLP as in tower_fwd_impl; the compact part in the MLP scratch.
+static int tower_fwd_packed_impl(const clipfs_tower* t, float* x, const int32_t* rows, const PackPlan& P, int batch,
+                                 float* saved, float* scratch, hipStream_t st) {
+  const int seq = t->seq, M = batch * seq, d = t->width, r = t->lora_r, R = P.R;
+  const size_t Rd = (size_t)R * d;
+  const SavedLayout SL = saved_layout_packed(t, (size_t)R, (size_t)batch);
+  const ScratchLayout SC = scratch_layout(t, (size_t)M);
+  CLIPFS_REQUIRE(!t->gemm_counters || t->gemm_counters_ints >= SC.counter_ints,
+                 "tower: gemm_counters holds %zu ints, %zu needed", t->gemm_counters_ints, SC.counter_ints);
+  const TowerCtx cx = make_ctx(t, scratch, SC);  // the compact part's `batch`-row products: as in tower_fwd_impl
+  TowerCtx cxp = cx;                             // the R-row products: unsplit (pack_fwd_ok)
+  cxp.ws = nullptr;
+  cxp.ws_floats = 0;
+  cxp.counters = nullptr;
+  cxp.counters_ints = 0;
+  const bool train = saved != nullptr;
+  const uint64_t seed = t->dropout_seed;
+  const int lo = t->grad_lo;
+  float* x_p = scratch + SC.b1 + al4(Rd);
+  // pack the input once (straight into the first saved record when every block saves)
+  CLIPFS_CHECK(clipfs_gather_rows_map(x, (size_t)d, P.map, train && lo == 0 ? saved + SL.x_in : x_p, R, d, st));
+  for (int l = 0; l < t->layers; ++l) {
+    const clipfs_block& b = t->blocks[l];
+    const bool keep_l = train && l >= lo;
+    if (train && l == lo && lo > 0) {
+      hipError_t e = hipMemcpyAsync(saved + SL.x_in, x_p, Rd * sizeof(float), hipMemcpyDeviceToDevice, st);
+      CLIPFS_REQUIRE(e == hipSuccess, "tower_fwd_packed: memcpy failed: %s", hipGetErrorString(e));
+    }
+    float* sv = keep_l ? saved + (size_t)(l - lo) * SL.total : nullptr;
+    const float* x_in = keep_l ? sv + SL.x_in : x_p;
+    float* h1 = keep_l ? sv + SL.h1 : scratch + SC.h;
+    float* qkv = keep_l ? sv + SL.qkv : scratch + SC.b3;
+    float* att = keep_l ? sv + SL.att : scratch + SC.b1;
+    float* x_mid = keep_l ? sv + SL.x_mid : x_p;
+    float* t_qkv = keep_l ? sv + SL.t_qkv : scratch + SC.dt;
+    float* t_o = keep_l ? sv + SL.t_o : scratch + SC.dt + al4((size_t)R * 3 * r);
+    float* x_next = keep_l && l + 1 < t->layers ? saved + (size_t)(l + 1 - lo) * SL.total + SL.x_in : x_p;
+    float* lse = keep_l ? sv + SL.lse : nullptr;  // the packed kernel is the same with or without statistics
+    const unsigned qkv_mask = b.lora_a_qkv ? (b.lora_mask & 7u) : 0u;
+    const bool lora_o = b.lora_a_o && (b.lora_mask & 8u);
+    const uint32_t ds = t->dropout_stream0 + 4u * (uint32_t)l;
+    float* mean1 = keep_l ? sv + SL.stat1 : nullptr;
+    float* rstd1 = keep_l ? sv + SL.stat1 + R : nullptr;
+    void* keep = (keep_l && qkv_mask && keep_bits_saved(t)) ? (void*)(sv + SL.keep) : nullptr;
+    if (qkv_mask && clipfs_layernorm_fwd_lora_ok(d, r, 3)) {
+      CLIPFS_CHECK(clipfs_layernorm_fwd_lora_map(x_in, d, b.ln1_g, b.ln1_b, h1, nullptr, mean1, rstd1, R, d, 1e-5f, b.lora_a_qkv,
+                                                 t_qkv, r, 3, qkv_mask, t->lora_dropout, seed, ds, t->dropout_row0, P.map, keep,
+                                                 st));
+    } else {
+      CLIPFS_CHECK(clipfs_layernorm_fwd(x_in, d, b.ln1_g, b.ln1_b, h1, mean1, rstd1, R, d, 1e-5f, st));
+      if (qkv_mask)  // no dropout here (pack_fwd_ok)
+        CLIPFS_CHECK(clipfs_lora_down(h1, b.lora_a_qkv, t_qkv, R, d, r, 3, qkv_mask, t->lora_dropout, seed, ds, t->dropout_row0,
+                                      keep, st));
+    }
+    CLIPFS_CHECK(gemm(cxp, h1, b.w_qkv, b.w_qkv_p, qkv, R, 3 * d, d, b.b_qkv, nullptr, 0, nullptr, nullptr,
+                      qkv_mask ? t_qkv : nullptr, b.lora_b_qkv, r, 3, d, t->lora_scale, st));
+    CLIPFS_CHECK(clipfs_attention_fwd_packed(qkv, att, lse, P.off, batch, seq, t->heads, st));
+    if (l == t->layers - 1) {
+      // ---- the rest of the last block on the EOT rows, as in tower_fwd_impl (rows read at eotp, saved rows put there)
+      const int Ms = batch;
+      float* att_s = scratch + SC.big;
+      float* xin_s = att_s + (size_t)Ms * d;
+      float* xmid_s = xin_s + (size_t)Ms * d;
+      float* h2_s = xmid_s + (size_t)Ms * d;
+      float* xout_s = h2_s + (size_t)Ms * d;
+      float* g_s = xout_s + (size_t)Ms * d;
+      float* u_s = g_s + (size_t)Ms * 4 * d;
+      float* mean_s = u_s + (size_t)Ms * 4 * d;
+      float* rstd_s = mean_s + al4((size_t)Ms);
+      CLIPFS_CHECK(clipfs_gather_rows_map(att, (size_t)d, P.eotp, att_s, Ms, d, st));
+      CLIPFS_CHECK(clipfs_gather_rows_map(x_in, (size_t)d, P.eotp, xin_s, Ms, d, st));
+      CLIPFS_CHECK(gemm(cx, att_s, b.w_o, b.w_o_p, xmid_s, Ms, d, d, b.b_o, xin_s, 0, nullptr, nullptr, nullptr, nullptr, 0, 0, 0,
+                        0.f, st));
+      CLIPFS_CHECK(clipfs_layernorm_fwd(xmid_s, d, b.ln2_g, b.ln2_b, h2_s, keep_l ? mean_s : nullptr, keep_l ? rstd_s : nullptr, Ms,
+                                        d, 1e-5f, st));
+      CLIPFS_CHECK(gemm(cx, h2_s, b.w_fc, b.w_fc_p, g_s, Ms, 4 * d, d, b.b_fc, nullptr, 1, keep_l ? u_s : nullptr, nullptr, nullptr,
+                        nullptr, 0, 0, 0, 0.f, st));
+      CLIPFS_CHECK(gemm(cx, g_s, b.w_pr, b.w_pr_p, xout_s, Ms, d, 4 * d, b.b_pr, xmid_s, 0, nullptr, nullptr, nullptr, nullptr, 0, 0,
+                        0, 0.f, st));
+      CLIPFS_CHECK(clipfs_put_seq_rows(xout_s, rows, x, (size_t)d, Ms, seq, d, st));
+      if (keep_l) {
+        CLIPFS_CHECK(clipfs_put_rows_map(xmid_s, P.eotp, sv + SL.x_mid, (size_t)d, Ms, d, st));
+        CLIPFS_CHECK(clipfs_put_rows_map(u_s, P.eotp, sv + SL.u, (size_t)4 * d, Ms, 4 * d, st));
+        CLIPFS_CHECK(clipfs_put_rows_map(mean_s, P.eotp, sv + SL.stat2, 1, Ms, 1, st));
+        CLIPFS_CHECK(clipfs_put_rows_map(rstd_s, P.eotp, sv + SL.stat2 + R, 1, Ms, 1, st));
+      }
+      break;
+    }
+    if (lora_o)  // no dropout here (pack_fwd_ok)
+      CLIPFS_CHECK(clipfs_lora_down(att, b.lora_a_o, t_o, R, d, r, 1, 1u, t->lora_dropout, seed, ds + 3, t->dropout_row0, nullptr,
+                                    st));
+    CLIPFS_CHECK(gemm(cxp, att, b.w_o, b.w_o_p, x_mid, R, d, d, b.b_o, x_in, 0, nullptr, nullptr, lora_o ? t_o : nullptr, b.lora_b_o,
+                      r, 1, d, t->lora_scale, st));
+    float* h2 = scratch + SC.h;
+    CLIPFS_CHECK(clipfs_layernorm_fwd(x_mid, d, b.ln2_g, b.ln2_b, h2, keep_l ? sv + SL.stat2 : nullptr,
+                                      keep_l ? sv + SL.stat2 + R : nullptr, R, d, 1e-5f, st));
+    float* gbuf = scratch + SC.big;
+    CLIPFS_CHECK(gemm(cxp, h2, b.w_fc, b.w_fc_p, gbuf, R, 4 * d, d, b.b_fc, nullptr, 1, keep_l ? sv + SL.u : nullptr, nullptr, nullptr,
+                      nullptr, 0, 0, 0, 0.f, st));
+    CLIPFS_CHECK(gemm(cxp, gbuf, b.w_pr, b.w_pr_p, x_next, R, d, 4 * d, b.b_pr, x_mid, 0, nullptr, nullptr, nullptr, nullptr, 0, 0, 0,
+                      0.f, st));
+  }
+  return CLIPFS_OK;
+}
+
+extern "C" int clipfs_tower_pack_fwd_mode(const clipfs_tower* t, int batch, int R) {
+  if (!t || !t->blocks || t->struct_size != sizeof(clipfs_tower) || t->block_size != sizeof(clipfs_block)) return 0;
+  if (batch <= 0 || t->layers <= 0 || t->seq <= 0 || t->grad_lo < 0 || t->grad_lo >= t->layers) return 0;
+  return pack_fwd_ok(t, batch, R) ? 1 : 0;
+}
+
+extern "C" int clipfs_tower_fwd_packed(const clipfs_tower* t, float* x, const int32_t* rows, const int32_t* plan, int R,
+                                       int batch, float* saved, float* scratch, void* stream) {
+  CLIPFS_CHECK(check_tower(t, batch));
+  CLIPFS_REQUIRE(x && rows && plan && scratch, "tower_fwd_packed: null buffer");
+  CLIPFS_REQUIRE(R >= batch && (size_t)R <= (size_t)batch * t->seq, "tower_fwd_packed: R %d outside [batch %d, batch*seq %zu]",
+                 R, batch, (size_t)batch * t->seq);
+  if (!pack_fwd_ok(t, batch, R))  // the dense rows (clipfs_tower_pack_fwd_mode says which)
+    return tower_fwd_impl(t, x, last_block_rows_ok(t) ? rows : nullptr, batch, saved, scratch, stream);
+  const PackPlan P = {plan, plan + batch + 1, plan + 2 * (size_t)batch + 1, R};
+  return tower_fwd_packed_impl(t, x, rows, P, batch, saved, scratch, (hipStream_t)stream);
+}
+
+extern "C" int clipfs_tower_bwd_packed_saved(const clipfs_tower* t, const float* dxs, const int32_t* rows, const int32_t* plan,
+                                             int R, float* dx, int batch, const float* saved, float* scratch, int stop_at_input,
+                                             void* stream) {
+  CLIPFS_CHECK(check_tower(t, batch));
+  CLIPFS_REQUIRE(t->grad_lo == 0 || stop_at_input,
+                 "tower_bwd_packed_saved: grad_lo %d > 0 needs stop_at_input (the input gradient runs through every block)",
+                 t->grad_lo);
+  CLIPFS_REQUIRE(dxs && rows && plan && dx && saved && scratch, "tower_bwd_packed_saved: null buffer");
+  CLIPFS_REQUIRE(R >= batch && (size_t)R <= (size_t)batch * t->seq,
+                 "tower_bwd_packed_saved: R %d outside [batch %d, batch*seq %zu]", R, batch, (size_t)batch * t->seq);
+  // the saved tensors must be clipfs_tower_fwd_packed's packed ones: no fall-back here
+  CLIPFS_REQUIRE(pack_fwd_ok(t, batch, R), "tower_bwd_packed_saved: this geometry runs the dense forward (pack_fwd_mode 0)");
+  const PackPlan P = {plan, plan + batch + 1, plan + 2 * (size_t)batch + 1, R};
+  return tower_bwd_sparse_impl(t, dxs, rows, dx, batch, saved, scratch, stop_at_input, (hipStream_t)stream, &P, true);
 }
