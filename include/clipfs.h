@@ -409,6 +409,25 @@ int clipfs_mta(const float* feats, const float* text, float* mode_out, float* lo
 int clipfs_tta_views(const uint8_t* image, int height, int width, const int32_t* recs, int n_views, int out_size,
                      const float* mean, const float* stdv, float* out, void* stream);
 
+/* ------------------------------------------------------- training crops --
+ * One kernel writes a whole training batch [n, 3, S, S]; each view names its own source inside ONE uint8 HWC pool of
+ * decoded images (back to back in HBM).  Per view: crop -> PIL-exact 8-bit resize (bilinear or bicubic, the resampling
+ * of clipfs_tta_views) -> S x S window -> optional horizontal flip.  Replaces the PIL training transform of
+ * lora_train_vlp.py:1196-1218 / slow_pace.py:1903-1935 (RandomResizedCrop, RandomHorizontalFlip, ImageNormalize,
+ * ToTensor).
+ * pool: device, pool_bytes long.  src: int64 [n_src, 3] = {byte offset into pool, height, width}; recs: int32 [n, 12] =
+ * {src index, top, left, h, w, flip, out_w, out_h, win_x, win_y, filter (0 bilinear, 1 bicubic), 0} (the box / resize /
+ * window / flip meaning of clipfs_tta_views' records).  src and recs are HOST tables, validated here; src_dev and
+ * recs_dev are their device copies, which the kernel reads (and re-checks against the pool, writing nothing for a view
+ * that fails).  out_norm: fp32 [n, 3, S, S] = (u8 - 255 mean) * ((1 / 255) / std), the formula of clipfs_tta_views;
+ * out_raw: fp32 [n, 3, S, S] = u8 / 255 (ToTensor).  Either output may be NULL, not both; both are written in one pass.
+ * CLIPFS_EINVAL (nothing launched) for NULL tables, a source side outside [1, 4096] or outside the pool, a src index out
+ * of range, a box outside its source, a window outside its resize, or more than 80 taps on an axis
+ * (ceil(support * max(in / out, 1)) * 2 + 1). */
+int clipfs_crop_batch(const uint8_t* pool, size_t pool_bytes, const int64_t* src, const int64_t* src_dev, int n_src,
+                      const int32_t* recs, const int32_t* recs_dev, int n, int out_size, const float* mean,
+                      const float* stdv, float* out_norm, float* out_raw, void* stream);
+
 /* --------------------------------------------------------- tower drivers --
  * C++ sequencing of the kernels above for one transformer tower, so that one call
  * from Python enqueues a whole forward or backward (no per-kernel interpreter cost).

@@ -801,3 +801,19 @@ class LoRATrainer:
         out = self.forward_backward(images, captions, target, templates_per_class, global_batch, row_offset)
         self.optimizer_step()
         return out
+
+
+def gpu_train_loader(root: str, split: str = 'train', image_dir: str = '', batch_size: int = 256, scale=(0.05, 1.0),
+                     normalize: bool = True, seed: int = 0, rank: int = 0, world: int = 1, prefetch: bool = True,
+                     size: int = 224, threads: int = 8, device=None):
+    """lora_train_vlp.py:1196-1218 on the GPU: ``JtDataset(root, split, transform=train_tranform1, mode='train')`` +
+    ``DataLoader(batch_size=256, shuffle=True)``.  The images listed in ``{root}/{split}.txt`` (paths relative to
+    ``image_dir``, like the reference's ``read_split(split_path, '')``) are decoded once into a device pool; each batch is
+    RandomResizedCrop(224, scale) -> RandomHorizontalFlip -> ImageNormalize (``normalize``) made by one kernel launch.
+    Yields ``(images, raw, target, index)`` (clipfs.data.TrainLoader); call ``set_epoch`` or iterate again for the next
+    epoch."""
+    from clipfs import data
+    paths, labels = data.read_split(os.path.join(root, f'{split}.txt'), image_dir)
+    pool = data.ImagePool.from_files(paths, labels, threads=threads, device=device)
+    return data.TrainLoader(pool, batch_size=batch_size, scale=scale, size=size, shuffle=True, seed=seed,
+                            outputs=("clip",) if normalize else ("raw",), rank=rank, world=world, prefetch=prefetch)

@@ -558,3 +558,20 @@ def solve_mta(image_features: torch.Tensor, text_features: torch.Tensor) -> torc
     text = text_features.t().contiguous().float()
     mode, _ = ops.mta(image_features.contiguous().float().unsqueeze(0), text, want_logits=False)
     return mode
+
+
+def gpu_train_loader(root: str, split: str = 'train', image_dir: str = '', batch_size: int = 128, scale=(0.05, 1.0),
+                     seed: int = 0, rank: int = 0, world: int = 1, prefetch: bool = True, size: int = 224,
+                     threads: int = 8, device=None):
+    """slow_pace.py:1903-1935 on the GPU: ``JtDataset(root, 'train', transform=train_tranform1, mode='train')`` +
+    ``DataLoader(batch_size=128, shuffle=True)`` where train_tranform1 is RandomResizedCrop(224, scale) ->
+    RandomHorizontalFlip -> ToTensor (no ImageNormalize: the loop applies ``tfm_clip`` / ``tfm_moco``).  Yields
+    ``(None, raw, target, index)``: ``raw`` in [0, 1], ``index`` the sample's position in the class-grouped split (the row
+    of the cached zero-shot features ``Stage2Trainer`` reads)."""
+    import os
+
+    from clipfs import data
+    paths, labels = data.read_split(os.path.join(root, f'{split}.txt'), image_dir)
+    pool = data.ImagePool.from_files(paths, labels, threads=threads, device=device)
+    return data.TrainLoader(pool, batch_size=batch_size, scale=scale, size=size, shuffle=True, seed=seed, outputs=("raw",),
+                            rank=rank, world=world, prefetch=prefetch)
