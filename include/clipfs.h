@@ -452,6 +452,17 @@ typedef struct clipfs_block {
    * LayerNorm biases, the q / k / v segments of the packed in-projection bias, out projection, c_fc, c_proj.
    * Refused in the fp16 storage mode (weight_format 2), which keeps dqkv and the MLP gradient as f16 images only. */
   float *g_ln1_b, *g_ln2_b, *g_b_q, *g_b_k, *g_b_v, *g_b_o, *g_b_fc, *g_b_pr;
+  /* deep prompt (IVLP vision_depth / language_depth, reference jclip/model1.py:95-116): every forward writes `prompt`
+   * [prompt_rows, width] over the rows prompt_first ... prompt_first + prompt_rows - 1 of each sequence of the block's
+   * input, before LN1 (rows past the sequence -- a trimmed or packed caption -- are skipped: clipfs_prompt_put); every
+   * backward takes their gradient right after the block's input gradient exists, accumulates it into g_prompt and zeroes
+   * those rows (clipfs_prompt_harvest) -- with g_prompt NULL (a frozen prompt) it only zeroes them.  A block with
+   * g_prompt forms its input gradient even as the floor block under stop_at_input.  prompt NULL = no prompt (the fields
+   * after it are ignored).  The placement lives here rather than in clipfs_tower so that a tower descriptor keeps its
+   * layout; every block of a tower uses the same one (the vision tower's last rows, the text tower's rows 1 ... n). */
+  const float* prompt;
+  float* g_prompt;
+  int prompt_first, prompt_rows;
 } clipfs_block;
 
 typedef struct clipfs_tower {
@@ -474,6 +485,19 @@ typedef struct clipfs_tower {
                                NULL.  0 <= grad_lo < layers; grad_lo > 0 needs stop_at_input != 0 in the backward
                                (the gradient wrt the tower input runs through every block). */
 } clipfs_tower;
+
+/* The two deep-prompt kernels the tower drivers run (also usable alone).  Rows: dense (off == NULL) row(c, j) =
+ * c * seq + first + j, skipped when first + j >= seq; packed (off = off[0 .. batch] of a clipfs_tower_bwd_packed plan)
+ * row(c, j) = off[c] + first + j, skipped when first + j >= off[c + 1] - off[c] (past the caption's EOT).  j < n, c < batch,
+ * every row `width` floats wide.
+ *   put:     x[row(c, j), :] = prompt[j, :]
+ *   harvest: g[j, :] += sum_c dx[row(c, j), :] (g NULL: nothing added), then those rows of dx -- and of its f16 image dx16
+ *            (halves, same layout; NULL = none) -- are set to zero.  Fixed summation order, no atomics: bitwise
+ *            reproducible. */
+int clipfs_prompt_put(const float* prompt, float* x, const int32_t* off, int batch, int seq, int first, int n, int width,
+                      void* stream);
+int clipfs_prompt_harvest(float* dx, void* dx16, const int32_t* off, int batch, int seq, int first, int n, int width,
+                          float* g, void* stream);
 
 /* floats needed per tower call for saved activations / scratch (saved: one record per block grad_lo ... layers-1;
  * 0 for a descriptor the library rejects) */

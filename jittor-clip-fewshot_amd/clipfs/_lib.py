@@ -54,7 +54,8 @@ class Block(C.Structure):
         "lora_a_qkv", "lora_b_qkv", "lora_a_o", "lora_b_o",
         "g_lora_a_qkv", "g_lora_b_qkv", "g_lora_a_o", "g_lora_b_o")] + [("lora_mask", C.c_uint)] + [
         (n, C.c_void_p) for n in ("w_qkv_p", "w_o_p", "w_fc_p", "w_pr_p", "w_qkv_t_p", "w_o_t_p", "w_fc_t_p", "w_pr_t_p",
-                                  "g_ln1_b", "g_ln2_b", "g_b_q", "g_b_k", "g_b_v", "g_b_o", "g_b_fc", "g_b_pr")]
+                                  "g_ln1_b", "g_ln2_b", "g_b_q", "g_b_k", "g_b_v", "g_b_o", "g_b_fc", "g_b_pr",
+                                  "prompt", "g_prompt")] + [("prompt_first", C.c_int), ("prompt_rows", C.c_int)]
 
 
 class Tower(C.Structure):
@@ -143,6 +144,8 @@ SIGNATURES = {
     "clipfs_im2col_nhwc": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p]),
     "clipfs_maxpool3x3s2_nhwc": (_i, [_p, _p, _i, _i, _i, _i, _p]),
     "clipfs_global_avgpool_nhwc": (_i, [_p, _p, _i, _i, _i, _p]),
+    "clipfs_prompt_put": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p]),
+    "clipfs_prompt_harvest": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p, _p]),
     "clipfs_tower_saved_floats": (_sz, [C.POINTER(Tower), _i]),
     "clipfs_tower_scratch_floats": (_sz, [C.POINTER(Tower), _i]),
     "clipfs_tower_counter_ints": (_sz, [C.POINTER(Tower), _i]),

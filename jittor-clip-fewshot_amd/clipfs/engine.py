@@ -22,8 +22,8 @@ def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
 
 
 def _bias_slot(p: Optional[torch.nn.Parameter]) -> Optional[torch.Tensor]:
-    """Gradient slot of a trainable bias (``grad_slot``, attached by FlatTrainables or the autograd route), else None:
-    a frozen bias gets no slot, and the backward launches nothing for it."""
+    """Gradient slot of a trainable bias or deep prompt (``grad_slot``, attached by FlatTrainables or the autograd
+    route), else None: a frozen bias gets no slot, and the backward launches nothing for it."""
     if p is None or not p.requires_grad:
         return None
     return getattr(p, "grad_slot", None)
@@ -101,9 +101,11 @@ class _TowerRT:
         return pl
 
     def _block_trains(self, i: int, blk) -> bool:
-        """Whether block i gets any gradient slot in ``descriptor`` (a trainable adapter or bias)."""
+        """Whether block i gets any gradient slot in ``descriptor`` (a trainable adapter, bias or deep prompt)."""
         a = blk.attn
         if getattr(a, "is_lora_mha", False) and a.r > 0 and _lora_trains(a, f"{self.name} block {i}"):
+            return True
+        if _bias_slot(getattr(blk, "VPT_shallow", None)) is not None:
             return True
         return any(_bias_slot(p) is not None for p in _blk_biases(blk))
 
@@ -122,9 +124,27 @@ class _TowerRT:
     def descriptor(self, train: bool, seed: int, seq: Optional[int] = None, row0: int = 0, grad_lo: int = 0) -> Tower:
         blocks = (Block * self.layers)()
         r, scale, p = 0, 0.0, 0.0
+        # deep prompts: the vision tower's last prompt_rows rows (its VPT rows), the text tower's rows 1 ... prompt_rows
+        n_pr = getattr(self.mod, "prompt_rows", 0)
+        first = (seq or self.seq) - n_pr if getattr(self.mod, "prompt_tail", False) else 1
         for i, blk in enumerate(self.mod.resblocks):
             a = blk.attn
             b = blocks[i]
+            vp = getattr(blk, "VPT_shallow", None)
+            if vp is not None:
+                # the kernels read prompt_rows rows of the prompt and add as many into its slot: both must be exactly
+                # [n_pr, width] fp32 on this device (the row count comes from the tensor and must match the placement)
+                g = _bias_slot(vp)
+                ok = (vp.dim() == 2 and tuple(vp.shape) == (n_pr, self.width) and vp.dtype == torch.float32
+                      and vp.is_contiguous() and vp.device == self.mod.resblocks[0].ln_1.weight.device and first >= 1)
+                if g is not None:
+                    ok = ok and g.shape == vp.shape and g.dtype == torch.float32 and g.is_contiguous() and g.device == vp.device
+                if not ok:
+                    raise ValueError(f"{self.name} block {i}: deep prompt {tuple(vp.shape)} (slot "
+                                     f"{None if g is None else tuple(g.shape)}) does not fit the tower's placement of "
+                                     f"{n_pr} rows of width {self.width} from row {first}")
+                b.prompt, b.g_prompt = _ptr(vp), _ptr(g)
+                b.prompt_first, b.prompt_rows = first, vp.shape[0]
             lora = getattr(a, "is_lora_mha", False)
             if lora:
                 w_qkv, b_qkv, w_o, b_o = a.qkv_weight, a.qkv_bias, a.proj.weight, a.proj.bias
@@ -630,12 +650,19 @@ def _bias_pairs(biases) -> List[Tuple[torch.nn.Parameter, torch.Tensor]]:
     return out
 
 
+def deep_prompts(tower_mod) -> List[torch.nn.Parameter]:
+    """The deep prompts of a tower's blocks (``resblocks[i].VPT_shallow``), block order."""
+    return [blk.VPT_shallow for blk in tower_mod.resblocks if getattr(blk, "VPT_shallow", None) is not None]
+
+
 def _image_trainables(model):
-    return _tower_trainables(model.visual.transformer) + _bias_pairs(image_biases(model))
+    return (_tower_trainables(model.visual.transformer) + _bias_pairs(image_biases(model))
+            + _bias_pairs(deep_prompts(model.visual.transformer)))
 
 
 def _text_trainables(model):
-    return _tower_trainables(model.transformer) + _bias_pairs(text_biases(model))
+    return (_tower_trainables(model.transformer) + _bias_pairs(text_biases(model))
+            + _bias_pairs(deep_prompts(model.transformer)))
 
 
 def _zero_slots(pairs):

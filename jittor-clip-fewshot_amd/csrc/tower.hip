@@ -138,8 +138,15 @@ static int check_tower(const clipfs_tower* t, int batch) {
   // blocks below the floor get no backward: a gradient slot there would silently stay untouched
   for (int l = 0; l < t->grad_lo; ++l) {
     const clipfs_block& b = t->blocks[l];
-    CLIPFS_REQUIRE(!b.g_lora_a_qkv && !b.g_lora_b_qkv && !b.g_lora_a_o && !b.g_lora_b_o && !block_has_bias_slots(b),
+    CLIPFS_REQUIRE(!b.g_lora_a_qkv && !b.g_lora_b_qkv && !b.g_lora_a_o && !b.g_lora_b_o && !block_has_bias_slots(b) &&
+                       !b.g_prompt,
                    "tower: block %d below grad_lo %d has gradient slots", l, t->grad_lo);
+  }
+  for (int l = 0; l < t->layers; ++l) {  // deep prompts (clipfs_block.prompt)
+    const clipfs_block& b = t->blocks[l];
+    CLIPFS_REQUIRE(b.prompt || !b.g_prompt, "tower: block %d has a prompt gradient slot but no prompt", l);
+    CLIPFS_REQUIRE(!b.prompt || (b.prompt_first >= 0 && b.prompt_rows > 0),
+                   "tower: block %d prompt rows first %d count %d", l, b.prompt_first, b.prompt_rows);
   }
   if (t->weight_format == 2)  // fp16 storage mode chains f16 results between GEMMs: every block needs all its f16 weights
     for (int l = 0; l < t->layers; ++l) {
@@ -221,6 +228,19 @@ static int gemm(const TowerCtx& cx, const float* A, const float* B, const void* 
   return clipfs_gemm_nt(&a, st);
 }
 
+// deep prompt of block b (clipfs_block.prompt): written over its rows of the block input x (off: the packed plan's
+// offsets, NULL = dense rows); its gradient taken from the input gradient dx (and those rows of dx / its f16 image
+// zeroed: the replaced rows do not depend on the block below)
+static int put_prompt(const clipfs_block& b, float* x, const int32_t* off, int batch, int seq, int d, hipStream_t st) {
+  if (!b.prompt) return CLIPFS_OK;
+  return clipfs_prompt_put(b.prompt, x, off, batch, seq, b.prompt_first, b.prompt_rows, d, st);
+}
+static int harvest_prompt(const clipfs_block& b, float* dx, void* dx16, const int32_t* off, int batch, int seq, int d,
+                          hipStream_t st) {
+  if (!b.prompt) return CLIPFS_OK;
+  return clipfs_prompt_harvest(dx, dx16, off, batch, seq, b.prompt_first, b.prompt_rows, d, b.g_prompt, st);
+}
+
 // accumulate the column sums of a dense [rows, cols] tensor into up to three bias slots (nothing when all are NULL)
 static int bias_sum(const float* x, int rows, int cols, int segw, float* o0, float* o1, float* o2, float* work,
                     hipStream_t st) {
@@ -299,6 +319,7 @@ static int tower_fwd_impl(const clipfs_tower* t, float* x, const int32_t* rows, 
     const unsigned qkv_mask = b.lora_a_qkv ? (b.lora_mask & 7u) : 0u;
     const bool lora_o = b.lora_a_o && (b.lora_mask & 8u);
     const uint32_t ds = t->dropout_stream0 + 4u * (uint32_t)l;
+    CLIPFS_CHECK(put_prompt(b, const_cast<float*>(x_in), nullptr, batch, t->seq, d, st));  // into the saved record, or x
 
     // fp16 storage mode: producers write the f16 image of every GEMM operand next to (or instead of) the fp32 tensor
     void* h16 = cx.a16;                                                        // [M, d] halves: ln1 / attention / ln2 / dx
@@ -486,7 +507,8 @@ static int tower_bwd_range(const clipfs_tower* t, float* dx, int batch, const fl
       CLIPFS_CHECK(clipfs_attention_bwd(sv + SL.qkv, datt, sv + SL.att, sv + SL.lse, dqkv, dh, batch, t->seq, t->heads,
                                         t->causal, st));
     CLIPFS_CHECK(bias_sum(dqkv, M, 3 * d, d, b.g_b_q, b.g_b_k, b.g_b_v, bwork, st));
-    const bool need_dx = !(l == lo && stop_at_input);
+    // a trainable prompt needs the block's input gradient even at the floor
+    const bool need_dx = !(l == lo && stop_at_input) || b.g_prompt;
     // dh1 (the gradient wrt LayerNorm 1's output) is also needed for ln_1's bias gradient, even where dx is not
     const bool need_dh = need_dx || b.g_ln1_b;
     if (need_dh)
@@ -504,6 +526,7 @@ static int tower_bwd_range(const clipfs_tower* t, float* dx, int batch, const fl
       else
         CLIPFS_CHECK(clipfs_layernorm_bwd(dh, sv + SL.x_in, d, b.ln1_g, sv + SL.stat1, sv + SL.stat1 + M, dx, dx, d, M, d,
                                           st));
+      CLIPFS_CHECK(harvest_prompt(b, dx, h16, nullptr, batch, t->seq, d, st));
     }
   }
   return CLIPFS_OK;
@@ -650,7 +673,7 @@ static int tower_bwd_packed_range(const clipfs_tower* t, float* dx, int batch, c
       CLIPFS_CHECK(clipfs_attention_bwd_packed(sv + SL.qkv, datt_p, sv + SL.att, sv + SL.lse, dqkv_p, P.off, batch, t->seq,
                                                t->heads, st));
     CLIPFS_CHECK(bias_sum(dqkv_p, R, 3 * d, d, b.g_b_q, b.g_b_k, b.g_b_v, bwork, st));
-    const bool need_dx = !(l == lo && stop_at_input);
+    const bool need_dx = !(l == lo && stop_at_input) || b.g_prompt;  // as in tower_bwd_range
     const bool need_dh = need_dx || b.g_ln1_b;
     if (need_dh)
       CLIPFS_CHECK(gemm(cx, dqkv_p, b.w_qkv_t, b.w_qkv_t_p, dh_p, R, d, 3 * d, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr,
@@ -676,6 +699,7 @@ static int tower_bwd_packed_range(const clipfs_tower* t, float* dx, int batch, c
       else
         CLIPFS_CHECK(clipfs_layernorm_bwd_rows(dh_p, sv + SL.x_in, d, b.ln1_g, sv + SL.stat1, sv + SL.stat1 + srows, P.map,
                                                dx_p, dx_p, d, R, d, st));
+      CLIPFS_CHECK(harvest_prompt(b, dx_p, nullptr, P.off, batch, t->seq, d, st));
     }
   }
   if (stop_at_input) return CLIPFS_OK;
@@ -775,7 +799,7 @@ static int tower_bwd_sparse_impl(const clipfs_tower* t, const float* dxs, const 
     CLIPFS_CHECK(clipfs_attention_bwd(sv + SL.qkv, datt, sv + SL.att, sv + SL.lse, dqkv, dh, batch, seq, t->heads, t->causal, st));
   CLIPFS_CHECK(bias_sum(dqkv, M, 3 * d, d, b.g_b_q, b.g_b_k, b.g_b_v, bwork, st));
   const uint32_t ds = t->dropout_stream0 + 4u * (uint32_t)l;
-  const bool need_dx = !(l == t->grad_lo && stop_at_input);
+  const bool need_dx = !(l == t->grad_lo && stop_at_input) || b.g_prompt;
   const bool need_dh = need_dx || b.g_ln1_b;  // as in tower_bwd_range
   if (need_dh)
     CLIPFS_CHECK(gemm(cx, dqkv, b.w_qkv_t, b.w_qkv_t_p, dh, M, d, 3 * d, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, 0, 0,
@@ -788,6 +812,7 @@ static int tower_bwd_sparse_impl(const clipfs_tower* t, const float* dxs, const 
   if (!need_dx) return CLIPFS_OK;
   CLIPFS_CHECK(clipfs_layernorm_bwd(dh, sv + SL.x_in, d, b.ln1_g, sv + SL.stat1, sv + SL.stat1 + M, nullptr, dx, d, M, d, st));
   CLIPFS_CHECK(clipfs_add_seq_rows(dxm_s, rows, dx, batch, seq, d, st));  // the residual branch around the attention
+  CLIPFS_CHECK(harvest_prompt(b, dx, nullptr, nullptr, batch, seq, d, st));  // (the f16 image of dx is made below)
   return tower_bwd_range(t, dx, batch, saved, scratch, stop_at_input, st, l - 1);
 }
 
@@ -895,6 +920,7 @@ static int tower_fwd_packed_impl(const clipfs_tower* t, float* x, const int32_t*
     const uint32_t ds = t->dropout_stream0 + 4u * (uint32_t)l;
     float* mean1 = keep_l ? sv + SL.stat1 : nullptr;
     float* rstd1 = keep_l ? sv + SL.stat1 + R : nullptr;
+    CLIPFS_CHECK(put_prompt(b, const_cast<float*>(x_in), P.off, batch, seq, d, st));
     void* keep = (keep_l && qkv_mask && keep_bits_saved(t)) ? (void*)(sv + SL.keep) : nullptr;
     if (qkv_mask && clipfs_layernorm_fwd_lora_ok(d, r, 3)) {
       CLIPFS_CHECK(clipfs_layernorm_fwd_lora_map(x_in, d, b.ln1_g, b.ln1_b, h1, nullptr, mean1, rstd1, R, d, 1e-5f, b.lora_a_qkv,

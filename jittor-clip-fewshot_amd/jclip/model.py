@@ -1,6 +1,8 @@
 """CLIP model objects with the attribute surface of the reference's ``jclip/model.py`` (``CLIP``,
 ``VisionTransformer``, ``Transformer``, ``ResidualAttentionBlock``, ``build_model``) and, with
-``design_details``, of ``jclip/model1.py`` (shallow VPT tokens, ``VisionTransformer.VPT``).
+``design_details``, of ``jclip/model1.py`` (shallow VPT tokens, ``VisionTransformer.VPT``; with
+``design_details["deep_prompts"]`` also the per-block prompts ``resblocks[i].VPT_shallow`` of
+``ResidualAttentionBlock_IVLP``, which the reference codes but never enables).
 
 These classes only HOLD parameters (device tensors, OpenAI-CLIP state-dict names) and expose the
 replaceable ``resblocks[i].attn`` that ``apply_lora`` swaps.  All arithmetic runs in the HIP engine:
@@ -49,8 +51,11 @@ class MLP(nn.Module):
 class ResidualAttentionBlock(nn.Module):
     """jclip/model.py:42-62 (parameter holder; see module docstring)."""
 
-    def __init__(self, sd: Dict[str, torch.Tensor], p: str, d_model: int, n_head: int, causal: bool):
+    def __init__(self, sd: Dict[str, torch.Tensor], p: str, d_model: int, n_head: int, causal: bool,
+                 prompt: Optional[torch.Tensor] = None):
         super().__init__()
+        # deep prompt (ResidualAttentionBlock_IVLP, model1.py:64-127): replaces its rows of this block's input
+        self.VPT_shallow = None if prompt is None else nn.Parameter(prompt.contiguous())
         self.attn = MultiheadAttention(d_model, n_head, sd[p + "attn.in_proj_weight"], sd[p + "attn.in_proj_bias"],
                                        sd[p + "attn.out_proj.weight"], sd[p + "attn.out_proj.bias"])
         self.ln_1 = LayerNorm(sd[p + "ln_1.weight"], sd[p + "ln_1.bias"])
@@ -59,15 +64,43 @@ class ResidualAttentionBlock(nn.Module):
         self.causal = causal
 
 
+def _deep_prompts(sd: Dict[str, torch.Tensor], prefix: str, width: int, depth: int, n_ctx: int, seed: int, device):
+    """Prompts of blocks 1 ... depth-1 (block 0's rows are the embedding's VPT / ctx): the state-dict tensor
+    ``{prefix}.resblocks.{i}.VPT_shallow`` when present, else normal(std 0.02) as model1.py:85-87.  A stored prompt
+    of another shape (a checkpoint saved with another vision_ctx / language_ctx) is refused."""
+    g = torch.Generator().manual_seed(seed)
+    out = {}
+    for i in range(1, depth):
+        key = f"{prefix}.resblocks.{i}.VPT_shallow"
+        if key in sd:
+            if tuple(sd[key].shape) != (n_ctx, width):
+                raise ValueError(f"deep prompts: {key} has shape {tuple(sd[key].shape)}, the design details ask for "
+                                 f"{(n_ctx, width)}")
+            out[i] = sd[key]
+        else:
+            out[i] = (torch.randn(n_ctx, width, generator=g) * 0.02).to(device)
+    return out
+
+
 class Transformer(nn.Module):
-    def __init__(self, sd: Dict[str, torch.Tensor], prefix: str, width: int, layers: int, heads: int, causal: bool):
+    def __init__(self, sd: Dict[str, torch.Tensor], prefix: str, width: int, layers: int, heads: int, causal: bool,
+                 prompt_depth: int = 1, prompt_rows: int = 0, prompt_tail: bool = False, prompt_seed: int = 0):
+        """``prompt_depth`` > 1: blocks 1 ... depth-1 carry a deep prompt of ``prompt_rows`` rows, placed over the last rows
+        of each sequence (``prompt_tail``: the vision tower's VPT rows) or over rows 1 ... prompt_rows (the text tower's
+        ctx rows)."""
         super().__init__()
         self.width = width
         self.layers = layers
         self.heads = heads
         self.causal = causal
+        self.prompt_depth = prompt_depth
+        self.prompt_rows = prompt_rows if prompt_depth > 1 else 0
+        self.prompt_tail = prompt_tail
+        prompts = _deep_prompts(sd, prefix, width, prompt_depth, prompt_rows, prompt_seed,
+                                sd[prefix + ".resblocks.0.ln_1.weight"].device)
         self.resblocks = nn.Sequential(*[
-            ResidualAttentionBlock(sd, f"{prefix}.resblocks.{i}.", width, heads, causal) for i in range(layers)])
+            ResidualAttentionBlock(sd, f"{prefix}.resblocks.{i}.", width, heads, causal, prompts.get(i))
+            for i in range(layers)])
 
 
 class _Conv1(nn.Module):
@@ -80,7 +113,7 @@ class VisionTransformer(nn.Module):
     """jclip/model.py:80-126; with ``n_vpt > 0`` the shallow-VPT variant of jclip/model1.py:160-207."""
 
     def __init__(self, sd: Dict[str, torch.Tensor], input_resolution: int, patch_size: int, width: int, layers: int,
-                 heads: int, output_dim: int, n_vpt: int = 0):
+                 heads: int, output_dim: int, n_vpt: int = 0, prompt_depth: int = 1):
         super().__init__()
         self.input_resolution = input_resolution
         self.patch_size = patch_size
@@ -90,12 +123,18 @@ class VisionTransformer(nn.Module):
         self.class_embedding = _param(sd["visual.class_embedding"])
         self.positional_embedding = _param(sd["visual.positional_embedding"])
         self.ln_pre = LayerNorm(sd["visual.ln_pre.weight"], sd["visual.ln_pre.bias"])
-        self.transformer = Transformer(sd, "visual.transformer", width, layers, heads, causal=False)
+        self.transformer = Transformer(sd, "visual.transformer", width, layers, heads, causal=False,
+                                       prompt_depth=prompt_depth, prompt_rows=n_vpt, prompt_tail=True, prompt_seed=1)
         self.ln_post = LayerNorm(sd["visual.ln_post.weight"], sd["visual.ln_post.bias"])
         self.proj = _param(sd["visual.proj"])
         if n_vpt > 0:
             if "visual.VPT" in sd:
                 vpt = sd["visual.VPT"]
+                # the deep prompts replace exactly the rows the VPT appended: a stored VPT of another row count would
+                # put them over patch tokens
+                if prompt_depth > 1 and tuple(vpt.shape) != (n_vpt, width):
+                    raise ValueError(f"deep prompts: visual.VPT has shape {tuple(vpt.shape)}, vision_ctx asks for "
+                                     f"{(n_vpt, width)}")
             else:  # normal_(ctx_vectors, std=0.02), model1.py:161-163
                 g = torch.Generator().manual_seed(0)
                 vpt = (torch.randn(n_vpt, width, generator=g) * 0.02).to(self.proj.device)
@@ -132,10 +171,11 @@ class CLIP(nn.Module):
         self.vocab_size = vocab_size
         self.embed_dim = embed_dim
         n_vpt = int(design_details["vision_ctx"]) if design_details else 0
+        v_depth, t_depth, n_txt = _prompt_depths(design_details, n_vpt, vision_layers, transformer_layers)
         self.visual = VisionTransformer(sd, image_resolution, vision_patch_size, vision_width, vision_layers,
-                                        vision_width // 64, embed_dim, n_vpt)
+                                        vision_width // 64, embed_dim, n_vpt, v_depth)
         self.transformer = Transformer(sd, "transformer", transformer_width, transformer_layers, transformer_heads,
-                                       causal=True)
+                                       causal=True, prompt_depth=t_depth, prompt_rows=n_txt, prompt_seed=2)
         self.token_embedding = _Embedding(sd["token_embedding.weight"])
         self.positional_embedding = _param(sd["positional_embedding"])
         self.ln_final = LayerNorm(sd["ln_final.weight"], sd["ln_final.bias"])
@@ -200,6 +240,26 @@ class CLIP(nn.Module):
 
     def cuda(self, device=None):  # tensors are created on the target device by build_model
         return self
+
+
+def _prompt_depths(design_details, n_vpt: int, vision_layers: int, text_layers: int):
+    """(vision depth, text depth, text prompt rows) of the deep prompts.  Off (depth 1 both) unless
+    ``design_details["deep_prompts"]`` is true; then ``vision_depth`` / ``language_depth`` (1 ... layers; 1 = none).  The
+    reference hard-codes 4 prompt rows per block (model1.py:80-83); here the rows are ``vision_ctx`` / ``language_ctx``
+    (identical with the default 4)."""
+    if not design_details or not design_details.get("deep_prompts", False):
+        return 1, 1, 0
+    v_depth = int(design_details.get("vision_depth", 1))
+    t_depth = int(design_details.get("language_depth", 1))
+    n_txt = int(design_details.get("language_ctx", 0))
+    for name, depth, layers in (("vision_depth", v_depth, vision_layers), ("language_depth", t_depth, text_layers)):
+        if not 1 <= depth <= layers:
+            raise ValueError(f"deep prompts: {name} {depth} outside [1, {layers}]")
+    if v_depth > 1 and n_vpt <= 0:
+        raise ValueError("deep vision prompts replace the shallow VPT rows: they need vision_ctx > 0")
+    if t_depth > 1 and n_txt <= 0:
+        raise ValueError("deep text prompts replace the ctx rows 1 ... language_ctx: they need language_ctx > 0")
+    return v_depth, t_depth, n_txt
 
 
 def _infer(sd: Dict[str, torch.Tensor]):

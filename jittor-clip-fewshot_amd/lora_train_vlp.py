@@ -507,8 +507,10 @@ def trainable_biases(model) -> List[Tuple[str, nn.Parameter]]:
     ``w_lora_A``), finds no such parameter and so hands the optimiser no bias at all -- kept as it is in
     ``get_lora_parameters`` (reference-faithful), not repeated here.
 
-    Any other CLIP parameter flagged trainable (a weight, an embedding, a LayerNorm gain) has no gradient in the fused
-    backward: ValueError naming it, instead of silently leaving it untouched."""
+    The VPT tokens and the deep prompts (``resblocks.{i}.VPT_shallow``) are trained too, but are not biases: they are left
+    out here (``FlatTrainables`` places them).  Any other CLIP parameter flagged trainable (a weight, an embedding, a
+    LayerNorm gain) has no gradient in the fused backward: ValueError naming it, instead of silently leaving it
+    untouched."""
     from clipfs.engine import image_biases, text_biases
     known = {id(p) for p in image_biases(model) + text_biases(model) if p is not None}
     out, bad = [], []
@@ -517,7 +519,7 @@ def trainable_biases(model) -> List[Tuple[str, nn.Parameter]]:
             continue
         if id(p) in known:
             out.append((n, p))
-        elif n != 'visual.VPT':  # the VPT tokens are trained as an extra tensor (LoRATrainer)
+        elif n != 'visual.VPT' and not n.endswith('.VPT_shallow'):  # VPT: an extra tensor (LoRATrainer); deep prompts
             bad.append(n)
     if bad:
         raise ValueError("the fused backward computes gradients for LoRA adapters, prompt / VPT tokens and biases only; "
@@ -525,12 +527,20 @@ def trainable_biases(model) -> List[Tuple[str, nn.Parameter]]:
     return out
 
 
+def trainable_deep_prompts(model) -> List[nn.Parameter]:
+    """The deep prompts (``resblocks.{i}.VPT_shallow``) with ``requires_grad``: text tower, then vision, block order."""
+    from clipfs.engine import deep_prompts
+    return [p for tower in (model.transformer, model.visual.transformer) for p in deep_prompts(tower) if p.requires_grad]
+
+
 class FlatTrainables:
     """Re-homes every stacked LoRA tensor (text blocks, then vision blocks: apply_lora order), the
     optional prompt / VPT tokens and the trainable biases (``trainable_biases``) into ONE contiguous fp32 buffer
     with matching gradient and AdamW moment buffers: a single RCCL all-reduce and a single optimiser launch per step.
 
-    Biases go last, so with none flagged the buffer is exactly what it was without them.  Each trainable bias parameter
+    Trainable deep prompts (``resblocks.{i}.VPT_shallow`` with ``requires_grad``; text tower, then vision, block order)
+    follow the extra tensors, and biases go last, so with neither flagged the buffer is exactly what it was without
+    them.  A deep prompt becomes a view of the buffer with ``grad_slot`` the matching gradient view, as a bias does.  Each trainable bias parameter
     becomes a view of the buffer (``state_dict`` returns the trained values) with ``grad_slot`` the matching view of the
     gradient buffer.  The packed in-projection bias the QKV GEMM reads: when all three q / k / v views of a LoRA block
     train, their slices are adjacent and the packed tensor IS that 3d slice; when only some do (``lora_only`` with
@@ -553,7 +563,9 @@ class FlatTrainables:
                     for name, p, _ in a.stacked():
                         entries.append((a, name, p))
         n_bias = sum(p.numel() for _, p in trainable_biases(model))
-        n = sum(p.numel() for _, _, p in entries) + sum(p.numel() for p in extra) + n_bias
+        deep = trainable_deep_prompts(model)
+        n = (sum(p.numel() for _, _, p in entries) + sum(p.numel() for p in extra) + sum(p.numel() for p in deep)
+             + n_bias)
         if n == 0:
             raise ValueError("model has nothing to train: no trainable adapter, bias or extra tensor (call apply_lora first)")
         dev = model.device
@@ -574,6 +586,13 @@ class FlatTrainables:
             p.data = self.params[off:off + k].view_as(p)
             p.grad_slot = self.grads[off:off + k].view_as(p)
             self.extra.append(p)
+            off += k
+        self.deep_prompts = deep
+        for p in deep:
+            k = p.numel()
+            self.params[off:off + k].copy_(p.data.reshape(-1))
+            p.data = self.params[off:off + k].view_as(p)
+            p.grad_slot = self.grads[off:off + k].view_as(p)
             off += k
         # biases (after the LoRA rebinds above: those rebuild the q / k / v / proj modules, flags carried over)
         named = dict(model.named_parameters())

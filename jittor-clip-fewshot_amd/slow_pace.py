@@ -488,7 +488,7 @@ class PromptQueue:
 class Stage2Trainer:
     """The loop body of slow_pace.py:1622-1697 as one object: prompt ctx + VPT tokens + Channel_LP head (+ the
     Moco_Adapter when ``moco_model`` / ``moco_adapter`` are given: ``loss_aux`` :1677-1680, parameters :1584-1586) are trained (the LoRA adapters stay applied but frozen: :1551-1556 clears ``requires_grad`` on
-    everything of the CLIP model that is not a VPT parameter), AdamW(weight_decay 1e-2, betas (0.9, 0.999)) with
+    everything of the CLIP model that is not a VPT parameter: the VPT tokens and the deep prompts train), AdamW(weight_decay 1e-2, betas (0.9, 0.999)) with
     ``CosineAnnealingLR(total_epoch, eta_min=1e-6)`` stepped once per iteration (:1590-1591,1696-1697).
 
     ``zs_image_features`` [N, d]: cached unit-norm zero-shot image features of the training set (``features_zs1.pkl``
@@ -511,6 +511,11 @@ class Stage2Trainer:
         if clip_model.visual.VPT is not None:
             clip_model.visual.VPT.requires_grad_(True)
             self.params.append(clip_model.visual.VPT)
+        # deep prompts (``resblocks.{i}.VPT_shallow``): their names contain "VPT", which the stage-2 rule keeps trainable
+        for n, p in clip_model.named_parameters():
+            if n.endswith(".VPT_shallow"):
+                p.requires_grad_(True)
+                self.params.append(p)
         self.params += list(channel_lp.parameters())
         if moco_adapter is not None:
             self.params += list(moco_adapter.parameters())
