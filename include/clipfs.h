@@ -84,7 +84,7 @@ typedef struct clipfs_gemm_args {
   const float* aux_in;     /* act 2: saved pre-activation (ld = ldc) */
   const float* lora_t;     /* [M, lora_nseg * lora_r] or NULL */
   const float* lora_b;     /* [N, lora_r] */
-  int lora_r, lora_nseg, lora_seg_width;
+  int lora_r, lora_nseg, lora_seg_width; /* f16 x f16 kernel: lora_r <= 64, lora_seg_width % 128 == 0 */
   float lora_scale;
   int a_mode;              /* 0 dense, 1 patch im2col */
   int img_res, patch, out_tokens; /* a_mode 1 */
@@ -235,14 +235,17 @@ int clipfs_attention_f16_bwd(const void* qkv, int qkv_f16, const void* dout, int
  * drop_s = Philox dropout of nn.Dropout(p) (:298-299), one independent stream per
  * segment s: stream id = stream_base + s, element (drow0 + m, k) as documented in DESIGN.md
  * (drow0 = index of row 0 in the GLOBAL batch: a data-parallel shard draws the masks of the
- * one-process run); p = 0 or seed == 0 disables dropout.  seg_mask bit s = 0 leaves t[:, s*r..] = 0. */
+ * one-process run); p = 0 or seed == 0 disables dropout.  seg_mask bit s = 0 leaves t[:, s*r..] = 0.
+ * Ranks: 1 <= r <= 64 with nseg * r <= 192 where the matrix-core kernels cover the shape (width % 128 == 0, nseg 1 or
+ * 3), nseg * r <= 64 elsewhere; a rank outside that is CLIPFS_EINVAL, the message naming the rank and the width. */
 int clipfs_lora_down(const float* x, const float* A, float* t, int rows, int width, int r, int nseg,
                      unsigned seg_mask, float p, uint64_t seed, uint32_t stream_base, uint32_t drow0,
                      void* keep_bits, void* stream);
 /* keep_bits (may be NULL): uint16 [rows, width/4]; with dropout active the forward records its masks there -- bit
  * 4*s + e of entry (m, c) set <=> element (m, 4*c + e) was kept for segment s -- and clipfs_lora_bwd / _f16dy given the
  * same buffer read them instead of evaluating Philox again (identical masks by construction; the adapter's dA / dx
- * products were VALU-bound on the generator).  Matrix-core kernels only: clipfs_lora_keep_bits_ok(...) != 0. */
+ * products were VALU-bound on the generator).  Matrix-core kernels only: clipfs_lora_keep_bits_ok(...) != 0
+ * (1 <= r <= 64, width % 128 == 0, nseg 1 or 3; 4 bits per segment and float4 at every rank). */
 int clipfs_lora_keep_bits_ok(int width, int segw, int r, int nseg);
 /* Backward of the adapter pair for one linear with nseg stacked segments:
  *   dt[m, s*r+j]  = scale * sum_n dy[m, s*segw + n] * B[s*segw + n, j]
@@ -250,6 +253,8 @@ int clipfs_lora_keep_bits_ok(int width, int segw, int r, int nseg);
  *   dA[s*r+j, k]  += sum_m dt[m, s*r+j] * drop_s(x)[m,k]
  *   dx[m,k]       += sum_{s,j} dt[m, s*r+j] * A[s*r+j,k] * dropscale_s(m,k)   (if dx != NULL)
  * work: caller scratch, >= clipfs_lora_bwd_work_floats(...) floats.
+ * Ranks: 1 ... 64 on the matrix-core kernels (width % 128 == 0, segw == width, nseg 1 or 3); elsewhere the
+ * one-wave-per-row kernels take r = 1, 2, 4, 8, 16 and any other rank is CLIPFS_EINVAL naming the rank and the width.
  * Frozen adapter: dA == dB == NULL computes dt and the dx contribution only -- no dB / dA partial products or slice
  * reductions are launched, and dt / dx are bitwise those of the call with slots.  With dx NULL as well only dt is
  * computed.  Exactly one of dA / dB NULL is CLIPFS_EINVAL.  The same holds for clipfs_lora_bwd_f16dy. */
@@ -260,7 +265,7 @@ int clipfs_lora_bwd(const float* dy, const float* x, const float* t, const float
                     uint32_t drow0, const void* keep_bits, float* work, void* stream);
 /* The same with dy given as its f16 image [rows, nseg*segw] (fp16 storage mode: the tensor the dgrad GEMM consumes), so
  * that the two passes over dy move half the bytes and the fp32 dy need not exist.  Matrix-core kernels only:
- * clipfs_lora_bwd_f16dy_ok(width, segw, r, nseg) != 0 says a shape is covered (r <= 16, width % 128 == 0, ...). */
+ * clipfs_lora_bwd_f16dy_ok(width, segw, r, nseg) != 0 says a shape is covered (r <= 64, width % 128 == 0, ...). */
 int clipfs_lora_bwd_f16dy_ok(int width, int segw, int r, int nseg);
 int clipfs_lora_bwd_f16dy(const void* dy16, const float* x, const float* t, const float* A, const float* B,
                           float* dt, float* dA, float* dB, float* dx, int rows, int width, int segw, int r,
@@ -469,7 +474,7 @@ typedef struct clipfs_tower {
   size_t struct_size;       /* = sizeof(clipfs_tower) of the caller's header (ABI check) */
   size_t block_size;        /* = sizeof(clipfs_block): the stride of `blocks` */
   int width, heads, layers, seq, causal;
-  int lora_r;
+  int lora_r;               /* 0 ... 64; ranks above 16 need width % 128 == 0 (the matrix-core adapter kernels) */
   float lora_scale, lora_dropout;
   uint64_t dropout_seed;    /* 0 = no dropout (eval) */
   uint32_t dropout_stream0; /* stream id of layer 0 segment 0; layer l uses stream0 + 4*l + s */

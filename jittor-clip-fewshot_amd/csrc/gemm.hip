@@ -960,8 +960,8 @@ static int gemm_nt_impl(const clipfs_gemm_args* args, void* stream) {
                    "gemm f16: K %% 32, lda/ldb %% 8, 16-byte aligned operands required");
     CLIPFS_REQUIRE(a.act >= 0 && a.act <= 2 && (a.act != 2 || a.aux_in) && (!a.residual || a.ldres >= a.N), "gemm f16: bad epilogue args");
     if (a.lora_t)
-      CLIPFS_REQUIRE(a.lora_b && a.lora_r > 0 && a.lora_r <= 16 && a.lora_nseg > 0 && a.lora_seg_width % 128 == 0 &&
-                         a.lora_seg_width * a.lora_nseg >= a.N, "gemm f16: lora rank <= 16 and segment width %% 128 required");
+      CLIPFS_REQUIRE(a.lora_b && a.lora_r > 0 && a.lora_r <= 64 && a.lora_nseg > 0 && a.lora_seg_width % 128 == 0 &&
+                         a.lora_seg_width * a.lora_nseg >= a.N, "gemm f16: lora rank <= 64 and segment width %% 128 required");
     return gemm_f16_dispatch(a, (hipStream_t)stream);
   }
   CLIPFS_REQUIRE(!a.C_f16 && !a.aux_f16, "gemm: C_f16 / aux_f16 belong to the f16 x f16 kernel only");

@@ -7,8 +7,8 @@
 //     main shape (128 fp32 accumulators per lane, two workgroups per CU);
 //   * LDS image per operand: [rows][32 k] f16 = 4 chunks of 16 B per row, chunk XOR (row >> 2) & 3 -- the same
 //     conflict-free layout as gemm_bf16.hip; three stages filled two K-steps ahead, one barrier per K-step;
-//   * the rank-r LoRA up-projection (r <= 16) is ONE extra MFMA K-step per tile: A-fragment = the rows of t,
-//     B-fragment = lora_scale * lora_b (zero padded to k = 16), both converted in registers;
+//   * the rank-r LoRA up-projection is ceil(r / 16) extra MFMA K-steps per tile (one for r <= 16): A-fragment = the
+//     rows of t, B-fragment = lora_scale * lora_b (zero padded to a multiple of 16), both converted in registers;
 //   * epilogue as gemm_common.h documents it (bias, QuickGELU / x dQuickGELU, residual), writing fp32 C and/or an
 //     f16 copy C16 for the next GEMM.
 // Rows that do not fill a whole BM block are better served by a second launch with a smaller tile (the caller --
@@ -55,45 +55,48 @@ struct F16Params {
 };
 
 // What both f16 kernels do after their K loop for the TM x TN accumulator tiles of one wave whose first row / column
-// are mw / nw: the rank-r LoRA up-projection as ONE more MFMA K-step, then the fused epilogue.
+// are mw / nw: the rank-r LoRA up-projection as ceil(r / 16) more MFMA K-steps (one for r <= 16), then the fused
+// epilogue.
 template <int TM, int TN>
 __device__ __forceinline__ void f16_lora_step(const F16Params& p, f32x16 (&acc)[TM][TN], int mw, int nw, int n0, int lane) {
   const clipfs_gemm_args& g = p.a;
   const int fr = lane & 31, fh = lane >> 5;
   const int Mend = p.m_end, N = g.N;
-  // ---- LoRA up-projection: one more K-step of 16 (rank zero-padded), operands converted in registers ----------
+  // ---- LoRA up-projection: K-steps of 16 (rank zero-padded), operands converted in registers -----------------
   if (g.lora_t) {
     const int r = g.lora_r;
     const int seg = n0 / g.lora_seg_width;  // the host guarantees a block tile lies inside one segment
-    f16x8 av[TM], bv[TN];
+    for (int k0 = 0; k0 < r; k0 += 16) {
+      f16x8 av[TM], bv[TN];
 #pragma unroll
-    for (int t = 0; t < TM; ++t) {
-      const int m = min(mw + t * 32 + fr, Mend - 1);
-      const float* tp = g.lora_t + (size_t)m * (g.lora_nseg * r) + seg * r;
+      for (int t = 0; t < TM; ++t) {
+        const int m = min(mw + t * 32 + fr, Mend - 1);
+        const float* tp = g.lora_t + (size_t)m * (g.lora_nseg * r) + seg * r;
 #pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const int k = 8 * fh + j;
-        av[t][j] = (_Float16)(tp[min(k, r - 1)] * (k < r ? 1.f : 0.f));
+        for (int j = 0; j < 8; ++j) {
+          const int k = k0 + 8 * fh + j;
+          av[t][j] = (_Float16)(tp[min(k, r - 1)] * (k < r ? 1.f : 0.f));
+        }
       }
-    }
 #pragma unroll
-    for (int t = 0; t < TN; ++t) {
-      const int n = min(nw + t * 32 + fr, N - 1);
-      const float* lb = g.lora_b + (size_t)n * r;
+      for (int t = 0; t < TN; ++t) {
+        const int n = min(nw + t * 32 + fr, N - 1);
+        const float* lb = g.lora_b + (size_t)n * r;
 #pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const int k = 8 * fh + j;
-        bv[t][j] = (_Float16)(lb[min(k, r - 1)] * (k < r ? g.lora_scale : 0.f));
+        for (int j = 0; j < 8; ++j) {
+          const int k = k0 + 8 * fh + j;
+          bv[t][j] = (_Float16)(lb[min(k, r - 1)] * (k < r ? g.lora_scale : 0.f));
+        }
       }
+#pragma unroll
+      for (int i = 0; i < TM; ++i)
+#pragma unroll
+        for (int j = 0; j < TN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(av[i], bv[j], acc[i][j], 0, 0, 0);
     }
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-      for (int j = 0; j < TN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(av[i], bv[j], acc[i][j], 0, 0, 0);
   }
 }
 
-// the same step for 8 x 4 accumulator tiles of v_mfma_f32_16x16x32_f16 (rank zero-padded to k = 32)
+// the same step for 8 x 4 accumulator tiles of v_mfma_f32_16x16x32_f16: ceil(r / 32) K-steps (rank zero-padded)
 __device__ __forceinline__ void f16_lora_step16(const F16Params& p, f32x4 (&acc)[8][4], int mw, int nw, int n0, int lane) {
   const clipfs_gemm_args& g = p.a;
   if (!g.lora_t) return;
@@ -101,32 +104,34 @@ __device__ __forceinline__ void f16_lora_step16(const F16Params& p, f32x4 (&acc)
   const int Mend = p.m_end, N = g.N;
   const int r = g.lora_r;
   const int seg = n0 / g.lora_seg_width;
-  f16x8 bv[4];
+  for (int k0 = 0; k0 < r; k0 += 32) {
+    f16x8 bv[4];
 #pragma unroll
-  for (int t = 0; t < 4; ++t) {
-    const int n = min(nw + t * 16 + li, N - 1);
-    const float* lb = g.lora_b + (size_t)n * r;
+    for (int t = 0; t < 4; ++t) {
+      const int n = min(nw + t * 16 + li, N - 1);
+      const float* lb = g.lora_b + (size_t)n * r;
 #pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const int k = 8 * lg + j;
-      bv[t][j] = (_Float16)(lb[min(k, r - 1)] * (k < r ? g.lora_scale : 0.f));
+      for (int j = 0; j < 8; ++j) {
+        const int k = k0 + 8 * lg + j;
+        bv[t][j] = (_Float16)(lb[min(k, r - 1)] * (k < r ? g.lora_scale : 0.f));
+      }
     }
-  }
-  f16x8 av[8];
+    f16x8 av[8];
 #pragma unroll
-  for (int t = 0; t < 8; ++t) {
-    const int m = min(mw + t * 16 + li, Mend - 1);
-    const float* tp = g.lora_t + (size_t)m * (g.lora_nseg * r) + seg * r;
+    for (int t = 0; t < 8; ++t) {
+      const int m = min(mw + t * 16 + li, Mend - 1);
+      const float* tp = g.lora_t + (size_t)m * (g.lora_nseg * r) + seg * r;
 #pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const int k = 8 * lg + j;
-      av[t][j] = (_Float16)(tp[min(k, r - 1)] * (k < r ? 1.f : 0.f));
+      for (int j = 0; j < 8; ++j) {
+        const int k = k0 + 8 * lg + j;
+        av[t][j] = (_Float16)(tp[min(k, r - 1)] * (k < r ? 1.f : 0.f));
+      }
     }
+#pragma unroll
+    for (int i = 0; i < 8; ++i)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(av[i], bv[j], acc[i][j], 0, 0, 0);
   }
-#pragma unroll
-  for (int i = 0; i < 8; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(av[i], bv[j], acc[i][j], 0, 0, 0);
 }
 
 template <int TM, int TN>

@@ -10,7 +10,8 @@
 namespace clipfs {
 
 constexpr int LORA_MAX_CHUNKS = 8;  // width <= 2048
-constexpr int LORA_MAX_OUT = 64;    // nseg * r
+constexpr int LORA_MAX_OUT = 64;    // nseg * r of the one-wave-per-row kernel
+constexpr int LORA_MFMA_MAX_OUT = 192;  // nseg * r of the matrix-core kernels (3 segments x r <= 64)
 
 // one wave per row
 __global__ __launch_bounds__(256) void lora_down_kernel(const float* __restrict__ x, const float* __restrict__ A,
@@ -273,6 +274,7 @@ static inline int lora_slice_rows(int rows) {
 
 // lora_mfma.hip
 bool lora_mfma_ok(int width, int segw, int r, int nseg);
+size_t lora_mfma_work_floats(int rows, int width, int segw, int r, int nseg);
 int lora_down_mfma(const float* x, const float* A, float* t, int rows, int width, int r, int nseg, unsigned seg_mask,
                    float p, uint64_t seed, uint32_t stream_base, uint32_t drow0, uint16_t* keep_bits, hipStream_t st);
 typedef void (*lora_reduce2_fn)(const float*, float*, size_t, int, float, const float*, float*, size_t, int, float, hipStream_t);
@@ -315,10 +317,13 @@ extern "C" int clipfs_lora_down(const float* x, const float* A, float* t, int ro
   CLIPFS_REQUIRE(!keep_bits || clipfs_lora_keep_bits_ok(width, width, r, nseg),
                  "lora_down: keep bits are recorded by the matrix-core kernels only (width %d r %d nseg %d)", width, r, nseg);
   CLIPFS_REQUIRE(rows > 0 && width > 0 && (width & 3) == 0 && width <= 256 * LORA_MAX_CHUNKS, "lora_down: width %d unsupported", width);
-  CLIPFS_REQUIRE(r > 0 && r <= 64 && nseg > 0 && nseg <= 4 && nseg * r <= LORA_MAX_OUT, "lora_down: r %d nseg %d unsupported", r, nseg);
+  const bool mfma = use_lora_mfma() && lora_mfma_ok(width, width, r, nseg);
+  CLIPFS_REQUIRE(r > 0 && r <= 64 && nseg > 0 && nseg <= 4 && nseg * r <= (mfma ? LORA_MFMA_MAX_OUT : LORA_MAX_OUT),
+                 "lora_down: rank %d x %d segments unsupported at width %d (%d outputs per row at most%s)", r, nseg, width,
+                 mfma ? LORA_MFMA_MAX_OUT : LORA_MAX_OUT, mfma ? "" : "; more need width % 128 == 0");
   CLIPFS_REQUIRE(p >= 0.f && p < 1.f, "lora_down: dropout p %f out of range", (double)p);
   CLIPFS_REQUIRE(aligned16(x) && aligned16(A), "lora_down: misaligned pointer");
-  if (use_lora_mfma() && lora_mfma_ok(width, width, r, nseg))
+  if (mfma)
     return lora_down_mfma(x, A, t, rows, width, r, nseg, seg_mask, p, seed, stream_base, drow0,
                           reinterpret_cast<uint16_t*>(keep_bits), (hipStream_t)stream);
   hipLaunchKernelGGL(lora_down_kernel, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, x, A, t, rows, width, r,
@@ -327,6 +332,9 @@ extern "C" int clipfs_lora_down(const float* x, const float* A, float* t, int ro
 }
 
 extern "C" size_t clipfs_lora_bwd_work_floats(int rows, int width, int r, int nseg) {
+  // r > 16 runs on the matrix-core kernels only: their own slice plan (which counts the rank groups as work, so the
+  // slices get longer as r grows) is the bound.  r <= 16 keeps the bound of both paths, unchanged.
+  if (r > 16) return lora_mfma_work_floats(rows, width, width, r, nseg) + 64;
   const int sr = lora_slice_rows(rows);
   const size_t slices = (size_t)(rows + sr - 1) / sr;
   // dB partials: slices * (nseg*segw) * r with segw <= 4*width (MLP never adapted; q/k/v/o segw == width)
@@ -404,7 +412,8 @@ extern "C" int clipfs_lora_bwd(const float* dy, const float* x, const float* t, 
     CLIPFS_LORA_CASE(8);
     CLIPFS_LORA_CASE(16);
     default:
-      set_error("lora_bwd: rank %d unsupported (1, 2, 4, 8, 16)", r);
+      set_error("lora_bwd: rank %d unsupported at width %d (one-wave-per-row kernels: 1, 2, 4, 8, 16; ranks up to 64 "
+                "need width %% 128 == 0)", r, width);
       return CLIPFS_EINVAL;
   }
 #undef CLIPFS_LORA_CASE

@@ -1,8 +1,10 @@
 // Rank-r LoRA products on the matrix cores, exact fp32 (v_mfma_f32_16x16x4_f32: the fp32 MFMA of the dense GEMMs
-// in its 16x16 shape, whose N = 16 fits ranks up to 16).  Same five products, same Philox dropout stream and same
-// results (up to summation order) as the one-wave-per-row kernels in lora.hip, which remain for shapes outside
-// r <= 16 / width % 64 == 0.  At r = 16 (cfg-5) the scalar kernels spend ~50 wave reductions per row; here every
-// product is a tall-skinny MFMA GEMM whose big operand is read once with 16-byte loads:
+// in its 16x16 shape).  Same five products, same Philox dropout stream and same results (up to summation order) as
+// the one-wave-per-row kernels in lora.hip, which remain for shapes outside width % 128 == 0 (ranks 1, 2, 4, 8, 16
+// there).  At r = 16 (cfg-5) the scalar kernels spend ~50 wave reductions per row; here every product is a tall-skinny
+// MFMA GEMM whose big operand is read once with 16-byte loads.  Ranks 1..64 run as G = ceil(r / 16) groups of 16
+// rank columns (N = 16 of the MFMA); a wave keeps all G groups' accumulators, so x or dy is still read once, and its
+// dropout masks drawn once, whatever the rank.  G = 1 is the r <= 16 arithmetic in its original order.
 //
 //   down  t[m, s r + j]   = sum_k drop_s(x)[m, k] A[s r + j, k]          A-operand = x rows, B-operand = A rows
 //   dt    dt[m, s r + j]  = scale sum_n dy[m, s w + n] B[s w + n, j]
@@ -59,14 +61,15 @@ __device__ __forceinline__ void block_sum4(f32x4 (&acc)[NACC], f32x4* red, int w
 }
 
 // t = drop(x) A^T.  One block per 16 rows; its 4 waves take a quarter of the columns each (rows / 16 waves alone
-// would leave ~2 waves per SIMD).
-template <int NSEG>
+// would leave ~2 waves per SIMD).  G = ceil(r / 16) rank groups of 16 output columns: every float4 of x (and its one
+// Philox call) feeds all G groups, so x is read once whatever the rank.
+template <int NSEG, int G>
 __global__ __launch_bounds__(256) void lora_down_mfma_kernel(const float* __restrict__ x, const float* __restrict__ A,
                                                              float* __restrict__ t, int rows, int width, int r,
                                                              unsigned seg_mask, float p, uint64_t seed,
                                                              uint32_t stream_base, uint32_t drow0,
                                                              uint16_t* __restrict__ keep_bits) {
-  __shared__ f32x4 red[3 * NSEG * 64];
+  __shared__ f32x4 red[3 * NSEG * G * 64];
   const int lane = threadIdx.x & 63, li = lane & 15, kg = lane >> 4;
   const int wave = threadIdx.x >> 6;
   const int row0 = blockIdx.x * 16;
@@ -75,10 +78,12 @@ __global__ __launch_bounds__(256) void lora_down_mfma_kernel(const float* __rest
   const uint32_t thr = dropout_threshold(p);
   const float inv_keep = 1.f / (1.f - p);
   const float* xr = x + (size_t)m * width + 4 * kg;
-  const float* ar = A + (size_t)min(li, r - 1) * width + 4 * kg;
-  f32x4 acc[NSEG];
+  const float* ar[G];  // row of A (segment 0) this lane feeds in rank group g
 #pragma unroll
-  for (int s = 0; s < NSEG; ++s) acc[s] = zero4();
+  for (int g = 0; g < G; ++g) ar[g] = A + (size_t)min(16 * g + li, r - 1) * width + 4 * kg;
+  f32x4 acc[NSEG * G];  // [s][g]
+#pragma unroll
+  for (int s = 0; s < NSEG * G; ++s) acc[s] = zero4();
   const int cw = width >> 2;  // columns per wave (width % 64 == 0)
   const int cend = (wave + 1) * cw;
   for (int c0 = wave * cw; c0 < cend; c0 += 64) {  // 4 steps of 16 columns, loads first
@@ -93,9 +98,11 @@ __global__ __launch_bounds__(256) void lora_down_mfma_kernel(const float* __rest
 #pragma unroll
     for (int s = 0; s < NSEG; ++s) {
       if (!((seg_mask >> s) & 1u)) continue;
-      f32x4 wv[4];
+      f32x4 wv[G][4];
 #pragma unroll
-      for (int u = 0; u < 4; ++u) wv[u] = ld4(ar + (size_t)s * r * width + min(c0 + 16 * u, cend - 16));
+      for (int g = 0; g < G; ++g)
+#pragma unroll
+        for (int u = 0; u < 4; ++u) wv[g][u] = ld4(ar[g] + (size_t)s * r * width + min(c0 + 16 * u, cend - 16));
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
         f32x4 xs = xv[u];
@@ -108,7 +115,9 @@ __global__ __launch_bounds__(256) void lora_down_mfma_kernel(const float* __rest
           kb[u] |= keep_bits4(mk) << (4 * s);
         }
 #pragma unroll
-        for (int e = 0; e < 4; ++e) acc[s] = mfma16(xs[e], wv[u][e], acc[s]);
+        for (int g = 0; g < G; ++g)
+#pragma unroll
+          for (int e = 0; e < 4; ++e) acc[s * G + g] = mfma16(xs[e], wv[g][u][e], acc[s * G + g]);
       }
     }
     if (keep_bits && drop && row0 + li < rows) {  // the masks of this pass, for the backward (4 bits per segment and float4)
@@ -117,21 +126,26 @@ __global__ __launch_bounds__(256) void lora_down_mfma_kernel(const float* __rest
         if (c0 + 16 * u < cend) keep_bits[(size_t)m * (width >> 2) + ((c0 + 16 * u) >> 2) + kg] = (uint16_t)kb[u];
     }
   }
-  block_sum4<NSEG>(acc, red, wave, lane);
-  if (wave == 0 && li < r) {
+  block_sum4<NSEG * G>(acc, red, wave, lane);
+  if (wave == 0) {
 #pragma unroll
-    for (int v = 0; v < 4; ++v) {
-      const int mo = row0 + 4 * kg + v;
-      if (mo < rows) {
+    for (int g = 0; g < G; ++g) {
+      const int j = 16 * g + li;
+      if (j >= r) continue;
 #pragma unroll
-        for (int s = 0; s < NSEG; ++s) t[(size_t)mo * (NSEG * r) + s * r + li] = ((seg_mask >> s) & 1u) ? acc[s][v] : 0.f;
+      for (int v = 0; v < 4; ++v) {
+        const int mo = row0 + 4 * kg + v;
+        if (mo < rows) {
+#pragma unroll
+          for (int s = 0; s < NSEG; ++s) t[(size_t)mo * (NSEG * r) + s * r + j] = ((seg_mask >> s) & 1u) ? acc[s * G + g][v] : 0.f;
+        }
       }
     }
   }
 }
 
-// dt = scale * dy_seg B_seg.  One block (index bx) per 16 rows.
-template <int NSEG, typename TY>
+// dt = scale * dy_seg B_seg.  One block (index bx) per 16 rows; each float4 of dy feeds all G rank groups.
+template <int NSEG, int G, typename TY>
 __device__ __forceinline__ void lora_dt_mfma_body(const TY* __restrict__ dy, const float* __restrict__ B,
                                                   float* __restrict__ dt, int rows, int segw, int r, unsigned seg_mask,
                                                   float scale, int bx, f32x4* red) {
@@ -141,49 +155,60 @@ __device__ __forceinline__ void lora_dt_mfma_body(const TY* __restrict__ dy, con
   const int m = min(row0 + li, rows - 1);
   const int cw = segw >> 2;
   const TY* dr = dy + (size_t)m * NSEG * segw + 4 * kg;
-  const int jj = min(li, r - 1);
-  f32x4 acc[NSEG];
+  f32x4 acc[NSEG * G];  // [s][g]
 #pragma unroll
-  for (int s = 0; s < NSEG; ++s) acc[s] = zero4();
+  for (int s = 0; s < NSEG * G; ++s) acc[s] = zero4();
 #pragma unroll
   for (int s = 0; s < NSEG; ++s) {
     if (!((seg_mask >> s) & 1u)) continue;
-    const float* bs = B + ((size_t)s * segw + 4 * kg) * r + jj;
+    const float* bs[G];  // column of B this lane feeds in rank group g
+#pragma unroll
+    for (int g = 0; g < G; ++g) bs[g] = B + ((size_t)s * segw + 4 * kg) * r + min(16 * g + li, r - 1);
     const int cend = (wave + 1) * cw;
     for (int c0 = wave * cw; c0 < cend; c0 += 64) {
-      f32x4 g[4];
-      float bv[4][4];
+      f32x4 gv[4];
+      float bv[4][G][4];
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
         const int cu = min(c0 + 16 * u, cend - 16);
-        g[u] = ld4(dr + s * segw + cu);
-        if (c0 + 16 * u >= cend) g[u] = zero4();
-        const float* bp = bs + (size_t)cu * r;
+        gv[u] = ld4(dr + s * segw + cu);
+        if (c0 + 16 * u >= cend) gv[u] = zero4();
 #pragma unroll
-        for (int e = 0; e < 4; ++e) bv[u][e] = bp[e * r];
+        for (int g = 0; g < G; ++g) {
+          const float* bp = bs[g] + (size_t)cu * r;
+#pragma unroll
+          for (int e = 0; e < 4; ++e) bv[u][g][e] = bp[e * r];
+        }
       }
 #pragma unroll
       for (int u = 0; u < 4; ++u)
 #pragma unroll
-        for (int e = 0; e < 4; ++e) acc[s] = mfma16(g[u][e], bv[u][e], acc[s]);
+        for (int e = 0; e < 4; ++e)
+#pragma unroll
+          for (int g = 0; g < G; ++g) acc[s * G + g] = mfma16(gv[u][e], bv[u][g][e], acc[s * G + g]);
     }
   }
-  block_sum4<NSEG>(acc, red, wave, lane);
-  if (wave == 0 && li < r) {
+  block_sum4<NSEG * G>(acc, red, wave, lane);
+  if (wave == 0) {
 #pragma unroll
-    for (int v = 0; v < 4; ++v) {
-      const int mo = row0 + 4 * kg + v;
-      if (mo < rows) {
+    for (int g = 0; g < G; ++g) {
+      const int j = 16 * g + li;
+      if (j >= r) continue;
 #pragma unroll
-        for (int s = 0; s < NSEG; ++s) dt[(size_t)mo * (NSEG * r) + s * r + li] = scale * acc[s][v];
+      for (int v = 0; v < 4; ++v) {
+        const int mo = row0 + 4 * kg + v;
+        if (mo < rows) {
+#pragma unroll
+          for (int s = 0; s < NSEG; ++s) dt[(size_t)mo * (NSEG * r) + s * r + j] = scale * acc[s * G + g][v];
+        }
       }
     }
   }
 }
 
 // dB partials: part[slice][n][j] = sum_{m in slice} dy[m, n] t[m, seg(n) r + j].  One wave per (64 columns, slice);
-// lane i owns columns n0 + 4 i + e of MFMA tile e.
-template <typename TY>
+// lane i owns columns n0 + 4 i + e of MFMA tile e; each float4 of dy feeds all G rank groups.
+template <int G, typename TY>
 __device__ __forceinline__ void lora_db_mfma_body(const TY* __restrict__ dy, const float* __restrict__ t,
                                                   float* __restrict__ part, int rows, int cols, int segw, int nseg, int r,
                                                   int rows_per_slice, int bx, int by) {
@@ -195,42 +220,54 @@ __device__ __forceinline__ void lora_db_mfma_body(const TY* __restrict__ dy, con
   const int s = n0 / segw;
   const int tw = nseg * r;
   const TY* dp = dy + n0 + 4 * li;
-  const float* tp = t + s * r + min(li, r - 1);
-  f32x4 acc[4];
+  const float* tp[G];  // rank column of t this lane feeds in group g
 #pragma unroll
-  for (int e = 0; e < 4; ++e) acc[e] = zero4();
+  for (int g = 0; g < G; ++g) tp[g] = t + s * r + min(16 * g + li, r - 1);
+  f32x4 acc[G][4];
+#pragma unroll
+  for (int g = 0; g < G; ++g)
+#pragma unroll
+    for (int e = 0; e < 4; ++e) acc[g][e] = zero4();
 
   for (int mb = m0; mb < m1; mb += 16) {  // 4 steps of 4 rows, loads first
-    f32x4 g[4];
-    float tv[4];
+    f32x4 gv[4];
+    float tv[4][G];
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       const int m = mb + 4 * u + kg;
       const bool ok = m < m1;
       const int mc = ok ? m : m1 - 1;
-      g[u] = ld4(dp + (size_t)mc * cols);
-      tv[u] = tp[(size_t)mc * tw];
+      gv[u] = ld4(dp + (size_t)mc * cols);
+#pragma unroll
+      for (int g = 0; g < G; ++g) tv[u][g] = tp[g][(size_t)mc * tw];
       if (!ok) {
-        g[u] = zero4();
-        tv[u] = 0.f;
+        gv[u] = zero4();
+#pragma unroll
+        for (int g = 0; g < G; ++g) tv[u][g] = 0.f;
       }
     }
 #pragma unroll
     for (int u = 0; u < 4; ++u)
 #pragma unroll
-      for (int e = 0; e < 4; ++e) acc[e] = mfma16(g[u][e], tv[u], acc[e]);
+      for (int e = 0; e < 4; ++e)
+#pragma unroll
+        for (int g = 0; g < G; ++g) acc[g][e] = mfma16(gv[u][e], tv[u][g], acc[g][e]);
   }
-  if (li < r) {
+#pragma unroll
+  for (int g = 0; g < G; ++g) {
+    const int j = 16 * g + li;
+    if (j >= r) continue;
 #pragma unroll
     for (int e = 0; e < 4; ++e)
 #pragma unroll
-      for (int v = 0; v < 4; ++v) part[((size_t)slice * cols + n0 + 4 * (4 * kg + v) + e) * r + li] = acc[e][v];
+      for (int v = 0; v < 4; ++v) part[((size_t)slice * cols + n0 + 4 * (4 * kg + v) + e) * r + j] = acc[g][e][v];
   }
 }
 
 // dA partials: part[slice][s r + j][k] = sum_{m in slice} dt[m, s r + j] drop_s(x)[m, k].  One wave per (64 columns,
-// slice); lane i owns columns k0 + 4 i + e of MFMA tile e (so one Philox call covers the lane's float4 of x).
-template <int NSEG>
+// slice); lane i owns columns k0 + 4 i + e of MFMA tile e (so one Philox call covers the lane's float4 of x, and that
+// float4 feeds all G rank groups).
+template <int NSEG, int G>
 __device__ __forceinline__ void lora_da_mfma_body(const float* __restrict__ x, const float* __restrict__ dt,
                                                   float* __restrict__ part, int rows, int width, int r, unsigned seg_mask,
                                                   float p, uint64_t seed, uint32_t stream_base, uint32_t drow0,
@@ -246,16 +283,20 @@ __device__ __forceinline__ void lora_da_mfma_body(const float* __restrict__ x, c
   const float inv_keep = 1.f / (1.f - p);
   const int tw = NSEG * r;
   const float* xp = x + k0 + 4 * li;
-  const float* dp = dt + min(li, r - 1);
+  const float* dp[G];  // rank column of dt this lane feeds in group g
+#pragma unroll
+  for (int g = 0; g < G; ++g) dp[g] = dt + min(16 * g + li, r - 1);
   const uint32_t c4 = (uint32_t)((k0 >> 2) + li);
-  f32x4 acc[NSEG][4];
+  f32x4 acc[NSEG][G][4];
 #pragma unroll
   for (int s = 0; s < NSEG; ++s)
 #pragma unroll
-    for (int e = 0; e < 4; ++e) acc[s][e] = zero4();
+    for (int g = 0; g < G; ++g)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) acc[s][g][e] = zero4();
   for (int mb = m0; mb < m1; mb += 8) {  // 2 steps of 4 rows, loads first
     f32x4 xv[2];
-    float g[2][NSEG];
+    float gv[2][NSEG][G];
     int mcs[2];
     uint32_t kbu[2] = {0u, 0u};
 #pragma unroll
@@ -267,7 +308,9 @@ __device__ __forceinline__ void lora_da_mfma_body(const float* __restrict__ x, c
       if (keep_bits) kbu[u] = keep_bits[(size_t)mcs[u] * (width >> 2) + c4];
       if (!ok) xv[u] = zero4();
 #pragma unroll
-      for (int s = 0; s < NSEG; ++s) g[u][s] = dp[(size_t)mcs[u] * tw + s * r];
+      for (int s = 0; s < NSEG; ++s)
+#pragma unroll
+        for (int g = 0; g < G; ++g) gv[u][s][g] = dp[g][(size_t)mcs[u] * tw + s * r];
     }
 #pragma unroll
     for (int u = 0; u < 2; ++u)
@@ -284,32 +327,42 @@ __device__ __forceinline__ void lora_da_mfma_body(const float* __restrict__ x, c
           xs[3] *= mk.w;
         }
 #pragma unroll
-        for (int e = 0; e < 4; ++e) acc[s][e] = mfma16(g[u][s], xs[e], acc[s][e]);
+        for (int g = 0; g < G; ++g)
+#pragma unroll
+          for (int e = 0; e < 4; ++e) acc[s][g][e] = mfma16(gv[u][s][g], xs[e], acc[s][g][e]);
       }
   }
-  // result tile e: D[i = rank index 4 kg + v][j = li] <-> column k0 + 4 li + e: one float4 per (s, v)
+  // result tile e: D[i = rank index 16 g + 4 kg + v][j = li] <-> column k0 + 4 li + e: one float4 per (s, g, v)
 #pragma unroll
   for (int s = 0; s < NSEG; ++s)
 #pragma unroll
-    for (int v = 0; v < 4; ++v) {
-      const int j = 4 * kg + v;
-      if (j < r) {
-        f32x4 o;
+    for (int g = 0; g < G; ++g)
 #pragma unroll
-        for (int e = 0; e < 4; ++e) o[e] = acc[s][e][v];
-        *reinterpret_cast<f32x4*>(part + ((size_t)slice * tw + s * r + j) * width + k0 + 4 * li) = o;
+      for (int v = 0; v < 4; ++v) {
+        const int j = 16 * g + 4 * kg + v;
+        if (j < r) {
+          f32x4 o;
+#pragma unroll
+          for (int e = 0; e < 4; ++e) o[e] = acc[s][g][e][v];
+          *reinterpret_cast<f32x4*>(part + ((size_t)slice * tw + s * r + j) * width + k0 + 4 * li) = o;
+        }
       }
-    }
 }
 
 // dx[m, k] += sum_s dropscale_s(m, k) sum_j dt[m, s r + j] A[s r + j, k].  One block per 16 rows (its 4 waves take a
 // quarter of the columns each); per 16-column tile
 // the result D[i <-> column k0 + i][j <-> row] gives a lane 4 consecutive columns of one row: a float4 of dx.
-template <int NSEG, int RQ>  // RQ = ceil(r / 4) MFMA K-steps
+// RQ = ceil(r / 4) MFMA K-steps for r <= 16 (one rank group), 4 G above (ranks past r enter as zeros).  The lane's
+// dt values stay in registers for the whole row.  Rank group 0's A values are loaded first, as at r <= 16; groups
+// 1 ... G-1 are streamed (4 K-steps at a time) from one base per segment, so that neither the A values nor their
+// addresses held at once grow with the rank.
+template <int NSEG, int RQ>
 __device__ __forceinline__ void lora_dx_mfma_body(const float* __restrict__ dt, const float* __restrict__ A,
                                                   float* __restrict__ dx, int rows, int width, int r, unsigned seg_mask,
                                                   float p, uint64_t seed, uint32_t stream_base, uint32_t drow0, int bx,
                                                   const uint16_t* __restrict__ keep_bits) {
+  constexpr int QG = RQ < 4 ? RQ : 4;  // K-steps per rank group
+  constexpr int G = (RQ + 3) / 4;
   const int lane = threadIdx.x & 63, li = lane & 15, kg = lane >> 4;
   const int wave = threadIdx.x >> 6;
   const int row0 = bx * 16;
@@ -320,22 +373,20 @@ __device__ __forceinline__ void lora_dx_mfma_body(const float* __restrict__ dt, 
   const uint32_t thr = dropout_threshold(p);
   const float inv_keep = 1.f / (1.f - p);
   float dtv[NSEG][RQ];  // B operand: k = rank index 4 q + kg, j = row li
-  const float* ap[NSEG][RQ];
-  float amask[RQ];
+  const float* ap[NSEG][QG];  // rank group 0's rows of A
 #pragma unroll
   for (int q = 0; q < RQ; ++q) {
     const int j = 4 * q + kg;
-    amask[q] = j < r ? 1.f : 0.f;
 #pragma unroll
     for (int s = 0; s < NSEG; ++s) {
-      dtv[s][q] = dt[(size_t)mc * (NSEG * r) + s * r + min(j, r - 1)] * amask[q];
-      ap[s][q] = A + (size_t)(s * r + min(j, r - 1)) * width + li;
+      dtv[s][q] = dt[(size_t)mc * (NSEG * r) + s * r + min(j, r - 1)] * (j < r ? 1.f : 0.f);
+      if (q < QG) ap[s][q] = A + (size_t)(s * r + min(j, r - 1)) * width + li;
     }
   }
   float* xr = dx + (size_t)mc * width + 4 * kg;
   for (int k0 = wave * cw; k0 < (wave + 1) * cw; k0 += 32) {  // two 16-column tiles, loads first (cw % 32 == 0)
     f32x4 tot[2];
-    float av[2][NSEG][RQ];
+    float av[2][NSEG][QG];
     uint32_t kbu[2] = {0u, 0u};
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
@@ -344,7 +395,7 @@ __device__ __forceinline__ void lora_dx_mfma_body(const float* __restrict__ dt, 
 #pragma unroll
       for (int s = 0; s < NSEG; ++s)
 #pragma unroll
-        for (int q = 0; q < RQ; ++q) av[u][s][q] = ap[s][q][k0 + 16 * u];
+        for (int q = 0; q < QG; ++q) av[u][s][q] = ap[s][q][k0 + 16 * u];
     }
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
@@ -353,7 +404,16 @@ __device__ __forceinline__ void lora_dx_mfma_body(const float* __restrict__ dt, 
         if (!((seg_mask >> s) & 1u)) continue;
         f32x4 acc = zero4();
 #pragma unroll
-        for (int q = 0; q < RQ; ++q) acc = mfma16(av[u][s][q], dtv[s][q], acc);
+        for (int q = 0; q < QG; ++q) acc = mfma16(av[u][s][q], dtv[s][q], acc);
+#pragma unroll
+        for (int g = 1; g < G; ++g) {  // r > 16: the further rank groups, streamed
+          float ag[4];
+#pragma unroll
+          for (int q = 0; q < 4; ++q)
+            ag[q] = A[(size_t)(s * r + min(4 * (4 * g + q) + kg, r - 1)) * width + li + k0 + 16 * u];
+#pragma unroll
+          for (int q = 0; q < 4; ++q) acc = mfma16(ag[q], dtv[s][4 * g + q], acc);
+        }
         if (drop) {
           const float4 mk = keep_bits ? keep_scale4(kbu[u] >> (4 * s), inv_keep)
                                       : dropout_scale4(seed, stream_base + s, drow0 + (uint32_t)mc, (uint32_t)(((k0 + 16 * u) >> 2) + kg), thr, inv_keep);
@@ -374,18 +434,18 @@ __device__ __forceinline__ void lora_dx_mfma_body(const float* __restrict__ dt, 
 // pair is ONE launch whose leading blocks do the first product and whose trailing blocks do the second (the bodies
 // above, unchanged: same arithmetic, same results): at the per-rank sizes of the 8-GPU step every one of these products
 // is a few microseconds of work behind ~10 us of launch, and the two halves of a pair fill each other's tail.
-template <int NSEG, typename TY>
+template <int NSEG, int G, typename TY>
 __global__ __launch_bounds__(256) void lora_db_dt_mfma_kernel(const TY* __restrict__ dy, const float* __restrict__ B,
                                                               const float* __restrict__ t, float* __restrict__ dt,
                                                               float* __restrict__ part_b, int rows, int segw, int r,
                                                               unsigned seg_mask, float scale, int rows_per_slice,
                                                               int gx_b, int n_db) {
-  __shared__ f32x4 red[3 * NSEG * 64];
+  __shared__ f32x4 red[3 * NSEG * G * 64];
   const int b = blockIdx.x;
   if (b < n_db)
-    lora_db_mfma_body<TY>(dy, t, part_b, rows, NSEG * segw, segw, NSEG, r, rows_per_slice, b % gx_b, b / gx_b);
+    lora_db_mfma_body<G, TY>(dy, t, part_b, rows, NSEG * segw, segw, NSEG, r, rows_per_slice, b % gx_b, b / gx_b);
   else
-    lora_dt_mfma_body<NSEG, TY>(dy, B, dt, rows, segw, r, seg_mask, scale, b - n_db, red);
+    lora_dt_mfma_body<NSEG, G, TY>(dy, B, dt, rows, segw, r, seg_mask, scale, b - n_db, red);
 }
 
 template <int NSEG, int RQ>
@@ -397,8 +457,8 @@ __global__ __launch_bounds__(256) void lora_da_dx_mfma_kernel(const float* __res
                                                               int gx_a, int n_da, const uint16_t* __restrict__ keep_bits) {
   const int b = blockIdx.x;
   if (b < n_da)
-    lora_da_mfma_body<NSEG>(x, dt, part_a, rows, width, r, seg_mask, p, seed, stream_base, drow0, rows_per_slice, b % gx_a,
-                            b / gx_a, keep_bits);
+    lora_da_mfma_body<NSEG, (RQ + 3) / 4>(x, dt, part_a, rows, width, r, seg_mask, p, seed, stream_base, drow0, rows_per_slice,
+                                          b % gx_a, b / gx_a, keep_bits);
   else
     lora_dx_mfma_body<NSEG, RQ>(dt, A, dx, rows, width, r, seg_mask, p, seed, stream_base, drow0, b - n_da, keep_bits);
 }
@@ -406,25 +466,66 @@ __global__ __launch_bounds__(256) void lora_da_dx_mfma_kernel(const float* __res
 // ---- host side (called from lora.hip) ---------------------------------------------------------------------
 
 bool lora_mfma_ok(int width, int segw, int r, int nseg) {
-  return r >= 1 && r <= 16 && (nseg == 1 || nseg == 3) && (width % 128) == 0 && (segw % 64) == 0;
+  return r >= 1 && r <= 64 && (nseg == 1 || nseg == 3) && (width % 128) == 0 && (segw % 64) == 0;
 }
 
-// rows per reduction slice: enough slices to put ~6000 waves (column groups x slices) on the chip, few enough that
-// the partial sums stay small; never below 64 rows (the work buffer is sized for 64-row slices)
+static inline int lora_groups(int r) { return (r + 15) / 16; }  // rank groups of 16 (G)
+
+// rows per reduction slice: enough slices to put ~6000 wave-groups (column groups x rank groups x slices) of work on
+// the chip, few enough that the partial sums stay small; never below 64 rows.  A wave does all G rank groups of its
+// columns, so a larger rank needs fewer slices for the same work.
 static int lora_mfma_slice_rows(int rows, int col_groups) {
   int sr = 2048;
   while (sr > 64 && (long)col_groups * ((rows + sr - 1) / sr) < 6144) sr >>= 1;
   return sr;
 }
 
+struct LoraMfmaSlices {
+  int sr_b, slices_b, sr_a, slices_a;
+  size_t nb, na;  // dB / dA floats per slice
+  size_t floats() const { return (((size_t)slices_b * nb + 3) & ~(size_t)3) + (size_t)slices_a * na; }
+};
+
+static LoraMfmaSlices lora_mfma_slices(int rows, int width, int segw, int r, int nseg) {
+  const int cols = nseg * segw, G = lora_groups(r);
+  LoraMfmaSlices S;
+  S.sr_b = lora_mfma_slice_rows(rows, cols / 64 * G);
+  S.slices_b = (rows + S.sr_b - 1) / S.sr_b;
+  S.sr_a = lora_mfma_slice_rows(rows, width / 64 * G);
+  S.slices_a = (rows + S.sr_a - 1) / S.sr_a;
+  S.nb = (size_t)cols * r;
+  S.na = (size_t)nseg * r * width;
+  return S;
+}
+
+// what lora_bwd_mfma writes into its work buffer (dB partials, then dA partials)
+size_t lora_mfma_work_floats(int rows, int width, int segw, int r, int nseg) {
+  return lora_mfma_slices(rows, width, segw, r, nseg).floats();
+}
+
+template <int NSEG, int G>
+static int lora_down_mfma_n(const float* x, const float* A, float* t, int rows, int width, int r, unsigned seg_mask, float p,
+                            uint64_t seed, uint32_t stream_base, uint32_t drow0, uint16_t* keep_bits, hipStream_t st) {
+  hipLaunchKernelGGL((lora_down_mfma_kernel<NSEG, G>), dim3((rows + 15) / 16), dim3(256), 0, st, x, A, t, rows, width, r, seg_mask, p,
+                     seed, stream_base, drow0, keep_bits);
+  return launch_status();
+}
+
+template <int NSEG>
+static int lora_down_mfma_g(const float* x, const float* A, float* t, int rows, int width, int r, unsigned seg_mask, float p,
+                            uint64_t seed, uint32_t stream_base, uint32_t drow0, uint16_t* keep_bits, hipStream_t st) {
+  switch (lora_groups(r)) {
+    case 1: return lora_down_mfma_n<NSEG, 1>(x, A, t, rows, width, r, seg_mask, p, seed, stream_base, drow0, keep_bits, st);
+    case 2: return lora_down_mfma_n<NSEG, 2>(x, A, t, rows, width, r, seg_mask, p, seed, stream_base, drow0, keep_bits, st);
+    case 3: return lora_down_mfma_n<NSEG, 3>(x, A, t, rows, width, r, seg_mask, p, seed, stream_base, drow0, keep_bits, st);
+    default: return lora_down_mfma_n<NSEG, 4>(x, A, t, rows, width, r, seg_mask, p, seed, stream_base, drow0, keep_bits, st);
+  }
+}
+
 int lora_down_mfma(const float* x, const float* A, float* t, int rows, int width, int r, int nseg, unsigned seg_mask,
                    float p, uint64_t seed, uint32_t stream_base, uint32_t drow0, uint16_t* keep_bits, hipStream_t st) {
-  const dim3 grid((rows + 15) / 16);
-  if (nseg == 1)
-    hipLaunchKernelGGL((lora_down_mfma_kernel<1>), grid, dim3(256), 0, st, x, A, t, rows, width, r, seg_mask, p, seed, stream_base, drow0, keep_bits);
-  else
-    hipLaunchKernelGGL((lora_down_mfma_kernel<3>), grid, dim3(256), 0, st, x, A, t, rows, width, r, seg_mask, p, seed, stream_base, drow0, keep_bits);
-  return launch_status();
+  if (nseg == 1) return lora_down_mfma_g<1>(x, A, t, rows, width, r, seg_mask, p, seed, stream_base, drow0, keep_bits, st);
+  return lora_down_mfma_g<3>(x, A, t, rows, width, r, seg_mask, p, seed, stream_base, drow0, keep_bits, st);
 }
 
 template <int NSEG, int RQ>
@@ -438,6 +539,16 @@ static void launch_da_dx(const float* x, const float* dt, const float* A, float*
                      r, seg_mask, p, seed, stream_base, drow0, sr_a, gx_a, n_da, keep_bits);
 }
 
+template <int NSEG, int G, typename TY>
+static void launch_db_dt(const TY* dy, const float* B, const float* t, float* dt, float* part_b, int rows, int segw, int r,
+                         unsigned seg_mask, float scale, int sr_b, int slices_b, hipStream_t st) {
+  const int cols = NSEG * segw;
+  const int gx_b = (cols + 255) / 256, n_db = gx_b * slices_b;
+  const int n_rows16 = (rows + 15) / 16;
+  hipLaunchKernelGGL((lora_db_dt_mfma_kernel<NSEG, G, TY>), dim3(n_db + n_rows16), dim3(256), 0, st, dy, B, t, dt, part_b, rows,
+                     segw, r, seg_mask, scale, sr_b, gx_b, n_db);
+}
+
 // reduce2(part_b, dB, nb, slices_b, scale_b, part_a, dA, na, slices_a, scale_a): both slice sums in one launch
 typedef void (*lora_reduce2_fn)(const float*, float*, size_t, int, float, const float*, float*, size_t, int, float, hipStream_t);
 
@@ -446,38 +557,36 @@ static int lora_bwd_mfma_n(const TY* dy, const float* x, const float* t, const f
                            float* dA, float* dB, float* dx, int rows, int width, int segw, int r, unsigned seg_mask,
                            float scale, float p, uint64_t seed, uint32_t stream_base, uint32_t drow0, const uint16_t* keep_bits,
                            float* work, hipStream_t st, lora_reduce2_fn reduce2) {
-  const int cols = NSEG * segw;
   // dA == dB == NULL: frozen adapter -- no dB / dA workgroups, no slice sums (dt and dx come out bitwise the same)
   const bool grads = dA != nullptr;
-  const int sr_b = lora_mfma_slice_rows(rows, cols / 64), slices_b = grads ? (rows + sr_b - 1) / sr_b : 0;
-  const int sr_a = lora_mfma_slice_rows(rows, width / 64), slices_a = grads ? (rows + sr_a - 1) / sr_a : 0;
-  const int n_rows16 = (rows + 15) / 16;
-  const size_t nb = (size_t)cols * r, na = (size_t)NSEG * r * width;
+  const LoraMfmaSlices S = lora_mfma_slices(rows, width, segw, r, NSEG);
+  const int slices_b = grads ? S.slices_b : 0, slices_a = grads ? S.slices_a : 0;
   float* part_b = work;
-  float* part_a = work + (((size_t)slices_b * nb + 3) & ~(size_t)3);
+  float* part_a = work + (((size_t)slices_b * S.nb + 3) & ~(size_t)3);
   // 1: dB partials || dt
-  const int gx_b = (cols + 255) / 256, n_db = gx_b * slices_b;
-  hipLaunchKernelGGL((lora_db_dt_mfma_kernel<NSEG, TY>), dim3(n_db + n_rows16), dim3(256), 0, st, dy, B, t, dt, part_b, rows,
-                     segw, r, seg_mask, scale, sr_b, gx_b, n_db);
-  CLIPFS_CHECK(launch_status());
-  // 2: dA partials || dx
-  switch ((r + 3) / 4) {
-    case 1:
-      launch_da_dx<NSEG, 1>(x, dt, A, part_a, dx, rows, width, r, seg_mask, p, seed, stream_base, drow0, sr_a, slices_a, keep_bits, st);
-      break;
-    case 2:
-      launch_da_dx<NSEG, 2>(x, dt, A, part_a, dx, rows, width, r, seg_mask, p, seed, stream_base, drow0, sr_a, slices_a, keep_bits, st);
-      break;
-    case 3:
-      launch_da_dx<NSEG, 3>(x, dt, A, part_a, dx, rows, width, r, seg_mask, p, seed, stream_base, drow0, sr_a, slices_a, keep_bits, st);
-      break;
-    default:
-      launch_da_dx<NSEG, 4>(x, dt, A, part_a, dx, rows, width, r, seg_mask, p, seed, stream_base, drow0, sr_a, slices_a, keep_bits, st);
-      break;
+  switch (lora_groups(r)) {
+    case 1: launch_db_dt<NSEG, 1, TY>(dy, B, t, dt, part_b, rows, segw, r, seg_mask, scale, S.sr_b, slices_b, st); break;
+    case 2: launch_db_dt<NSEG, 2, TY>(dy, B, t, dt, part_b, rows, segw, r, seg_mask, scale, S.sr_b, slices_b, st); break;
+    case 3: launch_db_dt<NSEG, 3, TY>(dy, B, t, dt, part_b, rows, segw, r, seg_mask, scale, S.sr_b, slices_b, st); break;
+    default: launch_db_dt<NSEG, 4, TY>(dy, B, t, dt, part_b, rows, segw, r, seg_mask, scale, S.sr_b, slices_b, st); break;
   }
   CLIPFS_CHECK(launch_status());
+  // 2: dA partials || dx.  r <= 16: ceil(r / 4) K-steps for dx; above, whole rank groups of 4 K-steps
+#define CLIPFS_DA_DX(RQ)                                                                                                         \
+  launch_da_dx<NSEG, RQ>(x, dt, A, part_a, dx, rows, width, r, seg_mask, p, seed, stream_base, drow0, S.sr_a, slices_a, keep_bits, st)
+  switch (r <= 16 ? (r + 3) / 4 : 4 * lora_groups(r)) {
+    case 1: CLIPFS_DA_DX(1); break;
+    case 2: CLIPFS_DA_DX(2); break;
+    case 3: CLIPFS_DA_DX(3); break;
+    case 4: CLIPFS_DA_DX(4); break;
+    case 8: CLIPFS_DA_DX(8); break;
+    case 12: CLIPFS_DA_DX(12); break;
+    default: CLIPFS_DA_DX(16); break;
+  }
+#undef CLIPFS_DA_DX
+  CLIPFS_CHECK(launch_status());
   // 3: both slice sums
-  if (grads) reduce2(part_b, dB, nb, slices_b, scale, part_a, dA, na, slices_a, 1.0f, st);
+  if (grads) reduce2(part_b, dB, S.nb, slices_b, scale, part_a, dA, S.na, slices_a, 1.0f, st);
   return launch_status();
 }
 

@@ -19,7 +19,7 @@ static inline bool f16_attention(const clipfs_tower* t) { return t->weight_forma
 // ... and then qkv itself is stored as f16 (written by the QKV GEMM, read by the attention kernels): needs the
 // f16 x f16 GEMM for the LoRA'd projection, i.e. a segment width that is a multiple of its 128-column tiles
 static inline bool qkv_f16(const clipfs_tower* t) {
-  return f16_attention(t) && (t->width % 128) == 0 && t->lora_r <= 16;
+  return f16_attention(t) && (t->width % 128) == 0 && t->lora_r <= 64;
 }
 
 struct SavedLayout {
@@ -132,7 +132,12 @@ static int check_tower(const clipfs_tower* t, int batch) {
                  t->struct_size, t->block_size, sizeof(clipfs_tower), sizeof(clipfs_block));
   CLIPFS_REQUIRE(batch > 0 && t->layers > 0 && t->seq > 0 && t->heads > 0 && t->width == t->heads * 64,
                  "tower: width %d must be heads %d * 64", t->width, t->heads);
-  CLIPFS_REQUIRE(t->lora_r >= 0 && t->lora_r <= 16, "tower: lora rank %d unsupported", t->lora_r);
+  CLIPFS_REQUIRE(t->lora_r >= 0 && t->lora_r <= 64, "tower: lora rank %d unsupported (0..64) at width %d", t->lora_r,
+                 t->width);
+  // ranks above 16 run on the matrix-core adapter kernels only (lora_mfma.hip), which need the width in 128-column steps
+  CLIPFS_REQUIRE(t->lora_r <= 16 || t->width % 128 == 0,
+                 "tower: lora rank %d at width %d unsupported (ranks above 16 need a width that is a multiple of 128)",
+                 t->lora_r, t->width);
   CLIPFS_REQUIRE(t->grad_lo >= 0 && t->grad_lo < t->layers, "tower: grad_lo %d outside [0, layers %d)", t->grad_lo,
                  t->layers);
   // blocks below the floor get no backward: a gradient slot there would silently stay untouched
@@ -204,7 +209,7 @@ static int gemm(const TowerCtx& cx, const float* A, const float* B, const void* 
   a.bias = bias; a.residual = res; a.ldres = N;
   a.act = act; a.aux_out = aux_out; a.aux_in = aux_in;
   a.lora_t = lt; a.lora_b = lb; a.lora_r = r; a.lora_nseg = nseg; a.lora_seg_width = segw; a.lora_scale = lscale;
-  if (cx.b_format == 2 && Bp && cx.a16 && (K % 32) == 0 && (!lt || (segw % 128 == 0 && r <= 16))) {
+  if (cx.b_format == 2 && Bp && cx.a16 && (K % 32) == 0 && (!lt || (segw % 128 == 0 && r <= 64))) {
     if (chain & CHAIN_IN16) {
       a.A_f16 = cx.c16;
     } else if (a16_ready) {
