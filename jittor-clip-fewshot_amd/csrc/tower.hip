@@ -6,9 +6,16 @@
 // Residual stream without copies: block l reads x_in[l], the out-projection epilogue writes
 // x_mid[l] = x_in[l] + attn, the c_proj epilogue writes x_in[l+1] = x_mid[l] + mlp, so the tensors the
 // backward needs are exactly the ones the forward had to produce anyway.
+//
+// The transformer block is written once per direction (fwd_block; bwd_mlp_half + bwd_attn_half).  A RowView says which
+// rows a walk runs on -- every row, or the live rows of a causal tower's plan -- and each step picks its kernel variant
+// from the view where the step is written.  The last block's one-row-per-sequence part is fwd_tail / bwd_head.
 #include "common.h"
 
 #include <stdlib.h>
+
+// the GEMM helper's arguments are named at the call site: designated initialisers, which clang accepts under -std=c++17
+#pragma clang diagnostic ignored "-Wc++20-designator"
 
 namespace clipfs {
 
@@ -22,6 +29,15 @@ static inline bool qkv_f16(const clipfs_tower* t) {
   return f16_attention(t) && (t->width % 128) == 0 && t->lora_r <= 64;
 }
 
+// which adapters of a block are switched on (clipfs_block.lora_mask: bits 0..2 = q / k / v, bit 3 = the out-projection)
+struct Adapters {
+  unsigned qkv_mask;
+  bool o;
+};
+static inline Adapters adapters(const clipfs_block& b) {
+  return {b.lora_a_qkv ? (b.lora_mask & 7u) : 0u, b.lora_a_o && (b.lora_mask & 8u)};
+}
+
 struct SavedLayout {
   size_t x_in, stat1, h1, t_qkv, qkv, att, lse, t_o, x_mid, stat2, u, keep, total;
 };
@@ -33,7 +49,9 @@ static inline bool keep_bits_slot(const clipfs_tower* t) {  // the slot exists (
 }
 static inline bool keep_bits_saved(const clipfs_tower* t) { return keep_bits_slot(t) && t->dropout_seed != 0; }
 
-// M per-row records; the lse slot keeps its [sequence * heads + head][seq] layout whatever the row count
+// One saved record of `rows` per-row entries: rows = batch * seq for the dense forward, the plan's R live rows for
+// clipfs_tower_fwd_packed (no larger than the dense record for R <= M).  The lse slot keeps its
+// [sequence * heads + head][seq] layout whatever the row count.
 static SavedLayout saved_layout_rows(const clipfs_tower* t, size_t M, size_t batch) {
   const size_t d = t->width, r = t->lora_r > 0 ? t->lora_r : 0;
   SavedLayout L;
@@ -56,12 +74,6 @@ static SavedLayout saved_layout_rows(const clipfs_tower* t, size_t M, size_t bat
   return L;
 }
 
-static SavedLayout saved_layout(const clipfs_tower* t, size_t M) { return saved_layout_rows(t, M, M / t->seq); }
-// the live-row forward (clipfs_tower_fwd_packed) keeps R packed rows per block: no larger than the dense record for R <= M
-static SavedLayout saved_layout_packed(const clipfs_tower* t, size_t R, size_t batch) {
-  return saved_layout_rows(t, R, batch);
-}
-
 // bias gradient slots (clipfs_block.g_*): NULL everywhere = bias='none', and then the backward launches exactly what it
 // launched before they existed
 static inline bool block_has_bias_slots(const clipfs_block& b) {
@@ -73,6 +85,11 @@ static bool tower_has_bias_slots(const clipfs_tower* t) {
     if (block_has_bias_slots(t->blocks[l])) return true;
   return false;
 }
+
+// (N, K) of a block's GEMMs in units of the width: QKV, out-projection, c_fc, c_proj, then the backward's dgrads into
+// LayerNorm 1's output, the pre-activation and the attention output (c_fc's dgrad has c_proj's shape)
+constexpr int kFwdGemms = 4, kGemms = 7;
+constexpr int kGemmShape[kGemms][2] = {{3, 1}, {1, 1}, {4, 1}, {1, 4}, {1, 3}, {4, 1}, {1, 1}};
 
 struct ScratchLayout {
   size_t h, big, b3, b1, dt, work, gemm_ws, gemm_ws_floats, a16, c16, bwork, total;
@@ -91,16 +108,15 @@ static ScratchLayout scratch_layout(const clipfs_tower* t, size_t M) {
   S.work = o; o += r ? al4(clipfs_lora_bwd_work_floats((int)M, (int)d, (int)r, 3)) : 0;
   // split-K scratch for the largest of the tower's GEMM shapes (0 unless the row count is small)
   size_t ws = 0, cnt = 0;
-  const int shapes[7][2] = {{3 * (int)d, (int)d}, {(int)d, (int)d}, {4 * (int)d, (int)d}, {(int)d, 4 * (int)d},
-                            {(int)d, 3 * (int)d}, {4 * (int)d, (int)d}, {(int)d, (int)d}};
   // ... at the tower's row count and at one row per sequence (the compact last block: clipfs_tower_fwd_rows /
   // clipfs_tower_bwd_sparse run their products on `batch` rows)
   const size_t row_counts[2] = {M, M / (size_t)t->seq};
   for (int k = 0; k < 2; ++k)
-    for (int i = 0; i < 7; ++i) {
+    for (int i = 0; i < kGemms; ++i) {
       if (!row_counts[k]) continue;
-      const size_t w = clipfs_gemm_workspace_floats((int)row_counts[k], shapes[i][0], shapes[i][1]);
-      const size_t c = clipfs_gemm_counter_ints((int)row_counts[k], shapes[i][0], shapes[i][1]);
+      const int N = kGemmShape[i][0] * (int)d, K = kGemmShape[i][1] * (int)d;
+      const size_t w = clipfs_gemm_workspace_floats((int)row_counts[k], N, K);
+      const size_t c = clipfs_gemm_counter_ints((int)row_counts[k], N, K);
       ws = w > ws ? w : ws;
       cnt = c > cnt ? c : cnt;
     }
@@ -164,6 +180,19 @@ static int check_tower(const clipfs_tower* t, int batch) {
   return CLIPFS_OK;
 }
 
+// Every block the backward walks needs its transposed weights, and in fp16 storage mode their f16 planes (dqkv and the
+// MLP gradient exist only as f16 images there: the fp32 dgrad would read a tensor nobody wrote).  Checked before the
+// first launch of every backward entry point.
+static int check_bwd_weights(const clipfs_tower* t) {
+  for (int l = t->grad_lo; l < t->layers; ++l) {
+    const clipfs_block& b = t->blocks[l];
+    CLIPFS_REQUIRE(b.w_pr_t && b.w_fc_t && b.w_o_t && b.w_qkv_t, "tower_bwd: block %d lacks transposed weights", l);
+    CLIPFS_REQUIRE(t->weight_format != 2 || (b.w_pr_t_p && b.w_fc_t_p && b.w_o_t_p && b.w_qkv_t_p),
+                   "tower_bwd: block %d lacks f16 copies of the transposed weights", l);
+  }
+  return CLIPFS_OK;
+}
+
 // Per-call state of a tower pass (no hidden / thread-local state: everything a GEMM of the pass needs travels here)
 struct TowerCtx {
   float* ws = nullptr;          // split-K / stream-K scratch (inside the call's scratch buffer)
@@ -189,68 +218,229 @@ static TowerCtx make_ctx(const clipfs_tower* t, float* scratch, const ScratchLay
 
 enum GemmChain { CHAIN_NONE = 0, CHAIN_OUT16 = 1, CHAIN_IN16 = 2 };
 
-// chain: CHAIN_OUT16 = the result is only the next GEMM's A operand: in fp16 mode write it as f16 alone;
-//        CHAIN_IN16  = A is the previous GEMM's CHAIN_OUT16 result.
-// a16_ready: f16 image of A written by the producing kernel (LayerNorm / attention); NULL = convert here.
-static int gemm(const TowerCtx& cx, const float* A, const float* B, const void* Bp, float* C, int M, int N, int K,
-                const float* bias, const float* res, int act, float* aux_out, const float* aux_in, const float* lt,
-                const float* lb, int r, int nseg, int segw, float lscale, hipStream_t st, int chain = CHAIN_NONE,
-                const void* a16_ready = nullptr, void* c16_only = nullptr) {
+// C[M, N] = A[M, K] B[N, K]^T (+ epilogue).  The first seven fields are mandatory, everything else defaults to "none".
+struct Gemm {
+  int M, N, K;
+  const float* A;
+  const float* B;
+  const void* planes;               // B's 16-bit copies (NULL: the fp32 master weights)
+  float* C;
+  const float* bias = nullptr;
+  const float* residual = nullptr;  // [M, N], added in the epilogue
+  int act = 0;                      // 1 = QuickGELU (pre-activation to aux_out), 2 = times gelu'(aux_in)
+  float* aux_out = nullptr;
+  const float* aux_in = nullptr;
+  struct {                          // adapter up-projection folded into the epilogue: t [M, nseg * r] (NULL = none)
+    const float* t = nullptr;
+    const float* b = nullptr;
+    int r = 0, nseg = 0, segw = 0;
+    float scale = 0.f;
+  } lora;
+  // CHAIN_OUT16 = the result is only the next GEMM's A operand: in fp16 mode write it as f16 alone;
+  // CHAIN_IN16  = A is the previous GEMM's CHAIN_OUT16 result
+  int chain = CHAIN_NONE;
+  const void* a16_ready = nullptr;  // f16 image of A written by the producing kernel (LayerNorm / attention); NULL = convert here
+  void* c16_only = nullptr;         // fp16 mode: keep the result as f16 alone, here (qkv, dO)
+};
+
+static int gemm(const TowerCtx& cx, const Gemm& g, hipStream_t st) {
   clipfs_gemm_args a = {};
   a.struct_size = sizeof(a);
-  a.B_planes = Bp;
+  a.B_planes = g.planes;
   a.b_format = cx.b_format;
   a.workspace = cx.ws;
   a.workspace_floats = cx.ws_floats;
   a.counters = cx.counters;
   a.counters_ints = cx.counters_ints;
-  a.A = A; a.B = B; a.C = C; a.M = M; a.N = N; a.K = K;
-  a.lda = K; a.ldb = K; a.ldc = N; a.alpha = 1.f;
-  a.bias = bias; a.residual = res; a.ldres = N;
-  a.act = act; a.aux_out = aux_out; a.aux_in = aux_in;
-  a.lora_t = lt; a.lora_b = lb; a.lora_r = r; a.lora_nseg = nseg; a.lora_seg_width = segw; a.lora_scale = lscale;
-  if (cx.b_format == 2 && Bp && cx.a16 && (K % 32) == 0 && (!lt || (segw % 128 == 0 && r <= 64))) {
-    if (chain & CHAIN_IN16) {
+  a.A = g.A; a.B = g.B; a.C = g.C; a.M = g.M; a.N = g.N; a.K = g.K;
+  a.lda = g.K; a.ldb = g.K; a.ldc = g.N; a.alpha = 1.f;
+  a.bias = g.bias; a.residual = g.residual; a.ldres = g.N;
+  a.act = g.act; a.aux_out = g.aux_out; a.aux_in = g.aux_in;
+  a.lora_t = g.lora.t; a.lora_b = g.lora.b; a.lora_r = g.lora.r; a.lora_nseg = g.lora.nseg;
+  a.lora_seg_width = g.lora.segw; a.lora_scale = g.lora.scale;
+  if (cx.b_format == 2 && g.planes && cx.a16 && (g.K % 32) == 0 &&
+      (!g.lora.t || (g.lora.segw % 128 == 0 && g.lora.r <= 64))) {
+    if (g.chain & CHAIN_IN16) {
       a.A_f16 = cx.c16;
-    } else if (a16_ready) {
-      a.A_f16 = a16_ready;  // the producing kernel already wrote the f16 image
+    } else if (g.a16_ready) {
+      a.A_f16 = g.a16_ready;  // the producing kernel already wrote the f16 image
     } else {
-      CLIPFS_CHECK(clipfs_convert_f16(A, cx.a16, (size_t)M * K, st));
+      CLIPFS_CHECK(clipfs_convert_f16(g.A, cx.a16, (size_t)g.M * g.K, st));
       a.A_f16 = cx.a16;
     }
-    if (chain & CHAIN_OUT16) {
+    if (g.chain & CHAIN_OUT16) {
       a.C_f16 = cx.c16;
       a.C = nullptr;
     }
     a.aux_f16 = 1;  // fp16 storage of the saved pre-activation (only the f16 x f16 GEMMs read or write it)
-    if (c16_only) {  // the result is kept as f16 alone (qkv in fp16 storage)
-      a.C_f16 = c16_only;
+    if (g.c16_only) {
+      a.C_f16 = g.c16_only;
       a.C = nullptr;
     }
   } else {
-    CLIPFS_REQUIRE(!c16_only, "tower: the f16 x f16 GEMM is required for an f16-only result");
+    CLIPFS_REQUIRE(!g.c16_only, "tower: the f16 x f16 GEMM is required for an f16-only result");
   }
   return clipfs_gemm_nt(&a, st);
 }
 
-// deep prompt of block b (clipfs_block.prompt): written over its rows of the block input x (off: the packed plan's
-// offsets, NULL = dense rows); its gradient taken from the input gradient dx (and those rows of dx / its f16 image
-// zeroed: the replaced rows do not depend on the block below)
-static int put_prompt(const clipfs_block& b, float* x, const int32_t* off, int batch, int seq, int d, hipStream_t st) {
-  if (!b.prompt) return CLIPFS_OK;
-  return clipfs_prompt_put(b.prompt, x, off, batch, seq, b.prompt_first, b.prompt_rows, d, st);
+// Which rows a walk runs on.  Three views exist: every row (dense); the live rows of a plan over the dense forward's
+// saved records (clipfs_tower_bwd_packed); the live rows over clipfs_tower_fwd_packed's own records.
+//
+// The plan (int32, device) of a causal tower: sequence c carries gradient on its rows c*seq + 0 .. eot_c only (the head
+// reads its EOT row and a row never attends to a later one), and forward the same rows are all the head depends on: the
+// R = sum (eot_c + 1) live rows are packed caption after caption.  off[0 .. batch] is the exclusive prefix sum of
+// eot_c + 1 (off[batch] = R), eotp[0 .. batch) = off[c + 1] - 1 the packed row of each EOT, map[0 .. R) = c * seq + p the
+// full-layout row of packed row i.
+struct RowView {
+  int n = 0;                      // rows of the walk: batch * seq, or R
+  int srows = 0;                  // rows of a saved record (offset of the rstd half of a statistics slot)
+  const int32_t* map = nullptr;   // NULL = dense rows
+  const int32_t* off = nullptr;
+  const int32_t* eotp = nullptr;
+  bool gather = false;            // the saved records are dense: their live rows are gathered through map into scratch
+  TowerCtx cx;                    // context of the n-row GEMMs
+  bool packed() const { return map != nullptr; }
+  bool saved_packed() const { return map && !gather; }
+};
+
+// One call's state, built by begin_pass
+struct Pass {
+  const clipfs_tower* t;
+  int batch, M;
+  float* scratch;
+  hipStream_t st;
+  ScratchLayout SC;
+  TowerCtx cx;          // the dense rows' and the compact `batch`-row products' GEMM context
+  void* dqkv16;         // fp16 mode: [M, 3d] halves behind the [M, d] image at cx.a16
+  const int32_t* plan;  // the live-row entry points' plan and its R
+  int R;
+  RowView v;
+  SavedLayout SL;       // of the view's saved records
+};
+
+// The checks the entry points share; nothing is enqueued here.  buffers: the entry point's pointer arguments are all
+// there; stop_at_input: NULL for a forward; plan / R: of the live-row entry points (NULL / 0 elsewhere).
+static int begin_pass(Pass* p, const char* who, const clipfs_tower* t, int batch, bool buffers, const int* stop_at_input,
+                      const int32_t* plan, int R, float* scratch, void* stream) {
+  CLIPFS_CHECK(check_tower(t, batch));
+  CLIPFS_REQUIRE(!stop_at_input || t->grad_lo == 0 || *stop_at_input,
+                 "%s: grad_lo %d > 0 needs stop_at_input (the input gradient runs through every block)", who, t->grad_lo);
+  CLIPFS_REQUIRE(buffers, "%s: null buffer", who);
+  const int M = batch * t->seq;
+  CLIPFS_REQUIRE(!plan || (R >= batch && R <= M), "%s: R %d outside [batch %d, batch*seq %d]", who, R, batch, M);
+  *p = Pass{t, batch, M, scratch, (hipStream_t)stream, scratch_layout(t, (size_t)M)};
+  CLIPFS_REQUIRE(!t->gemm_counters || t->gemm_counters_ints >= p->SC.counter_ints,
+                 "tower: gemm_counters holds %zu ints, %zu needed", t->gemm_counters_ints, p->SC.counter_ints);
+  p->cx = make_ctx(t, scratch, p->SC);
+  p->dqkv16 = p->cx.a16 ? (void*)((char*)p->cx.a16 + (size_t)M * t->width * 2) : nullptr;
+  p->plan = plan;
+  p->R = R;
+  p->v.n = p->v.srows = M;  // the dense view, unless packed_rows follows
+  p->v.cx = p->cx;
+  p->SL = saved_layout_rows(t, (size_t)M, (size_t)batch);
+  return CLIPFS_OK;
 }
-static int harvest_prompt(const clipfs_block& b, float* dx, void* dx16, const int32_t* off, int batch, int seq, int d,
-                          hipStream_t st) {
+
+// saved_packed: the saved records are the live-row forward's.  unsplit: the R-row GEMMs run without split-K -- the K
+// order of one output element depends on the split factor only, never on the tile height, so an unsplit R-row launch
+// reproduces the unsplit dense launch bitwise (pack_fwd_ok)
+static void packed_rows(Pass* p, bool saved_packed, bool unsplit) {
+  const int32_t* plan = p->plan;
+  p->v.n = p->R;
+  p->v.srows = saved_packed ? p->R : p->M;
+  p->v.off = plan;
+  p->v.eotp = plan + p->batch + 1;
+  p->v.map = plan + 2 * (size_t)p->batch + 1;
+  p->v.gather = !saved_packed;
+  p->v.cx = p->cx;
+  if (unsplit) {
+    p->v.cx.ws = nullptr;
+    p->v.cx.counters = nullptr;
+    p->v.cx.ws_floats = p->v.cx.counters_ints = 0;
+  }
+  p->SL = saved_layout_rows(p->t, (size_t)p->v.srows, (size_t)p->batch);
+}
+
+// the packed walks keep their residual stream (forward: x, backward: dx) in the second half of the b1 slot, the
+// attention output / its gradient in the first half (R <= M / 2, pack_ok)
+static float* packed_x(const Pass& p) { return p.scratch + p.SC.b1 + al4((size_t)p.v.n * p.t->width); }
+
+// A per-row saved tensor ([srows, w] floats) as the view's walk reads it: in place, or -- live rows over dense records --
+// gathered into `slot`
+static int saved_rows(const Pass& p, const float* src, int w, float* slot, const float** out) {
+  *out = src;
+  if (!p.v.gather) return CLIPFS_OK;
+  *out = slot;
+  return clipfs_gather_rows_map(src, (size_t)w, p.v.map, slot, p.v.n, w, p.st);
+}
+
+// where the backward gathers them (the MLP scratch, dead by then): h1 / t_qkv / keep bits, and att / t_o for an
+// o-projection adapter
+struct GatherSlots {
+  float *h1, *t_qkv, *keep, *att, *t_o;
+};
+static GatherSlots gather_slots(const Pass& p) {
+  const size_t R = (size_t)p.v.n, d = p.t->width, r = p.t->lora_r;
+  GatherSlots g;
+  g.h1 = p.scratch + p.SC.big;
+  g.t_qkv = g.h1 + al4(R * d);
+  g.keep = g.t_qkv + al4(R * 3 * r);
+  g.att = g.keep + al4(R * d / 8);
+  g.t_o = g.att + al4(R * d);
+  return g;
+}
+
+// The compact (one row per sequence) part of the last block picks its `batch` rows of a [rows, w] tensor, and puts them
+// back, either at rows[c] within sequence c of the full layout or -- packed records -- at the plan's EOT rows.
+// f16: the tensor holds halves (the saved pre-activation in fp16 storage mode).
+static int pick_rows(const Pass& p, const int32_t* rows, const float* src, int w, float* dst, bool f16 = false) {
+  if (p.v.saved_packed()) return clipfs_gather_rows_map(src, (size_t)w, p.v.eotp, dst, p.batch, w, p.st);
+  if (f16) return clipfs_gather_seq_rows_f16(src, (size_t)w, rows, dst, p.batch, p.t->seq, w, p.st);
+  return clipfs_gather_seq_rows(src, (size_t)w, rows, dst, p.batch, p.t->seq, w, p.st);
+}
+static int put_rows(const Pass& p, const int32_t* rows, const float* src, int w, float* dst, bool f16 = false) {
+  if (p.v.saved_packed()) return clipfs_put_rows_map(src, p.v.eotp, dst, (size_t)w, p.batch, w, p.st);
+  if (f16) return clipfs_put_seq_rows_f16(src, rows, dst, (size_t)w, p.batch, p.t->seq, w, p.st);
+  return clipfs_put_seq_rows(src, rows, dst, (size_t)w, p.batch, p.t->seq, w, p.st);
+}
+
+// deep prompt of block b (clipfs_block.prompt): written over its rows of the block input x (through the view's offsets
+// on packed rows); its gradient taken from the input gradient dx (and those rows of dx / its f16 image zeroed: the
+// replaced rows do not depend on the block below)
+static int put_prompt(const Pass& p, const clipfs_block& b, float* x) {
   if (!b.prompt) return CLIPFS_OK;
-  return clipfs_prompt_harvest(dx, dx16, off, batch, seq, b.prompt_first, b.prompt_rows, d, b.g_prompt, st);
+  return clipfs_prompt_put(b.prompt, x, p.v.off, p.batch, p.t->seq, b.prompt_first, b.prompt_rows, p.t->width, p.st);
+}
+static int harvest_prompt(const Pass& p, const clipfs_block& b, float* dx, void* dx16) {
+  if (!b.prompt) return CLIPFS_OK;
+  return clipfs_prompt_harvest(dx, dx16, p.v.off, p.batch, p.t->seq, b.prompt_first, b.prompt_rows, p.t->width, b.g_prompt,
+                               p.st);
 }
 
 // accumulate the column sums of a dense [rows, cols] tensor into up to three bias slots (nothing when all are NULL)
-static int bias_sum(const float* x, int rows, int cols, int segw, float* o0, float* o1, float* o2, float* work,
-                    hipStream_t st) {
+static int bias_sum(const Pass& p, const float* x, int rows, int cols, int segw, float* o0, float* o1 = nullptr,
+                    float* o2 = nullptr) {
   if (!o0 && !o1 && !o2) return CLIPFS_OK;
-  return clipfs_bias_grad(x, (size_t)cols, rows, cols, segw, o0, o1, o2, work, st);
+  return clipfs_bias_grad(x, (size_t)cols, rows, cols, segw, o0, o1, o2, p.scratch + p.SC.bwork, p.st);
+}
+
+// LayerNorm over the view's rows.  stat: the saved mean | rstd slot (forward: NULL = not kept); y16: fp16 mode, the f16
+// image of the result for the next GEMM.
+static int ln_fwd(const Pass& p, const float* x, const float* g, const float* be, float* y, void* y16, float* stat) {
+  const int d = p.t->width;
+  float* rstd = stat ? stat + p.v.srows : nullptr;
+  if (y16) return clipfs_layernorm_fwd_f16(x, d, g, be, y, y16, stat, rstd, p.v.n, d, 1e-5f, p.st);
+  return clipfs_layernorm_fwd(x, d, g, be, y, stat, rstd, p.v.n, d, 1e-5f, p.st);
+}
+// out = res + LN'(dy); x and its statistics are read in place, through the row map where the records are dense and the
+// rows packed
+static int ln_bwd(const Pass& p, const float* dy, const float* x, const float* g, const float* stat, const float* res,
+                  float* out, void* out16) {
+  const int d = p.t->width;
+  const float* rstd = stat + p.v.srows;
+  if (p.v.gather) return clipfs_layernorm_bwd_rows(dy, x, d, g, stat, rstd, p.v.map, res, out, d, p.v.n, d, p.st);
+  if (out16) return clipfs_layernorm_bwd_f16(dy, x, d, g, stat, rstd, res, out, out16, d, p.v.n, d, p.st);
+  return clipfs_layernorm_bwd(dy, x, d, g, stat, rstd, res, out, d, p.v.n, d, p.st);
 }
 
 }  // namespace clipfs
@@ -260,7 +450,8 @@ using namespace clipfs;
 extern "C" size_t clipfs_tower_saved_floats(const clipfs_tower* t, int batch) {
   if (!t || batch <= 0 || t->struct_size != sizeof(clipfs_tower)) return 0;
   if (t->grad_lo < 0 || t->grad_lo >= t->layers) return 0;
-  return saved_layout(t, (size_t)batch * t->seq).total * (size_t)(t->layers - t->grad_lo);  // blocks grad_lo ... top
+  // blocks grad_lo ... top
+  return saved_layout_rows(t, (size_t)batch * t->seq, (size_t)batch).total * (size_t)(t->layers - t->grad_lo);
 }
 
 extern "C" size_t clipfs_tower_scratch_floats(const clipfs_tower* t, int batch) {
@@ -277,293 +468,431 @@ extern "C" size_t clipfs_tower_counter_ints(const clipfs_tower* t, int batch) {
 // the compact forward leaves the skipped rows of x_mid / u / stat2 unwritten.
 static bool last_block_rows_ok(const clipfs_tower* t) {
   static const bool force_dense = getenv("CLIPFS_DENSE_BWD") && atoi(getenv("CLIPFS_DENSE_BWD")) != 0;  // A/B aid
-  const clipfs_block& b = t->blocks[t->layers - 1];
-  const bool lora_o = b.lora_a_o && (b.lora_mask & 8u);
-  return !(force_dense || lora_o || t->seq < 8);
+  return !(force_dense || adapters(t->blocks[t->layers - 1]).o || t->seq < 8);
 }
 
-// rows == NULL: every row of every block.  rows != NULL (and last_block_rows_ok): the LAST block's output projection,
-// LayerNorm 2 and MLP run on the `batch` rows c * seq + rows[c] only.
-static int tower_fwd_impl(const clipfs_tower* t, float* x, const int32_t* rows, int batch, float* saved, float* scratch,
-                          void* stream) {
-  CLIPFS_CHECK(check_tower(t, batch));
-  CLIPFS_REQUIRE(x && scratch, "tower_fwd: null buffer");
-  hipStream_t st = (hipStream_t)stream;
-  const int M = batch * t->seq, d = t->width, r = t->lora_r;
-  const SavedLayout SL = saved_layout(t, (size_t)M);
-  const ScratchLayout SC = scratch_layout(t, (size_t)M);
-  const bool train = saved != nullptr;
-  const TowerCtx cx = make_ctx(t, scratch, SC);
-  CLIPFS_REQUIRE(!t->gemm_counters || t->gemm_counters_ints >= SC.counter_ints,
-                 "tower: gemm_counters holds %zu ints, %zu needed", t->gemm_counters_ints, SC.counter_ints);
-  // dropout follows the caller's train MODE (is_training(), lora_train_vlp.py:297-298), carried by a non-zero seed;
-  // `saved` only decides whether activations are kept (a no-grad forward in train mode still drops)
-  const uint64_t seed = t->dropout_seed;
-  // gradient floor: blocks below it run the no-save path (nothing of theirs is back-propagated); saved record l - lo
+// ---- forward -------------------------------------------------------------------------------------------------------
+
+// The rest of the LAST block on one row per sequence: the head reads nothing else (jclip/model.py:121-124, :213-214) and
+// every remaining operation is row-wise.  att / x_in: the block's attention output and input on the view's rows.  The
+// compact buffers live in the MLP scratch (batch (13 d + 2) floats <= M 4 d for seq >= 4); what the backward's compact
+// head picks again (x_mid, u, LayerNorm-2 statistics) is put back at those rows of the saved record sv (NULL: nothing
+// is kept), the block output at rows[c] of x.
+static int fwd_tail(const Pass& p, const clipfs_block& b, float* sv, const float* att, const float* x_in,
+                    const int32_t* rows, float* x) {
+  const clipfs_tower* t = p.t;
+  const int d = t->width, Ms = p.batch;
+  const SavedLayout& SL = p.SL;
+  const size_t Md = (size_t)Ms * d;
+  float* at = p.scratch + p.SC.big;
+  auto take = [&at](size_t floats) { float* q = at; at += floats; return q; };
+  float *att_s = take(Md), *xin_s = take(Md), *xmid_s = take(Md), *h2_s = take(Md), *xout_s = take(Md);
+  float *g_s = take(4 * Md), *u_s = take(4 * Md), *mean_s = take(al4((size_t)Ms)), *rstd_s = take((size_t)Ms);
+  CLIPFS_CHECK(pick_rows(p, rows, att, d, att_s));
+  CLIPFS_CHECK(pick_rows(p, rows, x_in, d, xin_s));
+  // fp16 storage mode: these `batch`-row products use the fp32 master weights (plane argument NULL) -- the f16 kernels
+  // are built for tens of thousands of rows -- and the pre-GELU rows go back into the f16 tensor the dense path keeps
+  const bool f16m = t->weight_format == 2;
+  CLIPFS_CHECK(gemm(p.cx, {.M = Ms, .N = d, .K = d, .A = att_s, .B = b.w_o, .planes = f16m ? nullptr : b.w_o_p, .C = xmid_s,
+                           .bias = b.b_o, .residual = xin_s}, p.st));
+  CLIPFS_CHECK(clipfs_layernorm_fwd(xmid_s, d, b.ln2_g, b.ln2_b, h2_s, sv ? mean_s : nullptr, sv ? rstd_s : nullptr, Ms, d,
+                                    1e-5f, p.st));
+  CLIPFS_CHECK(gemm(p.cx, {.M = Ms, .N = 4 * d, .K = d, .A = h2_s, .B = b.w_fc, .planes = f16m ? nullptr : b.w_fc_p, .C = g_s,
+                           .bias = b.b_fc, .act = 1, .aux_out = sv ? u_s : nullptr}, p.st));
+  CLIPFS_CHECK(gemm(p.cx, {.M = Ms, .N = d, .K = 4 * d, .A = g_s, .B = b.w_pr, .planes = f16m ? nullptr : b.w_pr_p, .C = xout_s,
+                           .bias = b.b_pr, .residual = xmid_s}, p.st));
+  CLIPFS_CHECK(clipfs_put_seq_rows(xout_s, rows, x, (size_t)d, Ms, t->seq, d, p.st));
+  if (!sv) return CLIPFS_OK;
+  CLIPFS_CHECK(put_rows(p, rows, xmid_s, d, sv + SL.x_mid));
+  CLIPFS_CHECK(put_rows(p, rows, u_s, 4 * d, sv + SL.u, f16m));
+  CLIPFS_CHECK(put_rows(p, rows, mean_s, 1, sv + SL.stat2));
+  return put_rows(p, rows, rstd_s, 1, sv + SL.stat2 + p.v.srows);
+}
+
+// Block l on the view's rows.  A block from the gradient floor up keeps its activations in saved record l - grad_lo (when
+// saved != NULL) and hands its output to the next record's x_in; the others work in the residual stream xr -- x itself,
+// or the packed rows -- in place.  rows != NULL: the compact tail follows the last block's attention.
+static int fwd_block(const Pass& p, int l, float* x, const int32_t* rows, float* saved) {
+  const clipfs_tower* t = p.t;
+  const clipfs_block& b = t->blocks[l];
+  const RowView& v = p.v;
+  const SavedLayout& SL = p.SL;
+  const ScratchLayout& SC = p.SC;
+  const int n = v.n, d = t->width, r = t->lora_r;
+  hipStream_t st = p.st;
   const int lo = t->grad_lo;
+  const bool train = saved != nullptr, keep_l = train && l >= lo;
+  float* sv = keep_l ? saved + (size_t)(l - lo) * SL.total : nullptr;
+  float* xr = v.packed() ? packed_x(p) : x;
+  float* x_next = keep_l && l + 1 < t->layers ? saved + (size_t)(l + 1 - lo) * SL.total + SL.x_in : xr;
+  float* x_in = sv ? sv + SL.x_in : xr;
+  float* h1 = sv ? sv + SL.h1 : p.scratch + SC.h;
+  float* qkv = sv ? sv + SL.qkv : p.scratch + SC.b3;
+  float* att = sv ? sv + SL.att : p.scratch + SC.b1;
+  float* x_mid = sv ? sv + SL.x_mid : xr;
+  float* t_qkv = sv ? sv + SL.t_qkv : p.scratch + SC.dt;
+  float* t_o = sv ? sv + SL.t_o : p.scratch + SC.dt + al4((size_t)n * 3 * r);
+  // attention statistics: kept, or -- below the floor of a saving dense forward -- written to the MLP scratch (dead until
+  // the c_fc GEMM): the attention kernels are picked by whether lse is requested, and a block below the floor must
+  // produce bitwise the block output of the saving forward.  The packed kernel is the same with or without statistics.
+  float* lse = sv ? sv + SL.lse : (train && !v.packed() ? p.scratch + SC.big : nullptr);
+  float* stat1 = sv ? sv + SL.stat1 : nullptr;
+  float* stat2 = sv ? sv + SL.stat2 : nullptr;
+  const Adapters ad = adapters(b);
+  // dropout follows the caller's train MODE (is_training(), lora_train_vlp.py:297-298), carried by a non-zero seed;
+  // saving only decides whether activations are kept (a no-grad forward in train mode still drops)
+  const uint64_t seed = t->dropout_seed;
+  const uint32_t ds = t->dropout_stream0 + 4u * (uint32_t)l;
+  CLIPFS_CHECK(put_prompt(p, b, x_in));  // into the saved record, or the residual stream
+
+  // fp16 storage mode: producers write the f16 image of every GEMM operand next to (or instead of) the fp32 tensor
+  void* h16 = v.cx.a16;  // [n, d] halves: ln1 / attention / ln2
+  void* keep = (sv && ad.qkv_mask && keep_bits_saved(t)) ? (void*)(sv + SL.keep) : nullptr;
+  if (ad.qkv_mask && clipfs_layernorm_fwd_lora_ok(d, r, 3)) {
+    // small ranks: the adapter's down-projection rides on the LayerNorm pass (the row is in registers there); on packed
+    // rows the dropout masks are drawn at the full-layout row, through the map
+    float* rstd1 = stat1 ? stat1 + v.srows : nullptr;
+    if (v.packed())
+      CLIPFS_CHECK(clipfs_layernorm_fwd_lora_map(x_in, d, b.ln1_g, b.ln1_b, h1, h16, stat1, rstd1, n, d, 1e-5f, b.lora_a_qkv,
+                                                 t_qkv, r, 3, ad.qkv_mask, t->lora_dropout, seed, ds, t->dropout_row0, v.map,
+                                                 keep, st));
+    else
+      CLIPFS_CHECK(clipfs_layernorm_fwd_lora(x_in, d, b.ln1_g, b.ln1_b, h1, h16, stat1, rstd1, n, d, 1e-5f, b.lora_a_qkv,
+                                             t_qkv, r, 3, ad.qkv_mask, t->lora_dropout, seed, ds, t->dropout_row0, keep, st));
+  } else {
+    CLIPFS_CHECK(ln_fwd(p, x_in, b.ln1_g, b.ln1_b, h1, h16, stat1));
+    if (ad.qkv_mask)  // (packed rows: no dropout here, pack_fwd_ok)
+      CLIPFS_CHECK(clipfs_lora_down(h1, b.lora_a_qkv, t_qkv, n, d, r, 3, ad.qkv_mask, t->lora_dropout, seed, ds,
+                                    t->dropout_row0, keep, st));
+  }
+  const bool q16 = qkv_f16(t);
+  CLIPFS_CHECK(gemm(v.cx, {.M = n, .N = 3 * d, .K = d, .A = h1, .B = b.w_qkv, .planes = b.w_qkv_p, .C = qkv, .bias = b.b_qkv,
+                           .lora = {ad.qkv_mask ? t_qkv : nullptr, b.lora_b_qkv, r, 3, d, t->lora_scale},
+                           .a16_ready = h16, .c16_only = q16 ? (void*)qkv : nullptr}, st));
+  const void* att16 = nullptr;
+  if (v.packed()) {
+    CLIPFS_CHECK(clipfs_attention_fwd_packed(qkv, att, lse, v.off, p.batch, t->seq, t->heads, st));
+  } else if (f16_attention(t)) {
+    CLIPFS_CHECK(clipfs_attention_f16_fwd(qkv, q16, att, h16, lse, p.batch, t->seq, t->heads, t->causal, st));
+    att16 = h16;
+  } else {
+    CLIPFS_CHECK(clipfs_attention_fwd(qkv, att, lse, p.batch, t->seq, t->heads, t->causal, st));
+  }
+  if (rows && l == t->layers - 1) return fwd_tail(p, b, sv, att, x_in, rows, x);
+  if (ad.o)  // (packed rows: no dropout here, pack_fwd_ok)
+    CLIPFS_CHECK(clipfs_lora_down(att, b.lora_a_o, t_o, n, d, r, 1, 1u, t->lora_dropout, seed, ds + 3, t->dropout_row0, nullptr,
+                                  st));
+  CLIPFS_CHECK(gemm(v.cx, {.M = n, .N = d, .K = d, .A = att, .B = b.w_o, .planes = b.w_o_p, .C = x_mid, .bias = b.b_o,
+                           .residual = x_in, .lora = {ad.o ? t_o : nullptr, b.lora_b_o, r, 1, d, t->lora_scale},
+                           .a16_ready = att16}, st));
+  float* h2 = p.scratch + SC.h;  // fp16 mode: only the f16 image is consumed (by the c_fc GEMM)
+  CLIPFS_CHECK(ln_fwd(p, x_mid, b.ln2_g, b.ln2_b, h16 ? nullptr : h2, h16, stat2));
+  float* gbuf = p.scratch + SC.big;
+  CLIPFS_CHECK(gemm(v.cx, {.M = n, .N = 4 * d, .K = d, .A = h2, .B = b.w_fc, .planes = b.w_fc_p, .C = gbuf, .bias = b.b_fc,
+                           .act = 1, .aux_out = sv ? sv + SL.u : nullptr, .chain = CHAIN_OUT16, .a16_ready = h16}, st));
+  return gemm(v.cx, {.M = n, .N = d, .K = 4 * d, .A = gbuf, .B = b.w_pr, .planes = b.w_pr_p, .C = x_next, .bias = b.b_pr,
+                     .residual = x_mid, .chain = CHAIN_IN16}, st);
+}
+
+// rows == NULL: every block in full.  rows != NULL: the LAST block's output projection, LayerNorm 2 and MLP run on the
+// `batch` rows c * seq + rows[c] only (fwd_tail); the packed views always do.
+// Packed rows: every value of a live row equals the dense forward's bitwise -- LayerNorm, the adapters and the GEMM
+// epilogues are row-wise, the attention masks a dead key exactly as the padding, the dropout masks are drawn at the
+// full-layout row (drow0 + map[i]), and each R-row GEMM is launched unsplit.  The block output goes back to x only at
+// `rows`.
+static int tower_fwd(const Pass& p, float* x, const int32_t* rows, float* saved) {
+  const clipfs_tower* t = p.t;
+  const SavedLayout& SL = p.SL;
+  const bool train = saved != nullptr, packed = p.v.packed();
+  const size_t nd = (size_t)p.v.n * t->width;
+  const int lo = t->grad_lo;  // gradient floor: blocks below it save nothing (nothing of theirs is back-propagated)
+  float* xr = packed ? packed_x(p) : x;
+  const bool in_place = packed && train && lo == 0;  // the input is packed straight into the first saved record
+  if (packed)
+    CLIPFS_CHECK(clipfs_gather_rows_map(x, (size_t)t->width, p.v.map, in_place ? saved + SL.x_in : xr, p.v.n, t->width, p.st));
   for (int l = 0; l < t->layers; ++l) {
-    const clipfs_block& b = t->blocks[l];
-    const bool keep_l = train && l >= lo;  // this block's activations are kept for the backward
-    if (train && l == lo) {
-      hipError_t e = hipMemcpyAsync(saved + SL.x_in, x, (size_t)M * d * sizeof(float), hipMemcpyDeviceToDevice, st);
+    if (train && l == lo && !in_place) {  // the first saved record's input
+      hipError_t e = hipMemcpyAsync(saved + SL.x_in, xr, nd * sizeof(float), hipMemcpyDeviceToDevice, p.st);
       CLIPFS_REQUIRE(e == hipSuccess, "tower_fwd: memcpy failed: %s", hipGetErrorString(e));
     }
-    float* sv = keep_l ? saved + (size_t)(l - lo) * SL.total : nullptr;
-    const float* x_in = keep_l ? sv + SL.x_in : x;
-    float* h1 = keep_l ? sv + SL.h1 : scratch + SC.h;
-    float* qkv = keep_l ? sv + SL.qkv : scratch + SC.b3;
-    float* att = keep_l ? sv + SL.att : scratch + SC.b1;
-    float* x_mid = keep_l ? sv + SL.x_mid : x;
-    float* t_qkv = keep_l ? sv + SL.t_qkv : scratch + SC.dt;
-    float* t_o = keep_l ? sv + SL.t_o : scratch + SC.dt + al4((size_t)M * 3 * r);
-    float* x_next = keep_l ? (l + 1 < t->layers ? saved + (size_t)(l + 1 - lo) * SL.total + SL.x_in : x) : x;
-    // attention statistics: kept (saved record), or -- below the floor of a saving forward -- written to the MLP scratch
-    // (dead until the c_fc GEMM): the attention kernels are picked by whether lse is requested, and a block below the floor
-    // must produce bitwise the block output of the saving forward
-    float* lse = keep_l ? sv + SL.lse : (train ? scratch + SC.big : nullptr);
-    const unsigned qkv_mask = b.lora_a_qkv ? (b.lora_mask & 7u) : 0u;
-    const bool lora_o = b.lora_a_o && (b.lora_mask & 8u);
-    const uint32_t ds = t->dropout_stream0 + 4u * (uint32_t)l;
-    CLIPFS_CHECK(put_prompt(b, const_cast<float*>(x_in), nullptr, batch, t->seq, d, st));  // into the saved record, or x
-
-    // fp16 storage mode: producers write the f16 image of every GEMM operand next to (or instead of) the fp32 tensor
-    void* h16 = cx.a16;                                                        // [M, d] halves: ln1 / attention / ln2 / dx
-    void* dqkv16 = cx.a16 ? (void*)((char*)cx.a16 + (size_t)M * d * 2) : nullptr;  // [M, 3d] halves
-    (void)dqkv16;
-    void* keep = (keep_l && qkv_mask && keep_bits_saved(t)) ? (void*)(sv + SL.keep) : nullptr;
-    if (qkv_mask && clipfs_layernorm_fwd_lora_ok(d, r, 3)) {
-      // small ranks: the adapter's down-projection rides on the LayerNorm pass (the row is in registers there)
-      CLIPFS_CHECK(clipfs_layernorm_fwd_lora(x_in, d, b.ln1_g, b.ln1_b, h1, h16, keep_l ? sv + SL.stat1 : nullptr,
-                                             keep_l ? sv + SL.stat1 + M : nullptr, M, d, 1e-5f, b.lora_a_qkv, t_qkv, r, 3, qkv_mask,
-                                             t->lora_dropout, seed, ds, t->dropout_row0, keep, st));
-    } else {
-      if (h16)
-        CLIPFS_CHECK(clipfs_layernorm_fwd_f16(x_in, d, b.ln1_g, b.ln1_b, h1, h16, keep_l ? sv + SL.stat1 : nullptr,
-                                              keep_l ? sv + SL.stat1 + M : nullptr, M, d, 1e-5f, st));
-      else
-        CLIPFS_CHECK(clipfs_layernorm_fwd(x_in, d, b.ln1_g, b.ln1_b, h1, keep_l ? sv + SL.stat1 : nullptr,
-                                          keep_l ? sv + SL.stat1 + M : nullptr, M, d, 1e-5f, st));
-      if (qkv_mask)
-        CLIPFS_CHECK(clipfs_lora_down(h1, b.lora_a_qkv, t_qkv, M, d, r, 3, qkv_mask, t->lora_dropout, seed, ds, t->dropout_row0,
-                                      keep, st));
-    }
-    const bool q16 = qkv_f16(t);
-    CLIPFS_CHECK(gemm(cx, h1, b.w_qkv, b.w_qkv_p, qkv, M, 3 * d, d, b.b_qkv, nullptr, 0, nullptr, nullptr, qkv_mask ? t_qkv : nullptr,
-                      b.lora_b_qkv, r, 3, d, t->lora_scale, st, CHAIN_NONE, h16, q16 ? (void*)qkv : nullptr));
-    const void* att16 = nullptr;
-    if (f16_attention(t)) {
-      CLIPFS_CHECK(clipfs_attention_f16_fwd(qkv, q16, att, h16, lse, batch, t->seq, t->heads, t->causal, st));
-      att16 = h16;
-    } else
-      CLIPFS_CHECK(clipfs_attention_fwd(qkv, att, lse, batch, t->seq, t->heads, t->causal, st));
-    if (rows && l == t->layers - 1) {
-      // ---- the rest of the LAST block on one row per sequence: the head reads nothing else (jclip/model.py:121-124,
-      // :213-214) and every remaining operation is row-wise.  Compact buffers live in the MLP scratch (Ms (13 d + 2)
-      // floats <= M 4 d for seq >= 4); what the sparse backward gathers (x_mid, u, LayerNorm-2 statistics) is put back
-      // at those rows of the saved tensors, the block output at those rows of x.
-      const int seq = t->seq, Ms = batch;
-      float* att_s = scratch + SC.big;
-      float* xin_s = att_s + (size_t)Ms * d;
-      float* xmid_s = xin_s + (size_t)Ms * d;
-      float* h2_s = xmid_s + (size_t)Ms * d;
-      float* xout_s = h2_s + (size_t)Ms * d;
-      float* g_s = xout_s + (size_t)Ms * d;
-      float* u_s = g_s + (size_t)Ms * 4 * d;
-      float* mean_s = u_s + (size_t)Ms * 4 * d;
-      float* rstd_s = mean_s + al4((size_t)Ms);
-      CLIPFS_CHECK(clipfs_gather_seq_rows(att, (size_t)d, rows, att_s, Ms, seq, d, st));
-      CLIPFS_CHECK(clipfs_gather_seq_rows(x_in, (size_t)d, rows, xin_s, Ms, seq, d, st));
-      // fp16 storage mode: these `batch`-row products use the fp32 master weights (plane argument NULL) -- the f16 kernels
-      // are built for tens of thousands of rows -- and the pre-GELU rows go back into the f16 tensor the dense path keeps
-      const bool f16m = t->weight_format == 2;
-      CLIPFS_CHECK(gemm(cx, att_s, b.w_o, f16m ? nullptr : b.w_o_p, xmid_s, Ms, d, d, b.b_o, xin_s, 0, nullptr, nullptr, nullptr, nullptr,
-                        0, 0, 0, 0.f, st));
-      CLIPFS_CHECK(clipfs_layernorm_fwd(xmid_s, d, b.ln2_g, b.ln2_b, h2_s, keep_l ? mean_s : nullptr, keep_l ? rstd_s : nullptr, Ms,
-                                        d, 1e-5f, st));
-      CLIPFS_CHECK(gemm(cx, h2_s, b.w_fc, f16m ? nullptr : b.w_fc_p, g_s, Ms, 4 * d, d, b.b_fc, nullptr, 1, keep_l ? u_s : nullptr,
-                        nullptr, nullptr, nullptr, 0, 0, 0, 0.f, st));
-      CLIPFS_CHECK(gemm(cx, g_s, b.w_pr, f16m ? nullptr : b.w_pr_p, xout_s, Ms, d, 4 * d, b.b_pr, xmid_s, 0, nullptr, nullptr, nullptr,
-                        nullptr, 0, 0, 0, 0.f, st));
-      CLIPFS_CHECK(clipfs_put_seq_rows(xout_s, rows, x, (size_t)d, Ms, seq, d, st));
-      if (keep_l) {
-        CLIPFS_CHECK(clipfs_put_seq_rows(xmid_s, rows, sv + SL.x_mid, (size_t)d, Ms, seq, d, st));
-        if (f16m)
-          CLIPFS_CHECK(clipfs_put_seq_rows_f16(u_s, rows, sv + SL.u, (size_t)4 * d, Ms, seq, 4 * d, st));
-        else
-          CLIPFS_CHECK(clipfs_put_seq_rows(u_s, rows, sv + SL.u, (size_t)4 * d, Ms, seq, 4 * d, st));
-        CLIPFS_CHECK(clipfs_put_seq_rows(mean_s, rows, sv + SL.stat2, 1, Ms, seq, 1, st));
-        CLIPFS_CHECK(clipfs_put_seq_rows(rstd_s, rows, sv + SL.stat2 + M, 1, Ms, seq, 1, st));
-      }
-      break;
-    }
-    if (lora_o)
-      CLIPFS_CHECK(clipfs_lora_down(att, b.lora_a_o, t_o, M, d, r, 1, 1u, t->lora_dropout, seed, ds + 3, t->dropout_row0, nullptr, st));
-    CLIPFS_CHECK(gemm(cx, att, b.w_o, b.w_o_p, x_mid, M, d, d, b.b_o, x_in, 0, nullptr, nullptr, lora_o ? t_o : nullptr, b.lora_b_o, r,
-                      1, d, t->lora_scale, st, CHAIN_NONE, att16));
-    float* h2 = scratch + SC.h;
-    if (h16)  // only the f16 image is consumed (by the c_fc GEMM)
-      CLIPFS_CHECK(clipfs_layernorm_fwd_f16(x_mid, d, b.ln2_g, b.ln2_b, nullptr, h16, keep_l ? sv + SL.stat2 : nullptr,
-                                            keep_l ? sv + SL.stat2 + M : nullptr, M, d, 1e-5f, st));
-    else
-      CLIPFS_CHECK(clipfs_layernorm_fwd(x_mid, d, b.ln2_g, b.ln2_b, h2, keep_l ? sv + SL.stat2 : nullptr,
-                                        keep_l ? sv + SL.stat2 + M : nullptr, M, d, 1e-5f, st));
-    float* gbuf = scratch + SC.big;
-    CLIPFS_CHECK(gemm(cx, h2, b.w_fc, b.w_fc_p, gbuf, M, 4 * d, d, b.b_fc, nullptr, 1, keep_l ? sv + SL.u : nullptr, nullptr, nullptr,
-                      nullptr, 0, 0, 0, 0.f, st, CHAIN_OUT16, h16));
-    CLIPFS_CHECK(gemm(cx, gbuf, b.w_pr, b.w_pr_p, x_next, M, d, 4 * d, b.b_pr, x_mid, 0, nullptr, nullptr, nullptr, nullptr, 0, 0, 0,
-                      0.f, st, CHAIN_IN16));
+    CLIPFS_CHECK(fwd_block(p, l, x, rows, saved));
   }
   return CLIPFS_OK;
 }
 
 extern "C" int clipfs_tower_fwd(const clipfs_tower* t, float* x, int batch, float* saved, float* scratch, void* stream) {
-  return tower_fwd_impl(t, x, nullptr, batch, saved, scratch, stream);
+  Pass p;
+  CLIPFS_CHECK(begin_pass(&p, "tower_fwd", t, batch, x && scratch, nullptr, nullptr, 0, scratch, stream));
+  return tower_fwd(p, x, nullptr, saved);
 }
 
 extern "C" int clipfs_tower_fwd_rows(const clipfs_tower* t, float* x, const int32_t* rows, int batch, float* saved,
                                      float* scratch, void* stream) {
   CLIPFS_REQUIRE(t && rows, "tower_fwd_rows: null argument");
-  CLIPFS_CHECK(check_tower(t, batch));
-  return tower_fwd_impl(t, x, last_block_rows_ok(t) ? rows : nullptr, batch, saved, scratch, stream);
+  Pass p;
+  CLIPFS_CHECK(begin_pass(&p, "tower_fwd", t, batch, x && scratch, nullptr, nullptr, 0, scratch, stream));
+  return tower_fwd(p, x, last_block_rows_ok(t) ? rows : nullptr, saved);
 }
 
 extern "C" int clipfs_tower_rows_mode(const clipfs_tower* t) {
   return (t && t->blocks && t->layers > 0 && last_block_rows_ok(t)) ? 1 : 0;
 }
 
-// Adapter backward of one block.  Gradient slots NULL = the adapter is frozen: only its dx contribution (when wanted) is
-// computed, and with nothing wanted nothing is launched.
-static int lora_bwd_block(const clipfs_tower* t, bool dy16, const float* dy, const void* dy16p, const float* x,
-                          const float* tt, const float* A, const float* B, float* dt, float* gA, float* gB, float* dx,
-                          int M, int nseg, unsigned mask, uint32_t ds, const void* keep, float* work, hipStream_t st, int l) {
-  CLIPFS_REQUIRE((gA == nullptr) == (gB == nullptr), "tower_bwd: block %d has only one of the LoRA gradient slots", l);
-  if (!gA && !dx) return CLIPFS_OK;  // frozen and nothing below needs its input gradient
+// ---- backward ------------------------------------------------------------------------------------------------------
+
+// Adapter backward of one block on the view's rows.  Gradient slots NULL = the adapter is frozen: only its dx
+// contribution (when wanted) is computed, and with nothing wanted nothing is launched.
+struct LoraBwd {
+  const float* dy;
+  const void* dy16;  // non-NULL: the output gradient exists as this f16 image alone
+  const float* x;    // the adapter's input and its down-projection, as the view reads them (saved_rows)
+  const float* tt;
+  const float *A, *B;
+  float *gA, *gB;
+  float* dx;         // accumulated into (NULL: not wanted)
+  int nseg;
+  unsigned mask;
+  uint32_t ds;
+  const void* keep;
+};
+static int lora_bwd_block(const Pass& p, int l, const LoraBwd& a) {
+  const clipfs_tower* t = p.t;
+  CLIPFS_REQUIRE((a.gA == nullptr) == (a.gB == nullptr), "tower_bwd: block %d has only one of the LoRA gradient slots", l);
+  if (!a.gA && !a.dx) return CLIPFS_OK;  // frozen and nothing below needs its input gradient
   const int d = t->width, r = t->lora_r;
-  if (dy16)
-    return clipfs_lora_bwd_f16dy(dy16p, x, tt, A, B, dt, gA, gB, dx, M, d, d, r, nseg, mask, t->lora_scale, t->lora_dropout,
-                                 t->dropout_seed, ds, t->dropout_row0, keep, work, st);
-  return clipfs_lora_bwd(dy, x, tt, A, B, dt, gA, gB, dx, M, d, d, r, nseg, mask, t->lora_scale, t->lora_dropout,
-                         t->dropout_seed, ds, t->dropout_row0, keep, work, st);
+  float* dt = p.scratch + p.SC.dt;
+  float* work = p.scratch + p.SC.work;
+  if (a.dy16)
+    return clipfs_lora_bwd_f16dy(a.dy16, a.x, a.tt, a.A, a.B, dt, a.gA, a.gB, a.dx, p.v.n, d, d, r, a.nseg, a.mask,
+                                 t->lora_scale, t->lora_dropout, t->dropout_seed, a.ds, t->dropout_row0, a.keep, work, p.st);
+  return clipfs_lora_bwd(a.dy, a.x, a.tt, a.A, a.B, dt, a.gA, a.gB, a.dx, p.v.n, d, d, r, a.nseg, a.mask, t->lora_scale,
+                         t->lora_dropout, t->dropout_seed, a.ds, t->dropout_row0, a.keep, work, p.st);
 }
 
-// blocks l_hi ... grad_lo of the backward; dx [batch*seq, width] in/out
-static int tower_bwd_range(const clipfs_tower* t, float* dx, int batch, const float* saved, float* scratch,
-                           int stop_at_input, hipStream_t st, int l_hi) {
-  const int M = batch * t->seq, d = t->width, r = t->lora_r;
-  const SavedLayout SL = saved_layout(t, (size_t)M);
-  const ScratchLayout SC = scratch_layout(t, (size_t)M);
-  const TowerCtx cx = make_ctx(t, scratch, SC);
-  void* h16 = cx.a16;                                                           // f16 image of dx (then of d ln-out ...)
-  void* dqkv16 = cx.a16 ? (void*)((char*)cx.a16 + (size_t)M * d * 2) : nullptr;  // [M, 3d] halves
-  if (h16) CLIPFS_CHECK(clipfs_convert_f16(dx, h16, (size_t)M * d, st));       // later images come from LayerNorm backward
-  const int lo = t->grad_lo;
-  for (int l = l_hi; l >= lo; --l) {
-    const clipfs_block& b = t->blocks[l];
-    const float* sv = saved + (size_t)(l - lo) * SL.total;
-    CLIPFS_REQUIRE(b.w_pr_t && b.w_fc_t && b.w_o_t && b.w_qkv_t, "tower_bwd: block %d lacks transposed weights", l);
-    CLIPFS_REQUIRE(t->weight_format != 2 || (b.w_pr_t_p && b.w_fc_t_p && b.w_o_t_p && b.w_qkv_t_p),
-                   "tower_bwd: block %d lacks f16 copies of the transposed weights", l);
-    const unsigned qkv_mask = b.lora_a_qkv ? (b.lora_mask & 7u) : 0u;
-    const bool lora_o = b.lora_a_o && (b.lora_mask & 8u);
-    const uint32_t ds = t->dropout_stream0 + 4u * (uint32_t)l;
-    float* du = scratch + SC.big;
-    float* dh = scratch + SC.h;
-    float* datt = scratch + SC.b1;
-    float* dqkv = scratch + SC.b3;
-    float* dt = scratch + SC.dt;
-    float* work = scratch + SC.work;
-    float* bwork = scratch + SC.bwork;
-    // bias gradients: column sums of the tensors below, each taken right after it is written (c_proj: the residual
-    // gradient entering the block; c_fc: du; ln_2: dh2; out projection: dx after LN2'; q/k/v: dqkv; ln_1: dh1)
-    CLIPFS_CHECK(bias_sum(dx, M, d, d, b.g_b_pr, nullptr, nullptr, bwork, st));
-    // MLP: du = (dx Wpr) * gelu'(u) ; dh2 = du Wfc ; dx += LN2'(dh2)
-    CLIPFS_CHECK(gemm(cx, dx, b.w_pr_t, b.w_pr_t_p, du, M, 4 * d, d, nullptr, nullptr, 2, nullptr, sv + SL.u, nullptr, nullptr, 0, 0, 0,
-                      0.f, st, CHAIN_OUT16, h16));
-    CLIPFS_CHECK(bias_sum(du, M, 4 * d, 4 * d, b.g_b_fc, nullptr, nullptr, bwork, st));
-    CLIPFS_CHECK(gemm(cx, du, b.w_fc_t, b.w_fc_t_p, dh, M, d, 4 * d, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 0.f,
-                      st, CHAIN_IN16));
-    CLIPFS_CHECK(bias_sum(dh, M, d, d, b.g_ln2_b, nullptr, nullptr, bwork, st));
-    if (h16)
-      CLIPFS_CHECK(clipfs_layernorm_bwd_f16(dh, sv + SL.x_mid, d, b.ln2_g, sv + SL.stat2, sv + SL.stat2 + M, dx, dx, h16, d,
-                                            M, d, st));
-    else
-      CLIPFS_CHECK(clipfs_layernorm_bwd(dh, sv + SL.x_mid, d, b.ln2_g, sv + SL.stat2, sv + SL.stat2 + M, dx, dx, d, M, d,
-                                        st));
-    CLIPFS_CHECK(bias_sum(dx, M, d, d, b.g_b_o, nullptr, nullptr, bwork, st));
-    // attention output projection.  fp16 storage mode without an o-projection adapter: its only consumer is the f16
-    // attention backward, which rounds dO to f16 for its MFMA operands anyway -- the GEMM writes the f16 image alone (into
-    // the same scratch slot): a quarter of the epilogue bytes of an fp32 result, half the bytes the attention kernels stage
-    const bool datt16 = f16_attention(t) && !lora_o && h16 != nullptr;
-    CLIPFS_CHECK(gemm(cx, dx, b.w_o_t, b.w_o_t_p, datt, M, d, d, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 0.f,
-                      st, CHAIN_NONE, h16, datt16 ? (void*)datt : nullptr));
-    if (lora_o)
-      CLIPFS_CHECK(lora_bwd_block(t, false, dx, nullptr, sv + SL.att, sv + SL.t_o, b.lora_a_o, b.lora_b_o, dt, b.g_lora_a_o,
-                                  b.g_lora_b_o, datt, M, 1, 1u, ds + 3, nullptr, work, st, l));
-    // (the D_i work vector of the long-sequence kernels lives in the dt scratch slot's neighbour: reuse `dh`, dead here)
-    const void* dqkv16_ready = nullptr;
-    // fp16 storage mode: the dgrad GEMM and (matrix-core shapes) the adapter backward read the f16 image of dqkv, so the
-    // attention backward does not write the fp32 tensor at all (404 MB per ViT-L/14 block at 128 images)
-    const bool dy16 = f16_attention(t) && dqkv16 && (!qkv_mask || clipfs_lora_bwd_f16dy_ok(d, d, r, 3));
-    if (f16_attention(t)) {
-      CLIPFS_CHECK(clipfs_attention_f16_bwd(sv + SL.qkv, qkv_f16(t), datt, datt16 ? 1 : 0, sv + SL.att, sv + SL.lse,
-                                            dy16 ? nullptr : dqkv, dqkv16, dh, batch, t->seq, t->heads, t->causal, st));
-      dqkv16_ready = dqkv16;
-    } else
-      CLIPFS_CHECK(clipfs_attention_bwd(sv + SL.qkv, datt, sv + SL.att, sv + SL.lse, dqkv, dh, batch, t->seq, t->heads,
-                                        t->causal, st));
-    CLIPFS_CHECK(bias_sum(dqkv, M, 3 * d, d, b.g_b_q, b.g_b_k, b.g_b_v, bwork, st));
-    // a trainable prompt needs the block's input gradient even at the floor
-    const bool need_dx = !(l == lo && stop_at_input) || b.g_prompt;
-    // dh1 (the gradient wrt LayerNorm 1's output) is also needed for ln_1's bias gradient, even where dx is not
-    const bool need_dh = need_dx || b.g_ln1_b;
-    if (need_dh)
-      CLIPFS_CHECK(gemm(cx, dqkv, b.w_qkv_t, b.w_qkv_t_p, dh, M, d, 3 * d, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, 0, 0, 0,
-                        0.f, st, CHAIN_NONE, dqkv16_ready));
-    if (qkv_mask)
-      CLIPFS_CHECK(lora_bwd_block(t, dy16, dqkv, dqkv16, sv + SL.h1, sv + SL.t_qkv, b.lora_a_qkv, b.lora_b_qkv, dt,
-                                  b.g_lora_a_qkv, b.g_lora_b_qkv, need_dh ? dh : nullptr, M, 3, qkv_mask, ds,
-                                  keep_bits_saved(t) ? (const void*)(sv + SL.keep) : nullptr, work, st, l));
-    CLIPFS_CHECK(bias_sum(dh, M, d, d, b.g_ln1_b, nullptr, nullptr, bwork, st));
-    if (need_dx) {
-      if (h16)
-        CLIPFS_CHECK(clipfs_layernorm_bwd_f16(dh, sv + SL.x_in, d, b.ln1_g, sv + SL.stat1, sv + SL.stat1 + M, dx, dx, h16, d,
-                                              M, d, st));
-      else
-        CLIPFS_CHECK(clipfs_layernorm_bwd(dh, sv + SL.x_in, d, b.ln1_g, sv + SL.stat1, sv + SL.stat1 + M, dx, dx, d, M, d,
-                                          st));
-      CLIPFS_CHECK(harvest_prompt(b, dx, h16, nullptr, batch, t->seq, d, st));
+// fp16 storage mode without an o-projection adapter: the only consumer of the gradient wrt the attention output is the
+// f16 attention backward, which rounds dO to f16 for its MFMA operands anyway -- the GEMM writes the f16 image alone (into
+// the same scratch slot): a quarter of the epilogue bytes of an fp32 result, half the bytes the attention kernels stage.
+// h16: the walk's f16 image of dx (NULL: the walk keeps none)
+static inline bool datt_f16(const clipfs_tower* t, const clipfs_block& b, const void* h16) {
+  return f16_attention(t) && !adapters(b).o && h16 != nullptr;
+}
+
+// a block's input gradient is wanted unless the walk stops at it -- and a trainable prompt needs it even at the floor
+static inline bool needs_dx(const clipfs_tower* t, int l, int stop_at_input) {
+  return !(l == t->grad_lo && stop_at_input) || t->blocks[l].g_prompt;
+}
+
+// Upper half of a block's backward, down to the attention residual: dx (in: the gradient wrt the block output; out: wrt
+// x_mid) and the gradient wrt the attention output in the b1 slot.  Slots: big = du (| the gathered u behind it); h = dh.
+// Bias gradients are column sums of the tensors below, each taken right after it is written (c_proj: the residual
+// gradient entering the block; c_fc: du; ln_2: dh2; out projection: dx after LN2').
+static int bwd_mlp_half(const Pass& p, int l, const float* sv, float* dx, void* h16) {
+  const clipfs_tower* t = p.t;
+  const clipfs_block& b = t->blocks[l];
+  const RowView& v = p.v;
+  const SavedLayout& SL = p.SL;
+  const int n = v.n, d = t->width;
+  float* du = p.scratch + p.SC.big;
+  float* dh = p.scratch + p.SC.h;
+  float* datt = p.scratch + p.SC.b1;
+  CLIPFS_CHECK(bias_sum(p, dx, n, d, d, b.g_b_pr));
+  // MLP: du = (dx Wpr) * gelu'(u) ; dh2 = du Wfc ; dx += LN2'(dh2)
+  const float* u;
+  CLIPFS_CHECK(saved_rows(p, sv + SL.u, 4 * d, du + 4 * (size_t)n * d, &u));
+  CLIPFS_CHECK(gemm(v.cx, {.M = n, .N = 4 * d, .K = d, .A = dx, .B = b.w_pr_t, .planes = b.w_pr_t_p, .C = du, .act = 2,
+                           .aux_in = u, .chain = CHAIN_OUT16, .a16_ready = h16}, p.st));
+  CLIPFS_CHECK(bias_sum(p, du, n, 4 * d, 4 * d, b.g_b_fc));
+  CLIPFS_CHECK(gemm(v.cx, {.M = n, .N = d, .K = 4 * d, .A = du, .B = b.w_fc_t, .planes = b.w_fc_t_p, .C = dh,
+                           .chain = CHAIN_IN16}, p.st));
+  CLIPFS_CHECK(bias_sum(p, dh, n, d, d, b.g_ln2_b));
+  CLIPFS_CHECK(ln_bwd(p, dh, sv + SL.x_mid, b.ln2_g, sv + SL.stat2, dx, dx, h16));
+  CLIPFS_CHECK(bias_sum(p, dx, n, d, d, b.g_b_o));
+  // attention output projection
+  CLIPFS_CHECK(gemm(v.cx, {.M = n, .N = d, .K = d, .A = dx, .B = b.w_o_t, .planes = b.w_o_t_p, .C = datt, .a16_ready = h16,
+                           .c16_only = datt_f16(t, b, h16) ? (void*)datt : nullptr}, p.st));
+  if (!adapters(b).o) return CLIPFS_OK;
+  // (packed rows: no dropout here, pack_dropout_ok -- the adapter backward evaluates no mask)
+  const GatherSlots gs = gather_slots(p);
+  const float *att, *t_o;
+  CLIPFS_CHECK(saved_rows(p, sv + SL.att, d, gs.att, &att));
+  CLIPFS_CHECK(saved_rows(p, sv + SL.t_o, t->lora_r, gs.t_o, &t_o));
+  return lora_bwd_block(p, l, {.dy = dx, .x = att, .tt = t_o, .A = b.lora_a_o, .B = b.lora_b_o, .gA = b.g_lora_a_o,
+                               .gB = b.g_lora_b_o, .dx = datt, .nseg = 1, .mask = 1u,
+                               .ds = t->dropout_stream0 + 4u * (uint32_t)l + 3});
+}
+
+// Lower half: attention, the QKV projection and LayerNorm 1.  In: the gradient wrt the attention output (b1 slot) and
+// wrt the attention residual (dx).  Out: dx = the gradient wrt the block input, when needs_dx.  res_s != NULL (the dense
+// rows under the compact head): the residual gradient is zero except on one row per sequence, res_s [batch, d] --
+// LayerNorm 1's backward then runs without a residual input, writes every row of dx, and res_s is added at `rows`.
+// Slots: b3 = dqkv; h = the D_i work vector of the long-sequence attention kernels, then dh1; big = the gathered
+// h1 / t_qkv / keep bits.
+static int bwd_attn_half(const Pass& p, int l, const float* sv, float* dx, void* h16, const float* res_s,
+                         const int32_t* rows, int stop_at_input) {
+  const clipfs_tower* t = p.t;
+  const clipfs_block& b = t->blocks[l];
+  const RowView& v = p.v;
+  const SavedLayout& SL = p.SL;
+  const int n = v.n, d = t->width, r = t->lora_r;
+  const unsigned qkv_mask = adapters(b).qkv_mask;
+  float* dh = p.scratch + p.SC.h;
+  float* datt = p.scratch + p.SC.b1;
+  float* dqkv = p.scratch + p.SC.b3;
+  // fp16 storage mode: the dgrad GEMM and (matrix-core shapes) the adapter backward read the f16 image of dqkv, so the
+  // attention backward does not write the fp32 tensor at all (404 MB per ViT-L/14 block at 128 images)
+  const bool f16a = f16_attention(t);
+  const bool dy16 = f16a && p.dqkv16 && (!qkv_mask || clipfs_lora_bwd_f16dy_ok(d, d, r, 3));
+  if (v.saved_packed())  // packed q/k/v and O; packed dO and dqkv either way
+    CLIPFS_CHECK(clipfs_attention_bwd_packed_io(sv + SL.qkv, datt, sv + SL.att, sv + SL.lse, dqkv, v.off, p.batch, t->seq,
+                                                t->heads, p.st));
+  else if (v.packed())
+    CLIPFS_CHECK(clipfs_attention_bwd_packed(sv + SL.qkv, datt, sv + SL.att, sv + SL.lse, dqkv, v.off, p.batch, t->seq,
+                                             t->heads, p.st));
+  else if (f16a)
+    CLIPFS_CHECK(clipfs_attention_f16_bwd(sv + SL.qkv, qkv_f16(t), datt, datt_f16(t, b, h16) ? 1 : 0, sv + SL.att,
+                                          sv + SL.lse, dy16 ? nullptr : dqkv, p.dqkv16, dh, p.batch, t->seq, t->heads,
+                                          t->causal, p.st));
+  else
+    CLIPFS_CHECK(clipfs_attention_bwd(sv + SL.qkv, datt, sv + SL.att, sv + SL.lse, dqkv, dh, p.batch, t->seq, t->heads,
+                                      t->causal, p.st));
+  CLIPFS_CHECK(bias_sum(p, dqkv, n, 3 * d, d, b.g_b_q, b.g_b_k, b.g_b_v));
+  const bool need_dx = needs_dx(t, l, stop_at_input);
+  // dh1 (the gradient wrt LayerNorm 1's output) is also needed for ln_1's bias gradient, even where dx is not
+  const bool need_dh = need_dx || b.g_ln1_b;
+  if (need_dh)
+    CLIPFS_CHECK(gemm(v.cx, {.M = n, .N = d, .K = 3 * d, .A = dqkv, .B = b.w_qkv_t, .planes = b.w_qkv_t_p, .C = dh,
+                             .a16_ready = f16a ? p.dqkv16 : nullptr}, p.st));
+  if (qkv_mask) {
+    const float *h1 = sv + SL.h1, *t_qkv = sv + SL.t_qkv, *keep = keep_bits_saved(t) ? sv + SL.keep : nullptr;
+    if (b.g_lora_a_qkv || need_dh) {  // (frozen and dh not wanted: lora_bwd_block launches nothing)
+      const GatherSlots gs = gather_slots(p);
+      CLIPFS_CHECK(saved_rows(p, h1, d, gs.h1, &h1));
+      CLIPFS_CHECK(saved_rows(p, t_qkv, 3 * r, gs.t_qkv, &t_qkv));
+      if (keep) CLIPFS_CHECK(saved_rows(p, keep, d / 8, gs.keep, &keep));  // uint16 per float4 of h1: d / 8 floats per row
     }
+    CLIPFS_CHECK(lora_bwd_block(p, l, {.dy = dqkv, .dy16 = dy16 ? p.dqkv16 : nullptr, .x = h1, .tt = t_qkv, .A = b.lora_a_qkv,
+                                       .B = b.lora_b_qkv, .gA = b.g_lora_a_qkv, .gB = b.g_lora_b_qkv,
+                                       .dx = need_dh ? dh : nullptr, .nseg = 3, .mask = qkv_mask,
+                                       .ds = t->dropout_stream0 + 4u * (uint32_t)l, .keep = keep}));
   }
-  return CLIPFS_OK;
+  CLIPFS_CHECK(bias_sum(p, dh, n, d, d, b.g_ln1_b));
+  if (!need_dx) return CLIPFS_OK;
+  CLIPFS_CHECK(ln_bwd(p, dh, sv + SL.x_in, b.ln1_g, sv + SL.stat1, res_s ? nullptr : dx, dx, h16));
+  if (res_s) CLIPFS_CHECK(clipfs_add_seq_rows(res_s, rows, dx, p.batch, t->seq, d, p.st));
+  return harvest_prompt(p, b, dx, h16);
 }
 
+// blocks l_hi ... grad_lo on the view's rows.  dx [batch*seq, width]: dense rows in/out.  Packed rows: the gradient
+// wrt block l_hi's output is in packed_x on entry, and dx receives the gradient wrt the tower input in the full layout
+// (unless stop_at_input).
+static int bwd_walk(const Pass& p, float* dx, const float* saved, int stop_at_input, int l_hi) {
+  const clipfs_tower* t = p.t;
+  const int d = t->width;
+  float* dxw = p.v.packed() ? packed_x(p) : dx;
+  void* h16 = p.v.cx.a16;  // fp16 mode: f16 image of dx; later images come from the LayerNorm backward
+  if (h16) CLIPFS_CHECK(clipfs_convert_f16(dxw, h16, (size_t)p.v.n * d, p.st));
+  for (int l = l_hi; l >= t->grad_lo; --l) {
+    const float* sv = saved + (size_t)(l - t->grad_lo) * p.SL.total;
+    CLIPFS_CHECK(bwd_mlp_half(p, l, sv, dxw, h16));
+    CLIPFS_CHECK(bwd_attn_half(p, l, sv, dxw, h16, nullptr, nullptr, stop_at_input));
+  }
+  if (!p.v.packed() || stop_at_input) return CLIPFS_OK;
+  // the dead rows are exact zeros
+  hipError_t e = hipMemsetAsync(dx, 0, (size_t)p.M * d * sizeof(float), p.st);
+  CLIPFS_REQUIRE(e == hipSuccess, "tower_bwd_packed: memset failed: %s", hipGetErrorString(e));
+  return clipfs_put_rows_map(dxw, p.v.map, dx, (size_t)d, p.v.n, d, p.st);
+}
+
+// The last block's MLP and output projection on the `batch` rows that carry gradient (dxs [batch, d]: the gradient wrt
+// the block output at rows[c] of each sequence; every other row's is an exact zero, so the bias gradients are column
+// sums over those rows).  Out: the gradient wrt the attention residual and wrt the attention output on those rows.  The
+// compact buffers live in the MLP scratch, which this block does not otherwise use: batch (8 d + 4 d + 2) floats
+// <= M 4 d for seq >= 3.
+static int bwd_head(const Pass& p, const float* sv, const float* dxs, const int32_t* rows, float** dxm_out,
+                    float** datt_out) {
+  const clipfs_tower* t = p.t;
+  const clipfs_block& b = t->blocks[t->layers - 1];
+  const SavedLayout& SL = p.SL;
+  const int d = t->width, Ms = p.batch;
+  const size_t Md = (size_t)Ms * d;
+  float* at = p.scratch + p.SC.big;
+  auto take = [&at](size_t floats) { float* q = at; at += floats; return q; };
+  float *u_s = take(4 * Md), *du_s = take(4 * Md), *xmid_s = take(Md), *dh_s = take(Md), *dxm_s = take(Md);
+  float *datt_s = take(Md), *mean_s = take(al4((size_t)Ms)), *rstd_s = take((size_t)Ms);
+  CLIPFS_CHECK(bias_sum(p, dxs, Ms, d, d, b.g_b_pr));
+  // fp16 storage mode: the `batch`-row products use the fp32 master weights (plane argument NULL); the saved pre-GELU
+  // activation is an f16 tensor there
+  const bool f16m = t->weight_format == 2;
+  CLIPFS_CHECK(pick_rows(p, rows, sv + SL.u, 4 * d, u_s, f16m));
+  CLIPFS_CHECK(pick_rows(p, rows, sv + SL.x_mid, d, xmid_s));
+  CLIPFS_CHECK(pick_rows(p, rows, sv + SL.stat2, 1, mean_s));
+  CLIPFS_CHECK(pick_rows(p, rows, sv + SL.stat2 + p.v.srows, 1, rstd_s));
+  CLIPFS_CHECK(gemm(p.cx, {.M = Ms, .N = 4 * d, .K = d, .A = dxs, .B = b.w_pr_t, .planes = f16m ? nullptr : b.w_pr_t_p,
+                           .C = du_s, .act = 2, .aux_in = u_s}, p.st));
+  CLIPFS_CHECK(bias_sum(p, du_s, Ms, 4 * d, 4 * d, b.g_b_fc));
+  CLIPFS_CHECK(gemm(p.cx, {.M = Ms, .N = d, .K = 4 * d, .A = du_s, .B = b.w_fc_t, .planes = f16m ? nullptr : b.w_fc_t_p,
+                           .C = dh_s}, p.st));
+  CLIPFS_CHECK(bias_sum(p, dh_s, Ms, d, d, b.g_ln2_b));
+  CLIPFS_CHECK(clipfs_layernorm_bwd(dh_s, xmid_s, d, b.ln2_g, mean_s, rstd_s, dxs, dxm_s, d, Ms, d, p.st));
+  CLIPFS_CHECK(bias_sum(p, dxm_s, Ms, d, d, b.g_b_o));
+  *dxm_out = dxm_s;
+  *datt_out = datt_s;
+  return gemm(p.cx, {.M = Ms, .N = d, .K = d, .A = dxm_s, .B = b.w_o_t, .planes = f16m ? nullptr : b.w_o_t_p, .C = datt_s},
+              p.st);
+}
+
+// Every backward entry point.  rows == NULL: dx holds the gradient wrt the tower output on every row
+// (clipfs_tower_bwd).  rows != NULL: dxs holds it on one row per sequence -- the last block runs bwd_head and then only
+// its lower half on the view's rows.
+static int tower_bwd(const Pass& p, const float* dxs, const int32_t* rows, float* dx, const float* saved,
+                     int stop_at_input) {
+  const clipfs_tower* t = p.t;
+  CLIPFS_CHECK(check_bwd_weights(t));
+  const int seq = t->seq, d = t->width, top = t->layers - 1;
+  if (!rows) return bwd_walk(p, dx, saved, stop_at_input, top);
+  if (!last_block_rows_ok(t)) {  // dense fall-back: the row gradients scattered into zeros
+    CLIPFS_CHECK(clipfs_scatter_rows(dxs, rows, dx, p.batch, seq, d, p.st));
+    return bwd_walk(p, dx, saved, stop_at_input, top);
+  }
+  const float* sv = saved + (size_t)(top - t->grad_lo) * p.SL.total;
+  float *dxm_s, *datt_s;
+  CLIPFS_CHECK(bwd_head(p, sv, dxs, rows, &dxm_s, &datt_s));
+  // attention and the QKV projection see every row of the view again
+  float* datt = p.scratch + p.SC.b1;
+  if (p.v.packed()) {
+    // datt and dx (the residual around the attention) are zero except at the EOT rows.  Put before the lower half
+    // gathers anything into the MLP scratch that holds datt_s / dxm_s.
+    float* dxw = packed_x(p);
+    hipError_t e = hipMemsetAsync(datt, 0, ((size_t)(dxw - datt) + (size_t)p.v.n * d) * sizeof(float), p.st);
+    CLIPFS_REQUIRE(e == hipSuccess, "tower_bwd_packed: memset failed: %s", hipGetErrorString(e));
+    CLIPFS_CHECK(clipfs_put_rows_map(datt_s, p.v.eotp, datt, (size_t)d, p.batch, d, p.st));
+    CLIPFS_CHECK(clipfs_put_rows_map(dxm_s, p.v.eotp, dxw, (size_t)d, p.batch, d, p.st));
+    CLIPFS_CHECK(bwd_attn_half(p, top, sv, dxw, nullptr, nullptr, nullptr, stop_at_input));
+  } else {
+    // LayerNorm 1's backward writes every row of dx (no f16 image: bwd_walk makes it on entry to the blocks below)
+    CLIPFS_CHECK(clipfs_scatter_rows(datt_s, rows, datt, p.batch, seq, d, p.st));
+    CLIPFS_CHECK(bwd_attn_half(p, top, sv, dx, nullptr, dxm_s, rows, stop_at_input));
+  }
+  if (!needs_dx(t, top, stop_at_input)) return CLIPFS_OK;
+  return bwd_walk(p, dx, saved, stop_at_input, top - 1);
+}
 
 extern "C" int clipfs_tower_bwd(const clipfs_tower* t, float* dx, int batch, const float* saved, float* scratch,
                                 int stop_at_input, void* stream) {
-  CLIPFS_CHECK(check_tower(t, batch));
-  CLIPFS_REQUIRE(t->grad_lo == 0 || stop_at_input,
-                 "tower_bwd: grad_lo %d > 0 needs stop_at_input (the input gradient runs through every block)", t->grad_lo);
-  CLIPFS_REQUIRE(dx && saved && scratch, "tower_bwd: null buffer");
-  const ScratchLayout SC = scratch_layout(t, (size_t)batch * t->seq);
-  CLIPFS_REQUIRE(!t->gemm_counters || t->gemm_counters_ints >= SC.counter_ints,
-                 "tower: gemm_counters holds %zu ints, %zu needed", t->gemm_counters_ints, SC.counter_ints);
-  return tower_bwd_range(t, dx, batch, saved, scratch, stop_at_input, (hipStream_t)stream, t->layers - 1);
+  Pass p;
+  CLIPFS_CHECK(begin_pass(&p, "tower_bwd", t, batch, dx && saved && scratch, &stop_at_input, nullptr, 0, scratch, stream));
+  return tower_bwd(p, nullptr, nullptr, dx, saved, stop_at_input);
 }
 
-// ---- packed (live-row) backward of a causal tower ------------------------------------------------------------------
-// Sequence c carries gradient on its rows c*seq + 0 .. eot_c only (the head reads its EOT row and a row never attends to a
-// later one): below the last block's compact part every operation runs on the R = sum (eot_c + 1) live rows, packed
-// caption after caption.  plan (int32, device): off[0 .. batch] (exclusive prefix sum of eot_c + 1, off[batch] = R),
-// eotp[0 .. batch) = off[c + 1] - 1 (packed row of each EOT), map[0 .. R) = c * seq + p (full-layout row of packed row i).
-// The saved per-row tensors a block's GEMM epilogue and adapter backward read (u, h1, t_qkv, keep bits; att / t_o for an
-// o-projection adapter) are gathered into packed scratch; the LayerNorm backward reads x and its statistics in place
-// through the row map (clipfs_layernorm_bwd_rows).
-struct PackPlan {
-  const int32_t* off;
-  const int32_t* eotp;
-  const int32_t* map;
-  int R;
-};
+extern "C" int clipfs_tower_bwd_sparse(const clipfs_tower* t, const float* dxs, const int32_t* rows, float* dx, int batch,
+                                       const float* saved, float* scratch, int stop_at_input, void* stream) {
+  Pass p;
+  CLIPFS_CHECK(begin_pass(&p, "tower_bwd_sparse", t, batch, dxs && rows && dx && saved && scratch, &stop_at_input, nullptr,
+                          0, scratch, stream));
+  return tower_bwd(p, dxs, rows, dx, saved, stop_at_input);
+}
+
+// ---- live rows of a causal tower -----------------------------------------------------------------------------------
 
 static bool pack_dropout_ok(const clipfs_tower* t) {
   // the adapter backward must not evaluate Philox on packed rows (it would index the masks by the packed row): with
@@ -571,15 +900,16 @@ static bool pack_dropout_ok(const clipfs_tower* t) {
   const bool drop = t->lora_r > 0 && t->lora_dropout > 0.f && t->dropout_seed != 0;
   if (!drop) return true;
   for (int l = t->grad_lo; l < t->layers; ++l) {
-    const clipfs_block& b = t->blocks[l];
-    if (b.lora_a_o && (b.lora_mask & 8u)) return false;
-    if (b.lora_a_qkv && (b.lora_mask & 7u) && !keep_bits_saved(t)) return false;
+    const Adapters ad = adapters(t->blocks[l]);
+    if (ad.o) return false;
+    if (ad.qkv_mask && !keep_bits_saved(t)) return false;
   }
   return true;
 }
 
-// Packing runs only where its buffers fit the existing scratch slots (R <= M / 2, see tower_bwd_packed_range), its
-// kernels exist and the tower is large enough to gain; everything else takes the dense path of clipfs_tower_bwd_sparse, so the scratch size does not change.
+// Packing runs only where its buffers fit the existing scratch slots (R <= M / 2: b1 = the attention gradient | the
+// residual gradient; big = du | the gathered u, then the other gathered tensors), its kernels exist and the tower is
+// large enough to gain; everything else keeps the dense rows, so the scratch size does not change.
 // Below kPackMinRows dense rows the text backward is launch-bound (a few captions: tens of microseconds per block) and
 // the per-block gathers would cost what the smaller products save; such towers keep the dense rows and their arithmetic.
 constexpr int kPackMinRows = 2048;
@@ -604,420 +934,65 @@ static bool pack_ok(const clipfs_tower* t, int batch, int R) {
   return true;
 }
 
-// blocks l_hi ... grad_lo on the packed rows.  On entry dx_p (scratch b1, second half) holds the packed gradient wrt
-// block l_hi's output -- or, with attn_only_top, wrt its attention residual, datt_p (b1, first half) the gradient wrt its
-// attention output.  Slots (R <= M / 2): b1 = datt_p | dx_p; big = du_p | u_p in the MLP part, then the gathered
-// h1 / t_qkv / keep bits (/ att / t_o); b3 = dqkv_p; h = dh_p.
-// saved_packed: the saved tensors are the live-row forward's (clipfs_tower_fwd_packed: R packed rows per record), read
-// in place -- no gathers, the plain LayerNorm backward, the attention backward on packed q/k/v and O.
-static int tower_bwd_packed_range(const clipfs_tower* t, float* dx, int batch, const PackPlan& P, const float* saved,
-                                  float* scratch, int stop_at_input, hipStream_t st, int l_hi, bool attn_only_top,
-                                  bool saved_packed) {
-  const int M = batch * t->seq, d = t->width, r = t->lora_r, R = P.R;
-  const SavedLayout SL = saved_packed ? saved_layout_packed(t, (size_t)R, (size_t)batch) : saved_layout(t, (size_t)M);
-  const int srows = saved_packed ? R : M;  // rows of a saved record (offset of the rstd half of a statistics slot)
-  const ScratchLayout SC = scratch_layout(t, (size_t)M);
-  const TowerCtx cx = make_ctx(t, scratch, SC);
-  const size_t Rd = (size_t)R * d;
-  float* datt_p = scratch + SC.b1;
-  float* dx_p = datt_p + al4(Rd);
-  float* dh_p = scratch + SC.h;
-  float* du_p = scratch + SC.big;
-  float* u_p = du_p + 4 * Rd;
-  float* dqkv_p = scratch + SC.b3;
-  float* h1_p = scratch + SC.big;
-  float* tq_p = h1_p + al4(Rd);
-  float* keep_p = tq_p + al4((size_t)R * 3 * r);
-  float* att_p = keep_p + al4((size_t)R * d / 8);
-  float* to_p = att_p + al4(Rd);
-  float* dt = scratch + SC.dt;
-  float* work = scratch + SC.work;
-  float* bwork = scratch + SC.bwork;
-  const int lo = t->grad_lo;
-  for (int l = l_hi; l >= lo; --l) {
-    const clipfs_block& b = t->blocks[l];
-    const float* sv = saved + (size_t)(l - lo) * SL.total;
-    CLIPFS_REQUIRE(b.w_pr_t && b.w_fc_t && b.w_o_t && b.w_qkv_t, "tower_bwd: block %d lacks transposed weights", l);
-    const unsigned qkv_mask = b.lora_a_qkv ? (b.lora_mask & 7u) : 0u;
-    const bool lora_o = b.lora_a_o && (b.lora_mask & 8u);
-    const uint32_t ds = t->dropout_stream0 + 4u * (uint32_t)l;
-    if (!(attn_only_top && l == l_hi)) {
-      // MLP and output projection, as in tower_bwd_range
-      CLIPFS_CHECK(bias_sum(dx_p, R, d, d, b.g_b_pr, nullptr, nullptr, bwork, st));
-      if (!saved_packed) CLIPFS_CHECK(clipfs_gather_rows_map(sv + SL.u, (size_t)4 * d, P.map, u_p, R, 4 * d, st));
-      CLIPFS_CHECK(gemm(cx, dx_p, b.w_pr_t, b.w_pr_t_p, du_p, R, 4 * d, d, nullptr, nullptr, 2, nullptr,
-                        saved_packed ? sv + SL.u : u_p, nullptr, nullptr, 0, 0, 0, 0.f, st));
-      CLIPFS_CHECK(bias_sum(du_p, R, 4 * d, 4 * d, b.g_b_fc, nullptr, nullptr, bwork, st));
-      CLIPFS_CHECK(gemm(cx, du_p, b.w_fc_t, b.w_fc_t_p, dh_p, R, d, 4 * d, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, 0,
-                        0, 0, 0.f, st));
-      CLIPFS_CHECK(bias_sum(dh_p, R, d, d, b.g_ln2_b, nullptr, nullptr, bwork, st));
-      if (saved_packed)
-        CLIPFS_CHECK(clipfs_layernorm_bwd(dh_p, sv + SL.x_mid, d, b.ln2_g, sv + SL.stat2, sv + SL.stat2 + srows, dx_p, dx_p, d,
-                                          R, d, st));
-      else
-        CLIPFS_CHECK(clipfs_layernorm_bwd_rows(dh_p, sv + SL.x_mid, d, b.ln2_g, sv + SL.stat2, sv + SL.stat2 + srows, P.map,
-                                               dx_p, dx_p, d, R, d, st));
-      CLIPFS_CHECK(bias_sum(dx_p, R, d, d, b.g_b_o, nullptr, nullptr, bwork, st));
-      CLIPFS_CHECK(gemm(cx, dx_p, b.w_o_t, b.w_o_t_p, datt_p, R, d, d, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, 0, 0,
-                        0, 0.f, st));
-      if (lora_o) {  // no dropout here (pack_dropout_ok): the adapter backward evaluates no mask
-        if (!saved_packed) {
-          CLIPFS_CHECK(clipfs_gather_rows_map(sv + SL.att, (size_t)d, P.map, att_p, R, d, st));
-          CLIPFS_CHECK(clipfs_gather_rows_map(sv + SL.t_o, (size_t)r, P.map, to_p, R, r, st));
-        }
-        CLIPFS_CHECK(lora_bwd_block(t, false, dx_p, nullptr, saved_packed ? sv + SL.att : att_p, saved_packed ? sv + SL.t_o : to_p,
-                                    b.lora_a_o, b.lora_b_o, dt, b.g_lora_a_o, b.g_lora_b_o, datt_p, R, 1, 1u, ds + 3, nullptr,
-                                    work, st, l));
-      }
+// The live-row forward reproduces the dense one bitwise (tower_fwd), which needs the dense launches to be unsplit too
+static bool pack_fwd_ok(const clipfs_tower* t, int batch, int R) {
+  if (!pack_ok(t, batch, R) || t->weight_format != 0) return false;  // exact fp32 only
+  const int M = batch * t->seq, d = t->width, r = t->lora_r;
+  for (int i = 0; i < kFwdGemms; ++i)  // split-K or stream-K at M?
+    if (clipfs_gemm_workspace_floats(M, kGemmShape[i][0] * d, kGemmShape[i][1] * d) != 0) return false;
+  // dropout on the packed rows: only the fused LayerNorm + down-projection draws its masks through the row map, and the
+  // blocks below grad_lo draw them too
+  if (r > 0 && t->lora_dropout > 0.f && t->dropout_seed != 0)
+    for (int l = 0; l < t->layers; ++l) {
+      const Adapters ad = adapters(t->blocks[l]);
+      if (ad.o) return false;
+      if (ad.qkv_mask && !clipfs_layernorm_fwd_lora_ok(d, r, 3)) return false;
     }
-    // attention (full-layout or packed q/k/v and O, lse; packed dO and dqkv) and the QKV projection
-    if (saved_packed)
-      CLIPFS_CHECK(clipfs_attention_bwd_packed_io(sv + SL.qkv, datt_p, sv + SL.att, sv + SL.lse, dqkv_p, P.off, batch, t->seq,
-                                                  t->heads, st));
-    else
-      CLIPFS_CHECK(clipfs_attention_bwd_packed(sv + SL.qkv, datt_p, sv + SL.att, sv + SL.lse, dqkv_p, P.off, batch, t->seq,
-                                               t->heads, st));
-    CLIPFS_CHECK(bias_sum(dqkv_p, R, 3 * d, d, b.g_b_q, b.g_b_k, b.g_b_v, bwork, st));
-    const bool need_dx = !(l == lo && stop_at_input) || b.g_prompt;  // as in tower_bwd_range
-    const bool need_dh = need_dx || b.g_ln1_b;
-    if (need_dh)
-      CLIPFS_CHECK(gemm(cx, dqkv_p, b.w_qkv_t, b.w_qkv_t_p, dh_p, R, d, 3 * d, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr,
-                        0, 0, 0, 0.f, st));
-    if (qkv_mask && (b.g_lora_a_qkv || need_dh)) {
-      const bool keep = keep_bits_saved(t);
-      if (!saved_packed) {
-        CLIPFS_CHECK(clipfs_gather_rows_map(sv + SL.h1, (size_t)d, P.map, h1_p, R, d, st));
-        CLIPFS_CHECK(clipfs_gather_rows_map(sv + SL.t_qkv, (size_t)3 * r, P.map, tq_p, R, 3 * r, st));
-        if (keep)  // uint16 per float4 of h1: d / 8 floats per row
-          CLIPFS_CHECK(clipfs_gather_rows_map(sv + SL.keep, (size_t)d / 8, P.map, keep_p, R, d / 8, st));
-      }
-      CLIPFS_CHECK(lora_bwd_block(t, false, dqkv_p, nullptr, saved_packed ? sv + SL.h1 : h1_p, saved_packed ? sv + SL.t_qkv : tq_p,
-                                  b.lora_a_qkv, b.lora_b_qkv, dt, b.g_lora_a_qkv, b.g_lora_b_qkv, need_dh ? dh_p : nullptr, R, 3,
-                                  qkv_mask, ds, keep ? (saved_packed ? (const void*)(sv + SL.keep) : (const void*)keep_p) : nullptr,
-                                  work, st, l));
-    }
-    CLIPFS_CHECK(bias_sum(dh_p, R, d, d, b.g_ln1_b, nullptr, nullptr, bwork, st));
-    if (need_dx) {
-      if (saved_packed)
-        CLIPFS_CHECK(clipfs_layernorm_bwd(dh_p, sv + SL.x_in, d, b.ln1_g, sv + SL.stat1, sv + SL.stat1 + srows, dx_p, dx_p, d, R,
-                                          d, st));
-      else
-        CLIPFS_CHECK(clipfs_layernorm_bwd_rows(dh_p, sv + SL.x_in, d, b.ln1_g, sv + SL.stat1, sv + SL.stat1 + srows, P.map,
-                                               dx_p, dx_p, d, R, d, st));
-      CLIPFS_CHECK(harvest_prompt(b, dx_p, nullptr, P.off, batch, t->seq, d, st));
-    }
-  }
-  if (stop_at_input) return CLIPFS_OK;
-  // the gradient wrt the tower input in the full layout: the dead rows are exact zeros
-  hipError_t e = hipMemsetAsync(dx, 0, (size_t)M * d * sizeof(float), st);
-  CLIPFS_REQUIRE(e == hipSuccess, "tower_bwd_packed: memset failed: %s", hipGetErrorString(e));
-  return clipfs_put_rows_map(dx_p, P.map, dx, (size_t)d, R, d, st);
+  return true;
 }
 
-// the last block's compact part, then (P != NULL) the packed or (P == NULL) the dense rows below it
-// (saved_packed: the saved tensors are clipfs_tower_fwd_packed's, P != NULL)
-static int tower_bwd_sparse_impl(const clipfs_tower* t, const float* dxs, const int32_t* rows, float* dx, int batch,
-                                 const float* saved, float* scratch, int stop_at_input, hipStream_t st, const PackPlan* P,
-                                 bool saved_packed = false) {
-  const int seq = t->seq, M = batch * seq, d = t->width, r = t->lora_r, Ms = batch;
-  const SavedLayout SL = saved_packed ? saved_layout_packed(t, (size_t)P->R, (size_t)batch) : saved_layout(t, (size_t)M);
-  const ScratchLayout SC = scratch_layout(t, (size_t)M);
-  CLIPFS_REQUIRE(!t->gemm_counters || t->gemm_counters_ints >= SC.counter_ints,
-                 "tower: gemm_counters holds %zu ints, %zu needed", t->gemm_counters_ints, SC.counter_ints);
-  const int l = t->layers - 1;
-  const clipfs_block& b = t->blocks[l];
-  if (!last_block_rows_ok(t)) {  // dense fall-back: the row gradients scattered into zeros
-    CLIPFS_CHECK(clipfs_scatter_rows(dxs, rows, dx, batch, seq, d, st));
-    return tower_bwd_range(t, dx, batch, saved, scratch, stop_at_input, st, l);
-  }
-  CLIPFS_REQUIRE(b.w_pr_t && b.w_fc_t && b.w_o_t && b.w_qkv_t, "tower_bwd: block %d lacks transposed weights", l);
-  const TowerCtx cx = make_ctx(t, scratch, SC);
-  const float* sv = saved + (size_t)(l - t->grad_lo) * SL.total;
-  // compact (one row per sequence) buffers live in the MLP scratch, which this block does not otherwise use:
-  // Ms (8 d + 4 d + 2) floats <= M 4 d for seq >= 3
-  float* u_s = scratch + SC.big;
-  float* du_s = u_s + (size_t)Ms * 4 * d;
-  float* xmid_s = du_s + (size_t)Ms * 4 * d;
-  float* dh_s = xmid_s + (size_t)Ms * d;
-  float* dxm_s = dh_s + (size_t)Ms * d;
-  float* datt_s = dxm_s + (size_t)Ms * d;
-  float* mean_s = datt_s + (size_t)Ms * d;
-  float* rstd_s = mean_s + al4((size_t)Ms);
-  float* bwork = scratch + SC.bwork;
-  // ---- MLP and output projection on the `batch` rows that carry gradient ----
-  // (their bias gradients are column sums over those rows: the other rows' gradients are exact zeros)
-  CLIPFS_CHECK(bias_sum(dxs, Ms, d, d, b.g_b_pr, nullptr, nullptr, bwork, st));
-  // fp16 storage mode: the `batch`-row products use the fp32 master weights (plane argument NULL); the saved pre-GELU
-  // activation is an f16 tensor there
-  const bool f16m = t->weight_format == 2;
-  if (saved_packed) {  // the compact forward put these rows at the packed EOT rows
-    CLIPFS_CHECK(clipfs_gather_rows_map(sv + SL.u, (size_t)4 * d, P->eotp, u_s, Ms, 4 * d, st));
-    CLIPFS_CHECK(clipfs_gather_rows_map(sv + SL.x_mid, (size_t)d, P->eotp, xmid_s, Ms, d, st));
-    CLIPFS_CHECK(clipfs_gather_rows_map(sv + SL.stat2, 1, P->eotp, mean_s, Ms, 1, st));
-    CLIPFS_CHECK(clipfs_gather_rows_map(sv + SL.stat2 + P->R, 1, P->eotp, rstd_s, Ms, 1, st));
-  } else {
-    if (f16m)
-      CLIPFS_CHECK(clipfs_gather_seq_rows_f16(sv + SL.u, (size_t)4 * d, rows, u_s, Ms, seq, 4 * d, st));
-    else
-      CLIPFS_CHECK(clipfs_gather_seq_rows(sv + SL.u, (size_t)4 * d, rows, u_s, Ms, seq, 4 * d, st));
-    CLIPFS_CHECK(clipfs_gather_seq_rows(sv + SL.x_mid, (size_t)d, rows, xmid_s, Ms, seq, d, st));
-    CLIPFS_CHECK(clipfs_gather_seq_rows(sv + SL.stat2, 1, rows, mean_s, Ms, seq, 1, st));
-    CLIPFS_CHECK(clipfs_gather_seq_rows(sv + SL.stat2 + M, 1, rows, rstd_s, Ms, seq, 1, st));
-  }
-  CLIPFS_CHECK(gemm(cx, dxs, b.w_pr_t, f16m ? nullptr : b.w_pr_t_p, du_s, Ms, 4 * d, d, nullptr, nullptr, 2, nullptr, u_s, nullptr, nullptr,
-                    0, 0, 0, 0.f, st));
-  CLIPFS_CHECK(bias_sum(du_s, Ms, 4 * d, 4 * d, b.g_b_fc, nullptr, nullptr, bwork, st));
-  CLIPFS_CHECK(gemm(cx, du_s, b.w_fc_t, f16m ? nullptr : b.w_fc_t_p, dh_s, Ms, d, 4 * d, nullptr, nullptr, 0, nullptr, nullptr, nullptr,
-                    nullptr, 0, 0, 0, 0.f, st));
-  CLIPFS_CHECK(bias_sum(dh_s, Ms, d, d, b.g_ln2_b, nullptr, nullptr, bwork, st));
-  CLIPFS_CHECK(clipfs_layernorm_bwd(dh_s, xmid_s, d, b.ln2_g, mean_s, rstd_s, dxs, dxm_s, d, Ms, d, st));
-  CLIPFS_CHECK(bias_sum(dxm_s, Ms, d, d, b.g_b_o, nullptr, nullptr, bwork, st));
-  CLIPFS_CHECK(gemm(cx, dxm_s, b.w_o_t, f16m ? nullptr : b.w_o_t_p, datt_s, Ms, d, d, nullptr, nullptr, 0, nullptr, nullptr, nullptr,
-                    nullptr, 0, 0, 0, 0.f, st));
-  if (P) {
-    // packed: datt_p and dx_p (the residual around the attention) are zero except at the EOT rows.  Put before the
-    // packed range gathers anything into the MLP scratch that holds datt_s / dxm_s.
-    float* datt_p = scratch + SC.b1;
-    const size_t Rd = (size_t)P->R * d;
-    hipError_t e = hipMemsetAsync(datt_p, 0, (al4(Rd) + Rd) * sizeof(float), st);
-    CLIPFS_REQUIRE(e == hipSuccess, "tower_bwd_packed: memset failed: %s", hipGetErrorString(e));
-    CLIPFS_CHECK(clipfs_put_rows_map(datt_s, P->eotp, datt_p, (size_t)d, Ms, d, st));
-    CLIPFS_CHECK(clipfs_put_rows_map(dxm_s, P->eotp, datt_p + al4(Rd), (size_t)d, Ms, d, st));
-    return tower_bwd_packed_range(t, dx, batch, *P, saved, scratch, stop_at_input, st, l, true, saved_packed);
-  }
-  // ---- attention and the QKV projection see every row again ----
-  float* dh = scratch + SC.h;
-  float* datt = scratch + SC.b1;
-  float* dqkv = scratch + SC.b3;
-  float* dt = scratch + SC.dt;
-  float* work = scratch + SC.work;
-  CLIPFS_CHECK(clipfs_scatter_rows(datt_s, rows, datt, batch, seq, d, st));
-  const unsigned qkv_mask = b.lora_a_qkv ? (b.lora_mask & 7u) : 0u;
-  const void* dqkv16_ready = nullptr;
-  void* dqkv16 = (f16_attention(t) && cx.a16) ? (void*)((char*)cx.a16 + (size_t)M * d * 2) : nullptr;  // [M, 3d] halves
-  const bool dy16 = dqkv16 && (!qkv_mask || clipfs_lora_bwd_f16dy_ok(d, d, r, 3));  // as in tower_bwd_range
-  if (f16_attention(t)) {
-    CLIPFS_CHECK(clipfs_attention_f16_bwd(sv + SL.qkv, qkv_f16(t), datt, 0, sv + SL.att, sv + SL.lse, dy16 ? nullptr : dqkv, dqkv16,
-                                          dh, batch, seq, t->heads, t->causal, st));
-    dqkv16_ready = dqkv16;
-  } else
-    CLIPFS_CHECK(clipfs_attention_bwd(sv + SL.qkv, datt, sv + SL.att, sv + SL.lse, dqkv, dh, batch, seq, t->heads, t->causal, st));
-  CLIPFS_CHECK(bias_sum(dqkv, M, 3 * d, d, b.g_b_q, b.g_b_k, b.g_b_v, bwork, st));
-  const uint32_t ds = t->dropout_stream0 + 4u * (uint32_t)l;
-  const bool need_dx = !(l == t->grad_lo && stop_at_input) || b.g_prompt;
-  const bool need_dh = need_dx || b.g_ln1_b;  // as in tower_bwd_range
-  if (need_dh)
-    CLIPFS_CHECK(gemm(cx, dqkv, b.w_qkv_t, b.w_qkv_t_p, dh, M, d, 3 * d, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, 0, 0,
-                      0, 0.f, st, CHAIN_NONE, dqkv16_ready));
-  if (qkv_mask)
-    CLIPFS_CHECK(lora_bwd_block(t, dy16, dqkv, dqkv16, sv + SL.h1, sv + SL.t_qkv, b.lora_a_qkv, b.lora_b_qkv, dt,
-                                b.g_lora_a_qkv, b.g_lora_b_qkv, need_dh ? dh : nullptr, M, 3, qkv_mask, ds,
-                                keep_bits_saved(t) ? (const void*)(sv + SL.keep) : nullptr, work, st, l));
-  CLIPFS_CHECK(bias_sum(dh, M, d, d, b.g_ln1_b, nullptr, nullptr, bwork, st));
-  if (!need_dx) return CLIPFS_OK;
-  CLIPFS_CHECK(clipfs_layernorm_bwd(dh, sv + SL.x_in, d, b.ln1_g, sv + SL.stat1, sv + SL.stat1 + M, nullptr, dx, d, M, d, st));
-  CLIPFS_CHECK(clipfs_add_seq_rows(dxm_s, rows, dx, batch, seq, d, st));  // the residual branch around the attention
-  CLIPFS_CHECK(harvest_prompt(b, dx, nullptr, nullptr, batch, seq, d, st));  // (the f16 image of dx is made below)
-  return tower_bwd_range(t, dx, batch, saved, scratch, stop_at_input, st, l - 1);
-}
-
-extern "C" int clipfs_tower_bwd_sparse(const clipfs_tower* t, const float* dxs, const int32_t* rows, float* dx, int batch,
-                                       const float* saved, float* scratch, int stop_at_input, void* stream) {
-  CLIPFS_CHECK(check_tower(t, batch));
-  CLIPFS_REQUIRE(t->grad_lo == 0 || stop_at_input,
-                 "tower_bwd_sparse: grad_lo %d > 0 needs stop_at_input (the input gradient runs through every block)",
-                 t->grad_lo);
-  CLIPFS_REQUIRE(dxs && rows && dx && saved && scratch, "tower_bwd_sparse: null buffer");
-  return tower_bwd_sparse_impl(t, dxs, rows, dx, batch, saved, scratch, stop_at_input, (hipStream_t)stream, nullptr);
+static bool mode_query_ok(const clipfs_tower* t, int batch) {
+  if (!t || !t->blocks || t->struct_size != sizeof(clipfs_tower) || t->block_size != sizeof(clipfs_block)) return false;
+  return batch > 0 && t->layers > 0 && t->seq > 0 && t->grad_lo >= 0 && t->grad_lo < t->layers;
 }
 
 extern "C" int clipfs_tower_pack_mode(const clipfs_tower* t, int batch, int R) {
-  if (!t || !t->blocks || t->struct_size != sizeof(clipfs_tower) || t->block_size != sizeof(clipfs_block)) return 0;
-  if (batch <= 0 || t->layers <= 0 || t->seq <= 0 || t->grad_lo < 0 || t->grad_lo >= t->layers) return 0;
-  return pack_ok(t, batch, R) ? 1 : 0;
+  return mode_query_ok(t, batch) && pack_ok(t, batch, R) ? 1 : 0;
+}
+
+extern "C" int clipfs_tower_pack_fwd_mode(const clipfs_tower* t, int batch, int R) {
+  return mode_query_ok(t, batch) && pack_fwd_ok(t, batch, R) ? 1 : 0;
 }
 
 extern "C" int clipfs_tower_bwd_packed(const clipfs_tower* t, const float* dxs, const int32_t* rows, const int32_t* plan,
                                        int R, float* dx, int batch, const float* saved, float* scratch, int stop_at_input,
                                        void* stream) {
-  CLIPFS_CHECK(check_tower(t, batch));
-  CLIPFS_REQUIRE(t->grad_lo == 0 || stop_at_input,
-                 "tower_bwd_packed: grad_lo %d > 0 needs stop_at_input (the input gradient runs through every block)",
-                 t->grad_lo);
-  CLIPFS_REQUIRE(dxs && rows && plan && dx && saved && scratch, "tower_bwd_packed: null buffer");
-  CLIPFS_REQUIRE(R >= batch && (size_t)R <= (size_t)batch * t->seq, "tower_bwd_packed: R %d outside [batch %d, batch*seq %zu]",
-                 R, batch, (size_t)batch * t->seq);
-  hipStream_t st = (hipStream_t)stream;
-  if (!pack_ok(t, batch, R))  // the dense rows (clipfs_tower_pack_mode says which)
-    return tower_bwd_sparse_impl(t, dxs, rows, dx, batch, saved, scratch, stop_at_input, st, nullptr);
-  const PackPlan P = {plan, plan + batch + 1, plan + 2 * (size_t)batch + 1, R};
-  return tower_bwd_sparse_impl(t, dxs, rows, dx, batch, saved, scratch, stop_at_input, st, &P);
-}
-
-// ---- packed (live-row) forward of a causal tower ---------------------------------------------------------------------
-// The same argument forward: row i of every block reads rows <= i of its caption only, and the head reads the EOT row,
-// so every block runs on the R live rows of the plan, packed caption after caption; the last block's compact part reads
-// its rows at the packed EOT rows (eotp).  Saved records hold R rows each (saved_layout_packed; the lse slot keeps its
-// [sequence * heads + head][seq] layout) and only clipfs_tower_bwd_packed_saved reads them.
-//
-// Every value of a live row equals the dense forward's bitwise: LayerNorm, the adapters and the GEMM epilogues are
-// row-wise, the attention masks a dead key exactly as the padding, the dropout masks are drawn at the full-layout row
-// (drow0 + map[i]), and each R-row GEMM is launched unsplit -- the K order of one output element depends on the split
-// factor only, never on the tile height -- which is why packing requires the dense launches to be unsplit too.
-static bool pack_fwd_ok(const clipfs_tower* t, int batch, int R) {
-  if (!pack_ok(t, batch, R) || t->weight_format != 0) return false;  // exact fp32 only
-  const int M = batch * t->seq, d = t->width, r = t->lora_r;
-  const int shapes[4][2] = {{3 * d, d}, {d, d}, {4 * d, d}, {d, 4 * d}};  // (N, K) of QKV, out-projection, c_fc, c_proj
-  for (int i = 0; i < 4; ++i)
-    if (clipfs_gemm_workspace_floats(M, shapes[i][0], shapes[i][1]) != 0) return false;  // split-K or stream-K at M
-  // dropout on the packed rows: only the fused LayerNorm + down-projection draws its masks through the row map, and the
-  // blocks below grad_lo draw them too
-  if (r > 0 && t->lora_dropout > 0.f && t->dropout_seed != 0)
-    for (int l = 0; l < t->layers; ++l) {
-      const clipfs_block& b = t->blocks[l];
-      if (b.lora_a_o && (b.lora_mask & 8u)) return false;
-      if (b.lora_a_qkv && (b.lora_mask & 7u) && !clipfs_layernorm_fwd_lora_ok(d, r, 3)) return false;
-    }
-  return true;
-}
-
-// Slots (R <= M / 2): the residual of the blocks that save nothing lives in b1's second half (x_p), their attention
-// output in its first half; h1 / qkv / t_qkv / t_o / the MLP as in tower_fwd_impl; the compact part in the MLP scratch.
-static int tower_fwd_packed_impl(const clipfs_tower* t, float* x, const int32_t* rows, const PackPlan& P, int batch,
-                                 float* saved, float* scratch, hipStream_t st) {
-  const int seq = t->seq, M = batch * seq, d = t->width, r = t->lora_r, R = P.R;
-  const size_t Rd = (size_t)R * d;
-  const SavedLayout SL = saved_layout_packed(t, (size_t)R, (size_t)batch);
-  const ScratchLayout SC = scratch_layout(t, (size_t)M);
-  CLIPFS_REQUIRE(!t->gemm_counters || t->gemm_counters_ints >= SC.counter_ints,
-                 "tower: gemm_counters holds %zu ints, %zu needed", t->gemm_counters_ints, SC.counter_ints);
-  const TowerCtx cx = make_ctx(t, scratch, SC);  // the compact part's `batch`-row products: as in tower_fwd_impl
-  TowerCtx cxp = cx;                             // the R-row products: unsplit (pack_fwd_ok)
-  cxp.ws = nullptr;
-  cxp.ws_floats = 0;
-  cxp.counters = nullptr;
-  cxp.counters_ints = 0;
-  const bool train = saved != nullptr;
-  const uint64_t seed = t->dropout_seed;
-  const int lo = t->grad_lo;
-  float* x_p = scratch + SC.b1 + al4(Rd);
-  // pack the input once (straight into the first saved record when every block saves)
-  CLIPFS_CHECK(clipfs_gather_rows_map(x, (size_t)d, P.map, train && lo == 0 ? saved + SL.x_in : x_p, R, d, st));
-  for (int l = 0; l < t->layers; ++l) {
-    const clipfs_block& b = t->blocks[l];
-    const bool keep_l = train && l >= lo;
-    if (train && l == lo && lo > 0) {
-      hipError_t e = hipMemcpyAsync(saved + SL.x_in, x_p, Rd * sizeof(float), hipMemcpyDeviceToDevice, st);
-      CLIPFS_REQUIRE(e == hipSuccess, "tower_fwd_packed: memcpy failed: %s", hipGetErrorString(e));
-    }
-    float* sv = keep_l ? saved + (size_t)(l - lo) * SL.total : nullptr;
-    const float* x_in = keep_l ? sv + SL.x_in : x_p;
-    float* h1 = keep_l ? sv + SL.h1 : scratch + SC.h;
-    float* qkv = keep_l ? sv + SL.qkv : scratch + SC.b3;
-    float* att = keep_l ? sv + SL.att : scratch + SC.b1;
-    float* x_mid = keep_l ? sv + SL.x_mid : x_p;
-    float* t_qkv = keep_l ? sv + SL.t_qkv : scratch + SC.dt;
-    float* t_o = keep_l ? sv + SL.t_o : scratch + SC.dt + al4((size_t)R * 3 * r);
-    float* x_next = keep_l && l + 1 < t->layers ? saved + (size_t)(l + 1 - lo) * SL.total + SL.x_in : x_p;
-    float* lse = keep_l ? sv + SL.lse : nullptr;  // the packed kernel is the same with or without statistics
-    const unsigned qkv_mask = b.lora_a_qkv ? (b.lora_mask & 7u) : 0u;
-    const bool lora_o = b.lora_a_o && (b.lora_mask & 8u);
-    const uint32_t ds = t->dropout_stream0 + 4u * (uint32_t)l;
-    float* mean1 = keep_l ? sv + SL.stat1 : nullptr;
-    float* rstd1 = keep_l ? sv + SL.stat1 + R : nullptr;
-    CLIPFS_CHECK(put_prompt(b, const_cast<float*>(x_in), P.off, batch, seq, d, st));
-    void* keep = (keep_l && qkv_mask && keep_bits_saved(t)) ? (void*)(sv + SL.keep) : nullptr;
-    if (qkv_mask && clipfs_layernorm_fwd_lora_ok(d, r, 3)) {
-      CLIPFS_CHECK(clipfs_layernorm_fwd_lora_map(x_in, d, b.ln1_g, b.ln1_b, h1, nullptr, mean1, rstd1, R, d, 1e-5f, b.lora_a_qkv,
-                                                 t_qkv, r, 3, qkv_mask, t->lora_dropout, seed, ds, t->dropout_row0, P.map, keep,
-                                                 st));
-    } else {
-      CLIPFS_CHECK(clipfs_layernorm_fwd(x_in, d, b.ln1_g, b.ln1_b, h1, mean1, rstd1, R, d, 1e-5f, st));
-      if (qkv_mask)  // no dropout here (pack_fwd_ok)
-        CLIPFS_CHECK(clipfs_lora_down(h1, b.lora_a_qkv, t_qkv, R, d, r, 3, qkv_mask, t->lora_dropout, seed, ds, t->dropout_row0,
-                                      keep, st));
-    }
-    CLIPFS_CHECK(gemm(cxp, h1, b.w_qkv, b.w_qkv_p, qkv, R, 3 * d, d, b.b_qkv, nullptr, 0, nullptr, nullptr,
-                      qkv_mask ? t_qkv : nullptr, b.lora_b_qkv, r, 3, d, t->lora_scale, st));
-    CLIPFS_CHECK(clipfs_attention_fwd_packed(qkv, att, lse, P.off, batch, seq, t->heads, st));
-    if (l == t->layers - 1) {
-      // ---- the rest of the last block on the EOT rows, as in tower_fwd_impl (rows read at eotp, saved rows put there)
-      const int Ms = batch;
-      float* att_s = scratch + SC.big;
-      float* xin_s = att_s + (size_t)Ms * d;
-      float* xmid_s = xin_s + (size_t)Ms * d;
-      float* h2_s = xmid_s + (size_t)Ms * d;
-      float* xout_s = h2_s + (size_t)Ms * d;
-      float* g_s = xout_s + (size_t)Ms * d;
-      float* u_s = g_s + (size_t)Ms * 4 * d;
-      float* mean_s = u_s + (size_t)Ms * 4 * d;
-      float* rstd_s = mean_s + al4((size_t)Ms);
-      CLIPFS_CHECK(clipfs_gather_rows_map(att, (size_t)d, P.eotp, att_s, Ms, d, st));
-      CLIPFS_CHECK(clipfs_gather_rows_map(x_in, (size_t)d, P.eotp, xin_s, Ms, d, st));
-      CLIPFS_CHECK(gemm(cx, att_s, b.w_o, b.w_o_p, xmid_s, Ms, d, d, b.b_o, xin_s, 0, nullptr, nullptr, nullptr, nullptr, 0, 0, 0,
-                        0.f, st));
-      CLIPFS_CHECK(clipfs_layernorm_fwd(xmid_s, d, b.ln2_g, b.ln2_b, h2_s, keep_l ? mean_s : nullptr, keep_l ? rstd_s : nullptr, Ms,
-                                        d, 1e-5f, st));
-      CLIPFS_CHECK(gemm(cx, h2_s, b.w_fc, b.w_fc_p, g_s, Ms, 4 * d, d, b.b_fc, nullptr, 1, keep_l ? u_s : nullptr, nullptr, nullptr,
-                        nullptr, 0, 0, 0, 0.f, st));
-      CLIPFS_CHECK(gemm(cx, g_s, b.w_pr, b.w_pr_p, xout_s, Ms, d, 4 * d, b.b_pr, xmid_s, 0, nullptr, nullptr, nullptr, nullptr, 0, 0,
-                        0, 0.f, st));
-      CLIPFS_CHECK(clipfs_put_seq_rows(xout_s, rows, x, (size_t)d, Ms, seq, d, st));
-      if (keep_l) {
-        CLIPFS_CHECK(clipfs_put_rows_map(xmid_s, P.eotp, sv + SL.x_mid, (size_t)d, Ms, d, st));
-        CLIPFS_CHECK(clipfs_put_rows_map(u_s, P.eotp, sv + SL.u, (size_t)4 * d, Ms, 4 * d, st));
-        CLIPFS_CHECK(clipfs_put_rows_map(mean_s, P.eotp, sv + SL.stat2, 1, Ms, 1, st));
-        CLIPFS_CHECK(clipfs_put_rows_map(rstd_s, P.eotp, sv + SL.stat2 + R, 1, Ms, 1, st));
-      }
-      break;
-    }
-    if (lora_o)  // no dropout here (pack_fwd_ok)
-      CLIPFS_CHECK(clipfs_lora_down(att, b.lora_a_o, t_o, R, d, r, 1, 1u, t->lora_dropout, seed, ds + 3, t->dropout_row0, nullptr,
-                                    st));
-    CLIPFS_CHECK(gemm(cxp, att, b.w_o, b.w_o_p, x_mid, R, d, d, b.b_o, x_in, 0, nullptr, nullptr, lora_o ? t_o : nullptr, b.lora_b_o,
-                      r, 1, d, t->lora_scale, st));
-    float* h2 = scratch + SC.h;
-    CLIPFS_CHECK(clipfs_layernorm_fwd(x_mid, d, b.ln2_g, b.ln2_b, h2, keep_l ? sv + SL.stat2 : nullptr,
-                                      keep_l ? sv + SL.stat2 + R : nullptr, R, d, 1e-5f, st));
-    float* gbuf = scratch + SC.big;
-    CLIPFS_CHECK(gemm(cxp, h2, b.w_fc, b.w_fc_p, gbuf, R, 4 * d, d, b.b_fc, nullptr, 1, keep_l ? sv + SL.u : nullptr, nullptr, nullptr,
-                      nullptr, 0, 0, 0, 0.f, st));
-    CLIPFS_CHECK(gemm(cxp, gbuf, b.w_pr, b.w_pr_p, x_next, R, d, 4 * d, b.b_pr, x_mid, 0, nullptr, nullptr, nullptr, nullptr, 0, 0, 0,
-                      0.f, st));
-  }
-  return CLIPFS_OK;
-}
-
-extern "C" int clipfs_tower_pack_fwd_mode(const clipfs_tower* t, int batch, int R) {
-  if (!t || !t->blocks || t->struct_size != sizeof(clipfs_tower) || t->block_size != sizeof(clipfs_block)) return 0;
-  if (batch <= 0 || t->layers <= 0 || t->seq <= 0 || t->grad_lo < 0 || t->grad_lo >= t->layers) return 0;
-  return pack_fwd_ok(t, batch, R) ? 1 : 0;
+  Pass p;
+  CLIPFS_CHECK(begin_pass(&p, "tower_bwd_packed", t, batch, dxs && rows && plan && dx && saved && scratch, &stop_at_input,
+                          plan, R, scratch, stream));
+  if (pack_ok(t, batch, R)) packed_rows(&p, false, false);  // else the dense rows (clipfs_tower_pack_mode says which)
+  return tower_bwd(p, dxs, rows, dx, saved, stop_at_input);
 }
 
 extern "C" int clipfs_tower_fwd_packed(const clipfs_tower* t, float* x, const int32_t* rows, const int32_t* plan, int R,
                                        int batch, float* saved, float* scratch, void* stream) {
-  CLIPFS_CHECK(check_tower(t, batch));
-  CLIPFS_REQUIRE(x && rows && plan && scratch, "tower_fwd_packed: null buffer");
-  CLIPFS_REQUIRE(R >= batch && (size_t)R <= (size_t)batch * t->seq, "tower_fwd_packed: R %d outside [batch %d, batch*seq %zu]",
-                 R, batch, (size_t)batch * t->seq);
-  if (!pack_fwd_ok(t, batch, R))  // the dense rows (clipfs_tower_pack_fwd_mode says which)
-    return tower_fwd_impl(t, x, last_block_rows_ok(t) ? rows : nullptr, batch, saved, scratch, stream);
-  const PackPlan P = {plan, plan + batch + 1, plan + 2 * (size_t)batch + 1, R};
-  return tower_fwd_packed_impl(t, x, rows, P, batch, saved, scratch, (hipStream_t)stream);
+  Pass p;
+  CLIPFS_CHECK(begin_pass(&p, "tower_fwd_packed", t, batch, x && rows && plan && scratch, nullptr, plan, R, scratch, stream));
+  if (pack_fwd_ok(t, batch, R)) {  // else the dense rows (clipfs_tower_pack_fwd_mode says which)
+    packed_rows(&p, true, true);
+    return tower_fwd(p, x, rows, saved);
+  }
+  return tower_fwd(p, x, last_block_rows_ok(t) ? rows : nullptr, saved);
 }
 
 extern "C" int clipfs_tower_bwd_packed_saved(const clipfs_tower* t, const float* dxs, const int32_t* rows, const int32_t* plan,
                                              int R, float* dx, int batch, const float* saved, float* scratch, int stop_at_input,
                                              void* stream) {
-  CLIPFS_CHECK(check_tower(t, batch));
-  CLIPFS_REQUIRE(t->grad_lo == 0 || stop_at_input,
-                 "tower_bwd_packed_saved: grad_lo %d > 0 needs stop_at_input (the input gradient runs through every block)",
-                 t->grad_lo);
-  CLIPFS_REQUIRE(dxs && rows && plan && dx && saved && scratch, "tower_bwd_packed_saved: null buffer");
-  CLIPFS_REQUIRE(R >= batch && (size_t)R <= (size_t)batch * t->seq,
-                 "tower_bwd_packed_saved: R %d outside [batch %d, batch*seq %zu]", R, batch, (size_t)batch * t->seq);
+  Pass p;
+  CLIPFS_CHECK(begin_pass(&p, "tower_bwd_packed_saved", t, batch, dxs && rows && plan && dx && saved && scratch,
+                          &stop_at_input, plan, R, scratch, stream));
   // the saved tensors must be clipfs_tower_fwd_packed's packed ones: no fall-back here
   CLIPFS_REQUIRE(pack_fwd_ok(t, batch, R), "tower_bwd_packed_saved: this geometry runs the dense forward (pack_fwd_mode 0)");
-  const PackPlan P = {plan, plan + batch + 1, plan + 2 * (size_t)batch + 1, R};
-  return tower_bwd_sparse_impl(t, dxs, rows, dx, batch, saved, scratch, stop_at_input, (hipStream_t)stream, &P, true);
+  packed_rows(&p, true, false);
+  return tower_bwd(p, dxs, rows, dx, saved, stop_at_input);
 }
