@@ -215,9 +215,14 @@ int clipfs_attention_fwd_packed(const float* qkv, float* out, float* lse, const 
                                 void* stream);
 int clipfs_attention_bwd_packed_io(const float* qkv, const float* dout, const float* out, const float* lse, float* dqkv,
                                    const int32_t* off, int batch, int seq, int heads, void* stream);
-/* fp16 storage mode (cfg-5), seq <= 288: the same function with both contractions on
+/* fp16 storage mode (cfg-5), seq <= clipfs_attention_f16_max_seq(): the same function with both contractions on
  * v_mfma_f32_32x32x16_f16 (operands rounded to f16 in the staging path; softmax statistics, accumulators and
- * outputs fp32).  lse as above (may be NULL when no backward follows). */
+ * outputs fp32).  lse as above (may be NULL when no backward follows).
+ * seq <= 288: one workgroup per (batch, head), the head's K / V (Q / dO) resident in LDS.  288 < seq <= max_seq (1024;
+ * ViT-L/14 at 336 px has 577 tokens): one workgroup per run of at most eight 32-token tiles of a head, the other side
+ * streamed through LDS in chunks of at most 288 tokens; every output element is written by one workgroup, so results are
+ * bitwise reproducible at every length.  A longer seq is refused before anything is launched. */
+int clipfs_attention_f16_max_seq(void);
 int clipfs_attention_f16_fwd(const void* qkv, int qkv_f16, float* out, void* out16, float* lse, int batch, int seq,
                              int heads, int causal, void* stream);
 /* dqkv from (qkv, dout, out, lse) of clipfs_attention_f16_fwd; work: batch*heads*seq floats (D_i = dO_i . O_i).

@@ -192,8 +192,14 @@ def attention_fwd(qkv, batch, seq, heads, causal, want_lse=False):
     return (out, lse) if want_lse else out
 
 
+def attention_f16_max_seq() -> int:
+    """Longest sequence the fp16-mode MFMA attention takes (a longer one is refused before anything is launched)."""
+    return _lib.load().clipfs_attention_f16_max_seq()
+
+
 def attention_f16_fwd(qkv, batch, seq, heads, causal=False):
-    """fp16-mode MFMA attention (seq <= 288): returns (out, lse)."""
+    """fp16-mode MFMA attention (seq <= attention_f16_max_seq(); K / V streamed through LDS past 288 tokens): returns
+    (out, lse)."""
     out = torch.empty(batch * seq, heads * 64, device=qkv.device, dtype=torch.float32)
     lse = torch.empty(batch * heads * seq, device=qkv.device, dtype=torch.float32)
     f16 = qkv.dtype == torch.float16
@@ -203,6 +209,7 @@ def attention_f16_fwd(qkv, batch, seq, heads, causal=False):
 
 
 def attention_f16_bwd(qkv, dout, out, lse, batch, seq, heads, causal=False):
+    """dqkv of attention_f16_fwd (same bound on seq); qkv and dout may each be fp32 or f16."""
     f16 = qkv.dtype == torch.float16
     dqkv = torch.empty(qkv.shape, device=qkv.device, dtype=torch.float32)
     work = torch.empty_like(lse)

@@ -402,9 +402,330 @@ __global__ __launch_bounds__(576) void attention_f16_bwd_kv_kernel(const TQ* __r
   }
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// Long sequences, AF_MAXL < L <= AF_LONG_MAXL (ViT-L/14 at 336 px: L = 577).  The same three passes with the same operand
+// rounding; what changes is that neither side of the product fits a workgroup any more:
+//   * own side: the sequence's 32-token tiles are cut into `parts` runs of blockDim / 64 tiles, one workgroup per
+//     (batch, head, run), blockIdx = (batch * H + head) * parts + run (the runs of one head are neighbours in dispatch order:
+//     they stream the same K / V through L2).  A wave owns ONE tile for the whole kernel, its state in registers
+//     (forward: O^T, m, l; dQ: dQ^T; dK/dV: dK^T, dV^T), and every output element is written by exactly one wave of
+//     one workgroup -- no atomics, no cross-workgroup sums, bitwise run-to-run results.
+//   * other side: passes through the LDS images in chunks of `ctok` <= AF_MAXL tokens (a multiple of 32; the host cuts
+//     the sequence into equal runs of tiles), staged by stage_head exactly as a whole head is in the short kernels.
+//     At ctok = 288 the images are those of the short kernels (forward 78 848 B, dQ 120 320 B, dK/dV 160 000 B); the host
+//     requests what the chunk needs, never more than the 160 KB of the short launches.
+// Barriers of the chunk loop: the __syncthreads() after staging orders the chunk's LDS writes before its reads (RAW);
+// the one in front of the next staging orders every wave's last read of the old chunk before it is overwritten (WAR).
+// Both are reached by every wave of the workgroup the same number of times: the chunk bounds depend on blockIdx alone,
+// and a wave with no tile (a short last run) or with nothing visible in a chunk (causal) only skips the tile loop.
+// Causal: a run stages key chunks up to its last query (forward / dQ) or query chunks from its first key (dK/dV) only.
+// ---------------------------------------------------------------------------------------------------------
+constexpr int AF_LONG_MAXL = 1024;
+constexpr int AF_LONG_WAVES = 8;  // tiles per run: 512 threads = 2 waves per SIMD, 256 registers each (dK/dV holds 144 live)
+
+template <typename TQ>
+__global__ __launch_bounds__(64 * AF_LONG_WAVES) void attention_f16_long_fwd_kernel(
+    const TQ* __restrict__ qkv, float* __restrict__ out, float* __restrict__ lse, int L, int H, int causal,
+    _Float16* __restrict__ out16, int parts, int ctok) {
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  _Float16* sK = reinterpret_cast<_Float16*>(smem_raw);  // [ctok][AF_ROW]
+  _Float16* sVt = sK + ctok * AF_ROW;                     // [64][chunk tokens + 4]
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int nw = (int)blockDim.x >> 6;
+  const int bh = blockIdx.x / parts, part = blockIdx.x - bh * parts;
+  const int b = bh / H, h = bh % H;
+  const int d = H * AF_HD;
+  const size_t ld = (size_t)3 * d;
+  const TQ* q0 = qkv + (size_t)b * L * ld + (size_t)h * AF_HD;
+  const int fr = lane & 31, fh = lane >> 5;
+  const float c = 0.125f * AF_LOG2E;  // scores in log2 units
+  const int qt = part * nw + wave;    // the wave's query tile
+  const int q_tok = qt * 32 + fr;
+  f16x8 qf[4];
+  load_own(q0, ld, qt * 32, L, lane, qf);
+  f32x16 o[2];
+#pragma unroll
+  for (int t = 0; t < 2; ++t)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) o[t][r] = 0.f;
+  float m = -INFINITY, l = 0.f;
+  const int kend = qt * 32 >= L ? 0 : causal ? min(L, qt * 32 + 32) : L;  // this wave's keys (none: no tile in a short run)
+  const int klim = causal ? q_tok : L - 1;                                // last visible key of this lane's query
+  const int kall = causal ? min(L, (part + 1) * nw * 32) : L;             // the run's keys
+  for (int c0 = 0; c0 < kall; c0 += ctok) {
+    const int Lc = min(ctok, kall - c0), Lpc = (Lc + 31) & ~31, TP = Lpc + 4;
+    if (c0) __syncthreads();
+    stage_head(q0 + d + (size_t)c0 * ld, ld, Lc, Lpc, sK, nullptr);
+    stage_head(q0 + 2 * d + (size_t)c0 * ld, ld, Lc, Lpc, nullptr, sVt);
+    __syncthreads();
+    const int kstop = min(Lc, kend - c0);
+    for (int k0 = 0; k0 < kstop; k0 += 32) {
+      f32x16 s = scores_T(sK, k0, lane, qf);
+      float mt = -INFINITY;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int key = c0 + k0 + (r & 3) + 8 * (r >> 2) + 4 * fh;
+        s[r] = (key < L && key <= klim) ? s[r] * c : -INFINITY;
+        mt = fmaxf(mt, s[r]);
+      }
+      mt = fmaxf(mt, xor32(mt));
+      const float mn = fmaxf(m, mt);
+      const float f = __builtin_amdgcn_exp2f(m - mn);
+      float ps = 0.f;
+      f16x8 pf[2];
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const float p = __builtin_amdgcn_exp2f(s[r] - mn);
+        ps += p;
+        pf[r >> 3][r & 7] = (_Float16)p;
+      }
+      l = l * f + ps;
+      m = mn;
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) o[t][r] *= f;
+#pragma unroll
+        for (int u = 0; u < 2; ++u)
+          o[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(load_T(sVt, TP, t, k0, u, lane), pf[u], o[t], 0, 0, 0);
+      }
+    }
+  }
+  l += xor32(l);
+  const float inv = 1.f / l;
+  if (q_tok < L) {
+    float* op = out + ((size_t)b * L + q_tok) * d + h * AF_HD + 4 * fh;
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+      for (int g4 = 0; g4 < 4; ++g4) {
+        f32x4 v;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[j] = o[t][4 * g4 + j] * inv;
+        *reinterpret_cast<f32x4*>(op + 32 * t + 8 * g4) = v;
+        if (out16)
+          *reinterpret_cast<f16x4*>(out16 + ((size_t)b * L + q_tok) * d + h * AF_HD + 4 * fh + 32 * t + 8 * g4) =
+              f16x4{(_Float16)v[0], (_Float16)v[1], (_Float16)v[2], (_Float16)v[3]};
+      }
+    if (lse && fh == 0) lse[((size_t)b * H + h) * L + q_tok] = (m + log2f(l)) * (1.f / AF_LOG2E);
+  }
+}
+
+// dQ (and D_i) of a long sequence: own side = the wave's query tile; K (both images) and V pass through LDS in key chunks.
+template <typename TQ, typename TG>
+__global__ __launch_bounds__(64 * AF_LONG_WAVES) void attention_f16_long_bwd_q_kernel(
+    const TQ* __restrict__ qkv, const TG* __restrict__ dout, const float* __restrict__ out, const float* __restrict__ lse,
+    float* __restrict__ dqkv, float* __restrict__ Dbuf, int L, int H, int causal, _Float16* __restrict__ dqkv16, int parts,
+    int ctok) {
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  _Float16* sK = reinterpret_cast<_Float16*>(smem_raw);  // [ctok][AF_ROW]
+  _Float16* sV = sK + ctok * AF_ROW;                      // [ctok][AF_ROW]
+  _Float16* sKt = sV + ctok * AF_ROW;                     // [64][chunk tokens + 4]
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int nw = (int)blockDim.x >> 6;
+  const int bh = blockIdx.x / parts, part = blockIdx.x - bh * parts;
+  const int b = bh / H, h = bh % H;
+  const int d = H * AF_HD;
+  const size_t ld = (size_t)3 * d;
+  const TQ* q0 = qkv + (size_t)b * L * ld + (size_t)h * AF_HD;
+  const int fr = lane & 31, fh = lane >> 5;
+  const float c = 0.125f * AF_LOG2E;
+  const int qt = part * nw + wave;
+  const int q_tok = qt * 32 + fr, q_cl = min(q_tok, L - 1);
+  f16x8 qf[4], gf[4];
+  load_own(q0, ld, qt * 32, L, lane, qf);
+  float Di = 0.f;
+  {
+    const TG* gp = dout + ((size_t)b * L + q_cl) * d + h * AF_HD + 8 * fh;
+    const float* op = out + ((size_t)b * L + q_cl) * d + h * AF_HD + 8 * fh;
+#pragma unroll
+    for (int sidx = 0; sidx < 4; ++sidx) {
+      f32x4 g0, g1;
+      if constexpr (sizeof(TG) == 2) {  // dO given as its f16 image (written by the output-projection dgrad GEMM)
+        gf[sidx] = *reinterpret_cast<const f16x8*>(gp + 16 * sidx);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          g0[j] = (float)gf[sidx][j];
+          g1[j] = (float)gf[sidx][4 + j];
+        }
+      } else {
+        g0 = *reinterpret_cast<const f32x4*>(gp + 16 * sidx);
+        g1 = *reinterpret_cast<const f32x4*>(gp + 16 * sidx + 4);
+        gf[sidx] = cvt8(g0, g1);
+      }
+      const f32x4 o0 = *reinterpret_cast<const f32x4*>(op + 16 * sidx), o1 = *reinterpret_cast<const f32x4*>(op + 16 * sidx + 4);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) Di += g0[j] * o0[j] + g1[j] * o1[j];
+    }
+    Di += xor32(Di);
+  }
+  const float lse2 = lse[((size_t)b * H + h) * L + q_cl] * AF_LOG2E;
+  if (q_tok < L && fh == 0) Dbuf[((size_t)b * H + h) * L + q_tok] = Di;
+  f32x16 acc[2];
+#pragma unroll
+  for (int t = 0; t < 2; ++t)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
+  const int kend = qt * 32 >= L ? 0 : causal ? min(L, qt * 32 + 32) : L;
+  const int klim = causal ? q_tok : L - 1;
+  const int kall = causal ? min(L, (part + 1) * nw * 32) : L;
+  for (int c0 = 0; c0 < kall; c0 += ctok) {
+    const int Lc = min(ctok, kall - c0), Lpc = (Lc + 31) & ~31, TP = Lpc + 4;
+    if (c0) __syncthreads();
+    stage_head(q0 + d + (size_t)c0 * ld, ld, Lc, Lpc, sK, sKt);
+    stage_head(q0 + 2 * d + (size_t)c0 * ld, ld, Lc, Lpc, sV, nullptr);
+    __syncthreads();
+    const int kstop = min(Lc, kend - c0);
+    for (int k0 = 0; k0 < kstop; k0 += 32) {
+      const f32x16 s = scores_T(sK, k0, lane, qf);
+      const f32x16 dp = scores_T(sV, k0, lane, gf);
+      f16x8 dsf[2];
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int key = c0 + k0 + (r & 3) + 8 * (r >> 2) + 4 * fh;
+        const float p = (key < L && key <= klim) ? __builtin_amdgcn_exp2f(s[r] * c - lse2) : 0.f;
+        dsf[r >> 3][r & 7] = (_Float16)(p * (dp[r] - Di) * 0.125f);
+      }
+#pragma unroll
+      for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int u = 0; u < 2; ++u)
+          acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(load_T(sKt, TP, t, k0, u, lane), dsf[u], acc[t], 0, 0, 0);
+    }
+  }
+  if (q_tok < L) {
+    float* op = dqkv + ((size_t)b * L + q_tok) * ld + h * AF_HD + 4 * fh;
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+      for (int g4 = 0; g4 < 4; ++g4) {
+        f32x4 v;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[j] = acc[t][4 * g4 + j];
+        if (dqkv) *reinterpret_cast<f32x4*>(op + 32 * t + 8 * g4) = v;
+        if (dqkv16)
+          *reinterpret_cast<f16x4*>(dqkv16 + ((size_t)b * L + q_tok) * ld + h * AF_HD + 4 * fh + 32 * t + 8 * g4) =
+              f16x4{(_Float16)v[0], (_Float16)v[1], (_Float16)v[2], (_Float16)v[3]};
+      }
+  }
+}
+
+// dK, dV of a long sequence: own side = the wave's key tile; Q and dO (both images each) with their lse and D values pass
+// through LDS in query chunks.
+template <typename TQ, typename TG>
+__global__ __launch_bounds__(64 * AF_LONG_WAVES) void attention_f16_long_bwd_kv_kernel(
+    const TQ* __restrict__ qkv, const TG* __restrict__ dout, const float* __restrict__ lse, const float* __restrict__ Dbuf,
+    float* __restrict__ dqkv, int L, int H, int causal, _Float16* __restrict__ dqkv16, int parts, int ctok) {
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  const int TPmax = ctok + 4;
+  _Float16* sQ = reinterpret_cast<_Float16*>(smem_raw);  // [ctok][AF_ROW]
+  _Float16* sG = sQ + ctok * AF_ROW;                      // [ctok][AF_ROW]
+  _Float16* sQt = sG + ctok * AF_ROW;                     // [64][chunk tokens + 4]
+  _Float16* sGt = sQt + 64 * TPmax;                       // [64][chunk tokens + 4]
+  float* sLse = reinterpret_cast<float*>(sGt + 64 * TPmax);  // [ctok] in log2 units
+  float* sD = sLse + ctok;
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int nw = (int)blockDim.x >> 6;
+  const int bh = blockIdx.x / parts, part = blockIdx.x - bh * parts;
+  const int b = bh / H, h = bh % H;
+  const int d = H * AF_HD;
+  const size_t ld = (size_t)3 * d;
+  const TQ* q0 = qkv + (size_t)b * L * ld + (size_t)h * AF_HD;
+  const TG* g0 = dout + (size_t)b * L * d + (size_t)h * AF_HD;
+  const int fr = lane & 31, fh = lane >> 5;
+  const float c = 0.125f * AF_LOG2E;
+  const int kt = part * nw + wave;  // the wave's key tile
+  const int k_tok = kt * 32 + fr;
+  f16x8 kf[4], vf[4];
+  load_own(q0 + d, ld, kt * 32, L, lane, kf);
+  load_own(q0 + 2 * d, ld, kt * 32, L, lane, vf);
+  f32x16 av[2], ak[2];
+#pragma unroll
+  for (int t = 0; t < 2; ++t)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      av[t][r] = 0.f;
+      ak[t][r] = 0.f;
+    }
+  const int ibeg = kt * 32 >= L ? L : causal ? kt * 32 : 0;  // this wave's queries: from the diagonal tile on (none: no tile)
+  const int iall = causal ? part * nw * 32 : 0;             // the run's queries
+  for (int c0 = iall; c0 < L; c0 += ctok) {
+    const int Lc = min(ctok, L - c0), Lpc = (Lc + 31) & ~31, TP = Lpc + 4;
+    if (c0 != iall) __syncthreads();
+    stage_head(q0 + (size_t)c0 * ld, ld, Lc, Lpc, sQ, sQt);
+    stage_head(g0 + (size_t)c0 * d, (size_t)d, Lc, Lpc, sG, sGt);
+    for (int i = threadIdx.x; i < Lpc; i += (int)blockDim.x) {
+      sLse[i] = i < Lc ? lse[((size_t)b * H + h) * L + c0 + i] * AF_LOG2E : 0.f;
+      sD[i] = i < Lc ? Dbuf[((size_t)b * H + h) * L + c0 + i] : 0.f;
+    }
+    __syncthreads();
+    for (int i0 = max(ibeg - c0, 0); i0 < Lc; i0 += 32) {
+      const f32x16 s = scores_T(sQ, i0, lane, kf);
+      const f32x16 dp = scores_T(sG, i0, lane, vf);
+      f16x8 pf[2], dsf[2];
+#pragma unroll
+      for (int g4 = 0; g4 < 4; ++g4) {
+        const f32x4 l4 = *reinterpret_cast<const f32x4*>(sLse + i0 + 8 * g4 + 4 * fh);
+        const f32x4 d4 = *reinterpret_cast<const f32x4*>(sD + i0 + 8 * g4 + 4 * fh);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const int r = 4 * g4 + j;
+          const int qi = c0 + i0 + 8 * g4 + 4 * fh + j;
+          const float p = (qi < L && (!causal || qi >= k_tok)) ? __builtin_amdgcn_exp2f(s[r] * c - l4[j]) : 0.f;
+          pf[r >> 3][r & 7] = (_Float16)p;
+          dsf[r >> 3][r & 7] = (_Float16)(p * (dp[r] - d4[j]) * 0.125f);
+        }
+      }
+#pragma unroll
+      for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+          av[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(load_T(sGt, TP, t, i0, u, lane), pf[u], av[t], 0, 0, 0);
+          ak[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(load_T(sQt, TP, t, i0, u, lane), dsf[u], ak[t], 0, 0, 0);
+        }
+    }
+  }
+  if (k_tok < L) {
+    float* kp = dqkv + ((size_t)b * L + k_tok) * ld + d + h * AF_HD + 4 * fh;
+    float* vp = kp + d;
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+      for (int g4 = 0; g4 < 4; ++g4) {
+        f32x4 k4, v4;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          k4[j] = ak[t][4 * g4 + j];
+          v4[j] = av[t][4 * g4 + j];
+        }
+        if (dqkv) {
+          *reinterpret_cast<f32x4*>(kp + 32 * t + 8 * g4) = k4;
+          *reinterpret_cast<f32x4*>(vp + 32 * t + 8 * g4) = v4;
+        }
+        if (dqkv16) {
+          _Float16* k16 = dqkv16 + ((size_t)b * L + k_tok) * ld + d + h * AF_HD + 4 * fh + 32 * t + 8 * g4;
+          *reinterpret_cast<f16x4*>(k16) = f16x4{(_Float16)k4[0], (_Float16)k4[1], (_Float16)k4[2], (_Float16)k4[3]};
+          *reinterpret_cast<f16x4*>(k16 + d) = f16x4{(_Float16)v4[0], (_Float16)v4[1], (_Float16)v4[2], (_Float16)v4[3]};
+        }
+      }
+  }
+}
+
 static size_t af_lds_bytes(int L, int images_rowmajor, int images_transposed) {
   const int Lp = (L + 31) & ~31;
   return ((size_t)images_rowmajor * Lp * AF_ROW + (size_t)images_transposed * 64 * (Lp + 4)) * sizeof(_Float16);
+}
+
+// the sequence's 32-token tiles cut into `parts` equal runs of `tiles` <= max_tiles (the last run may be shorter, never empty)
+struct AfRuns {
+  int parts, tiles;
+};
+static AfRuns af_runs(int seq, int max_tiles) {
+  const int tiles = (seq + 31) / 32, parts = (tiles + max_tiles - 1) / max_tiles;
+  return {parts, (tiles + parts - 1) / parts};
 }
 
 }  // namespace clipfs
@@ -413,9 +734,14 @@ using namespace clipfs;
 
 static int check_af(const void* a, const void* b, int batch, int seq, int heads) {
   CLIPFS_REQUIRE(a && b, "attention_f16: null pointer");
-  CLIPFS_REQUIRE(batch > 0 && heads > 0 && seq > 0 && seq <= AF_MAXL, "attention_f16: seq %d outside 1..%d", seq, AF_MAXL);
+  CLIPFS_REQUIRE(batch > 0 && heads > 0 && seq > 0 && seq <= AF_LONG_MAXL, "attention_f16: seq %d outside 1..%d", seq,
+                 AF_LONG_MAXL);
+  CLIPFS_REQUIRE(seq <= AF_MAXL || (long long)batch * heads * af_runs(seq, AF_LONG_WAVES).parts <= 0x7fffffffLL,
+                 "attention_f16: batch %d x heads %d too large for seq %d", batch, heads, seq);
   return CLIPFS_OK;
 }
+
+extern "C" int clipfs_attention_f16_max_seq(void) { return AF_LONG_MAXL; }
 
 static int af_threads(int seq, int max_waves) {
   const int tiles = (seq + 31) / 32;
@@ -428,6 +754,8 @@ static void af_set_attrs() {
   if (done) return;
   (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attention_f16_fwd_kernel<TQ>),
                             hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attention_f16_long_fwd_kernel<TQ>),
+                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
   done = true;
 }
 
@@ -435,6 +763,13 @@ template <typename TQ>
 static int af_fwd(const void* qkv, float* out, void* out16, float* lse, int batch, int seq, int heads, int causal,
                   hipStream_t st) {
   af_set_attrs<TQ>();
+  if (seq > AF_MAXL) {  // one workgroup per run of query tiles; K / V in chunks of `kc.tiles` tiles
+    const AfRuns own = af_runs(seq, AF_LONG_WAVES), kc = af_runs(seq, AF_MAXL / 32);
+    hipLaunchKernelGGL(attention_f16_long_fwd_kernel<TQ>, dim3(batch * heads * own.parts), dim3(64 * own.tiles),
+                       af_lds_bytes(32 * kc.tiles, 1, 1), st, reinterpret_cast<const TQ*>(qkv), out, lse, seq, heads, causal,
+                       reinterpret_cast<_Float16*>(out16), own.parts, 32 * kc.tiles);
+    return launch_status();
+  }
   hipLaunchKernelGGL(attention_f16_fwd_kernel<TQ>, dim3(batch * heads), dim3(af_threads(seq, 5)), af_lds_bytes(seq, 1, 1), st,
                      reinterpret_cast<const TQ*>(qkv), out, lse, seq, heads, causal, reinterpret_cast<_Float16*>(out16));
   return launch_status();
@@ -452,7 +787,25 @@ static int af_bwd(const void* qkv, const void* dout, const float* out, const flo
                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attention_f16_bwd_kv_kernel<TQ, TG>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attention_f16_long_bwd_q_kernel<TQ, TG>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attention_f16_long_bwd_kv_kernel<TQ, TG>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     attr = true;
+  }
+  if (seq > AF_MAXL) {  // one workgroup per run of own tiles (dQ: queries, dK/dV: keys); the other side in chunks
+    const AfRuns own = af_runs(seq, AF_LONG_WAVES), oc = af_runs(seq, AF_MAXL / 32);
+    const int ctok = 32 * oc.tiles;
+    const dim3 grid(batch * heads * own.parts), block(64 * own.tiles);
+    hipLaunchKernelGGL((attention_f16_long_bwd_q_kernel<TQ, TG>), grid, block, af_lds_bytes(ctok, 2, 1), st,
+                       reinterpret_cast<const TQ*>(qkv), reinterpret_cast<const TG*>(dout), out, lse, dqkv, work, seq, heads,
+                       causal, reinterpret_cast<_Float16*>(dqkv16), own.parts, ctok);
+    CLIPFS_CHECK(launch_status());
+    hipLaunchKernelGGL((attention_f16_long_bwd_kv_kernel<TQ, TG>), grid, block,
+                       af_lds_bytes(ctok, 2, 2) + 2 * (size_t)ctok * sizeof(float), st, reinterpret_cast<const TQ*>(qkv),
+                       reinterpret_cast<const TG*>(dout), lse, work, dqkv, seq, heads, causal,
+                       reinterpret_cast<_Float16*>(dqkv16), own.parts, ctok);
+    return launch_status();
   }
   hipLaunchKernelGGL((attention_f16_bwd_q_kernel<TQ, TG>), dim3(batch * heads), dim3(threads), lds_q, st,
                      reinterpret_cast<const TQ*>(qkv), reinterpret_cast<const TG*>(dout), out, lse, dqkv, work, seq, heads, causal,

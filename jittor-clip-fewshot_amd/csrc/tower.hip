@@ -21,8 +21,10 @@ namespace clipfs {
 
 static inline size_t al4(size_t n) { return (n + 3) & ~(size_t)3; }
 
-// fp16 storage mode runs attention on the f16 MFMA kernels (attention_f16.hip; sequences up to 288 tokens)
-static inline bool f16_attention(const clipfs_tower* t) { return t->weight_format == 2 && t->seq <= 288; }
+// fp16 storage mode runs attention on the f16 MFMA kernels (attention_f16.hip; sequences up to its bound, 1024 tokens)
+static inline bool f16_attention(const clipfs_tower* t) {
+  return t->weight_format == 2 && t->seq <= clipfs_attention_f16_max_seq();
+}
 // ... and then qkv itself is stored as f16 (written by the QKV GEMM, read by the attention kernels): needs the
 // f16 x f16 GEMM for the LoRA'd projection, i.e. a segment width that is a multiple of its 128-column tiles
 static inline bool qkv_f16(const clipfs_tower* t) {
