@@ -399,6 +399,51 @@ int clipfs_kl_logits(const float* logits, const float* target_logits, float* los
 int clipfs_adamw(float* p, const float* g, float* m, float* v, size_t n, int step, float lr, float beta1,
                  float beta2, float eps, float weight_decay, float grad_scale, void* stream);
 
+/* ---------------------------------------------------------- loss scaling --
+ * For the fp16 storage mode, whose backward keeps every activation gradient as an f16 image (anything below 3e-8
+ * becomes zero there): the logits gradient is multiplied by a scale S, the whole backward (linear in it) carries S, and
+ * the optimiser divides it out again.  All of it is driven by a device-resident SCALER RECORD owned by the caller:
+ * CLIPFS_SCALER_WORDS 32-bit words (64 bytes, 16-byte aligned), fp32 or int32 as listed, which no entry point reads
+ * back to the host.  The caller initialises SCALE (> 0, a power of two keeps the scaling exact), INV_SCALE = 1 / SCALE
+ * and zeroes the rest.
+ *
+ * One optimiser step is three launches on the caller's stream, in this order (after any gradient all-reduce, so that
+ * every data-parallel rank sees the same buffer and takes the same decision):
+ *   clipfs_grads_nonfinite  one pass over the flat gradient buffer [n] (any 4-byte aligned base: 16-byte loads between
+ *                           the first and the last 16-byte boundary, scalar loads for the up to 3 floats on either
+ *                           side); sets FOUND when an entry is NaN or +-inf.  Finite values of any magnitude
+ *                           (FLT_MAX, subnormals) do not.
+ *   clipfs_scaler_decide    one thread.  FOUND clear: STEP += 1; INV_SQRT_BC2 = 1 / sqrt(1 - beta2^STEP) and
+ *                           STEP_SIZE = lr / (1 - beta1^STEP), evaluated in double like clipfs_adamw does on the host;
+ *                           SKIP = 0; TRACKER += 1, and when growth_interval > 0 and TRACKER reaches it, SCALE *=
+ *                           growth_factor (unless that overflows) and TRACKER = 0.  FOUND set: SKIPPED += 1; SKIP = 1;
+ *                           SCALE *= backoff_factor; TRACKER = 0; STEP is left alone.  Either way INV_SCALE = 1 / the
+ *                           scale this step's gradients carry, and FOUND = 0 for the next step.
+ *                           growth_interval = 0 with backoff_factor = 1 is a static scale (it still skips).
+ *                           growth_factor >= 1, 0 < backoff_factor <= 1, growth_interval >= 0.
+ *   clipfs_adamw_scaled     clipfs_adamw's arithmetic with grad_scale = INV_SCALE and the two bias-correction floats
+ *                           of the record; with SKIP set it writes nothing (p, m, v bitwise unchanged, no weight decay).
+ * clipfs_cross_entropy_scaled is clipfs_cross_entropy with the gradient scale grad_scale * SCALE; loss_sum and correct
+ * are unscaled.  Each of the four is CLIPFS_EINVAL (nothing launched) for a NULL or misaligned record or buffer or n = 0. */
+#define CLIPFS_SCALER_SCALE 0        /* fp32: the scale the next cross entropy applies */
+#define CLIPFS_SCALER_INV_SCALE 1    /* fp32: 1 / the scale of the step last decided */
+#define CLIPFS_SCALER_FOUND 2        /* int32: a non-finite gradient entry was seen since the last decision */
+#define CLIPFS_SCALER_TRACKER 3      /* int32: consecutive clean steps since the scale last changed */
+#define CLIPFS_SCALER_STEP 4         /* int32: optimiser steps applied (skipped steps not counted) */
+#define CLIPFS_SCALER_SKIPPED 5      /* int32: steps skipped */
+#define CLIPFS_SCALER_INV_SQRT_BC2 6 /* fp32 */
+#define CLIPFS_SCALER_STEP_SIZE 7    /* fp32 */
+#define CLIPFS_SCALER_SKIP 8         /* int32: the step last decided is skipped */
+#define CLIPFS_SCALER_WORDS 16       /* words 9 .. 15 are reserved (zero) */
+int clipfs_cross_entropy_scaled(const float* logits, const int64_t* target, float* dlogits, float* loss_rows,
+                                float* loss_sum, int32_t* correct, int rows, int classes, float grad_scale,
+                                const float* scaler_state, void* stream);
+int clipfs_grads_nonfinite(const float* g, size_t n, float* scaler_state, void* stream);
+int clipfs_scaler_decide(float* scaler_state, float lr, float beta1, float beta2, float growth_factor,
+                         float backoff_factor, int growth_interval, void* stream);
+int clipfs_adamw_scaled(float* p, const float* g, float* m, float* v, size_t n, float lr, float beta1, float beta2,
+                        float eps, float weight_decay, const float* scaler_state, void* stream);
+
 /* -------------------------------------------------------------------- MTA --
  * solve_mta (lora_train_vlp.py:742-811; slow_pace.py:1363-1433), one workgroup per image.
  * feats [n_img, V, d] unit rows (row 0 = centre view), text [C, d] (unit rows; the reference

@@ -134,6 +134,10 @@ SIGNATURES = {
     "clipfs_l1_loss": (_i, [_p, _p, _sz, _p, _p, _f, _p]),
     "clipfs_kl_logits": (_i, [_p, _p, _p, _p, _i, _i, _f, _p]),
     "clipfs_adamw": (_i, [_p, _p, _p, _p, _sz, _i, _f, _f, _f, _f, _f, _f, _p]),
+    "clipfs_cross_entropy_scaled": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _f, _p, _p]),
+    "clipfs_grads_nonfinite": (_i, [_p, _sz, _p, _p]),
+    "clipfs_scaler_decide": (_i, [_p, _f, _f, _f, _f, _f, _i, _p]),
+    "clipfs_adamw_scaled": (_i, [_p, _p, _p, _p, _sz, _f, _f, _f, _f, _f, _p, _p]),
     "clipfs_mta_work_floats": (_sz, [_i, _i, _i, _i]),
     "clipfs_mta": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _p]),
     "clipfs_tta_views": (_i, [_p, _i, _i, _p, _i, _i, _p, _p, _p, _p]),
@@ -170,6 +174,11 @@ SIGNATURES = {
     "clipfs_tower_fwd_packed": (_i, [C.POINTER(Tower), _p, _p, _p, _i, _i, _p, _p, _p]),
     "clipfs_tower_bwd_packed_saved": (_i, [C.POINTER(Tower), _p, _p, _p, _i, _p, _i, _p, _p, _i, _p]),
 }
+
+# word indices of the loss-scaling record (CLIPFS_SCALER_* of include/clipfs.h)
+SCALER_SCALE, SCALER_INV_SCALE, SCALER_FOUND, SCALER_TRACKER, SCALER_STEP, SCALER_SKIPPED = 0, 1, 2, 3, 4, 5
+SCALER_INV_SQRT_BC2, SCALER_STEP_SIZE, SCALER_SKIP, SCALER_WORDS = 6, 7, 8, 16
+
 
 def new_gemm_args() -> GemmArgs:
     g = GemmArgs()

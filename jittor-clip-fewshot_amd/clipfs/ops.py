@@ -354,16 +354,22 @@ def class_mean_bwd(emb, dout, classes, templates):
     return demb
 
 
-def cross_entropy(logits, target, want_grad=True, grad_scale=1.0):
-    """returns (loss_sum [1], dlogits or None, correct [1] int32)"""
+def cross_entropy(logits, target, want_grad=True, grad_scale=1.0, scale_state=None):
+    """returns (loss_sum [1], dlogits or None, correct [1] int32).  ``scale_state`` (a loss-scaling record,
+    ``new_scaler_state``): dlogits additionally carries the record's current scale; the loss and the hit count do not."""
     rows, classes = logits.shape
     assert target.dtype == torch.int64
     dl = torch.empty_like(logits) if want_grad else None
     loss_rows = torch.empty(2 * rows, device=logits.device, dtype=torch.float32)
     loss_sum = torch.empty(1, device=logits.device, dtype=torch.float32)
     correct = torch.empty(1, device=logits.device, dtype=torch.int32)
-    check(_lib.load().clipfs_cross_entropy(_p(_f32(logits)), _p(target), _p(dl), _p(loss_rows), _p(loss_sum),
-                                           _p(correct), rows, classes, grad_scale, _stream()), "cross_entropy")
+    if scale_state is None:
+        check(_lib.load().clipfs_cross_entropy(_p(_f32(logits)), _p(target), _p(dl), _p(loss_rows), _p(loss_sum),
+                                               _p(correct), rows, classes, grad_scale, _stream()), "cross_entropy")
+    else:
+        check(_lib.load().clipfs_cross_entropy_scaled(_p(_f32(logits)), _p(target), _p(dl), _p(loss_rows), _p(loss_sum),
+                                                      _p(correct), rows, classes, grad_scale, _p(_scaler(scale_state)),
+                                                      _stream()), "cross_entropy_scaled")
     return loss_sum, dl, correct
 
 
@@ -426,6 +432,41 @@ def bias_grad(x, out, seg_width: int = 0, rows: Optional[int] = None, work: Opti
 def adamw(p, g, m, v, step, lr=2e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, grad_scale=1.0):
     check(_lib.load().clipfs_adamw(_p(p), _p(g), _p(m), _p(v), p.numel(), step, lr, betas[0], betas[1], eps,
                                    weight_decay, grad_scale, _stream()), "adamw")
+
+
+def new_scaler_state(scale: float, device) -> torch.Tensor:
+    """A loss-scaling record (include/clipfs.h, CLIPFS_SCALER_*): fp32 [16] on ``device`` with SCALE = ``scale``,
+    INV_SCALE = 1 / scale and everything else zero.  The int32 words are read through ``state.view(torch.int32)``."""
+    st = torch.zeros(_lib.SCALER_WORDS, dtype=torch.float32)
+    st[_lib.SCALER_SCALE] = scale
+    st[_lib.SCALER_INV_SCALE] = 1.0 / scale
+    return st.to(device)
+
+
+def _scaler(state: torch.Tensor) -> torch.Tensor:
+    assert state.is_cuda and state.dtype == torch.float32 and state.is_contiguous() and state.numel() >= _lib.SCALER_WORDS
+    return state
+
+
+def grads_nonfinite(g: torch.Tensor, scale_state: torch.Tensor) -> None:
+    """Set the record's flag when the flat fp32 buffer ``g`` (any 4-byte aligned slice) holds NaN or +-inf."""
+    assert g.dim() == 1
+    check(_lib.load().clipfs_grads_nonfinite(_p(_f32(g)), g.numel(), _p(_scaler(scale_state)), _stream()), "grads_nonfinite")
+
+
+def scaler_decide(scale_state: torch.Tensor, lr=2e-4, betas=(0.9, 0.999), growth_factor=2.0, backoff_factor=0.5,
+                  growth_interval=2000) -> None:
+    """Turn the flag into the step's decision (apply / skip), the step's AdamW bias corrections and the next scale.
+    ``growth_interval=0`` with ``backoff_factor=1.0`` keeps the scale static."""
+    check(_lib.load().clipfs_scaler_decide(_p(_scaler(scale_state)), lr, betas[0], betas[1], growth_factor, backoff_factor,
+                                           growth_interval, _stream()), "scaler_decide")
+
+
+def adamw_scaled(p, g, m, v, scale_state, lr=2e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2):
+    """``adamw`` with the step number's bias corrections, 1 / scale as the gradient scale and the skip decision taken
+    from the record (after ``scaler_decide``)."""
+    check(_lib.load().clipfs_adamw_scaled(_p(p), _p(g), _p(m), _p(v), p.numel(), lr, betas[0], betas[1], eps,
+                                          weight_decay, _p(_scaler(scale_state)), _stream()), "adamw_scaled")
 
 
 def mta(feats, text, want_mode=True, want_logits=True):

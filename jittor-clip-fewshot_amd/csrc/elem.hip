@@ -291,11 +291,11 @@ __global__ __launch_bounds__(64) void class_mean_bwd_kernel(const float* __restr
 }
 
 // ---- softmax cross entropy, one wave per row (lora_train_vlp.py:997) ----
-__global__ __launch_bounds__(256) void cross_entropy_kernel(const float* __restrict__ logits,
-                                                            const int64_t* __restrict__ target,
-                                                            float* __restrict__ dlogits, float* __restrict__ loss_rows,
-                                                            int32_t* __restrict__ correct_rows, int rows, int classes,
-                                                            float grad_scale) {
+__device__ __forceinline__ void cross_entropy_rows(const float* __restrict__ logits,
+                                                   const int64_t* __restrict__ target,
+                                                   float* __restrict__ dlogits, float* __restrict__ loss_rows,
+                                                   int32_t* __restrict__ correct_rows, int rows, int classes,
+                                                   float grad_scale) {
   const int lane = threadIdx.x & 63;
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= rows) return;
@@ -335,6 +335,25 @@ __global__ __launch_bounds__(256) void cross_entropy_kernel(const float* __restr
       dlogits[(size_t)row * classes + k] = gk;
     }
   }
+}
+__global__ __launch_bounds__(256) void cross_entropy_kernel(const float* __restrict__ logits,
+                                                            const int64_t* __restrict__ target,
+                                                            float* __restrict__ dlogits, float* __restrict__ loss_rows,
+                                                            int32_t* __restrict__ correct_rows, int rows, int classes,
+                                                            float grad_scale) {
+  cross_entropy_rows(logits, target, dlogits, loss_rows, correct_rows, rows, classes, grad_scale);
+}
+// the same with the loss scale of a scaler record (clipfs.h: "loss scaling") folded into the gradient scale; the
+// per-row losses and hit flags are those of the plain kernel
+__global__ __launch_bounds__(256) void cross_entropy_scaled_kernel(const float* __restrict__ logits,
+                                                                   const int64_t* __restrict__ target,
+                                                                   float* __restrict__ dlogits,
+                                                                   float* __restrict__ loss_rows,
+                                                                   int32_t* __restrict__ correct_rows, int rows,
+                                                                   int classes, float grad_scale,
+                                                                   const float* __restrict__ state) {
+  cross_entropy_rows(logits, target, dlogits, loss_rows, correct_rows, rows, classes,
+                     grad_scale * state[CLIPFS_SCALER_SCALE]);
 }
 
 // deterministic final reduction of the per-row losses / hit flags (single wave, fixed order)
@@ -512,12 +531,10 @@ __global__ __launch_bounds__(256) void colsum_kernel(const float* __restrict__ x
 }
 
 // ---- AdamW over the flat trainable buffer (lora_train_vlp.py:946,1002) ----
-__global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
-                                                    float* __restrict__ m, float* __restrict__ v, size_t n, float lr,
-                                                    float b1, float b2, float eps, float wd, float inv_sqrt_bc2,
-                                                    float step_size, float grad_scale) {
-  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
+__device__ __forceinline__ void adamw_element(float* __restrict__ p, const float* __restrict__ g,
+                                              float* __restrict__ m, float* __restrict__ v, size_t i, float lr,
+                                              float b1, float b2, float eps, float wd, float inv_sqrt_bc2,
+                                              float step_size, float grad_scale) {
   const float gi = g[i] * grad_scale;
   float pi = p[i] * (1.f - lr * wd);
   const float mi = b1 * m[i] + (1.f - b1) * gi;
@@ -527,6 +544,79 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const
   p[i] = pi;
   m[i] = mi;
   v[i] = vi;
+}
+__global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                    float* __restrict__ m, float* __restrict__ v, size_t n, float lr,
+                                                    float b1, float b2, float eps, float wd, float inv_sqrt_bc2,
+                                                    float step_size, float grad_scale) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  adamw_element(p, g, m, v, i, lr, b1, b2, eps, wd, inv_sqrt_bc2, step_size, grad_scale);
+}
+
+// ---- loss scaling for f16 gradient storage: the scaler record is CLIPFS_SCALER_WORDS 32-bit words (clipfs.h) ----
+// One pass over the flat gradient buffer: a lane that meets NaN or +-inf (exponent field all ones) stores 1 to the
+// record's flag.  Every writer stores the same value: no atomics.  Up to 3 floats before the first 16-byte boundary
+// and up to 3 after the last whole float4 are read one by one by the first threads of block 0.
+__global__ __launch_bounds__(256) void grads_nonfinite_kernel(const float* __restrict__ g, size_t n, unsigned head,
+                                                              int32_t* __restrict__ state) {
+  const size_t nvec = (n - head) >> 2;
+  const unsigned tail = (unsigned)((n - head) & 3);
+  const uint4* gv = reinterpret_cast<const uint4*>(g + head);
+  unsigned bad = 0;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < nvec; i += (size_t)gridDim.x * 256) {
+    const uint4 w = gv[i];
+    bad |= (unsigned)((w.x & 0x7f800000u) == 0x7f800000u) | (unsigned)((w.y & 0x7f800000u) == 0x7f800000u) |
+           (unsigned)((w.z & 0x7f800000u) == 0x7f800000u) | (unsigned)((w.w & 0x7f800000u) == 0x7f800000u);
+  }
+  if (blockIdx.x == 0 && threadIdx.x < head + tail) {
+    const size_t i = threadIdx.x < head ? (size_t)threadIdx.x : (size_t)head + 4 * nvec + (threadIdx.x - head);
+    bad |= (unsigned)((__float_as_uint(g[i]) & 0x7f800000u) == 0x7f800000u);
+  }
+  if (bad) state[CLIPFS_SCALER_FOUND] = 1;
+}
+
+// One thread: turn the flag into this step's decision and the next step's scale.
+__global__ __launch_bounds__(64) void scaler_decide_kernel(float* __restrict__ sf, float lr, float b1, float b2,
+                                                           float growth_factor, float backoff_factor,
+                                                           int growth_interval) {
+  if (threadIdx.x != 0) return;
+  int32_t* si = reinterpret_cast<int32_t*>(sf);
+  const float scale = sf[CLIPFS_SCALER_SCALE];
+  sf[CLIPFS_SCALER_INV_SCALE] = 1.f / scale;  // of the scale THIS step's gradients carry
+  if (si[CLIPFS_SCALER_FOUND] == 0) {
+    const int step = si[CLIPFS_SCALER_STEP] + 1;
+    si[CLIPFS_SCALER_STEP] = step;
+    const double bc1 = 1.0 - pow((double)b1, (double)step);
+    const double bc2 = 1.0 - pow((double)b2, (double)step);
+    sf[CLIPFS_SCALER_INV_SQRT_BC2] = (float)(1.0 / sqrt(bc2));
+    sf[CLIPFS_SCALER_STEP_SIZE] = (float)((double)lr / bc1);
+    si[CLIPFS_SCALER_SKIP] = 0;
+    int tracker = si[CLIPFS_SCALER_TRACKER] + 1;
+    if (growth_interval > 0 && tracker >= growth_interval) {
+      const float grown = scale * growth_factor;
+      if (grown <= 3.402823466e38f) sf[CLIPFS_SCALER_SCALE] = grown;  // a scale that would overflow stays
+      tracker = 0;
+    }
+    si[CLIPFS_SCALER_TRACKER] = tracker;
+  } else {
+    si[CLIPFS_SCALER_SKIPPED] += 1;
+    si[CLIPFS_SCALER_SKIP] = 1;
+    sf[CLIPFS_SCALER_SCALE] = scale * backoff_factor;
+    si[CLIPFS_SCALER_TRACKER] = 0;
+  }
+  si[CLIPFS_SCALER_FOUND] = 0;
+}
+
+// adamw_kernel with the gradient scale, the bias corrections and the skip decision of the scaler record
+__global__ __launch_bounds__(256) void adamw_scaled_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                           float* __restrict__ m, float* __restrict__ v, size_t n,
+                                                           float lr, float b1, float b2, float eps, float wd,
+                                                           const float* __restrict__ sf) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n || reinterpret_cast<const int32_t*>(sf)[CLIPFS_SCALER_SKIP] != 0) return;
+  adamw_element(p, g, m, v, i, lr, b1, b2, eps, wd, sf[CLIPFS_SCALER_INV_SQRT_BC2], sf[CLIPFS_SCALER_STEP_SIZE],
+                sf[CLIPFS_SCALER_INV_SCALE]);
 }
 
 // C[m,n] = alpha * sum_k A[m*sam + k*sak] * B[k*sbk + n*sbn]   (tiny products whose reduction dim is
@@ -768,6 +858,20 @@ extern "C" int clipfs_cross_entropy(const float* logits, const int64_t* target, 
   return launch_status();
 }
 
+extern "C" int clipfs_cross_entropy_scaled(const float* logits, const int64_t* target, float* dlogits, float* loss_rows,
+                                           float* loss_sum, int32_t* correct, int rows, int classes, float grad_scale,
+                                           const float* scaler_state, void* stream) {
+  CLIPFS_REQUIRE(logits && target && loss_rows && loss_sum && rows > 0 && classes > 0, "cross_entropy_scaled: bad args");
+  CLIPFS_REQUIRE(scaler_state && aligned16(scaler_state), "cross_entropy_scaled: null or misaligned scaler state");
+  int32_t* flags = correct ? reinterpret_cast<int32_t*>(loss_rows + rows) : nullptr;
+  hipLaunchKernelGGL(cross_entropy_scaled_kernel, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, logits, target,
+                     dlogits, loss_rows, flags, rows, classes, grad_scale, scaler_state);
+  CLIPFS_CHECK(launch_status());
+  hipLaunchKernelGGL(ce_finish_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, loss_rows, flags, loss_sum, correct,
+                     rows);
+  return launch_status();
+}
+
 extern "C" int clipfs_topk(const float* logits, int32_t* labels, int rows, int classes, int k, void* stream) {
   CLIPFS_REQUIRE(logits && labels && rows > 0 && classes > 0 && k > 0 && k <= classes, "topk: bad args");
   hipLaunchKernelGGL(topk_kernel, dim3(rows), dim3(64), 0, (hipStream_t)stream, logits, labels, classes, k);
@@ -809,6 +913,41 @@ extern "C" int clipfs_adamw(float* p, const float* g, float* m, float* v, size_t
   const double bc2 = 1.0 - pow((double)beta2, step);
   hipLaunchKernelGGL(adamw_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, lr,
                      beta1, beta2, eps, weight_decay, (float)(1.0 / sqrt(bc2)), (float)((double)lr / bc1), grad_scale);
+  return launch_status();
+}
+
+static inline bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
+
+extern "C" int clipfs_grads_nonfinite(const float* g, size_t n, float* scaler_state, void* stream) {
+  CLIPFS_REQUIRE(scaler_state && aligned16(scaler_state), "grads_nonfinite: null or misaligned scaler state");
+  CLIPFS_REQUIRE(g && aligned4(g), "grads_nonfinite: null or misaligned gradient pointer");
+  CLIPFS_REQUIRE(n > 0, "grads_nonfinite: n = 0");
+  size_t head = ((16u - (reinterpret_cast<uintptr_t>(g) & 15u)) & 15u) / 4;  // floats before the first 16-byte boundary
+  if (head > n) head = n;
+  hipLaunchKernelGGL(grads_nonfinite_kernel, dim3(grid_for((n - head) / 4)), dim3(256), 0, (hipStream_t)stream, g, n,
+                     (unsigned)head, reinterpret_cast<int32_t*>(scaler_state));
+  return launch_status();
+}
+
+extern "C" int clipfs_scaler_decide(float* scaler_state, float lr, float beta1, float beta2, float growth_factor,
+                                    float backoff_factor, int growth_interval, void* stream) {
+  CLIPFS_REQUIRE(scaler_state && aligned16(scaler_state), "scaler_decide: null or misaligned scaler state");
+  CLIPFS_REQUIRE(growth_factor >= 1.f && backoff_factor > 0.f && backoff_factor <= 1.f && growth_interval >= 0,
+                 "scaler_decide: growth_factor %g must be >= 1, backoff_factor %g in (0, 1], growth_interval %d >= 0",
+                 (double)growth_factor, (double)backoff_factor, growth_interval);
+  hipLaunchKernelGGL(scaler_decide_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, scaler_state, lr, beta1, beta2,
+                     growth_factor, backoff_factor, growth_interval);
+  return launch_status();
+}
+
+extern "C" int clipfs_adamw_scaled(float* p, const float* g, float* m, float* v, size_t n, float lr, float beta1,
+                                   float beta2, float eps, float weight_decay, const float* scaler_state, void* stream) {
+  CLIPFS_REQUIRE(scaler_state && aligned16(scaler_state), "adamw_scaled: null or misaligned scaler state");
+  CLIPFS_REQUIRE(p && g && m && v && aligned4(p) && aligned4(g) && aligned4(m) && aligned4(v),
+                 "adamw_scaled: null or misaligned pointer");
+  CLIPFS_REQUIRE(n > 0, "adamw_scaled: n = 0");
+  hipLaunchKernelGGL(adamw_scaled_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, p, g, m,
+                     v, n, lr, beta1, beta2, eps, weight_decay, scaler_state);
   return launch_status();
 }
 

@@ -15,6 +15,7 @@ all-reduce and the optimiser a single fused launch."""
 from __future__ import annotations
 
 import math
+import numbers
 import os
 import pickle
 from typing import Dict, List, Optional, Sequence, Tuple
@@ -648,6 +649,28 @@ class FlatTrainables:
         self.grads.zero_()
 
 
+def _check_loss_scale(loss_scale, init_scale, growth_factor, backoff_factor, growth_interval):
+    """Validate the loss-scaling arguments of ``LoRATrainer``; returns None (off), 'static' or 'dynamic'."""
+    if loss_scale is None:
+        return None
+    if isinstance(loss_scale, str):
+        if loss_scale != "dynamic":
+            raise ValueError(f"loss_scale must be None, a positive number or 'dynamic', not {loss_scale!r}")
+        if not (math.isfinite(init_scale) and init_scale > 0):
+            raise ValueError(f"init_scale must be a positive finite number, not {init_scale!r}")
+        if not (math.isfinite(growth_factor) and growth_factor > 1):
+            raise ValueError(f"growth_factor must be > 1, not {growth_factor!r}")
+        if not 0 < backoff_factor < 1:
+            raise ValueError(f"backoff_factor must lie in (0, 1), not {backoff_factor!r}")
+        if int(growth_interval) != growth_interval or growth_interval < 1:
+            raise ValueError(f"growth_interval must be a positive integer, not {growth_interval!r}")
+        return "dynamic"
+    if isinstance(loss_scale, bool) or not isinstance(loss_scale, numbers.Real) or not math.isfinite(loss_scale) \
+            or loss_scale <= 0:
+        raise ValueError(f"loss_scale must be None, a positive number or 'dynamic', not {loss_scale!r}")
+    return "static"
+
+
 class LoRATrainer:
     """One object = the state of run_lora (:921-1023) that matters for the hot path: model with adapters,
     flat trainables, AdamW moments, step counter.  ``step`` is the loop body :956-1002:
@@ -657,12 +680,28 @@ class LoRATrainer:
         logits = 100 * img @ txt^T ; mean cross entropy ; backward into LoRA (+ prompt) ; AdamW
 
     Data-parallel: every rank holds the full model, takes its shard of the image batch, and the flat
-    gradient buffer is summed with one all-reduce (losses are pre-scaled by B_local / B_global)."""
+    gradient buffer is summed with one all-reduce (losses are pre-scaled by B_local / B_global).
+
+    Loss scaling (opt-in, for the fp16 storage mode whose backward keeps activation gradients as f16 images; allowed
+    and harmless in the other modes).  ``loss_scale=None`` is the unscaled step, launch for launch.  A positive number is
+    a static scale; ``"dynamic"`` starts at ``init_scale`` (65536), multiplies by ``growth_factor`` after
+    ``growth_interval`` consecutive clean steps and by ``backoff_factor`` after a step whose gradients held NaN / inf.
+    Either kind SKIPS such a step: parameters and moments stay bitwise untouched.  The logits gradient is multiplied by
+    the scale on the device, ``flat.grads`` holds SCALED gradients between ``forward_backward`` and ``optimizer_step``
+    (several ``forward_backward`` calls accumulate under one scale), and ``optimizer_step`` is three launches (non-finite
+    check, decision, AdamW) instead of one, with no host synchronisation; under data parallelism the check runs after
+    the all-reduce, so every rank takes the same decision without a further collective.  ``t`` still counts
+    ``optimizer_step`` calls; with scaling on, AdamW's step number is ``optimizer_steps``, which leaves skipped steps
+    out.  ``loss_scale_value`` / ``skipped_steps`` / ``optimizer_steps`` read the device record back (they synchronise;
+    ``step`` never uses them).  Not covered: ``Stage2Trainer`` and the autograd route of ``encode_image`` /
+    ``encode_text``; bias training still needs a non-fp16 mode."""
 
     def __init__(self, model, lr: float = 2e-4, weight_decay: float = 1e-2, betas=(0.9, 0.999), eps: float = 1e-8,
                  logit_scale: float = 100.0, prompt_ctx: Optional[nn.Parameter] = None, process_group=None,
-                 shard_text: bool = True):
+                 shard_text: bool = True, loss_scale=None, growth_factor: float = 2.0, backoff_factor: float = 0.5,
+                 growth_interval: int = 2000, init_scale: float = 65536.0):
         from clipfs import dist as D
+        self.loss_scaling = _check_loss_scale(loss_scale, init_scale, growth_factor, backoff_factor, growth_interval)
         self.model = model
         extra = []
         if prompt_ctx is not None:
@@ -688,6 +727,36 @@ class LoRATrainer:
         self.last_plan = None  # gradient floors of the last forward_backward: {"text": lo or None, "vision": lo or None}
         self.time_collectives = False      # bench: bracket every collective with HIP events on the launch stream
         self._coll_events = []
+        # loss scaling: the device record (clipfs.h CLIPFS_SCALER_*) and the scaler's constants; None = off
+        self.scale_state = None
+        if self.loss_scaling == "dynamic":
+            self._scaler_rule = (float(growth_factor), float(backoff_factor), int(growth_interval))
+            self.scale_state = ops.new_scaler_state(float(init_scale), self.flat.params.device)
+        elif self.loss_scaling == "static":
+            self._scaler_rule = (1.0, 1.0, 0)  # never grows, never backs off; still skips a non-finite step
+            self.scale_state = ops.new_scaler_state(float(loss_scale), self.flat.params.device)
+
+    # -- loss scaling: host views of the device record (each one synchronises) -------------------------
+    def _scaler_word(self, index: int, as_int: bool):
+        if self.scale_state is None:
+            return None
+        st = self.scale_state.cpu()
+        return int(st.view(torch.int32)[index]) if as_int else float(st[index])
+
+    @property
+    def loss_scale_value(self) -> Optional[float]:
+        """The scale the next ``forward_backward`` applies (None with loss scaling off)."""
+        return self._scaler_word(ops._lib.SCALER_SCALE, False)
+
+    @property
+    def skipped_steps(self) -> int:
+        """``optimizer_step`` calls that changed nothing because a gradient was NaN / inf (0 with loss scaling off)."""
+        return self._scaler_word(ops._lib.SCALER_SKIPPED, True) or 0
+
+    @property
+    def optimizer_steps(self) -> int:
+        """AdamW steps applied: ``t`` minus the skipped steps."""
+        return self.t if self.scale_state is None else self._scaler_word(ops._lib.SCALER_STEP, True)
 
     # -- collectives ---------------------------------------------------------------------------------
     def _exchange_buffers(self, classes: int, width: int):
@@ -774,7 +843,7 @@ class LoRATrainer:
             txt = full[:classes]
         logits = ops.gemm_nt(img_n, txt, alpha=self.logit_scale)
         self.last_features = (img_n, txt)  # unit image features of this rank's shard, unit class features [C, d] (tests)
-        loss_sum, dl, correct = ops.cross_entropy(logits, target, True, grad_scale=B / gb)
+        loss_sum, dl, correct = ops.cross_entropy(logits, target, True, grad_scale=B / gb, scale_state=self.scale_state)
         if vis_lo is not None:
             d_img_n = ops.matmul_small(dl, txt, B, d, classes, classes, 1, d, 1, self.logit_scale)
         if text_lo is not None:
@@ -810,8 +879,15 @@ class LoRATrainer:
             # only, so this same sum is already the batch total (d_txt is linear in the local dlogits)
             self._timed("all_reduce", lambda: D.allreduce_sum_(self.flat.grads, self.pg))
         self.t += 1
-        ops.adamw(self.flat.params, self.flat.grads, self.flat.m, self.flat.v, self.t, self.lr, self.betas, self.eps,
-                  self.wd, grad_scale)
+        if self.scale_state is not None:
+            growth, backoff, interval = self._scaler_rule
+            ops.grads_nonfinite(self.flat.grads, self.scale_state)
+            ops.scaler_decide(self.scale_state, self.lr, self.betas, growth, backoff, interval)
+            ops.adamw_scaled(self.flat.params, self.flat.grads, self.flat.m, self.flat.v, self.scale_state, self.lr,
+                             self.betas, self.eps, self.wd)
+        else:
+            ops.adamw(self.flat.params, self.flat.grads, self.flat.m, self.flat.v, self.t, self.lr, self.betas,
+                      self.eps, self.wd, grad_scale)
         self.flat.sync_packed()
 
     def step(self, images, captions, target, templates_per_class: int = 1, global_batch: Optional[int] = None,
