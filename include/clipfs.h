@@ -189,15 +189,33 @@ int clipfs_layernorm_fwd_lora_map(const float* x, int ldx, const float* gamma, c
 int clipfs_attention_fwd(const float* qkv, float* out, float* lse, int batch, int seq, int heads, int causal,
                          void* stream);
 /* dqkv from dout, recomputing the probabilities from qkv.
- * Default path, seq <= 288: exact-fp32 MFMA kernels (v_mfma_f32_32x32x2_f32, scores kept transposed so that the
- * softmax statistics are per-lane scalars).  The forward writes lse [clipfs_attention_lse_floats] (log-sum-exp of
- * the scaled scores per (batch, head, query)) when given the buffer; the backward takes the forward's `out`, that
- * `lse` and a `work` buffer of the same size.
+ * Default path, seq <= clipfs_attention_mfma_max_seq(): exact-fp32 MFMA kernels (v_mfma_f32_32x32x2_f32, scores kept
+ * transposed so that the softmax statistics are per-lane scalars).  Up to 288 tokens one workgroup takes a (batch, head)
+ * with the other side's transposed image whole in LDS; past that the own side is cut into runs of 32-token tiles, one
+ * workgroup each, and the other side passes through LDS in chunks of at most 288 tokens -- the same tile arithmetic in the
+ * same order, every output element written by one wave, so results are bitwise reproducible at every length.  The
+ * forward writes lse [clipfs_attention_lse_floats] (log-sum-exp of the scaled scores per (batch, head, query)) when
+ * given the buffer; the backward takes the forward's `out`, that `lse` and a `work` buffer of the same size.
  * Without lse: seq <= 96 falls back to register/LDS-resident VALU kernels that recompute the softmax (out, lse and
- * work may be NULL); seq > 96 requires lse; seq > 288 runs streaming kernels with an online softmax. */
+ * work may be NULL); seq > 96 requires lse.  Streaming VALU kernels with an online softmax take what the MFMA kernels do
+ * not: seq > clipfs_attention_mfma_max_seq(), misaligned out / dqkv, CLIPFS_ATTN_MFMA=0. */
 int clipfs_attention_bwd(const float* qkv, const float* dout, const float* out, const float* lse, float* dqkv,
                          float* work, int batch, int seq, int heads, int causal, void* stream);
 size_t clipfs_attention_lse_floats(int batch, int seq, int heads);
+/* Longest sequence the exact-fp32 MFMA attention takes (1024). */
+int clipfs_attention_mfma_max_seq(void);
+/* The long-sequence MFMA kernels with an explicit cut, for any 96 < seq <= clipfs_attention_mfma_max_seq() (the default
+ * dispatch launches them past 288 tokens with chunk_tokens = run_tiles = 0): the other side passes through LDS in chunks
+ * of at most chunk_tokens tokens (a multiple of 32, <= 288; 0 = 288), the own side is cut into runs of at most run_tiles
+ * 32-token tiles (1 .. 4; 0 = 4), both evened out over the sequence.  Neither changes a bit of the result: for
+ * seq <= 288 it is the result of clipfs_attention_fwd / _bwd.  lse may be NULL in the forward; the backward needs out, lse
+ * and work (batch*heads*seq floats).  CLIPFS_EINVAL (nothing launched) for a seq, chunk_tokens or run_tiles outside
+ * those ranges and for a NULL or misaligned pointer, the message naming the argument. */
+int clipfs_attention_mfma_long_fwd(const float* qkv, float* out, float* lse, int batch, int seq, int heads, int causal,
+                                   int chunk_tokens, int run_tiles, void* stream);
+int clipfs_attention_mfma_long_bwd(const float* qkv, const float* dout, const float* out, const float* lse, float* dqkv,
+                                   float* work, int batch, int seq, int heads, int causal, int chunk_tokens, int run_tiles,
+                                   void* stream);
 /* Packed (live-row) causal backward of the text tower, seq <= 96 on the exact-fp32 16-token-tile kernels
  * (clipfs_attention_bwd_packed_ok(seq, causal) != 0; needs causal and the MFMA kernels).  Sequence b is live on tokens
  * 0 .. Lb - 1, Lb = off[b + 1] - off[b] in [1, seq] (off: int32 [batch + 1], device, off[0] = 0): qkv, out and lse are the

@@ -98,6 +98,9 @@ SIGNATURES = {
     "clipfs_attention_fwd": (_i, [_p, _p, _p, _i, _i, _i, _i, _p]),
     "clipfs_attention_bwd": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p]),
     "clipfs_attention_lse_floats": (_sz, [_i, _i, _i]),
+    "clipfs_attention_mfma_max_seq": (_i, []),
+    "clipfs_attention_mfma_long_fwd": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
+    "clipfs_attention_mfma_long_bwd": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
     "clipfs_attention_f16_max_seq": (_i, []),
     "clipfs_attention_f16_fwd": (_i, [_p, _i, _p, _p, _p, _i, _i, _i, _i, _p]),
     "clipfs_attention_f16_bwd": (_i, [_p, _i, _p, _i, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p]),

@@ -192,6 +192,36 @@ def attention_fwd(qkv, batch, seq, heads, causal, want_lse=False):
     return (out, lse) if want_lse else out
 
 
+def attention_mfma_max_seq() -> int:
+    """Longest sequence the exact-fp32 MFMA attention takes; attention_fwd / attention_bwd run streaming VALU kernels past it."""
+    return _lib.load().clipfs_attention_mfma_max_seq()
+
+
+ATTENTION_MFMA_LONG_RUN = 4  # most 32-token tiles per run (= waves per workgroup) of the long-sequence fp32 MFMA kernels
+
+
+def attention_mfma_long_fwd(qkv, batch, seq, heads, causal=False, chunk_tokens=0, run_tiles=0, want_lse=True):
+    """The long-sequence fp32 MFMA forward (96 < seq <= attention_mfma_max_seq()) with an explicit cut: the other side in
+    chunks of at most chunk_tokens tokens (a multiple of 32 up to 288), the own side in runs of at most run_tiles tiles
+    (1 .. ATTENTION_MFMA_LONG_RUN); 0 = the default attention_fwd uses past 288 tokens.  The cut changes no bit of the
+    result.  Returns (out, lse), or out alone with want_lse=False."""
+    out = torch.empty(batch * seq, heads * 64, device=qkv.device, dtype=torch.float32)
+    lse = torch.empty(batch * heads * seq, device=qkv.device, dtype=torch.float32) if want_lse else None
+    check(_lib.load().clipfs_attention_mfma_long_fwd(_p(_f32(qkv)), _p(out), _p(lse), batch, seq, heads, int(causal),
+                                                     chunk_tokens, run_tiles, _stream()), "attention_mfma_long_fwd")
+    return (out, lse) if want_lse else out
+
+
+def attention_mfma_long_bwd(qkv, dout, out, lse, batch, seq, heads, causal=False, chunk_tokens=0, run_tiles=0):
+    """dqkv of attention_mfma_long_fwd (same bounds, same meaning of chunk_tokens and run_tiles)."""
+    dqkv = torch.empty_like(qkv)
+    work = torch.empty_like(lse)
+    check(_lib.load().clipfs_attention_mfma_long_bwd(_p(_f32(qkv)), _p(_f32(dout)), _p(out), _p(lse), _p(dqkv), _p(work),
+                                                     batch, seq, heads, int(causal), chunk_tokens, run_tiles, _stream()),
+          "attention_mfma_long_bwd")
+    return dqkv
+
+
 def attention_f16_max_seq() -> int:
     """Longest sequence the fp16-mode MFMA attention takes (a longer one is refused before anything is launched)."""
     return _lib.load().clipfs_attention_f16_max_seq()

@@ -646,12 +646,19 @@ __global__ __launch_bounds__(512) void attention_lds_bwd_kv_kernel(const float* 
 }
 
 // attention_mfma.hip: exact-fp32 MFMA kernels for seq <= 288 (the default path; the VALU kernels below remain for
-// longer sequences, for backward calls without the forward's lse, and as the CLIPFS_ATTN_MFMA=0 comparison)
+// sequences past clipfs_attention_mfma_max_seq(), for backward calls without the forward's lse, and as the
+// CLIPFS_ATTN_MFMA=0 comparison)
 bool attention_mfma_enabled();
 int attention_mfma_fwd(const float* qkv, float* out, float* lse, int batch, int seq, int heads, int causal, hipStream_t st);
 int attention_mfma_bwd(const float* qkv, const float* dout, const float* out, const float* lse, float* dqkv, float* work,
                        int batch, int seq, int heads, int causal, hipStream_t st);
 constexpr int ATTN_MFMA_MAX = 288;
+// ... and their long-sequence form (own side in runs of tiles, other side through LDS in chunks) up to
+// clipfs_attention_mfma_max_seq() tokens; chunk_tokens = run_tiles = 0: the default cut
+int attention_mfma_long_fwd(const float* qkv, float* out, float* lse, int batch, int seq, int heads, int causal,
+                            int chunk_tokens, int run_tiles, hipStream_t st);
+int attention_mfma_long_bwd(const float* qkv, const float* dout, const float* out, const float* lse, float* dqkv, float* work,
+                            int batch, int seq, int heads, int causal, int chunk_tokens, int run_tiles, hipStream_t st);
 // attention_mfma16.hip: the 16-token-tile kernels (seq <= 96) and their packed (live-row) backward
 bool attention16_enabled(int seq);
 int attention16_bwd_packed(const float* qkv, const float* dout, const float* out, const float* lse, float* dqkv,
@@ -688,6 +695,8 @@ extern "C" int clipfs_attention_fwd(const float* qkv, float* out, float* lse, in
   hipStream_t st = (hipStream_t)stream;
   if (attention_mfma_enabled() && seq <= ATTN_MFMA_MAX && aligned16(out))
     return attention_mfma_fwd(qkv, out, lse, batch, seq, heads, causal, st);
+  if (attention_mfma_enabled() && seq > ATTN_MFMA_MAX && seq <= clipfs_attention_mfma_max_seq() && aligned16(out))
+    return attention_mfma_long_fwd(qkv, out, lse, batch, seq, heads, causal, 0, 0, st);
   if ((seq > 128 || (seq > ATTN_FAST_MAX && lse)) && seq <= ATTN_LDS_MAX) {
     const size_t lds = ((size_t)2 * seq * KSTRIDE + 8 * 64) * sizeof(float);
     static bool attr = false;
@@ -726,6 +735,9 @@ extern "C" int clipfs_attention_bwd(const float* qkv, const float* dout, const f
   hipStream_t st = (hipStream_t)stream;
   if (attention_mfma_enabled() && seq <= ATTN_MFMA_MAX && out && lse && work && aligned16(out) && aligned16(dqkv))
     return attention_mfma_bwd(qkv, dout, out, lse, dqkv, work, batch, seq, heads, causal, st);
+  if (attention_mfma_enabled() && seq > ATTN_MFMA_MAX && seq <= clipfs_attention_mfma_max_seq() && out && lse && work &&
+      aligned16(out) && aligned16(dqkv))
+    return attention_mfma_long_bwd(qkv, dout, out, lse, dqkv, work, batch, seq, heads, causal, 0, 0, st);
   if (seq > ATTN_FAST_MAX) {
     CLIPFS_REQUIRE(out && lse && work, "attention_bwd: seq %d > %d needs the forward's out and lse and a work buffer", seq,
                    ATTN_FAST_MAX);
