@@ -162,6 +162,12 @@ int clipfs_layernorm_fwd_f16(const float* x, int ldx, const float* gamma, const 
 int clipfs_layernorm_bwd_f16(const float* dy, const float* x, int ldx, const float* gamma, const float* mean,
                              const float* rstd, const float* dres, float* dx, void* dx16, int lddx, int rows, int width,
                              void* stream);
+/* clipfs_layernorm_bwd_rows with the f16 copy of clipfs_layernorm_bwd_f16: x, mean and rstd read at row xmap[r], dy,
+ * dres, dx and dx16 (may be NULL) dense [rows, ...].  The fp16 storage mode's packed text backward; the arithmetic per
+ * row is that of both siblings, and dres may alias dx. */
+int clipfs_layernorm_bwd_rows_f16(const float* dy, const float* x, int ldx, const float* gamma, const float* mean,
+                                  const float* rstd, const int32_t* xmap, const float* dres, float* dx, void* dx16, int lddx,
+                                  int rows, int width, void* stream);
 /* LayerNorm forward with the adapter's down-projection in the same pass: y = LN(x) (and / or its f16 copy y16) and
  * t[row, s*r + j] = sum_k dropout_s(y)[row, k] * A[s*r + j, k], exactly clipfs_layernorm_fwd(_f16) followed by
  * clipfs_lora_down on y (same Philox counters, so clipfs_lora_bwd regenerates the same masks; t agrees to fp32 summation
@@ -251,6 +257,17 @@ int clipfs_attention_f16_fwd(const void* qkv, int qkv_f16, float* out, void* out
 int clipfs_attention_f16_bwd(const void* qkv, int qkv_f16, const void* dout, int dout_f16, const float* out,
                              const float* lse, float* dqkv, void* dqkv16, float* work, int batch, int seq, int heads,
                              int causal, void* stream);
+/* Packed (live-row) causal backward of the text tower in fp16 storage mode, seq <= 288 on the one-workgroup-per-head
+ * kernels above (clipfs_attention_f16_bwd_packed_ok(seq, causal) != 0; needs causal).  As clipfs_attention_bwd_packed:
+ * sequence b is live on tokens 0 .. Lb - 1, Lb = off[b + 1] - off[b] in [1, seq]; qkv (fp32 or f16), out and lse are the
+ * dense forward's tensors (row b * seq + tok, lse [b * heads + h][seq]) and work keeps that dense layout; dout (fp32 or
+ * f16) and dqkv / dqkv16 are packed (row off[b] + tok).  Either of dqkv / dqkv16 may be NULL, not both.  Each live row
+ * gets exactly the values clipfs_attention_f16_bwd computes when every dead row of dout is 0, in both images; tiles past
+ * Lb do no work. */
+int clipfs_attention_f16_bwd_packed_ok(int seq, int causal);
+int clipfs_attention_f16_bwd_packed(const void* qkv, int qkv_f16, const void* dout, int dout_f16, const float* out,
+                                    const float* lse, float* dqkv, void* dqkv16, float* work, const int32_t* off, int batch,
+                                    int seq, int heads, void* stream);
 
 /* ------------------------------------------------------------------ LoRA --
  * t[m, s*r + j] = sum_k drop_s(x)[m,k] * A[s*r + j, k]       (the "down" half of

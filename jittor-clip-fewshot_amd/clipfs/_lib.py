@@ -176,6 +176,9 @@ SIGNATURES = {
     "clipfs_tower_pack_fwd_mode": (_i, [C.POINTER(Tower), _i, _i]),
     "clipfs_tower_fwd_packed": (_i, [C.POINTER(Tower), _p, _p, _p, _i, _i, _p, _p, _p]),
     "clipfs_tower_bwd_packed_saved": (_i, [C.POINTER(Tower), _p, _p, _p, _i, _p, _i, _p, _p, _i, _p]),
+    "clipfs_attention_f16_bwd_packed_ok": (_i, [_i, _i]),
+    "clipfs_attention_f16_bwd_packed": (_i, [_p, _i, _p, _i, _p, _p, _p, _p, _p, _p, _i, _i, _i, _p]),
+    "clipfs_layernorm_bwd_rows_f16": (_i, [_p, _p, _i, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _p]),
 }
 
 # word indices of the loss-scaling record (CLIPFS_SCALER_* of include/clipfs.h)

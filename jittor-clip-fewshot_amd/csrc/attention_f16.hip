@@ -205,14 +205,34 @@ __global__ __launch_bounds__(320) void attention_f16_fwd_kernel(const TQ* __rest
 // backward, pass 1: dQ (and D_i = dO_i . O_i for pass 2).  Own side = queries; K (both images) and V in LDS.
 //   S^T = K Q^T ; P^T = exp(S^T c - lse) ; dP^T = V dO^T ; dS^T = P^T (dP^T - D) / 8 ; dQ^T += K^T dS^T
 // ---------------------------------------------------------------------------------------------------------
-template <typename TQ, typename TG>
+//
+// PACKED (the live-row text backward, causal towers only): sequence b has Lb = off[b + 1] - off[b] live tokens.  q/k/v, O,
+// lse and the D vector keep the dense layout (row b * S + tok, [b * H + h][S]; S = the sequence length of the records);
+// dO is read and dQ / dK / dV are written at the packed row off[b] + tok.  The kernels run as on a sequence of L = Lb tokens:
+// tokens past Lb are staged as zeros and the wave loop ends at Lb (there is no barrier after the first one, so a wave
+// whose tile starts past Lb simply falls out of it).
+// Given dO that is exactly 0 on the dead rows, every live row gets the value of the dense kernels, in both images: a live
+// query's key tiles are the same (causal: up to its diagonal tile, all of them live or masked by key <= query), and a dead
+// query contributes dO = 0, hence dP = D = 0 and dS = 0: exact zeros added to dK and dV -- the tiles this walk skips.
+// The offsets are a trailing argument pack, OFF = {const int32_t*} when PACKED and empty otherwise: the dense
+// instantiations keep their argument list, and compile to the code they were before the packed ones existed.
+// live tokens of sequence b, and its first row in dO and dqkv:
+__device__ __forceinline__ int af_live(int, int S) { return S; }
+__device__ __forceinline__ int af_live(int b, int S, const int32_t* off) { return min(max(off[b + 1] - off[b], 0), S); }
+__device__ __forceinline__ size_t af_row0(int b, int S) { return (size_t)b * S; }
+__device__ __forceinline__ size_t af_row0(int b, int, const int32_t* off) { return (size_t)off[b]; }
+
+template <typename TQ, typename TG, bool PACKED = false, typename... OFF>
 __global__ __launch_bounds__(576) void attention_f16_bwd_q_kernel(const TQ* __restrict__ qkv,
                                                                   const TG* __restrict__ dout,
                                                                   const float* __restrict__ out,
                                                                   const float* __restrict__ lse, float* __restrict__ dqkv,
-                                                                  float* __restrict__ Dbuf, int L, int H, int causal,
-                                                                  _Float16* __restrict__ dqkv16) {
+                                                                  float* __restrict__ Dbuf, int S, int H, int causal,
+                                                                  _Float16* __restrict__ dqkv16,
+                                                                  OFF... off) {
+  static_assert(sizeof...(OFF) == (PACKED ? 1 : 0), "the packed kernels take the plan's offsets, the dense ones nothing");
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  const int L = af_live(blockIdx.x / H, S, off...);
   const int Lp = (L + 31) & ~31, TP = Lp + 4;
   _Float16* sK = reinterpret_cast<_Float16*>(smem_raw);
   _Float16* sV = sK + Lp * AF_ROW;
@@ -223,7 +243,9 @@ __global__ __launch_bounds__(576) void attention_f16_bwd_q_kernel(const TQ* __re
   const int b = blockIdx.x / H, h = blockIdx.x % H;
   const int d = H * AF_HD;
   const size_t ld = (size_t)3 * d;
-  const TQ* q0 = qkv + (size_t)b * L * ld + (size_t)h * AF_HD;
+  const size_t drow = (size_t)b * S;            // first row of the sequence in the dense tensors
+  const size_t prow = af_row0(b, S, off...);       // ... in dO and dqkv
+  const TQ* q0 = qkv + drow * ld + (size_t)h * AF_HD;
   stage_head(q0 + d, ld, L, Lp, sK, sKt);
   stage_head(q0 + 2 * d, ld, L, Lp, sV, nullptr);
   __syncthreads();
@@ -235,8 +257,8 @@ __global__ __launch_bounds__(576) void attention_f16_bwd_q_kernel(const TQ* __re
     load_own(q0, ld, qt * 32, L, lane, qf);
     float Di = 0.f;
     {
-      const TG* gp = dout + ((size_t)b * L + q_cl) * d + h * AF_HD + 8 * fh;
-      const float* op = out + ((size_t)b * L + q_cl) * d + h * AF_HD + 8 * fh;
+      const TG* gp = dout + (prow + q_cl) * d + h * AF_HD + 8 * fh;
+      const float* op = out + (drow + q_cl) * d + h * AF_HD + 8 * fh;
 #pragma unroll
       for (int sidx = 0; sidx < 4; ++sidx) {
         f32x4 g0, g1;
@@ -258,8 +280,8 @@ __global__ __launch_bounds__(576) void attention_f16_bwd_q_kernel(const TQ* __re
       }
       Di += xor32(Di);
     }
-    const float lse2 = lse[((size_t)b * H + h) * L + q_cl] * AF_LOG2E;
-    if (q_tok < L && fh == 0) Dbuf[((size_t)b * H + h) * L + q_tok] = Di;
+    const float lse2 = lse[((size_t)b * H + h) * S + q_cl] * AF_LOG2E;
+    if (q_tok < L && fh == 0) Dbuf[((size_t)b * H + h) * S + q_tok] = Di;
     f32x16 acc[2];
 #pragma unroll
     for (int t = 0; t < 2; ++t)
@@ -284,7 +306,7 @@ __global__ __launch_bounds__(576) void attention_f16_bwd_q_kernel(const TQ* __re
           acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(load_T(sKt, TP, t, k0, u, lane), dsf[u], acc[t], 0, 0, 0);
     }
     if (q_tok < L) {
-      float* op = dqkv + ((size_t)b * L + q_tok) * ld + h * AF_HD + 4 * fh;
+      float* op = dqkv + (prow + q_tok) * ld + h * AF_HD + 4 * fh;
 #pragma unroll
       for (int t = 0; t < 2; ++t)
 #pragma unroll
@@ -294,7 +316,7 @@ __global__ __launch_bounds__(576) void attention_f16_bwd_q_kernel(const TQ* __re
           for (int j = 0; j < 4; ++j) v[j] = acc[t][4 * g4 + j];
           if (dqkv) *reinterpret_cast<f32x4*>(op + 32 * t + 8 * g4) = v;
           if (dqkv16)
-            *reinterpret_cast<f16x4*>(dqkv16 + ((size_t)b * L + q_tok) * ld + h * AF_HD + 4 * fh + 32 * t + 8 * g4) =
+            *reinterpret_cast<f16x4*>(dqkv16 + (prow + q_tok) * ld + h * AF_HD + 4 * fh + 32 * t + 8 * g4) =
                 f16x4{(_Float16)v[0], (_Float16)v[1], (_Float16)v[2], (_Float16)v[3]};
         }
     }
@@ -306,14 +328,18 @@ __global__ __launch_bounds__(576) void attention_f16_bwd_q_kernel(const TQ* __re
 //   S = Q K^T ; P = exp(S c - lse) ; dP = dO V^T ; dS = P (dP - D) / 8 ; dV^T += dO^T P ; dK^T += Q^T dS
 // (rows of the MFMA result = queries, so lse and D vary with the register index: read as 4-float groups from LDS).
 // ---------------------------------------------------------------------------------------------------------
-template <typename TQ, typename TG>
+// PACKED: as in pass 1 -- Q, lse and D at the dense rows, dO and dK / dV at the packed rows, L = the sequence's live tokens.
+template <typename TQ, typename TG, bool PACKED = false, typename... OFF>
 __global__ __launch_bounds__(576) void attention_f16_bwd_kv_kernel(const TQ* __restrict__ qkv,
                                                                    const TG* __restrict__ dout,
                                                                    const float* __restrict__ lse,
                                                                    const float* __restrict__ Dbuf,
-                                                                   float* __restrict__ dqkv, int L, int H, int causal,
-                                                                   _Float16* __restrict__ dqkv16) {
+                                                                   float* __restrict__ dqkv, int S, int H, int causal,
+                                                                   _Float16* __restrict__ dqkv16,
+                                                                   OFF... off) {
+  static_assert(sizeof...(OFF) == (PACKED ? 1 : 0), "the packed kernels take the plan's offsets, the dense ones nothing");
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  const int L = af_live(blockIdx.x / H, S, off...);
   const int Lp = (L + 31) & ~31, TP = Lp + 4;
   _Float16* sQ = reinterpret_cast<_Float16*>(smem_raw);
   _Float16* sG = sQ + Lp * AF_ROW;
@@ -327,12 +353,13 @@ __global__ __launch_bounds__(576) void attention_f16_bwd_kv_kernel(const TQ* __r
   const int b = blockIdx.x / H, h = blockIdx.x % H;
   const int d = H * AF_HD;
   const size_t ld = (size_t)3 * d;
-  const TQ* q0 = qkv + (size_t)b * L * ld + (size_t)h * AF_HD;
+  const size_t drow = (size_t)b * S, prow = af_row0(b, S, off...);
+  const TQ* q0 = qkv + drow * ld + (size_t)h * AF_HD;
   stage_head(q0, ld, L, Lp, sQ, sQt);
-  stage_head(dout + (size_t)b * L * d + (size_t)h * AF_HD, (size_t)d, L, Lp, sG, sGt);
+  stage_head(dout + prow * d + (size_t)h * AF_HD, (size_t)d, L, Lp, sG, sGt);
   for (int i = threadIdx.x; i < Lp; i += (int)blockDim.x) {
-    sLse[i] = i < L ? lse[((size_t)b * H + h) * L + i] * AF_LOG2E : 0.f;
-    sD[i] = i < L ? Dbuf[((size_t)b * H + h) * L + i] : 0.f;
+    sLse[i] = i < L ? lse[((size_t)b * H + h) * S + i] * AF_LOG2E : 0.f;
+    sD[i] = i < L ? Dbuf[((size_t)b * H + h) * S + i] : 0.f;
   }
   __syncthreads();
   const int fr = lane & 31, fh = lane >> 5;
@@ -376,7 +403,7 @@ __global__ __launch_bounds__(576) void attention_f16_bwd_kv_kernel(const TQ* __r
         }
     }
     if (k_tok < L) {
-      float* kp = dqkv + ((size_t)b * L + k_tok) * ld + d + h * AF_HD + 4 * fh;
+      float* kp = dqkv + (prow + k_tok) * ld + d + h * AF_HD + 4 * fh;
       float* vp = kp + d;
 #pragma unroll
       for (int t = 0; t < 2; ++t)
@@ -393,7 +420,7 @@ __global__ __launch_bounds__(576) void attention_f16_bwd_kv_kernel(const TQ* __r
             *reinterpret_cast<f32x4*>(vp + 32 * t + 8 * g4) = v4;
           }
           if (dqkv16) {
-            _Float16* k16 = dqkv16 + ((size_t)b * L + k_tok) * ld + d + h * AF_HD + 4 * fh + 32 * t + 8 * g4;
+            _Float16* k16 = dqkv16 + (prow + k_tok) * ld + d + h * AF_HD + 4 * fh + 32 * t + 8 * g4;
             *reinterpret_cast<f16x4*>(k16) = f16x4{(_Float16)k4[0], (_Float16)k4[1], (_Float16)k4[2], (_Float16)k4[3]};
             *reinterpret_cast<f16x4*>(k16 + d) = f16x4{(_Float16)v4[0], (_Float16)v4[1], (_Float16)v4[2], (_Float16)v4[3]};
           }
@@ -817,6 +844,31 @@ static int af_bwd(const void* qkv, const void* dout, const float* out, const flo
   return launch_status();
 }
 
+// live rows over dense records (causal only): the launch geometry is the dense one for `seq`
+template <typename TQ, typename TG>
+static int af_bwd_packed(const void* qkv, const void* dout, const float* out, const float* lse, float* dqkv, void* dqkv16,
+                         float* work, const int32_t* off, int batch, int seq, int heads, hipStream_t st) {
+  const int threads = af_threads(seq, 9);
+  const size_t lds_q = af_lds_bytes(seq, 2, 1);
+  const size_t lds_kv = af_lds_bytes(seq, 2, 2) + 2 * (size_t)((seq + 31) & ~31) * sizeof(float);
+  static bool attr = false;  // per instantiation
+  if (!attr) {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attention_f16_bwd_q_kernel<TQ, TG, true, const int32_t*>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attention_f16_bwd_kv_kernel<TQ, TG, true, const int32_t*>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    attr = true;
+  }
+  hipLaunchKernelGGL((attention_f16_bwd_q_kernel<TQ, TG, true, const int32_t*>), dim3(batch * heads), dim3(threads), lds_q, st,
+                     reinterpret_cast<const TQ*>(qkv), reinterpret_cast<const TG*>(dout), out, lse, dqkv, work, seq, heads, 1,
+                     reinterpret_cast<_Float16*>(dqkv16), off);
+  CLIPFS_CHECK(launch_status());
+  hipLaunchKernelGGL((attention_f16_bwd_kv_kernel<TQ, TG, true, const int32_t*>), dim3(batch * heads), dim3(threads), lds_kv, st,
+                     reinterpret_cast<const TQ*>(qkv), reinterpret_cast<const TG*>(dout), lse, work, dqkv, seq, heads, 1,
+                     reinterpret_cast<_Float16*>(dqkv16), off);
+  return launch_status();
+}
+
 extern "C" int clipfs_attention_f16_fwd(const void* qkv, int qkv_f16, float* out, void* out16, float* lse, int batch, int seq,
                                         int heads, int causal, void* stream) {
   CLIPFS_CHECK(check_af(qkv, out, batch, seq, heads));
@@ -838,4 +890,27 @@ extern "C" int clipfs_attention_f16_bwd(const void* qkv, int qkv_f16, const void
                    : af_bwd<float, _Float16>(qkv, dout, out, lse, dqkv, dqkv16, work, batch, seq, heads, causal, st);
   return qkv_f16 ? af_bwd<_Float16, float>(qkv, dout, out, lse, dqkv, dqkv16, work, batch, seq, heads, causal, st)
                  : af_bwd<float, float>(qkv, dout, out, lse, dqkv, dqkv16, work, batch, seq, heads, causal, st);
+}
+
+extern "C" int clipfs_attention_f16_bwd_packed_ok(int seq, int causal) {
+  return (causal && seq > 0 && seq <= AF_MAXL) ? 1 : 0;  // the short kernels: one workgroup per (sequence, head)
+}
+
+extern "C" int clipfs_attention_f16_bwd_packed(const void* qkv, int qkv_f16, const void* dout, int dout_f16, const float* out,
+                                               const float* lse, float* dqkv, void* dqkv16, float* work, const int32_t* off,
+                                               int batch, int seq, int heads, void* stream) {
+  CLIPFS_REQUIRE(qkv && dout && out && lse && work && off && (dqkv || dqkv16), "attention_f16_bwd_packed: null pointer");
+  CLIPFS_REQUIRE(batch > 0 && heads > 0 && seq > 0, "attention_f16_bwd_packed: batch %d seq %d heads %d", batch, seq, heads);
+  CLIPFS_REQUIRE(clipfs_attention_f16_bwd_packed_ok(seq, 1), "attention_f16_bwd_packed: seq %d has no packed kernel (1..%d)",
+                 seq, AF_MAXL);
+  CLIPFS_REQUIRE((long long)batch * heads <= 0x7fffffffLL, "attention_f16_bwd_packed: batch %d x heads %d too large", batch,
+                 heads);
+  CLIPFS_REQUIRE(aligned16(qkv) && aligned16(dout) && aligned16(out) && aligned16(dqkv) && aligned16(dqkv16),
+                 "attention_f16_bwd_packed: misaligned pointer");
+  hipStream_t st = (hipStream_t)stream;
+  if (dout_f16)
+    return qkv_f16 ? af_bwd_packed<_Float16, _Float16>(qkv, dout, out, lse, dqkv, dqkv16, work, off, batch, seq, heads, st)
+                   : af_bwd_packed<float, _Float16>(qkv, dout, out, lse, dqkv, dqkv16, work, off, batch, seq, heads, st);
+  return qkv_f16 ? af_bwd_packed<_Float16, float>(qkv, dout, out, lse, dqkv, dqkv16, work, off, batch, seq, heads, st)
+                 : af_bwd_packed<float, float>(qkv, dout, out, lse, dqkv, dqkv16, work, off, batch, seq, heads, st);
 }

@@ -384,6 +384,22 @@ extern "C" int clipfs_layernorm_bwd_f16(const float* dy, const float* x, int ldx
   return launch_status();
 }
 
+// ... and on packed rows over dense records: x, mean and rstd read at row xmap[row] as clipfs_layernorm_bwd_rows does,
+// the f16 image written as clipfs_layernorm_bwd_f16 does (the live-row text backward of the fp16 storage mode).  The
+// arithmetic per row is that of both; dres may alias dx.
+extern "C" int clipfs_layernorm_bwd_rows_f16(const float* dy, const float* x, int ldx, const float* gamma, const float* mean,
+                                             const float* rstd, const int32_t* xmap, const float* dres, float* dx, void* dx16,
+                                             int lddx, int rows, int width, void* stream) {
+  CLIPFS_CHECK(check_rows("layernorm_bwd_rows_f16", rows, width));
+  CLIPFS_REQUIRE(dy && x && gamma && mean && rstd && xmap && dx, "layernorm_bwd_rows_f16: null pointer");
+  CLIPFS_REQUIRE(ldx >= width && (ldx & 3) == 0 && lddx >= width && (lddx & 3) == 0 && aligned16(x) && aligned16(dy) &&
+                     aligned16(dx) && aligned16(gamma) && (!dres || aligned16(dres)) && (!dx16 || aligned16(dx16)),
+                 "layernorm_bwd_rows_f16: alignment");
+  hipLaunchKernelGGL(layernorm_bwd_kernel<true>, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, dy, x, ldx, gamma,
+                     mean, rstd, dres, dx, lddx, rows, width, reinterpret_cast<_Float16*>(dx16), xmap);
+  return launch_status();
+}
+
 // LayerNorm + adapter down-projection in one pass; covered shapes: 3 segments (q, k, v), rank 1, 2 or 4
 extern "C" int clipfs_layernorm_fwd_lora_ok(int width, int r, int nseg) {
   static const int cfg = getenv("CLIPFS_LN_LORA") ? atoi(getenv("CLIPFS_LN_LORA")) : 1;  // 0: separate launches (A/B aid)

@@ -440,6 +440,8 @@ static int ln_bwd(const Pass& p, const float* dy, const float* x, const float* g
                   float* out, void* out16) {
   const int d = p.t->width;
   const float* rstd = stat + p.v.srows;
+  if (p.v.gather && out16)
+    return clipfs_layernorm_bwd_rows_f16(dy, x, d, g, stat, rstd, p.v.map, res, out, out16, d, p.v.n, d, p.st);
   if (p.v.gather) return clipfs_layernorm_bwd_rows(dy, x, d, g, stat, rstd, p.v.map, res, out, d, p.v.n, d, p.st);
   if (out16) return clipfs_layernorm_bwd_f16(dy, x, d, g, stat, rstd, res, out, out16, d, p.v.n, d, p.st);
   return clipfs_layernorm_bwd(dy, x, d, g, stat, rstd, res, out, d, p.v.n, d, p.st);
@@ -699,8 +701,9 @@ static int bwd_mlp_half(const Pass& p, int l, const float* sv, float* dx, void* 
   float* datt = p.scratch + p.SC.b1;
   CLIPFS_CHECK(bias_sum(p, dx, n, d, d, b.g_b_pr));
   // MLP: du = (dx Wpr) * gelu'(u) ; dh2 = du Wfc ; dx += LN2'(dh2)
+  // (fp16 storage mode keeps u as halves: 2 d floats per row)
   const float* u;
-  CLIPFS_CHECK(saved_rows(p, sv + SL.u, 4 * d, du + 4 * (size_t)n * d, &u));
+  CLIPFS_CHECK(saved_rows(p, sv + SL.u, t->weight_format == 2 ? 2 * d : 4 * d, du + 4 * (size_t)n * d, &u));
   CLIPFS_CHECK(gemm(v.cx, {.M = n, .N = 4 * d, .K = d, .A = dx, .B = b.w_pr_t, .planes = b.w_pr_t_p, .C = du, .act = 2,
                            .aux_in = u, .chain = CHAIN_OUT16, .a16_ready = h16}, p.st));
   CLIPFS_CHECK(bias_sum(p, du, n, 4 * d, 4 * d, b.g_b_fc));
@@ -747,6 +750,10 @@ static int bwd_attn_half(const Pass& p, int l, const float* sv, float* dx, void*
   if (v.saved_packed())  // packed q/k/v and O; packed dO and dqkv either way
     CLIPFS_CHECK(clipfs_attention_bwd_packed_io(sv + SL.qkv, datt, sv + SL.att, sv + SL.lse, dqkv, v.off, p.batch, t->seq,
                                                 t->heads, p.st));
+  else if (v.packed() && f16a)  // fp16 storage mode: the dense flags, dqkv16 at the packed rows of its slot
+    CLIPFS_CHECK(clipfs_attention_f16_bwd_packed(sv + SL.qkv, qkv_f16(t), datt, datt_f16(t, b, h16) ? 1 : 0, sv + SL.att,
+                                                 sv + SL.lse, dy16 ? nullptr : dqkv, p.dqkv16, dh, v.off, p.batch, t->seq,
+                                                 t->heads, p.st));
   else if (v.packed())
     CLIPFS_CHECK(clipfs_attention_bwd_packed(sv + SL.qkv, datt, sv + SL.att, sv + SL.lse, dqkv, v.off, p.batch, t->seq,
                                              t->heads, p.st));
@@ -916,11 +923,23 @@ static bool pack_dropout_ok(const clipfs_tower* t) {
 // the per-block gathers would cost what the smaller products save; such towers keep the dense rows and their arithmetic.
 constexpr int kPackMinRows = 2048;
 
+// fp16 storage mode packs the backward on the f16 attention kernels; the walk reads the transposed f16 planes of every
+// block it visits (check_bwd_weights refuses a backward without them: a descriptor without them is no training one).
+// Its gathers fit the `big` slot as the fp32 mode's do: u as halves sits behind the (unwritten) fp32 du, 4 R d + 2 R d
+// <= 4 M d for R <= M / 2, and the later h1 / t_qkv / keep-bit gathers take R (2.125 d + 4 r) floats.
 static bool pack_ok(const clipfs_tower* t, int batch, int R) {
   const int M = batch * t->seq, d = t->width, r = t->lora_r;
   if (M < kPackMinRows) return false;
-  if (!t->causal || t->weight_format == 2 || !last_block_rows_ok(t)) return false;
-  if (!clipfs_attention_bwd_packed_ok(t->seq, 1)) return false;
+  if (!t->causal || !last_block_rows_ok(t)) return false;
+  if (t->weight_format == 2) {
+    if (!f16_attention(t) || !clipfs_attention_f16_bwd_packed_ok(t->seq, 1)) return false;
+    for (int l = t->grad_lo; l < t->layers; ++l) {
+      const clipfs_block& b = t->blocks[l];
+      if (!b.w_qkv_t_p || !b.w_o_t_p || !b.w_fc_t_p || !b.w_pr_t_p) return false;
+    }
+  } else if (!clipfs_attention_bwd_packed_ok(t->seq, 1)) {
+    return false;
+  }
   if (R < batch || 2 * (size_t)R > (size_t)M || (d % 8) != 0) return false;
   if (!pack_dropout_ok(t)) return false;
   const ScratchLayout SC = scratch_layout(t, (size_t)M);
