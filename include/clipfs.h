@@ -427,6 +427,29 @@ int clipfs_bias_grad(const float* x, size_t ldx, int rows, int cols, int seg_wid
 int clipfs_l1_loss(const float* a, const float* b, size_t n, float* loss, float* da, float grad_scale, void* stream);
 int clipfs_kl_logits(const float* logits, const float* target_logits, float* loss_rows, float* dlogits, int rows,
                      int classes, float grad_scale, void* stream);
+/* The stage-2 objective without its head branch (slow_pace.py:1640,1650-1658,1684-1686) in one launch plus a one-wave
+ * fixed-order reduction: sim_ce = CE(cos, target) (:1686), scl_logits = kl_div(log_softmax(cos), log_softmax(zs_logits))
+ * / numel (:1656-1658), scl_image = l1_loss(img, zs_img) (:1655), scl_text = l1_loss(txt, zs_txt) (:1654), and their
+ * gradients, for ONE data-parallel rank: B of the B_g = 1 / inv_global_batch images and C_loc of the C classes.
+ *   cos, zs_logits [B, C]   the rank's logit block and 100 * zs_img[index] * zs_txt^T; target [B] int64 in [0, C)
+ *   img, zs_img    [B, d]   unit image features and their zero-shot counterparts
+ *   txt, zs_txt [C_loc, d]  the unit text rows this call accounts for (C_loc = 0: none, both may be NULL)
+ *   dcos [B, C]   = S * ((softmax(cos) - onehot) / B_g + (softmax(cos) - softmax(zs_logits)) / (B_g * C))
+ *   dimg [B, d]   = S * sign(img - zs_img) / (B_g * d);  dtxt [C_loc, d] = S * sign(txt - zs_txt) / (C * d)
+ *                   (sign(0) = 0 as clipfs_l1_loss; each of the three may be NULL = not wanted)
+ *   terms [4]     = this call's SHARE of {sim_ce, scl_logits, scl_image, scl_text}: row sums over B_g, B_g * C,
+ *                   B_g * d and C * d, so the shares of all ranks add up to the terms of the whole batch
+ *   correct [1]   (int32, may be NULL) rows whose arg-max of cos is the target (ties to the smaller index)
+ *   work          4 * B + C_loc 32-bit words: the per-row partials, added in row order (no atomics: bitwise run to run)
+ * S is word CLIPFS_SCALER_SCALE of scaler_state (a loss-scaling record, see "loss scaling"), or 1 when it is NULL; it is
+ * the last factor of every gradient entry, terms and correct never carry it.  A wave per row; float4 accesses where the
+ * row width (C, d) is a multiple of 4 and the bases are 16-byte aligned, any C, d, B otherwise.  CLIPFS_EINVAL (nothing
+ * launched) for a NULL required pointer, a misaligned pointer, a non-positive B, C, d or inv_global_batch, or C_loc
+ * outside [0, C]. */
+int clipfs_stage2_objective(const float* cos, const float* zs_logits, const int64_t* target, const float* img,
+                            const float* zs_img, const float* txt, const float* zs_txt, float* dcos, float* dimg,
+                            float* dtxt, float* work, float* terms, int32_t* correct, int B, int C, int d, int C_loc,
+                            float inv_global_batch, const float* scaler_state, void* stream);
 
 /* ------------------------------------------------------------- optimiser --
  * jittor.optim.AdamW.step (lora_train_vlp.py:946,1002): p *= 1 - lr*wd; m,v update;

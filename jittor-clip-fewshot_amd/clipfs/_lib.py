@@ -136,6 +136,7 @@ SIGNATURES = {
     "clipfs_bias_grad": (_i, [_p, _sz, _i, _i, _i, _p, _p, _p, _p, _p]),
     "clipfs_l1_loss": (_i, [_p, _p, _sz, _p, _p, _f, _p]),
     "clipfs_kl_logits": (_i, [_p, _p, _p, _p, _i, _i, _f, _p]),
+    "clipfs_stage2_objective": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _f, _p, _p]),
     "clipfs_adamw": (_i, [_p, _p, _p, _p, _sz, _i, _f, _f, _f, _f, _f, _f, _p]),
     "clipfs_cross_entropy_scaled": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _f, _p, _p]),
     "clipfs_grads_nonfinite": (_i, [_p, _sz, _p, _p]),

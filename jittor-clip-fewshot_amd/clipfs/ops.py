@@ -327,6 +327,15 @@ def matmul_small(a, b, M, N, K, sam, sak, sbk, sbn, alpha=1.0, out=None):
     return out
 
 
+def add_rows_(dst: torch.Tensor, src: torch.Tensor, zero_idx: torch.Tensor) -> torch.Tensor:
+    """dst += src for two contiguous [n, width] tensors (clipfs_add_seq_rows with one row per sequence); ``zero_idx``: at
+    least n int32 zeros on the device (``Engine._class_rows``)."""
+    n, width = src.shape
+    assert dst.shape == src.shape and dst.is_contiguous() and zero_idx.dtype == torch.int32 and zero_idx.numel() >= n
+    check(_lib.load().clipfs_add_seq_rows(_p(_f32(src)), _p(zero_idx), _p(_f32(dst)), n, 1, width, _stream()), "add_seq_rows")
+    return dst
+
+
 def eot_index(ids: torch.Tensor) -> torch.Tensor:
     """idx[c] = position of the EOT token (largest id, first maximum) of caption c, int32 [n] (jclip/model.py:213-214)."""
     assert ids.is_cuda and ids.dtype == torch.int64 and ids.is_contiguous()
@@ -352,9 +361,10 @@ def scatter_rows(dy, idx, seq, out=None):
     return dx
 
 
-def l2norm_fwd(x, save_inv=False):
+def l2norm_fwd(x, save_inv=False, out=None):
     rows, width = x.shape
-    y = torch.empty_like(x)
+    y = torch.empty_like(x) if out is None else out
+    assert y.is_contiguous() and y.shape == x.shape and y.dtype == torch.float32
     inv = torch.empty(rows, device=x.device, dtype=torch.float32) if save_inv else None
     check(_lib.load().clipfs_l2norm_fwd(_p(_f32(x)), _p(y), _p(inv), rows, width, _stream()), "l2norm_fwd")
     return (y, inv) if save_inv else y
@@ -432,8 +442,11 @@ def logit_normalize_bwd(z, dzn):
     return dz
 
 
-def colsum(x, y=None):
-    out = torch.empty(x.shape[1], device=x.device, dtype=torch.float32)
+def colsum(x, y=None, out=None):
+    """out[k] = sum_r x[r, k] (* y[r, k]); ``out``: a contiguous fp32 tensor of x.shape[1] elements to write instead."""
+    if out is None:
+        out = torch.empty(x.shape[1], device=x.device, dtype=torch.float32)
+    assert out.is_contiguous() and out.numel() == x.shape[1] and out.dtype == torch.float32
     check(_lib.load().clipfs_colsum(_p(_f32(x)), _p(y), _p(out), x.shape[0], x.shape[1], _stream()), "colsum")
     return out
 
@@ -531,3 +544,40 @@ def kl_logits(logits: torch.Tensor, target_logits: torch.Tensor, want_grad: bool
     dx = torch.empty_like(x) if want_grad else None
     check(_lib.load().clipfs_kl_logits(_p(x), _p(t), _p(loss_rows), _p(dx), rows, cols, grad_scale, _stream()), "kl_logits")
     return (loss_rows, dx) if want_grad else loss_rows
+
+
+def stage2_objective(cos, zs_logits, target, img, zs_img, txt, zs_txt, classes: int, inv_global_batch: float,
+                     want_grad: bool = True, scale_state: Optional[torch.Tensor] = None,
+                     terms: Optional[torch.Tensor] = None):
+    """The stage-2 objective without its head branch (clipfs_stage2_objective): ``cos`` / ``zs_logits`` [B, C],
+    ``target`` [B] int64, unit image features ``img`` and their zero-shot counterparts ``zs_img`` [B, d], this rank's unit
+    text rows ``txt`` and ``zs_txt`` [C_loc, d] (None or empty: no text row is accounted for here), ``classes`` = C.
+    Returns (terms [4] = this rank's share of sim_ce, scl_logits, scl_image, scl_text; correct [1] int32; dcos; dimg;
+    dtxt) -- the gradients carry the scale of ``scale_state`` (a loss-scaling record) and are None without
+    ``want_grad``; dtxt is None when there is no text row.  ``terms``: a contiguous fp32 tensor whose first four elements
+    receive the shares instead of a fresh one."""
+    B, C = cos.shape
+    d = img.shape[1]
+    assert C == classes and zs_logits.shape == cos.shape and zs_img.shape == img.shape == (B, d)
+    assert target.dtype == torch.int64 and target.is_contiguous() and target.numel() == B
+    n_loc = 0 if txt is None else txt.shape[0]
+    if n_loc:
+        assert zs_txt is not None and zs_txt.shape == txt.shape == (n_loc, d)
+        _f32(txt), _f32(zs_txt)
+    else:
+        txt = zs_txt = None
+    dev = cos.device
+    dcos = torch.empty_like(cos) if want_grad else None
+    dimg = torch.empty_like(img) if want_grad else None
+    dtxt = torch.empty_like(txt) if want_grad and n_loc else None
+    work = torch.empty(4 * B + n_loc, device=dev, dtype=torch.float32)
+    if terms is None:
+        terms = torch.empty(4, device=dev, dtype=torch.float32)
+    assert terms.dtype == torch.float32 and terms.is_contiguous() and terms.numel() >= 4 and terms.device == dev
+    correct = torch.empty(1, device=dev, dtype=torch.int32)
+    check(_lib.load().clipfs_stage2_objective(_p(_f32(cos)), _p(_f32(zs_logits)), _p(target), _p(_f32(img)), _p(_f32(zs_img)),
+                                              _p(txt), _p(zs_txt), _p(dcos), _p(dimg), _p(dtxt), _p(work), _p(terms),
+                                              _p(correct), B, C, d, n_loc, inv_global_batch,
+                                              None if scale_state is None else _p(_scaler(scale_state)), _stream()),
+          "stage2_objective")
+    return terms, correct, dcos, dimg, dtxt

@@ -699,6 +699,185 @@ __global__ __launch_bounds__(256) void kl_logits_kernel(const float* __restrict_
   if (lane == 0) loss_rows[row] = acc;
 }
 
+// ---- the stage-2 objective without its head branch, in one launch (slow_pace.py:1640,1650-1658,1684-1686) ----------
+// A wave per row over three kinds of rows: B logits rows (cross entropy of cos + KL against the zero-shot logits), then
+// B image-feature rows and n_loc text-feature rows (L1 against the zero-shot features).  V = 4 moves float4 (the host
+// checked that the row width and every base of that kind are 16-byte multiples).  Every row leaves one partial per term
+// in `work`; stage2_finish_kernel adds them in a fixed order.  `state` (may be NULL) is a loss-scaling record: the three
+// gradient outputs carry its scale as their LAST multiplication, so a power-of-two scale changes exponents only.
+template <int V>
+__device__ __forceinline__ void s2_load(const float* __restrict__ p, int k, float (&v)[4]) {
+  if (V == 4) {
+    const float4 t = *reinterpret_cast<const float4*>(p + k);
+    v[0] = t.x, v[1] = t.y, v[2] = t.z, v[3] = t.w;
+  } else {
+    v[0] = p[k];
+  }
+}
+template <int V>
+__device__ __forceinline__ void s2_store(float* __restrict__ p, int k, const float (&v)[4]) {
+  if (V == 4)
+    *reinterpret_cast<float4*>(p + k) = make_float4(v[0], v[1], v[2], v[3]);
+  else
+    p[k] = v[0];
+}
+
+template <int V>
+__device__ __forceinline__ void s2_logits_row(const float* __restrict__ x, const float* __restrict__ t, int tgt,
+                                              float* __restrict__ dx, int n, float inv_bg, float inv_bgc, float S,
+                                              int lane, float* __restrict__ ce_out, float* __restrict__ kl_out,
+                                              int32_t* __restrict__ hit_out) {
+  float mx = -INFINITY, mt = -INFINITY;
+  int am = 0x7fffffff;
+  for (int k = lane * V; k < n; k += 64 * V) {
+    float a[4], b[4];
+    s2_load<V>(x, k, a);
+    s2_load<V>(t, k, b);
+#pragma unroll
+    for (int e = 0; e < V; ++e) {
+      if (a[e] > mx) {
+        mx = a[e];
+        am = k + e;
+      }
+      mt = fmaxf(mt, b[e]);
+    }
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {  // arg-max with ties to the smaller index (clipfs_cross_entropy's rule)
+    const float ov = __shfl_xor(mx, off, 64);
+    const int oi = __shfl_xor(am, off, 64);
+    if (ov > mx || (ov == mx && oi < am)) {
+      mx = ov;
+      am = oi;
+    }
+  }
+  mt = wave_max(mt);
+  float sx = 0.f, st = 0.f;
+  for (int k = lane * V; k < n; k += 64 * V) {
+    float a[4], b[4];
+    s2_load<V>(x, k, a);
+    s2_load<V>(t, k, b);
+#pragma unroll
+    for (int e = 0; e < V; ++e) {
+      sx += __expf(a[e] - mx);
+      st += __expf(b[e] - mt);
+    }
+  }
+  sx = wave_sum(sx);
+  st = wave_sum(st);
+  const float lx = mx + __logf(sx), lt = mt + __logf(st);
+  const bool tgt_ok = tgt >= 0 && tgt < n;  // a label outside [0, C) reads nothing: its row's loss is NaN
+  float kl = 0.f;
+  for (int k = lane * V; k < n; k += 64 * V) {
+    float a[4], b[4], g[4];
+    s2_load<V>(x, k, a);
+    s2_load<V>(t, k, b);
+#pragma unroll
+    for (int e = 0; e < V; ++e) {
+      const float la = a[e] - lx, lb = b[e] - lt;  // log p, log q
+      const float p = __expf(la), q = __expf(lb);
+      kl += q * (lb - la);
+      const float ce = (p - ((k + e) == tgt ? 1.f : 0.f)) * inv_bg;
+      g[e] = S * (ce + (p - q) * inv_bgc);
+    }
+    if (dx) s2_store<V>(dx, k, g);
+  }
+  kl = wave_sum(kl);
+  if (lane == 0) {
+    *ce_out = tgt_ok ? lx - x[tgt] : NAN;
+    *kl_out = kl;
+    *hit_out = (tgt_ok && am == tgt) ? 1 : 0;
+  }
+}
+
+template <int V>
+__device__ __forceinline__ void s2_l1_row(const float* __restrict__ a, const float* __restrict__ b,
+                                          float* __restrict__ da, int n, float g, int lane, float* __restrict__ out) {
+  float acc = 0.f;
+  for (int k = lane * V; k < n; k += 64 * V) {
+    float u[4], w[4], s[4];
+    s2_load<V>(a, k, u);
+    s2_load<V>(b, k, w);
+#pragma unroll
+    for (int e = 0; e < V; ++e) {
+      const float d = u[e] - w[e];
+      acc += fabsf(d);
+      s[e] = d > 0.f ? g : (d < 0.f ? -g : 0.f);  // sign(0) = 0, as l1_loss_kernel
+    }
+    if (da) s2_store<V>(da, k, s);
+  }
+  acc = wave_sum(acc);
+  if (lane == 0) *out = acc;
+}
+
+__global__ __launch_bounds__(256) void stage2_objective_kernel(
+    const float* __restrict__ cosl, const float* __restrict__ zsl, const int64_t* __restrict__ target,
+    const float* __restrict__ img, const float* __restrict__ zs_img, const float* __restrict__ txt,
+    const float* __restrict__ zs_txt, float* __restrict__ dcos, float* __restrict__ dimg, float* __restrict__ dtxt,
+    float* __restrict__ work, int B, int C, int d, int n_loc, float inv_bg, const float* __restrict__ state, int vec_c,
+    int vec_d) {
+  const int lane = threadIdx.x & 63;
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= 2 * B + n_loc) return;
+  const float S = state ? state[CLIPFS_SCALER_SCALE] : 1.f;
+  int32_t* hits = reinterpret_cast<int32_t*>(work + 3 * (size_t)B + n_loc);
+  if (row < B) {
+    const size_t o = (size_t)row * C;
+    const int tgt = (int)target[row];
+    float* dx = dcos ? dcos + o : nullptr;
+    const float inv_bgc = inv_bg / (float)C;
+    if (vec_c)
+      s2_logits_row<4>(cosl + o, zsl + o, tgt, dx, C, inv_bg, inv_bgc, S, lane, work + row, work + B + row, hits + row);
+    else
+      s2_logits_row<1>(cosl + o, zsl + o, tgt, dx, C, inv_bg, inv_bgc, S, lane, work + row, work + B + row, hits + row);
+  } else {
+    const bool image = row < 2 * B;
+    const int r = image ? row - B : row - 2 * B;
+    const size_t o = (size_t)r * d;
+    const float* a = (image ? img : txt) + o;
+    const float* b = (image ? zs_img : zs_txt) + o;
+    float* dst = image ? dimg : dtxt;
+    float* da = dst ? dst + o : nullptr;
+    const float g = S * (image ? inv_bg / (float)d : 1.f / ((float)C * (float)d));
+    float* out = work + 2 * (size_t)B + (image ? r : B + r);
+    if (vec_d)
+      s2_l1_row<4>(a, b, da, d, g, lane, out);
+    else
+      s2_l1_row<1>(a, b, da, d, g, lane, out);
+  }
+}
+
+// The per-row partials in row order (one wave: lane l adds rows l, l + 64, ... in turn, then the fixed DPP tree), each
+// sum scaled to this call's share of its term: terms = {sim_ce, scl_logits, scl_image, scl_text}.
+__global__ __launch_bounds__(64) void stage2_finish_kernel(const float* __restrict__ work, float* __restrict__ terms,
+                                                           int32_t* __restrict__ correct, int B, int C, int d, int n_loc,
+                                                           float inv_bg) {
+  const int lane = threadIdx.x;
+  const int32_t* hits = reinterpret_cast<const int32_t*>(work + 3 * (size_t)B + n_loc);
+  float ce = 0.f, kl = 0.f, li = 0.f, lt = 0.f;
+  int c = 0;
+  for (int r = lane; r < B; r += 64) {
+    ce += work[r];
+    kl += work[B + r];
+    li += work[2 * (size_t)B + r];
+    c += hits[r];
+  }
+  for (int r = lane; r < n_loc; r += 64) lt += work[3 * (size_t)B + r];
+  ce = wave_sum(ce);
+  kl = wave_sum(kl);
+  li = wave_sum(li);
+  lt = wave_sum(lt);
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) c += __shfl_xor(c, off, 64);
+  if (lane == 0) {
+    terms[0] = ce * inv_bg;
+    terms[1] = kl * (inv_bg / (float)C);
+    terms[2] = li * (inv_bg / (float)d);
+    terms[3] = lt / ((float)C * (float)d);
+    if (correct) correct[0] = c;
+  }
+}
+
 }  // namespace clipfs
 
 using namespace clipfs;
@@ -963,5 +1142,38 @@ extern "C" int clipfs_kl_logits(const float* logits, const float* target_logits,
   CLIPFS_REQUIRE(logits && target_logits && loss_rows && rows > 0 && classes > 0, "kl_logits: bad args");
   hipLaunchKernelGGL(kl_logits_kernel, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, logits, target_logits,
                      loss_rows, dlogits, rows, classes, grad_scale);
+  return launch_status();
+}
+
+extern "C" int clipfs_stage2_objective(const float* cos, const float* zs_logits, const int64_t* target, const float* img,
+                                       const float* zs_img, const float* txt, const float* zs_txt, float* dcos,
+                                       float* dimg, float* dtxt, float* work, float* terms, int32_t* correct, int B,
+                                       int C, int d, int C_loc, float inv_global_batch, const float* scaler_state,
+                                       void* stream) {
+  CLIPFS_REQUIRE(B > 0 && C > 0 && d > 0, "stage2_objective: sizes B %d, C %d, d %d must be positive", B, C, d);
+  CLIPFS_REQUIRE(C_loc >= 0 && C_loc <= C, "stage2_objective: C_loc %d outside [0, C = %d]", C_loc, C);
+  CLIPFS_REQUIRE(2 * (long long)B + C_loc <= 0x7ffffff0LL, "stage2_objective: 2 B + C_loc = %lld rows is too many",
+                 2 * (long long)B + C_loc);
+  CLIPFS_REQUIRE(cos && zs_logits && target, "stage2_objective: null pointer (cos, zs_logits or target)");
+  CLIPFS_REQUIRE(img && zs_img, "stage2_objective: null pointer (img or zs_img)");
+  CLIPFS_REQUIRE(C_loc == 0 || (txt && zs_txt), "stage2_objective: null pointer (txt or zs_txt with C_loc %d)", C_loc);
+  CLIPFS_REQUIRE(work && terms, "stage2_objective: null pointer (work or terms)");
+  CLIPFS_REQUIRE(aligned4(cos) && aligned4(zs_logits) && aligned4(img) && aligned4(zs_img) && aligned4(txt) &&
+                     aligned4(zs_txt) && aligned4(dcos) && aligned4(dimg) && aligned4(dtxt) && aligned4(work) &&
+                     aligned4(terms) && aligned4(correct) && (reinterpret_cast<uintptr_t>(target) & 7u) == 0,
+                 "stage2_objective: misaligned pointer");
+  CLIPFS_REQUIRE(!scaler_state || aligned16(scaler_state), "stage2_objective: misaligned scaler state");
+  CLIPFS_REQUIRE(inv_global_batch > 0.f && inv_global_batch <= 3.402823466e38f,
+                 "stage2_objective: inv_global_batch %g must be positive and finite", (double)inv_global_batch);
+  const bool txt16 = C_loc == 0 || (aligned16(txt) && aligned16(zs_txt) && aligned16(dtxt));
+  const int vec_c = (C % 4 == 0 && aligned16(cos) && aligned16(zs_logits) && aligned16(dcos)) ? 1 : 0;
+  const int vec_d = (d % 4 == 0 && aligned16(img) && aligned16(zs_img) && aligned16(dimg) && txt16) ? 1 : 0;
+  const unsigned rows = 2u * (unsigned)B + (unsigned)C_loc;
+  hipLaunchKernelGGL(stage2_objective_kernel, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, cos, zs_logits,
+                     target, img, zs_img, txt, zs_txt, dcos, dimg, dtxt, work, B, C, d, C_loc, inv_global_batch,
+                     scaler_state, vec_c, vec_d);
+  CLIPFS_CHECK(launch_status());
+  hipLaunchKernelGGL(stage2_finish_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, work, terms, correct, B, C, d, C_loc,
+                     inv_global_batch);
   return launch_status();
 }

@@ -693,8 +693,8 @@ class LoRATrainer:
     the all-reduce, so every rank takes the same decision without a further collective.  ``t`` still counts
     ``optimizer_step`` calls; with scaling on, AdamW's step number is ``optimizer_steps``, which leaves skipped steps
     out.  ``loss_scale_value`` / ``skipped_steps`` / ``optimizer_steps`` read the device record back (they synchronise;
-    ``step`` never uses them).  Not covered: ``Stage2Trainer`` and the autograd route of ``encode_image`` /
-    ``encode_text``; bias training still needs a non-fp16 mode."""
+    ``step`` never uses them).  Not covered: the autograd route of ``encode_image`` / ``encode_text`` (stage 2 scales
+    through ``slow_pace.Stage2Trainer(..., fused=True)``); bias training still needs a non-fp16 mode."""
 
     def __init__(self, model, lr: float = 2e-4, weight_decay: float = 1e-2, betas=(0.9, 0.999), eps: float = 1e-8,
                  logit_scale: float = 100.0, prompt_ctx: Optional[nn.Parameter] = None, process_group=None,

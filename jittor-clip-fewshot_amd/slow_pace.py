@@ -10,6 +10,8 @@
     CosineAnnealingLR slow_pace.py:1591      jt.lr_scheduler.CosineAnnealingLR(total_epoch, eta_min=1e-6)
     stage2_loss       slow_pace.py:1622-1688 the stage-2 objective without the MoCo branch
     Stage2Trainer     slow_pace.py:1590-1697 the loop body (prompt ctx + VPT + head, AdamW + cosine LR)
+    FusedStage2Trainer                       the same step on the flat buffer: one objective launch, one AdamW launch,
+                                             data parallelism and loss scaling (``Stage2Trainer(..., fused=True)``)
     load_lora_swa     slow_pace.py:736-816   average of several saved LoRA files
     pre_load_zs       slow_pace.py:1435-1477 cached zero-shot MTA features of the training images
     PromptQueue       README.md:22           queue of learned prompt features blended with the hand-written ones
@@ -29,6 +31,7 @@ from torch import nn
 from clipfs import engine as E
 from clipfs import ops
 from jclip import clip
+from lora_train_vlp import FlatTrainables, LoRATrainer, _check_loss_scale, trainable_biases
 from lora_train_vlp import clip_classifier  # noqa: F401  (re-exported like the reference's copy)
 
 
@@ -493,13 +496,35 @@ class Stage2Trainer:
 
     ``zs_image_features`` [N, d]: cached unit-norm zero-shot image features of the training set (``features_zs1.pkl``
     in the reference), indexed by the loader's sample index; ``zs_text_features`` [C, d]: zero-shot classifier;
-    ``zs_text_feature_sets``: the cached per-template-file classifiers one of which is drawn per step (:1603-1609,1662)."""
+    ``zs_text_feature_sets``: the cached per-template-file classifiers one of which is drawn per step (:1603-1609,1662).
+
+    ``fused=True`` builds a ``FusedStage2Trainer`` instead (same arguments; see there): the step on one flat buffer,
+    with data parallelism (``process_group`` / ``shard_text``) and loss scaling (``loss_scale`` ...).  Without it this
+    class is the autograd-route step it always was, and refuses those arguments."""
+
+    def __new__(cls, *args, **kwargs):
+        if cls is Stage2Trainer:
+            import inspect
+            try:
+                bound = inspect.signature(cls.__init__).bind_partial(None, *args, **kwargs).arguments
+            except TypeError:  # __init__ reports the bad call
+                bound = {}
+            if bound.get("fused", False):
+                cls = FusedStage2Trainer
+        return object.__new__(cls)
 
     def __init__(self, clip_model, prompt_learner: "VLPromptLearner", channel_lp: "Channel_LP",
                  zs_image_features: torch.Tensor, zs_text_features: torch.Tensor,
                  zs_text_feature_sets: Optional[Sequence[torch.Tensor]] = None, lr: float = 2e-4, total_epoch: int = 20,
                  weight_decay: float = 1e-2, betas=(0.9, 0.999), eps: float = 1e-8, moco_model=None,
-                 moco_adapter: Optional["Moco_Adapter"] = None):
+                 moco_adapter: Optional["Moco_Adapter"] = None, fused: bool = False, process_group=None,
+                 shard_text: bool = True, loss_scale=None, growth_factor: float = 2.0, backoff_factor: float = 0.5,
+                 growth_interval: int = 2000, init_scale: float = 65536.0):
+        _check_loss_scale(loss_scale, init_scale, growth_factor, backoff_factor, growth_interval)
+        if loss_scale is not None or (process_group is not None and process_group.size() > 1):
+            raise ValueError("data parallelism (process_group) and loss scaling (loss_scale) belong to the fused step: "
+                             "pass fused=True")
+        self.fused = False
         self.model, self.prompt_learner, self.head = clip_model, prompt_learner, channel_lp
         self.moco_model, self.moco_adapter = moco_model, moco_adapter
         self.text_encoder = TextEncoder(clip_model)
@@ -555,6 +580,273 @@ class Stage2Trainer:
                           self.betas, self.eps, self.wd, 1.0)
         self.lr = self.sched.step()                                               # :1697
         return loss.detach(), terms, cos.detach()
+
+
+class FusedStage2Trainer(Stage2Trainer):
+    """``Stage2Trainer(..., fused=True)``: the same loop body (slow_pace.py:1622-1697, without the MoCo branch) built the
+    way ``LoRATrainer`` builds stage 1 instead of through autograd.
+
+    Trainables: ctx, the VPT tokens, the Channel_LP head (scale1, bias1, fc.weight, fc.bias) and the deep prompts live
+    in ONE flat buffer (``flat``: ``FlatTrainables``) with one gradient buffer and one AdamW moment pair; the head keeps
+    working as a module on its re-homed parameters.  A step is: text tower (side stream) and image tower (main stream)
+    forward, the second no-grad image forward (:1660-1661), ONE objective launch for CE + KL + the two L1 terms and
+    their gradients (clipfs_stage2_objective), the head branch on the existing head kernels, both tower backwards, ONE
+    AdamW launch at the pre-step learning rate, then ``sched.step()`` (:1696-1697).  Dropout seeds are drawn in the
+    unfused order (text, image, second image) and the masks are indexed by global rows, so from the same engine state
+    a fused and an unfused step see the same masks.
+
+    Data parallelism (``process_group``): ``step`` takes this rank's images / targets / sample indices -- rows
+    ``clipfs.dist.block_bounds(global_batch, rank, world)`` of the batch -- and, with ``shard_text``, the rank encodes
+    the classes ``block_bounds(C, rank, world)``.  Collectives per step (``collectives_per_step``): all_gather of the
+    unit class features, all_gather of the head inputs (the second forward's image features with the targets as an
+    extra column), reduce_scatter of the class-feature gradient, all_reduce of the flat gradient: 4; with a replicated
+    text tower (``shard_text=False``) the head all_gather and the all_reduce: 2.  ``logit_normalize`` divides by the
+    standard deviation of the whole [B_g + C, C] matrix, so the head branch is evaluated on the gathered batch, by rank
+    0 alone; the all-reduce then carries exactly the one-process head gradient to every rank.  The per-class text L1
+    gradient is added once: by the class's owner (sharded) or by rank 0 (replicated).
+
+    Loss scaling (``loss_scale`` / ``init_scale`` / ``growth_factor`` / ``backoff_factor`` / ``growth_interval``) is
+    ``LoRATrainer``'s scheme on the same kernels and device record: the objective's and the head's gradients are
+    multiplied by the scale on the device, and the optimiser step is non-finite check (after the all-reduce, so every
+    rank decides alike without a further collective), decision, scaled AdamW.  A skipped step leaves parameters and
+    moments bitwise untouched.  The cosine schedule counts iterations (:1697), so it advances on a skipped step too;
+    AdamW's own step number (``optimizer_steps``) does not.  ``step`` never synchronises with the host;
+    ``loss_scale_value`` / ``skipped_steps`` / ``optimizer_steps`` do.
+
+    ``step`` returns ``(loss, terms, cos)``: device tensors holding this rank's SHARE of the loss and of each term
+    (their sums over the ranks are the values of the whole batch; on one process they are what the unfused step
+    returns), ``lp_ce`` -- and ``scl_text`` with a replicated text tower -- reported by rank 0 only; ``cos`` is the
+    rank's [B_local, C] logit block.
+
+    Refused (ValueError): the MoCo branch, and a model with a trainable LoRA adapter or bias -- the unfused trainer
+    never updates them (the reference freezes them, :1551-1556), so training them here would be another problem.  Not
+    covered beyond that: bias training in the fp16 storage mode (as in stage 1)."""
+
+    def __init__(self, clip_model, prompt_learner: "VLPromptLearner", channel_lp: "Channel_LP",
+                 zs_image_features: torch.Tensor, zs_text_features: torch.Tensor,
+                 zs_text_feature_sets: Optional[Sequence[torch.Tensor]] = None, lr: float = 2e-4, total_epoch: int = 20,
+                 weight_decay: float = 1e-2, betas=(0.9, 0.999), eps: float = 1e-8, moco_model=None,
+                 moco_adapter: Optional["Moco_Adapter"] = None, fused: bool = True, process_group=None,
+                 shard_text: bool = True, loss_scale=None, growth_factor: float = 2.0, backoff_factor: float = 0.5,
+                 growth_interval: int = 2000, init_scale: float = 65536.0):
+        from clipfs import dist as D
+        self.loss_scaling = _check_loss_scale(loss_scale, init_scale, growth_factor, backoff_factor, growth_interval)
+        if not fused:
+            raise ValueError("FusedStage2Trainer is the fused step: pass fused=True (or build a Stage2Trainer)")
+        if moco_model is not None or moco_adapter is not None:
+            raise ValueError("fused=True does not cover the MoCo branch: drop moco_model / moco_adapter or use fused=False")
+        bad = [n for n, p in clip_model.named_parameters() if "lora_" in n and p.requires_grad]
+        if bad:
+            raise ValueError("fused=True trains prompt ctx, VPT / deep prompts and the head only, as the unfused trainer "
+                             f"does; these LoRA adapters are flagged trainable (freeze them): {', '.join(bad[:4])}"
+                             + (f" and {len(bad) - 4} more" if len(bad) > 4 else ""))
+        if clip_model.visual.VPT is not None:
+            clip_model.visual.VPT.requires_grad_(True)
+        for n, p in clip_model.named_parameters():
+            if n.endswith(".VPT_shallow"):
+                p.requires_grad_(True)
+        bad = [n for n, _ in trainable_biases(clip_model)]
+        if bad:
+            raise ValueError("fused=True trains prompt ctx, VPT / deep prompts and the head only, as the unfused trainer "
+                             f"does; these biases are flagged trainable (freeze them): {', '.join(bad[:4])}"
+                             + (f" and {len(bad) - 4} more" if len(bad) > 4 else ""))
+        self.fused = True
+        self.model, self.prompt_learner, self.head = clip_model, prompt_learner, channel_lp
+        self.moco_model = self.moco_adapter = None
+        self.text_encoder = TextEncoder(clip_model)
+        dev = clip_model.device
+        self.zs_img = zs_image_features.to(dev, torch.float32).contiguous()
+        self.zs_txt = zs_text_features.to(dev, torch.float32).contiguous()
+        self.zs_sets = [t.to(dev, torch.float32).contiguous() for t in (zs_text_feature_sets or [zs_text_features])]
+        extra = [prompt_learner.ctx]
+        if clip_model.visual.VPT is not None:
+            extra.append(clip_model.visual.VPT)
+        extra += [channel_lp.scale1, channel_lp.bias1, channel_lp.fc.weight, channel_lp.fc.bias]
+        self.flat = FlatTrainables(clip_model, extra)
+        n_tok = len(extra) - 4
+        self.params: List[nn.Parameter] = extra[:n_tok] + list(self.flat.deep_prompts) + extra[n_tok:]  # each has .grad_slot
+        self.sched = CosineAnnealingLR(lr, total_epoch)
+        self.lr, self.wd, self.betas, self.eps = lr, weight_decay, betas, eps
+        self.t = 0
+        self.pg = process_group
+        self.rank, self.world = D.world_info(process_group)
+        live = self.world > 1 or D.FORCE_COLLECTIVES
+        self.shard_text = shard_text and live
+        self.collectives_per_step = (4 if self.shard_text else 2) if live else 0
+        self.overlap_towers = True  # text tower on the side HIP stream (False serialises, e.g. for per-kernel timing)
+        self._xbuf, self._hbuf = {}, {}
+        self._arange = None
+        self.last_plan = None
+        self.time_collectives = False
+        self._coll_events = []
+        self.scale_state = None
+        if self.loss_scaling == "dynamic":
+            self._scaler_rule = (float(growth_factor), float(backoff_factor), int(growth_interval))
+            self.scale_state = ops.new_scaler_state(float(init_scale), dev)
+        elif self.loss_scaling == "static":
+            self._scaler_rule = (1.0, 1.0, 0)  # never grows, never backs off; still skips a non-finite step
+            self.scale_state = ops.new_scaler_state(float(loss_scale), dev)
+
+    # the device record's host views, the exchange buffers and the collective timers are LoRATrainer's own
+    _scaler_word = LoRATrainer._scaler_word
+    loss_scale_value = LoRATrainer.loss_scale_value
+    skipped_steps = LoRATrainer.skipped_steps
+    optimizer_steps = LoRATrainer.optimizer_steps
+    _exchange_buffers = LoRATrainer._exchange_buffers
+    _side_stream = LoRATrainer._side_stream
+    _timed = LoRATrainer._timed
+    collective_times_ms = LoRATrainer.collective_times_ms
+
+    def loss(self, *args, **kwargs):
+        raise NotImplementedError("the fused trainer evaluates the objective inside step(); use fused=False for loss()")
+
+    def _head_buffers(self, global_batch: int, width: int):
+        """Send block [S, d + 1] (padding rows stay zero) and gathered table [world * S, d + 1] of the head inputs."""
+        from clipfs import dist as D
+        key = (global_batch, width)
+        b = self._hbuf.get(key)
+        if b is None:
+            s = D.block_rows(global_batch, self.world)
+            dev = self.flat.params.device
+            b = dict(S=s, send=torch.zeros(s, width + 1, device=dev), full=torch.empty(self.world * s, width + 1, device=dev))
+            self._hbuf = {key: b}
+        return b
+
+    def _head_branch(self, feats_img: torch.Tensor, target_all: torch.Tensor, lp_txt: torch.Tensor, out: torch.Tensor):
+        """:1663-1669 on the whole batch: ``out`` [1] receives lp_ce and the head's slots of the flat gradient buffer
+        its (scaled) gradient -- the arithmetic of ``_ChannelLPFn`` / ``_LogitNormFn`` / the CE kernel, without autograd."""
+        h = self.head
+        C, d = lp_txt.shape
+        feats = torch.cat((feats_img, lp_txt), dim=0)                                    # :1663
+        if self._arange is None or self._arange.numel() != C:
+            self._arange = torch.arange(C, device=feats.device)
+        tgt = torch.cat((target_all.long(), self._arange))                               # :1667-1668
+        R = feats.shape[0]
+        s1, b1, w, c = h.scale1.data, h.bias1.data, h.fc.weight.data, h.fc.bias.data
+        fp = ops.channel_affine(feats, s1, b1)
+        z = ops.gemm_nt(fp, w, bias=c)                                                   # :1665
+        zn = ops.logit_normalize(z)                                                      # :1666
+        loss_sum, dzn, _ = ops.cross_entropy(zn, tgt, True, 1.0, scale_state=self.scale_state)  # :1669
+        torch.div(loss_sum, float(R), out=out)
+        dz = ops.logit_normalize_bwd(z, dzn)
+        ops.matmul_small(dz, fp, C, d, R, 1, C, d, 1, out=h.fc.weight.grad_slot)         # dW[c,k] = sum_r dz[r,c] f'[r,k]
+        ops.colsum(dz, out=h.fc.bias.grad_slot)
+        dfp = ops.matmul_small(dz, w, R, d, C, C, 1, d, 1)                               # df'[r,k] = sum_c dz[r,c] W[c,k]
+        ops.colsum(dfp, feats, out=h.scale1.grad_slot)
+        ops.colsum(dfp, out=h.bias1.grad_slot)
+
+    def forward_backward(self, images, target, index, template_choice: int = 0, global_batch: Optional[int] = None,
+                         row_offset: int = 0):
+        """Forward and backward of one step for THIS RANK's shard (rows ``row_offset ...`` of the global batch); the
+        gradients land in ``flat.grads`` (scaled, with loss scaling on).  Returns what ``step`` returns."""
+        from clipfs import dist as D
+        m = self.model
+        eng = m.engine
+        dev = m.device
+        ctx = self.prompt_learner.ctx
+        ids = self.prompt_learner.tokenized_prompts
+        live = self.world > 1 or D.FORCE_COLLECTIVES
+        images = images.to(device=dev, dtype=torch.float32)
+        target = target.to(dev).long().contiguous()
+        B = images.shape[0]
+        gb = int(global_batch or B * self.world)
+        C, d = ids.shape[0], m.embed_dim
+        if B < 1:
+            raise ValueError("every rank needs at least one image of the batch")
+        if self.world > 1 and (row_offset, row_offset + B) != D.block_bounds(gb, self.rank, self.world):
+            raise ValueError(f"rank {self.rank} of {self.world} got rows [{row_offset}, {row_offset + B}) of a batch of {gb}: "
+                             "shard the batch with clipfs.dist.block_bounds (the head branch gathers fixed-size blocks)")
+        self.flat.sync_packed()
+        # seeds in the order the unfused trainer draws them: text tower, image tower, second (no-grad) image forward
+        s_txt, s_img, s_lp = (eng.next_seed(), eng.next_seed(), eng.next_seed()) if m.training else (0, 0, 0)
+        c_lo, c_hi = D.block_bounds(C, self.rank, self.world) if self.shard_text else (0, C)
+        n_loc = c_hi - c_lo
+        if self.shard_text and eng.trim_text and m.training and eng.txt.lora_dropout_rate() > 0:
+            raise ValueError("trim_text cannot be combined with a class-sharded text tower and LoRA dropout > 0: the "
+                             "Philox rows would depend on each rank's trimmed length (use trim_text=False or shard_text=False)")
+        xb = self._exchange_buffers(C, d) if self.shard_text else None
+        text_lo, vis_lo = eng.text_plan(True), eng.image_plan()
+        self.last_plan = {"text": text_lo, "vision": vis_lo}
+        main = torch.cuda.current_stream()
+        side = self._side_stream() if self.overlap_towers else main
+        side.wait_stream(main)
+        tctx = txt_loc = tinv = None
+        with torch.cuda.stream(side):
+            if n_loc > 0:
+                emb, tctx = eng.text_forward(ids[c_lo:c_hi], ctx, True, s_txt, row0=c_lo)
+                txt_loc, tinv = ops.l2norm_fwd(emb, save_inv=True, out=None if xb is None else xb["send"][:n_loc])
+        feat, ictx = eng.vit_forward(images, True, s_img, row0=row_offset)
+        img_n, inv = ops.l2norm_fwd(feat, save_inv=True)
+        lp_img, _ = eng.vit_forward(images, False, s_lp, row0=row_offset)                 # :1660-1661
+        zs_img = self.zs_img[index.to(dev)]
+        zs_logits = ops.gemm_nt(zs_img, self.zs_txt, alpha=100.0)                         # :1650
+        out = torch.zeros(5, device=dev)  # sim_ce, scl_logits, scl_image, scl_text, lp_ce: this rank's shares
+        # head branch: on the gathered batch, by rank 0 alone (every rank takes part in the gather)
+        if live:
+            hb = self._head_buffers(gb, d)
+            hb["send"][:B, :d].copy_(lp_img)
+            hb["send"][:B, d].copy_(target)
+            table = self._timed("all_gather_head", lambda: D.allgather_blocks(hb["send"], hb["full"], self.pg))
+            feats_img, target_all = table[:gb, :d], table[:gb, d]
+        else:
+            feats_img, target_all = lp_img, target
+        if self.rank == 0:
+            self._head_branch(feats_img, target_all, self.zs_sets[template_choice % len(self.zs_sets)], out[4:5])
+        main.wait_stream(side)
+        if self.shard_text:
+            full = self._timed("all_gather", lambda: D.allgather_blocks(xb["send"], xb["full"], self.pg))
+            txt_n = full[:C]
+            mine = (txt_loc, self.zs_txt[c_lo:c_hi]) if n_loc > 0 else (None, None)
+        else:
+            txt_n = txt_loc
+            mine = (txt_n, self.zs_txt) if self.rank == 0 else (None, None)   # the text L1 term exists once per step
+        cos = ops.gemm_nt(img_n, txt_n, alpha=100.0)                                      # :1640
+        self.last_features = (img_n, txt_n)
+        _, _, dcos, dimg, dtxt = ops.stage2_objective(cos, zs_logits, target, img_n, zs_img, mine[0], mine[1], C, 1.0 / gb,
+                                                      True, self.scale_state, terms=out)
+        zeros = eng._class_rows(max(B, C), dev)
+        if vis_lo is not None:
+            d_img_n = ops.matmul_small(dcos, txt_n, B, d, C, C, 1, d, 1, 100.0)
+            ops.add_rows_(d_img_n, dimg, zeros)
+        if text_lo is not None:
+            d_txt = ops.matmul_small(dcos, img_n, C, d, B, 1, C, d, 1, 100.0, out=None if xb is None else xb["dfull"][:C])
+            if self.shard_text:  # every rank needs the batch-total gradient of ITS classes only
+                got = self._timed("reduce_scatter", lambda: D.reduce_scatter_blocks(xb["dfull"], xb["dmine"], self.pg))
+                d_txt = got[:n_loc]
+            if dtxt is not None:
+                ops.add_rows_(d_txt, dtxt, zeros)
+            side.wait_stream(main)
+            with torch.cuda.stream(side):
+                if n_loc > 0:
+                    eng.text_backward(tctx, ops.l2norm_bwd(d_txt, txt_loc, tinv), ctx.grad_slot)
+        if vis_lo is not None:
+            eng.vit_backward(ictx, ops.l2norm_bwd(d_img_n, img_n, inv))
+        main.wait_stream(side)
+        terms = {"sim_ce": out[0], "scl_text": out[3], "scl_image": out[2], "scl_logits": out[1], "lp_ce": out[4]}
+        return out.sum(), terms, cos
+
+    def optimizer_step(self):
+        from clipfs import dist as D
+        if self.world > 1 or D.FORCE_COLLECTIVES:
+            self._timed("all_reduce", lambda: D.allreduce_sum_(self.flat.grads, self.pg))
+        self.t += 1
+        if self.scale_state is not None:
+            growth, backoff, interval = self._scaler_rule
+            ops.grads_nonfinite(self.flat.grads, self.scale_state)
+            ops.scaler_decide(self.scale_state, self.lr, self.betas, growth, backoff, interval)
+            ops.adamw_scaled(self.flat.params, self.flat.grads, self.flat.m, self.flat.v, self.scale_state, self.lr,
+                             self.betas, self.eps, self.wd)
+        else:
+            ops.adamw(self.flat.params, self.flat.grads, self.flat.m, self.flat.v, self.t, self.lr, self.betas, self.eps,
+                      self.wd, 1.0)
+        self.lr = self.sched.step()                                                       # :1697 (counts iterations)
+
+    def step(self, images, target, index, template_choice: int = 0, global_batch: Optional[int] = None,
+             row_offset: int = 0):
+        self.flat.zero_grad()
+        out = self.forward_backward(images, target, index, template_choice, global_batch, row_offset)
+        self.optimizer_step()
+        return out
 
 
 @torch.no_grad()
