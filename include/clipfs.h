@@ -293,7 +293,7 @@ int clipfs_lora_keep_bits_ok(int width, int segw, int r, int nseg);
  *   dA[s*r+j, k]  += sum_m dt[m, s*r+j] * drop_s(x)[m,k]
  *   dx[m,k]       += sum_{s,j} dt[m, s*r+j] * A[s*r+j,k] * dropscale_s(m,k)   (if dx != NULL)
  * work: caller scratch, >= clipfs_lora_bwd_work_floats(...) floats.
- * Ranks: 1 ... 64 on the matrix-core kernels (width % 128 == 0, segw == width, nseg 1 or 3); elsewhere the
+ * Ranks: 1 ... 64 on the matrix-core kernels (width % 128 == 0, segw % 64 == 0, nseg 1 or 3); elsewhere the
  * one-wave-per-row kernels take r = 1, 2, 4, 8, 16 and any other rank is CLIPFS_EINVAL naming the rank and the width.
  * Frozen adapter: dA == dB == NULL computes dt and the dx contribution only -- no dB / dA partial products or slice
  * reductions are launched, and dt / dx are bitwise those of the call with slots.  With dx NULL as well only dt is
@@ -303,6 +303,21 @@ int clipfs_lora_bwd(const float* dy, const float* x, const float* t, const float
                     float* dt, float* dA, float* dB, float* dx, int rows, int width, int segw, int r,
                     int nseg, unsigned seg_mask, float scale, float p, uint64_t seed, uint32_t stream_base,
                     uint32_t drow0, const void* keep_bits, float* work, void* stream);
+/* Rectangular adapters (nseg == 1 only): clipfs_lora_bwd also takes segw != width -- width the adapter's input width,
+ * segw its output width (dy [rows, segw], B [segw, r], A [r, width]; both multiples of 4) -- the MLP linears' d -> 4d and
+ * 4d -> d.  Matrix-core kernels where width % 128 == 0 and segw % 64 == 0 (ranks 1 ... 64), the one-wave-per-row kernels
+ * elsewhere (r = 1, 2, 4, 8, 16).  Their work buffer is sized by clipfs_lora_bwd_work_floats2, which equals
+ * clipfs_lora_bwd_work_floats for segw == width.  clipfs_lora_down takes widths up to 4096 (c_proj's input).
+ * clipfs_lora_bwd_xact is the one-segment call (seg_mask 1, no keep bits) with a switch on how x is read: x_act = 1 says x
+ * holds a pre-activation u and the adapter's input was QuickGELU(u), which the dA product applies as it loads x -- the
+ * c_proj adapter, whose forward saves u alone; dx then receives the gradient wrt QuickGELU(u).  x_act = 0 reads x as is.
+ * clipfs_gelu_bwd_inplace: dg[i] *= dQuickGELU(u[i]) for i < n (16-byte accesses, any n; pointers 16-byte aligned) -- the
+ * step that follows when the c_proj dgrad GEMM ran without act = 2 so that the adapter's term could be added first. */
+size_t clipfs_lora_bwd_work_floats2(int rows, int width, int segw, int r, int nseg);
+int clipfs_lora_bwd_xact(const float* dy, const float* x, const float* t, const float* A, const float* B, float* dt,
+                         float* dA, float* dB, float* dx, int rows, int width, int segw, int r, float scale, float p,
+                         uint64_t seed, uint32_t stream_base, uint32_t drow0, int x_act, float* work, void* stream);
+int clipfs_gelu_bwd_inplace(float* dg, const float* u, size_t n, void* stream);
 /* The same with dy given as its f16 image [rows, nseg*segw] (fp16 storage mode: the tensor the dgrad GEMM consumes), so
  * that the two passes over dy move half the bytes and the fp32 dy need not exist.  Matrix-core kernels only:
  * clipfs_lora_bwd_f16dy_ok(width, segw, r, nseg) != 0 says a shape is covered (r <= 64, width % 128 == 0, ...). */
@@ -556,7 +571,7 @@ typedef struct clipfs_block {
   /* LoRA on q,k,v (stacked: A [3r,d], B [3d,r]) and on the out projection (A [r,d], B [d,r]) */
   const float *lora_a_qkv, *lora_b_qkv, *lora_a_o, *lora_b_o;
   float *g_lora_a_qkv, *g_lora_b_qkv, *g_lora_a_o, *g_lora_b_o; /* gradient slots (accumulated into) */
-  unsigned lora_mask;                   /* bit0 q, bit1 k, bit2 v, bit3 o */
+  unsigned lora_mask;                   /* bit0 q, bit1 k, bit2 v, bit3 o, bit4 c_fc, bit5 c_proj (lora_a_fc ... below) */
   /* optional 16-bit copies of the four weights and of their transposed copies (clipfs_split_bf16 /
    * clipfs_convert_f16, format in clipfs_tower.weight_format); when present the tower's GEMMs use the
    * bf16 x 3 or f16 MFMA kernel, otherwise the exact fp32 MFMA kernel */
@@ -565,6 +580,20 @@ typedef struct clipfs_block {
    * LayerNorm biases, the q / k / v segments of the packed in-projection bias, out projection, c_fc, c_proj.
    * Refused in the fp16 storage mode (weight_format 2), which keeps dqkv and the MLP gradient as f16 images only. */
   float *g_ln1_b, *g_ln2_b, *g_b_q, *g_b_k, *g_b_v, *g_b_o, *g_b_fc, *g_b_pr;
+  /* LoRA on the MLP linears (LinearLoRA.execute, lora_train_vlp.py:296-306, on jclip/model.py:34-39), switched on by
+   * lora_mask bit 4 (c_fc: A [r, d], B [4d, r]) and bit 5 (c_proj: A [r, 4d], B [d, r]) with the tower's r / scale / dropout:
+   *     u = LN2(x_mid) Wfc^T + b_fc + s * (drop(LN2(x_mid)) A_fc^T) B_fc^T         (u is the saved pre-activation)
+   *     x_out = x_mid + g Wpr^T + b_pr + s * (drop(g) A_pr^T) B_pr^T,  g = QuickGELU(u)
+   * Dropout streams: dropout_stream0 + 500 + 2 * l (c_fc) and + 1 (c_proj), element (global token row, column).  The g_
+   * slots are accumulated into; both NULL = a frozen adapter (only its input-gradient term is computed), exactly one NULL
+   * is CLIPFS_EINVAL.  A tower with such an adapter keeps two more [rows, r] tensors per saved record, runs every block on
+   * the dense rows (clipfs_tower_pack_mode 0; clipfs_tower_rows_mode 0 when the LAST block has one) and is refused in the
+   * fp16 storage mode (h2, g and du exist only as f16 images there), the message naming the block and c_fc / c_proj.
+   * Without one, every layout and launch is what it was before these fields existed.  The fields sit in front of the deep
+   * prompt's, which stay the tail of the struct; sizeof(clipfs_block) grows either way, so a caller built against the
+   * earlier layout is rejected by the block_size check instead of being read at shifted offsets. */
+  const float *lora_a_fc, *lora_b_fc, *lora_a_pr, *lora_b_pr;
+  float *g_lora_a_fc, *g_lora_b_fc, *g_lora_a_pr, *g_lora_b_pr;
   /* deep prompt (IVLP vision_depth / language_depth, reference jclip/model1.py:95-116): every forward writes `prompt`
    * [prompt_rows, width] over the rows prompt_first ... prompt_first + prompt_rows - 1 of each sequence of the block's
    * input, before LN1 (rows past the sequence -- a trimmed or packed caption -- are skipped: clipfs_prompt_put); every

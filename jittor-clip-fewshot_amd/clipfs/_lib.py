@@ -55,6 +55,8 @@ class Block(C.Structure):
         "g_lora_a_qkv", "g_lora_b_qkv", "g_lora_a_o", "g_lora_b_o")] + [("lora_mask", C.c_uint)] + [
         (n, C.c_void_p) for n in ("w_qkv_p", "w_o_p", "w_fc_p", "w_pr_p", "w_qkv_t_p", "w_o_t_p", "w_fc_t_p", "w_pr_t_p",
                                   "g_ln1_b", "g_ln2_b", "g_b_q", "g_b_k", "g_b_v", "g_b_o", "g_b_fc", "g_b_pr",
+                                  "lora_a_fc", "lora_b_fc", "lora_a_pr", "lora_b_pr",
+                                  "g_lora_a_fc", "g_lora_b_fc", "g_lora_a_pr", "g_lora_b_pr",
                                   "prompt", "g_prompt")] + [("prompt_first", C.c_int), ("prompt_rows", C.c_int)]
 
 
@@ -108,6 +110,9 @@ SIGNATURES = {
     "clipfs_lora_down": (_i, [_p, _p, _p, _i, _i, _i, _i, _u, _f, _u64, _u32, _u32, _p, _p]),
     "clipfs_lora_bwd_work_floats": (_sz, [_i, _i, _i, _i]),
     "clipfs_lora_bwd": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _u, _f, _f, _u64, _u32, _u32, _p, _p, _p]),
+    "clipfs_lora_bwd_work_floats2": (_sz, [_i, _i, _i, _i, _i]),
+    "clipfs_lora_bwd_xact": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _f, _f, _u64, _u32, _u32, _i, _p, _p]),
+    "clipfs_gelu_bwd_inplace": (_i, [_p, _p, _sz, _p]),
     "clipfs_lora_bwd_f16dy_ok": (_i, [_i, _i, _i, _i]),
     "clipfs_lora_bwd_f16dy": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _u, _f, _f, _u64, _u32, _u32, _p, _p, _p]),
     "clipfs_vit_fill_special": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _p]),

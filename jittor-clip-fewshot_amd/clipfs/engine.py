@@ -39,6 +39,19 @@ def _lora_trains(a, where: str) -> bool:
     return flags == {True}
 
 
+def _mlp_lora_trains(m, where: str) -> bool:
+    """Whether one MLP adapter (a ``LinearLoRA`` on ``mlp.c_fc`` / ``mlp.c_proj``) trains; A and B go together."""
+    if m.w_lora_A.requires_grad != m.w_lora_B.requires_grad:
+        raise ValueError(f"{where}: one of w_lora_A / w_lora_B is frozen and the other trainable; freeze or train both")
+    return bool(m.w_lora_A.requires_grad)
+
+
+def _mlp_adapters(blk):
+    """[(token, LinearLoRA)] of the block's adapted MLP linears (lora_train_vlp.mlp_adapters, without the import cycle)."""
+    return [(tok, getattr(blk.mlp, tok)) for tok in ("c_fc", "c_proj")
+            if getattr(getattr(blk.mlp, tok), "is_mlp_lora", False) and getattr(blk.mlp, tok).r > 0]
+
+
 def _blk_biases(blk) -> List[torch.nn.Parameter]:
     """The bias parameters of one block (LoRA blocks: the q / k / v views of the packed in-projection bias)."""
     a = blk.attn
@@ -104,6 +117,8 @@ class _TowerRT:
         """Whether block i gets any gradient slot in ``descriptor`` (a trainable adapter, bias or deep prompt)."""
         a = blk.attn
         if getattr(a, "is_lora_mha", False) and a.r > 0 and _lora_trains(a, f"{self.name} block {i}"):
+            return True
+        if any(_mlp_lora_trains(m, f"{self.name} block {i} mlp.{tok}") for tok, m in _mlp_adapters(blk)):
             return True
         if _bias_slot(getattr(blk, "VPT_shallow", None)) is not None:
             return True
@@ -197,6 +212,23 @@ class _TowerRT:
                     b.lora_a_o, b.lora_b_o = _ptr(a.lora_A_o), _ptr(a.lora_B_o)
                     if trains:
                         b.g_lora_a_o, b.g_lora_b_o = _ptr(a.grad_A_o), _ptr(a.grad_B_o)
+            for tok, m in _mlp_adapters(blk):  # lora_mask bits 4 (c_fc) and 5 (c_proj)
+                if r and (m.r != r or abs(m.scaling - scale) > 0 or abs(m.dropout_rate - p) > 0):
+                    raise ValueError("all LoRA layers of one tower must share r / alpha / dropout")
+                r, scale, p = m.r, float(m.scaling), float(m.dropout_rate)
+                trains = _mlp_lora_trains(m, f"{self.name} block {i} mlp.{tok}")
+                for q in (m.w_lora_A, m.w_lora_B):
+                    if not (q.dtype == torch.float32 and q.is_contiguous() and q.data_ptr() % 16 == 0):
+                        raise ValueError(f"{self.name} block {i} mlp.{tok}: adapter tensors must be contiguous fp32, 16-byte aligned")
+                    if trains:
+                        _ensure_slot(q)
+                ga, gb = (_ptr(m.w_lora_A.grad_slot), _ptr(m.w_lora_B.grad_slot)) if trains else (None, None)
+                if tok == "c_fc":
+                    b.lora_mask |= 16
+                    b.lora_a_fc, b.lora_b_fc, b.g_lora_a_fc, b.g_lora_b_fc = _ptr(m.w_lora_A), _ptr(m.w_lora_B), ga, gb
+                else:
+                    b.lora_mask |= 32
+                    b.lora_a_pr, b.lora_b_pr, b.g_lora_a_pr, b.g_lora_b_pr = _ptr(m.w_lora_A), _ptr(m.w_lora_B), ga, gb
         t = _lib.new_tower()
         t.width, t.heads, t.layers, t.seq, t.causal = (self.width, self.heads, self.layers, seq or self.seq,
                                                        int(self.causal))
@@ -214,11 +246,12 @@ class _TowerRT:
         return t
 
     def lora_dropout_rate(self) -> float:
-        return max((float(b.attn.dropout_rate) for b in self.mod.resblocks
-                    if getattr(b.attn, "is_lora_mha", False) and b.attn.r > 0), default=0.0)
+        return max([float(b.attn.dropout_rate) for b in self.mod.resblocks
+                    if getattr(b.attn, "is_lora_mha", False) and b.attn.r > 0]
+                   + [float(m.dropout_rate) for b in self.mod.resblocks for _, m in _mlp_adapters(b)], default=0.0)
 
     def has_lora(self) -> bool:
-        return any(getattr(b.attn, "is_lora_mha", False) and b.attn.r > 0 for b in self.mod.resblocks)
+        return any((getattr(b.attn, "is_lora_mha", False) and b.attn.r > 0) or _mlp_adapters(b) for b in self.mod.resblocks)
 
     # -- workspaces -----------------------------------------------------------------------------
     def buffer(self, kind: str, n_floats: int, device) -> torch.Tensor:
@@ -623,6 +656,11 @@ def _tower_trainables(tower_mod) -> List[Tuple[torch.nn.Parameter, torch.Tensor]
         a = blk.attn
         if getattr(a, "is_lora_mha", False):
             out.extend(a.trainable_pairs())
+        for _, m in _mlp_adapters(blk):
+            for q in (m.w_lora_A, m.w_lora_B):
+                if q.requires_grad:
+                    _ensure_slot(q)
+                    out.append((q, q.grad_slot))
     return out
 
 

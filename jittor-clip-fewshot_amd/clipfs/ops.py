@@ -296,6 +296,30 @@ def lora_bwd(dy, x, t, A, B, dA, dB, *, dx=None, scale, p=0.0, seed=0, stream_ba
     return dt
 
 
+def lora_bwd_rect(dy, x, t, A, B, dA, dB, *, dx=None, scale, p=0.0, seed=0, stream_base=0, row0=0, x_act=False):
+    """Backward of ONE adapter whose output width (``dy`` [rows, out]) may differ from its input width (``x`` [rows, in]):
+    the MLP linears' adapters (clipfs_lora_bwd_xact).  ``x_act``: ``x`` holds the pre-activation u and the adapter read
+    QuickGELU(u) -- applied as x is loaded, and ``dx`` then receives the gradient wrt QuickGELU(u).  dA / dB None = frozen.
+    Returns dt [rows, r]."""
+    rows, width = x.shape
+    segw = dy.shape[1]
+    r = B.shape[1]
+    lib = _lib.load()
+    work = torch.empty(lib.clipfs_lora_bwd_work_floats2(rows, width, segw, r, 1), device=x.device, dtype=torch.float32)
+    dt = torch.empty(rows, r, device=x.device, dtype=torch.float32)
+    check(lib.clipfs_lora_bwd_xact(_p(_f32(dy)), _p(_f32(x)), _p(_f32(t)), _p(_f32(A)), _p(_f32(B)), _p(dt), _p(dA), _p(dB),
+                                   _p(dx), rows, width, segw, r, scale, p, seed, stream_base, row0, int(bool(x_act)), _p(work),
+                                   _stream()), "lora_bwd_xact")
+    return dt
+
+
+def gelu_bwd_inplace(dg, u):
+    """dg *= QuickGELU'(u), in place (clipfs_gelu_bwd_inplace)."""
+    assert dg.is_contiguous() and u.is_contiguous() and dg.numel() == u.numel()
+    check(_lib.load().clipfs_gelu_bwd_inplace(_p(_f32(dg)), _p(_f32(u)), dg.numel(), _stream()), "gelu_bwd_inplace")
+    return dg
+
+
 def vit_fill_special(x, class_emb, pos, vpt, batch, tokens, n_patch):
     n_vpt = 0 if vpt is None else vpt.shape[0]
     check(_lib.load().clipfs_vit_fill_special(_p(x), _p(class_emb), _p(pos), _p(vpt), batch, tokens, n_patch, n_vpt,

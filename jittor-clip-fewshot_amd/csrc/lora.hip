@@ -9,7 +9,8 @@
 
 namespace clipfs {
 
-constexpr int LORA_MAX_CHUNKS = 8;  // width <= 2048
+constexpr int LORA_MAX_CHUNKS = 8;  // width <= 2048 (one-wave-per-row kernel; the matrix-core kernel has no such bound)
+constexpr int LORA_MAX_WIDTH = 4096;  // c_proj's input, 4 d
 constexpr int LORA_MAX_OUT = 64;    // nseg * r of the one-wave-per-row kernel
 constexpr int LORA_MFMA_MAX_OUT = 192;  // nseg * r of the matrix-core kernels (3 segments x r <= 64)
 
@@ -135,7 +136,9 @@ __global__ __launch_bounds__(256) void lora_db_partial_kernel(const float* __res
 
 // dA partials: thread = 4 consecutive columns k of x; acc[s][j] over the slice's rows, dropout
 // multipliers regenerated from the Philox stream (never stored).  One wave per (256 columns, row slice).
-template <int R, int NSEG>
+// XACT: x holds a pre-activation u and the adapter's input is QuickGELU(u), applied as it is loaded (the c_proj adapter:
+// only u is saved, g = QuickGELU(u) is never materialised).
+template <int R, int NSEG, bool XACT = false>
 __global__ __launch_bounds__(64) void lora_da_partial_kernel(const float* __restrict__ x, const float* __restrict__ dt,
                                                              float* __restrict__ part, int rows, int width,
                                                              unsigned seg_mask, float p, uint64_t seed,
@@ -154,7 +157,8 @@ __global__ __launch_bounds__(64) void lora_da_partial_kernel(const float* __rest
     for (int j = 0; j < R; ++j) acc[s][j] = make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll 2
   for (int m = m0; m < m1; ++m) {
-    const float4 xv = *reinterpret_cast<const float4*>(x + (size_t)m * width + 4 * c4);
+    float4 xv = *reinterpret_cast<const float4*>(x + (size_t)m * width + 4 * c4);
+    if (XACT) xv = make_float4(quick_gelu(xv.x), quick_gelu(xv.y), quick_gelu(xv.z), quick_gelu(xv.w));
     const float* dr = dt + (size_t)m * (NSEG * R);
 #pragma unroll
     for (int s = 0; s < NSEG; ++s) {
@@ -264,6 +268,24 @@ __global__ __launch_bounds__(256) void lora_dx_kernel(const float* __restrict__ 
   }
 }
 
+// dg[i] *= QuickGELU'(u[i]), in place: the c_proj dgrad of a block with a c_proj adapter runs without the activation in
+// its epilogue (the adapter's term is added to dg first).  16-byte accesses over n4 float4s, grid-stride; the up to 3
+// trailing floats go to the first threads of block 0.
+__global__ __launch_bounds__(256) void gelu_bwd_inplace_kernel(float* __restrict__ dg, const float* __restrict__ u, size_t n4,
+                                                               size_t n) {
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
+    float4 g = reinterpret_cast<float4*>(dg)[i];
+    const float4 uv = reinterpret_cast<const float4*>(u)[i];
+    g.x *= quick_gelu_grad(uv.x);
+    g.y *= quick_gelu_grad(uv.y);
+    g.z *= quick_gelu_grad(uv.z);
+    g.w *= quick_gelu_grad(uv.w);
+    reinterpret_cast<float4*>(dg)[i] = g;
+  }
+  const size_t tail = 4 * n4 + threadIdx.x;
+  if (blockIdx.x == 0 && threadIdx.x < 3 && tail < n) dg[tail] *= quick_gelu_grad(u[tail]);
+}
+
 // rows per reduction slice: 64 for large row counts, smaller when there are few rows so that the partial
 // kernels still put >= ~1000 waves on the chip (per-rank batches of 32 images: M = 1600)
 static inline int lora_slice_rows(int rows) {
@@ -286,6 +308,11 @@ int lora_bwd_mfma(const float* dy, const float* x, const float* t, const float* 
                   float* dB, float* dx, int rows, int width, int segw, int r, int nseg, unsigned seg_mask, float scale,
                   float p, uint64_t seed, uint32_t stream_base, uint32_t drow0, const uint16_t* keep_bits, float* work,
                   hipStream_t st, lora_reduce2_fn reduce);
+
+// nseg == 1 with the adapter's input given as its pre-activation (x_act: QuickGELU applied as x is loaded for dA)
+int lora_bwd_mfma_xact(const float* dy, const float* x, const float* t, const float* A, const float* B, float* dt, float* dA,
+                       float* dB, float* dx, int rows, int width, int segw, int r, unsigned seg_mask, float scale, float p,
+                       uint64_t seed, uint32_t stream_base, uint32_t drow0, float* work, hipStream_t st, lora_reduce2_fn reduce);
 
 // the dB and dA slice sums of one adapter backward in one launch (blocks [0, nblk0) take the first)
 static void launch_reduce_slices2(const float* part0, float* out0, size_t n0, int slices0, float scale0, const float* part1,
@@ -316,8 +343,10 @@ extern "C" int clipfs_lora_down(const float* x, const float* A, float* t, int ro
   CLIPFS_REQUIRE(x && A && t, "lora_down: null pointer");
   CLIPFS_REQUIRE(!keep_bits || clipfs_lora_keep_bits_ok(width, width, r, nseg),
                  "lora_down: keep bits are recorded by the matrix-core kernels only (width %d r %d nseg %d)", width, r, nseg);
-  CLIPFS_REQUIRE(rows > 0 && width > 0 && (width & 3) == 0 && width <= 256 * LORA_MAX_CHUNKS, "lora_down: width %d unsupported", width);
+  CLIPFS_REQUIRE(rows > 0 && width > 0 && (width & 3) == 0 && width <= LORA_MAX_WIDTH, "lora_down: width %d unsupported", width);
   const bool mfma = use_lora_mfma() && lora_mfma_ok(width, width, r, nseg);
+  // widths above 2048 (the c_proj adapter's input) run on the matrix-core kernel only
+  CLIPFS_REQUIRE(mfma || width <= 256 * LORA_MAX_CHUNKS, "lora_down: width %d needs the matrix-core kernel (width %% 128 == 0)", width);
   CLIPFS_REQUIRE(r > 0 && r <= 64 && nseg > 0 && nseg <= 4 && nseg * r <= (mfma ? LORA_MFMA_MAX_OUT : LORA_MAX_OUT),
                  "lora_down: rank %d x %d segments unsupported at width %d (%d outputs per row at most%s)", r, nseg, width,
                  mfma ? LORA_MFMA_MAX_OUT : LORA_MAX_OUT, mfma ? "" : "; more need width % 128 == 0");
@@ -337,12 +366,28 @@ extern "C" size_t clipfs_lora_bwd_work_floats(int rows, int width, int r, int ns
   if (r > 16) return lora_mfma_work_floats(rows, width, width, r, nseg) + 64;
   const int sr = lora_slice_rows(rows);
   const size_t slices = (size_t)(rows + sr - 1) / sr;
-  // dB partials: slices * (nseg*segw) * r with segw <= 4*width (MLP never adapted; q/k/v/o segw == width)
+  // dB partials: slices * (nseg*segw) * r with segw == width (q/k/v/o; the MLP adapters: clipfs_lora_bwd_work_floats2)
   // dA partials: slices * nseg * r * width
   return slices * (size_t)nseg * r * width * 2 + 64;
 }
 
-template <int R>
+// The same bound for an adapter whose output width segw differs from its input width (nseg == 1: the MLP linears):
+// dB partials slices * segw * r, dA partials slices * r * width.  segw == width returns clipfs_lora_bwd_work_floats.
+extern "C" size_t clipfs_lora_bwd_work_floats2(int rows, int width, int segw, int r, int nseg) {
+  if (segw == width) return clipfs_lora_bwd_work_floats(rows, width, r, nseg);
+  if (rows <= 0 || width <= 0 || segw <= 0 || r <= 0 || nseg != 1) return 0;
+  size_t need = 0;
+  if (lora_mfma_ok(width, segw, r, nseg)) need = lora_mfma_work_floats(rows, width, segw, r, nseg);
+  if (r <= 16) {  // either family may take the call (CLIPFS_LORA_MFMA)
+    const int sr = lora_slice_rows(rows);
+    const size_t slices = (size_t)(rows + sr - 1) / sr;
+    const size_t scalar = ((slices * (size_t)segw * r + 3) & ~(size_t)3) + slices * (size_t)r * width;
+    need = scalar > need ? scalar : need;
+  }
+  return need + 64;
+}
+
+template <int R, bool XACT = false>
 static int lora_bwd_r(const float* dy, const float* x, const float* t, const float* A, const float* B, float* dt,
                       float* dA, float* dB, float* dx, int rows, int width, int segw, int nseg, unsigned seg_mask,
                       float scale, float p, uint64_t seed, uint32_t stream_base, uint32_t drow0, float* work, hipStream_t st) {
@@ -363,9 +408,12 @@ static int lora_bwd_r(const float* dy, const float* x, const float* t, const flo
                        scale);
     CLIPFS_CHECK(launch_status());
     // dA
-    float* part_a = work + (size_t)slices * nb;
+    float* part_a = work + (((size_t)slices * nb + 3) & ~(size_t)3);  // (nb is a multiple of 4 wherever segw == width)
     const dim3 ga((width / 4 + 63) / 64, slices);
-    if (nseg == 1)
+    if (nseg == 1 && XACT)
+      hipLaunchKernelGGL((lora_da_partial_kernel<R, 1, true>), ga, dim3(64), 0, st, x, dt, part_a, rows, width, seg_mask, p,
+                         seed, stream_base, drow0, sr);
+    else if (nseg == 1)
       hipLaunchKernelGGL((lora_da_partial_kernel<R, 1>), ga, dim3(64), 0, st, x, dt, part_a, rows, width, seg_mask, p,
                          seed, stream_base, drow0, sr);
     else
@@ -385,24 +433,35 @@ static int lora_bwd_r(const float* dy, const float* x, const float* t, const flo
   return CLIPFS_OK;
 }
 
-extern "C" int clipfs_lora_bwd(const float* dy, const float* x, const float* t, const float* A, const float* B,
-                               float* dt, float* dA, float* dB, float* dx, int rows, int width, int segw, int r,
-                               int nseg, unsigned seg_mask, float scale, float p, uint64_t seed, uint32_t stream_base, uint32_t drow0,
-                               const void* keep_bits, float* work, void* stream) {
+static int lora_bwd_impl(const float* dy, const float* x, const float* t, const float* A, const float* B, float* dt, float* dA,
+                         float* dB, float* dx, int rows, int width, int segw, int r, int nseg, unsigned seg_mask, float scale,
+                         float p, uint64_t seed, uint32_t stream_base, uint32_t drow0, const void* keep_bits, int x_act,
+                         float* work, void* stream) {
   CLIPFS_REQUIRE((dA == nullptr) == (dB == nullptr), "lora_bwd: dA and dB must both be given or both NULL (frozen adapter)");
   CLIPFS_REQUIRE(dy && x && t && A && B && dt && work, "lora_bwd: null pointer");
   CLIPFS_REQUIRE(nseg == 1 || nseg == 3, "lora_bwd: nseg %d unsupported (1 or 3)", nseg);
   CLIPFS_REQUIRE(!keep_bits || (clipfs_lora_keep_bits_ok(width, segw, r, nseg) && aligned16(dy) && aligned16(dx ? dx : x)),
                  "lora_bwd: keep bits are read by the matrix-core kernels only (width %d r %d nseg %d)", width, r, nseg);
-  CLIPFS_REQUIRE(rows > 0 && width > 0 && (width & 3) == 0 && segw == width, "lora_bwd: width %d segw %d unsupported (segw must equal width)", width, segw);
+  // segw != width: one segment whose output width differs from its input width (the MLP linears: d -> 4d, 4d -> d)
+  CLIPFS_REQUIRE(rows > 0 && width > 0 && (width & 3) == 0 && (segw == width || (nseg == 1 && segw > 0 && (segw & 3) == 0)),
+                 "lora_bwd: width %d segw %d nseg %d unsupported (segw must equal width unless nseg is 1; both multiples of 4)",
+                 width, segw, nseg);
+  CLIPFS_REQUIRE(!x_act || (nseg == 1 && !keep_bits), "lora_bwd: x_act needs nseg 1 and no keep bits");
+  CLIPFS_REQUIRE(segw == width || aligned16(dy), "lora_bwd: misaligned dy");
   CLIPFS_REQUIRE(p >= 0.f && p < 1.f, "lora_bwd: dropout p out of range");
   CLIPFS_REQUIRE(aligned16(x) && aligned16(A) && aligned16(work) && (!dx || aligned16(dx)), "lora_bwd: misaligned pointer");
   hipStream_t st = (hipStream_t)stream;
+  if (x_act && use_lora_mfma() && lora_mfma_ok(width, segw, r, nseg) && aligned16(dy) && aligned16(dx ? dx : x))
+    return lora_bwd_mfma_xact(dy, x, t, A, B, dt, dA, dB, dx, rows, width, segw, r, seg_mask, scale, p, seed, stream_base, drow0,
+                              work, st, launch_reduce_slices2);
   if (use_lora_mfma() && lora_mfma_ok(width, segw, r, nseg) && aligned16(dy) && aligned16(dx ? dx : x))
     return lora_bwd_mfma(dy, x, t, A, B, dt, dA, dB, dx, rows, width, segw, r, nseg, seg_mask, scale, p, seed, stream_base, drow0,
                          reinterpret_cast<const uint16_t*>(keep_bits), work, st, launch_reduce_slices2);
 #define CLIPFS_LORA_CASE(RR)                                                                                       \
   case RR:                                                                                                         \
+    if (x_act)                                                                                                     \
+      return lora_bwd_r<RR, true>(dy, x, t, A, B, dt, dA, dB, dx, rows, width, segw, nseg, seg_mask, scale, p,     \
+                                  seed, stream_base, drow0, work, st);                                             \
     return lora_bwd_r<RR>(dy, x, t, A, B, dt, dA, dB, dx, rows, width, segw, nseg, seg_mask, scale, p, seed,       \
                           stream_base, drow0, work, st)
   switch (r) {
@@ -417,6 +476,26 @@ extern "C" int clipfs_lora_bwd(const float* dy, const float* x, const float* t, 
       return CLIPFS_EINVAL;
   }
 #undef CLIPFS_LORA_CASE
+}
+
+extern "C" int clipfs_lora_bwd(const float* dy, const float* x, const float* t, const float* A, const float* B,
+                               float* dt, float* dA, float* dB, float* dx, int rows, int width, int segw, int r,
+                               int nseg, unsigned seg_mask, float scale, float p, uint64_t seed, uint32_t stream_base, uint32_t drow0,
+                               const void* keep_bits, float* work, void* stream) {
+  return lora_bwd_impl(dy, x, t, A, B, dt, dA, dB, dx, rows, width, segw, r, nseg, seg_mask, scale, p, seed, stream_base, drow0,
+                       keep_bits, 0, work, stream);
+}
+
+// One-segment adapter backward with a switch on how x is read: x_act == 1 means x holds the pre-activation u and the
+// adapter's input was QuickGELU(u) -- applied as x is loaded for dA, so the activation is never materialised (the c_proj
+// adapter: the forward saves u alone).  dx then receives the gradient wrt QuickGELU(u), not wrt u.  x_act == 0 is
+// clipfs_lora_bwd with nseg 1 and no keep bits.
+extern "C" int clipfs_lora_bwd_xact(const float* dy, const float* x, const float* t, const float* A, const float* B, float* dt,
+                                    float* dA, float* dB, float* dx, int rows, int width, int segw, int r, float scale, float p,
+                                    uint64_t seed, uint32_t stream_base, uint32_t drow0, int x_act, float* work, void* stream) {
+  CLIPFS_REQUIRE(x_act == 0 || x_act == 1, "lora_bwd_xact: x_act %d (0 or 1)", x_act);
+  return lora_bwd_impl(dy, x, t, A, B, dt, dA, dB, dx, rows, width, segw, r, 1, 1u, scale, p, seed, stream_base, drow0, nullptr,
+                       x_act, work, stream);
 }
 
 // fp16 storage mode: the incoming gradient dy is read from its f16 image (what the dgrad GEMM consumes anyway) -- half
@@ -441,4 +520,13 @@ extern "C" int clipfs_lora_bwd_f16dy(const void* dy16, const float* x, const flo
   CLIPFS_REQUIRE(!keep_bits || clipfs_lora_keep_bits_ok(width, segw, r, nseg), "lora_bwd_f16dy: keep bits not covered");
   return lora_bwd_mfma_f16dy(dy16, x, t, A, B, dt, dA, dB, dx, rows, width, segw, r, nseg, seg_mask, scale, p, seed, stream_base,
                              drow0, reinterpret_cast<const uint16_t*>(keep_bits), work, (hipStream_t)stream, launch_reduce_slices2);
+}
+
+extern "C" int clipfs_gelu_bwd_inplace(float* dg, const float* u, size_t n, void* stream) {
+  CLIPFS_REQUIRE(dg && u && n > 0 && aligned16(dg) && aligned16(u), "gelu_bwd_inplace: null or misaligned pointer, or n = 0");
+  const size_t n4 = n / 4;
+  const size_t want = (n4 + 255) / 256;
+  const unsigned blocks = (unsigned)(want > 8192 ? 8192 : (want ? want : 1));
+  hipLaunchKernelGGL(gelu_bwd_inplace_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, dg, u, n4, n);
+  return launch_status();
 }

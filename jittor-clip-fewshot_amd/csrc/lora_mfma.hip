@@ -267,7 +267,8 @@ __device__ __forceinline__ void lora_db_mfma_body(const TY* __restrict__ dy, con
 // dA partials: part[slice][s r + j][k] = sum_{m in slice} dt[m, s r + j] drop_s(x)[m, k].  One wave per (64 columns,
 // slice); lane i owns columns k0 + 4 i + e of MFMA tile e (so one Philox call covers the lane's float4 of x, and that
 // float4 feeds all G rank groups).
-template <int NSEG, int G>
+// XACT: x holds a pre-activation u and the adapter's input is QuickGELU(u), applied as the float4 is loaded.
+template <int NSEG, int G, bool XACT = false>
 __device__ __forceinline__ void lora_da_mfma_body(const float* __restrict__ x, const float* __restrict__ dt,
                                                   float* __restrict__ part, int rows, int width, int r, unsigned seg_mask,
                                                   float p, uint64_t seed, uint32_t stream_base, uint32_t drow0,
@@ -306,6 +307,10 @@ __device__ __forceinline__ void lora_da_mfma_body(const float* __restrict__ x, c
       mcs[u] = ok ? m : m1 - 1;
       xv[u] = ld4(xp + (size_t)mcs[u] * width);
       if (keep_bits) kbu[u] = keep_bits[(size_t)mcs[u] * (width >> 2) + c4];
+      if (XACT) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) xv[u][e] = quick_gelu(xv[u][e]);
+      }
       if (!ok) xv[u] = zero4();
 #pragma unroll
       for (int s = 0; s < NSEG; ++s)
@@ -448,7 +453,7 @@ __global__ __launch_bounds__(256) void lora_db_dt_mfma_kernel(const TY* __restri
     lora_dt_mfma_body<NSEG, G, TY>(dy, B, dt, rows, segw, r, seg_mask, scale, b - n_db, red);
 }
 
-template <int NSEG, int RQ>
+template <int NSEG, int RQ, bool XACT = false>
 __global__ __launch_bounds__(256) void lora_da_dx_mfma_kernel(const float* __restrict__ x, const float* __restrict__ dt,
                                                               const float* __restrict__ A, float* __restrict__ part_a,
                                                               float* __restrict__ dx, int rows, int width, int r,
@@ -457,7 +462,7 @@ __global__ __launch_bounds__(256) void lora_da_dx_mfma_kernel(const float* __res
                                                               int gx_a, int n_da, const uint16_t* __restrict__ keep_bits) {
   const int b = blockIdx.x;
   if (b < n_da)
-    lora_da_mfma_body<NSEG, (RQ + 3) / 4>(x, dt, part_a, rows, width, r, seg_mask, p, seed, stream_base, drow0, rows_per_slice,
+    lora_da_mfma_body<NSEG, (RQ + 3) / 4, XACT>(x, dt, part_a, rows, width, r, seg_mask, p, seed, stream_base, drow0, rows_per_slice,
                                           b % gx_a, b / gx_a, keep_bits);
   else
     lora_dx_mfma_body<NSEG, RQ>(dt, A, dx, rows, width, r, seg_mask, p, seed, stream_base, drow0, b - n_da, keep_bits);
@@ -528,14 +533,14 @@ int lora_down_mfma(const float* x, const float* A, float* t, int rows, int width
   return lora_down_mfma_g<3>(x, A, t, rows, width, r, seg_mask, p, seed, stream_base, drow0, keep_bits, st);
 }
 
-template <int NSEG, int RQ>
+template <int NSEG, int RQ, bool XACT = false>
 static void launch_da_dx(const float* x, const float* dt, const float* A, float* part_a, float* dx, int rows, int width, int r,
                          unsigned seg_mask, float p, uint64_t seed, uint32_t stream_base, uint32_t drow0, int sr_a, int slices_a,
                          const uint16_t* keep_bits, hipStream_t st) {
   const int gx_a = (width + 255) / 256, n_da = gx_a * slices_a;
   const int n_dx = dx ? (rows + 15) / 16 : 0;
   if (n_da + n_dx == 0) return;
-  hipLaunchKernelGGL((lora_da_dx_mfma_kernel<NSEG, RQ>), dim3(n_da + n_dx), dim3(256), 0, st, x, dt, A, part_a, dx, rows, width,
+  hipLaunchKernelGGL((lora_da_dx_mfma_kernel<NSEG, RQ, XACT>), dim3(n_da + n_dx), dim3(256), 0, st, x, dt, A, part_a, dx, rows, width,
                      r, seg_mask, p, seed, stream_base, drow0, sr_a, gx_a, n_da, keep_bits);
 }
 
@@ -552,7 +557,7 @@ static void launch_db_dt(const TY* dy, const float* B, const float* t, float* dt
 // reduce2(part_b, dB, nb, slices_b, scale_b, part_a, dA, na, slices_a, scale_a): both slice sums in one launch
 typedef void (*lora_reduce2_fn)(const float*, float*, size_t, int, float, const float*, float*, size_t, int, float, hipStream_t);
 
-template <int NSEG, typename TY>
+template <int NSEG, typename TY, bool XACT = false>
 static int lora_bwd_mfma_n(const TY* dy, const float* x, const float* t, const float* A, const float* B, float* dt,
                            float* dA, float* dB, float* dx, int rows, int width, int segw, int r, unsigned seg_mask,
                            float scale, float p, uint64_t seed, uint32_t stream_base, uint32_t drow0, const uint16_t* keep_bits,
@@ -573,7 +578,7 @@ static int lora_bwd_mfma_n(const TY* dy, const float* x, const float* t, const f
   CLIPFS_CHECK(launch_status());
   // 2: dA partials || dx.  r <= 16: ceil(r / 4) K-steps for dx; above, whole rank groups of 4 K-steps
 #define CLIPFS_DA_DX(RQ)                                                                                                         \
-  launch_da_dx<NSEG, RQ>(x, dt, A, part_a, dx, rows, width, r, seg_mask, p, seed, stream_base, drow0, S.sr_a, slices_a, keep_bits, st)
+  launch_da_dx<NSEG, RQ, XACT>(x, dt, A, part_a, dx, rows, width, r, seg_mask, p, seed, stream_base, drow0, S.sr_a, slices_a, keep_bits, st)
   switch (r <= 16 ? (r + 3) / 4 : 4 * lora_groups(r)) {
     case 1: CLIPFS_DA_DX(1); break;
     case 2: CLIPFS_DA_DX(2); break;
@@ -599,6 +604,13 @@ int lora_bwd_mfma(const float* dy, const float* x, const float* t, const float* 
                                      keep_bits, work, st, reduce);
   return lora_bwd_mfma_n<3, float>(dy, x, t, A, B, dt, dA, dB, dx, rows, width, segw, r, seg_mask, scale, p, seed, stream_base, drow0,
                                    keep_bits, work, st, reduce);
+}
+
+int lora_bwd_mfma_xact(const float* dy, const float* x, const float* t, const float* A, const float* B, float* dt, float* dA,
+                       float* dB, float* dx, int rows, int width, int segw, int r, unsigned seg_mask, float scale, float p,
+                       uint64_t seed, uint32_t stream_base, uint32_t drow0, float* work, hipStream_t st, lora_reduce2_fn reduce) {
+  return lora_bwd_mfma_n<1, float, true>(dy, x, t, A, B, dt, dA, dB, dx, rows, width, segw, r, seg_mask, scale, p, seed,
+                                         stream_base, drow0, nullptr, work, st, reduce);
 }
 
 // the same with dy given as its f16 image [rows, nseg * segw] (fp16 storage mode)

@@ -31,17 +31,30 @@ static inline bool qkv_f16(const clipfs_tower* t) {
   return f16_attention(t) && (t->width % 128) == 0 && t->lora_r <= 64;
 }
 
-// which adapters of a block are switched on (clipfs_block.lora_mask: bits 0..2 = q / k / v, bit 3 = the out-projection)
+// which adapters of a block are switched on (clipfs_block.lora_mask: bits 0..2 = q / k / v, bit 3 = the out-projection,
+// bit 4 = mlp.c_fc, bit 5 = mlp.c_proj)
 struct Adapters {
   unsigned qkv_mask;
-  bool o;
+  bool o, fc, pr;
+  bool mlp() const { return fc || pr; }
 };
 static inline Adapters adapters(const clipfs_block& b) {
-  return {b.lora_a_qkv ? (b.lora_mask & 7u) : 0u, b.lora_a_o && (b.lora_mask & 8u)};
+  return {b.lora_a_qkv ? (b.lora_mask & 7u) : 0u, b.lora_a_o && (b.lora_mask & 8u), b.lora_a_fc && (b.lora_mask & 16u),
+          b.lora_a_pr && (b.lora_mask & 32u)};
 }
+// some block of the tower has an MLP adapter: the saved record gets the t_fc | t_pr slot, the adapter workspace covers the
+// rectangular products, and every walk keeps the dense rows.  Without one nothing of the layouts or launches changes.
+static bool tower_has_mlp_lora(const clipfs_tower* t) {
+  if (!t->blocks || t->block_size != sizeof(clipfs_block) || t->lora_r <= 0) return false;
+  for (int l = 0; l < t->layers; ++l)
+    if (adapters(t->blocks[l]).mlp()) return true;
+  return false;
+}
+// dropout streams of block l's MLP adapters (c_fc, then c_proj): disjoint from the attention adapters' stream0 + 4 l + s
+static inline uint32_t mlp_stream(const clipfs_tower* t, int l) { return t->dropout_stream0 + 500u + 2u * (uint32_t)l; }
 
 struct SavedLayout {
-  size_t x_in, stat1, h1, t_qkv, qkv, att, lse, t_o, x_mid, stat2, u, keep, total;
+  size_t x_in, stat1, h1, t_qkv, qkv, att, lse, t_o, x_mid, stat2, u, keep, t_mlp, total;
 };
 
 // the q/k/v adapters' dropout masks travel from the forward to the backward as keep bits (2 bytes per float4 of the
@@ -72,6 +85,8 @@ static SavedLayout saved_layout_rows(const clipfs_tower* t, size_t M, size_t bat
   L.stat2 = o; o += al4(2 * M);
   L.u = o;     o += al4(t->weight_format == 2 ? M * 2 * d : M * 4 * d);  // fp16 mode: pre-activation saved as f16
   L.keep = o;  o += keep_bits_slot(t) ? al4((M * (d / 4) + 1) / 2) : 0;    // uint16 per float4 of h1
+  // towers with an MLP adapter only: t_fc | t_pr, the two down-projections [M, r] each
+  L.t_mlp = o; o += tower_has_mlp_lora(t) ? 2 * al4(M * r) : 0;
   L.total = o;
   return L;
 }
@@ -107,7 +122,14 @@ static ScratchLayout scratch_layout(const clipfs_tower* t, size_t M) {
   S.b3 = o;   o += al4(M * 3 * d);
   S.b1 = o;   o += al4(M * d);
   S.dt = o;   o += al4(M * 4 * r);
-  S.work = o; o += r ? al4(clipfs_lora_bwd_work_floats((int)M, (int)d, (int)r, 3)) : 0;
+  size_t lw = r ? al4(clipfs_lora_bwd_work_floats((int)M, (int)d, (int)r, 3)) : 0;
+  if (r && tower_has_mlp_lora(t)) {  // the d -> 4d and 4d -> d adapters' slice plans
+    const size_t w_fc = al4(clipfs_lora_bwd_work_floats2((int)M, (int)d, 4 * (int)d, (int)r, 1));
+    const size_t w_pr = al4(clipfs_lora_bwd_work_floats2((int)M, 4 * (int)d, (int)d, (int)r, 1));
+    lw = w_fc > lw ? w_fc : lw;
+    lw = w_pr > lw ? w_pr : lw;
+  }
+  S.work = o; o += lw;
   // split-K scratch for the largest of the tower's GEMM shapes (0 unless the row count is small)
   size_t ws = 0, cnt = 0;
   // ... at the tower's row count and at one row per sequence (the compact last block: clipfs_tower_fwd_rows /
@@ -161,8 +183,8 @@ static int check_tower(const clipfs_tower* t, int batch) {
   // blocks below the floor get no backward: a gradient slot there would silently stay untouched
   for (int l = 0; l < t->grad_lo; ++l) {
     const clipfs_block& b = t->blocks[l];
-    CLIPFS_REQUIRE(!b.g_lora_a_qkv && !b.g_lora_b_qkv && !b.g_lora_a_o && !b.g_lora_b_o && !block_has_bias_slots(b) &&
-                       !b.g_prompt,
+    CLIPFS_REQUIRE(!b.g_lora_a_qkv && !b.g_lora_b_qkv && !b.g_lora_a_o && !b.g_lora_b_o && !b.g_lora_a_fc && !b.g_lora_b_fc &&
+                       !b.g_lora_a_pr && !b.g_lora_b_pr && !block_has_bias_slots(b) && !b.g_prompt,
                    "tower: block %d below grad_lo %d has gradient slots", l, t->grad_lo);
   }
   for (int l = 0; l < t->layers; ++l) {  // deep prompts (clipfs_block.prompt)
@@ -170,6 +192,17 @@ static int check_tower(const clipfs_tower* t, int batch) {
     CLIPFS_REQUIRE(b.prompt || !b.g_prompt, "tower: block %d has a prompt gradient slot but no prompt", l);
     CLIPFS_REQUIRE(!b.prompt || (b.prompt_first >= 0 && b.prompt_rows > 0),
                    "tower: block %d prompt rows first %d count %d", l, b.prompt_first, b.prompt_rows);
+  }
+  for (int l = 0; l < t->layers; ++l) {  // MLP adapters (clipfs_block.lora_a_fc / lora_a_pr)
+    const clipfs_block& b = t->blocks[l];
+    const Adapters ad = adapters(b);
+    if (!ad.mlp()) continue;
+    CLIPFS_REQUIRE(t->lora_r > 0, "tower: block %d has an MLP adapter but lora_r is 0", l);
+    CLIPFS_REQUIRE(!ad.fc || b.lora_b_fc, "tower: block %d c_fc adapter lacks its B matrix", l);
+    CLIPFS_REQUIRE(!ad.pr || b.lora_b_pr, "tower: block %d c_proj adapter lacks its B matrix", l);
+    // h2, g and du exist only as f16 images in the fp16 storage mode: nothing the adapter products could read
+    CLIPFS_REQUIRE(t->weight_format != 2, "tower: block %d has a %s adapter: MLP adapters are not supported in the fp16 storage mode",
+                   l, ad.fc ? "c_fc" : "c_proj");
   }
   if (t->weight_format == 2)  // fp16 storage mode chains f16 results between GEMMs: every block needs all its f16 weights
     for (int l = 0; l < t->layers; ++l) {
@@ -472,7 +505,8 @@ extern "C" size_t clipfs_tower_counter_ints(const clipfs_tower* t, int batch) {
 // the compact forward leaves the skipped rows of x_mid / u / stat2 unwritten.
 static bool last_block_rows_ok(const clipfs_tower* t) {
   static const bool force_dense = getenv("CLIPFS_DENSE_BWD") && atoi(getenv("CLIPFS_DENSE_BWD")) != 0;  // A/B aid
-  return !(force_dense || adapters(t->blocks[t->layers - 1]).o || t->seq < 8);
+  const Adapters ad = adapters(t->blocks[t->layers - 1]);
+  return !(force_dense || ad.o || ad.mlp() || t->seq < 8);
 }
 
 // ---- forward -------------------------------------------------------------------------------------------------------
@@ -592,10 +626,23 @@ static int fwd_block(const Pass& p, int l, float* x, const int32_t* rows, float*
   float* h2 = p.scratch + SC.h;  // fp16 mode: only the f16 image is consumed (by the c_fc GEMM)
   CLIPFS_CHECK(ln_fwd(p, x_mid, b.ln2_g, b.ln2_b, h16 ? nullptr : h2, h16, stat2));
   float* gbuf = p.scratch + SC.big;
+  // MLP adapters (dense rows, never the fp16 storage mode: check_tower, pack_ok): the down-projections read h2 and g in
+  // scratch and are kept for the backward; below the floor they live in the dt slot, whose t_qkv / t_o are consumed by now
+  float* t_fc = sv ? sv + SL.t_mlp : p.scratch + SC.dt;
+  float* t_pr = t_fc + al4((size_t)n * r);
+  if (ad.fc)
+    CLIPFS_CHECK(clipfs_lora_down(h2, b.lora_a_fc, t_fc, n, d, r, 1, 1u, t->lora_dropout, seed, mlp_stream(t, l), t->dropout_row0,
+                                  nullptr, st));
   CLIPFS_CHECK(gemm(v.cx, {.M = n, .N = 4 * d, .K = d, .A = h2, .B = b.w_fc, .planes = b.w_fc_p, .C = gbuf, .bias = b.b_fc,
-                           .act = 1, .aux_out = sv ? sv + SL.u : nullptr, .chain = CHAIN_OUT16, .a16_ready = h16}, st));
+                           .act = 1, .aux_out = sv ? sv + SL.u : nullptr,
+                           .lora = {ad.fc ? t_fc : nullptr, b.lora_b_fc, r, 1, 4 * d, t->lora_scale},
+                           .chain = CHAIN_OUT16, .a16_ready = h16}, st));
+  if (ad.pr)
+    CLIPFS_CHECK(clipfs_lora_down(gbuf, b.lora_a_pr, t_pr, n, 4 * d, r, 1, 1u, t->lora_dropout, seed, mlp_stream(t, l) + 1,
+                                  t->dropout_row0, nullptr, st));
   return gemm(v.cx, {.M = n, .N = d, .K = 4 * d, .A = gbuf, .B = b.w_pr, .planes = b.w_pr_p, .C = x_next, .bias = b.b_pr,
-                     .residual = x_mid, .chain = CHAIN_IN16}, st);
+                     .residual = x_mid, .lora = {ad.pr ? t_pr : nullptr, b.lora_b_pr, r, 1, d, t->lora_scale},
+                     .chain = CHAIN_IN16}, st);
 }
 
 // rows == NULL: every block in full.  rows != NULL: the LAST block's output projection, LayerNorm 2 and MLP run on the
@@ -704,11 +751,38 @@ static int bwd_mlp_half(const Pass& p, int l, const float* sv, float* dx, void* 
   // (fp16 storage mode keeps u as halves: 2 d floats per row)
   const float* u;
   CLIPFS_CHECK(saved_rows(p, sv + SL.u, t->weight_format == 2 ? 2 * d : 4 * d, du + 4 * (size_t)n * d, &u));
-  CLIPFS_CHECK(gemm(v.cx, {.M = n, .N = 4 * d, .K = d, .A = dx, .B = b.w_pr_t, .planes = b.w_pr_t_p, .C = du, .act = 2,
-                           .aux_in = u, .chain = CHAIN_OUT16, .a16_ready = h16}, p.st));
+  const Adapters ad = adapters(b);
+  const int r = t->lora_r;
+  float* dt = p.scratch + p.SC.dt;
+  float* work = p.scratch + p.SC.work;
+  if (!ad.pr) {
+    CLIPFS_CHECK(gemm(v.cx, {.M = n, .N = 4 * d, .K = d, .A = dx, .B = b.w_pr_t, .planes = b.w_pr_t_p, .C = du, .act = 2,
+                             .aux_in = u, .chain = CHAIN_OUT16, .a16_ready = h16}, p.st));
+  } else {
+    // c_proj adapter: dg = dx Wpr without the activation, the adapter adds (dt_pr A_pr) * dropscale to it and takes dA_pr
+    // from QuickGELU(u) read on the fly, then du = dg * gelu'(u) in place.  One route for p = 0 and p > 0.
+    CLIPFS_REQUIRE((b.g_lora_a_pr == nullptr) == (b.g_lora_b_pr == nullptr),
+                   "tower_bwd: block %d has only one of the c_proj LoRA gradient slots", l);
+    CLIPFS_CHECK(gemm(v.cx, {.M = n, .N = 4 * d, .K = d, .A = dx, .B = b.w_pr_t, .planes = b.w_pr_t_p, .C = du}, p.st));
+    CLIPFS_CHECK(clipfs_lora_bwd_xact(dx, u, sv + SL.t_mlp + al4((size_t)n * r), b.lora_a_pr, b.lora_b_pr, dt, b.g_lora_a_pr,
+                                      b.g_lora_b_pr, du, n, 4 * d, d, r, t->lora_scale, t->lora_dropout, t->dropout_seed,
+                                      mlp_stream(t, l) + 1, t->dropout_row0, 1, work, p.st));
+    CLIPFS_CHECK(clipfs_gelu_bwd_inplace(du, u, (size_t)n * 4 * d, p.st));
+  }
   CLIPFS_CHECK(bias_sum(p, du, n, 4 * d, 4 * d, b.g_b_fc));
   CLIPFS_CHECK(gemm(v.cx, {.M = n, .N = d, .K = 4 * d, .A = du, .B = b.w_fc_t, .planes = b.w_fc_t_p, .C = dh,
                            .chain = CHAIN_IN16}, p.st));
+  if (ad.fc) {
+    // c_fc adapter: its input h2 = LN2(x_mid) is not saved -- recomputed into the b3 slot (dqkv, not yet written) by the
+    // forward's kernel; the adapter's dx term goes into dh2 before LayerNorm 2's backward (and ln_2's bias sum) read it
+    CLIPFS_REQUIRE((b.g_lora_a_fc == nullptr) == (b.g_lora_b_fc == nullptr),
+                   "tower_bwd: block %d has only one of the c_fc LoRA gradient slots", l);
+    float* h2 = p.scratch + p.SC.b3;
+    CLIPFS_CHECK(clipfs_layernorm_fwd(sv + SL.x_mid, d, b.ln2_g, b.ln2_b, h2, nullptr, nullptr, n, d, 1e-5f, p.st));
+    CLIPFS_CHECK(clipfs_lora_bwd_xact(du, h2, sv + SL.t_mlp, b.lora_a_fc, b.lora_b_fc, dt, b.g_lora_a_fc, b.g_lora_b_fc, dh, n,
+                                      d, 4 * d, r, t->lora_scale, t->lora_dropout, t->dropout_seed, mlp_stream(t, l),
+                                      t->dropout_row0, 0, work, p.st));
+  }
   CLIPFS_CHECK(bias_sum(p, dh, n, d, d, b.g_ln2_b));
   CLIPFS_CHECK(ln_bwd(p, dh, sv + SL.x_mid, b.ln2_g, sv + SL.stat2, dx, dx, h16));
   CLIPFS_CHECK(bias_sum(p, dx, n, d, d, b.g_b_o));
@@ -931,6 +1005,9 @@ static bool pack_ok(const clipfs_tower* t, int batch, int R) {
   const int M = batch * t->seq, d = t->width, r = t->lora_r;
   if (M < kPackMinRows) return false;
   if (!t->causal || !last_block_rows_ok(t)) return false;
+  // MLP adapters keep the dense rows in both directions: their down-projections and backward products are not carried
+  // through the row map (the masks would have to be drawn at the full-layout row)
+  if (tower_has_mlp_lora(t)) return false;
   if (t->weight_format == 2) {
     if (!f16_attention(t) || !clipfs_attention_f16_bwd_packed_ok(t->seq, 1)) return false;
     for (int l = t->grad_lo; l < t->layers; ++l) {

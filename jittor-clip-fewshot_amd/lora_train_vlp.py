@@ -45,6 +45,9 @@ INDEX_POSITIONS_VISION = {
 
 _PROJ_BIT = {'q': 1, 'k': 2, 'v': 4, 'o': 8}
 _PROJ_NAME = {'q': 'q_proj', 'k': 'k_proj', 'v': 'v_proj', 'o': 'proj'}
+# the MLP linears of a block (jclip/model.py:34-39): tokens of ``args.params`` = attribute names of ``block.mlp``
+_MLP_TOKENS = ('c_fc', 'c_proj')
+_MLP_BIT = {'c_fc': 16, 'c_proj': 32}
 
 
 # ----------------------------------------------------------------------------------------------
@@ -153,6 +156,30 @@ class LinearLoRA(nn.Module, LoRALayer):
     def merge_BA(self, param_name: str = 'weight') -> torch.Tensor:
         """B @ A (:218-221); host-side helper for inspection / merged-weight checks."""
         return (self.w_lora_B.data @ self.w_lora_A.data).reshape(self.weight.shape)
+
+
+def mlp_lora_linear(linear, r: int, lora_alpha: int, dropout_rate: float, gen: torch.Generator) -> LinearLoRA:
+    """``LinearLoRA`` over one MLP linear (``mlp.c_fc``: d -> 4d, ``mlp.c_proj``: 4d -> d), sharing its weight and bias
+    storage.  A [r, in] ~ U(+-1/sqrt(in_features)), B [out, r] = 0 (lora_train_vlp.py:209-213).  Unlike the attention
+    projections' views these adapters own their tensors; their gradient slots are ``w_lora_A.grad_slot`` /
+    ``w_lora_B.grad_slot`` (views of the flat gradient buffer once ``FlatTrainables`` has re-homed them)."""
+    out_f, in_f = linear.weight.shape
+    dev = linear.weight.device
+    a = ((torch.rand(r, in_f, generator=gen) * 2 - 1) / math.sqrt(in_f)).to(dev)
+    m = LinearLoRA(linear.weight.data, None if linear.bias is None else linear.bias.data, a,
+                   torch.zeros(out_f, r, device=dev), r, lora_alpha, dropout_rate)
+    if linear.bias is not None:
+        m.bias.requires_grad_(linear.bias.requires_grad)
+    m.is_mlp_lora = True
+    for p in (m.w_lora_A, m.w_lora_B):
+        p.grad_slot = torch.zeros_like(p.data)
+    return m
+
+
+def mlp_adapters(blk) -> List[Tuple[str, LinearLoRA]]:
+    """[(token, LinearLoRA)] of the adapted MLP linears of one block, c_fc before c_proj."""
+    return [(tok, getattr(blk.mlp, tok)) for tok in _MLP_TOKENS
+            if getattr(getattr(blk.mlp, tok), 'is_mlp_lora', False) and getattr(blk.mlp, tok).r > 0]
 
 
 class _FrozenLinear(nn.Module):
@@ -317,17 +344,35 @@ class PlainMultiheadAttentionLoRA(nn.Module, LoRALayer):
 
 def apply_lora(args, clip_model):
     """lora_train_vlp.py:516-548: text blocks first, then vision blocks; a block is adapted when its
-    ``attn`` is (still) a ``MultiheadAttention``."""
+    ``attn`` is (still) a ``MultiheadAttention``.
+
+    ``args.params`` takes ``c_fc`` and ``c_proj`` beside ``q k v o``: the selected blocks' ``mlp.c_fc`` / ``mlp.c_proj`` are
+    wrapped in ``LinearLoRA`` (parameters ``...mlp.c_fc.w_lora_A`` and so on).  The list still holds one entry per adapted
+    block, the block's ``PlainMultiheadAttentionLoRA`` -- also for a block adapted in its MLP only, whose attention module
+    then carries no adapter (``lora_mask`` 0); the entry's ``c_fc`` / ``c_proj`` attributes are the wrapped MLP linears."""
     list_lora_layers = []
+    for tok in args.params:
+        if tok not in _PROJ_BIT and tok not in _MLP_TOKENS:
+            raise ValueError(f"unknown projection {tok!r} (expected q, k, v, o, c_fc, c_proj)")
+    attn_tokens = [tok for tok in args.params if tok in _PROJ_BIT]
+    mlp_tokens = [tok for tok in _MLP_TOKENS if tok in args.params]
+    gen = torch.Generator(device="cpu")
+    gen.manual_seed(torch.initial_seed())
 
     def adapt(blocks, indices):
         for i, block in enumerate(blocks):
             if i in indices:
                 sub = block.attn
                 if sub.__class__.__name__ == 'MultiheadAttention':
-                    new = PlainMultiheadAttentionLoRA(sub, enable_lora=args.params, r=args.r, lora_alpha=args.alpha,
+                    new = PlainMultiheadAttentionLoRA(sub, enable_lora=attn_tokens, r=args.r, lora_alpha=args.alpha,
                                                       dropout_rate=args.dropout_rate)
                     block.attn = new
+                    if args.r > 0:
+                        for tok in mlp_tokens:
+                            lin = mlp_lora_linear(getattr(block.mlp, tok), args.r, args.alpha, args.dropout_rate, gen)
+                            setattr(block.mlp, tok, lin)
+                            # reachable from the list entry without registering the module a second time
+                            object.__setattr__(new, tok, lin)
                     list_lora_layers.append(new)
 
     if args.encoder == 'text' or args.encoder == 'both':
@@ -349,6 +394,11 @@ def _layer_weights(args, layer) -> dict:
             m = getattr(layer, _PROJ_NAME[p])
             out[_PROJ_NAME[p]] = {'w_lora_A': m.w_lora_A.detach().cpu().numpy().copy(),
                                   'w_lora_B': m.w_lora_B.detach().cpu().numpy().copy()}
+    for tok in _MLP_TOKENS:  # the MLP adapters, under their own token
+        if tok in args.params and getattr(layer, tok, None) is not None:
+            m = getattr(layer, tok)
+            out[tok] = {'w_lora_A': m.w_lora_A.detach().cpu().numpy().copy(),
+                        'w_lora_B': m.w_lora_B.detach().cpu().numpy().copy()}
     return out
 
 
@@ -391,6 +441,11 @@ def load_lora(args, list_lora_layers, load_path):
                     m = getattr(layer, name)
                     m.w_lora_A.data.copy_(torch.from_numpy(np.ascontiguousarray(lw[name]['w_lora_A'])))
                     m.w_lora_B.data.copy_(torch.from_numpy(np.ascontiguousarray(lw[name]['w_lora_B'])))
+            for tok in _MLP_TOKENS:
+                m = getattr(layer, tok, None)
+                if tok in args.params and tok in lw and m is not None:
+                    m.w_lora_A.data.copy_(torch.from_numpy(np.ascontiguousarray(lw[tok]['w_lora_A'])))
+                    m.w_lora_B.data.copy_(torch.from_numpy(np.ascontiguousarray(lw[tok]['w_lora_B'])))
     print(f'LoRA weights loaded from {load_path}')
 
 
@@ -553,20 +608,24 @@ class FlatTrainables:
     moved by AdamW (the stage-2 layout, slow_pace.py:1556-1564: LoRA applied but frozen)."""
 
     def __init__(self, model, extra: Sequence[nn.Parameter] = ()):
-        from clipfs.engine import _lora_trains
+        from clipfs.engine import _lora_trains, _mlp_lora_trains
         self.model = model
         bias_names = [n for n, _ in trainable_biases(model)]
         entries = []
+        mlp_params = []  # trainable MLP adapters (mlp.c_fc / mlp.c_proj): A then B, after the attention adapters
         for tname, tower in (("text", model.transformer), ("vision", model.visual.transformer)):
             for i, blk in enumerate(tower.resblocks):
                 a = blk.attn
                 if getattr(a, "is_lora_mha", False) and _lora_trains(a, f"{tname} block {i}"):
                     for name, p, _ in a.stacked():
                         entries.append((a, name, p))
+                for tok, m in mlp_adapters(blk):
+                    if _mlp_lora_trains(m, f"{tname} block {i} mlp.{tok}"):
+                        mlp_params += [m.w_lora_A, m.w_lora_B]
         n_bias = sum(p.numel() for _, p in trainable_biases(model))
         deep = trainable_deep_prompts(model)
-        n = (sum(p.numel() for _, _, p in entries) + sum(p.numel() for p in extra) + sum(p.numel() for p in deep)
-             + n_bias)
+        n = (sum(p.numel() for _, _, p in entries) + sum(p.numel() for p in mlp_params) + sum(p.numel() for p in extra)
+             + sum(p.numel() for p in deep) + n_bias)
         if n == 0:
             raise ValueError("model has nothing to train: no trainable adapter, bias or extra tensor (call apply_lora first)")
         dev = model.device
@@ -579,6 +638,13 @@ class FlatTrainables:
             k = p.numel()
             self.params[off:off + k].copy_(p.reshape(-1))
             a.rebind(name, self.params[off:off + k].view_as(p), self.grads[off:off + k].view_as(p))
+            off += k
+        self.mlp_params = mlp_params
+        for p in mlp_params:  # (none without c_fc / c_proj in apply_lora's params: the layout is then unchanged)
+            k = p.numel()
+            self.params[off:off + k].copy_(p.data.reshape(-1))
+            p.data = self.params[off:off + k].view_as(p)
+            p.grad_slot = self.grads[off:off + k].view_as(p)
             off += k
         self.extra = []
         for p in extra:
@@ -709,6 +775,13 @@ class LoRATrainer:
         if model.visual.VPT is not None and model.visual.VPT.requires_grad:
             extra.append(model.visual.VPT)
         self.flat = FlatTrainables(model, extra)
+        if model.engine.precision == "fp16":
+            for tname, tower in (("text", model.transformer), ("vision", model.visual.transformer)):
+                for i, blk in enumerate(tower.resblocks):
+                    for tok, _ in mlp_adapters(blk):
+                        raise ValueError(f"{tname} block {i} has a {tok} adapter: MLP adapters are not supported in the fp16 "
+                                         "storage mode (LayerNorm 2's output, the activation and the MLP gradient exist only "
+                                         "as f16 images there): use precision 'fp32' or 'bf16x3'")
         if self.flat.bias_names and model.engine.precision == "fp16":
             raise ValueError("bias training is not supported in the fp16 storage mode (dqkv and the MLP gradient exist "
                              "only as f16 images there): use precision 'fp32' or 'bf16x3'")
