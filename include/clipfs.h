@@ -121,6 +121,8 @@ int clipfs_split_bf16(const float* src, void* planes, size_t n, void* stream);
  * rounded to f16 in the staging path).  Tolerance is that of fp16 products (~5e-4 relative), stated in the tests. */
 int clipfs_convert_f16(const float* src, void* dst, size_t n, void* stream);
 int clipfs_gemm_splits(int M, int N, int K);
+/* rows of the block tile (64 or 32) the exact fp32 kernels use for an [M,N] output: host-only query, no launch */
+int clipfs_gemm_tile_rows(int M, int N);
 size_t clipfs_gemm_workspace_floats(int M, int N, int K);
 /* Stream-K (opt-in: environment CLIPFS_GEMM_SK=1|2; dense fp32 products with K % 32 == 0, when `workspace` and `counters`
  * are both supplied; clipfs_gemm_counter_ints returns 0 while it is off): the tiles x K-steps

@@ -86,6 +86,7 @@ SIGNATURES = {
     "clipfs_split_bf16": (_i, [_p, _p, _sz, _p]),
     "clipfs_convert_f16": (_i, [_p, _p, _sz, _p]),
     "clipfs_gemm_splits": (_i, [_i, _i, _i]),
+    "clipfs_gemm_tile_rows": (_i, [_i, _i]),
     "clipfs_gemm_workspace_floats": (_sz, [_i, _i, _i]),
     "clipfs_gemm_counter_ints": (_sz, [_i, _i, _i]),
     "clipfs_gemm_timing": (_i, [_i]),

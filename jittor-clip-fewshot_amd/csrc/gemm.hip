@@ -822,6 +822,8 @@ static inline int gemm_bm(int M, int N) {
   return cost32 < cost64 ? 32 : 64;
 }
 
+extern "C" int clipfs_gemm_tile_rows(int M, int N) { return gemm_bm(M, N); }
+
 // Split-K factor for a [M,N,K] product: only when even the 32 x 128 tiling leaves the 512 resident workgroup slots
 // short of work (strong-scaling per-rank batches, the one-row-per-sequence products of the last block) and K is long
 // enough to cut.  The slices of a tile are combined by the last one to arrive inside the same launch (no second
