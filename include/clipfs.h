@@ -56,6 +56,8 @@ const char* clipfs_last_error(void);
  * Epilogue, in this order (each part optional):
  *     v  = alpha * acc + bias[n]
  *     v += lora_scale * sum_j lora_t[m, seg*r + j] * lora_b[n, j]      seg = n / lora_seg_width
+ *         (the f16 x f16 kernel adds this product inside its accumulator, i.e. before alpha: it refuses lora_t with
+ *          alpha != 1 -- CLIPFS_EINVAL -- rather than scale the adapter term; no caller combines the two)
  *     if act == 1:  (aux_out[m,n] = v);  v = v * sigmoid(1.702 v)        QuickGELU, model.py:24-27
  *     if act == 2:  v = v * dQuickGELU(aux_in[m,n])                      backward of act 1
  *     v += residual[rm, n]                                               model.py:60-61
@@ -123,6 +125,32 @@ int clipfs_convert_f16(const float* src, void* dst, size_t n, void* stream);
 int clipfs_gemm_splits(int M, int N, int K);
 /* rows of the block tile (64 or 32) the exact fp32 kernels use for an [M,N] output: host-only query, no launch */
 int clipfs_gemm_tile_rows(int M, int N);
+/* The f16 x f16 kernel (args->A_f16 set) is nine kernels and a row split: whole rounds of 256 x 256 tiles over the CUs on
+ * a ping-pong or phased kernel, the leftover rows on 4-wave kernels, on the internal side stream when `side` is set.
+ * clipfs_gemm_f16_plan writes the launches clipfs_gemm_nt would make for `args` on a device of `cus` compute units
+ * (cus <= 0: the current device's count; 256 when there is none) -- it IS the function the dispatch executes.  Host-only:
+ * no launch, and no pointer of `args` is dereferenced (their alignment takes part in the choice).  Returns CLIPFS_EINVAL
+ * for arguments clipfs_gemm_nt would refuse, or without A_f16.  The tuning aids CLIPFS_F16_TILE / _PP_FILL / _SIDE /
+ * _EPILOGUE / _PHASED are read once per process and show in the plan. */
+#define CLIPFS_F16_64X128 0     /* 4-wave kernels: 64 x 128 tile, three LDS stages */
+#define CLIPFS_F16_64X128_S2 1  /*   64 x 128, two stages (fits beside a ping-pong workgroup) */
+#define CLIPFS_F16_128X128 2
+#define CLIPFS_F16_256X128 3
+#define CLIPFS_F16_PP_REG 4     /* 256 x 256 ping-pong, per-lane register epilogue */
+#define CLIPFS_F16_PP_LDS 5     /* 256 x 256 ping-pong, epilogue through LDS */
+#define CLIPFS_F16_PH16 6       /* 256 x 256 phased on 16x16x32 MFMAs, LDS epilogue, 4 columns per thread */
+#define CLIPFS_F16_PH16_WIDE 7  /*   the same with 8 columns per thread (f16-only result) */
+#define CLIPFS_F16_PH32 8       /* 256 x 256 phased on 32x32x16 MFMAs */
+typedef struct clipfs_f16_launch {
+  int kernel;            /* CLIPFS_F16_* */
+  int m_begin, m_end;    /* rows [m_begin, m_end) of the problem */
+  int side;              /* 1: on the side stream */
+} clipfs_f16_launch;
+typedef struct clipfs_f16_plan {
+  int n;                 /* launches, 1 .. 3, in row order */
+  clipfs_f16_launch launch[3];
+} clipfs_f16_plan;
+int clipfs_gemm_f16_plan(const clipfs_gemm_args* args, int cus, clipfs_f16_plan* out);
 size_t clipfs_gemm_workspace_floats(int M, int N, int K);
 /* Stream-K (opt-in: environment CLIPFS_GEMM_SK=1|2; dense fp32 products with K % 32 == 0, when `workspace` and `counters`
  * are both supplied; clipfs_gemm_counter_ints returns 0 while it is off): the tiles x K-steps

@@ -44,6 +44,18 @@ class GemmArgs(C.Structure):
     ]
 
 
+class F16Launch(C.Structure):
+    _fields_ = [("kernel", C.c_int), ("m_begin", C.c_int), ("m_end", C.c_int), ("side", C.c_int)]
+
+
+class F16Plan(C.Structure):
+    _fields_ = [("n", C.c_int), ("launch", F16Launch * 3)]
+
+
+# CLIPFS_F16_* kernel ids of include/clipfs.h, by value
+F16_KERNELS = ("64x128", "64x128_s2", "128x128", "256x128", "pp_reg", "pp_lds", "ph16", "ph16_wide", "ph32")
+
+
 class Block(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in (
         "ln1_g", "ln1_b", "ln2_g", "ln2_b",
@@ -87,6 +99,7 @@ SIGNATURES = {
     "clipfs_convert_f16": (_i, [_p, _p, _sz, _p]),
     "clipfs_gemm_splits": (_i, [_i, _i, _i]),
     "clipfs_gemm_tile_rows": (_i, [_i, _i]),
+    "clipfs_gemm_f16_plan": (_i, [C.POINTER(GemmArgs), _i, C.POINTER(F16Plan)]),
     "clipfs_gemm_workspace_floats": (_sz, [_i, _i, _i]),
     "clipfs_gemm_counter_ints": (_sz, [_i, _i, _i]),
     "clipfs_gemm_timing": (_i, [_i]),
@@ -197,6 +210,13 @@ def new_gemm_args() -> GemmArgs:
     g = GemmArgs()
     g.struct_size = C.sizeof(GemmArgs)
     return g
+
+
+def gemm_f16_plan(g: GemmArgs, cus: int = 0):
+    """[(kernel name, m_begin, m_end, side)] clipfs_gemm_nt would launch for the f16 x f16 product `g` (host-only)."""
+    plan = F16Plan()
+    check(load().clipfs_gemm_f16_plan(C.byref(g), cus, C.byref(plan)), "gemm_f16_plan")
+    return [(F16_KERNELS[l.kernel], l.m_begin, l.m_end, bool(l.side)) for l in plan.launch[:plan.n]]
 
 
 def new_tower() -> Tower:

@@ -48,7 +48,8 @@ def gemm_nt(a: torch.Tensor, b: torch.Tensor, out: Optional[torch.Tensor] = None
             a16: Optional[torch.Tensor] = None, out16: Optional[torch.Tensor] = None, only16: bool = False,
             aux_f16: bool = False) -> torch.Tensor:
     """out = epi(alpha * a @ b.T); a [M,K], b [N,K].  ``a16`` (f16 [M,K]) with f16 ``b_planes`` selects the
-    f16 x f16 kernel (``a`` may then be None); ``out16`` (f16 [M,N]) receives an f16 copy of the result."""
+    f16 x f16 kernel (``a`` may then be None); ``out16`` (f16 [M,N]) receives an f16 copy of the result.  That kernel
+    refuses ``alpha != 1`` together with ``lora_t`` (its adapter product would be scaled by alpha)."""
     if a is not None:
         _f32(a)
     _f32(b)

@@ -922,9 +922,41 @@ extern "C" int clipfs_gemm_timing_collect(double* total_ms, double* total_flops,
 namespace clipfs {
 int gemm_bf16x3_dispatch(const GemmParams& base, hipStream_t stream);  // gemm_bf16.hip
 int gemm_f16_dispatch(const clipfs_gemm_args& a, hipStream_t stream);  // gemm_f16.hip
+void gemm_f16_plan(const clipfs_gemm_args& a, int cus, clipfs_f16_plan* out);
 }
 
 static int gemm_nt_impl(const clipfs_gemm_args* args, void* stream);
+
+// what the f16 x f16 kernel requires of its arguments (shared by clipfs_gemm_nt and clipfs_gemm_f16_plan)
+static int gemm_f16_validate(const clipfs_gemm_args& a) {
+  CLIPFS_REQUIRE(a.B_planes && a.b_format == 2, "gemm: A_f16 needs the f16 copy of B (b_format 2)");
+  CLIPFS_REQUIRE(a.C || a.C_f16, "gemm: no output");
+  CLIPFS_REQUIRE(a.a_mode == 0 && (a.K % BK) == 0 && (a.lda & 7) == 0 && (a.ldb & 7) == 0 && a.lda >= a.K && a.ldb >= a.K &&
+                     a.ldc >= a.N && aligned16(a.A_f16) && aligned16(a.B_planes),
+                 "gemm f16: K %% 32, lda/ldb %% 8, 16-byte aligned operands required");
+  CLIPFS_REQUIRE(a.act >= 0 && a.act <= 2 && (a.act != 2 || a.aux_in) && (!a.residual || a.ldres >= a.N), "gemm f16: bad epilogue args");
+  if (a.lora_t) {
+    CLIPFS_REQUIRE(a.lora_b && a.lora_r > 0 && a.lora_r <= 64 && a.lora_nseg > 0 && a.lora_seg_width % 128 == 0 &&
+                       a.lora_seg_width * a.lora_nseg >= a.N, "gemm f16: lora rank <= 64 and segment width %% 128 required");
+    // the adapter product is accumulated by MFMA steps into the same accumulator that alpha then scales
+    CLIPFS_REQUIRE(a.alpha == 1.f, "gemm f16: alpha != 1 (%g) together with lora_t is not supported: alpha would scale the adapter term",
+                   (double)a.alpha);
+  }
+  return CLIPFS_OK;
+}
+
+extern "C" int clipfs_gemm_f16_plan(const clipfs_gemm_args* args, int cus, clipfs_f16_plan* out) {
+  CLIPFS_REQUIRE(args != nullptr && out != nullptr, "gemm f16 plan: null args / out");
+  const clipfs_gemm_args& a = *args;
+  CLIPFS_REQUIRE(a.struct_size == sizeof(clipfs_gemm_args),
+                 "gemm f16 plan: args built against another clipfs.h (struct_size %zu, library has %zu)", a.struct_size,
+                 sizeof(clipfs_gemm_args));
+  CLIPFS_REQUIRE(a.M > 0 && a.N > 0 && a.K > 0, "gemm f16 plan: bad dims %d %d %d", a.M, a.N, a.K);
+  CLIPFS_REQUIRE(a.A_f16 != nullptr, "gemm f16 plan: A_f16 is not set (the plan is that of the f16 x f16 kernel)");
+  CLIPFS_CHECK(gemm_f16_validate(a));
+  clipfs::gemm_f16_plan(a, cus, out);
+  return CLIPFS_OK;
+}
 
 extern "C" int clipfs_gemm_nt(const clipfs_gemm_args* args, void* stream) {
   if (!g_timing) return gemm_nt_impl(args, stream);
@@ -955,15 +987,7 @@ static int gemm_nt_impl(const clipfs_gemm_args* args, void* stream) {
                  sizeof(clipfs_gemm_args));
   CLIPFS_REQUIRE(a.M > 0 && a.N > 0 && a.K > 0, "gemm: bad dims %d %d %d", a.M, a.N, a.K);
   if (a.A_f16) {  // f16 x f16 kernel
-    CLIPFS_REQUIRE(a.B_planes && a.b_format == 2, "gemm: A_f16 needs the f16 copy of B (b_format 2)");
-    CLIPFS_REQUIRE(a.C || a.C_f16, "gemm: no output");
-    CLIPFS_REQUIRE(a.a_mode == 0 && (a.K % BK) == 0 && (a.lda & 7) == 0 && (a.ldb & 7) == 0 && a.lda >= a.K && a.ldb >= a.K &&
-                       a.ldc >= a.N && aligned16(a.A_f16) && aligned16(a.B_planes),
-                   "gemm f16: K %% 32, lda/ldb %% 8, 16-byte aligned operands required");
-    CLIPFS_REQUIRE(a.act >= 0 && a.act <= 2 && (a.act != 2 || a.aux_in) && (!a.residual || a.ldres >= a.N), "gemm f16: bad epilogue args");
-    if (a.lora_t)
-      CLIPFS_REQUIRE(a.lora_b && a.lora_r > 0 && a.lora_r <= 64 && a.lora_nseg > 0 && a.lora_seg_width % 128 == 0 &&
-                         a.lora_seg_width * a.lora_nseg >= a.N, "gemm f16: lora rank <= 64 and segment width %% 128 required");
+    CLIPFS_CHECK(gemm_f16_validate(a));
     return gemm_f16_dispatch(a, (hipStream_t)stream);
   }
   CLIPFS_REQUIRE(!a.C_f16 && !a.aux_f16, "gemm: C_f16 / aux_f16 belong to the f16 x f16 kernel only");

@@ -453,7 +453,7 @@ __device__ __forceinline__ void f16_epilogue_lds(const F16Params& p, AccT& acc, 
   auto tile_row = [&](int ps, int lr) { return (lr >> 6) * 128 + ps * 64 + (lr & 63); };
 
   // One load buffer per pass: the residual rows (fp32 x 4) OR the saved pre-activation (f16 x 4 in the low two dwords).
-  // The host never sends both, nor an fp32 pre-activation, to this epilogue (launch_f16_pp: register-epilogue kernel).
+  // The host never sends both, nor an fp32 pre-activation, to this epilogue (f16_pp_kernel_id: register-epilogue kernel).
   typedef float f32x2 __attribute__((ext_vector_type(2)));
   f32x4 ld0[RP], ld1[RP];
   auto issue_loads = [&](int ps, f32x4 (&r)[RP]) __attribute__((always_inline)) {
@@ -535,7 +535,7 @@ __device__ __forceinline__ void f16_epilogue_lds(const F16Params& p, AccT& acc, 
   // width), so a thread takes 8 consecutive columns of 8 rows per pass: one 16-byte store per row instead of two 8-byte
   // ones (and one 16-byte load of the saved pre-activation).  Same arithmetic per element.
   typedef _Float16 f16x8e __attribute__((ext_vector_type(8)));
-  // (WIDE is chosen on the host -- f16_wide_epilogue_ok -- and is a template parameter so that the two paths do not
+  // (WIDE is chosen on the host -- f16_pp_kernel_id -- and is a template parameter so that the two paths do not
   // share a register allocation: as one runtime branch the fp32-result path spilled and ran 3x slower)
   if constexpr (WIDE) {
     constexpr int RW = 8;                      // rows per thread and pass
@@ -987,19 +987,137 @@ __global__ __launch_bounds__(512, 2) void gemm_f16_ph_kernel(const F16Params p) 
   F16_STAMP(3);
 }
 
-static int launch_f16_pp(F16Params& p, hipStream_t stream) {
-  p.n_blocks_n = (p.a.N + 255) / 256;
-  {
-    const clipfs_gemm_args& a = p.a;
-    static const int cfg = getenv("CLIPFS_F16_EPILOGUE") ? atoi(getenv("CLIPFS_F16_EPILOGUE")) : 1;  // 0: register epilogue (A/B aid)
-    auto al = [](const void* q, size_t n) { return q == nullptr || ((uintptr_t)q & (n - 1)) == 0; };
-    p.row_major_epilogue = cfg != 0 && (a.N & 3) == 0 && (a.ldc & 3) == 0 && (!a.residual || (a.ldres & 3) == 0) &&
-                           al(a.C, 16) && al(p.C16, 8) && al(a.bias, 16) && al(a.residual, 16) &&
-                           al(a.aux_out, 8) && al(a.aux_in, 8) &&
-                           // the LDS epilogue reads / writes the pre-activation as f16 only and keeps ONE per-row load
-                           // buffer (residual or pre-activation): everything else goes to the register-epilogue kernel
-                           ((!a.aux_out && a.act != 2) || a.aux_f16) && !(a.residual && a.act == 2);
+// ---- the dispatch decision --------------------------------------------------------------------------------------
+// Which kernels run which rows of one f16 x f16 product is decided HERE, by one pure host function of the arguments,
+// the CU count and the (cached) tuning aids: gemm_f16_dispatch executes the plan it returns and clipfs_gemm_f16_plan
+// (include/clipfs.h) answers with the same plan without a launch, so the tests can assert the kernel a shape reaches.
+struct F16Aids {
+  int tile;      // CLIPFS_F16_TILE: 1 / 2 / 3 force the 128x128 / 64x128 / 256x128 4-wave kernel, 4 forces the 256x256
+                 // ping-pong kernel on every row, 5 disables it
+  int fill;      // CLIPFS_F16_PP_FILL: percent of the CUs a (last) round of 256x256 tiles must fill
+  int side;      // CLIPFS_F16_SIDE: 0 = leftover rows on the caller's stream (A/B aid)
+  int epilogue;  // CLIPFS_F16_EPILOGUE: 0 = register epilogue (A/B aid)
+  int phased;    // CLIPFS_F16_PHASED: 0 = the 2-phase kernel, 2 = phased on 32x32x16 MFMAs (A/B aids)
+};
+
+static const F16Aids& f16_aids() {
+  auto env = [](const char* name, int dflt) { return getenv(name) ? atoi(getenv(name)) : dflt; };
+  static const F16Aids aids = {env("CLIPFS_F16_TILE", 0), env("CLIPFS_F16_PP_FILL", 30), env("CLIPFS_F16_SIDE", 1),
+                               env("CLIPFS_F16_EPILOGUE", 1), env("CLIPFS_F16_PHASED", 1)};
+  return aids;
+}
+
+static inline void plan_push(clipfs_f16_plan* o, int kernel, int m_begin, int m_end, int side) {
+  clipfs_f16_launch& l = o->launch[o->n++];
+  l.kernel = kernel;
+  l.m_begin = m_begin;
+  l.m_end = m_end;
+  l.side = side;
+}
+
+// the 256 x 256 kernel for these arguments: 2-phase with the register or the LDS epilogue, or one of the phased kernels
+static int f16_pp_kernel_id(const clipfs_gemm_args& a, const F16Aids& aids) {
+  auto al = [](const void* q, size_t n) { return q == nullptr || ((uintptr_t)q & (n - 1)) == 0; };
+  const bool row_major = aids.epilogue != 0 && (a.N & 3) == 0 && (a.ldc & 3) == 0 && (!a.residual || (a.ldres & 3) == 0) &&
+                         al(a.C, 16) && al(a.C_f16, 8) && al(a.bias, 16) && al(a.residual, 16) &&
+                         al(a.aux_out, 8) && al(a.aux_in, 8) &&
+                         // the LDS epilogue reads / writes the pre-activation as f16 only and keeps ONE per-row load
+                         // buffer (residual or pre-activation): everything else goes to the register-epilogue kernel
+                         ((!a.aux_out && a.act != 2) || a.aux_f16) && !(a.residual && a.act == 2);
+  if (!row_major) return CLIPFS_F16_PP_REG;
+  // MFMA shape of the phased kernel.  The board sits at its power cap under f16 MFMA load and holds a higher clock on
+  // 16x16x32 than on 32x32x16 (MI355X_MICROARCH.md, DVFS give-back item 7): 1.58 vs 1.76 us per K-tile and round at
+  // M = 32768, N = 4096 (scripts/ksweep_f16.py: K = 128 ... 4096 150.6 ... 915.3 us vs 154.1 ... 1000.8), so 16x16x32
+  // is the default; 32x32x16 stays as CLIPFS_F16_PHASED=2.
+  const bool phased = aids.phased != 0 && (a.K % 64) == 0 && a.K >= 128;
+  if (!phased) return CLIPFS_F16_PP_LDS;
+  if (aids.phased == 2) return CLIPFS_F16_PH32;
+  // f16-only result without a residual: the 8-columns-per-thread epilogue (16-byte stores / pre-activation loads)
+  const bool wide = !a.C && a.C_f16 && !a.residual && (a.N & 7) == 0 && (a.ldc & 7) == 0 &&
+                    ((reinterpret_cast<uintptr_t>(a.C_f16) | reinterpret_cast<uintptr_t>(a.aux_out) |
+                      reinterpret_cast<uintptr_t>(a.aux_in) | reinterpret_cast<uintptr_t>(a.bias)) & 15) == 0;
+  return wide ? CLIPFS_F16_PH16_WIDE : CLIPFS_F16_PH16;
+}
+
+// rows [begin, end) on the 4-wave kernels: 256 x 128 tiles on the rows that fill whole rounds of 512 workgroup
+// slots (2 per CU), the leftover rows in 64-row tiles behind them; small problems on small tiles
+static void plan_rows_4wave(const clipfs_gemm_args& a, int begin, int end, int tile_cfg, int side, clipfs_f16_plan* o) {
+  const int M = end - begin;
+  const bool lora_ok_256 = !a.lora_t || a.lora_seg_width % 128 == 0;
+  if (tile_cfg == 2) return plan_push(o, CLIPFS_F16_64X128, begin, end, side);
+  if (tile_cfg == 1) return plan_push(o, CLIPFS_F16_128X128, begin, end, side);
+  if (tile_cfg == 3 && lora_ok_256) return plan_push(o, CLIPFS_F16_256X128, begin, end, side);
+  const int nbn = (a.N + 127) / 128;
+  if ((long)((M + 255) / 256) * nbn < 512)
+    return plan_push(o, ((long)((M + 127) / 128) * nbn >= 512) ? CLIPFS_F16_128X128 : CLIPFS_F16_64X128, begin, end, side);
+  const int mb = (M + 255) / 256;
+  const long tiles = (long)mb * nbn;
+  const long over = tiles % 512;  // tiles beyond the last full round of 512 slots
+  int peel_blocks = 0;
+  if (tiles > 512 && over > 0 && over * 8 <= 512) peel_blocks = (int)((over + nbn - 1) / nbn);
+  const int split = begin + (mb - peel_blocks) * 256;
+  if (peel_blocks == 0 || split >= end || split <= begin) return plan_push(o, CLIPFS_F16_256X128, begin, end, side);
+  plan_push(o, CLIPFS_F16_256X128, begin, split, side);
+  plan_push(o, CLIPFS_F16_64X128, split, end, side);
+}
+
+void gemm_f16_make_plan(const clipfs_gemm_args& a, int cus, const F16Aids& aids, clipfs_f16_plan* o) {
+  o->n = 0;
+  for (clipfs_f16_launch& l : o->launch) l.kernel = l.m_begin = l.m_end = l.side = 0;
+  const int tile_cfg = aids.tile;
+  const bool lora_ok_pp = !a.lora_t || a.lora_seg_width % 256 == 0;
+  if (tile_cfg == 4 && lora_ok_pp) return plan_push(o, f16_pp_kernel_id(a, aids), 0, a.M, 0);
+  if (tile_cfg >= 1 && tile_cfg <= 3) return plan_rows_4wave(a, 0, a.M, tile_cfg, 0, o);
+  int begin = 0;
+  // 256 x 256 ping-pong tiles (one workgroup per CU) on the rows that fill whole rounds over the CUs -- a last round is
+  // accepted when it is at least `fill` % full -- and the 4-wave kernels on what is left
+  if (tile_cfg != 5 && lora_ok_pp && a.K >= 4 * BK) {
+    const int nbn = (a.N + 255) / 256;
+    const int mb = a.M / 256;  // whole 256-row blocks
+    const long tiles = (long)mb * nbn;
+    int use_mb = mb;
+    if (tiles >= cus) {
+      const long rem = tiles % cus;
+      if (rem != 0 && rem * 100 < (long)cus * aids.fill) use_mb = (int)((tiles - rem) / nbn);
+    } else if (tiles * 100 < (long)cus * aids.fill) {
+      use_mb = 0;
+    }
+    if (use_mb > 0 && (long)use_mb * 256 * 5 >= (long)a.M * 3) {
+      const int split = use_mb * 256;
+      plan_push(o, f16_pp_kernel_id(a, aids), 0, split, 0);
+      if (split >= a.M) return;
+      if (aids.side != 0) {
+        // leftover rows on the side stream: one launch of two-stage 64 x 128 workgroups while they are few
+        const long small_tiles = (long)((a.M - split + 63) / 64) * ((a.N + 127) / 128);
+        if (small_tiles <= 1024) return plan_push(o, CLIPFS_F16_64X128_S2, split, a.M, 1);
+        return plan_rows_4wave(a, split, a.M, 0, 1, o);
+      }
+      begin = split;
+    }
   }
+  plan_rows_4wave(a, begin, a.M, 0, 0, o);
+}
+
+// CU count of the current device (256 when there is none to ask)
+static int f16_device_cus() {
+  static int cus = 0;
+  if (!cus) {
+    int dev = 0, v = 0;
+    cus = (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess &&
+           v > 0) ? v : 256;
+  }
+  return cus;
+}
+
+// clipfs_gemm_f16_plan (gemm.hip validates the arguments first)
+void gemm_f16_plan(const clipfs_gemm_args& a, int cus, clipfs_f16_plan* out) {
+  gemm_f16_make_plan(a, cus > 0 ? cus : f16_device_cus(), f16_aids(), out);
+}
+
+// one of the five 256 x 256 kernels (CLIPFS_F16_PP_REG ... CLIPFS_F16_PH32) on rows [p.m_begin, p.m_end)
+static int launch_f16_pp(F16Params& p, int kernel, hipStream_t stream) {
+  p.n_blocks_n = (p.a.N + 255) / 256;
+  p.row_major_epilogue = kernel != CLIPFS_F16_PP_REG;
   const int mb = (p.m_end - p.m_begin + 255) / 256;
   const size_t lds = 4 * (size_t)(2 * 256 * 64);
   static bool attr = false;
@@ -1016,28 +1134,14 @@ static int launch_f16_pp(F16Params& p, hipStream_t stream) {
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     attr = true;
   }
-  static const int ph_cfg = getenv("CLIPFS_F16_PHASED") ? atoi(getenv("CLIPFS_F16_PHASED")) : 1;  // 0: the 2-phase kernel, 2: phased on 32x32x16 MFMAs (A/B aids)
-  // MFMA shape of the phased kernel.  The board sits at its power cap under f16 MFMA load and holds a higher clock on
-  // 16x16x32 than on 32x32x16 (MI355X_MICROARCH.md, DVFS give-back item 7): 1.58 vs 1.76 us per K-tile and round at
-  // M = 32768, N = 4096 (scripts/ksweep_f16.py: K = 128 ... 4096 150.6 ... 915.3 us vs 154.1 ... 1000.8), so 16x16x32
-  // is the default; 32x32x16 stays as CLIPFS_F16_PHASED=2.
-  const bool phased = p.row_major_epilogue && ph_cfg != 0 && (p.a.K % 64) == 0 && p.a.K >= 128;
-  const bool shape16 = ph_cfg != 2;
-  // f16-only result without a residual: the 8-columns-per-thread epilogue (16-byte stores / pre-activation loads)
-  const clipfs_gemm_args& ga = p.a;
-  const bool wide = !ga.C && p.C16 && !ga.residual && (ga.N & 7) == 0 && (ga.ldc & 7) == 0 &&
-                    ((reinterpret_cast<uintptr_t>(p.C16) | reinterpret_cast<uintptr_t>(ga.aux_out) |
-                      reinterpret_cast<uintptr_t>(ga.aux_in) | reinterpret_cast<uintptr_t>(ga.bias)) & 15) == 0;
-  if (phased && shape16 && wide)
-    hipLaunchKernelGGL((gemm_f16_ph_kernel<true, true>), dim3(mb * p.n_blocks_n), dim3(512), lds, stream, p);
-  else if (phased && shape16)
-    hipLaunchKernelGGL((gemm_f16_ph_kernel<true, false>), dim3(mb * p.n_blocks_n), dim3(512), lds, stream, p);
-  else if (phased)
-    hipLaunchKernelGGL((gemm_f16_ph_kernel<false, false>), dim3(mb * p.n_blocks_n), dim3(512), lds, stream, p);
-  else if (p.row_major_epilogue)
-    hipLaunchKernelGGL(gemm_f16_pp_kernel<true>, dim3(mb * p.n_blocks_n), dim3(512), lds, stream, p);
-  else
-    hipLaunchKernelGGL(gemm_f16_pp_kernel<false>, dim3(mb * p.n_blocks_n), dim3(512), lds, stream, p);
+  const dim3 grid(mb * p.n_blocks_n), block(512);
+  switch (kernel) {
+    case CLIPFS_F16_PH16_WIDE: hipLaunchKernelGGL((gemm_f16_ph_kernel<true, true>), grid, block, lds, stream, p); break;
+    case CLIPFS_F16_PH16: hipLaunchKernelGGL((gemm_f16_ph_kernel<true, false>), grid, block, lds, stream, p); break;
+    case CLIPFS_F16_PH32: hipLaunchKernelGGL((gemm_f16_ph_kernel<false, false>), grid, block, lds, stream, p); break;
+    case CLIPFS_F16_PP_LDS: hipLaunchKernelGGL(gemm_f16_pp_kernel<true>, grid, block, lds, stream, p); break;
+    default: hipLaunchKernelGGL(gemm_f16_pp_kernel<false>, grid, block, lds, stream, p); break;
+  }
   return launch_status();
 }
 
@@ -1097,35 +1201,20 @@ static SideStream* side_stream_for(hipStream_t main) {
   return &table.back().second;
 }
 
-// rows [p.m_begin, p.m_end) on the 4-wave kernels: 256 x 128 tiles on the rows that fill whole rounds of 512 workgroup
-// slots (2 per CU), the leftover rows in 64-row tiles behind them; small problems on small tiles
-static int dispatch_rows_4wave(F16Params& p, int tile_cfg, hipStream_t stream) {
-  const clipfs_gemm_args& a = p.a;
-  const int M = p.m_end - p.m_begin;
-  const bool lora_ok_256 = !a.lora_t || a.lora_seg_width % 128 == 0;
-  if (tile_cfg == 2) return launch_f16<64, 128>(p, stream);
-  if (tile_cfg == 1) return launch_f16<128, 128>(p, stream);
-  if (tile_cfg == 3 && lora_ok_256) return launch_f16<256, 128>(p, stream);
-  const int nbn = (a.N + 127) / 128;
-  if ((long)((M + 255) / 256) * nbn < 512) {
-    return ((long)((M + 127) / 128) * nbn >= 512) ? launch_f16<128, 128>(p, stream) : launch_f16<64, 128>(p, stream);
+// rows [l.m_begin, l.m_end) on the kernel the plan names
+static int run_f16_launch(F16Params& p, const clipfs_f16_launch& l, hipStream_t stream) {
+  p.m_begin = l.m_begin;
+  p.m_end = l.m_end;
+  switch (l.kernel) {
+    case CLIPFS_F16_64X128: return launch_f16<64, 128>(p, stream);
+    case CLIPFS_F16_64X128_S2: return launch_f16<64, 128, 2>(p, stream);
+    case CLIPFS_F16_128X128: return launch_f16<128, 128>(p, stream);
+    case CLIPFS_F16_256X128: return launch_f16<256, 128>(p, stream);
+    default: return launch_f16_pp(p, l.kernel, stream);
   }
-  const int mb = (M + 255) / 256;
-  const long tiles = (long)mb * nbn;
-  const long over = tiles % 512;  // tiles beyond the last full round of 512 slots
-  int peel_blocks = 0;
-  if (tiles > 512 && over > 0 && over * 8 <= 512) peel_blocks = (int)((over + nbn - 1) / nbn);
-  const int begin = p.m_begin, end = p.m_end;
-  const int split = begin + (mb - peel_blocks) * 256;
-  if (peel_blocks == 0 || split >= end || split <= begin) return launch_f16<256, 128>(p, stream);
-  p.m_end = split;
-  CLIPFS_CHECK((launch_f16<256, 128>(p, stream)));
-  p.m_begin = split;
-  p.m_end = end;
-  return launch_f16<64, 128>(p, stream);
 }
 
-// called from clipfs_gemm_nt when args->A_f16 is set
+// called from clipfs_gemm_nt when args->A_f16 is set: executes the plan of gemm_f16_make_plan
 int gemm_f16_dispatch(const clipfs_gemm_args& a, hipStream_t stream) {
   F16Params p;
   p.a = a;
@@ -1135,62 +1224,31 @@ int gemm_f16_dispatch(const clipfs_gemm_args& a, hipStream_t stream) {
   p.m_begin = 0;
   p.m_end = a.M;
   p.row_major_epilogue = 0;
-  // tuning aid CLIPFS_F16_TILE: 1 / 2 / 3 force the 128x128 / 64x128 / 256x128 4-wave kernel, 4 forces the 256x256
-  // ping-pong kernel on every row, 5 disables it
-  static const int tile_cfg = getenv("CLIPFS_F16_TILE") ? atoi(getenv("CLIPFS_F16_TILE")) : 0;
-  const bool lora_ok_pp = !a.lora_t || a.lora_seg_width % 256 == 0;
-  if (tile_cfg == 4 && lora_ok_pp) return launch_f16_pp(p, stream);
-  if (tile_cfg >= 1 && tile_cfg <= 3) return dispatch_rows_4wave(p, tile_cfg, stream);
-  // 256 x 256 ping-pong tiles (one workgroup per CU) on the rows that fill whole rounds over the CUs -- a last round is
-  // accepted when it is at least 80 % full -- and the 4-wave kernels on what is left
-  if (tile_cfg != 5 && lora_ok_pp && a.K >= 4 * BK) {
-    static int cus = 0;
-    if (!cus) {
-      int dev = 0, v = 0;
-      cus = (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess &&
-             v > 0) ? v : 256;
-    }
-    const int nbn = (a.N + 255) / 256;
-    const int mb = a.M / 256;  // whole 256-row blocks
-    long tiles = (long)mb * nbn;
-    int use_mb = mb;
-    static const int fill = getenv("CLIPFS_F16_PP_FILL") ? atoi(getenv("CLIPFS_F16_PP_FILL")) : 30;  // percent
-    if (tiles >= cus) {
-      const long rem = tiles % cus;
-      if (rem != 0 && rem * 100 < (long)cus * fill) use_mb = (int)((tiles - rem) / nbn);
-    } else if (tiles * 100 < (long)cus * fill) {
-      use_mb = 0;
-    }
-    if (use_mb > 0 && (long)use_mb * 256 * 5 >= (long)a.M * 3) {
-      const int split = use_mb * 256;
-      static const int side_cfg = getenv("CLIPFS_F16_SIDE") ? atoi(getenv("CLIPFS_F16_SIDE")) : 1;  // 0: same stream (A/B aid)
-      SideStream* side = (side_cfg != 0 && split < a.M) ? side_stream_for(stream) : nullptr;
-      if (side) {
-        // leftover rows first, on the side stream (ordered after everything already queued on `stream`)
-        F16_HIP(hipEventRecord(side->fork, stream));
-        F16_HIP(hipStreamWaitEvent(side->stream, side->fork, 0));
-        F16Params q = p;
-        q.m_begin = split;
-        q.m_end = a.M;
-        const long small_tiles = (long)((a.M - split + 63) / 64) * ((a.N + 127) / 128);
-        if (small_tiles <= 1024)
-          CLIPFS_CHECK((launch_f16<64, 128, 2>(q, side->stream)));
-        else
-          CLIPFS_CHECK(dispatch_rows_4wave(q, 0, side->stream));
-        F16_HIP(hipEventRecord(side->join, side->stream));
-      }
-      p.m_end = split;
-      CLIPFS_CHECK(launch_f16_pp(p, stream));
-      if (side) {
-        F16_HIP(hipStreamWaitEvent(stream, side->join, 0));
-        return CLIPFS_OK;
-      }
-      if (p.m_end >= a.M) return CLIPFS_OK;
-      p.m_begin = p.m_end;
-      p.m_end = a.M;
-    }
+  clipfs_f16_plan plan;
+  gemm_f16_make_plan(a, f16_device_cus(), f16_aids(), &plan);
+  auto wants_side = [&]() {
+    for (int i = 0; i < plan.n; ++i)
+      if (plan.launch[i].side) return true;
+    return false;
+  };
+  SideStream* side = nullptr;
+  if (wants_side() && !(side = side_stream_for(stream))) {  // no side stream to be had: the same-stream plan
+    F16Aids aids = f16_aids();
+    aids.side = 0;
+    gemm_f16_make_plan(a, f16_device_cus(), aids, &plan);
   }
-  return dispatch_rows_4wave(p, 0, stream);
+  if (side) {
+    // leftover rows first, on the side stream (ordered after everything already queued on `stream`)
+    F16_HIP(hipEventRecord(side->fork, stream));
+    F16_HIP(hipStreamWaitEvent(side->stream, side->fork, 0));
+    for (int i = 0; i < plan.n; ++i)
+      if (plan.launch[i].side) CLIPFS_CHECK(run_f16_launch(p, plan.launch[i], side->stream));
+    F16_HIP(hipEventRecord(side->join, side->stream));
+  }
+  for (int i = 0; i < plan.n; ++i)
+    if (!plan.launch[i].side) CLIPFS_CHECK(run_f16_launch(p, plan.launch[i], stream));
+  if (side) F16_HIP(hipStreamWaitEvent(stream, side->join, 0));
+  return CLIPFS_OK;
 }
 
 }  // namespace clipfs

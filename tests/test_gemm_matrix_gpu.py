@@ -22,10 +22,10 @@ import pytest
 import torch
 
 from gemm_matrix_cases import (BK, PLANE_SHAPES, SCHEDULE_CLASSES, ceil_div, lora_seg_width, plane_big_tile)
+from gemm_matrix_helpers import SENT, _embed, _err, _nan_f32, _untouched, ref_gemm
 
 pytestmark = pytest.mark.gpu
 
-SENT = 0x7FC5A5A5          # a quiet NaN nobody computes
 GUARD_ROWS = 3
 WS_TAIL = 4096             # floats behind the workspace
 CNT_TAIL = 64              # ints behind the counters
@@ -67,61 +67,7 @@ EPI = {e["name"]: e for e in EPILOGUES}
 LORA_RANKS = sorted({e["lora_r"] for e in EPILOGUES if e["lora_r"]})
 
 
-# ------------------------------------------------------------------ the one reference
-def quick_gelu(x):
-    return x * torch.sigmoid(1.702 * x)
-
-
-def quick_gelu_grad(x):
-    s = torch.sigmoid(1.702 * x)
-    return s + 1.702 * x * s * (1.0 - s)
-
-
-def ref_gemm(a, b, *, alpha=1.0, bias=None, lora=None, act=0, aux_in=None, residual=None, acc=None):
-    """fp64 restatement of the epilogue order of include/clipfs.h.  a [M,K], b [N,K]; lora = (t [M, nseg r], lb [N, r],
-    segment width, scale); returns (C, pre_activation) (the latter None unless act == 1).  `acc` = a @ b.T when the
-    caller already has it."""
-    assert all(x is None or (x.dtype == torch.float64 and not x.is_cuda) for x in (a, b, bias, aux_in, residual, acc))
-    v = (a @ b.t() if acc is None else acc) * alpha
-    if bias is not None:
-        v = v + bias
-    if lora is not None:
-        t, lb, seg, scale = lora
-        r = lb.shape[1]
-        N = v.shape[1]
-        v = v.clone()
-        for s in range(t.shape[1] // r):
-            lo, hi = s * seg, min((s + 1) * seg, N)
-            if lo < hi:
-                v[:, lo:hi] += scale * (t[:, s * r:(s + 1) * r] @ lb[lo:hi].t())
-    pre = None
-    if act == 1:
-        pre = v
-        v = quick_gelu(v)
-    elif act == 2:
-        v = v * quick_gelu_grad(aux_in)
-    if residual is not None:
-        v = v + residual
-    if act == 3:
-        v = torch.clamp(v, min=0.0)
-    return v, pre
-
-
 # ------------------------------------------------------------------ inputs, once per shape
-def _nan_f32(*shape, dev):
-    return torch.full(shape, SENT, dtype=torch.int32, device=dev).view(torch.float32)
-
-
-def _embed(x, rows, ld, dev, row_index=None):
-    """x [m, n] inside a NaN matrix [rows, ld] (at `row_index` rows, default the first m)"""
-    buf = _nan_f32(rows, ld, dev=dev)
-    if row_index is None:
-        buf[:x.shape[0], :x.shape[1]] = x.to(dev)
-    else:
-        buf[:, :x.shape[1]][row_index.to(dev)] = x.to(dev)
-    return buf
-
-
 class Problem:
     """Seeded inputs of one (shape, layout), their device images and the fp64 products; shared by every variant."""
 
@@ -207,10 +153,6 @@ def problem(dev, M, N, K, *, pad=True, ldb_pad=True, patch=None):
 
 
 # ------------------------------------------------------------------ the one driver
-def _untouched(buf):
-    return bool((buf.view(torch.int32) == SENT).all().item())
-
-
 def run_gemm(dev, shape, epilogue, *, precision="fp32", split=True, pad=True, patch=None, ldb_pad=None, expect_rc=0):
     """One clipfs_gemm_nt call on padded, guarded buffers.  Asserts that the guards of C / aux_out, the workspace tail
     and the counters are as the call found them; returns (C [M,N], aux_out [M,N] or None, bits of both whole buffers)."""
@@ -285,12 +227,6 @@ def run_gemm(dev, shape, epilogue, *, precision="fp32", split=True, pad=True, pa
     out = c_buf[:, :N][rows].cpu()
     aux = aux_buf[:, :N][rows].cpu() if writes_aux else None
     return out, aux, (c_buf.view(torch.int32), aux_buf.view(torch.int32))
-
-
-def _err(got, want):
-    """max |got - want|; NaN (an element never written, or computed from padding) counts as infinite"""
-    d = (got.double() - want).abs()
-    return float("inf") if torch.isnan(d).any() else d.max().item()
 
 
 def check_case(dev, shape, epi_name, *, precision="fp32", patch=None, ldb_pad=None, splits=1, budget_of=None):
