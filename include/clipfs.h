@@ -225,19 +225,52 @@ int clipfs_layernorm_fwd_lora_map(const float* x, int ldx, const float* gamma, c
 int clipfs_attention_fwd(const float* qkv, float* out, float* lse, int batch, int seq, int heads, int causal,
                          void* stream);
 /* dqkv from dout, recomputing the probabilities from qkv.
- * Default path, seq <= clipfs_attention_mfma_max_seq(): exact-fp32 MFMA kernels (v_mfma_f32_32x32x2_f32, scores kept
- * transposed so that the softmax statistics are per-lane scalars).  Up to 288 tokens one workgroup takes a (batch, head)
- * with the other side's transposed image whole in LDS; past that the own side is cut into runs of 32-token tiles, one
- * workgroup each, and the other side passes through LDS in chunks of at most 288 tokens -- the same tile arithmetic in the
- * same order, every output element written by one wave, so results are bitwise reproducible at every length.  The
- * forward writes lse [clipfs_attention_lse_floats] (log-sum-exp of the scaled scores per (batch, head, query)) when
- * given the buffer; the backward takes the forward's `out`, that `lse` and a `work` buffer of the same size.
- * Without lse: seq <= 96 falls back to register/LDS-resident VALU kernels that recompute the softmax (out, lse and
- * work may be NULL); seq > 96 requires lse.  Streaming VALU kernels with an online softmax take what the MFMA kernels do
- * not: seq > clipfs_attention_mfma_max_seq(), misaligned out / dqkv, CLIPFS_ATTN_MFMA=0. */
+ * Default path, seq <= clipfs_attention_mfma_max_seq(): exact-fp32 MFMA kernels (scores kept transposed so that the
+ * softmax statistics are per-lane scalars).  Up to 96 tokens 16-token tiles with every operand in LDS; up to 288 tokens
+ * one workgroup of 32-token tiles takes a (batch, head) with the other side's transposed image whole in LDS; past that the
+ * own side is cut into runs of 32-token tiles, one workgroup each, and the other side passes through LDS in chunks of at
+ * most 288 tokens -- the same tile arithmetic in the same order, every output element written by one wave, so results are
+ * bitwise reproducible at every length.  The forward writes lse [clipfs_attention_lse_floats = batch * heads * seq]
+ * (log-sum-exp of the scaled scores per (batch, head, query)) when given the buffer -- no kernel is chosen by it; the
+ * backward takes the forward's `out`, that `lse` and a `work` buffer of the same size.
+ * What the MFMA kernels decline -- seq > clipfs_attention_mfma_max_seq() (up to 4096), an out / dqkv that is not 16-byte
+ * aligned (same function, not the same bits), CLIPFS_ATTN_MFMA=0 at every length -- runs on streaming VALU kernels with
+ * an online softmax.  A backward without out, lse or work: seq <= 96 runs a VALU kernel that recomputes the softmax,
+ * seq > 96 is refused.  clipfs_attention_plan tells which of these a call gets. */
 int clipfs_attention_bwd(const float* qkv, const float* dout, const float* out, const float* lse, float* dqkv,
                          float* work, int batch, int seq, int heads, int causal, void* stream);
 size_t clipfs_attention_lse_floats(int batch, int seq, int heads);
+/* The dispatch of the five entry points as data: clipfs_attention_plan IS the function they execute.  Host-only (no GPU
+ * is opened, nothing is launched).  Returns CLIPFS_EINVAL with the refusal's message for what the entry point would
+ * refuse.  The aids CLIPFS_ATTN_MFMA=0 (streaming kernels at every length) and CLIPFS_ATTN16=0 (32-token tiles below 97
+ * tokens too, no packed kernels) are read once per process and show in the plan. */
+#define CLIPFS_ATTN_FWD 0             /* direction: clipfs_attention_fwd */
+#define CLIPFS_ATTN_BWD 1             /*   clipfs_attention_bwd */
+#define CLIPFS_ATTN_FWD_PACKED 2      /*   clipfs_attention_fwd_packed */
+#define CLIPFS_ATTN_BWD_PACKED 3      /*   clipfs_attention_bwd_packed (dense records) */
+#define CLIPFS_ATTN_BWD_PACKED_IO 4   /*   clipfs_attention_bwd_packed_io (packed records) */
+#define CLIPFS_ATTN_STATS 1           /* flag: backward has out, lse and work (forward: lse asked for; changes nothing) */
+#define CLIPFS_ATTN_ALIGNED 2         /* flag: out / dqkv are 16-byte aligned */
+#define CLIPFS_ATTN_MFMA16 0          /* family: 16-token-tile MFMA, `nt` tiles (seq <= 96) */
+#define CLIPFS_ATTN_MFMA16_PACKED 1   /*   ... on live rows, records dense */
+#define CLIPFS_ATTN_MFMA16_PINNED 2   /*   ... on live rows, records packed too */
+#define CLIPFS_ATTN_MFMA32 3          /*   32-token-tile MFMA, one workgroup per head (seq <= 288) */
+#define CLIPFS_ATTN_MFMA_LONG 4       /*   the same tiles in `parts` runs of `tiles`, other side in chunks of `ctok` */
+#define CLIPFS_ATTN_STREAM 5          /*   streaming VALU */
+#define CLIPFS_ATTN_RECOMPUTE 6       /*   softmax-recomputing VALU backward, instance `lmax` (64, 80, 96) */
+struct clipfs_attention_launch {
+  unsigned grid_x, grid_y, block, lds_bytes; /* lds_bytes: dynamic LDS */
+};
+struct clipfs_attention_plan {
+  int family;               /* CLIPFS_ATTN_* family */
+  int nt;                   /* MFMA16*: 16-token tiles, 1 .. 6 (0 otherwise, as the next four) */
+  int parts, tiles, ctok;   /* MFMA_LONG: the cut */
+  int lmax;                 /* RECOMPUTE */
+  int launches;             /* 1 or 2 */
+  struct clipfs_attention_launch launch[2];
+};
+int clipfs_attention_plan(int direction, int batch, int seq, int heads, int causal, int flags,
+                          struct clipfs_attention_plan* plan);
 /* Longest sequence the exact-fp32 MFMA attention takes (1024). */
 int clipfs_attention_mfma_max_seq(void);
 /* The long-sequence MFMA kernels with an explicit cut, for any 96 < seq <= clipfs_attention_mfma_max_seq() (the default

@@ -52,6 +52,20 @@ class F16Plan(C.Structure):
     _fields_ = [("n", C.c_int), ("launch", F16Launch * 3)]
 
 
+class AttentionLaunch(C.Structure):
+    _fields_ = [("grid_x", C.c_uint), ("grid_y", C.c_uint), ("block", C.c_uint), ("lds_bytes", C.c_uint)]
+
+
+class AttentionPlan(C.Structure):
+    _fields_ = [("family", C.c_int), ("nt", C.c_int), ("parts", C.c_int), ("tiles", C.c_int), ("ctok", C.c_int),
+                ("lmax", C.c_int), ("launches", C.c_int), ("launch", AttentionLaunch * 2)]
+
+
+# CLIPFS_ATTN_* directions, flags and kernel families of include/clipfs.h, by value
+ATTN_DIRECTIONS = ("fwd", "bwd", "fwd_packed", "bwd_packed", "bwd_packed_io")
+ATTN_STATS, ATTN_ALIGNED = 1, 2
+ATTN_FAMILIES = ("mfma16", "mfma16_packed", "mfma16_pinned", "mfma32", "mfma_long", "stream", "recompute")
+
 # CLIPFS_F16_* kernel ids of include/clipfs.h, by value
 F16_KERNELS = ("64x128", "64x128_s2", "128x128", "256x128", "pp_reg", "pp_lds", "ph16", "ph16_wide", "ph32")
 
@@ -114,6 +128,7 @@ SIGNATURES = {
     "clipfs_attention_fwd": (_i, [_p, _p, _p, _i, _i, _i, _i, _p]),
     "clipfs_attention_bwd": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p]),
     "clipfs_attention_lse_floats": (_sz, [_i, _i, _i]),
+    "clipfs_attention_plan": (_i, [_i, _i, _i, _i, _i, _i, C.POINTER(AttentionPlan)]),
     "clipfs_attention_mfma_max_seq": (_i, []),
     "clipfs_attention_mfma_long_fwd": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
     "clipfs_attention_mfma_long_bwd": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
@@ -217,6 +232,20 @@ def gemm_f16_plan(g: GemmArgs, cus: int = 0):
     plan = F16Plan()
     check(load().clipfs_gemm_f16_plan(C.byref(g), cus, C.byref(plan)), "gemm_f16_plan")
     return [(F16_KERNELS[l.kernel], l.m_begin, l.m_end, bool(l.side)) for l in plan.launch[:plan.n]]
+
+
+def attention_plan(direction: str, batch: int, seq: int, heads: int, causal: bool, stats: bool = True, aligned: bool = True):
+    """The plan clipfs_attention_fwd / _bwd and their packed forms execute for these arguments (host-only), as a dict:
+    family, the family's own fields (nt | parts, tiles, ctok | lmax) and launches = ((grid_x, grid_y, block, lds_bytes), ...).
+    A refusal raises ClipfsError with its message."""
+    plan = AttentionPlan()
+    flags = (ATTN_STATS if stats else 0) | (ATTN_ALIGNED if aligned else 0)
+    check(load().clipfs_attention_plan(ATTN_DIRECTIONS.index(direction), batch, seq, heads, int(causal), flags, C.byref(plan)),
+          "attention_plan")
+    own = {"mfma16": ("nt",), "mfma16_packed": ("nt",), "mfma16_pinned": ("nt",), "mfma_long": ("parts", "tiles", "ctok"),
+           "recompute": ("lmax",)}.get(ATTN_FAMILIES[plan.family], ())
+    return dict(family=ATTN_FAMILIES[plan.family], **{k: getattr(plan, k) for k in own},
+                launches=tuple((l.grid_x, l.grid_y, l.block, l.lds_bytes) for l in plan.launch[:plan.launches]))
 
 
 def new_tower() -> Tower:

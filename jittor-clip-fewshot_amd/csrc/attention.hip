@@ -1,18 +1,24 @@
-// Self-attention forward / backward for head_dim 64 and short sequences (CLIP ViT-B/32: L = 50, 54 with
-// VPT; text: L = 77), one workgroup (4 waves) per (batch, head).
+// Exact-fp32 self-attention for head_dim 64: the ONE dispatch plan of clipfs_attention_fwd / _bwd and their packed
+// (live-row) forms, and the VALU kernels that take what the matrix-core kernels decline.
 //
-// ~1 % of the layer's FLOPs, and the fp32 matrix rate equals the fp32 vector rate on gfx950, so this runs on
-// the VALU -- what matters is operand delivery.  v1 read one LDS word per FMA (LDS-bound, 20 % VALU
-// utilisation); here every inner loop is  FMA(register operand, broadcast operand):
-//   * "row" operands (K rows, V rows: lane = key j) and "column" operands (V / K / Q / dO columns:
-//     lane = feature d) live in VGPRs, loaded once per wave;
-//   * the broadcast operand is either a wave-uniform global row (q_i, dO_i: scalar/broadcast loads) or a
-//     probability / score-gradient vector that the wave parked in LDS and reads back 4 at a time with one
-//     same-address ds_read_b128 (1 LDS instruction per 4 FMAs);
-//   * softmax max / sum are DPP wave reductions (common.h).
-// The [L, L] matrices of the reference (jclip/mha.py:79-83: a 30-77 MB HBM round trip per layer) stay on
-// chip: registers in the forward, LDS (P^T, dS^T, dS) in the backward.  Heads are merged by the store
-// address (no permute pass, mha.py:458).
+// The path is on the matrix cores: 16-token tiles up to 96 tokens (attention_mfma16.hip), 32-token tiles up to 288 and
+// runs of tiles against a chunked other side up to 1024 (attention_mfma.hip).  attention_plan() below is the only place
+// that chooses between them: direction, seq, causal, flags -> kernel family, launches, grid, block, dynamic LDS.  The
+// entry points execute that plan, clipfs_attention_plan() returns it without opening a GPU, and
+// tests/test_attention_plan.py pins it.  Each kernel file states the geometry of its own family (attention16_plan,
+// attention_mfma_plan, attention_mfma_long_plan); nothing outside attention_plan() decides a family.
+//
+// The kernels of this file:
+//   * attention_generic_*: one wave per query (forward, dQ) or key (dK, dV) row, the other side streamed from L2 in
+//     blocks of 64 with an online softmax.  Correct for any length and any alignment of out / dqkv, not tuned: the
+//     fallback for seq > 1024, a misaligned out / dqkv, and CLIPFS_ATTN_MFMA=0.
+//   * attention_bwd_kernel<LMAX>: one workgroup per (batch, head), seq <= 96, recomputes the softmax from q and k:
+//     the backward of a caller that did not keep the forward's out / lse.  Every inner loop is
+//     FMA(register operand, broadcast operand): "row" operands (lane = key) and "column" operands (lane = feature)
+//     live in VGPRs, the broadcast operand is a wave-uniform global row or a vector parked in LDS and read back 4 at
+//     a time with one same-address ds_read_b128; softmax max / sum are DPP wave reductions (common.h).
+// The [L, L] matrices of the reference (jclip/mha.py:79-83: a 30-77 MB HBM round trip per layer) never leave the chip,
+// and heads are merged by the store address (no permute pass, mha.py:458).
 #include "common.h"
 
 #include <stdlib.h>
@@ -134,94 +140,6 @@ __device__ __forceinline__ float bcast_dot(const float* __restrict__ vec, const 
   return (a0 + a1) + (a2 + a3);
 }
 
-// two query rows (uniform global rows u0, u1) against this lane's K rows read from the staged LDS image:
-// each ds_read_b128 of K feeds 8 FMAs (used when the K rows do not fit in VGPRs next to the V column)
-template <int KPL>
-__device__ __forceinline__ void dot_rows_lds2(const float* __restrict__ u0, const float* __restrict__ u1,
-                                              const float* __restrict__ sK, int lane, int L, float (&o0)[KPL],
-                                              float (&o1)[KPL]) {
-  const float* row[KPL];
-#pragma unroll
-  for (int kk = 0; kk < KPL; ++kk) {
-    const int j = lane + 64 * kk;
-    row[kk] = sK + (j < L ? j : 0) * KSTRIDE;  // rows >= L are masked to -inf afterwards
-    o0[kk] = o1[kk] = 0.f;
-  }
-#pragma unroll
-  for (int c = 0; c < HD / 4; ++c) {
-    const f32x4 qa = *reinterpret_cast<const f32x4*>(u0 + 4 * c);
-    const f32x4 qb = *reinterpret_cast<const f32x4*>(u1 + 4 * c);
-#pragma unroll
-    for (int kk = 0; kk < KPL; ++kk) {
-      const f32x4 k = *reinterpret_cast<const f32x4*>(row[kk] + 4 * c);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        o0[kk] = fmaf(qa[e], k[e], o0[kk]);
-        o1[kk] = fmaf(qb[e], k[e], o1[kk]);
-      }
-    }
-  }
-}
-
-template <int LMAX>
-__global__ __launch_bounds__(512) void attention_fwd_kernel(const float* __restrict__ qkv, float* __restrict__ out,
-                                                            int L, int H, int causal) {
-  constexpr int KPL = (LMAX + 63) / 64;
-  constexpr int PROW = 64 * KPL;
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  float* sK = smem;                 // [L][KSTRIDE] staged K rows
-  float* sP = smem + L * KSTRIDE;   // [16][PROW] probability rows of the waves' current queries
-  const int NW = (int)blockDim.x >> 6;
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int b = blockIdx.x / H, h = blockIdx.x % H;
-  const int d = H * HD;
-  const size_t ld = (size_t)3 * d;
-  const float* q0 = qkv + (size_t)b * L * ld + (size_t)h * HD;
-  float* o0 = out + (size_t)b * L * d + (size_t)h * HD;
-  stage_rows(q0 + d, ld, sK, L, tid);
-  float vcol[LMAX];
-  col_to_regs<LMAX>(q0 + 2 * d, ld, lane, L, vcol);  // V[:, lane]
-  __syncthreads();
-  if constexpr (KPL == 1) {
-    float krow[KPL][HD];
-    rows_to_regs<KPL>(sK, lane, L, krow);
-    float* myP = sP + wave * PROW;
-    for (int i = wave; i < L; i += NW) {
-      float s[KPL];
-      dot_rows<KPL>(q0 + (size_t)i * ld, krow, s, causal ? i + 1 : L);
-      softmax_row<KPL>(s, i, lane, L, causal);
-      myP[lane] = s[0];
-      __builtin_amdgcn_wave_barrier();  // same wave writes then reads: LDS is in order per wave
-      const float o = bcast_dot<LMAX>(myP, vcol, causal ? i + 1 : L);
-      __builtin_amdgcn_wave_barrier();
-      o0[(size_t)i * d + lane] = o;
-    }
-  } else {
-    float* pa = sP + (2 * wave) * PROW;
-    float* pb = pa + PROW;
-    for (int i = wave; i < L; i += 2 * NW) {
-      const int i2 = i + NW;
-      const bool two = i2 < L;
-      float sa[KPL], sb[KPL];
-      dot_rows_lds2<KPL>(q0 + (size_t)i * ld, q0 + (size_t)(two ? i2 : i) * ld, sK, lane, L, sa, sb);
-      softmax_row<KPL>(sa, i, lane, L, causal);
-      softmax_row<KPL>(sb, two ? i2 : i, lane, L, causal);
-#pragma unroll
-      for (int kk = 0; kk < KPL; ++kk) {
-        pa[lane + 64 * kk] = sa[kk];
-        pb[lane + 64 * kk] = sb[kk];
-      }
-      __builtin_amdgcn_wave_barrier();
-      const float oa = bcast_dot<LMAX>(pa, vcol, causal ? i + 1 : L);
-      const float ob = bcast_dot<LMAX>(pb, vcol, causal ? (two ? i2 : i) + 1 : L);
-      __builtin_amdgcn_wave_barrier();
-      o0[(size_t)i * d + lane] = oa;
-      if (two) o0[(size_t)i2 * d + lane] = ob;
-    }
-  }
-}
-
 // Backward: dQ = scale dS K, dK = scale dS^T Q, dV = P^T dO, dS = P * (dP - rowsum(P * dP)), dP = dO V^T.
 // P is recomputed (phase A1), never stored in HBM.  Phases (register sets are reused between phases):
 //   A1  lane = key, K rows in VGPRs : P_i  -> LDS P^T[j][i]
@@ -318,10 +236,10 @@ __global__ __launch_bounds__(512) void attention_bwd_kernel(const float* __restr
 
 
 // ---------------------------------------------------------------------------------------------------------
-// Long sequences (ViT-L/14: L = 257): K/V no longer fit next to a wave's registers, so these kernels stream key
-// (or query) blocks of 64 from L2 with an online softmax -- one wave per query row (forward, dQ) or per key row
-// (dK, dV).  Correct for any L; not tuned (the B/32 path never takes them).  lse[(b*H + h)*L + i] =
-// max_i + log(sum_i) of the scaled scores is written by the forward and reused by the backward.
+// The streaming kernels: key (or query) blocks of 64 come from L2 with an online softmax -- one wave per query row
+// (forward, dQ) or per key row (dK, dV).  Correct for any L and any alignment of out / dqkv; not tuned (no default plan
+// of the project's towers returns them).  lse[(b*H + h)*L + i] = max_i + log(sum_i) of the scaled scores is written by
+// the forward when it is given the buffer and reused by the backward.
 // ---------------------------------------------------------------------------------------------------------
 
 __device__ __forceinline__ float dot64_row(const f32x4 (&u)[HD / 4], const float* __restrict__ row) {
@@ -473,359 +391,204 @@ __global__ __launch_bounds__(256) void attention_generic_bwd_kv_kernel(const flo
   dqkv[((size_t)b * L + j) * ld + d + h * HD + lane] = ak;
 }
 
+// ---- the kernel files' share of the plan and their launchers ------------------------------------------------------
+// attention_mfma16.hip: 16-token tiles (seq <= 96), dense / packed / pinned (family = CLIPFS_ATTN_MFMA16*)
+void attention16_plan(int family, bool backward, int batch, int seq, int heads, AttnPlan& p);
+int attention16_fwd(const AttnPlan& p, const float* qkv, float* out, float* lse, const int32_t* off, int seq, int heads,
+                    int causal, hipStream_t st);
+int attention16_bwd(const AttnPlan& p, const float* qkv, const float* dout, const float* out, const float* lse, float* dqkv,
+                    const int32_t* off, int seq, int heads, int causal, hipStream_t st);
+// attention_mfma.hip: 32-token tiles, one workgroup per head (seq <= 288) ...
+void attention_mfma_plan(bool backward, int batch, int seq, int heads, AttnPlan& p);
+int attention_mfma_fwd(const AttnPlan& p, const float* qkv, float* out, float* lse, int seq, int heads, int causal,
+                       hipStream_t st);
+int attention_mfma_bwd(const AttnPlan& p, const float* qkv, const float* dout, const float* out, const float* lse,
+                       float* dqkv, float* work, int seq, int heads, int causal, hipStream_t st);
+// ... and the long form (seq <= clipfs_attention_mfma_max_seq()); chunk_tokens = run_tiles = 0: the default cut
+int attention_mfma_long_plan(const char* what, bool backward, int batch, int seq, int heads, int chunk_tokens, int run_tiles,
+                             AttnPlan& p);
+int attention_mfma_long_fwd(const AttnPlan& p, const float* qkv, float* out, float* lse, int seq, int heads, int causal,
+                            hipStream_t st);
+int attention_mfma_long_bwd(const AttnPlan& p, const float* qkv, const float* dout, const float* out, const float* lse,
+                            float* dqkv, float* work, int seq, int heads, int causal, hipStream_t st);
 
-// ---------------------------------------------------------------------------------------------------------
-// Medium sequences (96 < L <= 300; ViT-L/14: 257): one workgroup of 8 waves per (batch, head) with the head's K and V
-// (or Q and dO) resident in LDS -- 2 x L x 68 floats = 140 KB at L = 257 -- instead of being re-streamed from L2 per
-// query row.  A wave owns one query (key) row at a time: its row is wave-uniform (scalar loads), the LDS rows are
-// read by the lane that owns that key (16 conflict-free ds_read_b128 at row stride 68) and column-wise
-// (ds_read_b32, lane = feature) for the accumulations; online softmax over key blocks of 64.
-// ---------------------------------------------------------------------------------------------------------
+constexpr int ATTN16_MAX = 96;      // 16-token tiles; also the longest sequence of the recomputing backward
+constexpr int ATTN_MFMA_MAX = 288;  // 32-token tiles with the other side whole in LDS
+constexpr int ATTN_MAX_SEQ = 4096;
 
-// acc[lane] += sum_{t < n} vec[t] * rows[(j0 + t) * KSTRIDE + lane]     (rows: LDS image, vec: the wave's LDS slot)
-__device__ __forceinline__ float axpy_block_lds(const float* __restrict__ vec, const float* __restrict__ rows, int lane,
-                                                int n, float acc) {
-  float a0 = acc, a1 = 0.f;
-  int t = 0;
-  for (; t + 4 <= n; t += 4) {
-    const f32x4 p = *reinterpret_cast<const f32x4*>(vec + t);
-    a0 = fmaf(p[0], rows[(t + 0) * KSTRIDE + lane], a0);
-    a1 = fmaf(p[1], rows[(t + 1) * KSTRIDE + lane], a1);
-    a0 = fmaf(p[2], rows[(t + 2) * KSTRIDE + lane], a0);
-    a1 = fmaf(p[3], rows[(t + 3) * KSTRIDE + lane], a1);
-  }
-  for (; t < n; ++t) a0 = fmaf(vec[t], rows[t * KSTRIDE + lane], a0);
-  return a0 + a1;
-}
-
-__device__ __forceinline__ void stage_rows_n(const float* __restrict__ base, size_t ld, float* __restrict__ dst, int L) {
-  for (int idx = threadIdx.x; idx < L * (HD / 4); idx += (int)blockDim.x) {
-    const int r = idx >> 4, c = idx & 15;
-    *reinterpret_cast<f32x4*>(dst + r * KSTRIDE + 4 * c) = *reinterpret_cast<const f32x4*>(base + (size_t)r * ld + 4 * c);
-  }
-}
-
-__global__ __launch_bounds__(512) void attention_lds_fwd_kernel(const float* __restrict__ qkv, float* __restrict__ out,
-                                                                float* __restrict__ lse, int L, int H, int causal) {
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  float* sK = smem;
-  float* sV = sK + L * KSTRIDE;
-  float* sP = sV + L * KSTRIDE;  // [8][64]
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int b = blockIdx.x / H, h = blockIdx.x % H;
-  const int d = H * HD;
-  const size_t ld = (size_t)3 * d;
-  const float* q0 = qkv + (size_t)b * L * ld + (size_t)h * HD;
-  stage_rows_n(q0 + d, ld, sK, L);
-  stage_rows_n(q0 + 2 * d, ld, sV, L);
-  __syncthreads();
-  float* myP = sP + wave * 64;
-  for (int i = wave; i < L; i += 8) {
-    f32x4 q[HD / 4];
-#pragma unroll
-    for (int c = 0; c < HD / 4; ++c) q[c] = *reinterpret_cast<const f32x4*>(q0 + (size_t)i * ld + 4 * c);  // uniform
-    float m = -INFINITY, l = 0.f, o = 0.f;
-    const int jend = causal ? i + 1 : L;
-    for (int j0 = 0; j0 < jend; j0 += 64) {
-      const int j = j0 + lane;
-      float sc = -INFINITY;
-      if (j < jend) sc = dot64_row(q, sK + j * KSTRIDE) * 0.125f;
-      const float mn = fmaxf(m, wave_max(sc));
-      const float pj = __expf(sc - mn);
-      const float f = __expf(m - mn);
-      l = l * f + wave_sum(pj);
-      myP[lane] = pj;
-      __builtin_amdgcn_wave_barrier();
-      o = axpy_block_lds(myP, sV + j0 * KSTRIDE, lane, min(64, jend - j0), o * f);
-      __builtin_amdgcn_wave_barrier();
-      m = mn;
-    }
-    out[((size_t)b * L + i) * d + h * HD + lane] = o / l;
-    if (lse && lane == 0) lse[((size_t)b * H + h) * L + i] = m + __logf(l);
-  }
-}
-
-__global__ __launch_bounds__(512) void attention_lds_bwd_q_kernel(const float* __restrict__ qkv,
-                                                                  const float* __restrict__ dout,
-                                                                  const float* __restrict__ out,
-                                                                  const float* __restrict__ lse, float* __restrict__ dqkv,
-                                                                  float* __restrict__ Dbuf, int L, int H, int causal) {
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  float* sK = smem;
-  float* sV = sK + L * KSTRIDE;
-  float* sP = sV + L * KSTRIDE;
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int b = blockIdx.x / H, h = blockIdx.x % H;
-  const int d = H * HD;
-  const size_t ld = (size_t)3 * d;
-  const float* q0 = qkv + (size_t)b * L * ld + (size_t)h * HD;
-  stage_rows_n(q0 + d, ld, sK, L);
-  stage_rows_n(q0 + 2 * d, ld, sV, L);
-  __syncthreads();
-  float* myP = sP + wave * 64;
-  for (int i = wave; i < L; i += 8) {
-    const float* do_i = dout + ((size_t)b * L + i) * d + h * HD;
-    f32x4 q[HD / 4], g[HD / 4];
-#pragma unroll
-    for (int c = 0; c < HD / 4; ++c) {
-      q[c] = *reinterpret_cast<const f32x4*>(q0 + (size_t)i * ld + 4 * c);
-      g[c] = *reinterpret_cast<const f32x4*>(do_i + 4 * c);
-    }
-    const float Di = wave_sum(do_i[lane] * out[((size_t)b * L + i) * d + h * HD + lane]);
-    const float li = lse[((size_t)b * H + h) * L + i];
-    if (lane == 0) Dbuf[((size_t)b * H + h) * L + i] = Di;
-    float acc = 0.f;
-    const int jend = causal ? i + 1 : L;
-    for (int j0 = 0; j0 < jend; j0 += 64) {
-      const int j = j0 + lane;
-      float ds = 0.f;
-      if (j < jend) {
-        const float pj = __expf(dot64_row(q, sK + j * KSTRIDE) * 0.125f - li);
-        ds = pj * (dot64_row(g, sV + j * KSTRIDE) - Di) * 0.125f;
-      }
-      myP[lane] = ds;
-      __builtin_amdgcn_wave_barrier();
-      acc = axpy_block_lds(myP, sK + j0 * KSTRIDE, lane, min(64, jend - j0), acc);
-      __builtin_amdgcn_wave_barrier();
-    }
-    dqkv[((size_t)b * L + i) * ld + h * HD + lane] = acc;
-  }
-}
-
-__global__ __launch_bounds__(512) void attention_lds_bwd_kv_kernel(const float* __restrict__ qkv,
-                                                                   const float* __restrict__ dout,
-                                                                   const float* __restrict__ lse,
-                                                                   const float* __restrict__ Dbuf,
-                                                                   float* __restrict__ dqkv, int L, int H, int causal) {
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  float* sQ = smem;
-  float* sG = sQ + L * KSTRIDE;  // dO rows
-  float* sP = sG + L * KSTRIDE;  // [8][64] p, then [8][64] dS
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int b = blockIdx.x / H, h = blockIdx.x % H;
-  const int d = H * HD;
-  const size_t ld = (size_t)3 * d;
-  const float* q0 = qkv + (size_t)b * L * ld + (size_t)h * HD;
-  stage_rows_n(q0, ld, sQ, L);
-  stage_rows_n(dout + (size_t)b * L * d + (size_t)h * HD, (size_t)d, sG, L);
-  __syncthreads();
-  float* myP = sP + wave * 64;
-  float* myS = sP + 8 * 64 + wave * 64;
-  const float* lse0 = lse + ((size_t)b * H + h) * L;
-  const float* D0 = Dbuf + ((size_t)b * H + h) * L;
-  for (int j = wave; j < L; j += 8) {
-    f32x4 k[HD / 4], v[HD / 4];
-#pragma unroll
-    for (int c = 0; c < HD / 4; ++c) {
-      k[c] = *reinterpret_cast<const f32x4*>(q0 + d + (size_t)j * ld + 4 * c);
-      v[c] = *reinterpret_cast<const f32x4*>(q0 + 2 * d + (size_t)j * ld + 4 * c);
-    }
-    float av = 0.f, ak = 0.f;
-    const int ibeg = causal ? j : 0;
-    for (int i0 = ibeg & ~63; i0 < L; i0 += 64) {
-      const int i = i0 + lane;
-      float pj = 0.f, ds = 0.f;
-      if (i < L && i >= ibeg) {
-        pj = __expf(dot64_row(k, sQ + i * KSTRIDE) * 0.125f - lse0[i]);
-        ds = pj * (dot64_row(v, sG + i * KSTRIDE) - D0[i]) * 0.125f;
-      }
-      myP[lane] = pj;
-      myS[lane] = ds;
-      __builtin_amdgcn_wave_barrier();
-      const int n = min(64, L - i0);
-      av = axpy_block_lds(myP, sG + i0 * KSTRIDE, lane, n, av);
-      ak = axpy_block_lds(myS, sQ + i0 * KSTRIDE, lane, n, ak);
-      __builtin_amdgcn_wave_barrier();
-    }
-    dqkv[((size_t)b * L + j) * ld + 2 * d + h * HD + lane] = av;
-    dqkv[((size_t)b * L + j) * ld + d + h * HD + lane] = ak;
-  }
-}
-
-// attention_mfma.hip: exact-fp32 MFMA kernels for seq <= 288 (the default path; the VALU kernels below remain for
-// sequences past clipfs_attention_mfma_max_seq(), for backward calls without the forward's lse, and as the
-// CLIPFS_ATTN_MFMA=0 comparison)
-bool attention_mfma_enabled();
-int attention_mfma_fwd(const float* qkv, float* out, float* lse, int batch, int seq, int heads, int causal, hipStream_t st);
-int attention_mfma_bwd(const float* qkv, const float* dout, const float* out, const float* lse, float* dqkv, float* work,
-                       int batch, int seq, int heads, int causal, hipStream_t st);
-constexpr int ATTN_MFMA_MAX = 288;
-// ... and their long-sequence form (own side in runs of tiles, other side through LDS in chunks) up to
-// clipfs_attention_mfma_max_seq() tokens; chunk_tokens = run_tiles = 0: the default cut
-int attention_mfma_long_fwd(const float* qkv, float* out, float* lse, int batch, int seq, int heads, int causal,
-                            int chunk_tokens, int run_tiles, hipStream_t st);
-int attention_mfma_long_bwd(const float* qkv, const float* dout, const float* out, const float* lse, float* dqkv, float* work,
-                            int batch, int seq, int heads, int causal, int chunk_tokens, int run_tiles, hipStream_t st);
-// attention_mfma16.hip: the 16-token-tile kernels (seq <= 96) and their packed (live-row) backward
-bool attention16_enabled(int seq);
-int attention16_bwd_packed(const float* qkv, const float* dout, const float* out, const float* lse, float* dqkv,
-                           const int32_t* off, int batch, int seq, int heads, bool pin, hipStream_t st);
-int attention16_fwd_packed(const float* qkv, float* out, float* lse, const int32_t* off, int batch, int seq, int heads,
-                           hipStream_t st);
-
-static int check_attn(const char* what, int batch, int seq, int heads, int max_seq) {
-  CLIPFS_REQUIRE(batch > 0 && heads > 0 && seq > 0 && seq <= max_seq, "%s: batch %d seq %d heads %d unsupported (seq <= %d)",
-                 what, batch, seq, heads, max_seq);
-  return CLIPFS_OK;
-}
-
-// padded row length of the LDS [L][LP] matrices: >= L rounded up to 4 (b128 broadcast reads), LP / 4 odd so the
-// transposed (stride-LP) writes spread over 8 distinct bank groups
+// padded row length of the recomputing backward's LDS [L][LP] matrices: >= L rounded up to 4 (b128 broadcast reads),
+// LP / 4 odd so the transposed (stride-LP) writes spread over 8 distinct bank groups
 static int padded_lp(int seq) {
   int lp = (seq + 3) & ~3;
   if (((lp >> 2) & 1) == 0) lp += 4;
   return lp;
 }
 
+// A/B aids, read once per process (never per launch: one rank's step is nearly host-bound).  "0" switches off.
+static bool aid_on(const char* name) {
+  const char* v = getenv(name);
+  return !v || atoi(v) != 0;
+}
+
+static const char* const kDirName[] = {"attention_fwd", "attention_bwd", "attention_fwd_packed", "attention_bwd_packed",
+                                       "attention_bwd_packed_io"};
+
+// THE dispatch.  Pure host arithmetic: no HIP call, no state beyond the two aids.  flags: CLIPFS_ATTN_STATS (forward: lse
+// was asked for -- it changes nothing, every forward kernel only guards one store with it; backward: the forward's out
+// and lse and a work buffer are there) and CLIPFS_ATTN_ALIGNED (out / dqkv are 16-byte aligned).
+static int attention_plan(int dir, int batch, int seq, int heads, int causal, int flags, AttnPlan& p) {
+  static const bool use_mfma = aid_on("CLIPFS_ATTN_MFMA");  // 0: the streaming kernels at every length
+  static const bool use_16 = aid_on("CLIPFS_ATTN16");       // 0: 32-token tiles below 97 tokens as well
+  CLIPFS_REQUIRE(dir >= CLIPFS_ATTN_FWD && dir <= CLIPFS_ATTN_BWD_PACKED_IO, "attention_plan: direction %d unknown", dir);
+  const char* what = kDirName[dir];
+  CLIPFS_REQUIRE(batch > 0 && heads > 0 && seq > 0 && seq <= ATTN_MAX_SEQ, "%s: batch %d seq %d heads %d unsupported (seq <= %d)",
+                 what, batch, seq, heads, ATTN_MAX_SEQ);
+  const bool backward = dir != CLIPFS_ATTN_FWD && dir != CLIPFS_ATTN_FWD_PACKED;
+  const bool stats = (flags & CLIPFS_ATTN_STATS) != 0, aligned = (flags & CLIPFS_ATTN_ALIGNED) != 0;
+  const bool tiles16 = use_mfma && use_16 && seq <= ATTN16_MAX;
+  p = AttnPlan{};
+  if (dir >= CLIPFS_ATTN_FWD_PACKED) {  // live rows: the causal 16-token-tile kernels or nothing
+    CLIPFS_REQUIRE(causal && tiles16, "%s: seq %d%s has no packed kernel", what, seq, causal ? "" : " without the causal mask");
+    CLIPFS_REQUIRE(!backward || stats, "%s: null pointer (out and lse of the forward are needed)", what);
+    CLIPFS_REQUIRE(aligned, "%s: misaligned pointer", what);
+    attention16_plan(dir == CLIPFS_ATTN_BWD_PACKED_IO ? CLIPFS_ATTN_MFMA16_PINNED : CLIPFS_ATTN_MFMA16_PACKED, backward, batch,
+                     seq, heads, p);
+    return CLIPFS_OK;
+  }
+  if (use_mfma && aligned && (stats || !backward) && seq <= clipfs_attention_mfma_max_seq()) {
+    if (tiles16)
+      attention16_plan(CLIPFS_ATTN_MFMA16, backward, batch, seq, heads, p);
+    else if (seq <= ATTN_MFMA_MAX)
+      attention_mfma_plan(backward, batch, seq, heads, p);
+    else
+      CLIPFS_CHECK(attention_mfma_long_plan(what, backward, batch, seq, heads, 0, 0, p));
+    return CLIPFS_OK;
+  }
+  const unsigned items = (unsigned)(batch * heads);
+  if (stats || !backward) {  // everything else with statistics (or a forward): the streaming kernels
+    p.family = CLIPFS_ATTN_STREAM;
+    p.launches = backward ? 2 : 1;  // backward: dQ and D_i, then dK and dV
+    p.launch[0] = p.launch[1] = {items, (unsigned)(seq + 3) / 4, 256, 0};
+    return CLIPFS_OK;
+  }
+  CLIPFS_REQUIRE(seq <= ATTN16_MAX, "%s: seq %d > %d needs the forward's out and lse and a work buffer", what, seq, ATTN16_MAX);
+  const int lp = padded_lp(seq);
+  // P^T, dS^T, and dS (whose storage first serves as the [seq][KSTRIDE] K/V staging buffer) + 16 floats overhang
+  const size_t third = (size_t)seq * (lp > KSTRIDE ? lp : KSTRIDE);
+  p.family = CLIPFS_ATTN_RECOMPUTE;
+  p.lmax = seq <= 64 ? 64 : seq <= 80 ? 80 : 96;
+  p.launches = 1;
+  p.launch[0] = {items, 1, seq > 64 ? 512u : 256u, (unsigned)(((size_t)2 * seq * lp + third + 16) * sizeof(float))};
+  return CLIPFS_OK;
+}
+
+template <int LMAX>
+static int recompute_bwd(const AttnPlan& p, const float* qkv, const float* dout, float* dqkv, int seq, int heads, int causal,
+                         hipStream_t st) {
+  static bool attr = false;
+  if (!attr) {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attention_bwd_kernel<LMAX>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    attr = true;
+  }
+  hipLaunchKernelGGL((attention_bwd_kernel<LMAX>), dim3(p.launch[0].grid_x), dim3(p.launch[0].block), p.launch[0].lds_bytes,
+                     st, qkv, dout, dqkv, seq, heads, causal, padded_lp(seq));
+  return launch_status();
+}
+
+// validate, make the plan, execute it.  off == NULL: the dense layout
+static int run_fwd(int dir, const float* qkv, float* out, float* lse, const int32_t* off, int batch, int seq, int heads,
+                   int causal, hipStream_t st) {
+  AttnPlan p;
+  CLIPFS_CHECK(attention_plan(dir, batch, seq, heads, causal,
+                              (lse ? CLIPFS_ATTN_STATS : 0) | (aligned16(out) ? CLIPFS_ATTN_ALIGNED : 0), p));
+  CLIPFS_REQUIRE(qkv && out && (off || dir == CLIPFS_ATTN_FWD), "%s: null pointer", kDirName[dir]);
+  CLIPFS_REQUIRE(aligned16(qkv), "%s: misaligned pointer", kDirName[dir]);
+  switch (p.family) {
+    case CLIPFS_ATTN_MFMA16:
+    case CLIPFS_ATTN_MFMA16_PACKED: return attention16_fwd(p, qkv, out, lse, off, seq, heads, causal, st);
+    case CLIPFS_ATTN_MFMA32: return attention_mfma_fwd(p, qkv, out, lse, seq, heads, causal, st);
+    case CLIPFS_ATTN_MFMA_LONG: return attention_mfma_long_fwd(p, qkv, out, lse, seq, heads, causal, st);
+    default:  // CLIPFS_ATTN_STREAM
+      hipLaunchKernelGGL(attention_generic_fwd_kernel, dim3(p.launch[0].grid_x, p.launch[0].grid_y), dim3(p.launch[0].block),
+                         0, st, qkv, out, lse, seq, heads, causal);
+      return launch_status();
+  }
+}
+
+static int run_bwd(int dir, const float* qkv, const float* dout, const float* out, const float* lse, float* dqkv, float* work,
+                   const int32_t* off, int batch, int seq, int heads, int causal, hipStream_t st) {
+  const bool stats = out && lse && (work || dir != CLIPFS_ATTN_BWD);  // the packed kernels need no work buffer
+  AttnPlan p;
+  CLIPFS_CHECK(attention_plan(dir, batch, seq, heads, causal,
+                              (stats ? CLIPFS_ATTN_STATS : 0) |
+                                  (aligned16(out) && aligned16(dqkv) ? CLIPFS_ATTN_ALIGNED : 0), p));
+  CLIPFS_REQUIRE(qkv && dout && dqkv && (off || dir == CLIPFS_ATTN_BWD), "%s: null pointer", kDirName[dir]);
+  CLIPFS_REQUIRE(aligned16(qkv) && aligned16(dout), "%s: misaligned pointer", kDirName[dir]);
+  switch (p.family) {
+    case CLIPFS_ATTN_MFMA16:
+    case CLIPFS_ATTN_MFMA16_PACKED:
+    case CLIPFS_ATTN_MFMA16_PINNED: return attention16_bwd(p, qkv, dout, out, lse, dqkv, off, seq, heads, causal, st);
+    case CLIPFS_ATTN_MFMA32: return attention_mfma_bwd(p, qkv, dout, out, lse, dqkv, work, seq, heads, causal, st);
+    case CLIPFS_ATTN_MFMA_LONG: return attention_mfma_long_bwd(p, qkv, dout, out, lse, dqkv, work, seq, heads, causal, st);
+    case CLIPFS_ATTN_STREAM: {
+      const dim3 grid(p.launch[0].grid_x, p.launch[0].grid_y), block(p.launch[0].block);
+      hipLaunchKernelGGL(attention_generic_bwd_q_kernel, grid, block, 0, st, qkv, dout, out, lse, dqkv, work, seq, heads,
+                         causal);
+      CLIPFS_CHECK(launch_status());
+      hipLaunchKernelGGL(attention_generic_bwd_kv_kernel, grid, block, 0, st, qkv, dout, lse, work, dqkv, seq, heads, causal);
+      return launch_status();
+    }
+    default:  // CLIPFS_ATTN_RECOMPUTE
+      if (p.lmax == 64) return recompute_bwd<64>(p, qkv, dout, dqkv, seq, heads, causal, st);
+      if (p.lmax == 80) return recompute_bwd<80>(p, qkv, dout, dqkv, seq, heads, causal, st);
+      return recompute_bwd<96>(p, qkv, dout, dqkv, seq, heads, causal, st);
+  }
+}
+
 }  // namespace clipfs
 
 using namespace clipfs;
 
-constexpr int ATTN_FAST_MAX = 96;   // register/LDS-resident kernels up to here (forward-only inference: 128)
-constexpr int ATTN_MAX_SEQ = 4096;
-constexpr int ATTN_LDS_MAX = 288;    // (2 * L * 68 + 16 * 64) floats <= 160 KiB: K and V (or Q and dO) of a head stay in LDS
+extern "C" int clipfs_attention_plan(int direction, int batch, int seq, int heads, int causal, int flags,
+                                     struct clipfs_attention_plan* plan) {
+  CLIPFS_REQUIRE(plan, "attention_plan: null plan");
+  AttnPlan p;
+  CLIPFS_CHECK(attention_plan(direction, batch, seq, heads, causal, flags, p));
+  *plan = p;
+  return CLIPFS_OK;
+}
 
 extern "C" int clipfs_attention_fwd(const float* qkv, float* out, float* lse, int batch, int seq, int heads, int causal,
                                     void* stream) {
-  CLIPFS_CHECK(check_attn("attention_fwd", batch, seq, heads, ATTN_MAX_SEQ));
-  CLIPFS_REQUIRE(qkv && out && aligned16(qkv), "attention_fwd: null or misaligned pointer");
-  hipStream_t st = (hipStream_t)stream;
-  if (attention_mfma_enabled() && seq <= ATTN_MFMA_MAX && aligned16(out))
-    return attention_mfma_fwd(qkv, out, lse, batch, seq, heads, causal, st);
-  if (attention_mfma_enabled() && seq > ATTN_MFMA_MAX && seq <= clipfs_attention_mfma_max_seq() && aligned16(out))
-    return attention_mfma_long_fwd(qkv, out, lse, batch, seq, heads, causal, 0, 0, st);
-  if ((seq > 128 || (seq > ATTN_FAST_MAX && lse)) && seq <= ATTN_LDS_MAX) {
-    const size_t lds = ((size_t)2 * seq * KSTRIDE + 8 * 64) * sizeof(float);
-    static bool attr = false;
-    if (!attr) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attention_lds_fwd_kernel),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      attr = true;
-    }
-    hipLaunchKernelGGL(attention_lds_fwd_kernel, dim3(batch * heads), dim3(512), lds, st, qkv, out, lse, seq, heads, causal);
-    return launch_status();
-  }
-  if (seq > 128 || (seq > ATTN_FAST_MAX && lse)) {
-    hipLaunchKernelGGL(attention_generic_fwd_kernel, dim3(batch * heads, (seq + 3) / 4), dim3(256), 0, st, qkv, out, lse,
-                       seq, heads, causal);
-    return launch_status();
-  }
-  static const int thr_cfg = getenv("CLIPFS_ATTN_FWD_THREADS") ? atoi(getenv("CLIPFS_ATTN_FWD_THREADS")) : 0;
-  const dim3 grid(batch * heads), block(thr_cfg ? thr_cfg : 256);
-  const size_t lds1 = ((size_t)seq * KSTRIDE + 16 * 64) * sizeof(float);
-  const size_t lds2 = ((size_t)seq * KSTRIDE + 16 * 128) * sizeof(float);
-  if (seq <= 64)
-    hipLaunchKernelGGL((attention_fwd_kernel<64>), grid, block, lds1, st, qkv, out, seq, heads, causal);
-  else if (seq <= 80)
-    hipLaunchKernelGGL((attention_fwd_kernel<80>), grid, block, lds2, st, qkv, out, seq, heads, causal);
-  else if (seq <= 96)
-    hipLaunchKernelGGL((attention_fwd_kernel<96>), grid, block, lds2, st, qkv, out, seq, heads, causal);
-  else
-    hipLaunchKernelGGL((attention_fwd_kernel<128>), grid, block, lds2, st, qkv, out, seq, heads, causal);
-  return launch_status();
+  return run_fwd(CLIPFS_ATTN_FWD, qkv, out, lse, nullptr, batch, seq, heads, causal, (hipStream_t)stream);
 }
 
 extern "C" int clipfs_attention_bwd(const float* qkv, const float* dout, const float* out, const float* lse, float* dqkv,
                                     float* work, int batch, int seq, int heads, int causal, void* stream) {
-  CLIPFS_CHECK(check_attn("attention_bwd", batch, seq, heads, ATTN_MAX_SEQ));
-  CLIPFS_REQUIRE(qkv && dout && dqkv && aligned16(qkv) && aligned16(dout), "attention_bwd: null or misaligned pointer");
-  hipStream_t st = (hipStream_t)stream;
-  if (attention_mfma_enabled() && seq <= ATTN_MFMA_MAX && out && lse && work && aligned16(out) && aligned16(dqkv))
-    return attention_mfma_bwd(qkv, dout, out, lse, dqkv, work, batch, seq, heads, causal, st);
-  if (attention_mfma_enabled() && seq > ATTN_MFMA_MAX && seq <= clipfs_attention_mfma_max_seq() && out && lse && work &&
-      aligned16(out) && aligned16(dqkv))
-    return attention_mfma_long_bwd(qkv, dout, out, lse, dqkv, work, batch, seq, heads, causal, 0, 0, st);
-  if (seq > ATTN_FAST_MAX) {
-    CLIPFS_REQUIRE(out && lse && work, "attention_bwd: seq %d > %d needs the forward's out and lse and a work buffer", seq,
-                   ATTN_FAST_MAX);
-    if (seq <= ATTN_LDS_MAX) {
-      const size_t lds = ((size_t)2 * seq * KSTRIDE + 16 * 64) * sizeof(float);
-      static bool attr = false;
-      if (!attr) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attention_lds_bwd_q_kernel),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attention_lds_bwd_kv_kernel),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attr = true;
-      }
-      hipLaunchKernelGGL(attention_lds_bwd_q_kernel, dim3(batch * heads), dim3(512), lds, st, qkv, dout, out, lse, dqkv,
-                         work, seq, heads, causal);
-      CLIPFS_CHECK(launch_status());
-      hipLaunchKernelGGL(attention_lds_bwd_kv_kernel, dim3(batch * heads), dim3(512), lds, st, qkv, dout, lse, work, dqkv,
-                         seq, heads, causal);
-      return launch_status();
-    }
-    const dim3 grid(batch * heads, (seq + 3) / 4);
-    hipLaunchKernelGGL(attention_generic_bwd_q_kernel, grid, dim3(256), 0, st, qkv, dout, out, lse, dqkv, work, seq, heads,
-                       causal);
-    CLIPFS_CHECK(launch_status());
-    hipLaunchKernelGGL(attention_generic_bwd_kv_kernel, grid, dim3(256), 0, st, qkv, dout, lse, work, dqkv, seq, heads,
-                       causal);
-    return launch_status();
-  }
-  const int lp = padded_lp(seq);
-  // P^T, dS^T, and dS (whose storage first serves as the [seq][KSTRIDE] K/V staging buffer) + 16 floats overhang
-  const size_t third = (size_t)seq * (lp > KSTRIDE ? lp : KSTRIDE);
-  const size_t lds = ((size_t)2 * seq * lp + third + 16) * sizeof(float);
-  CLIPFS_REQUIRE(lds <= 160 * 1024, "attention_bwd: seq %d needs %zu bytes of LDS (> 160 KiB)", seq, lds);
-  static const int thr_cfg = getenv("CLIPFS_ATTN_BWD_THREADS") ? atoi(getenv("CLIPFS_ATTN_BWD_THREADS")) : 0;
-  const dim3 grid(batch * heads), block(thr_cfg ? thr_cfg : (seq > 64 ? 512 : 256));
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attention_bwd_kernel<64>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attention_bwd_kernel<80>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attention_bwd_kernel<96>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    attr = true;
-  }
-  if (seq <= 64)
-    hipLaunchKernelGGL((attention_bwd_kernel<64>), grid, block, lds, st, qkv, dout, dqkv, seq, heads, causal, lp);
-  else if (seq <= 80)
-    hipLaunchKernelGGL((attention_bwd_kernel<80>), grid, block, lds, st, qkv, dout, dqkv, seq, heads, causal, lp);
-  else
-    hipLaunchKernelGGL((attention_bwd_kernel<96>), grid, block, lds, st, qkv, dout, dqkv, seq, heads, causal, lp);
-  return launch_status();
+  return run_bwd(CLIPFS_ATTN_BWD, qkv, dout, out, lse, dqkv, work, nullptr, batch, seq, heads, causal, (hipStream_t)stream);
 }
 
 extern "C" int clipfs_attention_bwd_packed_ok(int seq, int causal) {
-  return (causal && seq > 0 && seq <= ATTN_MFMA_MAX && attention_mfma_enabled() && attention16_enabled(seq)) ? 1 : 0;
-}
-
-extern "C" int clipfs_attention_bwd_packed(const float* qkv, const float* dout, const float* out, const float* lse,
-                                           float* dqkv, const int32_t* off, int batch, int seq, int heads, void* stream) {
-  CLIPFS_CHECK(check_attn("attention_bwd_packed", batch, seq, heads, ATTN_MAX_SEQ));
-  CLIPFS_REQUIRE(clipfs_attention_bwd_packed_ok(seq, 1), "attention_bwd_packed: seq %d has no packed kernel", seq);
-  CLIPFS_REQUIRE(qkv && dout && out && lse && dqkv && off, "attention_bwd_packed: null pointer");
-  CLIPFS_REQUIRE(aligned16(qkv) && aligned16(dout) && aligned16(out) && aligned16(dqkv),
-                 "attention_bwd_packed: misaligned pointer");
-  return attention16_bwd_packed(qkv, dout, out, lse, dqkv, off, batch, seq, heads, false, (hipStream_t)stream);
+  AttnPlan p;
+  return attention_plan(CLIPFS_ATTN_BWD_PACKED, 1, seq, 1, causal, CLIPFS_ATTN_STATS | CLIPFS_ATTN_ALIGNED, p) == CLIPFS_OK;
 }
 
 extern "C" int clipfs_attention_fwd_packed(const float* qkv, float* out, float* lse, const int32_t* off, int batch, int seq,
                                            int heads, void* stream) {
-  CLIPFS_CHECK(check_attn("attention_fwd_packed", batch, seq, heads, ATTN_MAX_SEQ));
-  CLIPFS_REQUIRE(clipfs_attention_bwd_packed_ok(seq, 1), "attention_fwd_packed: seq %d has no packed kernel", seq);
-  CLIPFS_REQUIRE(qkv && out && off, "attention_fwd_packed: null pointer");
-  CLIPFS_REQUIRE(aligned16(qkv) && aligned16(out), "attention_fwd_packed: misaligned pointer");
-  return attention16_fwd_packed(qkv, out, lse, off, batch, seq, heads, (hipStream_t)stream);
+  return run_fwd(CLIPFS_ATTN_FWD_PACKED, qkv, out, lse, off, batch, seq, heads, 1, (hipStream_t)stream);
+}
+
+extern "C" int clipfs_attention_bwd_packed(const float* qkv, const float* dout, const float* out, const float* lse,
+                                           float* dqkv, const int32_t* off, int batch, int seq, int heads, void* stream) {
+  return run_bwd(CLIPFS_ATTN_BWD_PACKED, qkv, dout, out, lse, dqkv, nullptr, off, batch, seq, heads, 1, (hipStream_t)stream);
 }
 
 extern "C" int clipfs_attention_bwd_packed_io(const float* qkv, const float* dout, const float* out, const float* lse,
                                               float* dqkv, const int32_t* off, int batch, int seq, int heads, void* stream) {
-  CLIPFS_CHECK(check_attn("attention_bwd_packed_io", batch, seq, heads, ATTN_MAX_SEQ));
-  CLIPFS_REQUIRE(clipfs_attention_bwd_packed_ok(seq, 1), "attention_bwd_packed_io: seq %d has no packed kernel", seq);
-  CLIPFS_REQUIRE(qkv && dout && out && lse && dqkv && off, "attention_bwd_packed_io: null pointer");
-  CLIPFS_REQUIRE(aligned16(qkv) && aligned16(dout) && aligned16(out) && aligned16(dqkv),
-                 "attention_bwd_packed_io: misaligned pointer");
-  return attention16_bwd_packed(qkv, dout, out, lse, dqkv, off, batch, seq, heads, true, (hipStream_t)stream);
+  return run_bwd(CLIPFS_ATTN_BWD_PACKED_IO, qkv, dout, out, lse, dqkv, nullptr, off, batch, seq, heads, 1,
+                 (hipStream_t)stream);
 }
 
-extern "C" size_t clipfs_attention_lse_floats(int batch, int seq, int heads) {
-  if (attention_mfma_enabled() && seq <= ATTN_MFMA_MAX) return (size_t)batch * heads * seq;
-  return seq > ATTN_FAST_MAX ? (size_t)batch * heads * seq : 0;
-}
+// one log-sum-exp per (batch, head, query): every forward kernel writes it when it is given the buffer
+extern "C" size_t clipfs_attention_lse_floats(int batch, int seq, int heads) { return (size_t)batch * heads * seq; }

@@ -16,8 +16,6 @@
 //     L2 (each lane 128 contiguous bytes), so LDS holds only the transposed images: 26 KB per head at L = 77.
 #include "common.h"
 
-#include <stdlib.h>
-
 namespace clipfs {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -503,58 +501,58 @@ __global__ __launch_bounds__(64 * AM_RUN) void attention_mfma_long_bwd_kv_kernel
   }
 }
 
-// ---- host side (called from attention.hip) ----------------------------------------------------------------
+// ---- host side: these families' share of the plan and their launchers (called from attention.hip) ----------------
 
-// attention_mfma16.hip: 16-token tiles on v_mfma_f32_16x16x4_f32, every operand in LDS (sequences up to 96 tokens)
-bool attention16_enabled(int seq);
-int attention16_fwd(const float* qkv, float* out, float* lse, int batch, int seq, int heads, int causal, hipStream_t st);
-int attention16_bwd(const float* qkv, const float* dout, const float* out, const float* lse, float* dqkv, float* work,
-                    int batch, int seq, int heads, int causal, hipStream_t st);
-
-bool attention_mfma_enabled() {
-  static const int cfg = getenv("CLIPFS_ATTN_MFMA") ? atoi(getenv("CLIPFS_ATTN_MFMA")) : 1;  // 0: VALU kernels (A/B aid)
-  return cfg != 0;
+// `images` transposed images of `tokens` (rounded up to whole tiles) + 4 pad; vectors: lse and D of the dK/dV pass
+static unsigned am_lds(int tokens, int images, bool vectors) {
+  const int Lp = (tokens + 31) & ~31;
+  return (unsigned)(((size_t)images * 64 * (Lp + 4) + (vectors ? 2 * (size_t)Lp : 0)) * sizeof(float));
 }
 
-static int am_threads(int seq) {
+// launches of both families: the forward; or the dQ pass (which also writes D_i to `work`), then the dK/dV pass
+static void am_launches(bool backward, unsigned grid, unsigned block, int lds_tokens, AttnPlan& p) {
+  p.launches = backward ? 2 : 1;
+  p.launch[0] = {grid, 1, block, am_lds(lds_tokens, 1, false)};
+  if (backward) p.launch[1] = {grid, 1, block, am_lds(lds_tokens, 2, true)};
+}
+
+static void am_allow_lds(const void* kernel) {
+  (void)hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+}
+
+void attention_mfma_plan(bool backward, int batch, int seq, int heads, AttnPlan& p) {
   const int tiles = (seq + 31) / 32;
-  return 64 * (tiles < 4 ? tiles : 4);
+  p.family = CLIPFS_ATTN_MFMA32;
+  am_launches(backward, (unsigned)(batch * heads), 64u * (tiles < 4 ? tiles : 4), seq, p);
 }
 
-static size_t am_lds(int seq, int images, bool vectors) {
-  const int Lp = (seq + 31) & ~31;
-  return ((size_t)images * 64 * (Lp + 4) + (vectors ? 2 * (size_t)Lp : 0)) * sizeof(float);
-}
-
-int attention_mfma_fwd(const float* qkv, float* out, float* lse, int batch, int seq, int heads, int causal, hipStream_t st) {
-  if (attention16_enabled(seq)) return attention16_fwd(qkv, out, lse, batch, seq, heads, causal, st);
+int attention_mfma_fwd(const AttnPlan& p, const float* qkv, float* out, float* lse, int seq, int heads, int causal,
+                       hipStream_t st) {
   static bool attr = false;
   if (!attr) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attention_mfma_fwd_kernel),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    am_allow_lds(reinterpret_cast<const void*>(&attention_mfma_fwd_kernel));
     attr = true;
   }
-  hipLaunchKernelGGL(attention_mfma_fwd_kernel, dim3(batch * heads), dim3(am_threads(seq)), am_lds(seq, 1, false), st, qkv,
-                     out, lse, seq, heads, causal);
+  const clipfs_attention_launch& l = p.launch[0];
+  hipLaunchKernelGGL(attention_mfma_fwd_kernel, dim3(l.grid_x), dim3(l.block), l.lds_bytes, st, qkv, out, lse, seq, heads,
+                     causal);
   return launch_status();
 }
 
-int attention_mfma_bwd(const float* qkv, const float* dout, const float* out, const float* lse, float* dqkv, float* work,
-                       int batch, int seq, int heads, int causal, hipStream_t st) {
-  if (attention16_enabled(seq)) return attention16_bwd(qkv, dout, out, lse, dqkv, work, batch, seq, heads, causal, st);
+int attention_mfma_bwd(const AttnPlan& p, const float* qkv, const float* dout, const float* out, const float* lse,
+                       float* dqkv, float* work, int seq, int heads, int causal, hipStream_t st) {
   static bool attr = false;
   if (!attr) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attention_mfma_bwd_q_kernel),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attention_mfma_bwd_kv_kernel),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    am_allow_lds(reinterpret_cast<const void*>(&attention_mfma_bwd_q_kernel));
+    am_allow_lds(reinterpret_cast<const void*>(&attention_mfma_bwd_kv_kernel));
     attr = true;
   }
-  hipLaunchKernelGGL(attention_mfma_bwd_q_kernel, dim3(batch * heads), dim3(am_threads(seq)), am_lds(seq, 1, false), st, qkv,
-                     dout, out, lse, dqkv, work, seq, heads, causal);
+  const clipfs_attention_launch &q = p.launch[0], &kv = p.launch[1];
+  hipLaunchKernelGGL(attention_mfma_bwd_q_kernel, dim3(q.grid_x), dim3(q.block), q.lds_bytes, st, qkv, dout, out, lse, dqkv,
+                     work, seq, heads, causal);
   CLIPFS_CHECK(launch_status());
-  hipLaunchKernelGGL(attention_mfma_bwd_kv_kernel, dim3(batch * heads), dim3(am_threads(seq)), am_lds(seq, 2, true), st, qkv,
-                     dout, lse, work, dqkv, seq, heads, causal);
+  hipLaunchKernelGGL(attention_mfma_bwd_kv_kernel, dim3(kv.grid_x), dim3(kv.block), kv.lds_bytes, st, qkv, dout, lse, work,
+                     dqkv, seq, heads, causal);
   return launch_status();
 }
 
@@ -567,67 +565,55 @@ static AmCut am_cut(int seq, int max_tiles) {
   return {parts, (tiles + parts - 1) / parts};
 }
 
-// Arguments of a long launch.  chunk_tokens / run_tiles == 0: the default policy (chunks of at most AM_MAXL tokens, runs of
+// The plan of a long launch.  chunk_tokens / run_tiles == 0: the default policy (chunks of at most AM_MAXL tokens, runs of
 // at most AM_RUN tiles); either is then evened out over the sequence (577 tokens: 224 + 224 + 129, runs of 4 + 4 + 4 + 4 + 3).
-static int am_long_plan(const char* what, int batch, int seq, int heads, int chunk_tokens, int run_tiles, AmCut& own,
-                        int& ctok) {
+int attention_mfma_long_plan(const char* what, bool backward, int batch, int seq, int heads, int chunk_tokens, int run_tiles,
+                             AttnPlan& p) {
   CLIPFS_REQUIRE(batch > 0 && heads > 0, "%s: batch %d heads %d unsupported", what, batch, heads);
   CLIPFS_REQUIRE(seq >= AM_LONG_MINL && seq <= AM_LONG_MAXL, "%s: seq %d outside %d..%d", what, seq, AM_LONG_MINL,
                  AM_LONG_MAXL);
   CLIPFS_REQUIRE(chunk_tokens >= 0 && chunk_tokens <= AM_MAXL && chunk_tokens % 32 == 0,
                  "%s: chunk_tokens %d is not 0 or a multiple of 32 up to %d", what, chunk_tokens, AM_MAXL);
   CLIPFS_REQUIRE(run_tiles >= 0 && run_tiles <= AM_RUN, "%s: run_tiles %d outside 0..%d", what, run_tiles, AM_RUN);
-  own = am_cut(seq, run_tiles ? run_tiles : AM_RUN);
-  ctok = 32 * am_cut(seq, (chunk_tokens ? chunk_tokens : AM_MAXL) / 32).tiles;
+  const AmCut own = am_cut(seq, run_tiles ? run_tiles : AM_RUN);
   CLIPFS_REQUIRE((long long)batch * heads * own.parts <= 0x7fffffffLL, "%s: batch %d x heads %d too large for seq %d", what,
                  batch, heads, seq);
+  p = AttnPlan{};
+  p.family = CLIPFS_ATTN_MFMA_LONG;
+  p.parts = own.parts;
+  p.tiles = own.tiles;
+  p.ctok = 32 * am_cut(seq, (chunk_tokens ? chunk_tokens : AM_MAXL) / 32).tiles;
+  am_launches(backward, (unsigned)(batch * heads * own.parts), 64u * own.tiles, p.ctok, p);
   return CLIPFS_OK;
 }
 
-static size_t am_long_lds(int ctok, int images, bool vectors) {
-  return ((size_t)images * 64 * (ctok + 4) + (vectors ? 2 * (size_t)ctok : 0)) * sizeof(float);
-}
-
-int attention_mfma_long_fwd(const float* qkv, float* out, float* lse, int batch, int seq, int heads, int causal,
-                            int chunk_tokens, int run_tiles, hipStream_t st) {
-  AmCut own;
-  int ctok;
-  CLIPFS_CHECK(am_long_plan("attention_mfma_long_fwd", batch, seq, heads, chunk_tokens, run_tiles, own, ctok));
-  CLIPFS_REQUIRE(qkv && out, "attention_mfma_long_fwd: null qkv or out");
-  CLIPFS_REQUIRE(aligned16(qkv) && aligned16(out), "attention_mfma_long_fwd: misaligned pointer");
+int attention_mfma_long_fwd(const AttnPlan& p, const float* qkv, float* out, float* lse, int seq, int heads, int causal,
+                            hipStream_t st) {
   static bool attr = false;
   if (!attr) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attention_mfma_long_fwd_kernel),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    am_allow_lds(reinterpret_cast<const void*>(&attention_mfma_long_fwd_kernel));
     attr = true;
   }
-  hipLaunchKernelGGL(attention_mfma_long_fwd_kernel, dim3(batch * heads * own.parts), dim3(64 * own.tiles),
-                     am_long_lds(ctok, 1, false), st, qkv, out, lse, seq, heads, causal, own.parts, ctok);
+  const clipfs_attention_launch& l = p.launch[0];
+  hipLaunchKernelGGL(attention_mfma_long_fwd_kernel, dim3(l.grid_x), dim3(l.block), l.lds_bytes, st, qkv, out, lse, seq, heads,
+                     causal, p.parts, p.ctok);
   return launch_status();
 }
 
-int attention_mfma_long_bwd(const float* qkv, const float* dout, const float* out, const float* lse, float* dqkv, float* work,
-                            int batch, int seq, int heads, int causal, int chunk_tokens, int run_tiles, hipStream_t st) {
-  AmCut own;
-  int ctok;
-  CLIPFS_CHECK(am_long_plan("attention_mfma_long_bwd", batch, seq, heads, chunk_tokens, run_tiles, own, ctok));
-  CLIPFS_REQUIRE(qkv && dout && out && lse && dqkv && work, "attention_mfma_long_bwd: null qkv, dout, out, lse, dqkv or work");
-  CLIPFS_REQUIRE(aligned16(qkv) && aligned16(dout) && aligned16(out) && aligned16(dqkv),
-                 "attention_mfma_long_bwd: misaligned pointer");
+int attention_mfma_long_bwd(const AttnPlan& p, const float* qkv, const float* dout, const float* out, const float* lse,
+                            float* dqkv, float* work, int seq, int heads, int causal, hipStream_t st) {
   static bool attr = false;
   if (!attr) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attention_mfma_long_bwd_q_kernel),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attention_mfma_long_bwd_kv_kernel),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    am_allow_lds(reinterpret_cast<const void*>(&attention_mfma_long_bwd_q_kernel));
+    am_allow_lds(reinterpret_cast<const void*>(&attention_mfma_long_bwd_kv_kernel));
     attr = true;
   }
-  const dim3 grid(batch * heads * own.parts), block(64 * own.tiles);
-  hipLaunchKernelGGL(attention_mfma_long_bwd_q_kernel, grid, block, am_long_lds(ctok, 1, false), st, qkv, dout, out, lse, dqkv,
-                     work, seq, heads, causal, own.parts, ctok);
+  const clipfs_attention_launch &q = p.launch[0], &kv = p.launch[1];
+  hipLaunchKernelGGL(attention_mfma_long_bwd_q_kernel, dim3(q.grid_x), dim3(q.block), q.lds_bytes, st, qkv, dout, out, lse,
+                     dqkv, work, seq, heads, causal, p.parts, p.ctok);
   CLIPFS_CHECK(launch_status());
-  hipLaunchKernelGGL(attention_mfma_long_bwd_kv_kernel, grid, block, am_long_lds(ctok, 2, true), st, qkv, dout, lse, work, dqkv,
-                     seq, heads, causal, own.parts, ctok);
+  hipLaunchKernelGGL(attention_mfma_long_bwd_kv_kernel, dim3(kv.grid_x), dim3(kv.block), kv.lds_bytes, st, qkv, dout, lse, work,
+                     dqkv, seq, heads, causal, p.parts, p.ctok);
   return launch_status();
 }
 
@@ -637,14 +623,23 @@ using namespace clipfs;
 
 extern "C" int clipfs_attention_mfma_max_seq(void) { return AM_LONG_MAXL; }
 
+// the long kernels with an explicit cut: their own plan, their own pointer checks
 extern "C" int clipfs_attention_mfma_long_fwd(const float* qkv, float* out, float* lse, int batch, int seq, int heads,
                                               int causal, int chunk_tokens, int run_tiles, void* stream) {
-  return attention_mfma_long_fwd(qkv, out, lse, batch, seq, heads, causal, chunk_tokens, run_tiles, (hipStream_t)stream);
+  AttnPlan p;
+  CLIPFS_CHECK(attention_mfma_long_plan("attention_mfma_long_fwd", false, batch, seq, heads, chunk_tokens, run_tiles, p));
+  CLIPFS_REQUIRE(qkv && out, "attention_mfma_long_fwd: null qkv or out");
+  CLIPFS_REQUIRE(aligned16(qkv) && aligned16(out), "attention_mfma_long_fwd: misaligned pointer");
+  return attention_mfma_long_fwd(p, qkv, out, lse, seq, heads, causal, (hipStream_t)stream);
 }
 
 extern "C" int clipfs_attention_mfma_long_bwd(const float* qkv, const float* dout, const float* out, const float* lse,
                                               float* dqkv, float* work, int batch, int seq, int heads, int causal,
                                               int chunk_tokens, int run_tiles, void* stream) {
-  return attention_mfma_long_bwd(qkv, dout, out, lse, dqkv, work, batch, seq, heads, causal, chunk_tokens, run_tiles,
-                                 (hipStream_t)stream);
+  AttnPlan p;
+  CLIPFS_CHECK(attention_mfma_long_plan("attention_mfma_long_bwd", true, batch, seq, heads, chunk_tokens, run_tiles, p));
+  CLIPFS_REQUIRE(qkv && dout && out && lse && dqkv && work, "attention_mfma_long_bwd: null qkv, dout, out, lse, dqkv or work");
+  CLIPFS_REQUIRE(aligned16(qkv) && aligned16(dout) && aligned16(out) && aligned16(dqkv),
+                 "attention_mfma_long_bwd: misaligned pointer");
+  return attention_mfma_long_bwd(p, qkv, dout, out, lse, dqkv, work, seq, heads, causal, (hipStream_t)stream);
 }

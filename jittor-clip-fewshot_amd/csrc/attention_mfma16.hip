@@ -1,6 +1,6 @@
 // Exact-fp32 attention for SHORT sequences (L <= 96: ViT-B/32's 50 / 54 tokens, the 77-token text tower) on
 // v_mfma_f32_16x16x4_f32: forward, dQ pass, dK/dV pass (jclip/mha.py:55-83,439-458).  Same mathematics and the same
-// transposed-score scheme as attention_mfma.hip (32x32x2 tiles, kept for 96 < L <= 288); what changes and why:
+// transposed-score scheme as attention_mfma.hip (32x32x2 tiles, for 96 < L <= 1024); what changes and why:
 //
 //   * 16-token tiles.  77 tokens are 5 tiles (80) instead of 3 x 32 (96), and the causal mask skips whole 16 x 16
 //     tiles: 15 of 25 tile pairs carry work for the text tower where the 32-token tiling computed 6 of 9 (3840 vs 6144
@@ -23,7 +23,7 @@
 // tokens 4 g .. 4 g + 3 of the tile (step r -> token 4 g + r), which is exactly the D layout of the score tile.
 #include "common.h"
 
-#include <stdlib.h>
+#include <type_traits>
 
 namespace clipfs {
 
@@ -394,98 +394,86 @@ __global__ __launch_bounds__(64 * NT) void attention16_bwd_kernel(const float* _
     attention16_bwd_q_body<NT, PACKED, PIN>(qkv, dout, out, lse, dqkv, L, H, causal, item, off, a16_smem);
 }
 
-// ---- host side (called from attention_mfma.hip) -------------------------------------------------------------
-
-bool attention16_enabled(int seq) {
-  static const int cfg = getenv("CLIPFS_ATTN16") ? atoi(getenv("CLIPFS_ATTN16")) : 1;  // 0: the 32x32 kernels (A/B aid)
-  return cfg != 0 && seq <= 16 * A16_MAX_TILES;
-}
+// ---- host side: this family's share of the plan and its launchers (called from attention.hip) --------------------
 
 static size_t a16_lds(int nt, bool vectors) {  // vectors: lse, D and the 16 partial-D rows of the dK/dV pass
   return ((size_t)2 * 64 * (16 * nt + 8) + (vectors ? 18 * (size_t)16 * nt : 0)) * sizeof(float);
 }
 
-template <int NT, bool PACKED = false>
-static int a16_fwd(const float* qkv, float* out, float* lse, int batch, int seq, int heads, int causal, hipStream_t st,
-                   const int32_t* off = nullptr) {
+// one launch: a workgroup per (batch, head) in the forward, two (dQ | dK/dV) in the backward, one wave per tile.  The
+// packed forms are sized by the full sequence; their tile bounds come from off[] at run time.
+void attention16_plan(int family, bool backward, int batch, int seq, int heads, AttnPlan& p) {
+  p.family = family;
+  p.nt = (seq + 15) / 16;
+  p.launches = 1;
+  p.launch[0] = {(unsigned)((backward ? 2 : 1) * batch * heads), 1, 64u * p.nt, (unsigned)a16_lds(p.nt, backward)};
+}
+
+// the template instance of the plan's tile count: launch(std::integral_constant<int, NT>)
+template <typename F>
+static int a16_instance(int nt, F&& launch) {
+  switch (nt) {
+    case 1: return launch(std::integral_constant<int, 1>());
+    case 2: return launch(std::integral_constant<int, 2>());
+    case 3: return launch(std::integral_constant<int, 3>());
+    case 4: return launch(std::integral_constant<int, 4>());
+    case 5: return launch(std::integral_constant<int, 5>());
+    default: return launch(std::integral_constant<int, A16_MAX_TILES>());
+  }
+}
+
+template <int NT, bool PACKED>
+static int a16_fwd(const AttnPlan& p, const float* qkv, float* out, float* lse, const int32_t* off, int seq, int heads,
+                   int causal, hipStream_t st) {
+  const clipfs_attention_launch& l = p.launch[0];
   static bool attr = false;
-  if (!attr && a16_lds(NT, false) > 48 * 1024) {
+  if (!attr && l.lds_bytes > 48 * 1024) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attention16_fwd_kernel<NT, PACKED>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)a16_lds(NT, false));
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)l.lds_bytes);
     attr = true;
   }
-  hipLaunchKernelGGL((attention16_fwd_kernel<NT, PACKED>), dim3(batch * heads), dim3(64 * NT), a16_lds(NT, false), st, qkv, out,
-                     lse, seq, heads, causal, off);
+  hipLaunchKernelGGL((attention16_fwd_kernel<NT, PACKED>), dim3(l.grid_x), dim3(l.block), l.lds_bytes, st, qkv, out, lse, seq,
+                     heads, causal, off);
   return launch_status();
 }
 
-template <int NT, bool PACKED = false, bool PIN = false>
-static int a16_bwd(const float* qkv, const float* dout, const float* out, const float* lse, float* dqkv, float* work,
-                   int batch, int seq, int heads, int causal, hipStream_t st, const int32_t* off = nullptr) {
-  (void)work;  // D_i no longer travels through memory
+template <int NT, bool PACKED, bool PIN>
+static int a16_bwd(const AttnPlan& p, const float* qkv, const float* dout, const float* out, const float* lse, float* dqkv,
+                   const int32_t* off, int seq, int heads, int causal, hipStream_t st) {
+  const clipfs_attention_launch& l = p.launch[0];
   static bool attr = false;
-  if (!attr && a16_lds(NT, true) > 48 * 1024) {
+  if (!attr && l.lds_bytes > 48 * 1024) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attention16_bwd_kernel<NT, PACKED, PIN>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)a16_lds(NT, true));
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)l.lds_bytes);
     attr = true;
   }
-  hipLaunchKernelGGL((attention16_bwd_kernel<NT, PACKED, PIN>), dim3(2 * batch * heads), dim3(64 * NT), a16_lds(NT, true), st,
-                     qkv, dout, out, lse, dqkv, seq, heads, causal, off);
+  hipLaunchKernelGGL((attention16_bwd_kernel<NT, PACKED, PIN>), dim3(l.grid_x), dim3(l.block), l.lds_bytes, st, qkv, dout, out,
+                     lse, dqkv, seq, heads, causal, off);
   return launch_status();
 }
 
-int attention16_fwd(const float* qkv, float* out, float* lse, int batch, int seq, int heads, int causal, hipStream_t st) {
-  switch ((seq + 15) / 16) {
-    case 1: return a16_fwd<1>(qkv, out, lse, batch, seq, heads, causal, st);
-    case 2: return a16_fwd<2>(qkv, out, lse, batch, seq, heads, causal, st);
-    case 3: return a16_fwd<3>(qkv, out, lse, batch, seq, heads, causal, st);
-    case 4: return a16_fwd<4>(qkv, out, lse, batch, seq, heads, causal, st);
-    case 5: return a16_fwd<5>(qkv, out, lse, batch, seq, heads, causal, st);
-    default: return a16_fwd<6>(qkv, out, lse, batch, seq, heads, causal, st);
-  }
+// off != NULL: the packed (live-row) causal forward -- qkv and out packed, lse in its [b * H + h][seq] layout
+int attention16_fwd(const AttnPlan& p, const float* qkv, float* out, float* lse, const int32_t* off, int seq, int heads,
+                    int causal, hipStream_t st) {
+  return a16_instance(p.nt, [&](auto nt) {
+    constexpr int NT = decltype(nt)::value;
+    return p.family == CLIPFS_ATTN_MFMA16_PACKED ? a16_fwd<NT, true>(p, qkv, out, lse, off, seq, heads, causal, st)
+                                                 : a16_fwd<NT, false>(p, qkv, out, lse, off, seq, heads, causal, st);
+  });
 }
 
-int attention16_bwd(const float* qkv, const float* dout, const float* out, const float* lse, float* dqkv, float* work,
-                    int batch, int seq, int heads, int causal, hipStream_t st) {
-  switch ((seq + 15) / 16) {
-    case 1: return a16_bwd<1>(qkv, dout, out, lse, dqkv, work, batch, seq, heads, causal, st);
-    case 2: return a16_bwd<2>(qkv, dout, out, lse, dqkv, work, batch, seq, heads, causal, st);
-    case 3: return a16_bwd<3>(qkv, dout, out, lse, dqkv, work, batch, seq, heads, causal, st);
-    case 4: return a16_bwd<4>(qkv, dout, out, lse, dqkv, work, batch, seq, heads, causal, st);
-    case 5: return a16_bwd<5>(qkv, dout, out, lse, dqkv, work, batch, seq, heads, causal, st);
-    default: return a16_bwd<6>(qkv, dout, out, lse, dqkv, work, batch, seq, heads, causal, st);
-  }
-}
-
-// packed (live-row) backward: runtime tile bounds from off[], the launch sized by the full sequence.  pin: q/k/v and O
-// are packed too (saved by the live-row forward), otherwise they keep the full layout
-int attention16_bwd_packed(const float* qkv, const float* dout, const float* out, const float* lse, float* dqkv,
-                           const int32_t* off, int batch, int seq, int heads, bool pin, hipStream_t st) {
-#define A16_BWD_PACKED(nt)                                                                              \
-  return pin ? a16_bwd<nt, true, true>(qkv, dout, out, lse, dqkv, nullptr, batch, seq, heads, 1, st, off) \
-             : a16_bwd<nt, true, false>(qkv, dout, out, lse, dqkv, nullptr, batch, seq, heads, 1, st, off)
-  switch ((seq + 15) / 16) {
-    case 1: A16_BWD_PACKED(1);
-    case 2: A16_BWD_PACKED(2);
-    case 3: A16_BWD_PACKED(3);
-    case 4: A16_BWD_PACKED(4);
-    case 5: A16_BWD_PACKED(5);
-    default: A16_BWD_PACKED(6);
-  }
-#undef A16_BWD_PACKED
-}
-
-// packed (live-row) causal forward: qkv and out packed, lse in its [b * H + h][seq] layout
-int attention16_fwd_packed(const float* qkv, float* out, float* lse, const int32_t* off, int batch, int seq, int heads,
-                           hipStream_t st) {
-  switch ((seq + 15) / 16) {
-    case 1: return a16_fwd<1, true>(qkv, out, lse, batch, seq, heads, 1, st, off);
-    case 2: return a16_fwd<2, true>(qkv, out, lse, batch, seq, heads, 1, st, off);
-    case 3: return a16_fwd<3, true>(qkv, out, lse, batch, seq, heads, 1, st, off);
-    case 4: return a16_fwd<4, true>(qkv, out, lse, batch, seq, heads, 1, st, off);
-    case 5: return a16_fwd<5, true>(qkv, out, lse, batch, seq, heads, 1, st, off);
-    default: return a16_fwd<6, true>(qkv, out, lse, batch, seq, heads, 1, st, off);
-  }
+// packed: qkv, out and lse keep the forward's full layout, dout and dqkv are packed; pinned: qkv and out are packed too
+// (saved by the live-row forward)
+int attention16_bwd(const AttnPlan& p, const float* qkv, const float* dout, const float* out, const float* lse, float* dqkv,
+                    const int32_t* off, int seq, int heads, int causal, hipStream_t st) {
+  return a16_instance(p.nt, [&](auto nt) {
+    constexpr int NT = decltype(nt)::value;
+    switch (p.family) {
+      case CLIPFS_ATTN_MFMA16_PINNED: return a16_bwd<NT, true, true>(p, qkv, dout, out, lse, dqkv, off, seq, heads, causal, st);
+      case CLIPFS_ATTN_MFMA16_PACKED: return a16_bwd<NT, true, false>(p, qkv, dout, out, lse, dqkv, off, seq, heads, causal, st);
+      default: return a16_bwd<NT, false, false>(p, qkv, dout, out, lse, dqkv, off, seq, heads, causal, st);
+    }
+  });
 }
 
 }  // namespace clipfs

@@ -10,6 +10,9 @@ namespace clipfs {
 
 void set_error(const char* fmt, ...);
 
+// the plan of the exact-fp32 attention (clipfs.h; the C function of the same name hides the struct's in C++)
+typedef struct clipfs_attention_plan AttnPlan;
+
 #define CLIPFS_REQUIRE(cond, ...)            \
   do {                                       \
     if (!(cond)) {                           \

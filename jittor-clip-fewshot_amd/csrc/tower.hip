@@ -77,7 +77,7 @@ static SavedLayout saved_layout_rows(const clipfs_tower* t, size_t M, size_t bat
   L.t_qkv = o; o += al4(M * 3 * r);
   L.qkv = o;   o += al4(qkv_f16(t) ? (M * 3 * d + 1) / 2 : M * 3 * d);  // fp16 mode: q | k | v saved as f16
   L.att = o;   o += al4(M * d);
-  // log-sum-exp rows: the long-sequence fp32 kernels (0 floats for seq <= 96) and every f16 MFMA attention need them
+  // log-sum-exp rows (batch * seq * heads floats in either mode): every backward with statistics reads them
   L.lse = o;   o += al4(t->weight_format == 2 ? batch * t->seq * (size_t)t->heads
                                               : clipfs_attention_lse_floats((int)batch, t->seq, t->heads));
   L.t_o = o;   o += al4(M * r);
@@ -570,10 +570,10 @@ static int fwd_block(const Pass& p, int l, float* x, const int32_t* rows, float*
   float* x_mid = sv ? sv + SL.x_mid : xr;
   float* t_qkv = sv ? sv + SL.t_qkv : p.scratch + SC.dt;
   float* t_o = sv ? sv + SL.t_o : p.scratch + SC.dt + al4((size_t)n * 3 * r);
-  // attention statistics: kept, or -- below the floor of a saving dense forward -- written to the MLP scratch (dead until
-  // the c_fc GEMM): the attention kernels are picked by whether lse is requested, and a block below the floor must
-  // produce bitwise the block output of the saving forward.  The packed kernel is the same with or without statistics.
-  float* lse = sv ? sv + SL.lse : (train && !v.packed() ? p.scratch + SC.big : nullptr);
+  // attention statistics: kept, or not written at all.  No forward kernel depends on lse (it only guards one store:
+  // the plan is the same with and without it, which tests/test_attention_plan.py asserts for every length), so a block
+  // below the floor produces bitwise the block output of the saving forward.
+  float* lse = sv ? sv + SL.lse : nullptr;
   float* stat1 = sv ? sv + SL.stat1 : nullptr;
   float* stat2 = sv ? sv + SL.stat2 : nullptr;
   const Adapters ad = adapters(b);
