@@ -339,25 +339,58 @@ int clipfs_attention_f16_bwd_packed(const void* qkv, int qkv_f16, const void* do
  * segment s: stream id = stream_base + s, element (drow0 + m, k) as documented in DESIGN.md
  * (drow0 = index of row 0 in the GLOBAL batch: a data-parallel shard draws the masks of the
  * one-process run); p = 0 or seed == 0 disables dropout.  seg_mask bit s = 0 leaves t[:, s*r..] = 0.
- * Ranks: 1 <= r <= 64 with nseg * r <= 192 where the matrix-core kernels cover the shape (width % 128 == 0, nseg 1 or
- * 3), nseg * r <= 64 elsewhere; a rank outside that is CLIPFS_EINVAL, the message naming the rank and the width. */
+ * Two kernel families run these calls, the matrix-core kernels (ranks 1 ... 64) and the one-wave-per-row kernels;
+ * clipfs_lora_plan below is the function that chooses, and says for any shape what runs or why it is refused.  A rank
+ * no family takes is CLIPFS_EINVAL, the message naming the rank and the width. */
 int clipfs_lora_down(const float* x, const float* A, float* t, int rows, int width, int r, int nseg,
                      unsigned seg_mask, float p, uint64_t seed, uint32_t stream_base, uint32_t drow0,
                      void* keep_bits, void* stream);
 /* keep_bits (may be NULL): uint16 [rows, width/4]; with dropout active the forward records its masks there -- bit
  * 4*s + e of entry (m, c) set <=> element (m, 4*c + e) was kept for segment s -- and clipfs_lora_bwd / _f16dy given the
  * same buffer read them instead of evaluating Philox again (identical masks by construction; the adapter's dA / dx
- * products were VALU-bound on the generator).  Matrix-core kernels only: clipfs_lora_keep_bits_ok(...) != 0
- * (1 <= r <= 64, width % 128 == 0, nseg 1 or 3; 4 bits per segment and float4 at every rank). */
+ * products were VALU-bound on the generator).  Matrix-core kernels only: clipfs_lora_keep_bits_ok(...) != 0, the
+ * plan's keep_bits_ok (4 bits per segment and float4 at every rank). */
 int clipfs_lora_keep_bits_ok(int width, int segw, int r, int nseg);
+/* The dispatch of the four entry points as data: clipfs_lora_plan IS the function they execute.  Host-only (no GPU is
+ * opened, nothing is launched).  Returns CLIPFS_EINVAL with the entry point's own message, which names the cause, for
+ * a shape the entry point would refuse.  The aids CLIPFS_LORA_MFMA=0 (one-wave-per-row kernels only) and
+ * CLIPFS_LORA_KEEP_BITS=0 (no keep bits) are read once per process and show in the plan.  The matrix-core family takes
+ * 1 <= r <= 64, nseg 1 or 3, width % 128 == 0 and segw % 64 == 0; what it declines goes to the row family: a
+ * down-projection of nseg * r <= 64 outputs at width <= 2048, a backward of rank 1, 2, 4, 8 or 16. */
+#define CLIPFS_LORA_OP_DOWN 0          /* operation: clipfs_lora_down (segw is not looked at) */
+#define CLIPFS_LORA_OP_BWD 1           /*   clipfs_lora_bwd, clipfs_lora_bwd_xact */
+#define CLIPFS_LORA_OP_BWD_F16DY 2     /*   clipfs_lora_bwd_f16dy */
+#define CLIPFS_LORA_FLAG_X_ACT 1       /* flag: x holds the pre-activation (clipfs_lora_bwd_xact with x_act = 1) */
+#define CLIPFS_LORA_FLAG_KEEP_BITS 2   /*   keep_bits given */
+#define CLIPFS_LORA_FLAG_FROZEN 4      /*   dA == dB == NULL */
+#define CLIPFS_LORA_FLAG_DX 8          /*   dx given */
+#define CLIPFS_LORA_FAMILY_MFMA 0      /* family: matrix-core kernels, `groups` rank groups of 16 */
+#define CLIPFS_LORA_FAMILY_ROW 1       /*   one-wave-per-row kernels */
+struct clipfs_lora_launch {
+  unsigned grid_x, grid_y, block;
+};
+struct clipfs_lora_plan {
+  int family;                 /* CLIPFS_LORA_FAMILY_* */
+  int groups, rq;             /* MFMA: the instance -- rank groups G = ceil(r / 16); K-steps RQ of the dA / dx launch,
+                                 ceil(r / 4) up to r = 16 and 4 G above (0 in the row family and for the down-projection) */
+  int sr_b, slices_b;         /* backward: rows per slice and slices of the dB reduction (no slices when frozen) */
+  int sr_a, slices_a;         /*   ... of the dA reduction */
+  size_t work_floats;         /* floats the call writes into `work`: the dB partials [slices_b][nseg * segw][r], then */
+  size_t part_a_offset;       /*   from this offset the dA partials [slices_a][nseg * r][width] */
+  int keep_bits_ok, f16dy_ok; /* whether the shape may record / read keep bits, and take dy as its f16 image */
+  int launches;               /* MFMA backward: dB partials || dt, dA partials || dx, both slice sums.  Row backward: dt,
+                                 dB partials, sum, dA partials, sum, dx.  Frozen or without dx: those launches are absent */
+  struct clipfs_lora_launch launch[6];
+};
+int clipfs_lora_plan(int op, int rows, int width, int segw, int r, int nseg, int flags, struct clipfs_lora_plan* plan);
 /* Backward of the adapter pair for one linear with nseg stacked segments:
  *   dt[m, s*r+j]  = scale * sum_n dy[m, s*segw + n] * B[s*segw + n, j]
  *   dB[s*segw+n,j] += scale * sum_m dy[m, s*segw+n] * t[m, s*r+j]
  *   dA[s*r+j, k]  += sum_m dt[m, s*r+j] * drop_s(x)[m,k]
  *   dx[m,k]       += sum_{s,j} dt[m, s*r+j] * A[s*r+j,k] * dropscale_s(m,k)   (if dx != NULL)
- * work: caller scratch, >= clipfs_lora_bwd_work_floats(...) floats.
- * Ranks: 1 ... 64 on the matrix-core kernels (width % 128 == 0, segw % 64 == 0, nseg 1 or 3); elsewhere the
- * one-wave-per-row kernels take r = 1, 2, 4, 8, 16 and any other rank is CLIPFS_EINVAL naming the rank and the width.
+ * work: caller scratch, >= clipfs_lora_bwd_work_floats(...) floats: a bound over the families that may take the call
+ * (the plan's work_floats is what the call writes).  dy, x, A, work and dx must be 16-byte aligned in all three backward
+ * entry points: a misaligned one is CLIPFS_EINVAL ("misaligned pointer"), never another kernel family.
  * Frozen adapter: dA == dB == NULL computes dt and the dx contribution only -- no dB / dA partial products or slice
  * reductions are launched, and dt / dx are bitwise those of the call with slots.  With dx NULL as well only dt is
  * computed.  Exactly one of dA / dB NULL is CLIPFS_EINVAL.  The same holds for clipfs_lora_bwd_f16dy. */
@@ -368,8 +401,7 @@ int clipfs_lora_bwd(const float* dy, const float* x, const float* t, const float
                     uint32_t drow0, const void* keep_bits, float* work, void* stream);
 /* Rectangular adapters (nseg == 1 only): clipfs_lora_bwd also takes segw != width -- width the adapter's input width,
  * segw its output width (dy [rows, segw], B [segw, r], A [r, width]; both multiples of 4) -- the MLP linears' d -> 4d and
- * 4d -> d.  Matrix-core kernels where width % 128 == 0 and segw % 64 == 0 (ranks 1 ... 64), the one-wave-per-row kernels
- * elsewhere (r = 1, 2, 4, 8, 16).  Their work buffer is sized by clipfs_lora_bwd_work_floats2, which equals
+ * 4d -> d.  Their work buffer is sized by clipfs_lora_bwd_work_floats2, which equals
  * clipfs_lora_bwd_work_floats for segw == width.  clipfs_lora_down takes widths up to 4096 (c_proj's input).
  * clipfs_lora_bwd_xact is the one-segment call (seg_mask 1, no keep bits) with a switch on how x is read: x_act = 1 says x
  * holds a pre-activation u and the adapter's input was QuickGELU(u), which the dA product applies as it loads x -- the
@@ -383,7 +415,7 @@ int clipfs_lora_bwd_xact(const float* dy, const float* x, const float* t, const 
 int clipfs_gelu_bwd_inplace(float* dg, const float* u, size_t n, void* stream);
 /* The same with dy given as its f16 image [rows, nseg*segw] (fp16 storage mode: the tensor the dgrad GEMM consumes), so
  * that the two passes over dy move half the bytes and the fp32 dy need not exist.  Matrix-core kernels only:
- * clipfs_lora_bwd_f16dy_ok(width, segw, r, nseg) != 0 says a shape is covered (r <= 64, width % 128 == 0, ...). */
+ * clipfs_lora_bwd_f16dy_ok(width, segw, r, nseg) != 0, the plan's f16dy_ok, says a shape is covered. */
 int clipfs_lora_bwd_f16dy_ok(int width, int segw, int r, int nseg);
 int clipfs_lora_bwd_f16dy(const void* dy16, const float* x, const float* t, const float* A, const float* B,
                           float* dt, float* dA, float* dB, float* dx, int rows, int width, int segw, int r,

@@ -66,6 +66,21 @@ ATTN_DIRECTIONS = ("fwd", "bwd", "fwd_packed", "bwd_packed", "bwd_packed_io")
 ATTN_STATS, ATTN_ALIGNED = 1, 2
 ATTN_FAMILIES = ("mfma16", "mfma16_packed", "mfma16_pinned", "mfma32", "mfma_long", "stream", "recompute")
 
+class LoraLaunch(C.Structure):
+    _fields_ = [("grid_x", C.c_uint), ("grid_y", C.c_uint), ("block", C.c_uint)]
+
+
+class LoraPlan(C.Structure):
+    _fields_ = [("family", C.c_int), ("groups", C.c_int), ("rq", C.c_int), ("sr_b", C.c_int), ("slices_b", C.c_int),
+                ("sr_a", C.c_int), ("slices_a", C.c_int), ("work_floats", C.c_size_t), ("part_a_offset", C.c_size_t),
+                ("keep_bits_ok", C.c_int), ("f16dy_ok", C.c_int), ("launches", C.c_int), ("launch", LoraLaunch * 6)]
+
+
+# CLIPFS_LORA_* operations, flags and kernel families of include/clipfs.h, by value
+LORA_OPS = ("down", "bwd", "bwd_f16dy")
+LORA_X_ACT, LORA_KEEP_BITS, LORA_FROZEN, LORA_DX = 1, 2, 4, 8
+LORA_FAMILIES = ("mfma", "row")
+
 # CLIPFS_F16_* kernel ids of include/clipfs.h, by value
 F16_KERNELS = ("64x128", "64x128_s2", "128x128", "256x128", "pp_reg", "pp_lds", "ph16", "ph16_wide", "ph32")
 
@@ -136,6 +151,7 @@ SIGNATURES = {
     "clipfs_attention_f16_fwd": (_i, [_p, _i, _p, _p, _p, _i, _i, _i, _i, _p]),
     "clipfs_attention_f16_bwd": (_i, [_p, _i, _p, _i, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p]),
     "clipfs_lora_keep_bits_ok": (_i, [_i, _i, _i, _i]),
+    "clipfs_lora_plan": (_i, [_i, _i, _i, _i, _i, _i, _i, C.POINTER(LoraPlan)]),
     "clipfs_lora_down": (_i, [_p, _p, _p, _i, _i, _i, _i, _u, _f, _u64, _u32, _u32, _p, _p]),
     "clipfs_lora_bwd_work_floats": (_sz, [_i, _i, _i, _i]),
     "clipfs_lora_bwd": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _u, _f, _f, _u64, _u32, _u32, _p, _p, _p]),
@@ -246,6 +262,18 @@ def attention_plan(direction: str, batch: int, seq: int, heads: int, causal: boo
            "recompute": ("lmax",)}.get(ATTN_FAMILIES[plan.family], ())
     return dict(family=ATTN_FAMILIES[plan.family], **{k: getattr(plan, k) for k in own},
                 launches=tuple((l.grid_x, l.grid_y, l.block, l.lds_bytes) for l in plan.launch[:plan.launches]))
+
+
+def lora_plan(op: str, rows: int, width: int, segw: int, r: int, nseg: int, x_act: bool = False, keep_bits: bool = False,
+              frozen: bool = False, dx: bool = True):
+    """The plan clipfs_lora_down / _bwd / _bwd_xact / _bwd_f16dy execute for these arguments (host-only), as a dict of the
+    fields of struct clipfs_lora_plan with launches = ((grid_x, grid_y, block), ...).  A refusal raises ClipfsError with
+    its message."""
+    plan = LoraPlan()
+    flags = (LORA_X_ACT if x_act else 0) | (LORA_KEEP_BITS if keep_bits else 0) | (LORA_FROZEN if frozen else 0) | (LORA_DX if dx else 0)
+    check(load().clipfs_lora_plan(LORA_OPS.index(op), rows, width, segw, r, nseg, flags, C.byref(plan)), "lora_plan")
+    d = {k: getattr(plan, k) for k, _ in LoraPlan._fields_[1:-2]}
+    return dict(family=LORA_FAMILIES[plan.family], **d, launches=tuple((l.grid_x, l.grid_y, l.block) for l in plan.launch[:plan.launches]))
 
 
 def new_tower() -> Tower:

@@ -3,7 +3,7 @@
 //   down : t = drop(x) A^T           [rows, nseg*r]   (this file, HBM-bound: one read of x)
 //   up   : y += scale * t B^T        (fused into the GEMM epilogue, gemm.hip)
 // and the backward is three skinny products that each read their big operand exactly once.
-#include "common.h"
+#include "lora.h"
 
 #include <stdlib.h>
 
@@ -11,8 +11,7 @@ namespace clipfs {
 
 constexpr int LORA_MAX_CHUNKS = 8;  // width <= 2048 (one-wave-per-row kernel; the matrix-core kernel has no such bound)
 constexpr int LORA_MAX_WIDTH = 4096;  // c_proj's input, 4 d
-constexpr int LORA_MAX_OUT = 64;    // nseg * r of the one-wave-per-row kernel
-constexpr int LORA_MFMA_MAX_OUT = 192;  // nseg * r of the matrix-core kernels (3 segments x r <= 64)
+constexpr int LORA_MAX_OUT = 64;    // nseg * r of the one-wave-per-row kernel (the matrix-core kernels: 3 x 64)
 
 // one wave per row
 __global__ __launch_bounds__(256) void lora_down_kernel(const float* __restrict__ x, const float* __restrict__ A,
@@ -286,204 +285,253 @@ __global__ __launch_bounds__(256) void gelu_bwd_inplace_kernel(float* __restrict
   if (blockIdx.x == 0 && threadIdx.x < 3 && tail < n) dg[tail] *= quick_gelu_grad(u[tail]);
 }
 
-// rows per reduction slice: 64 for large row counts, smaller when there are few rows so that the partial
-// kernels still put >= ~1000 waves on the chip (per-rank batches of 32 images: M = 1600)
-static inline int lora_slice_rows(int rows) {
+// ---- the plan ---------------------------------------------------------------------------------------------------
+
+constexpr int MFMA = CLIPFS_LORA_FAMILY_MFMA, ROW = CLIPFS_LORA_FAMILY_ROW;
+static const char* const LORA_OP_NAME[] = {"lora_down", "lora_bwd", "lora_bwd_f16dy"};
+
+static LoraAids lora_aids() {
+  static const LoraAids a = {(getenv("CLIPFS_LORA_MFMA") ? atoi(getenv("CLIPFS_LORA_MFMA")) : 1) != 0,
+                             (getenv("CLIPFS_LORA_KEEP_BITS") ? atoi(getenv("CLIPFS_LORA_KEEP_BITS")) : 1) != 0};
+  return a;
+}
+
+// why the matrix-core family declines a shape; nullptr: it takes it
+static const char* lora_mfma_declines(const LoraAids& aids, int width, int segw, int r, int nseg) {
+  if (!aids.mfma) return "switched off by CLIPFS_LORA_MFMA=0";
+  if (r < 1 || r > 64) return "they take ranks 1 ... 64";
+  if (nseg != 1 && nseg != 3) return "they take 1 or 3 segments";
+  if (width % 128) return "they need width % 128 == 0";
+  if (segw % 64) return "they need segw % 64 == 0";
+  return nullptr;
+}
+
+// Rows per reduction slice of the row family: 64 for large row counts, smaller when there are few rows so that the
+// partial kernels still put >= ~1000 waves on the chip (per-rank batches of 32 images: M = 1600).
+static int lora_slice_rows(int rows) {
   int r = 64;
   while (r > 8 && (rows + r - 1) / r < 256) r >>= 1;
   return r;
 }
 
-// lora_mfma.hip
-bool lora_mfma_ok(int width, int segw, int r, int nseg);
-size_t lora_mfma_work_floats(int rows, int width, int segw, int r, int nseg);
-int lora_down_mfma(const float* x, const float* A, float* t, int rows, int width, int r, int nseg, unsigned seg_mask,
-                   float p, uint64_t seed, uint32_t stream_base, uint32_t drow0, uint16_t* keep_bits, hipStream_t st);
-typedef void (*lora_reduce2_fn)(const float*, float*, size_t, int, float, const float*, float*, size_t, int, float, hipStream_t);
-int lora_bwd_mfma_f16dy(const void* dy16, const float* x, const float* t, const float* A, const float* B, float* dt, float* dA,
-                        float* dB, float* dx, int rows, int width, int segw, int r, int nseg, unsigned seg_mask, float scale,
-                        float p, uint64_t seed, uint32_t stream_base, uint32_t drow0, const uint16_t* keep_bits,
-                        float* work, hipStream_t st, lora_reduce2_fn reduce);
-int lora_bwd_mfma(const float* dy, const float* x, const float* t, const float* A, const float* B, float* dt, float* dA,
-                  float* dB, float* dx, int rows, int width, int segw, int r, int nseg, unsigned seg_mask, float scale,
-                  float p, uint64_t seed, uint32_t stream_base, uint32_t drow0, const uint16_t* keep_bits, float* work,
-                  hipStream_t st, lora_reduce2_fn reduce);
-
-// nseg == 1 with the adapter's input given as its pre-activation (x_act: QuickGELU applied as x is loaded for dA)
-int lora_bwd_mfma_xact(const float* dy, const float* x, const float* t, const float* A, const float* B, float* dt, float* dA,
-                       float* dB, float* dx, int rows, int width, int segw, int r, unsigned seg_mask, float scale, float p,
-                       uint64_t seed, uint32_t stream_base, uint32_t drow0, float* work, hipStream_t st, lora_reduce2_fn reduce);
-
-// the dB and dA slice sums of one adapter backward in one launch (blocks [0, nblk0) take the first)
-static void launch_reduce_slices2(const float* part0, float* out0, size_t n0, int slices0, float scale0, const float* part1,
-                                  float* out1, size_t n1, int slices1, float scale1, hipStream_t st) {
-  const unsigned nblk0 = (unsigned)((n0 + 63) / 64), nblk1 = (unsigned)((n1 + 63) / 64);
-  hipLaunchKernelGGL(reduce_slices2_kernel, dim3(nblk0 + nblk1), dim3(1024), 0, st, part0, out0, n0, slices0, scale0, part1,
-                     out1, n1, slices1, scale1, nblk0);
+// ... of the matrix-core family: enough slices to put ~6000 wave-groups (column groups x rank groups x slices) of work on
+// the chip, few enough that the partial sums stay small; never below 64 rows.  A wave does all G rank groups of its
+// columns, so a larger rank needs fewer slices for the same work.
+static int lora_mfma_slice_rows(int rows, int col_groups) {
+  int sr = 2048;
+  while (sr > 64 && (long)col_groups * ((rows + sr - 1) / sr) < 6144) sr >>= 1;
+  return sr;
 }
 
-static bool use_lora_mfma() {
-  static const int cfg = getenv("CLIPFS_LORA_MFMA") ? atoi(getenv("CLIPFS_LORA_MFMA")) : 1;  // 0: scalar kernels (A/B aid)
-  return cfg != 0;
+static unsigned cdiv(size_t a, size_t b) { return (unsigned)((a + b - 1) / b); }
+
+static void lora_add_launch(LoraPlan& p, unsigned grid_x, unsigned grid_y, unsigned block) {
+  p.launch[p.launches++] = {grid_x, grid_y, block};
+}
+
+// The backward in p.family: slices, layout of `work`, launches.  Geometry alone -- what a family takes is lora_plan's.
+static void lora_bwd_geometry(LoraPlan& p, int rows, int width, int segw, int r, int nseg, int flags) {
+  const bool grads = !(flags & CLIPFS_LORA_FLAG_FROZEN), dx = (flags & CLIPFS_LORA_FLAG_DX) != 0;
+  const int cols = nseg * segw;
+  const size_t nb = (size_t)cols * r, na = (size_t)nseg * r * width;  // dB / dA floats per slice
+  if (p.family == MFMA) {
+    p.groups = (r + 15) / 16;
+    p.rq = r <= 16 ? (r + 3) / 4 : 4 * p.groups;  // dx: ceil(r / 4) K-steps in one rank group, whole groups of 4 above
+    p.sr_b = lora_mfma_slice_rows(rows, cols / 64 * p.groups);
+    p.sr_a = lora_mfma_slice_rows(rows, width / 64 * p.groups);
+  } else {
+    p.sr_b = p.sr_a = lora_slice_rows(rows);
+  }
+  // frozen adapter: no dB / dA workgroups, no slice sums (dt and dx come out bitwise the same)
+  p.slices_b = grads ? (rows + p.sr_b - 1) / p.sr_b : 0;
+  p.slices_a = grads ? (rows + p.sr_a - 1) / p.sr_a : 0;
+  p.part_a_offset = ((size_t)p.slices_b * nb + 3) & ~(size_t)3;  // (nb is a multiple of 4 wherever segw == width)
+  p.work_floats = p.part_a_offset + (size_t)p.slices_a * na;
+  const unsigned rows16 = cdiv(rows, 16), rows4 = cdiv(rows, 4);
+  if (p.family == MFMA) {
+    // dt and dB both read dy and do not depend on each other; dA and dx both need dt and touch different tensors: each
+    // pair is one launch whose leading blocks do the partials of 256 columns x one slice, the trailing ones 16 rows
+    lora_add_launch(p, cdiv(cols, 256) * p.slices_b + rows16, 1, 256);
+    if (grads || dx) lora_add_launch(p, cdiv(width, 256) * p.slices_a + (dx ? rows16 : 0), 1, 256);
+    if (grads) lora_add_launch(p, cdiv(nb, 64) + cdiv(na, 64), 1, 1024);
+  } else {
+    lora_add_launch(p, rows4, 1, 256);  // dt
+    if (grads) {
+      lora_add_launch(p, cdiv(cols, 256), p.slices_b, 256);  // dB partials, deterministic two-stage sum
+      lora_add_launch(p, cdiv(nb, 64), 1, 1024);
+      lora_add_launch(p, cdiv(width / 4, 64), p.slices_a, 64);  // dA partials
+      lora_add_launch(p, cdiv(na, 64), 1, 1024);
+    }
+    if (dx) lora_add_launch(p, rows4, 1, 256);
+  }
+}
+
+int lora_plan(const LoraAids& aids, int op, int rows, int width, int segw, int r, int nseg, int flags, LoraPlan& p) {
+  CLIPFS_REQUIRE(op >= CLIPFS_LORA_OP_DOWN && op <= CLIPFS_LORA_OP_BWD_F16DY, "lora_plan: operation %d unknown", op);
+  const char* who = LORA_OP_NAME[op];
+  const bool keep = (flags & CLIPFS_LORA_FLAG_KEEP_BITS) != 0, x_act = (flags & CLIPFS_LORA_FLAG_X_ACT) != 0;
+  if (op == CLIPFS_LORA_OP_DOWN) {
+    segw = width;
+    CLIPFS_REQUIRE(rows > 0 && width > 0 && (width & 3) == 0 && width <= LORA_MAX_WIDTH,
+                   "%s: rows %d width %d unsupported (width a multiple of 4 up to %d)", who, rows, width, LORA_MAX_WIDTH);
+  } else {
+    CLIPFS_REQUIRE(nseg == 1 || nseg == 3, "%s: nseg %d unsupported (1 or 3)", who, nseg);
+    // segw != width: one segment whose output width differs from its input width (the MLP linears: d -> 4d, 4d -> d)
+    CLIPFS_REQUIRE(rows > 0 && width > 0 && (width & 3) == 0 && (segw == width || (nseg == 1 && segw > 0 && (segw & 3) == 0)),
+                   "%s: rows %d width %d segw %d nseg %d unsupported (segw must equal width unless nseg is 1; both multiples of 4)",
+                   who, rows, width, segw, nseg);
+    CLIPFS_REQUIRE(!x_act || (op == CLIPFS_LORA_OP_BWD && nseg == 1 && !keep), "%s: x_act needs nseg 1, no keep bits and an fp32 dy", who);
+  }
+  const char* why = lora_mfma_declines(aids, width, segw, r, nseg);
+  p = LoraPlan{};
+  p.family = why ? ROW : MFMA;
+  p.f16dy_ok = !why && segw == width;
+  p.keep_bits_ok = p.f16dy_ok && aids.keep_bits;
+  CLIPFS_REQUIRE(!keep || p.keep_bits_ok, "%s: keep bits are %s by the matrix-core kernels only, where segw equals width (width %d segw %d r %d nseg %d: %s)",
+                 who, op == CLIPFS_LORA_OP_DOWN ? "recorded" : "read", width, segw, r, nseg,
+                 why ? why : segw != width ? "segw differs" : "switched off by CLIPFS_LORA_KEEP_BITS=0");
+  CLIPFS_REQUIRE(op != CLIPFS_LORA_OP_BWD_F16DY || p.f16dy_ok, "%s: width %d segw %d r %d nseg %d is outside the matrix-core kernels (%s)",
+                 who, width, segw, r, nseg, why ? why : "segw differs from width");
+  if (op == CLIPFS_LORA_OP_DOWN) {
+    // widths above 2048 (the c_proj adapter's input) and more than 64 outputs per row run on the matrix-core kernel only
+    CLIPFS_REQUIRE(!why || width <= 256 * LORA_MAX_CHUNKS, "%s: width %d needs the matrix-core kernels: %s", who, width, why);
+    CLIPFS_REQUIRE(!why || (r > 0 && nseg > 0 && nseg <= 4 && nseg * r <= LORA_MAX_OUT),
+                   "%s: rank %d x %d segments unsupported at width %d (%d outputs per row at most off the matrix-core kernels: %s)",
+                   who, r, nseg, width, LORA_MAX_OUT, why);
+    p.groups = why ? 0 : (r + 15) / 16;
+    lora_add_launch(p, why ? cdiv(rows, 4) : cdiv(rows, 16), 1, 256);
+    return CLIPFS_OK;
+  }
+  CLIPFS_REQUIRE(!why || r == 1 || r == 2 || r == 4 || r == 8 || r == 16,
+                 "%s: rank %d unsupported at width %d segw %d (one-wave-per-row kernels: 1, 2, 4, 8, 16; matrix-core kernels: %s)",
+                 who, r, width, segw, why);
+  lora_bwd_geometry(p, rows, width, segw, r, nseg, flags);
+  return CLIPFS_OK;
+}
+
+void launch_reduce_slices2(const clipfs_lora_launch& l, const float* part0, float* out0, size_t n0, int slices0, float scale0,
+                           const float* part1, float* out1, size_t n1, int slices1, float scale1, hipStream_t st) {
+  hipLaunchKernelGGL(reduce_slices2_kernel, dim3(l.grid_x), dim3(l.block), 0, st, part0, out0, n0, slices0, scale0, part1, out1,
+                     n1, slices1, scale1, cdiv(n0, 64));  // blocks [0, ceil(n0 / 64)) take the first
+}
+
+// ---- the row family executing a plan ------------------------------------------------------------------------------
+
+template <int R>
+static int lora_bwd_row(const LoraCall& c, const LoraPlan& p) {
+  const float* dy = static_cast<const float*>(c.dy);
+  const int cols = c.nseg * c.segw;
+  const clipfs_lora_launch* l = p.launch;
+  lora_launch(lora_dt_kernel<R>, *l++, c.st, dy, c.B, c.dt, c.rows, c.segw, c.nseg, c.seg_mask, c.scale);
+  CLIPFS_CHECK(launch_status());
+  if (c.dA) {  // dA == dB == NULL: frozen adapter, dt and dx only
+    lora_launch(lora_db_partial_kernel<R>, *l++, c.st, dy, c.t, c.work, c.rows, cols, c.segw, c.nseg, p.sr_b);
+    CLIPFS_CHECK(launch_status());
+    lora_launch(reduce_slices_kernel, *l++, c.st, c.work, c.dB, (size_t)cols * R, p.slices_b, c.scale);
+    CLIPFS_CHECK(launch_status());
+    float* part_a = c.work + p.part_a_offset;
+    const auto da = c.nseg == 3 ? lora_da_partial_kernel<R, 3, false>
+                                : c.x_act ? lora_da_partial_kernel<R, 1, true> : lora_da_partial_kernel<R, 1, false>;
+    lora_launch(da, *l++, c.st, c.x, c.dt, part_a, c.rows, c.width, c.seg_mask, c.p, c.seed, c.stream_base, c.drow0, p.sr_a);
+    CLIPFS_CHECK(launch_status());
+    lora_launch(reduce_slices_kernel, *l++, c.st, part_a, c.dA, (size_t)c.nseg * R * c.width, p.slices_a, 1.0f);
+    CLIPFS_CHECK(launch_status());
+  }
+  if (c.dx) {
+    lora_launch(lora_dx_kernel, *l++, c.st, c.dt, c.A, c.dx, c.rows, c.width, R, c.nseg, c.seg_mask, c.p, c.seed, c.stream_base,
+                c.drow0);
+    CLIPFS_CHECK(launch_status());
+  }
+  return CLIPFS_OK;
+}
+
+// the three backward entry points: validate, plan, execute
+static int lora_bwd(int op, const LoraCall& c) {
+  const char* who = LORA_OP_NAME[op];
+  CLIPFS_REQUIRE((c.dA == nullptr) == (c.dB == nullptr), "%s: dA and dB must both be given or both NULL (frozen adapter)", who);
+  CLIPFS_REQUIRE(c.dy && c.x && c.t && c.A && c.B && c.dt && c.work, "%s: null pointer", who);
+  CLIPFS_REQUIRE(c.p >= 0.f && c.p < 1.f, "%s: dropout p out of range", who);
+  // (dy as well: every kernel of both families reads it 16 bytes at a time)
+  CLIPFS_REQUIRE(aligned16(c.dy) && aligned16(c.x) && aligned16(c.A) && aligned16(c.work) && (!c.dx || aligned16(c.dx)),
+                 "%s: misaligned pointer", who);
+  LoraPlan p;
+  CLIPFS_CHECK(lora_plan(lora_aids(), op, c.rows, c.width, c.segw, c.r, c.nseg,
+                         (c.x_act ? CLIPFS_LORA_FLAG_X_ACT : 0) | (c.keep_bits ? CLIPFS_LORA_FLAG_KEEP_BITS : 0) |
+                             (c.dA ? 0 : CLIPFS_LORA_FLAG_FROZEN) | (c.dx ? CLIPFS_LORA_FLAG_DX : 0), p));
+  if (p.family == MFMA) return lora_bwd_mfma(c, p);
+  switch (c.r) {  // (the plan admits no other rank to this family)
+    case 1: return lora_bwd_row<1>(c, p);
+    case 2: return lora_bwd_row<2>(c, p);
+    case 4: return lora_bwd_row<4>(c, p);
+    case 8: return lora_bwd_row<8>(c, p);
+    default: return lora_bwd_row<16>(c, p);
+  }
 }
 
 }  // namespace clipfs
 
 using namespace clipfs;
 
-// whether the forward can record its dropout masks as keep bits for the backward (matrix-core kernels, <= 4 segments)
+extern "C" int clipfs_lora_plan(int op, int rows, int width, int segw, int r, int nseg, int flags, struct clipfs_lora_plan* plan) {
+  CLIPFS_REQUIRE(plan, "lora_plan: null plan");
+  LoraPlan p;
+  CLIPFS_CHECK(lora_plan(lora_aids(), op, rows, width, segw, r, nseg, flags, p));
+  *plan = p;
+  return CLIPFS_OK;
+}
+
+// whether the forward can record its dropout masks as keep bits for the backward / the backward can read dy as f16
 extern "C" int clipfs_lora_keep_bits_ok(int width, int segw, int r, int nseg) {
-  static const int cfg = getenv("CLIPFS_LORA_KEEP_BITS") ? atoi(getenv("CLIPFS_LORA_KEEP_BITS")) : 1;  // 0: Philox again in the backward (A/B aid)
-  return (cfg != 0 && use_lora_mfma() && lora_mfma_ok(width, segw, r, nseg) && segw == width && nseg <= 4) ? 1 : 0;
+  LoraPlan p;
+  return lora_plan(lora_aids(), CLIPFS_LORA_OP_BWD, 1, width, segw, r, nseg, 0, p) == CLIPFS_OK && p.keep_bits_ok;
+}
+
+extern "C" int clipfs_lora_bwd_f16dy_ok(int width, int segw, int r, int nseg) {
+  LoraPlan p;
+  return lora_plan(lora_aids(), CLIPFS_LORA_OP_BWD, 1, width, segw, r, nseg, 0, p) == CLIPFS_OK && p.f16dy_ok;
 }
 
 extern "C" int clipfs_lora_down(const float* x, const float* A, float* t, int rows, int width, int r, int nseg,
                                 unsigned seg_mask, float p, uint64_t seed, uint32_t stream_base, uint32_t drow0, void* keep_bits,
                                 void* stream) {
+  const LoraCall c = {.x = x, .t = t, .A = A, .rows = rows, .width = width, .segw = width, .r = r, .nseg = nseg,
+                      .seg_mask = seg_mask, .p = p, .seed = seed, .stream_base = stream_base, .drow0 = drow0,
+                      .keep_bits = static_cast<uint16_t*>(keep_bits), .st = (hipStream_t)stream};
   CLIPFS_REQUIRE(x && A && t, "lora_down: null pointer");
-  CLIPFS_REQUIRE(!keep_bits || clipfs_lora_keep_bits_ok(width, width, r, nseg),
-                 "lora_down: keep bits are recorded by the matrix-core kernels only (width %d r %d nseg %d)", width, r, nseg);
-  CLIPFS_REQUIRE(rows > 0 && width > 0 && (width & 3) == 0 && width <= LORA_MAX_WIDTH, "lora_down: width %d unsupported", width);
-  const bool mfma = use_lora_mfma() && lora_mfma_ok(width, width, r, nseg);
-  // widths above 2048 (the c_proj adapter's input) run on the matrix-core kernel only
-  CLIPFS_REQUIRE(mfma || width <= 256 * LORA_MAX_CHUNKS, "lora_down: width %d needs the matrix-core kernel (width %% 128 == 0)", width);
-  CLIPFS_REQUIRE(r > 0 && r <= 64 && nseg > 0 && nseg <= 4 && nseg * r <= (mfma ? LORA_MFMA_MAX_OUT : LORA_MAX_OUT),
-                 "lora_down: rank %d x %d segments unsupported at width %d (%d outputs per row at most%s)", r, nseg, width,
-                 mfma ? LORA_MFMA_MAX_OUT : LORA_MAX_OUT, mfma ? "" : "; more need width % 128 == 0");
   CLIPFS_REQUIRE(p >= 0.f && p < 1.f, "lora_down: dropout p %f out of range", (double)p);
   CLIPFS_REQUIRE(aligned16(x) && aligned16(A), "lora_down: misaligned pointer");
-  if (mfma)
-    return lora_down_mfma(x, A, t, rows, width, r, nseg, seg_mask, p, seed, stream_base, drow0,
-                          reinterpret_cast<uint16_t*>(keep_bits), (hipStream_t)stream);
-  hipLaunchKernelGGL(lora_down_kernel, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, x, A, t, rows, width, r,
-                     nseg, seg_mask, p, seed, stream_base, drow0);
+  LoraPlan pl;
+  CLIPFS_CHECK(lora_plan(lora_aids(), CLIPFS_LORA_OP_DOWN, rows, width, width, r, nseg, keep_bits ? CLIPFS_LORA_FLAG_KEEP_BITS : 0, pl));
+  if (pl.family == MFMA) return lora_down_mfma(c, pl);
+  lora_launch(lora_down_kernel, pl.launch[0], c.st, x, A, t, rows, width, r, nseg, seg_mask, p, seed, stream_base, drow0);
   return launch_status();
 }
 
-extern "C" size_t clipfs_lora_bwd_work_floats(int rows, int width, int r, int nseg) {
-  // r > 16 runs on the matrix-core kernels only: their own slice plan (which counts the rank groups as work, so the
-  // slices get longer as r grows) is the bound.  r <= 16 keeps the bound of both paths, unchanged.
-  if (r > 16) return lora_mfma_work_floats(rows, width, width, r, nseg) + 64;
-  const int sr = lora_slice_rows(rows);
-  const size_t slices = (size_t)(rows + sr - 1) / sr;
-  // dB partials: slices * (nseg*segw) * r with segw == width (q/k/v/o; the MLP adapters: clipfs_lora_bwd_work_floats2)
-  // dA partials: slices * nseg * r * width
-  return slices * (size_t)nseg * r * width * 2 + 64;
-}
-
-// The same bound for an adapter whose output width segw differs from its input width (nseg == 1: the MLP linears):
-// dB partials slices * segw * r, dA partials slices * r * width.  segw == width returns clipfs_lora_bwd_work_floats.
+// The work bound of a backward, whichever family takes it: r > 16 is the matrix-core family's alone; up to 16 either may
+// run (CLIPFS_LORA_MFMA) and the row family, whose slices are never the longer ones, needs the most.  segw != width: an
+// adapter whose output width differs from its input width (nseg == 1: the MLP linears).
 extern "C" size_t clipfs_lora_bwd_work_floats2(int rows, int width, int segw, int r, int nseg) {
-  if (segw == width) return clipfs_lora_bwd_work_floats(rows, width, r, nseg);
-  if (rows <= 0 || width <= 0 || segw <= 0 || r <= 0 || nseg != 1) return 0;
-  size_t need = 0;
-  if (lora_mfma_ok(width, segw, r, nseg)) need = lora_mfma_work_floats(rows, width, segw, r, nseg);
-  if (r <= 16) {  // either family may take the call (CLIPFS_LORA_MFMA)
-    const int sr = lora_slice_rows(rows);
-    const size_t slices = (size_t)(rows + sr - 1) / sr;
-    const size_t scalar = ((slices * (size_t)segw * r + 3) & ~(size_t)3) + slices * (size_t)r * width;
-    need = scalar > need ? scalar : need;
-  }
-  return need + 64;
+  if (segw != width && (rows <= 0 || width <= 0 || segw <= 0 || r <= 0 || nseg != 1)) return 0;
+  if (segw != width && r > 16 && lora_mfma_declines({true, true}, width, segw, r, nseg)) return 64;  // no family: nothing to size
+  LoraPlan p{};
+  p.family = r > 16 ? MFMA : ROW;
+  lora_bwd_geometry(p, rows, width, segw, r, nseg, 0);
+  return p.work_floats + 64;
 }
 
-template <int R, bool XACT = false>
-static int lora_bwd_r(const float* dy, const float* x, const float* t, const float* A, const float* B, float* dt,
-                      float* dA, float* dB, float* dx, int rows, int width, int segw, int nseg, unsigned seg_mask,
-                      float scale, float p, uint64_t seed, uint32_t stream_base, uint32_t drow0, float* work, hipStream_t st) {
-  const int sr = lora_slice_rows(rows);
-  const int slices = (rows + sr - 1) / sr;
-  const int cols = nseg * segw;
-  hipLaunchKernelGGL((lora_dt_kernel<R>), dim3((rows + 3) / 4), dim3(256), 0, st, dy, B, dt, rows, segw, nseg, seg_mask,
-                     scale);
-  CLIPFS_CHECK(launch_status());
-  if (dA) {  // dA == dB == NULL: frozen adapter, dt and dx only
-    // dB
-    float* part_b = work;
-    hipLaunchKernelGGL((lora_db_partial_kernel<R>), dim3((cols + 255) / 256, slices), dim3(256), 0, st, dy, t, part_b,
-                       rows, cols, segw, nseg, sr);
-    CLIPFS_CHECK(launch_status());
-    const size_t nb = (size_t)cols * R;
-    hipLaunchKernelGGL(reduce_slices_kernel, dim3((unsigned)((nb + 63) / 64)), dim3(1024), 0, st, part_b, dB, nb, slices,
-                       scale);
-    CLIPFS_CHECK(launch_status());
-    // dA
-    float* part_a = work + (((size_t)slices * nb + 3) & ~(size_t)3);  // (nb is a multiple of 4 wherever segw == width)
-    const dim3 ga((width / 4 + 63) / 64, slices);
-    if (nseg == 1 && XACT)
-      hipLaunchKernelGGL((lora_da_partial_kernel<R, 1, true>), ga, dim3(64), 0, st, x, dt, part_a, rows, width, seg_mask, p,
-                         seed, stream_base, drow0, sr);
-    else if (nseg == 1)
-      hipLaunchKernelGGL((lora_da_partial_kernel<R, 1>), ga, dim3(64), 0, st, x, dt, part_a, rows, width, seg_mask, p,
-                         seed, stream_base, drow0, sr);
-    else
-      hipLaunchKernelGGL((lora_da_partial_kernel<R, 3>), ga, dim3(64), 0, st, x, dt, part_a, rows, width, seg_mask, p,
-                         seed, stream_base, drow0, sr);
-    CLIPFS_CHECK(launch_status());
-    const size_t na = (size_t)nseg * R * width;
-    hipLaunchKernelGGL(reduce_slices_kernel, dim3((unsigned)((na + 63) / 64)), dim3(1024), 0, st, part_a, dA, na, slices,
-                       1.0f);
-    CLIPFS_CHECK(launch_status());
-  }
-  if (dx) {
-    hipLaunchKernelGGL(lora_dx_kernel, dim3((rows + 3) / 4), dim3(256), 0, st, dt, A, dx, rows, width, R, nseg, seg_mask,
-                       p, seed, stream_base, drow0);
-    CLIPFS_CHECK(launch_status());
-  }
-  return CLIPFS_OK;
-}
-
-static int lora_bwd_impl(const float* dy, const float* x, const float* t, const float* A, const float* B, float* dt, float* dA,
-                         float* dB, float* dx, int rows, int width, int segw, int r, int nseg, unsigned seg_mask, float scale,
-                         float p, uint64_t seed, uint32_t stream_base, uint32_t drow0, const void* keep_bits, int x_act,
-                         float* work, void* stream) {
-  CLIPFS_REQUIRE((dA == nullptr) == (dB == nullptr), "lora_bwd: dA and dB must both be given or both NULL (frozen adapter)");
-  CLIPFS_REQUIRE(dy && x && t && A && B && dt && work, "lora_bwd: null pointer");
-  CLIPFS_REQUIRE(nseg == 1 || nseg == 3, "lora_bwd: nseg %d unsupported (1 or 3)", nseg);
-  CLIPFS_REQUIRE(!keep_bits || (clipfs_lora_keep_bits_ok(width, segw, r, nseg) && aligned16(dy) && aligned16(dx ? dx : x)),
-                 "lora_bwd: keep bits are read by the matrix-core kernels only (width %d r %d nseg %d)", width, r, nseg);
-  // segw != width: one segment whose output width differs from its input width (the MLP linears: d -> 4d, 4d -> d)
-  CLIPFS_REQUIRE(rows > 0 && width > 0 && (width & 3) == 0 && (segw == width || (nseg == 1 && segw > 0 && (segw & 3) == 0)),
-                 "lora_bwd: width %d segw %d nseg %d unsupported (segw must equal width unless nseg is 1; both multiples of 4)",
-                 width, segw, nseg);
-  CLIPFS_REQUIRE(!x_act || (nseg == 1 && !keep_bits), "lora_bwd: x_act needs nseg 1 and no keep bits");
-  CLIPFS_REQUIRE(segw == width || aligned16(dy), "lora_bwd: misaligned dy");
-  CLIPFS_REQUIRE(p >= 0.f && p < 1.f, "lora_bwd: dropout p out of range");
-  CLIPFS_REQUIRE(aligned16(x) && aligned16(A) && aligned16(work) && (!dx || aligned16(dx)), "lora_bwd: misaligned pointer");
-  hipStream_t st = (hipStream_t)stream;
-  if (x_act && use_lora_mfma() && lora_mfma_ok(width, segw, r, nseg) && aligned16(dy) && aligned16(dx ? dx : x))
-    return lora_bwd_mfma_xact(dy, x, t, A, B, dt, dA, dB, dx, rows, width, segw, r, seg_mask, scale, p, seed, stream_base, drow0,
-                              work, st, launch_reduce_slices2);
-  if (use_lora_mfma() && lora_mfma_ok(width, segw, r, nseg) && aligned16(dy) && aligned16(dx ? dx : x))
-    return lora_bwd_mfma(dy, x, t, A, B, dt, dA, dB, dx, rows, width, segw, r, nseg, seg_mask, scale, p, seed, stream_base, drow0,
-                         reinterpret_cast<const uint16_t*>(keep_bits), work, st, launch_reduce_slices2);
-#define CLIPFS_LORA_CASE(RR)                                                                                       \
-  case RR:                                                                                                         \
-    if (x_act)                                                                                                     \
-      return lora_bwd_r<RR, true>(dy, x, t, A, B, dt, dA, dB, dx, rows, width, segw, nseg, seg_mask, scale, p,     \
-                                  seed, stream_base, drow0, work, st);                                             \
-    return lora_bwd_r<RR>(dy, x, t, A, B, dt, dA, dB, dx, rows, width, segw, nseg, seg_mask, scale, p, seed,       \
-                          stream_base, drow0, work, st)
-  switch (r) {
-    CLIPFS_LORA_CASE(1);
-    CLIPFS_LORA_CASE(2);
-    CLIPFS_LORA_CASE(4);
-    CLIPFS_LORA_CASE(8);
-    CLIPFS_LORA_CASE(16);
-    default:
-      set_error("lora_bwd: rank %d unsupported at width %d (one-wave-per-row kernels: 1, 2, 4, 8, 16; ranks up to 64 "
-                "need width %% 128 == 0)", r, width);
-      return CLIPFS_EINVAL;
-  }
-#undef CLIPFS_LORA_CASE
+extern "C" size_t clipfs_lora_bwd_work_floats(int rows, int width, int r, int nseg) {
+  return clipfs_lora_bwd_work_floats2(rows, width, width, r, nseg);
 }
 
 extern "C" int clipfs_lora_bwd(const float* dy, const float* x, const float* t, const float* A, const float* B,
                                float* dt, float* dA, float* dB, float* dx, int rows, int width, int segw, int r,
                                int nseg, unsigned seg_mask, float scale, float p, uint64_t seed, uint32_t stream_base, uint32_t drow0,
                                const void* keep_bits, float* work, void* stream) {
-  return lora_bwd_impl(dy, x, t, A, B, dt, dA, dB, dx, rows, width, segw, r, nseg, seg_mask, scale, p, seed, stream_base, drow0,
-                       keep_bits, 0, work, stream);
+  return lora_bwd(CLIPFS_LORA_OP_BWD,
+                  {.dy = dy, .x = x, .t = const_cast<float*>(t), .A = A, .B = B, .dt = dt, .dA = dA, .dB = dB, .dx = dx,
+                   .rows = rows, .width = width, .segw = segw, .r = r, .nseg = nseg, .seg_mask = seg_mask, .scale = scale,
+                   .p = p, .seed = seed, .stream_base = stream_base, .drow0 = drow0,
+                   .keep_bits = static_cast<uint16_t*>(const_cast<void*>(keep_bits)), .work = work, .st = (hipStream_t)stream});
 }
 
 // One-segment adapter backward with a switch on how x is read: x_act == 1 means x holds the pre-activation u and the
@@ -494,32 +542,25 @@ extern "C" int clipfs_lora_bwd_xact(const float* dy, const float* x, const float
                                     float* dA, float* dB, float* dx, int rows, int width, int segw, int r, float scale, float p,
                                     uint64_t seed, uint32_t stream_base, uint32_t drow0, int x_act, float* work, void* stream) {
   CLIPFS_REQUIRE(x_act == 0 || x_act == 1, "lora_bwd_xact: x_act %d (0 or 1)", x_act);
-  return lora_bwd_impl(dy, x, t, A, B, dt, dA, dB, dx, rows, width, segw, r, 1, 1u, scale, p, seed, stream_base, drow0, nullptr,
-                       x_act, work, stream);
+  return lora_bwd(CLIPFS_LORA_OP_BWD,
+                  {.dy = dy, .x = x, .t = const_cast<float*>(t), .A = A, .B = B, .dt = dt, .dA = dA, .dB = dB, .dx = dx,
+                   .rows = rows, .width = width, .segw = segw, .r = r, .nseg = 1, .seg_mask = 1u, .scale = scale, .p = p,
+                   .seed = seed, .stream_base = stream_base, .drow0 = drow0, .x_act = x_act != 0, .work = work,
+                   .st = (hipStream_t)stream});
 }
 
 // fp16 storage mode: the incoming gradient dy is read from its f16 image (what the dgrad GEMM consumes anyway) -- half
 // the bytes of the two passes over dy, and the producer (clipfs_attention_f16_bwd) no longer has to write the fp32
 // tensor at all.  Matrix-core kernels only: clipfs_lora_bwd_f16dy_ok says whether a shape is covered.
-extern "C" int clipfs_lora_bwd_f16dy_ok(int width, int segw, int r, int nseg) {
-  return (use_lora_mfma() && lora_mfma_ok(width, segw, r, nseg) && segw == width) ? 1 : 0;
-}
-
 extern "C" int clipfs_lora_bwd_f16dy(const void* dy16, const float* x, const float* t, const float* A, const float* B,
                                      float* dt, float* dA, float* dB, float* dx, int rows, int width, int segw, int r,
                                      int nseg, unsigned seg_mask, float scale, float p, uint64_t seed, uint32_t stream_base,
                                      uint32_t drow0, const void* keep_bits, float* work, void* stream) {
-  CLIPFS_REQUIRE((dA == nullptr) == (dB == nullptr),
-                 "lora_bwd_f16dy: dA and dB must both be given or both NULL (frozen adapter)");
-  CLIPFS_REQUIRE(dy16 && x && t && A && B && dt && work, "lora_bwd_f16dy: null pointer");
-  CLIPFS_REQUIRE(rows > 0 && clipfs_lora_bwd_f16dy_ok(width, segw, r, nseg),
-                 "lora_bwd_f16dy: width %d segw %d r %d nseg %d is outside the matrix-core kernels", width, segw, r, nseg);
-  CLIPFS_REQUIRE(p >= 0.f && p < 1.f, "lora_bwd_f16dy: dropout p out of range");
-  CLIPFS_REQUIRE(aligned16(dy16) && aligned16(x) && aligned16(A) && aligned16(work) && (!dx || aligned16(dx)),
-                 "lora_bwd_f16dy: misaligned pointer");
-  CLIPFS_REQUIRE(!keep_bits || clipfs_lora_keep_bits_ok(width, segw, r, nseg), "lora_bwd_f16dy: keep bits not covered");
-  return lora_bwd_mfma_f16dy(dy16, x, t, A, B, dt, dA, dB, dx, rows, width, segw, r, nseg, seg_mask, scale, p, seed, stream_base,
-                             drow0, reinterpret_cast<const uint16_t*>(keep_bits), work, (hipStream_t)stream, launch_reduce_slices2);
+  return lora_bwd(CLIPFS_LORA_OP_BWD_F16DY,
+                  {.dy = dy16, .dy_f16 = true, .x = x, .t = const_cast<float*>(t), .A = A, .B = B, .dt = dt, .dA = dA, .dB = dB,
+                   .dx = dx, .rows = rows, .width = width, .segw = segw, .r = r, .nseg = nseg, .seg_mask = seg_mask,
+                   .scale = scale, .p = p, .seed = seed, .stream_base = stream_base, .drow0 = drow0,
+                   .keep_bits = static_cast<uint16_t*>(const_cast<void*>(keep_bits)), .work = work, .st = (hipStream_t)stream});
 }
 
 extern "C" int clipfs_gelu_bwd_inplace(float* dg, const float* u, size_t n, void* stream) {

@@ -1,8 +1,8 @@
 // Rank-r LoRA products on the matrix cores, exact fp32 (v_mfma_f32_16x16x4_f32: the fp32 MFMA of the dense GEMMs
 // in its 16x16 shape).  Same five products, same Philox dropout stream and same results (up to summation order) as
-// the one-wave-per-row kernels in lora.hip, which remain for shapes outside width % 128 == 0 (ranks 1, 2, 4, 8, 16
-// there).  At r = 16 (cfg-5) the scalar kernels spend ~50 wave reductions per row; here every product is a tall-skinny
-// MFMA GEMM whose big operand is read once with 16-byte loads.  Ranks 1..64 run as G = ceil(r / 16) groups of 16
+// the one-wave-per-row kernels in lora.hip (lora_plan there says which family a call gets).  At r = 16 (cfg-5) the
+// scalar kernels spend ~50 wave reductions per row; here every product is a tall-skinny MFMA GEMM whose big operand
+// is read once with 16-byte loads.  Ranks 1..64 run as G = ceil(r / 16) groups of 16
 // rank columns (N = 16 of the MFMA); a wave keeps all G groups' accumulators, so x or dy is still read once, and its
 // dropout masks drawn once, whatever the rank.  G = 1 is the r <= 16 arithmetic in its original order.
 //
@@ -16,7 +16,7 @@
 // result lane l = D[i = 4 (l >> 4) + v][j = l & 15], v = 0..3.  The k (and, for dB/dA/dx, the column) assignment is
 // free as long as both operands agree, so a lane always loads FOUR CONSECUTIVE floats (one float4 = one Philox call
 // = 4 dropout multipliers) and feeds them to four successive MFMAs.
-#include "common.h"
+#include "lora.h"
 
 namespace clipfs {
 
@@ -435,10 +435,10 @@ __device__ __forceinline__ void lora_dx_mfma_body(const float* __restrict__ dt, 
 }
 
 // ---- the backward as three launches ---------------------------------------------------------------------------
-// dt and dB both read dy and do not depend on each other; dA and dx both need dt and touch different tensors.  Each
-// pair is ONE launch whose leading blocks do the first product and whose trailing blocks do the second (the bodies
-// above, unchanged: same arithmetic, same results): at the per-rank sizes of the 8-GPU step every one of these products
-// is a few microseconds of work behind ~10 us of launch, and the two halves of a pair fill each other's tail.
+// dB partials || dt, dA partials || dx, both slice sums: each pair is ONE launch whose leading blocks do the first
+// product and whose trailing blocks do the second (the bodies above: same arithmetic, same results).  At the per-rank
+// sizes of the 8-GPU step every product is a few microseconds of work behind ~10 us of launch, and the two halves of a
+// pair fill each other's tail.
 template <int NSEG, int G, typename TY>
 __global__ __launch_bounds__(256) void lora_db_dt_mfma_kernel(const TY* __restrict__ dy, const float* __restrict__ B,
                                                               const float* __restrict__ t, float* __restrict__ dt,
@@ -468,162 +468,66 @@ __global__ __launch_bounds__(256) void lora_da_dx_mfma_kernel(const float* __res
     lora_dx_mfma_body<NSEG, RQ>(dt, A, dx, rows, width, r, seg_mask, p, seed, stream_base, drow0, b - n_da, keep_bits);
 }
 
-// ---- host side (called from lora.hip) ---------------------------------------------------------------------
-
-bool lora_mfma_ok(int width, int segw, int r, int nseg) {
-  return r >= 1 && r <= 64 && (nseg == 1 || nseg == 3) && (width % 128) == 0 && (segw % 64) == 0;
-}
-
-static inline int lora_groups(int r) { return (r + 15) / 16; }  // rank groups of 16 (G)
-
-// rows per reduction slice: enough slices to put ~6000 wave-groups (column groups x rank groups x slices) of work on
-// the chip, few enough that the partial sums stay small; never below 64 rows.  A wave does all G rank groups of its
-// columns, so a larger rank needs fewer slices for the same work.
-static int lora_mfma_slice_rows(int rows, int col_groups) {
-  int sr = 2048;
-  while (sr > 64 && (long)col_groups * ((rows + sr - 1) / sr) < 6144) sr >>= 1;
-  return sr;
-}
-
-struct LoraMfmaSlices {
-  int sr_b, slices_b, sr_a, slices_a;
-  size_t nb, na;  // dB / dA floats per slice
-  size_t floats() const { return (((size_t)slices_b * nb + 3) & ~(size_t)3) + (size_t)slices_a * na; }
-};
-
-static LoraMfmaSlices lora_mfma_slices(int rows, int width, int segw, int r, int nseg) {
-  const int cols = nseg * segw, G = lora_groups(r);
-  LoraMfmaSlices S;
-  S.sr_b = lora_mfma_slice_rows(rows, cols / 64 * G);
-  S.slices_b = (rows + S.sr_b - 1) / S.sr_b;
-  S.sr_a = lora_mfma_slice_rows(rows, width / 64 * G);
-  S.slices_a = (rows + S.sr_a - 1) / S.sr_a;
-  S.nb = (size_t)cols * r;
-  S.na = (size_t)nseg * r * width;
-  return S;
-}
-
-// what lora_bwd_mfma writes into its work buffer (dB partials, then dA partials)
-size_t lora_mfma_work_floats(int rows, int width, int segw, int r, int nseg) {
-  return lora_mfma_slices(rows, width, segw, r, nseg).floats();
-}
-
-template <int NSEG, int G>
-static int lora_down_mfma_n(const float* x, const float* A, float* t, int rows, int width, int r, unsigned seg_mask, float p,
-                            uint64_t seed, uint32_t stream_base, uint32_t drow0, uint16_t* keep_bits, hipStream_t st) {
-  hipLaunchKernelGGL((lora_down_mfma_kernel<NSEG, G>), dim3((rows + 15) / 16), dim3(256), 0, st, x, A, t, rows, width, r, seg_mask, p,
-                     seed, stream_base, drow0, keep_bits);
-  return launch_status();
-}
+// ---- host side: the plan (lora.hip) says what to launch; the switches below only select the compiled instance ------
 
 template <int NSEG>
-static int lora_down_mfma_g(const float* x, const float* A, float* t, int rows, int width, int r, unsigned seg_mask, float p,
-                            uint64_t seed, uint32_t stream_base, uint32_t drow0, uint16_t* keep_bits, hipStream_t st) {
-  switch (lora_groups(r)) {
-    case 1: return lora_down_mfma_n<NSEG, 1>(x, A, t, rows, width, r, seg_mask, p, seed, stream_base, drow0, keep_bits, st);
-    case 2: return lora_down_mfma_n<NSEG, 2>(x, A, t, rows, width, r, seg_mask, p, seed, stream_base, drow0, keep_bits, st);
-    case 3: return lora_down_mfma_n<NSEG, 3>(x, A, t, rows, width, r, seg_mask, p, seed, stream_base, drow0, keep_bits, st);
-    default: return lora_down_mfma_n<NSEG, 4>(x, A, t, rows, width, r, seg_mask, p, seed, stream_base, drow0, keep_bits, st);
+static int lora_down_mfma_s(const LoraCall& c, const LoraPlan& p) {
+  decltype(&lora_down_mfma_kernel<NSEG, 1>) down = nullptr;
+  switch (p.groups) {
+    case 1: down = lora_down_mfma_kernel<NSEG, 1>; break;
+    case 2: down = lora_down_mfma_kernel<NSEG, 2>; break;
+    case 3: down = lora_down_mfma_kernel<NSEG, 3>; break;
+    case 4: down = lora_down_mfma_kernel<NSEG, 4>; break;
   }
-}
-
-int lora_down_mfma(const float* x, const float* A, float* t, int rows, int width, int r, int nseg, unsigned seg_mask,
-                   float p, uint64_t seed, uint32_t stream_base, uint32_t drow0, uint16_t* keep_bits, hipStream_t st) {
-  if (nseg == 1) return lora_down_mfma_g<1>(x, A, t, rows, width, r, seg_mask, p, seed, stream_base, drow0, keep_bits, st);
-  return lora_down_mfma_g<3>(x, A, t, rows, width, r, seg_mask, p, seed, stream_base, drow0, keep_bits, st);
-}
-
-template <int NSEG, int RQ, bool XACT = false>
-static void launch_da_dx(const float* x, const float* dt, const float* A, float* part_a, float* dx, int rows, int width, int r,
-                         unsigned seg_mask, float p, uint64_t seed, uint32_t stream_base, uint32_t drow0, int sr_a, int slices_a,
-                         const uint16_t* keep_bits, hipStream_t st) {
-  const int gx_a = (width + 255) / 256, n_da = gx_a * slices_a;
-  const int n_dx = dx ? (rows + 15) / 16 : 0;
-  if (n_da + n_dx == 0) return;
-  hipLaunchKernelGGL((lora_da_dx_mfma_kernel<NSEG, RQ, XACT>), dim3(n_da + n_dx), dim3(256), 0, st, x, dt, A, part_a, dx, rows, width,
-                     r, seg_mask, p, seed, stream_base, drow0, sr_a, gx_a, n_da, keep_bits);
-}
-
-template <int NSEG, int G, typename TY>
-static void launch_db_dt(const TY* dy, const float* B, const float* t, float* dt, float* part_b, int rows, int segw, int r,
-                         unsigned seg_mask, float scale, int sr_b, int slices_b, hipStream_t st) {
-  const int cols = NSEG * segw;
-  const int gx_b = (cols + 255) / 256, n_db = gx_b * slices_b;
-  const int n_rows16 = (rows + 15) / 16;
-  hipLaunchKernelGGL((lora_db_dt_mfma_kernel<NSEG, G, TY>), dim3(n_db + n_rows16), dim3(256), 0, st, dy, B, t, dt, part_b, rows,
-                     segw, r, seg_mask, scale, sr_b, gx_b, n_db);
-}
-
-// reduce2(part_b, dB, nb, slices_b, scale_b, part_a, dA, na, slices_a, scale_a): both slice sums in one launch
-typedef void (*lora_reduce2_fn)(const float*, float*, size_t, int, float, const float*, float*, size_t, int, float, hipStream_t);
-
-template <int NSEG, typename TY, bool XACT = false>
-static int lora_bwd_mfma_n(const TY* dy, const float* x, const float* t, const float* A, const float* B, float* dt,
-                           float* dA, float* dB, float* dx, int rows, int width, int segw, int r, unsigned seg_mask,
-                           float scale, float p, uint64_t seed, uint32_t stream_base, uint32_t drow0, const uint16_t* keep_bits,
-                           float* work, hipStream_t st, lora_reduce2_fn reduce2) {
-  // dA == dB == NULL: frozen adapter -- no dB / dA workgroups, no slice sums (dt and dx come out bitwise the same)
-  const bool grads = dA != nullptr;
-  const LoraMfmaSlices S = lora_mfma_slices(rows, width, segw, r, NSEG);
-  const int slices_b = grads ? S.slices_b : 0, slices_a = grads ? S.slices_a : 0;
-  float* part_b = work;
-  float* part_a = work + (((size_t)slices_b * S.nb + 3) & ~(size_t)3);
-  // 1: dB partials || dt
-  switch (lora_groups(r)) {
-    case 1: launch_db_dt<NSEG, 1, TY>(dy, B, t, dt, part_b, rows, segw, r, seg_mask, scale, S.sr_b, slices_b, st); break;
-    case 2: launch_db_dt<NSEG, 2, TY>(dy, B, t, dt, part_b, rows, segw, r, seg_mask, scale, S.sr_b, slices_b, st); break;
-    case 3: launch_db_dt<NSEG, 3, TY>(dy, B, t, dt, part_b, rows, segw, r, seg_mask, scale, S.sr_b, slices_b, st); break;
-    default: launch_db_dt<NSEG, 4, TY>(dy, B, t, dt, part_b, rows, segw, r, seg_mask, scale, S.sr_b, slices_b, st); break;
-  }
-  CLIPFS_CHECK(launch_status());
-  // 2: dA partials || dx.  r <= 16: ceil(r / 4) K-steps for dx; above, whole rank groups of 4 K-steps
-#define CLIPFS_DA_DX(RQ)                                                                                                         \
-  launch_da_dx<NSEG, RQ, XACT>(x, dt, A, part_a, dx, rows, width, r, seg_mask, p, seed, stream_base, drow0, S.sr_a, slices_a, keep_bits, st)
-  switch (r <= 16 ? (r + 3) / 4 : 4 * lora_groups(r)) {
-    case 1: CLIPFS_DA_DX(1); break;
-    case 2: CLIPFS_DA_DX(2); break;
-    case 3: CLIPFS_DA_DX(3); break;
-    case 4: CLIPFS_DA_DX(4); break;
-    case 8: CLIPFS_DA_DX(8); break;
-    case 12: CLIPFS_DA_DX(12); break;
-    default: CLIPFS_DA_DX(16); break;
-  }
-#undef CLIPFS_DA_DX
-  CLIPFS_CHECK(launch_status());
-  // 3: both slice sums
-  if (grads) reduce2(part_b, dB, S.nb, slices_b, scale, part_a, dA, S.na, slices_a, 1.0f, st);
+  CLIPFS_REQUIRE(down, "lora_down: no matrix-core instance for %d rank groups", p.groups);
+  lora_launch(down, p.launch[0], c.st, c.x, c.A, c.t, c.rows, c.width, c.r, c.seg_mask, c.p, c.seed, c.stream_base, c.drow0,
+                     c.keep_bits);
   return launch_status();
 }
 
-int lora_bwd_mfma(const float* dy, const float* x, const float* t, const float* A, const float* B, float* dt, float* dA,
-                  float* dB, float* dx, int rows, int width, int segw, int r, int nseg, unsigned seg_mask, float scale,
-                  float p, uint64_t seed, uint32_t stream_base, uint32_t drow0, const uint16_t* keep_bits, float* work,
-                  hipStream_t st, lora_reduce2_fn reduce) {
-  if (nseg == 1)
-    return lora_bwd_mfma_n<1, float>(dy, x, t, A, B, dt, dA, dB, dx, rows, width, segw, r, seg_mask, scale, p, seed, stream_base, drow0,
-                                     keep_bits, work, st, reduce);
-  return lora_bwd_mfma_n<3, float>(dy, x, t, A, B, dt, dA, dB, dx, rows, width, segw, r, seg_mask, scale, p, seed, stream_base, drow0,
-                                   keep_bits, work, st, reduce);
+int lora_down_mfma(const LoraCall& c, const LoraPlan& p) {
+  return c.nseg == 1 ? lora_down_mfma_s<1>(c, p) : lora_down_mfma_s<3>(c, p);
 }
 
-int lora_bwd_mfma_xact(const float* dy, const float* x, const float* t, const float* A, const float* B, float* dt, float* dA,
-                       float* dB, float* dx, int rows, int width, int segw, int r, unsigned seg_mask, float scale, float p,
-                       uint64_t seed, uint32_t stream_base, uint32_t drow0, float* work, hipStream_t st, lora_reduce2_fn reduce) {
-  return lora_bwd_mfma_n<1, float, true>(dy, x, t, A, B, dt, dA, dB, dx, rows, width, segw, r, seg_mask, scale, p, seed,
-                                         stream_base, drow0, nullptr, work, st, reduce);
+template <int NSEG, typename TY, bool XACT = false>
+static int lora_bwd_mfma_s(const LoraCall& c, const LoraPlan& p) {
+  decltype(&lora_db_dt_mfma_kernel<NSEG, 1, TY>) db_dt = nullptr;
+  switch (p.groups) {
+    case 1: db_dt = lora_db_dt_mfma_kernel<NSEG, 1, TY>; break;
+    case 2: db_dt = lora_db_dt_mfma_kernel<NSEG, 2, TY>; break;
+    case 3: db_dt = lora_db_dt_mfma_kernel<NSEG, 3, TY>; break;
+    case 4: db_dt = lora_db_dt_mfma_kernel<NSEG, 4, TY>; break;
+  }
+  decltype(&lora_da_dx_mfma_kernel<NSEG, 1, XACT>) da_dx = nullptr;
+  switch (p.rq) {
+    case 1: da_dx = lora_da_dx_mfma_kernel<NSEG, 1, XACT>; break;
+    case 2: da_dx = lora_da_dx_mfma_kernel<NSEG, 2, XACT>; break;
+    case 3: da_dx = lora_da_dx_mfma_kernel<NSEG, 3, XACT>; break;
+    case 4: da_dx = lora_da_dx_mfma_kernel<NSEG, 4, XACT>; break;
+    case 8: da_dx = lora_da_dx_mfma_kernel<NSEG, 8, XACT>; break;
+    case 12: da_dx = lora_da_dx_mfma_kernel<NSEG, 12, XACT>; break;
+    case 16: da_dx = lora_da_dx_mfma_kernel<NSEG, 16, XACT>; break;
+  }
+  CLIPFS_REQUIRE(db_dt && da_dx, "lora_bwd: no matrix-core instance for %d rank groups, %d dA / dx K-steps", p.groups, p.rq);
+  const int gx_b = (NSEG * c.segw + 255) / 256, gx_a = (c.width + 255) / 256;  // blocks per slice of the partials
+  float* part_a = c.work + p.part_a_offset;
+  lora_launch(db_dt, p.launch[0], c.st, static_cast<const TY*>(c.dy), c.B, c.t, c.dt, c.work, c.rows, c.segw, c.r, c.seg_mask,
+                     c.scale, p.sr_b, gx_b, gx_b * p.slices_b);
+  CLIPFS_CHECK(launch_status());
+  if (p.launches > 1)
+    lora_launch(da_dx, p.launch[1], c.st, c.x, c.dt, c.A, part_a, c.dx, c.rows, c.width, c.r, c.seg_mask, c.p, c.seed,
+                       c.stream_base, c.drow0, p.sr_a, gx_a, gx_a * p.slices_a, c.keep_bits);
+  CLIPFS_CHECK(launch_status());
+  if (p.launches > 2)
+    launch_reduce_slices2(p.launch[2], c.work, c.dB, (size_t)NSEG * c.segw * c.r, p.slices_b, c.scale, part_a, c.dA,
+                          (size_t)NSEG * c.r * c.width, p.slices_a, 1.0f, c.st);
+  return launch_status();
 }
 
-// the same with dy given as its f16 image [rows, nseg * segw] (fp16 storage mode)
-int lora_bwd_mfma_f16dy(const void* dy16, const float* x, const float* t, const float* A, const float* B, float* dt, float* dA,
-                        float* dB, float* dx, int rows, int width, int segw, int r, int nseg, unsigned seg_mask, float scale,
-                        float p, uint64_t seed, uint32_t stream_base, uint32_t drow0, const uint16_t* keep_bits,
-                        float* work, hipStream_t st, lora_reduce2_fn reduce) {
-  const _Float16* dy = reinterpret_cast<const _Float16*>(dy16);
-  if (nseg == 1)
-    return lora_bwd_mfma_n<1, _Float16>(dy, x, t, A, B, dt, dA, dB, dx, rows, width, segw, r, seg_mask, scale, p, seed, stream_base,
-                                        drow0, keep_bits, work, st, reduce);
-  return lora_bwd_mfma_n<3, _Float16>(dy, x, t, A, B, dt, dA, dB, dx, rows, width, segw, r, seg_mask, scale, p, seed, stream_base,
-                                      drow0, keep_bits, work, st, reduce);
+int lora_bwd_mfma(const LoraCall& c, const LoraPlan& p) {
+  if (c.dy_f16) return c.nseg == 1 ? lora_bwd_mfma_s<1, _Float16>(c, p) : lora_bwd_mfma_s<3, _Float16>(c, p);
+  if (c.x_act) return lora_bwd_mfma_s<1, float, true>(c, p);  // (nseg 1: the plan refuses x_act otherwise)
+  return c.nseg == 1 ? lora_bwd_mfma_s<1, float>(c, p) : lora_bwd_mfma_s<3, float>(c, p);
 }
 
 }  // namespace clipfs

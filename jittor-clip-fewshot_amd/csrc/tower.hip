@@ -174,8 +174,9 @@ static int check_tower(const clipfs_tower* t, int batch) {
                  "tower: width %d must be heads %d * 64", t->width, t->heads);
   CLIPFS_REQUIRE(t->lora_r >= 0 && t->lora_r <= 64, "tower: lora rank %d unsupported (0..64) at width %d", t->lora_r,
                  t->width);
-  // ranks above 16 run on the matrix-core adapter kernels only (lora_mfma.hip), which need the width in 128-column steps
-  CLIPFS_REQUIRE(t->lora_r <= 16 || t->width % 128 == 0,
+  // ranks above 16: the adapter kernels' plan says whether a family takes them at this width
+  struct clipfs_lora_plan lp;
+  CLIPFS_REQUIRE(t->lora_r <= 16 || clipfs_lora_plan(CLIPFS_LORA_OP_BWD, 1, t->width, t->width, t->lora_r, 3, 0, &lp) == CLIPFS_OK,
                  "tower: lora rank %d at width %d unsupported (ranks above 16 need a width that is a multiple of 128)",
                  t->lora_r, t->width);
   CLIPFS_REQUIRE(t->grad_lo >= 0 && t->grad_lo < t->layers, "tower: grad_lo %d outside [0, layers %d)", t->grad_lo,
