@@ -125,6 +125,11 @@ int clipfs_convert_f16(const float* src, void* dst, size_t n, void* stream);
 int clipfs_gemm_splits(int M, int N, int K);
 /* rows of the block tile (64 or 32) the exact fp32 kernels use for an [M,N] output: host-only query, no launch */
 int clipfs_gemm_tile_rows(int M, int N);
+/* Dense unsplit fp32 products of 4096 rows or more (K % 32 == 0) for which clipfs_gemm_tile_rows answers 32 may deal
+ * rows [0, clipfs_gemm_mixed_rows64) as 64-row tiles -- whole rounds of the resident workgroup slots -- and only the rows
+ * behind them as 32-row tiles, in one launch; 0 = one height, that of clipfs_gemm_tile_rows.  It changes no result bit: an
+ * element's k order does not depend on the tile that holds it.  Host-only query, no launch. */
+int clipfs_gemm_mixed_rows64(int M, int N, int K);
 /* The f16 x f16 kernel (args->A_f16 set) is nine kernels and a row split: whole rounds of 256 x 256 tiles over the CUs on
  * a ping-pong or phased kernel, the leftover rows on 4-wave kernels, on the internal side stream when `side` is set.
  * clipfs_gemm_f16_plan writes the launches clipfs_gemm_nt would make for `args` on a device of `cus` compute units

@@ -128,6 +128,7 @@ SIGNATURES = {
     "clipfs_convert_f16": (_i, [_p, _p, _sz, _p]),
     "clipfs_gemm_splits": (_i, [_i, _i, _i]),
     "clipfs_gemm_tile_rows": (_i, [_i, _i]),
+    "clipfs_gemm_mixed_rows64": (_i, [_i, _i, _i]),
     "clipfs_gemm_f16_plan": (_i, [C.POINTER(GemmArgs), _i, C.POINTER(F16Plan)]),
     "clipfs_gemm_workspace_floats": (_sz, [_i, _i, _i]),
     "clipfs_gemm_counter_ints": (_sz, [_i, _i, _i]),

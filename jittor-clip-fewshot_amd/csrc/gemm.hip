@@ -73,8 +73,11 @@ __device__ __forceinline__ void glds16(const float* gsrc, float* lds_wave_base) 
 // AMODE 0: dense A, K % 32 == 0 (the hot configuration: the K loop is pointer bumps + 16-byte loads only)
 // AMODE 1: patch im2col with patch == 32 (one K-step == one (channel, ky) image row segment)
 // AMODE 2: generic (dense with a K tail, or any patch size): per-element address arithmetic
+//
+// gemm_nt_tile is one workgroup's whole job: the BM x BN tile at (m0, n0), K slice `split` of tile number `tile` (both
+// only matter when p.splits > 1).  The kernels below differ in how a workgroup finds its tile.
 template <int BM, int BN, int AMODE>
-__global__ __launch_bounds__(256) void gemm_nt_kernel(const GemmParams p) {
+__device__ __forceinline__ void gemm_nt_tile(const GemmParams& p, const int tile, const int split, const int m0, const int n0) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   constexpr int WM = BM >= 64 ? 2 : 1;   // wave grid WM x WN (4 waves); BM = 32 puts the 4 waves side by side
   constexpr int WN = 4 / WM;
@@ -90,27 +93,6 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel(const GemmParams p) {
   const int lane = tid & 63;
   const int wave = tid >> 6;
   const int wm = wave / WN, wn = wave % WN;
-  // Tile order.  Workgroups are dealt round-robin over the 8 XCDs (blockIdx % 8 labels the XCD, speed only),
-  // each XCD has a private 4 MB L2: give every XCD a CONTIGUOUS run of the tile list, and order the list in
-  // super-tiles of GM m-blocks x all n-blocks (m fastest) so the ~96 tiles an XCD runs at once share
-  // 8 A panels and 12 B panels instead of ~40 + 18 (FETCH_SIZE: DESIGN.md section 8; GM = 8 fetches 10-25 % less than
-  // 16 on four of the five path shapes, 4 and 32 more; the time does not move: the kernel is MFMA-bound).
-  int tile;
-  {
-    const int nwg = gridDim.x, bid = blockIdx.x;
-    const int xcd = bid & 7, li = bid >> 3, q = nwg >> 3, r = nwg & 7;
-    tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + li;
-  }
-  const int split = tile % p.splits;  // consecutive units = the K slices of one tile (same XCD: shared panels)
-  tile /= p.splits;
-  const int GM = p.gm;
-  const int nbn = p.n_blocks_n;
-  const int grp = tile / (GM * nbn);
-  const int rem = tile - grp * (GM * nbn);
-  const int mb_total = (g.M + BM - 1) / BM;
-  const int gm = min(GM, mb_total - grp * GM);  // the last group may be shorter
-  const int m0 = (grp * GM + rem % gm) * BM;
-  const int n0 = (rem / gm) * BN;
   const int M = g.M, N = g.N, K = g.K;
 
   // ---- staging addresses -------------------------------------------------------------------
@@ -356,6 +338,51 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel(const GemmParams p) {
   }
   finish_tiles<TM, TN>(g, p.patches, acc, m0 + wm * (BM / WM), n0 + wn * (BN / WN), m0 + BM <= M && n0 + BN <= N, lane);
   CLIPFS_STAMP(3);
+}
+
+// Tile order.  Workgroups are dealt round-robin over the 8 XCDs (blockIdx % 8 labels the XCD, speed only),
+// each XCD has a private 4 MB L2: give every XCD a CONTIGUOUS run of the tile list (unit `bid` of `nwg`), and order
+// the list in super-tiles of GM m-blocks x all n-blocks (m fastest) so the ~96 tiles an XCD runs at once share
+// 8 A panels and 12 B panels instead of ~40 + 18 (FETCH_SIZE: DESIGN.md section 8; GM = 8 fetches 10-25 % less than
+// 16 on four of the five path shapes, 4 and 32 more; the time does not move: the kernel is MFMA-bound).
+__device__ __forceinline__ int xcd_contiguous(int bid, int nwg) {
+  const int xcd = bid & 7, li = bid >> 3, q = nwg >> 3, r = nwg & 7;
+  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + li;
+}
+
+// block coordinates of tile number `tile` among mb_total x nbn blocks
+__device__ __forceinline__ void tile_blocks(int tile, int GM, int nbn, int mb_total, int& mb, int& nb) {
+  const int grp = tile / (GM * nbn);
+  const int rem = tile - grp * (GM * nbn);
+  const int gm = min(GM, mb_total - grp * GM);  // the last group may be shorter
+  mb = grp * GM + rem % gm;
+  nb = rem / gm;
+}
+
+template <int BM, int BN, int AMODE>
+__global__ __launch_bounds__(256) void gemm_nt_kernel(const GemmParams p) {
+  int tile = xcd_contiguous(blockIdx.x, gridDim.x);
+  const int split = tile % p.splits;  // consecutive units = the K slices of one tile (same XCD: shared panels)
+  tile /= p.splits;
+  int mb, nb;
+  tile_blocks(tile, p.gm, p.n_blocks_n, (p.a.M + BM - 1) / BM, mb, nb);
+  gemm_nt_tile<BM, BN, AMODE>(p, tile, split, mb * BM, nb * BN);
+}
+
+// Two tile heights in one launch (dense operands, unsplit): rows [0, mix_rows64) as mix_tiles64 tiles of 64 x 128 --
+// whole rounds of the resident workgroup slots, dispatched first -- and the rows behind them as 32 x 128 tiles that
+// fill the last round.  The branch is per workgroup; an element's k order does not depend on the tile that holds it,
+// so the result is bitwise that of either uniform tiling.
+__global__ __launch_bounds__(256) void gemm_nt_mixed_kernel(const GemmParams p) {
+  const int bid = blockIdx.x, t64 = p.mix_tiles64;
+  int mb, nb;
+  if (bid < t64) {
+    tile_blocks(xcd_contiguous(bid, t64), p.gm, p.n_blocks_n, p.mix_rows64 / 64, mb, nb);
+    gemm_nt_tile<64, 128, 3>(p, 0, 0, mb * 64, nb * 128);
+  } else {
+    tile_blocks(xcd_contiguous(bid - t64, gridDim.x - t64), p.gm, p.n_blocks_n, (p.a.M - p.mix_rows64 + 31) / 32, mb, nb);
+    gemm_nt_tile<32, 128, 3>(p, 0, 0, p.mix_rows64 + mb * 32, nb * 128);
+  }
 }
 
 // ---- stream-K ------------------------------------------------------------------------------------------------
@@ -690,22 +717,36 @@ static thread_local double g_last_bytes = 0.0;
 static thread_local bool g_timing = false;
 static thread_local std::vector<TimedLaunch>* g_timed = nullptr;
 
-template <int BM, int BN, int AMODE>
-static int launch(const GemmParams& p, hipStream_t stream) {
-  const int mb = (p.a.M + BM - 1) / BM;
-  // 8 KiB more than the two stages need: two workgroups per CU instead of three.  The K loop is as fast with two
-  // (the MFMA pipe is the shared resource either way) and the third of the CU left free lets the other tower's
-  // LayerNorm / attention / LoRA kernels run beside the GEMM: +1.3 % on the step, +3.4 % on the 8-GPU per-rank step.
+// Dynamic LDS of a workgroup with BM + BN staged rows.  8 KiB more than the two stages need: two workgroups per CU
+// instead of three.  The K loop is as fast with two (the MFMA pipe is the shared resource either way) and the third of
+// the CU left free lets the other tower's LayerNorm / attention / LoRA kernels run beside the GEMM: +1.3 % on the step,
+// +3.4 % on the 8-GPU per-rank step.
+static size_t gemm_lds_bytes(int BM, int BN) {
   static const int lds_pad = getenv("CLIPFS_GEMM_LDS_PAD") ? atoi(getenv("CLIPFS_GEMM_LDS_PAD")) : 8;  // KiB
-  const size_t lds = 2 * (size_t)(BM + BN) * BK * sizeof(float) + (size_t)lds_pad * 1024 + 64;  // + the split-K flag word
-  static bool attr_set = false;
+  return 2 * (size_t)(BM + BN) * BK * sizeof(float) + (size_t)lds_pad * 1024 + 64;  // + the split-K flag word
+}
+
+template <typename Kernel>
+static int launch_kernel(Kernel kernel, bool& attr_set, unsigned grid, size_t lds, const GemmParams& p, hipStream_t stream) {
   if (!attr_set && lds > 48 * 1024) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_nt_kernel<BM, BN, AMODE>),
-                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     attr_set = true;
   }
-  hipLaunchKernelGGL((gemm_nt_kernel<BM, BN, AMODE>), dim3(mb * p.n_blocks_n * p.splits), dim3(256), lds, stream, p);
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), lds, stream, p);
   return launch_status();
+}
+
+template <int BM, int BN, int AMODE>
+static int launch(const GemmParams& p, hipStream_t stream) {
+  static bool attr_set = false;
+  const int mb = (p.a.M + BM - 1) / BM;
+  return launch_kernel(&gemm_nt_kernel<BM, BN, AMODE>, attr_set, (unsigned)(mb * p.n_blocks_n * p.splits), gemm_lds_bytes(BM, BN), p, stream);
+}
+
+static int launch_mixed(const GemmParams& p, hipStream_t stream) {
+  static bool attr_set = false;
+  const int mb32 = (p.a.M - p.mix_rows64 + 31) / 32;
+  return launch_kernel(&gemm_nt_mixed_kernel, attr_set, (unsigned)(p.mix_tiles64 + mb32 * p.n_blocks_n), gemm_lds_bytes(64, 128), p, stream);
 }
 
 static int cu_count() {
@@ -810,9 +851,11 @@ using namespace clipfs;
 
 // Tile height: 64 x 128, or 32 x 128 when that balances the 256 CUs better.  All tiles of a launch that fits the
 // resident slots start together and share their CU's MFMA pipe, so a launch lasts ceil(tiles / 256) tile-times of
-// the busiest CU: cost = ceil(tiles / 256) * rows-per-tile, with 8 % on top for the 32-row tile (it re-reads B
-// twice as often).  Measured on the per-rank shapes of the strong-scaling run (scripts/bench_small_m.py): e.g. 600
-// tiles of 64 rows (3 vs 2.34 per CU) lose 7-9 % against 1200 tiles of 32 rows, 450 tiles of 64 rows win by 9 %.
+// the busiest CU: cost = ceil(tiles / 256) * rows-per-tile, with 8 % on top for the 32-row tile (one LDS read per 2
+// MFMAs instead of 3 per 8, 1.67 x the LDS-DMA bytes per FLOP).  The 8 % was measured on the per-rank shapes of the
+// strong-scaling run (scripts/bench_small_m.py): e.g. 600 tiles of 64 rows (3 vs 2.34 per CU) lose 7-9 % against 1200
+// tiles of 32 rows, 450 tiles of 64 rows win by 9 %.  It was not re-measured at ~10 k rows (several rounds per launch);
+// there a launch that mixes the two heights beats the 32-row tiling this model picks for N = 512: gemm_mixed_rows64.
 static inline int gemm_bm(int M, int N) {
   static const int force = getenv("CLIPFS_GEMM_BM") ? atoi(getenv("CLIPFS_GEMM_BM")) : 0;  // tuning aid: 32 / 64
   if (force == 32 || force == 64) return force;
@@ -823,6 +866,31 @@ static inline int gemm_bm(int M, int N) {
 }
 
 extern "C" int clipfs_gemm_tile_rows(int M, int N) { return gemm_bm(M, N); }
+
+// ---- the large-M band: two tile heights in one launch ---------------------------------------------------------------
+// Where gemm_bm picks 32 rows for a dense unsplit product of BAND_MIN_M rows or more (the packed text tower's N = 512
+// products on ~10 k live rows: 4.8 32-row tiles per slot), most of the launch is whole rounds of tiles and only the
+// last round needs the finer balance.  The rows of the whole rounds of the 512 workgroup slots are dealt as 64 x 128
+// tiles (3 LDS reads per 8 MFMAs against 4, and 0.6 x the LDS-DMA bytes per FLOP of the 32-row tile) and only the
+// rows behind them as 32 x 128 tiles, in one launch (gemm_nt_mixed_kernel).  [9748, 512]: 512 + 196 workgroups; the
+// busiest CU does 2 x 64 + 1.08 x 32 = 163 row-units against 173 (all 32-row) and 192 (all 64-row).  Measured on
+// MI355X (profiles/text_band): 3-7 % on each N = 512 product alone, 0.5 ms of the 52.6 ms step.  The per-rank shapes,
+// every split product and every shape of the schedule table (tests/gemm_matrix_cases.py) lie below the band.
+constexpr int BAND_MIN_M = 4096;
+
+// rows [0, result) go in 64-row tiles, the rest in 32-row tiles; 0: one height (gemm_bm)
+static inline int gemm_mixed_rows64(int M, int N, int K) {
+  if (M < BAND_MIN_M || N <= 0 || K <= 0 || (K % BK) != 0 || gemm_bm(M, N) != 32 || clipfs_gemm_splits(M, N, K) > 1) return 0;
+  const long nbn = (N + 127) / 128;
+  const long rounds = (long)(M / 64) * nbn / 512;
+  const long mb64 = rounds * 512 / nbn;  // whole m-blocks inside the whole rounds
+  const long t32 = ((M - mb64 * 64 + 31) / 32) * nbn;
+  const double cost_mix = (double)((mb64 * nbn + 255) / 256) * 64.0 + (double)((t32 + 255) / 256) * 32.0 * 1.08;
+  const double cost32 = (double)(((long)((M + 31) / 32) * nbn + 255) / 256) * 32.0 * 1.08;  // as in gemm_bm
+  return mb64 > 0 && cost_mix < cost32 ? (int)(mb64 * 64) : 0;
+}
+
+extern "C" int clipfs_gemm_mixed_rows64(int M, int N, int K) { return gemm_mixed_rows64(M, N, K); }
 
 // Split-K factor for a [M,N,K] product: only when even the 32 x 128 tiling leaves the 512 resident workgroup slots
 // short of work (strong-scaling per-rank batches, the one-row-per-sequence products of the last block) and K is long
@@ -1029,6 +1097,7 @@ static int gemm_nt_impl(const clipfs_gemm_args* args, void* stream) {
   p.splits = 1;
   p.part = nullptr;
   p.n_blocks_n = 0;
+  p.mix_rows64 = p.mix_tiles64 = 0;
   if (a.B_planes && (a.b_format == 1 || a.b_format == 2) && a.a_mode == 0 && (a.K % BK) == 0 && a.ldb == a.K)
     return gemm_bf16x3_dispatch(p, s);
   p.sk_cnt = nullptr;
@@ -1067,8 +1136,13 @@ static int gemm_nt_impl(const clipfs_gemm_args* args, void* stream) {
     return launch_sk<64, 128, 2>(p, sk_config(a.M, a.N, a.K).per_cu, s);
   }
   p.n_blocks_n = (a.N + 127) / 128;
-  if (gemm_bm(a.M, a.N) == 32 && a.a_mode == 0 && (a.K % BK) == 0) return launch<32, 128, 3>(p, s);
   static const int glds_cfg = getenv("CLIPFS_GEMM_GLDS") ? atoi(getenv("CLIPFS_GEMM_GLDS")) : 1;  // 0: register staging (A/B aid)
+  if (a.a_mode == 0 && p.splits == 1 && glds_cfg) {  // the large-M band: 64-row tiles first, 32-row tiles behind them
+    p.mix_rows64 = gemm_mixed_rows64(a.M, a.N, a.K);
+    p.mix_tiles64 = p.mix_rows64 / 64 * p.n_blocks_n;
+    if (p.mix_rows64 > 0) return launch_mixed(p, s);
+  }
+  if (gemm_bm(a.M, a.N) == 32 && a.a_mode == 0 && (a.K % BK) == 0) return launch<32, 128, 3>(p, s);
   if (a.a_mode == 0 && (a.K % BK) == 0) return glds_cfg ? launch<64, 128, 3>(p, s) : launch<64, 128, 0>(p, s);
   if (a.a_mode == 1 && a.patch == 32 && (a.img_res & 3) == 0) return launch<64, 128, 1>(p, s);
   return launch<64, 128, 2>(p, s);

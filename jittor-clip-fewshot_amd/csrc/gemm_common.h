@@ -23,6 +23,8 @@ struct GemmParams {
   float* sk_part;  // partial-tile slabs: slot (2 w + kind) of BM*BN floats, w = run index, kind 0 = the run's first
                    // (head) tile, 1 = its last (tail) tile
   int* sk_cnt;     // arrival counter per tile (zero on entry, zero again on exit)
+  // mixed-height launch (gemm_nt_mixed_kernel): rows [0, mix_rows64) as mix_tiles64 tiles of 64 rows, the rest in 32-row tiles
+  int mix_rows64, mix_tiles64;
 };
 
 constexpr int BK = 32;
