@@ -617,6 +617,54 @@ int clipfs_scaler_decide(float* scaler_state, float lr, float beta1, float beta2
 int clipfs_adamw_scaled(float* p, const float* g, float* m, float* v, size_t n, float lr, float beta1, float beta2,
                         float eps, float weight_decay, const float* scaler_state, void* stream);
 
+/* ------------------------------------------------- optimiser step options --
+ * Gradient clipping by global 2-norm and an exponential moving average of the parameters, in the optimiser step.
+ * Clipping is driven by a device-resident CLIP RECORD owned by the caller: CLIPFS_CLIP_WORDS fp32 words (32 bytes,
+ * 16-byte aligned), zeroed by the caller, which no entry point reads back to the host.  It is separate from the scaler
+ * record, whose reserved words stay zero.
+ *
+ * With clipping one optimiser step is, on the caller's stream and after any gradient all-reduce (every data-parallel
+ * rank then forms the same norm from the same bytes in the same order):
+ *   [clipfs_grads_nonfinite, clipfs_scaler_decide]   with loss scaling only
+ *   clipfs_grad_sumsq    pass 1 of the sum of squares of the flat gradient buffer [n] (any 4-byte aligned base: 16-byte
+ *                        loads between the first and the last 16-byte boundary of each workgroup's run, scalar loads
+ *                        for the up to 3 floats on either side).  Squares and sums are double: exact squares, and a
+ *                        scaled gradient of 1e19 does not overflow.  Fixed-order reduction through LDS, no float
+ *                        atomics; one double per workgroup goes to work [clipfs_grad_sumsq_work_doubles(n)] (8-byte
+ *                        aligned).  Grid and runs depend on n alone (and the order inside a run on the base's offset
+ *                        from a 16-byte boundary): the same buffer gives the same bits on every call.
+ *   clipfs_clip_decide   one workgroup adds the partials of the same n in index order and writes the record:
+ *                        NORM = sqrt(sum) * INV_SCALE of scaler_state (after clipfs_scaler_decide that is the scale
+ *                        these gradients carry), or sqrt(sum) when it is NULL; COEF = min(1, max_norm / (NORM + 1e-6)),
+ *                        the rule of torch.nn.utils.clip_grad_norm_; MULT = INV_SCALE * COEF (fp32 product), or COEF.
+ *                        A NaN or infinite NORM gives COEF = 0 (torch with error_if_nonfinite=False: the non-finite
+ *                        entries themselves still poison the update -- loss scaling is what skips such a step; with
+ *                        its SKIP set the record still gets NORM and MULT is never used).
+ *   clipfs_adamw_ext     clipfs_adamw's arithmetic on p, g, m, v [n] with three optional pointers:
+ *                        scaler_state  the bias corrections, the skip decision and grad_scale = INV_SCALE come from the
+ *                                      record, as in clipfs_adamw_scaled (step is then ignored);
+ *                        clip_state    grad_scale = MULT of the record (it already carries INV_SCALE);
+ *                        ema_shadow    [n]: shadow = fmaf(ema_decay, shadow, (1 - ema_decay) * p_new) from the parameter
+ *                                      just computed, 1 - ema_decay formed once in fp32 (lora_train_vlp.py:887).
+ *                        With SKIP set it writes nothing: p, m, v and the shadow stay bitwise untouched.  All three
+ *                        NULL is bitwise clipfs_adamw (step, grad_scale as given); scaler_state alone is bitwise
+ *                        clipfs_adamw_scaled.
+ * clipfs_grad_sumsq_work_doubles is host-only, monotone in n and 0 for n = 0.  The other three are CLIPFS_EINVAL
+ * (nothing launched) for a NULL or misaligned record or buffer (an optional one: misaligned), n = 0, a max_norm that
+ * is not positive and finite, an ema_decay outside (0, 1) or a shadow that aliases p, m or v (shadow given), and
+ * step < 1 without a scaler record. */
+#define CLIPFS_CLIP_NORM 0  /* fp32: the unscaled total 2-norm of the gradients last decided */
+#define CLIPFS_CLIP_COEF 1  /* fp32: min(1, max_norm / (NORM + 1e-6)); 0 for a non-finite NORM */
+#define CLIPFS_CLIP_MULT 2  /* fp32: the gradient multiplier clipfs_adamw_ext applies */
+#define CLIPFS_CLIP_WORDS 8 /* words 3 .. 7 are reserved (zero) */
+size_t clipfs_grad_sumsq_work_doubles(size_t n);
+int clipfs_grad_sumsq(const float* g, size_t n, double* work, void* stream);
+int clipfs_clip_decide(const double* work, size_t n, float max_norm, const float* scaler_state, float* clip_state,
+                       void* stream);
+int clipfs_adamw_ext(float* p, const float* g, float* m, float* v, size_t n, int step, float lr, float beta1, float beta2,
+                     float eps, float weight_decay, float grad_scale, const float* scaler_state, const float* clip_state,
+                     float* ema_shadow, float ema_decay, void* stream);
+
 /* -------------------------------------------------------------------- MTA --
  * solve_mta (lora_train_vlp.py:742-811; slow_pace.py:1363-1433), one workgroup per image.
  * feats [n_img, V, d] unit rows (row 0 = centre view), text [C, d] (unit rows; the reference

@@ -193,6 +193,10 @@ SIGNATURES = {
     "clipfs_grads_nonfinite": (_i, [_p, _sz, _p, _p]),
     "clipfs_scaler_decide": (_i, [_p, _f, _f, _f, _f, _f, _i, _p]),
     "clipfs_adamw_scaled": (_i, [_p, _p, _p, _p, _sz, _f, _f, _f, _f, _f, _p, _p]),
+    "clipfs_grad_sumsq_work_doubles": (_sz, [_sz]),
+    "clipfs_grad_sumsq": (_i, [_p, _sz, _p, _p]),
+    "clipfs_clip_decide": (_i, [_p, _sz, _f, _p, _p, _p]),
+    "clipfs_adamw_ext": (_i, [_p, _p, _p, _p, _sz, _i, _f, _f, _f, _f, _f, _f, _p, _p, _p, _f, _p]),
     "clipfs_mta_work_floats": (_sz, [_i, _i, _i, _i]),
     "clipfs_mta": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _p]),
     "clipfs_tta_views": (_i, [_p, _i, _i, _p, _i, _i, _p, _p, _p, _p]),
@@ -236,6 +240,8 @@ SIGNATURES = {
 # word indices of the loss-scaling record (CLIPFS_SCALER_* of include/clipfs.h)
 SCALER_SCALE, SCALER_INV_SCALE, SCALER_FOUND, SCALER_TRACKER, SCALER_STEP, SCALER_SKIPPED = 0, 1, 2, 3, 4, 5
 SCALER_INV_SQRT_BC2, SCALER_STEP_SIZE, SCALER_SKIP, SCALER_WORDS = 6, 7, 8, 16
+# word indices of the clip record (CLIPFS_CLIP_* of include/clipfs.h)
+CLIP_NORM, CLIP_COEF, CLIP_MULT, CLIP_WORDS = 0, 1, 2, 8
 
 
 def new_gemm_args() -> GemmArgs:

@@ -537,6 +537,59 @@ def adamw_scaled(p, g, m, v, scale_state, lr=2e-4, betas=(0.9, 0.999), eps=1e-8,
                                           weight_decay, _p(_scaler(scale_state)), _stream()), "adamw_scaled")
 
 
+def new_clip_state(device) -> torch.Tensor:
+    """A zeroed clip record (include/clipfs.h, CLIPFS_CLIP_*): fp32 [8] on ``device``."""
+    return torch.zeros(_lib.CLIP_WORDS, dtype=torch.float32, device=device)
+
+
+def _clip(state: torch.Tensor) -> torch.Tensor:
+    assert state.is_cuda and state.dtype == torch.float32 and state.is_contiguous() and state.numel() >= _lib.CLIP_WORDS
+    return state
+
+
+def grad_sumsq_work(n: int, device) -> torch.Tensor:
+    """The float64 work buffer ``grad_sumsq`` / ``clip_decide`` need for a flat buffer of ``n`` floats."""
+    return torch.empty(_lib.load().clipfs_grad_sumsq_work_doubles(n), dtype=torch.float64, device=device)
+
+
+def grad_sumsq(g: torch.Tensor, work: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Pass 1 of the sum of squares of the flat fp32 buffer ``g`` (any 4-byte aligned slice): one float64 partial per
+    workgroup into ``work`` (``grad_sumsq_work``), which is returned.  Bitwise deterministic."""
+    assert g.dim() == 1
+    need = _lib.load().clipfs_grad_sumsq_work_doubles(g.numel())
+    if work is None:
+        work = grad_sumsq_work(g.numel(), g.device)
+    assert work.is_cuda and work.dtype == torch.float64 and work.is_contiguous() and work.numel() >= need
+    check(_lib.load().clipfs_grad_sumsq(_p(_f32(g)), g.numel(), _p(work), _stream()), "grad_sumsq")
+    return work
+
+
+def clip_decide(work: torch.Tensor, n: int, max_norm: float, clip_state: torch.Tensor,
+                scale_state: Optional[torch.Tensor] = None) -> None:
+    """Add the partials ``grad_sumsq`` left for a buffer of ``n`` floats and write the clip record: NORM (divided by
+    the scale of ``scale_state``, after ``scaler_decide``), COEF = min(1, max_norm / (NORM + 1e-6)) and MULT.  A NaN or
+    infinite norm gives COEF = 0, as ``torch.nn.utils.clip_grad_norm_(error_if_nonfinite=False)`` does for an infinite
+    one; the update is then poisoned by the non-finite entries themselves: ``loss_scale`` is what skips such a step."""
+    assert work.is_cuda and work.dtype == torch.float64 and work.is_contiguous()
+    assert work.numel() >= _lib.load().clipfs_grad_sumsq_work_doubles(n)
+    check(_lib.load().clipfs_clip_decide(_p(work), n, max_norm, None if scale_state is None else _p(_scaler(scale_state)),
+                                         _p(_clip(clip_state)), _stream()), "clip_decide")
+
+
+def adamw_ext(p, g, m, v, step, lr=2e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, grad_scale=1.0,
+              scale_state=None, clip_state=None, ema_shadow=None, ema_decay=0.999):
+    """``adamw`` with three optional device inputs: the loss-scaling record (bias corrections, skip decision and
+    1 / scale, as ``adamw_scaled``; ``step`` is then unused), the clip record (its MULT is the gradient multiplier) and
+    an EMA shadow [n] updated as ``decay * shadow + (1 - decay) * p_new``.  A skipped step writes nothing at all."""
+    if ema_shadow is not None:
+        assert ema_shadow.shape == p.shape and ema_shadow.device == p.device
+        _f32(ema_shadow)
+    check(_lib.load().clipfs_adamw_ext(_p(p), _p(g), _p(m), _p(v), p.numel(), step, lr, betas[0], betas[1], eps,
+                                       weight_decay, grad_scale, None if scale_state is None else _p(_scaler(scale_state)),
+                                       None if clip_state is None else _p(_clip(clip_state)), _p(ema_shadow), ema_decay,
+                                       _stream()), "adamw_ext")
+
+
 def mta(feats, text, want_mode=True, want_logits=True):
     """feats [n_img, V, d] unit rows, text [C, d] unit rows -> (mode [n_img,d], logits [n_img,C])"""
     n_img, V, d = feats.shape

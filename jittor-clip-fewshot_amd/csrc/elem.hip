@@ -619,6 +619,109 @@ __global__ __launch_bounds__(256) void adamw_scaled_kernel(float* __restrict__ p
                 sf[CLIPFS_SCALER_INV_SCALE]);
 }
 
+// ---- gradient clipping by global norm + EMA shadow (clipfs.h: "optimiser step options") ----
+// Sum of squares of the flat gradient, two launches, no float atomics.  The buffer is cut into `chunks` runs of `cpe`
+// elements (both functions of n alone, cpe a multiple of 4); workgroup b owns elements [b * cpe, min(n, (b + 1) * cpe)).
+// Every run starts at the same offset from a 16-byte boundary as the buffer does, so each workgroup reads its up to 3
+// floats before the first boundary and up to 3 after the last whole float4 one by one and everything between with
+// 16-byte loads; nothing outside [0, n) is touched.  The square of an fp32 value is exact in double and so is its
+// range: 1e19^2 * n stays far below DBL_MAX.
+constexpr size_t kSumsqMinChunk = 4096;  // elements per workgroup at least: 256 threads x 4 float4
+constexpr size_t kSumsqMaxChunks = 512;  // partials the decision's single lane adds
+
+static inline size_t sumsq_chunks(size_t n) {
+  if (n == 0) return 0;
+  const size_t c = (n + kSumsqMinChunk - 1) / kSumsqMinChunk;
+  return c < kSumsqMaxChunks ? c : kSumsqMaxChunks;
+}
+static inline size_t sumsq_chunk_elems(size_t n) {  // multiple of 4, >= kSumsqMinChunk for n > 0
+  const size_t chunks = sumsq_chunks(n);
+  const size_t cpe = chunks == kSumsqMaxChunks ? (n + chunks - 1) / chunks : kSumsqMinChunk;
+  return (cpe + 3) & ~(size_t)3;
+}
+
+__global__ __launch_bounds__(256) void grad_sumsq_kernel(const float* __restrict__ g, size_t n, size_t cpe,
+                                                         unsigned head_of_base, double* __restrict__ work) {
+  const size_t e0 = (size_t)blockIdx.x * cpe;
+  if (e0 >= n) {  // uniform over the workgroup; sumsq_chunk_elems leaves no run empty, but the partial stays defined
+    if (threadIdx.x == 0) work[blockIdx.x] = 0.0;
+    return;
+  }
+  const size_t len = (n - e0 < cpe) ? n - e0 : cpe;
+  const unsigned head = head_of_base < len ? head_of_base : (unsigned)len;
+  const size_t nvec = (len - head) >> 2;
+  const unsigned tail = (unsigned)((len - head) & 3);
+  const float* gb = g + e0;
+  const float4* gv = reinterpret_cast<const float4*>(gb + head);
+  double acc = 0.0;
+  for (size_t i = threadIdx.x; i < nvec; i += 256) {
+    const float4 w = gv[i];
+    acc += (double)w.x * (double)w.x;
+    acc += (double)w.y * (double)w.y;
+    acc += (double)w.z * (double)w.z;
+    acc += (double)w.w * (double)w.w;
+  }
+  if (threadIdx.x < head + tail) {
+    const size_t i = threadIdx.x < head ? (size_t)threadIdx.x : (size_t)head + 4 * nvec + (threadIdx.x - head);
+    const double x = (double)gb[i];
+    acc += x * x;
+  }
+  __shared__ double red[256];
+  red[threadIdx.x] = acc;
+  __syncthreads();
+#pragma unroll
+  for (int s = 128; s > 0; s >>= 1) {  // fixed tree: thread t adds slot t + s
+    if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) work[blockIdx.x] = red[0];
+}
+
+// One workgroup: the partials go through LDS, lane 0 adds them in index order and writes the clip record with
+// ordinary vector stores.  sf = the loss-scaling record (after scaler_decide: INV_SCALE is the scale these gradients
+// carry) or NULL.
+__global__ __launch_bounds__(256) void clip_decide_kernel(const double* __restrict__ work, int chunks, float max_norm,
+                                                          const float* __restrict__ sf, float* __restrict__ cs) {
+  __shared__ double part[kSumsqMaxChunks];
+  for (int k = threadIdx.x; k < chunks; k += 256) part[k] = work[k];
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  double total = 0.0;
+  for (int k = 0; k < chunks; ++k) total += part[k];
+  const float inv_scale = sf ? sf[CLIPFS_SCALER_INV_SCALE] : 1.f;
+  const float norm = (float)(sqrt(total) * (double)inv_scale);
+  float coef = 0.f;  // a NaN or infinite norm
+  if (norm <= 3.402823466e38f) {
+    const double c = (double)max_norm / ((double)norm + 1e-6);
+    coef = c < 1.0 ? (float)c : 1.f;
+  }
+  cs[CLIPFS_CLIP_NORM] = norm;
+  cs[CLIPFS_CLIP_COEF] = coef;
+  cs[CLIPFS_CLIP_MULT] = inv_scale * coef;
+}
+
+// adamw_kernel / adamw_scaled_kernel with the optional records: bias corrections and the skip decision from the
+// loss-scaling record when there is one, the gradient multiplier from the clip record when there is one, and the EMA
+// shadow updated from the parameter just computed.
+__global__ __launch_bounds__(256) void adamw_ext_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                        float* __restrict__ m, float* __restrict__ v, size_t n, float lr,
+                                                        float b1, float b2, float eps, float wd, float inv_sqrt_bc2,
+                                                        float step_size, float grad_scale,
+                                                        const float* __restrict__ sf, const float* __restrict__ cs,
+                                                        float* __restrict__ shadow, float decay, float one_minus_decay) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  if (sf) {
+    if (reinterpret_cast<const int32_t*>(sf)[CLIPFS_SCALER_SKIP] != 0) return;
+    inv_sqrt_bc2 = sf[CLIPFS_SCALER_INV_SQRT_BC2];
+    step_size = sf[CLIPFS_SCALER_STEP_SIZE];
+    grad_scale = sf[CLIPFS_SCALER_INV_SCALE];
+  }
+  if (cs) grad_scale = cs[CLIPFS_CLIP_MULT];
+  adamw_element(p, g, m, v, i, lr, b1, b2, eps, wd, inv_sqrt_bc2, step_size, grad_scale);
+  if (shadow) shadow[i] = fmaf(decay, shadow[i], one_minus_decay * p[i]);
+}
+
 // C[m,n] = alpha * sum_k A[m*sam + k*sak] * B[k*sbk + n*sbn]   (tiny products whose reduction dim is
 // not 16-byte friendly, e.g. over the 403 classes in the logits backward)
 __global__ __launch_bounds__(256) void matmul_small_kernel(const float* __restrict__ A, const float* __restrict__ B,
@@ -1127,6 +1230,57 @@ extern "C" int clipfs_adamw_scaled(float* p, const float* g, float* m, float* v,
   CLIPFS_REQUIRE(n > 0, "adamw_scaled: n = 0");
   hipLaunchKernelGGL(adamw_scaled_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, p, g, m,
                      v, n, lr, beta1, beta2, eps, weight_decay, scaler_state);
+  return launch_status();
+}
+
+extern "C" size_t clipfs_grad_sumsq_work_doubles(size_t n) { return sumsq_chunks(n); }
+
+extern "C" int clipfs_grad_sumsq(const float* g, size_t n, double* work, void* stream) {
+  CLIPFS_REQUIRE(g && aligned4(g), "grad_sumsq: null or misaligned gradient pointer");
+  CLIPFS_REQUIRE(work && (reinterpret_cast<uintptr_t>(work) & 7u) == 0, "grad_sumsq: null or misaligned work buffer");
+  CLIPFS_REQUIRE(n > 0, "grad_sumsq: n = 0");
+  const unsigned head = (unsigned)(((16u - (reinterpret_cast<uintptr_t>(g) & 15u)) & 15u) / 4);
+  hipLaunchKernelGGL(grad_sumsq_kernel, dim3((unsigned)sumsq_chunks(n)), dim3(256), 0, (hipStream_t)stream, g, n,
+                     sumsq_chunk_elems(n), head, work);
+  return launch_status();
+}
+
+extern "C" int clipfs_clip_decide(const double* work, size_t n, float max_norm, const float* scaler_state,
+                                  float* clip_state, void* stream) {
+  CLIPFS_REQUIRE(clip_state && aligned16(clip_state), "clip_decide: null or misaligned clip state");
+  CLIPFS_REQUIRE(!scaler_state || aligned16(scaler_state), "clip_decide: misaligned scaler state");
+  CLIPFS_REQUIRE(work && (reinterpret_cast<uintptr_t>(work) & 7u) == 0, "clip_decide: null or misaligned work buffer");
+  CLIPFS_REQUIRE(n > 0, "clip_decide: n = 0");
+  CLIPFS_REQUIRE(max_norm > 0.f && max_norm <= 3.402823466e38f, "clip_decide: max_norm %g must be positive and finite",
+                 (double)max_norm);
+  hipLaunchKernelGGL(clip_decide_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, work, (int)sumsq_chunks(n), max_norm,
+                     scaler_state, clip_state);
+  return launch_status();
+}
+
+extern "C" int clipfs_adamw_ext(float* p, const float* g, float* m, float* v, size_t n, int step, float lr, float beta1,
+                                float beta2, float eps, float weight_decay, float grad_scale, const float* scaler_state,
+                                const float* clip_state, float* ema_shadow, float ema_decay, void* stream) {
+  CLIPFS_REQUIRE(p && g && m && v && aligned4(p) && aligned4(g) && aligned4(m) && aligned4(v),
+                 "adamw_ext: null or misaligned pointer");
+  CLIPFS_REQUIRE(!scaler_state || aligned16(scaler_state), "adamw_ext: misaligned scaler state");
+  CLIPFS_REQUIRE(!clip_state || aligned16(clip_state), "adamw_ext: misaligned clip state");
+  CLIPFS_REQUIRE(!ema_shadow || (aligned4(ema_shadow) && ema_shadow != p && ema_shadow != m && ema_shadow != v),
+                 "adamw_ext: misaligned or aliased ema shadow");
+  CLIPFS_REQUIRE(!ema_shadow || (ema_decay > 0.f && ema_decay < 1.f), "adamw_ext: ema_decay %g must lie in (0, 1)",
+                 (double)ema_decay);
+  CLIPFS_REQUIRE(n > 0, "adamw_ext: n = 0");
+  CLIPFS_REQUIRE(scaler_state || step >= 1, "adamw_ext: step %d must be >= 1 without a scaler state", step);
+  float inv_sqrt_bc2 = 0.f, step_size = 0.f;  // read from the record when there is one
+  if (!scaler_state) {
+    const double bc1 = 1.0 - pow((double)beta1, step);
+    const double bc2 = 1.0 - pow((double)beta2, step);
+    inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2));
+    step_size = (float)((double)lr / bc1);
+  }
+  hipLaunchKernelGGL(adamw_ext_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n,
+                     lr, beta1, beta2, eps, weight_decay, inv_sqrt_bc2, step_size, grad_scale, scaler_state, clip_state,
+                     ema_shadow, ema_decay, 1.f - ema_decay);
   return launch_status();
 }
 

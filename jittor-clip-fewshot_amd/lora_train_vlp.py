@@ -613,15 +613,19 @@ class FlatTrainables:
         bias_names = [n for n, _ in trainable_biases(model)]
         entries = []
         mlp_params = []  # trainable MLP adapters (mlp.c_fc / mlp.c_proj): A then B, after the attention adapters
+        labels = []      # one name per segment of the buffer, in buffer order (``segments``)
+        mlp_labels = []
         for tname, tower in (("text", model.transformer), ("vision", model.visual.transformer)):
             for i, blk in enumerate(tower.resblocks):
                 a = blk.attn
                 if getattr(a, "is_lora_mha", False) and _lora_trains(a, f"{tname} block {i}"):
                     for name, p, _ in a.stacked():
                         entries.append((a, name, p))
+                        labels.append(f"{tname}.{i}.attn.{name}/mask{a.lora_mask}")
                 for tok, m in mlp_adapters(blk):
                     if _mlp_lora_trains(m, f"{tname} block {i} mlp.{tok}"):
                         mlp_params += [m.w_lora_A, m.w_lora_B]
+                        mlp_labels += [f"{tname}.{i}.mlp.{tok}.w_lora_A", f"{tname}.{i}.mlp.{tok}.w_lora_B"]
         n_bias = sum(p.numel() for _, p in trainable_biases(model))
         deep = trainable_deep_prompts(model)
         n = (sum(p.numel() for _, _, p in entries) + sum(p.numel() for p in mlp_params) + sum(p.numel() for p in extra)
@@ -701,6 +705,13 @@ class FlatTrainables:
                     self._packed_src.append(self.params[o:o + d])
         assert off == n
         self.numel = n
+        # ordered (name, size) of every segment: the layout fingerprint a saved optimiser state is checked against
+        sizes = ([p.numel() for _, _, p in entries] + [p.numel() for p in mlp_params] + [p.numel() for p in extra]
+                 + [p.numel() for p in deep] + [named[nm].numel() for nm in bias_names])
+        labels += mlp_labels + [f"extra.{j}" for j in range(len(self.extra))] + [f"deep_prompt.{j}" for j in range(len(deep))]
+        labels += [f"bias.{nm}" for nm in bias_names]
+        self.segments = [(nm, int(k)) for nm, k in zip(labels, sizes)]
+        assert len(labels) == len(sizes) and sum(sizes) == n
         self.sync_packed()
         model.invalidate_engine()
 
@@ -737,7 +748,175 @@ def _check_loss_scale(loss_scale, init_scale, growth_factor, backoff_factor, gro
     return "static"
 
 
-class LoRATrainer:
+def _check_step_options(max_grad_norm, ema_decay):
+    """Validate the clipping / EMA arguments of the trainers (None = off)."""
+    for name, x in (("max_grad_norm", max_grad_norm), ("ema_decay", ema_decay)):
+        if x is not None and (isinstance(x, bool) or not isinstance(x, numbers.Real) or not math.isfinite(x)):
+            raise ValueError(f"{name} must be None or a finite number, not {x!r}")
+    if max_grad_norm is not None and not 0 < max_grad_norm <= float(np.finfo(np.float32).max):
+        raise ValueError(f"max_grad_norm must be None or a positive number that fp32 holds, not {max_grad_norm!r}")
+    if ema_decay is not None and not (0 < float(np.float32(ema_decay)) < 1):
+        raise ValueError(f"ema_decay must be None or lie in (0, 1) as an fp32 number, not {ema_decay!r}")
+
+
+class OptimizerStepOptions:
+    """What ``LoRATrainer`` and the fused ``Stage2Trainer`` share around their one AdamW launch over ``flat``: gradient
+    clipping by global norm, an EMA shadow of the parameters, and handing the whole optimiser state out and back.
+
+    ``max_grad_norm``: ``torch.nn.utils.clip_grad_norm_``'s rule on the UNSCALED gradient, on the device: after the
+    all-reduce (every rank forms the same norm from the same bytes: no new collective) and after the scaler's decision,
+    two more launches (sum of squares, decision) and the multiplier folded into AdamW's gradient scale: 1 -> 3 launches
+    per optimiser step, 3 -> 5 with loss scaling, no host synchronisation.  ``last_grad_norm`` / ``last_clip_coef`` read
+    the device record back (they synchronise; ``step`` never uses them).  A non-finite norm without loss scaling gives
+    a coefficient of 0 and a poisoned update, as torch with ``error_if_nonfinite=False``: ``loss_scale`` skips such steps.
+
+    ``ema_decay``: a flat fp32 shadow beside ``flat.m`` / ``flat.v``, set to the parameters at construction (the
+    reference's ``EMA.register``, lora_train_vlp.py:870-904) and updated inside the AdamW launch
+    (``shadow = decay * shadow + (1 - decay) * param``, :887); a skipped step leaves it untouched.  ``apply_shadow()`` puts
+    the averaged values into ``flat.params`` for evaluation and ``restore()`` brings the live ones back.
+
+    With both None the step is the launches it was without them."""
+
+    def _init_step_options(self, max_grad_norm, ema_decay):
+        dev = self.flat.params.device
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.ema_decay = None if ema_decay is None else float(ema_decay)
+        self.clip_state = self._sumsq_work = self.ema_shadow = self._ema_backup = None
+        if self.max_grad_norm is not None:
+            self.clip_state = ops.new_clip_state(dev)
+            self._sumsq_work = ops.grad_sumsq_work(self.flat.numel, dev)
+        if self.ema_decay is not None:
+            self.ema_shadow = self.flat.params.clone()
+
+    def _apply_update(self):
+        """The launches of one optimiser step after the all-reduce (``self.t`` already counts this step)."""
+        f = self.flat
+        if self.scale_state is not None:
+            growth, backoff, interval = self._scaler_rule
+            ops.grads_nonfinite(f.grads, self.scale_state)
+            ops.scaler_decide(self.scale_state, self.lr, self.betas, growth, backoff, interval)
+        if self.clip_state is not None:
+            ops.grad_sumsq(f.grads, self._sumsq_work)
+            ops.clip_decide(self._sumsq_work, f.numel, self.max_grad_norm, self.clip_state, self.scale_state)
+        if self.clip_state is not None or self.ema_shadow is not None:
+            ops.adamw_ext(f.params, f.grads, f.m, f.v, self.t, self.lr, self.betas, self.eps, self.wd, 1.0,
+                          self.scale_state, self.clip_state, self.ema_shadow, self.ema_decay or 0.0)
+        elif self.scale_state is not None:
+            ops.adamw_scaled(f.params, f.grads, f.m, f.v, self.scale_state, self.lr, self.betas, self.eps, self.wd)
+        else:
+            ops.adamw(f.params, f.grads, f.m, f.v, self.t, self.lr, self.betas, self.eps, self.wd, 1.0)
+
+    # -- clipping: host views of the device record (each one synchronises) ----------------------------
+    @property
+    def last_grad_norm(self) -> Optional[float]:
+        """The unscaled global 2-norm of the gradients of the last ``optimizer_step`` (None with clipping off)."""
+        return None if self.clip_state is None else float(self.clip_state[ops._lib.CLIP_NORM].item())
+
+    @property
+    def last_clip_coef(self) -> Optional[float]:
+        """The factor the last ``optimizer_step`` multiplied the gradients by, in (0, 1] (None with clipping off)."""
+        return None if self.clip_state is None else float(self.clip_state[ops._lib.CLIP_COEF].item())
+
+    # -- EMA: evaluation-time swaps ---------------------------------------------------------------------
+    @property
+    def shadow_applied(self) -> bool:
+        return self._ema_backup is not None
+
+    @torch.no_grad()
+    def apply_shadow(self):
+        """Put the averaged values into the flat parameter buffer (the live ones are kept for ``restore``)."""
+        if self.ema_shadow is None:
+            raise RuntimeError("apply_shadow needs ema_decay")
+        if self._ema_backup is not None:
+            raise RuntimeError("the EMA shadow is already applied: call restore() first")
+        self._ema_backup = self.flat.params.clone()
+        self.flat.params.copy_(self.ema_shadow)
+        self.flat.sync_packed()
+
+    @torch.no_grad()
+    def restore(self):
+        """Bring back the live parameters ``apply_shadow`` set aside."""
+        if self._ema_backup is None:
+            raise RuntimeError("restore without a preceding apply_shadow")
+        self.flat.params.copy_(self._ema_backup)
+        self._ema_backup = None
+        self.flat.sync_packed()
+
+    # -- resumable state ----------------------------------------------------------------------------------
+    def _switches(self) -> Dict[str, bool]:
+        return {"loss_scale": self.scale_state is not None, "max_grad_norm": self.clip_state is not None,
+                "ema_decay": self.ema_shadow is not None}
+
+    def state_dict(self) -> dict:
+        """Everything a run needs to go on where it stopped, as CPU tensors and plain Python values (store it with
+        ``torch.save``; adapter files of ``save_lora`` are another matter): the flat parameters and AdamW moments, the EMA
+        shadow (and the live values set aside while it is applied), the loss-scaling and clip records, ``t``, ``lr``, the
+        scheduler position (stage 2), the engine's dropout seed state, the hyper-parameters and the layout of the flat
+        buffer.  Synchronises."""
+        cpu = lambda x: None if x is None else x.detach().cpu().clone()
+        eng = self.model.engine
+        sched = getattr(self, "sched", None)
+        return {
+            "layout": [(n, k) for n, k in self.flat.segments],
+            "switches": self._switches(),
+            "params": cpu(self.flat.params), "m": cpu(self.flat.m), "v": cpu(self.flat.v),
+            "ema_shadow": cpu(self.ema_shadow), "shadow_applied": self._ema_backup is not None,
+            "ema_backup": cpu(self._ema_backup),
+            "scale_state": cpu(self.scale_state), "clip_state": cpu(self.clip_state),
+            "t": int(self.t), "lr": float(self.lr),
+            "scheduler": None if sched is None else {"base_lr": sched.base_lr, "T_max": sched.T_max,
+                                                     "eta_min": sched.eta_min, "last_epoch": sched.last_epoch},
+            "engine": {"seed_base": int(eng.seed_base), "step": int(eng.step)},
+            "hyper": {"weight_decay": float(self.wd), "betas": (float(self.betas[0]), float(self.betas[1])),
+                      "eps": float(self.eps), "max_grad_norm": self.max_grad_norm, "ema_decay": self.ema_decay,
+                      "loss_scaling": self.loss_scaling,
+                      "scaler_rule": None if self.scale_state is None else tuple(self._scaler_rule)},
+        }
+
+    @torch.no_grad()
+    def load_state_dict(self, sd: dict) -> None:
+        """Take back a ``state_dict()``.  The trainer must have been built like the one that wrote it: the same flat
+        layout and the same of loss scaling, clipping and EMA switched on -- a ``ValueError`` names what differs and
+        nothing is changed.  Everything else (hyper-parameters included) is restored from ``sd``."""
+        mine, theirs = [(n, k) for n, k in self.flat.segments], [(n, int(k)) for n, k in sd["layout"]]
+        if mine != theirs:
+            a, b = dict(theirs), dict(mine)
+            diff = ([f"{n}: saved {a[n]} floats, this trainer {b[n]}" for n in a if n in b and a[n] != b[n]]
+                    + [f"{n}: only in the saved state" for n in a if n not in b]
+                    + [f"{n}: only in this trainer" for n in b if n not in a]) or ["the segments come in another order"]
+            raise ValueError("the saved state belongs to another flat layout (" + "; ".join(diff[:4])
+                             + (f"; and {len(diff) - 4} more" if len(diff) > 4 else "") + ")")
+        sw = self._switches()
+        bad = [f"{k} is {'on' if sd['switches'][k] else 'off'} in the saved state and {'on' if sw[k] else 'off'} in this "
+               "trainer" for k in sw if bool(sd["switches"][k]) != sw[k]]
+        if bad:
+            raise ValueError("the saved state was written with other options: " + "; ".join(bad))
+        sched = getattr(self, "sched", None)
+        if (sched is None) != (sd["scheduler"] is None):
+            raise ValueError("the saved state " + ("has no" if sched is not None else "carries a")
+                             + " scheduler position: it was written by the other kind of trainer")
+        f = self.flat
+        for dst, key in ((f.params, "params"), (f.m, "m"), (f.v, "v"), (self.ema_shadow, "ema_shadow"),
+                         (self.scale_state, "scale_state"), (self.clip_state, "clip_state")):
+            if dst is not None:
+                dst.copy_(sd[key])
+        self._ema_backup = sd["ema_backup"].to(f.params.device) if sd["shadow_applied"] else None
+        self.t, self.lr = int(sd["t"]), float(sd["lr"])
+        if sched is not None:
+            s = sd["scheduler"]
+            sched.base_lr, sched.T_max, sched.eta_min = float(s["base_lr"]), int(s["T_max"]), float(s["eta_min"])
+            sched.last_epoch = int(s["last_epoch"])
+        eng = self.model.engine
+        eng.seed_base, eng.step = int(sd["engine"]["seed_base"]), int(sd["engine"]["step"])
+        h = sd["hyper"]
+        self.wd, self.betas, self.eps = float(h["weight_decay"]), tuple(h["betas"]), float(h["eps"])
+        self.max_grad_norm, self.ema_decay, self.loss_scaling = h["max_grad_norm"], h["ema_decay"], h["loss_scaling"]
+        if self.scale_state is not None:
+            self._scaler_rule = tuple(h["scaler_rule"])
+        f.sync_packed()
+
+
+class LoRATrainer(OptimizerStepOptions):
     """One object = the state of run_lora (:921-1023) that matters for the hot path: model with adapters,
     flat trainables, AdamW moments, step counter.  ``step`` is the loop body :956-1002:
 
@@ -760,14 +939,19 @@ class LoRATrainer:
     ``optimizer_step`` calls; with scaling on, AdamW's step number is ``optimizer_steps``, which leaves skipped steps
     out.  ``loss_scale_value`` / ``skipped_steps`` / ``optimizer_steps`` read the device record back (they synchronise;
     ``step`` never uses them).  Not covered: the autograd route of ``encode_image`` / ``encode_text`` (stage 2 scales
-    through ``slow_pace.Stage2Trainer(..., fused=True)``); bias training still needs a non-fp16 mode."""
+    through ``slow_pace.Stage2Trainer(..., fused=True)``); bias training still needs a non-fp16 mode.
+
+    ``max_grad_norm`` / ``ema_decay`` (both off by default) and ``state_dict`` / ``load_state_dict``: see
+    ``OptimizerStepOptions``."""
 
     def __init__(self, model, lr: float = 2e-4, weight_decay: float = 1e-2, betas=(0.9, 0.999), eps: float = 1e-8,
                  logit_scale: float = 100.0, prompt_ctx: Optional[nn.Parameter] = None, process_group=None,
                  shard_text: bool = True, loss_scale=None, growth_factor: float = 2.0, backoff_factor: float = 0.5,
-                 growth_interval: int = 2000, init_scale: float = 65536.0):
+                 growth_interval: int = 2000, init_scale: float = 65536.0, max_grad_norm: Optional[float] = None,
+                 ema_decay: Optional[float] = None):
         from clipfs import dist as D
         self.loss_scaling = _check_loss_scale(loss_scale, init_scale, growth_factor, backoff_factor, growth_interval)
+        _check_step_options(max_grad_norm, ema_decay)
         self.model = model
         extra = []
         if prompt_ctx is not None:
@@ -808,6 +992,7 @@ class LoRATrainer:
         elif self.loss_scaling == "static":
             self._scaler_rule = (1.0, 1.0, 0)  # never grows, never backs off; still skips a non-finite step
             self.scale_state = ops.new_scaler_state(float(loss_scale), self.flat.params.device)
+        self._init_step_options(max_grad_norm, ema_decay)
 
     # -- loss scaling: host views of the device record (each one synchronises) -------------------------
     def _scaler_word(self, index: int, as_int: bool):
@@ -946,21 +1131,14 @@ class LoRATrainer:
 
     def optimizer_step(self):
         from clipfs import dist as D
-        grad_scale = 1.0
+        if self.shadow_applied:
+            raise RuntimeError("optimizer_step while the EMA shadow is applied: call restore() first")
         if self.world > 1 or D.FORCE_COLLECTIVES:
             # replicated text tower (shard_text=False): every rank back-propagated the text gradient of ITS images
             # only, so this same sum is already the batch total (d_txt is linear in the local dlogits)
             self._timed("all_reduce", lambda: D.allreduce_sum_(self.flat.grads, self.pg))
         self.t += 1
-        if self.scale_state is not None:
-            growth, backoff, interval = self._scaler_rule
-            ops.grads_nonfinite(self.flat.grads, self.scale_state)
-            ops.scaler_decide(self.scale_state, self.lr, self.betas, growth, backoff, interval)
-            ops.adamw_scaled(self.flat.params, self.flat.grads, self.flat.m, self.flat.v, self.scale_state, self.lr,
-                             self.betas, self.eps, self.wd)
-        else:
-            ops.adamw(self.flat.params, self.flat.grads, self.flat.m, self.flat.v, self.t, self.lr, self.betas,
-                      self.eps, self.wd, grad_scale)
+        self._apply_update()  # AdamW, behind the scaler's and the clip's launches when those are on
         self.flat.sync_packed()
 
     def step(self, images, captions, target, templates_per_class: int = 1, global_batch: Optional[int] = None,

@@ -31,7 +31,8 @@ from torch import nn
 from clipfs import engine as E
 from clipfs import ops
 from jclip import clip
-from lora_train_vlp import FlatTrainables, LoRATrainer, _check_loss_scale, trainable_biases
+from lora_train_vlp import (FlatTrainables, LoRATrainer, OptimizerStepOptions, _check_loss_scale, _check_step_options,
+                            trainable_biases)
 from lora_train_vlp import clip_classifier  # noqa: F401  (re-exported like the reference's copy)
 
 
@@ -499,8 +500,9 @@ class Stage2Trainer:
     ``zs_text_feature_sets``: the cached per-template-file classifiers one of which is drawn per step (:1603-1609,1662).
 
     ``fused=True`` builds a ``FusedStage2Trainer`` instead (same arguments; see there): the step on one flat buffer,
-    with data parallelism (``process_group`` / ``shard_text``) and loss scaling (``loss_scale`` ...).  Without it this
-    class is the autograd-route step it always was, and refuses those arguments."""
+    with data parallelism (``process_group`` / ``shard_text``), loss scaling (``loss_scale`` ...), gradient clipping
+    (``max_grad_norm``) and averaged weights (``ema_decay``).  Without it this class is the autograd-route step it
+    always was, and refuses those arguments."""
 
     def __new__(cls, *args, **kwargs):
         if cls is Stage2Trainer:
@@ -517,12 +519,17 @@ class Stage2Trainer:
                  zs_image_features: torch.Tensor, zs_text_features: torch.Tensor,
                  zs_text_feature_sets: Optional[Sequence[torch.Tensor]] = None, lr: float = 2e-4, total_epoch: int = 20,
                  weight_decay: float = 1e-2, betas=(0.9, 0.999), eps: float = 1e-8, moco_model=None,
-                 moco_adapter: Optional["Moco_Adapter"] = None, fused: bool = False, process_group=None,
+                 moco_adapter: Optional["Moco_Adapter"] = None, max_grad_norm: Optional[float] = None,
+                 ema_decay: Optional[float] = None, fused: bool = False, process_group=None,
                  shard_text: bool = True, loss_scale=None, growth_factor: float = 2.0, backoff_factor: float = 0.5,
                  growth_interval: int = 2000, init_scale: float = 65536.0):
         _check_loss_scale(loss_scale, init_scale, growth_factor, backoff_factor, growth_interval)
+        _check_step_options(max_grad_norm, ema_decay)
         if loss_scale is not None or (process_group is not None and process_group.size() > 1):
             raise ValueError("data parallelism (process_group) and loss scaling (loss_scale) belong to the fused step: "
+                             "pass fused=True")
+        if max_grad_norm is not None or ema_decay is not None:
+            raise ValueError("gradient clipping (max_grad_norm) and averaged weights (ema_decay) belong to the fused step: "
                              "pass fused=True")
         self.fused = False
         self.model, self.prompt_learner, self.head = clip_model, prompt_learner, channel_lp
@@ -582,7 +589,7 @@ class Stage2Trainer:
         return loss.detach(), terms, cos.detach()
 
 
-class FusedStage2Trainer(Stage2Trainer):
+class FusedStage2Trainer(Stage2Trainer, OptimizerStepOptions):
     """``Stage2Trainer(..., fused=True)``: the same loop body (slow_pace.py:1622-1697, without the MoCo branch) built the
     way ``LoRATrainer`` builds stage 1 instead of through autograd.
 
@@ -613,6 +620,11 @@ class FusedStage2Trainer(Stage2Trainer):
     AdamW's own step number (``optimizer_steps``) does not.  ``step`` never synchronises with the host;
     ``loss_scale_value`` / ``skipped_steps`` / ``optimizer_steps`` do.
 
+    Gradient clipping (``max_grad_norm``), averaged weights (``ema_decay``, ``apply_shadow`` / ``restore``) and the
+    resumable state (``state_dict`` / ``load_state_dict``, which carries the cosine schedule's position) are
+    ``lora_train_vlp.OptimizerStepOptions``, as in ``LoRATrainer``; ``apply_shadow`` swaps every trainable of the flat
+    buffer, the head's included.
+
     ``step`` returns ``(loss, terms, cos)``: device tensors holding this rank's SHARE of the loss and of each term
     (their sums over the ranks are the values of the whole batch; on one process they are what the unfused step
     returns), ``lp_ce`` -- and ``scl_text`` with a replicated text tower -- reported by rank 0 only; ``cos`` is the
@@ -626,11 +638,13 @@ class FusedStage2Trainer(Stage2Trainer):
                  zs_image_features: torch.Tensor, zs_text_features: torch.Tensor,
                  zs_text_feature_sets: Optional[Sequence[torch.Tensor]] = None, lr: float = 2e-4, total_epoch: int = 20,
                  weight_decay: float = 1e-2, betas=(0.9, 0.999), eps: float = 1e-8, moco_model=None,
-                 moco_adapter: Optional["Moco_Adapter"] = None, fused: bool = True, process_group=None,
+                 moco_adapter: Optional["Moco_Adapter"] = None, max_grad_norm: Optional[float] = None,
+                 ema_decay: Optional[float] = None, fused: bool = True, process_group=None,
                  shard_text: bool = True, loss_scale=None, growth_factor: float = 2.0, backoff_factor: float = 0.5,
                  growth_interval: int = 2000, init_scale: float = 65536.0):
         from clipfs import dist as D
         self.loss_scaling = _check_loss_scale(loss_scale, init_scale, growth_factor, backoff_factor, growth_interval)
+        _check_step_options(max_grad_norm, ema_decay)
         if not fused:
             raise ValueError("FusedStage2Trainer is the fused step: pass fused=True (or build a Stage2Trainer)")
         if moco_model is not None or moco_adapter is not None:
@@ -686,6 +700,7 @@ class FusedStage2Trainer(Stage2Trainer):
         elif self.loss_scaling == "static":
             self._scaler_rule = (1.0, 1.0, 0)  # never grows, never backs off; still skips a non-finite step
             self.scale_state = ops.new_scaler_state(float(loss_scale), dev)
+        self._init_step_options(max_grad_norm, ema_decay)
 
     # the device record's host views, the exchange buffers and the collective timers are LoRATrainer's own
     _scaler_word = LoRATrainer._scaler_word
@@ -827,18 +842,12 @@ class FusedStage2Trainer(Stage2Trainer):
 
     def optimizer_step(self):
         from clipfs import dist as D
+        if self.shadow_applied:
+            raise RuntimeError("optimizer_step while the EMA shadow is applied: call restore() first")
         if self.world > 1 or D.FORCE_COLLECTIVES:
             self._timed("all_reduce", lambda: D.allreduce_sum_(self.flat.grads, self.pg))
         self.t += 1
-        if self.scale_state is not None:
-            growth, backoff, interval = self._scaler_rule
-            ops.grads_nonfinite(self.flat.grads, self.scale_state)
-            ops.scaler_decide(self.scale_state, self.lr, self.betas, growth, backoff, interval)
-            ops.adamw_scaled(self.flat.params, self.flat.grads, self.flat.m, self.flat.v, self.scale_state, self.lr,
-                             self.betas, self.eps, self.wd)
-        else:
-            ops.adamw(self.flat.params, self.flat.grads, self.flat.m, self.flat.v, self.t, self.lr, self.betas, self.eps,
-                      self.wd, 1.0)
+        self._apply_update()  # AdamW at the pre-step rate, behind the scaler's and the clip's launches when those are on
         self.lr = self.sched.step()                                                       # :1697 (counts iterations)
 
     def step(self, images, target, index, template_choice: int = 0, global_batch: Optional[int] = None,
