@@ -494,6 +494,20 @@ int clipfs_im2col_nhwc(const float* x, float* col, int N, int H, int W, int C, i
 int clipfs_maxpool3x3s2_nhwc(const float* x, float* y, int N, int H, int W, int C, void* stream);
 int clipfs_global_avgpool_nhwc(const float* x, float* y, int N, int HW, int C, void* stream);
 
+/* ------------------------------------------------ CLIP ModifiedResNet tower --
+ * What CLIP's ModifiedResNet (RN50 family) needs beside the kernels above (forward only, fp32, NHWC; every pointer
+ * 16-byte aligned, C a multiple of 4; bad arguments return CLIPFS_EINVAL before anything is launched):
+ *   avgpool_nhwc    : y [N, H/k, W/k, C] = k x k mean with stride k, no padding, sizes floored (rows / columns past the
+ *                     last full window are never read); sum order row-major inside the window.  1 <= k <= min(H, W).
+ *   attnpool_tokens : x [N, HW, C], pos [HW+1, C] -> tok [N, HW+1, C]:  tok[n,0] = mean_i x[n,i] + pos[0],
+ *                     tok[n,1+i] = x[n,i] + pos[1+i]; one pass over x, the mean summed in ascending i.
+ *   attnpool_attend : q [N, heads*64], kv [N*L, 2*heads*64] (k | v) -> out [N, heads*64] = softmax_j(q.k_j / 8) . v_j per
+ *                     (image, head): the pool's single query row.  Max-subtracted softmax, fp32.  2 <= L <= 1024,
+ *                     1 <= heads <= 128. */
+int clipfs_avgpool_nhwc(const float* x, float* y, int N, int H, int W, int C, int k, void* stream);
+int clipfs_attnpool_tokens(const float* x, const float* pos, float* tok, int N, int HW, int C, void* stream);
+int clipfs_attnpool_attend(const float* q, const float* kv, float* out, int N, int L, int heads, void* stream);
+
 /* ---------------------------------------------------------- head / loss --
  * y = x / ||x||_2 per row; inv_norm[row] saved (may be NULL).  jclip/model.py:222-224. */
 int clipfs_l2norm_fwd(const float* x, float* y, float* inv_norm, int rows, int width, void* stream);

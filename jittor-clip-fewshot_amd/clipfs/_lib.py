@@ -208,6 +208,9 @@ SIGNATURES = {
     "clipfs_im2col_nhwc": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p]),
     "clipfs_maxpool3x3s2_nhwc": (_i, [_p, _p, _i, _i, _i, _i, _p]),
     "clipfs_global_avgpool_nhwc": (_i, [_p, _p, _i, _i, _i, _p]),
+    "clipfs_avgpool_nhwc": (_i, [_p, _p, _i, _i, _i, _i, _i, _p]),
+    "clipfs_attnpool_tokens": (_i, [_p, _p, _p, _i, _i, _i, _p]),
+    "clipfs_attnpool_attend": (_i, [_p, _p, _p, _i, _i, _i, _p]),
     "clipfs_prompt_put": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p]),
     "clipfs_prompt_harvest": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p, _p]),
     "clipfs_tower_saved_floats": (_sz, [C.POINTER(Tower), _i]),

@@ -379,9 +379,14 @@ class Engine:
     def __init__(self, model):
         self.model = model
         v = model.visual
-        self.vis = _TowerRT(v.transformer, v.tokens, stream0=1000, name="vision")
+        # A ModifiedResNet image tower (RN50 family, jclip.model.ModifiedResNet) is a frozen fp32 feature extractor with a
+        # runner of its own (clipfs/resnet.py: ClipResNet): no tower runtime (``vis``), no projection copy, no backward.
+        self.resnet = _is_resnet(v)
+        if not self.resnet:
+            self.vis = _TowerRT(v.transformer, v.tokens, stream0=1000, name="vision")
         self.txt = _TowerRT(model.transformer, model.context_length, stream0=0, name="text")
-        self.vproj_t = v.proj.data.t().contiguous()                  # [E, width]  (NT form of x @ proj)
+        if not self.resnet:
+            self.vproj_t = v.proj.data.t().contiguous()              # [E, width]  (NT form of x @ proj)
         self.tproj_t = model.text_projection.data.t().contiguous()   # [E, width]
         self.seed_base = 0x5EED
         self.step = 0
@@ -419,7 +424,7 @@ class Engine:
 
     @property
     def precision(self) -> str:
-        return self.vis.precision
+        return self.txt.precision if self.resnet else self.vis.precision
 
     @precision.setter
     def precision(self, mode: str) -> None:
@@ -427,15 +432,20 @@ class Engine:
         as split-bf16 with three bf16 MFMA products per operand pair, fp32 accumulate (weights are split once;
         logits move by ~2e-4 on 100 x cosine, inside the 1e-3 budget).  LayerNorm, attention, LoRA, the patch /
         projection / logits GEMMs and all reductions stay fp32.  "fp16": the same GEMMs with f16 operands
-        (v_mfma_f32_32x32x16_f16, fp32 accumulate) -- cfg-5's "MFMA fp16 path"; tolerance ~1e-2 on the logits."""
+        (v_mfma_f32_32x32x16_f16, fp32 accumulate) -- cfg-5's "MFMA fp16 path"; tolerance ~1e-2 on the logits.
+        A ModifiedResNet image tower stays fp32 in every mode: the setting then reaches the text tower only."""
         if mode not in ("fp32", "bf16x3", "fp16"):
             raise ValueError("precision must be 'fp32', 'bf16x3' or 'fp16'")
-        self.vis.precision = mode
+        if not self.resnet:
+            self.vis.precision = mode
         self.txt.precision = mode
 
     # -- backward plan --------------------------------------------------------------------------------
     def image_plan(self) -> Optional[int]:
-        """Gradient floor of the image tower (None: nothing of it trains).  0 with a VPT or a trainable ln_pre bias."""
+        """Gradient floor of the image tower (None: nothing of it trains).  0 with a VPT or a trainable ln_pre bias.
+        Always None for a ModifiedResNet: the trunk is frozen."""
+        if self.resnet:
+            return None
         if not self.prune_backward:
             return 0
         v = self.model.visual
@@ -457,7 +467,7 @@ class Engine:
     def vit_forward(self, images: torch.Tensor, train: bool, seed: int = 0, own_saved: bool = False, row0: int = 0):
         """``row0``: index of images[0] in the GLOBAL batch (data-parallel shard) -- only the dropout masks see it.
         ``train``: keep what the backward needs; with nothing of the image side to train (``image_plan`` None) the pass
-        is the no-grad one and the returned ctx is None."""
+        is the no-grad one and the returned ctx is None.  A ModifiedResNet tower (frozen, no dropout) always is."""
         lo = self.image_plan() if train else 0
         if lo is None:
             train = False
@@ -468,6 +478,8 @@ class Engine:
         B = images.shape[0]
         if images.shape[1] != 3 or images.shape[2] != v.input_resolution or images.shape[3] != v.input_resolution:
             raise ValueError(f"expected images [B,3,{v.input_resolution},{v.input_resolution}], got {tuple(images.shape)}")
+        if self.resnet:
+            return v(images), None
         L, d = v.tokens, v.width
         P = (v.input_resolution // v.patch_size) ** 2
         x0 = torch.empty(B * L, d, device=images.device, dtype=torch.float32)
@@ -669,8 +681,14 @@ def _block_biases(tower_mod) -> List[torch.nn.Parameter]:
     return [p for blk in tower_mod.resblocks for p in _blk_biases(blk)]
 
 
+def _is_resnet(visual) -> bool:
+    return bool(getattr(visual, "is_modified_resnet", False))
+
+
 def image_biases(model) -> List[torch.nn.Parameter]:
     v = model.visual
+    if _is_resnet(v):  # a frozen trunk: none of its biases is reachable by the fused backward
+        return []
     return [v.ln_pre.bias] + _block_biases(v.transformer) + [v.ln_post.bias]
 
 
@@ -694,6 +712,8 @@ def deep_prompts(tower_mod) -> List[torch.nn.Parameter]:
 
 
 def _image_trainables(model):
+    if _is_resnet(model.visual):
+        return []
     return (_tower_trainables(model.visual.transformer) + _bias_pairs(image_biases(model))
             + _bias_pairs(deep_prompts(model.visual.transformer)))
 
@@ -755,6 +775,8 @@ class _EncodeText(torch.autograd.Function):
 
 
 def encode_image(model, images: torch.Tensor) -> torch.Tensor:
+    """Image features; differentiable with respect to the image tower's adapters / prompts where it has any.  A
+    ModifiedResNet tower has none: its features come from the no-grad route, without a graph."""
     images = images.to(device=model.device, dtype=torch.float32)
     pairs = _image_trainables(model)
     params = [p for p, _ in pairs]

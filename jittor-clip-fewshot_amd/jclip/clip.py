@@ -5,7 +5,8 @@
   (lora_train_vlp.py:1163).  Accepted formats: a Jittor-saved ``.pkl`` state dict (read with the inert
   reader ``clipfs.safe_pkl`` -- nothing in the file is executed), a ``.npz`` of arrays, or a torch
   ``.pt`` state dict (``weights_only=True``).  A registry name (``"ViT-B/32"``) would need a download
-  (clip.py:171-174): there is no network, so it raises the reference's RuntimeError.
+  (clip.py:171-174): there is no network, so it raises the reference's RuntimeError.  The backbone is read off the
+  checkpoint's keys: a ViT, or a ModifiedResNet of the RN50 family (``mode="res"`` insists on the latter).
 * returns the reference's 5-tuple ``(model, tfm_nonorm, tfm_norm, tfm_train_nonorm, tfm_train_norm)``
   (clip.py:187); the transforms are PIL -> float32 CHW tensors (Resize 256 bicubic, CenterCrop 224,
   optional horizontal flip / CLIP mean-std normalisation, clip.py:130-163).
@@ -113,9 +114,15 @@ def _load(name, design_details=None, mode="vit", device=None):
                            f"Pass the path of a local checkpoint instead.")
     if not os.path.isfile(name):
         raise RuntimeError(f"Model {name} not found; available models = {available_models()}")
-    if mode != "vit":
-        raise NotImplementedError("ModifiedResNet backbones are outside the accelerated path (SURVEY.md section 2 row 16)")
-    model = build_model(read_state_dict(name), design_details=design_details, device=device)
+    if mode not in ("vit", "res"):
+        raise NotImplementedError(f"mode must be 'vit' or 'res', got {mode!r}")
+    state_dict = read_state_dict(name)
+    if mode == "res" and "visual.proj" in state_dict:
+        raise NotImplementedError('mode="res" needs a ModifiedResNet checkpoint (RN50 family: visual.layer1 ... '
+                                  f'visual.attnpool); {name} holds a ViT -- load it with mode="vit"')
+    # build_model tells the two backbones apart by their keys (jclip/model.py:235-285), so a ModifiedResNet checkpoint
+    # loads under either mode
+    model = build_model(state_dict, design_details=design_details, device=device)
     r = model.visual.input_resolution
     return model, _transform1(r), _transform2(r), tfm_train_base(r), tfm_train_base1(r)
 

@@ -9,7 +9,10 @@ replaceable ``resblocks[i].attn`` that ``apply_lora`` swaps.  All arithmetic run
 ``encode_image`` / ``encode_text`` hand the whole tower to ``clipfs.engine`` (one C call per pass),
 differentiable through ``torch.autograd`` with respect to the LoRA / prompt parameters only -- the
 backbone is frozen (dgrad only), which is the reference's training regime
-(mark_only_lora_as_trainable, lora_train_vlp.py:143-160)."""
+(mark_only_lora_as_trainable, lora_train_vlp.py:143-160).
+
+A checkpoint without ``visual.proj`` is one of the RN50 family: ``build_model`` then builds ``ModifiedResNet``
+(jclip/model_res.py), a frozen fp32 image tower run forward only by ``clipfs.resnet.ClipResNet``."""
 from __future__ import annotations
 
 from typing import Dict, Optional
@@ -147,6 +150,93 @@ class VisionTransformer(nn.Module):
         return (self.input_resolution // self.patch_size) ** 2 + 1 + (0 if self.VPT is None else self.VPT.shape[0])
 
 
+class _BatchNorm(nn.Module):
+    """Affine as frozen parameters, running statistics as buffers (the checkpoint's ``num_batches_tracked`` is not kept)."""
+
+    def __init__(self, sd: Dict[str, torch.Tensor], p: str):
+        super().__init__()
+        self.weight = _param(sd[p + ".weight"])
+        self.bias = _param(sd[p + ".bias"])
+        self.register_buffer("running_mean", sd[p + ".running_mean"].contiguous())
+        self.register_buffer("running_var", sd[p + ".running_var"].contiguous())
+        self.eps = 1e-5
+
+
+class Bottleneck(nn.Module):
+    """jclip/model_res.py:84-121 (parameter holder)."""
+
+    expansion = 4
+
+    def __init__(self, sd: Dict[str, torch.Tensor], p: str, stride: int):
+        super().__init__()
+        self.stride = stride
+        for i in (1, 2, 3):
+            setattr(self, f"conv{i}", _Conv1(sd[f"{p}.conv{i}.weight"]))
+            setattr(self, f"bn{i}", _BatchNorm(sd, f"{p}.bn{i}"))
+        self.downsample = None
+        if p + ".downsample.0.weight" in sd:  # children "0" (convolution) and "1" (BatchNorm); "-1" is the parameter-free pool
+            self.downsample = nn.Sequential(_Conv1(sd[p + ".downsample.0.weight"]), _BatchNorm(sd, p + ".downsample.1"))
+
+
+class AttentionPool2d(nn.Module):
+    """jclip/model_res.py:65-82 (parameter holder; the semantics are the published ones, clipfs/resnet.py: ClipResNet)."""
+
+    def __init__(self, sd: Dict[str, torch.Tensor], p: str, num_heads: int):
+        super().__init__()
+        self.positional_embedding = _param(sd[p + ".positional_embedding"])
+        for name in ("k_proj", "q_proj", "v_proj", "c_proj"):
+            setattr(self, name, Linear(sd[f"{p}.{name}.weight"], sd[f"{p}.{name}.bias"]))
+        self.num_heads = num_heads
+
+
+class ModifiedResNet(nn.Module):
+    """The image tower of the RN50 family (jclip/model_res.py:123-170): every tensor under its checkpoint name, as a
+    frozen parameter (running statistics: buffers), so ``CLIP.save`` / ``CLIP.load`` round-trip it.  ``forward`` hands the
+    images to the HIP runner ``clipfs.resnet.ClipResNet``, which folds the BatchNorms once (rebuilt after ``CLIP.load``):
+    forward only, fp32, BatchNorm on the running statistics whatever ``train()`` says -- the flagged deviations are in
+    that class's docstring.  Nothing in this tower trains: ``VPT`` is None, there is no ``transformer`` to adapt."""
+
+    is_modified_resnet = True
+    VPT = None
+
+    def __init__(self, sd: Dict[str, torch.Tensor], layers, output_dim: int, heads: int, input_resolution: int, width: int):
+        super().__init__()
+        self.layers = tuple(int(n) for n in layers)
+        self.output_dim = output_dim
+        self.input_resolution = input_resolution
+        self.width = width
+        self.heads = heads
+        for i in (1, 2, 3):
+            setattr(self, f"conv{i}", _Conv1(sd[f"visual.conv{i}.weight"]))
+            setattr(self, f"bn{i}", _BatchNorm(sd, f"visual.bn{i}"))
+        for li, nb in enumerate(self.layers):
+            setattr(self, f"layer{li + 1}", nn.Sequential(*[
+                Bottleneck(sd, f"visual.layer{li + 1}.{bi}", 2 if (bi == 0 and li > 0) else 1) for bi in range(nb)]))
+        self.attnpool = AttentionPool2d(sd, "visual.attnpool", heads)
+        self._runner = None
+
+    @property
+    def tokens(self) -> int:
+        return (self.input_resolution // 32) ** 2 + 1
+
+    @property
+    def runner(self):
+        if self._runner is None:
+            from clipfs.resnet import ClipResNet
+            self._runner = ClipResNet(self.state_dict(), self.conv1.weight.device)
+        return self._runner
+
+    def invalidate(self):
+        """The tensors changed (``CLIP.load``): the runner's folded copies are stale."""
+        self._runner = None
+
+    @torch.no_grad()
+    def forward(self, images: torch.Tensor) -> torch.Tensor:
+        return self.runner(images)
+
+    execute = forward
+
+
 class _Embedding(nn.Module):
     def __init__(self, weight: torch.Tensor):
         super().__init__()
@@ -171,9 +261,18 @@ class CLIP(nn.Module):
         self.vocab_size = vocab_size
         self.embed_dim = embed_dim
         n_vpt = int(design_details["vision_ctx"]) if design_details else 0
-        v_depth, t_depth, n_txt = _prompt_depths(design_details, n_vpt, vision_layers, transformer_layers)
-        self.visual = VisionTransformer(sd, image_resolution, vision_patch_size, vision_width, vision_layers,
-                                        vision_width // 64, embed_dim, n_vpt, v_depth)
+        if isinstance(vision_layers, (tuple, list)):  # jclip/model_res.py:227-235
+            if n_vpt > 0 or (design_details and design_details.get("deep_prompts", False)
+                             and int(design_details.get("vision_depth", 1)) > 1):
+                raise ValueError("the image tower of this checkpoint is a ModifiedResNet (RN50 family): it has no token "
+                                 "sequence for visual prompts -- pass design_details with vision_ctx=0 (and vision_depth=1)")
+            _, t_depth, n_txt = _prompt_depths(design_details, 0, 1, transformer_layers)
+            self.visual = ModifiedResNet(sd, vision_layers, embed_dim, vision_width * 32 // 64, image_resolution,
+                                         vision_width)
+        else:
+            v_depth, t_depth, n_txt = _prompt_depths(design_details, n_vpt, vision_layers, transformer_layers)
+            self.visual = VisionTransformer(sd, image_resolution, vision_patch_size, vision_width, vision_layers,
+                                            vision_width // 64, embed_dim, n_vpt, v_depth)
         self.transformer = Transformer(sd, "transformer", transformer_width, transformer_layers, transformer_heads,
                                        causal=True, prompt_depth=t_depth, prompt_rows=n_txt, prompt_seed=2)
         self.token_embedding = _Embedding(sd["token_embedding.weight"])
@@ -202,6 +301,8 @@ class CLIP(nn.Module):
     def load(self, path: str) -> None:
         from clipfs import module_io
         module_io.load_module(self, path)
+        if hasattr(self.visual, "invalidate"):
+            self.visual.invalidate()  # a ModifiedResNet's runner holds BatchNorm-folded copies
         self.invalidate_engine()  # transposed / 16-bit weight copies of the engine are stale now
 
     def invalidate_engine(self):
@@ -263,14 +364,23 @@ def _prompt_depths(design_details, n_vpt: int, vision_layers: int, text_layers: 
 
 
 def _infer(sd: Dict[str, torch.Tensor]):
-    """Hyper-parameters from tensor shapes, jclip/model.py:235-274."""
-    if "visual.proj" not in sd:
-        raise NotImplementedError("only ViT backbones are on the accelerated path (ModifiedResNet: SURVEY.md section 2 row 16)")
-    vision_width = sd["visual.conv1.weight"].shape[0]
-    vision_layers = len([k for k in sd if k.startswith("visual.") and k.endswith(".attn.in_proj_weight")])
-    vision_patch_size = sd["visual.conv1.weight"].shape[-1]
-    grid_size = round((sd["visual.positional_embedding"].shape[0] - 1) ** 0.5)
-    image_resolution = vision_patch_size * grid_size
+    """Hyper-parameters from tensor shapes, jclip/model.py:235-274; a checkpoint without ``visual.proj`` is a
+    ModifiedResNet (jclip/model_res.py:316-331): ``vision_layers`` is then the tuple of blocks per stage."""
+    if "visual.proj" in sd:
+        vision_width = sd["visual.conv1.weight"].shape[0]
+        vision_layers = len([k for k in sd if k.startswith("visual.") and k.endswith(".attn.in_proj_weight")])
+        vision_patch_size = sd["visual.conv1.weight"].shape[-1]
+        grid_size = round((sd["visual.positional_embedding"].shape[0] - 1) ** 0.5)
+        image_resolution = vision_patch_size * grid_size
+    else:
+        if "visual.layer1.0.conv1.weight" not in sd or "visual.attnpool.positional_embedding" not in sd:
+            raise NotImplementedError("the checkpoint holds neither a ViT (visual.proj) nor a ModifiedResNet "
+                                      "(visual.layer1.0.conv1.weight, visual.attnpool.positional_embedding) image tower")
+        vision_layers = tuple(len({k.split(".")[2] for k in sd if k.startswith(f"visual.layer{b}.")}) for b in (1, 2, 3, 4))
+        vision_width = sd["visual.layer1.0.conv1.weight"].shape[0]
+        grid_size = round((sd["visual.attnpool.positional_embedding"].shape[0] - 1) ** 0.5)
+        vision_patch_size = None
+        image_resolution = grid_size * 32
     embed_dim = sd["text_projection"].shape[1]
     context_length = sd["positional_embedding"].shape[0]
     vocab_size = sd["token_embedding.weight"].shape[0]
@@ -294,6 +404,8 @@ def build_model(state_dict: dict, design_details=None, device=None) -> CLIP:
     sd = {}
     for k, v in state_dict.items():
         if k in ("input_resolution", "context_length", "vocab_size"):
+            continue
+        if k.endswith("num_batches_tracked"):  # BatchNorm's int64 counter (ModifiedResNet checkpoints): not a weight
             continue
         t = torch.from_numpy(np.ascontiguousarray(v)) if isinstance(v, np.ndarray) else torch.as_tensor(v)
         sd[k] = t.detach().to(device=device, dtype=torch.float32).contiguous()

@@ -375,6 +375,9 @@ def apply_lora(args, clip_model):
                             object.__setattr__(new, tok, lin)
                     list_lora_layers.append(new)
 
+    if args.encoder in ('vision', 'both') and getattr(clip_model.visual, "transformer", None) is None:
+        raise ValueError(f"encoder={args.encoder!r}: the image tower is a ModifiedResNet (RN50 family), which has no "
+                         "transformer blocks to adapt -- pass encoder='text'")
     if args.encoder == 'text' or args.encoder == 'both':
         adapt(clip_model.transformer.resblocks, INDEX_POSITIONS_TEXT[args.position])
     if args.encoder == 'vision' or args.encoder == 'both':
@@ -549,6 +552,13 @@ def evaluate_lora(args, clip_model, loader, templates=None, textual_features=Non
 # flat trainable buffer + stage-1 step (lora_train_vlp.py:946,956-1002)
 # ----------------------------------------------------------------------------------------------
 
+def towers(model) -> List[Tuple[str, nn.Module]]:
+    """(name, transformer) of the towers that have blocks to adapt: text, then vision.  A ModifiedResNet image tower
+    (RN50 family) has no transformer and is left out: nothing of it trains."""
+    vt = getattr(model.visual, "transformer", None)
+    return [("text", model.transformer)] + ([] if vt is None else [("vision", vt)])
+
+
 def trainable_biases(model) -> List[Tuple[str, nn.Parameter]]:
     """(name, parameter) of the biases ``LoRATrainer`` trains: exactly those with ``requires_grad=True``, in
     ``model.named_parameters()`` order.  The flags come from ``mark_only_lora_as_trainable(model, bias)``:
@@ -586,7 +596,7 @@ def trainable_biases(model) -> List[Tuple[str, nn.Parameter]]:
 def trainable_deep_prompts(model) -> List[nn.Parameter]:
     """The deep prompts (``resblocks.{i}.VPT_shallow``) with ``requires_grad``: text tower, then vision, block order."""
     from clipfs.engine import deep_prompts
-    return [p for tower in (model.transformer, model.visual.transformer) for p in deep_prompts(tower) if p.requires_grad]
+    return [p for _, tower in towers(model) for p in deep_prompts(tower) if p.requires_grad]
 
 
 class FlatTrainables:
@@ -615,7 +625,7 @@ class FlatTrainables:
         mlp_params = []  # trainable MLP adapters (mlp.c_fc / mlp.c_proj): A then B, after the attention adapters
         labels = []      # one name per segment of the buffer, in buffer order (``segments``)
         mlp_labels = []
-        for tname, tower in (("text", model.transformer), ("vision", model.visual.transformer)):
+        for tname, tower in towers(model):
             for i, blk in enumerate(tower.resblocks):
                 a = blk.attn
                 if getattr(a, "is_lora_mha", False) and _lora_trains(a, f"{tname} block {i}"):
@@ -671,7 +681,7 @@ class FlatTrainables:
         self.bias_offset = off
         self._packed_dst, self._packed_src = [], []
         owner = {}  # id(q/k/v_proj.bias) -> (attention block, segment)
-        for tower in (model.transformer, model.visual.transformer):
+        for _, tower in towers(model):
             for blk in tower.resblocks:
                 a = blk.attn
                 if getattr(a, "is_lora_mha", False):
@@ -689,7 +699,7 @@ class FlatTrainables:
                 a, s = owner[id(p)]
                 seg_off.setdefault(a, {})[s] = off
             off += k
-        for tower in (model.transformer, model.visual.transformer):
+        for _, tower in towers(model):
             for blk in tower.resblocks:
                 a = blk.attn
                 if getattr(a, "is_lora_mha", False) and a.proj.bias.requires_grad:
@@ -960,7 +970,7 @@ class LoRATrainer(OptimizerStepOptions):
             extra.append(model.visual.VPT)
         self.flat = FlatTrainables(model, extra)
         if model.engine.precision == "fp16":
-            for tname, tower in (("text", model.transformer), ("vision", model.visual.transformer)):
+            for tname, tower in towers(model):
                 for i, blk in enumerate(tower.resblocks):
                     for tok, _ in mlp_adapters(blk):
                         raise ValueError(f"{tname} block {i} has a {tok} adapter: MLP adapters are not supported in the fp16 "

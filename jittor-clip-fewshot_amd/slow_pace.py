@@ -630,7 +630,8 @@ class FusedStage2Trainer(Stage2Trainer, OptimizerStepOptions):
     returns), ``lp_ce`` -- and ``scl_text`` with a replicated text tower -- reported by rank 0 only; ``cos`` is the
     rank's [B_local, C] logit block.
 
-    Refused (ValueError): the MoCo branch, and a model with a trainable LoRA adapter or bias -- the unfused trainer
+    Refused (ValueError): the MoCo branch, a ModifiedResNet image tower (RN50 family: the unfused trainer, which only needs
+    the tower's features, takes it), and a model with a trainable LoRA adapter or bias -- the unfused trainer
     never updates them (the reference freezes them, :1551-1556), so training them here would be another problem.  Not
     covered beyond that: bias training in the fp16 storage mode (as in stage 1)."""
 
@@ -654,6 +655,9 @@ class FusedStage2Trainer(Stage2Trainer, OptimizerStepOptions):
             raise ValueError("fused=True trains prompt ctx, VPT / deep prompts and the head only, as the unfused trainer "
                              f"does; these LoRA adapters are flagged trainable (freeze them): {', '.join(bad[:4])}"
                              + (f" and {len(bad) - 4} more" if len(bad) > 4 else ""))
+        if getattr(clip_model.visual, "is_modified_resnet", False):
+            raise ValueError("fused=True does not cover a ModifiedResNet image tower (RN50 family): the fused step walks the "
+                             "ViT tower's forward and backward -- use fused=False, which only needs its features")
         if clip_model.visual.VPT is not None:
             clip_model.visual.VPT.requires_grad_(True)
         for n, p in clip_model.named_parameters():
