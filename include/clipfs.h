@@ -93,15 +93,15 @@ typedef struct clipfs_gemm_args {
   const void* B_planes;    /* optional 16-bit copy of B (a_mode 0, K % 32 == 0, ldb == K); NULL = exact fp32 */
   int b_format;            /* 1: bf16 hi/lo planes (clipfs_split_bf16) -> split-bf16 x3 kernel;
                               2: one f16 plane (clipfs_convert_f16) -> f16 MFMA kernel (cfg-5's fp16 path) */
-  float* workspace;        /* optional split-K / stream-K slab scratch, 16-byte aligned (NULL: never split) */
+  float* workspace;        /* optional split-K slab scratch, 16-byte aligned (NULL: never split) */
   size_t workspace_floats;
   const void* A_f16;       /* optional f16 copy of A [M,K] (ld = lda): with b_format 2 selects the f16 x f16 kernel
                               (operands stream HBM -> LDS -> MFMA untouched); A may then be NULL */
   void* C_f16;             /* f16 x f16 kernel only: also (or, with C == NULL, only) write the result as f16, ld = ldc */
   int aux_f16;             /* f16 x f16 kernel only: aux_out / aux_in hold f16 values (fp16 storage of the saved
                               pre-activation), ld = ldc */
-  int* counters;           /* optional arrival counters (split-K, stream-K): >= clipfs_gemm_counter_ints(M,N,K) ints, ZERO on
-                              entry (the kernel leaves them zero); with `workspace` enables those schedules */
+  int* counters;           /* optional arrival counters (split-K): >= clipfs_gemm_counter_ints(M,N,K) ints, ZERO on
+                              entry (the kernel leaves them zero); with `workspace` enables the split */
   size_t counters_ints;
 } clipfs_gemm_args;
 /* Ordering: everything the call does is ordered on `stream` (work queued on it before the call happens-before, work
@@ -122,13 +122,46 @@ int clipfs_split_bf16(const float* src, void* planes, size_t n, void* stream);
 /* dst[0..n) = f16(src): weights for the fp16 MFMA mode (v_mfma_f32_32x32x16_f16, fp32 accumulate; activations are
  * rounded to f16 in the staging path).  Tolerance is that of fp16 products (~5e-4 relative), stated in the tests. */
 int clipfs_convert_f16(const float* src, void* dst, size_t n, void* stream);
+/* The dispatch of the exact fp32 and the 16-bit-plane kernels as data: clipfs_gemm_plan IS the function clipfs_gemm_nt
+ * executes (validate, plan, one switch over `kernel`).  Host-only: nothing is launched and no pointer of `args` is
+ * dereferenced; their nullness and 16-byte alignment take part in the choice.  Returns CLIPFS_EINVAL with the refusal's
+ * message for arguments clipfs_gemm_nt would refuse (`plan` is left untouched), and with A_f16 set: that kernel's plan
+ * is clipfs_gemm_f16_plan.  The schedule is stated for the MI355X's 256 CUs.  The aids CLIPFS_GEMM_BM (32 / 64),
+ * _SPLITS, _GM, _LDS_PAD (KiB), _GLDS=0 and CLIPFS_BF16_TILE (1 / 2) are read once per process and show in the plan. */
+#define CLIPFS_GEMM_NT64 0       /* dense, K % 32 == 0: 64 x 128 tile, operands staged by LDS-DMA */
+#define CLIPFS_GEMM_NT64_REG 1   /*   the same staged through registers (CLIPFS_GEMM_GLDS=0) */
+#define CLIPFS_GEMM_NT32 2       /*   32 x 128 tile */
+#define CLIPFS_GEMM_MIXED 3      /*   rows [0, mix_rows64) as 64 x 128 tiles, the rows behind them as 32 x 128, one launch */
+#define CLIPFS_GEMM_PATCH32 4    /* a_mode 1 with patch 32 and 16-byte aligned image rows: 64 x 128 */
+#define CLIPFS_GEMM_GENERIC 5    /* K % 32 != 0, or any other patch size: 64 x 128, per-element addresses */
+#define CLIPFS_GEMM_PLANES64 6   /* B_planes (a_mode 0, K % 32 == 0, ldb == K): 64 x 128 */
+#define CLIPFS_GEMM_PLANES128 7  /*   128 x 128 */
+struct clipfs_gemm_plan {
+  int kernel;               /* CLIPFS_GEMM_* */
+  int planes;               /* PLANES*: 16-bit planes per operand, 2 (bf16 hi / lo) or 1 (f16); 0 otherwise */
+  int tile_rows;            /* rows of the tile that runs; MIXED: 32, the height of the tail tiles */
+  int splits;               /* split-K factor granted with the scratch as given (1: unsplit) */
+  int want_splits;          /* the factor the call would get with enough scratch (1 on a route that cannot split) */
+  int mix_rows64;           /* MIXED: rows dealt as 64-row tiles (0 otherwise) */
+  int gm;                   /* m-blocks per super-tile of the tile order */
+  int grid, block;          /* workgroups, threads per workgroup */
+  int lds_bytes;            /* dynamic LDS per workgroup */
+  size_t workspace_floats;  /* what want_splits needs of `workspace` ... */
+  size_t counter_ints;      /* ... and of `counters` (both 0 when want_splits is 1) */
+};
+int clipfs_gemm_plan(const clipfs_gemm_args* args, struct clipfs_gemm_plan* plan);
+/* The five shape-only queries below describe a DENSE fp32 product (a_mode 0, no planes) that is given enough scratch,
+ * whatever K % 32 is: they size scratch ahead of a call and keep their answers where the call then takes another route
+ * (K % 32 != 0, patch mode and planes never split; those kernels exist with 64-row tiles only).  The plan is the truth
+ * for a given call.  Host-only, no launch.
+ * clipfs_gemm_splits: the split-K factor (the plan's want_splits). */
 int clipfs_gemm_splits(int M, int N, int K);
-/* rows of the block tile (64 or 32) the exact fp32 kernels use for an [M,N] output: host-only query, no launch */
+/* rows of the block tile (64 or 32) for an [M,N] output (the plan's tile_rows) */
 int clipfs_gemm_tile_rows(int M, int N);
 /* Dense unsplit fp32 products of 4096 rows or more (K % 32 == 0) for which clipfs_gemm_tile_rows answers 32 may deal
  * rows [0, clipfs_gemm_mixed_rows64) as 64-row tiles -- whole rounds of the resident workgroup slots -- and only the rows
  * behind them as 32-row tiles, in one launch; 0 = one height, that of clipfs_gemm_tile_rows.  It changes no result bit: an
- * element's k order does not depend on the tile that holds it.  Host-only query, no launch. */
+ * element's k order does not depend on the tile that holds it. */
 int clipfs_gemm_mixed_rows64(int M, int N, int K);
 /* The f16 x f16 kernel (args->A_f16 set) is nine kernels and a row split: whole rounds of 256 x 256 tiles over the CUs on
  * a ping-pong or phased kernel, the leftover rows on 4-wave kernels, on the internal side stream when `side` is set.
@@ -156,13 +189,10 @@ typedef struct clipfs_f16_plan {
   clipfs_f16_launch launch[3];
 } clipfs_f16_plan;
 int clipfs_gemm_f16_plan(const clipfs_gemm_args* args, int cus, clipfs_f16_plan* out);
+/* floats of `workspace` and ints of `counters` the split of clipfs_gemm_splits needs: one slab of a whole tile per K slice
+ * and tile, one arrival counter per tile (the plan's workspace_floats / counter_ints); 0 for a shape that does not split.
+ * The opt-in stream-K schedule that also used them (CLIPFS_GEMM_SK) was removed at this commit: it lost inside the step. */
 size_t clipfs_gemm_workspace_floats(int M, int N, int K);
-/* Stream-K (opt-in: environment CLIPFS_GEMM_SK=1|2; dense fp32 products with K % 32 == 0, when `workspace` and `counters`
- * are both supplied; clipfs_gemm_counter_ints returns 0 while it is off): the tiles x K-steps
- * iteration space is cut into equal contiguous runs, one per resident workgroup, instead of one tile per workgroup
- * (whose last round leaves most CUs idle at the path's 2-9 tiles per slot).  A tile shared by several runs is summed by
- * the last run to arrive, in run order (bitwise reproducible, no float atomics, nobody waits).  `workspace` holds the
- * partial-tile slabs, `counters` one arrival counter per tile: zeroed once by the caller, left zero by every launch. */
 size_t clipfs_gemm_counter_ints(int M, int N, int K);
 /* Diagnostics for bench.py's roofline leg (never enabled inside a timed region): while enabled, every
  * GEMM launch of the calling thread is bracketed by HIP events on its launch stream;
@@ -781,7 +811,7 @@ typedef struct clipfs_tower {
   const clipfs_block* blocks; /* HOST array [layers] of device pointers */
   int weight_format;        /* format of the blocks' *_p copies: 0 none (exact fp32), 1 bf16 hi/lo, 2 f16 */
   int* gemm_counters;       /* optional: >= clipfs_tower_counter_ints(t, batch) ints, zeroed ONCE by the caller (every
-                               GEMM leaves them zero) -- enables the stream-K GEMM schedule; one buffer per stream */
+                               GEMM leaves them zero) -- with the scratch enables split-K; one buffer per stream */
   size_t gemm_counters_ints;
   int grad_lo;              /* gradient floor: the lowest block whose parameters train.  0 = every block (today's
                                behaviour).  Blocks below it keep no activations in the forward (same kernels, same
@@ -859,8 +889,8 @@ int clipfs_tower_bwd_packed(const clipfs_tower* t, const float* dxs, const int32
  * forward's values, dropout masks and keep bits included.  `saved` (NULL: no-grad) keeps R rows per block inside the
  * clipfs_tower_saved_floats buffer; its backward is clipfs_tower_bwd_packed_saved.  Runs clipfs_tower_fwd_rows instead
  * (and the backward is then clipfs_tower_bwd_packed) when clipfs_tower_pack_fwd_mode(t, batch, R) == 0: whenever
- * clipfs_tower_pack_mode is 0, outside the exact fp32 mode, where a dense GEMM of the tower's shapes would run split-K or
- * stream-K at batch*seq rows (an unsplit R-row launch would sum in another order), or with LoRA dropout on an
+ * clipfs_tower_pack_mode is 0, outside the exact fp32 mode, where a dense GEMM of the tower's shapes would run split-K
+ * at batch*seq rows (an unsplit R-row launch would sum in another order), or with LoRA dropout on an
  * o-projection adapter or on a rank the fused LayerNorm + down-projection does not cover. */
 int clipfs_tower_pack_fwd_mode(const clipfs_tower* t, int batch, int R);
 int clipfs_tower_fwd_packed(const clipfs_tower* t, float* x, const int32_t* rows, const int32_t* plan, int R, int batch,

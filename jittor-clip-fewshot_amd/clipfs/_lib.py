@@ -52,6 +52,12 @@ class F16Plan(C.Structure):
     _fields_ = [("n", C.c_int), ("launch", F16Launch * 3)]
 
 
+class GemmPlan(C.Structure):
+    _fields_ = [("kernel", C.c_int), ("planes", C.c_int), ("tile_rows", C.c_int), ("splits", C.c_int), ("want_splits", C.c_int),
+                ("mix_rows64", C.c_int), ("gm", C.c_int), ("grid", C.c_int), ("block", C.c_int), ("lds_bytes", C.c_int),
+                ("workspace_floats", C.c_size_t), ("counter_ints", C.c_size_t)]
+
+
 class AttentionLaunch(C.Structure):
     _fields_ = [("grid_x", C.c_uint), ("grid_y", C.c_uint), ("block", C.c_uint), ("lds_bytes", C.c_uint)]
 
@@ -83,6 +89,8 @@ LORA_FAMILIES = ("mfma", "row")
 
 # CLIPFS_F16_* kernel ids of include/clipfs.h, by value
 F16_KERNELS = ("64x128", "64x128_s2", "128x128", "256x128", "pp_reg", "pp_lds", "ph16", "ph16_wide", "ph32")
+# CLIPFS_GEMM_* kernel ids of include/clipfs.h, by value
+GEMM_KERNELS = ("nt64", "nt64_reg", "nt32", "mixed", "patch32", "generic", "planes64", "planes128")
 
 
 class Block(C.Structure):
@@ -126,6 +134,7 @@ SIGNATURES = {
     "clipfs_gemm_nt": (_i, [C.POINTER(GemmArgs), _p]),
     "clipfs_split_bf16": (_i, [_p, _p, _sz, _p]),
     "clipfs_convert_f16": (_i, [_p, _p, _sz, _p]),
+    "clipfs_gemm_plan": (_i, [C.POINTER(GemmArgs), C.POINTER(GemmPlan)]),
     "clipfs_gemm_splits": (_i, [_i, _i, _i]),
     "clipfs_gemm_tile_rows": (_i, [_i, _i]),
     "clipfs_gemm_mixed_rows64": (_i, [_i, _i, _i]),
@@ -258,6 +267,14 @@ def gemm_f16_plan(g: GemmArgs, cus: int = 0):
     plan = F16Plan()
     check(load().clipfs_gemm_f16_plan(C.byref(g), cus, C.byref(plan)), "gemm_f16_plan")
     return [(F16_KERNELS[l.kernel], l.m_begin, l.m_end, bool(l.side)) for l in plan.launch[:plan.n]]
+
+
+def gemm_plan(g: GemmArgs):
+    """The plan clipfs_gemm_nt executes for the exact fp32 / 16-bit-plane product `g` (host-only), as a dict of the fields of
+    struct clipfs_gemm_plan with the kernel by name.  A refusal raises ClipfsError with its message."""
+    plan = GemmPlan()
+    check(load().clipfs_gemm_plan(C.byref(g), C.byref(plan)), "gemm_plan")
+    return dict(kernel=GEMM_KERNELS[plan.kernel], **{k: getattr(plan, k) for k, _ in GemmPlan._fields_[1:]})
 
 
 def attention_plan(direction: str, batch: int, seq: int, heads: int, causal: bool, stats: bool = True, aligned: bool = True):

@@ -266,7 +266,7 @@ class _TowerRT:
         return buf
 
     def _attach_counters(self, t: Tower, batch: int, device) -> None:
-        """Stream-K arrival counters of the tower's GEMMs: zeroed once here, left zero by every launch; one buffer per
+        """Split-K arrival counters of the tower's GEMMs: zeroed once here, left zero by every launch; one buffer per
         tower (the two towers run on different streams)."""
         n = _lib.load().clipfs_tower_counter_ints(C.byref(t), batch)
         if n == 0:

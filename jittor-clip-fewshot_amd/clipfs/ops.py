@@ -32,7 +32,7 @@ _COUNTERS = {}
 
 
 def _gemm_counters(device, n: int) -> torch.Tensor:
-    """Zeroed stream-K arrival counters for a stand-alone GEMM call: cached per (device, stream) -- launches on one
+    """Zeroed split-K arrival counters for a stand-alone GEMM call: cached per (device, stream) -- launches on one
     stream are ordered and every launch leaves the counters zero."""
     key = (device.index, _stream())
     buf = _COUNTERS.get(key)

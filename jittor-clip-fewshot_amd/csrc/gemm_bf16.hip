@@ -238,34 +238,28 @@ __global__ __launch_bounds__(256) void gemm_bf16x3_kernel(const Bf16Params bp) {
 }
 
 template <int BM, int BN, int NPL>
-static int launch_bf16(Bf16Params& bp, hipStream_t stream) {
-  const clipfs_gemm_args& a = bp.g.a;
-  bp.g.n_blocks_n = (a.N + BN - 1) / BN;
-  const int mb = (a.M + BM - 1) / BM;
-  const size_t lds = 2 * (size_t)(NPL * BM * 64 + NPL * BN * 64);
+static int launch_bf16(const Bf16Params& bp, const GemmPlan& plan, hipStream_t stream) {
   static bool attr = false;
-  if (!attr && lds > 48 * 1024) {
+  if (!attr && plan.lds_bytes > 48 * 1024) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_bf16x3_kernel<BM, BN, NPL>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+                              hipFuncAttributeMaxDynamicSharedMemorySize, plan.lds_bytes);
     attr = true;
   }
-  hipLaunchKernelGGL((gemm_bf16x3_kernel<BM, BN, NPL>), dim3(mb * bp.g.n_blocks_n), dim3(256), lds, stream, bp);
+  hipLaunchKernelGGL((gemm_bf16x3_kernel<BM, BN, NPL>), dim3(plan.grid), dim3(plan.block), plan.lds_bytes, stream, bp);
   return launch_status();
 }
 
-// called from clipfs_gemm_nt when args->B_planes is set and the shape qualifies
-int gemm_bf16x3_dispatch(const GemmParams& base, hipStream_t stream) {
+// called from clipfs_gemm_nt when the plan's kernel is CLIPFS_GEMM_PLANES64 / _PLANES128: tile, grid and LDS size are the
+// plan's (gemm.hip, gemm_schedule)
+int gemm_bf16x3_dispatch(const GemmParams& base, const GemmPlan& plan, hipStream_t stream) {
   Bf16Params bp;
   bp.g = base;
-  bp.g.splits = 1;
   const clipfs_gemm_args& a = base.a;
   bp.b_hi = a.B_planes;
   bp.b_lo = reinterpret_cast<const char*>(a.B_planes) + (size_t)a.N * a.ldb * 2;
-  static const int tile_cfg = getenv("CLIPFS_BF16_TILE") ? atoi(getenv("CLIPFS_BF16_TILE")) : 0;
-  const long t128 = (long)((a.M + 127) / 128) * ((a.N + 127) / 128);
-  const bool big = tile_cfg == 1 || (tile_cfg == 0 && t128 >= 1024);
-  if (a.b_format == 2) return big ? launch_bf16<128, 128, 1>(bp, stream) : launch_bf16<64, 128, 1>(bp, stream);
-  return big ? launch_bf16<128, 128, 2>(bp, stream) : launch_bf16<64, 128, 2>(bp, stream);
+  const bool big = plan.kernel == CLIPFS_GEMM_PLANES128;
+  if (plan.planes == 1) return big ? launch_bf16<128, 128, 1>(bp, plan, stream) : launch_bf16<64, 128, 1>(bp, plan, stream);
+  return big ? launch_bf16<128, 128, 2>(bp, plan, stream) : launch_bf16<64, 128, 2>(bp, plan, stream);
 }
 
 }  // namespace clipfs

@@ -110,7 +110,7 @@ constexpr int kGemmShape[kGemms][2] = {{3, 1}, {1, 1}, {4, 1}, {1, 4}, {1, 3}, {
 
 struct ScratchLayout {
   size_t h, big, b3, b1, dt, work, gemm_ws, gemm_ws_floats, a16, c16, bwork, total;
-  size_t counter_ints;  // stream-K arrival counters the tower's largest GEMM needs (a separate, caller-zeroed buffer)
+  size_t counter_ints;  // split-K arrival counters the tower's largest GEMM needs (a separate, caller-zeroed buffer)
 };
 
 static ScratchLayout scratch_layout(const clipfs_tower* t, size_t M) {
@@ -231,9 +231,9 @@ static int check_bwd_weights(const clipfs_tower* t) {
 
 // Per-call state of a tower pass (no hidden / thread-local state: everything a GEMM of the pass needs travels here)
 struct TowerCtx {
-  float* ws = nullptr;          // split-K / stream-K scratch (inside the call's scratch buffer)
+  float* ws = nullptr;          // split-K scratch (inside the call's scratch buffer)
   size_t ws_floats = 0;
-  int* counters = nullptr;      // stream-K arrival counters (caller-zeroed; every launch leaves them zero)
+  int* counters = nullptr;      // split-K arrival counters (caller-zeroed; every launch leaves them zero)
   size_t counters_ints = 0;
   int b_format = 0;             // format of the blocks' 16-bit weight copies
   void* a16 = nullptr;          // fp16 mode: f16 image of the A operand (converted per GEMM)
@@ -1037,7 +1037,7 @@ static bool pack_ok(const clipfs_tower* t, int batch, int R) {
 static bool pack_fwd_ok(const clipfs_tower* t, int batch, int R) {
   if (!pack_ok(t, batch, R) || t->weight_format != 0) return false;  // exact fp32 only
   const int M = batch * t->seq, d = t->width, r = t->lora_r;
-  for (int i = 0; i < kFwdGemms; ++i)  // split-K or stream-K at M?
+  for (int i = 0; i < kFwdGemms; ++i)  // split-K at M?
     if (clipfs_gemm_workspace_floats(M, kGemmShape[i][0] * d, kGemmShape[i][1] * d) != 0) return false;
   // dropout on the packed rows: only the fused LayerNorm + down-projection draws its masks through the row map, and the
   // blocks below grad_lo draw them too

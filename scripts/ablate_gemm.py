@@ -1,5 +1,7 @@
-"""Timing of the stream-K GEMM under tuning knobs (CLIPFS_GEMM_SK_TILE, CLIPFS_GEMM_SK_PER_CU, CLIPFS_GEMM_SK, and the
-timing-only CLIPFS_GEMM_ABLATE bits: 1 no LDS-DMA, 4 no barrier, 8 no LDS fragment reads, 16 no epilogue -- WRONG results)."""
+"""Timing of the fp32 GEMM under its tuning aids (CLIPFS_GEMM_BM, _SPLITS, _GM, _LDS_PAD, _GLDS: every CLIPFS_GEMM_* set
+is printed in front of the line) and, in a -DCLIPFS_ABLATION_BUILD library with CLIPFS_GEMM_GLDS=0, the timing-only
+CLIPFS_GEMM_ABLATE bits of the register-staging K loop: 1 no global prefetch, 2 no LDS store, 4 no barrier -- WRONG
+results.  The stream-K schedule and its knobs, which this script was written for, are gone."""
 import os, sys, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "jittor-clip-fewshot_amd"))

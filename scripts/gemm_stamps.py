@@ -34,12 +34,10 @@ for name, M, N, K in shapes:
     e1.record()
     torch.cuda.synchronize()
     ev_us = e0.elapsed_time(e1) * 1e3
-    tile_cfg = int(os.environ.get('CLIPFS_GEMM_TILE', '0'))
-    bm, bn = (128, 128) if tile_cfg == 1 else (64, 128)
-    S = lib.clipfs_gemm_splits(M, N, K)
-    if tile_cfg == 1:
-        S = 1
-    units = -(-M // bm) * -(-N // bn) * S
+    # dense, K % 32 == 0, scratch supplied by ops.gemm_nt, below the mixed band: the shape-only queries are what ran
+    assert lib.clipfs_gemm_mixed_rows64(M, N, K) == 0
+    bm, S = lib.clipfs_gemm_tile_rows(M, N), lib.clipfs_gemm_splits(M, N, K)
+    units = -(-M // bm) * -(-N // 128) * S
     n = min(units, 16384)
     buf = (ctypes.c_ulonglong * (n * 6))()
     assert raw.clipfs_debug_read_stamps(buf, n * 6) == 0

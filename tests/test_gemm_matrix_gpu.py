@@ -153,8 +153,10 @@ def problem(dev, M, N, K, *, pad=True, ldb_pad=True, patch=None):
 
 
 # ------------------------------------------------------------------ the one driver
-def run_gemm(dev, shape, epilogue, *, precision="fp32", split=True, pad=True, patch=None, ldb_pad=None, expect_rc=0):
-    """One clipfs_gemm_nt call on padded, guarded buffers.  Asserts that the guards of C / aux_out, the workspace tail
+def run_gemm(dev, shape, epilogue, *, precision="fp32", split=True, pad=True, patch=None, ldb_pad=None, expect_rc=0,
+             expect_plan=None):
+    """One clipfs_gemm_nt call on padded, guarded buffers.  Asserts first that clipfs_gemm_plan answers `expect_plan`
+    (fields of the plan) for the very arguments of the call, then that the guards of C / aux_out, the workspace tail
     and the counters are as the call found them; returns (C [M,N], aux_out [M,N] or None, bits of both whole buffers)."""
     from clipfs import _lib
     lib = _lib.load()
@@ -205,6 +207,9 @@ def run_gemm(dev, shape, epilogue, *, precision="fp32", split=True, pad=True, pa
     for ptr in (g.A, g.B, g.C, g.workspace, g.B_planes):
         assert not ptr or ptr % 16 == 0
     assert g.lda % 4 == 0 and g.ldb % 4 == 0
+    if expect_plan:
+        plan = _lib.gemm_plan(g)
+        assert {k: plan[k] for k in expect_plan} == expect_plan, plan
 
     rc = lib.clipfs_gemm_nt(C.byref(g), torch.cuda.current_stream().cuda_stream)
     assert rc == expect_rc, (rc, lib.clipfs_last_error())
@@ -229,11 +234,15 @@ def run_gemm(dev, shape, epilogue, *, precision="fp32", split=True, pad=True, pa
     return out, aux, (c_buf.view(torch.int32), aux_buf.view(torch.int32))
 
 
-def check_case(dev, shape, epi_name, *, precision="fp32", patch=None, ldb_pad=None, splits=1, budget_of=None):
-    """(a) - (f) of the module docstring's contract for one case."""
+def check_case(dev, shape, epi_name, *, kernel, tile_rows=64, precision="fp32", patch=None, ldb_pad=None, splits=1, budget_of=None,
+               plan_splits=None):
+    """(a) - (f) of the module docstring's contract for one case; `kernel`, `tile_rows` and `splits` (`plan_splits` where
+    the case does not compare against the unsplit kernel) are what the plan of every launch must name."""
     e = EPI[epi_name]
     M, N, K = shape
-    out, aux, bits = run_gemm(dev, shape, e, precision=precision, patch=patch, ldb_pad=ldb_pad)
+    plan_splits = plan_splits or splits
+    want_plan = dict(kernel=kernel, tile_rows=tile_rows, splits=plan_splits, want_splits=plan_splits)
+    out, aux, bits = run_gemm(dev, shape, e, precision=precision, patch=patch, ldb_pad=ldb_pad, expect_plan=want_plan)
     p = problem(dev, M, N, K, pad=True, ldb_pad=(precision == "fp32") if ldb_pad is None else ldb_pad, patch=patch)
     budget_of = budget_of or precision
     kind = "f16_rounded" if budget_of == "f16_plane" else "exact"
@@ -258,11 +267,12 @@ def check_case(dev, shape, epi_name, *, precision="fp32", patch=None, ldb_pad=No
     if e["act"] == 3:
         assert (out == 0).any() and (out > 0).any() and not (out < 0).any(), "ReLU case must clip some and keep some"
     # (b) - (d) were asserted by run_gemm;  (e) a second call into fresh buffers gives the same bits
-    out2, aux2, bits2 = run_gemm(dev, shape, e, precision=precision, patch=patch, ldb_pad=ldb_pad)
+    out2, aux2, bits2 = run_gemm(dev, shape, e, precision=precision, patch=patch, ldb_pad=ldb_pad, expect_plan=want_plan)
     assert torch.equal(bits[0], bits2[0]) and torch.equal(bits[1], bits2[1]), "not bitwise reproducible"
     # (f) split-K against the unsplit kernel on the same inputs
     if splits > 1:
-        out_u, aux_u, _ = run_gemm(dev, shape, e, precision=precision, patch=patch, ldb_pad=ldb_pad, split=False)
+        out_u, aux_u, _ = run_gemm(dev, shape, e, precision=precision, patch=patch, ldb_pad=ldb_pad, split=False,
+                                   expect_plan=dict(want_plan, splits=1))
         d = _err(out, out_u.double())
         if aux is not None:
             d = max(d, _err(aux, aux_u.double()))
@@ -285,7 +295,9 @@ def test_fp32_schedule_class(dev, c, epi):
     if c.S > 1:
         assert c.K % BK == 0 and lib.clipfs_gemm_workspace_floats(c.M, c.N, c.K) > 0
         assert lib.clipfs_gemm_counter_ints(c.M, c.N, c.K) > 0
-    check_case(dev, (c.M, c.N, c.K), epi, splits=c.S)
+    # the generic kernel exists with 64-row tiles only and never splits, whatever the shape-only queries answer
+    kernel, rows = ("generic", 64) if c.K % BK else ("nt32", 32) if c.tile_rows == 32 else ("nt64", 64)
+    check_case(dev, (c.M, c.N, c.K), epi, kernel=kernel, tile_rows=rows, splits=c.S)
 
 
 # ------------------------------------------------------------------ 16-bit-plane kernels
@@ -296,7 +308,8 @@ PLANE_CASES = [(pr, s, e) for s in PLANE_SHAPES for pr in ("bf16x3", "f16_plane"
 @pytest.mark.parametrize("precision,s,epi", PLANE_CASES, ids=[f"{pr}-{s.name}-{e}" for pr, s, e in PLANE_CASES])
 def test_plane_kernels(dev, precision, s, epi):
     assert plane_big_tile(s.M, s.N) == s.big_tile and s.K % BK == 0
-    check_case(dev, (s.M, s.N, s.K), epi, precision=precision)
+    check_case(dev, (s.M, s.N, s.K), epi, precision=precision, kernel="planes128" if s.big_tile else "planes64",
+               tile_rows=128 if s.big_tile else 64)
 
 
 @pytest.mark.parametrize("precision", ["bf16x3", "f16_plane"])
@@ -313,7 +326,7 @@ def test_planes_with_padded_ldb_fall_back_to_exact(dev, precision):
     fp64 product must hold (the f16 plane kernel would miss it by two orders of magnitude)."""
     s = PLANE_SHAPES[1]
     check_case(dev, (s.M, s.N, s.K), "bias_lora4_res", precision=precision, ldb_pad=True, budget_of="fp32",
-               splits=1)
+               splits=1, kernel="nt32", tile_rows=32, plan_splits=2)
 
 
 # ------------------------------------------------------------------ patch-embed A-mode
@@ -328,4 +341,4 @@ def test_patch_embed_mode(dev, patch, width, epi):
     the patches, the rows of the image behind the batch and the guard rows keep the sentinel (run_gemm's guard check)."""
     B, R, ps = patch
     M, K = B * (R // ps) ** 2, 3 * ps * ps
-    check_case(dev, (M, width, K), epi, patch=patch)
+    check_case(dev, (M, width, K), epi, patch=patch, kernel="generic")
