@@ -340,11 +340,23 @@ int clipfs_attention_bwd_packed_io(const float* qkv, const float* dout, const fl
 /* fp16 storage mode (cfg-5), seq <= clipfs_attention_f16_max_seq(): the same function with both contractions on
  * v_mfma_f32_32x32x16_f16 (operands rounded to f16 in the staging path; softmax statistics, accumulators and
  * outputs fp32).  lse as above (may be NULL when no backward follows).
- * seq <= 288: one workgroup per (batch, head), the head's K / V (Q / dO) resident in LDS.  288 < seq <= max_seq (1024;
- * ViT-L/14 at 336 px has 577 tokens): one workgroup per run of at most eight 32-token tiles of a head, the other side
- * streamed through LDS in chunks of at most 288 tokens; every output element is written by one workgroup, so results are
- * bitwise reproducible at every length.  A longer seq is refused before anything is launched. */
+ * Up to 288 tokens one workgroup takes a (batch, head) with the other side resident in LDS; past that (ViT-L/14 at 336 px
+ * has 577 tokens) the own side is cut into runs of 32-token tiles and the other side passes through LDS in chunks.
+ * Every output element is written by one workgroup, so results are bitwise reproducible at every length.
+ * clipfs_attention_f16_plan tells which of the two a call gets, with its cut, grids and LDS bytes.  This family has no
+ * fallback: a longer seq, a NULL or a misaligned pointer is refused before anything is launched. */
 int clipfs_attention_f16_max_seq(void);
+/* The dispatch of the three entry points below as data: clipfs_attention_f16_plan IS the function they execute, under
+ * the contract of clipfs_attention_plan (host-only, nothing written to `plan` on refusal, a NULL `plan` refused).
+ * flags: CLIPFS_ATTN_STATS (backward: out, lse and work are there; the forward's plan does not depend on it) and
+ * CLIPFS_ATTN_ALIGNED (every pointer the entry point checks is 16-byte aligned).  nt and lmax stay 0. */
+#define CLIPFS_ATTN_F16_FWD 0         /* direction: clipfs_attention_f16_fwd */
+#define CLIPFS_ATTN_F16_BWD 1         /*   clipfs_attention_f16_bwd */
+#define CLIPFS_ATTN_F16_BWD_PACKED 2  /*   clipfs_attention_f16_bwd_packed */
+#define CLIPFS_ATTN_F16_SHORT 7       /* family: one workgroup per (batch, head), seq <= 288 */
+#define CLIPFS_ATTN_F16_LONG 8        /*   `parts` runs of `tiles` 32-token tiles, other side in chunks of `ctok` */
+int clipfs_attention_f16_plan(int direction, int batch, int seq, int heads, int causal, int flags,
+                              struct clipfs_attention_plan* plan);
 int clipfs_attention_f16_fwd(const void* qkv, int qkv_f16, float* out, void* out16, float* lse, int batch, int seq,
                              int heads, int causal, void* stream);
 /* dqkv from (qkv, dout, out, lse) of clipfs_attention_f16_fwd; work: batch*heads*seq floats (D_i = dO_i . O_i).
@@ -355,9 +367,9 @@ int clipfs_attention_f16_fwd(const void* qkv, int qkv_f16, float* out, void* out
 int clipfs_attention_f16_bwd(const void* qkv, int qkv_f16, const void* dout, int dout_f16, const float* out,
                              const float* lse, float* dqkv, void* dqkv16, float* work, int batch, int seq, int heads,
                              int causal, void* stream);
-/* Packed (live-row) causal backward of the text tower in fp16 storage mode, seq <= 288 on the one-workgroup-per-head
- * kernels above (clipfs_attention_f16_bwd_packed_ok(seq, causal) != 0; needs causal).  As clipfs_attention_bwd_packed:
- * sequence b is live on tokens 0 .. Lb - 1, Lb = off[b + 1] - off[b] in [1, seq]; qkv (fp32 or f16), out and lse are the
+/* Packed (live-row) causal backward of the text tower in fp16 storage mode, on the one-workgroup-per-head kernels
+ * above (clipfs_attention_f16_bwd_packed_ok(seq, causal) != 0: the CLIPFS_ATTN_F16_BWD_PACKED plan succeeds).
+ * As clipfs_attention_bwd_packed: sequence b is live on tokens 0 .. Lb - 1, Lb = off[b + 1] - off[b] in [1, seq]; qkv (fp32 or f16), out and lse are the
  * dense forward's tensors (row b * seq + tok, lse [b * heads + h][seq]) and work keeps that dense layout; dout (fp32 or
  * f16) and dqkv / dqkv16 are packed (row off[b] + tok).  Either of dqkv / dqkv16 may be NULL, not both.  Each live row
  * gets exactly the values clipfs_attention_f16_bwd computes when every dead row of dout is 0, in both images; tiles past

@@ -70,7 +70,9 @@ class AttentionPlan(C.Structure):
 # CLIPFS_ATTN_* directions, flags and kernel families of include/clipfs.h, by value
 ATTN_DIRECTIONS = ("fwd", "bwd", "fwd_packed", "bwd_packed", "bwd_packed_io")
 ATTN_STATS, ATTN_ALIGNED = 1, 2
-ATTN_FAMILIES = ("mfma16", "mfma16_packed", "mfma16_pinned", "mfma32", "mfma_long", "stream", "recompute")
+ATTN_FAMILIES = ("mfma16", "mfma16_packed", "mfma16_pinned", "mfma32", "mfma_long", "stream", "recompute",
+                 "f16_short", "f16_long")  # the first seven: what clipfs_attention_plan returns; the last two: the f16 plan
+ATTN_F16_DIRECTIONS = ("fwd", "bwd", "bwd_packed")
 
 class LoraLaunch(C.Structure):
     _fields_ = [("grid_x", C.c_uint), ("grid_y", C.c_uint), ("block", C.c_uint)]
@@ -158,6 +160,7 @@ SIGNATURES = {
     "clipfs_attention_mfma_long_fwd": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
     "clipfs_attention_mfma_long_bwd": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
     "clipfs_attention_f16_max_seq": (_i, []),
+    "clipfs_attention_f16_plan": (_i, [_i, _i, _i, _i, _i, _i, C.POINTER(AttentionPlan)]),
     "clipfs_attention_f16_fwd": (_i, [_p, _i, _p, _p, _p, _i, _i, _i, _i, _p]),
     "clipfs_attention_f16_bwd": (_i, [_p, _i, _p, _i, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p]),
     "clipfs_lora_keep_bits_ok": (_i, [_i, _i, _i, _i]),
@@ -285,10 +288,25 @@ def attention_plan(direction: str, batch: int, seq: int, heads: int, causal: boo
     flags = (ATTN_STATS if stats else 0) | (ATTN_ALIGNED if aligned else 0)
     check(load().clipfs_attention_plan(ATTN_DIRECTIONS.index(direction), batch, seq, heads, int(causal), flags, C.byref(plan)),
           "attention_plan")
+    return _attention_plan_dict(plan)
+
+
+def _attention_plan_dict(plan: AttentionPlan):
     own = {"mfma16": ("nt",), "mfma16_packed": ("nt",), "mfma16_pinned": ("nt",), "mfma_long": ("parts", "tiles", "ctok"),
-           "recompute": ("lmax",)}.get(ATTN_FAMILIES[plan.family], ())
+           "recompute": ("lmax",), "f16_long": ("parts", "tiles", "ctok")}.get(ATTN_FAMILIES[plan.family], ())
     return dict(family=ATTN_FAMILIES[plan.family], **{k: getattr(plan, k) for k in own},
                 launches=tuple((l.grid_x, l.grid_y, l.block, l.lds_bytes) for l in plan.launch[:plan.launches]))
+
+
+def attention_f16_plan(direction: str, batch: int, seq: int, heads: int, causal: bool, stats: bool = True, aligned: bool = True):
+    """The plan clipfs_attention_f16_fwd / _bwd / _bwd_packed execute for these arguments (host-only), as the dict of
+    attention_plan: family "f16_short" or "f16_long" (with parts, tiles, ctok) and the launches.  A refusal raises
+    ClipfsError with its message."""
+    plan = AttentionPlan()
+    flags = (ATTN_STATS if stats else 0) | (ATTN_ALIGNED if aligned else 0)
+    check(load().clipfs_attention_f16_plan(ATTN_F16_DIRECTIONS.index(direction), batch, seq, heads, int(causal), flags,
+                                           C.byref(plan)), "attention_f16_plan")
+    return _attention_plan_dict(plan)
 
 
 def lora_plan(op: str, rows: int, width: int, segw: int, r: int, nseg: int, x_act: bool = False, keep_bits: bool = False,

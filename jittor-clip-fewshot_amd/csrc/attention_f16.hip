@@ -741,6 +741,11 @@ __global__ __launch_bounds__(64 * AF_LONG_WAVES) void attention_f16_long_bwd_kv_
   }
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// Host half.  af_plan() is the only place that decides a launch of this file (family, cut, grid, block, LDS bytes); the
+// three entry points execute that plan, clipfs_attention_f16_plan() returns it without opening a GPU, and
+// tests/test_attention_f16_plan.py pins it.
+// ---------------------------------------------------------------------------------------------------------
 static size_t af_lds_bytes(int L, int images_rowmajor, int images_transposed) {
   const int Lp = (L + 31) & ~31;
   return ((size_t)images_rowmajor * Lp * AF_ROW + (size_t)images_transposed * 64 * (Lp + 4)) * sizeof(_Float16);
@@ -755,162 +760,177 @@ static AfRuns af_runs(int seq, int max_tiles) {
   return {parts, (tiles + parts - 1) / parts};
 }
 
-}  // namespace clipfs
-
-using namespace clipfs;
-
-static int check_af(const void* a, const void* b, int batch, int seq, int heads) {
-  CLIPFS_REQUIRE(a && b, "attention_f16: null pointer");
-  CLIPFS_REQUIRE(batch > 0 && heads > 0 && seq > 0 && seq <= AF_LONG_MAXL, "attention_f16: seq %d outside 1..%d", seq,
-                 AF_LONG_MAXL);
-  CLIPFS_REQUIRE(seq <= AF_MAXL || (long long)batch * heads * af_runs(seq, AF_LONG_WAVES).parts <= 0x7fffffffLL,
-                 "attention_f16: batch %d x heads %d too large for seq %d", batch, heads, seq);
-  return CLIPFS_OK;
-}
-
-extern "C" int clipfs_attention_f16_max_seq(void) { return AF_LONG_MAXL; }
-
 static int af_threads(int seq, int max_waves) {
   const int tiles = (seq + 31) / 32;
   return 64 * (tiles < max_waves ? tiles : max_waves);
 }
 
-template <typename TQ>
-static void af_set_attrs() {
-  static bool done = false;
-  if (done) return;
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attention_f16_fwd_kernel<TQ>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attention_f16_long_fwd_kernel<TQ>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  done = true;
+static const char* const kAfName[] = {"attention_f16_fwd", "attention_f16_bwd", "attention_f16_bwd_packed"};
+
+// THE dispatch, and the validation of everything but the pointers a call cannot do without.  Pure host arithmetic: no HIP
+// call, no state.  flags: CLIPFS_ATTN_STATS (backward: out, lse and work are there; the forward's plan does not depend on
+// it) and CLIPFS_ATTN_ALIGNED (every pointer the entry point checks is 16-byte aligned).  This family has no fallback:
+// without either the plan refuses.
+static int af_plan(int dir, int batch, int seq, int heads, int causal, int flags, AttnPlan& p) {
+  CLIPFS_REQUIRE(dir >= CLIPFS_ATTN_F16_FWD && dir <= CLIPFS_ATTN_F16_BWD_PACKED, "attention_f16_plan: direction %d unknown",
+                 dir);
+  const bool backward = dir != CLIPFS_ATTN_F16_FWD, packed = dir == CLIPFS_ATTN_F16_BWD_PACKED;
+  const char* what = kAfName[dir];
+  const char* fam = packed ? what : "attention_f16";  // the dense pair's range refusals name the family
+  if (packed) {  // live rows over dense records: the short causal kernels or nothing
+    CLIPFS_REQUIRE(batch > 0 && heads > 0 && seq > 0, "%s: batch %d seq %d heads %d", what, batch, seq, heads);
+    CLIPFS_REQUIRE(causal && seq <= AF_MAXL, "%s: seq %d has no packed kernel (1..%d)", what, seq, AF_MAXL);
+  } else {
+    CLIPFS_REQUIRE(batch > 0 && heads > 0 && seq > 0 && seq <= AF_LONG_MAXL, "%s: seq %d outside 1..%d", fam, seq, AF_LONG_MAXL);
+  }
+  const bool is_long = seq > AF_MAXL;
+  const AfRuns own = is_long ? af_runs(seq, AF_LONG_WAVES) : AfRuns{1, 0};
+  CLIPFS_REQUIRE((long long)batch * heads * own.parts <= 0x7fffffffLL, "%s: batch %d x heads %d too large for seq %d", fam, batch,
+                 heads, seq);
+  CLIPFS_REQUIRE(!backward || (flags & CLIPFS_ATTN_STATS), "%s: null pointer", what);
+  CLIPFS_REQUIRE(flags & CLIPFS_ATTN_ALIGNED, "%s: misaligned pointer", what);
+  p = AttnPlan{};
+  int tok = seq;  // tokens of the other side in LDS at a time
+  unsigned block = (unsigned)af_threads(seq, backward ? 9 : 5);
+  if (is_long) {  // one workgroup per run of own tiles; the other side in equal chunks of at most AF_MAXL tokens
+    p.family = CLIPFS_ATTN_F16_LONG;
+    p.parts = own.parts;
+    p.tiles = own.tiles;
+    p.ctok = tok = 32 * af_runs(seq, AF_MAXL / 32).tiles;
+    block = 64u * own.tiles;
+  } else {
+    p.family = CLIPFS_ATTN_F16_SHORT;
+  }
+  const unsigned grid = (unsigned)(batch * heads * own.parts);
+  p.launches = backward ? 2 : 1;
+  if (backward) {  // the dQ pass (which also writes D_i to `work`), then the dK/dV pass with lse and D of the chunk beside it
+    p.launch[0] = {grid, 1, block, (unsigned)af_lds_bytes(tok, 2, 1)};
+    p.launch[1] = {grid, 1, block, (unsigned)(af_lds_bytes(tok, 2, 2) + 2 * (size_t)((tok + 31) & ~31) * sizeof(float))};
+  } else {
+    p.launch[0] = {grid, 1, block, (unsigned)af_lds_bytes(tok, 1, 1)};
+  }
+  return CLIPFS_OK;
+}
+
+template <typename K>
+static void af_allow_lds(K kernel) {
+  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
 }
 
 template <typename TQ>
-static int af_fwd(const void* qkv, float* out, void* out16, float* lse, int batch, int seq, int heads, int causal,
-                  hipStream_t st) {
-  af_set_attrs<TQ>();
-  if (seq > AF_MAXL) {  // one workgroup per run of query tiles; K / V in chunks of `kc.tiles` tiles
-    const AfRuns own = af_runs(seq, AF_LONG_WAVES), kc = af_runs(seq, AF_MAXL / 32);
-    hipLaunchKernelGGL(attention_f16_long_fwd_kernel<TQ>, dim3(batch * heads * own.parts), dim3(64 * own.tiles),
-                       af_lds_bytes(32 * kc.tiles, 1, 1), st, reinterpret_cast<const TQ*>(qkv), out, lse, seq, heads, causal,
-                       reinterpret_cast<_Float16*>(out16), own.parts, 32 * kc.tiles);
-    return launch_status();
+static int af_run_fwd(const AttnPlan& p, const void* qkv, float* out, void* out16, float* lse, int seq, int heads, int causal,
+                      hipStream_t st) {
+  static bool attr = false;  // per instantiation
+  if (!attr) {
+    af_allow_lds(&attention_f16_fwd_kernel<TQ>);
+    af_allow_lds(&attention_f16_long_fwd_kernel<TQ>);
+    attr = true;
   }
-  hipLaunchKernelGGL(attention_f16_fwd_kernel<TQ>, dim3(batch * heads), dim3(af_threads(seq, 5)), af_lds_bytes(seq, 1, 1), st,
-                     reinterpret_cast<const TQ*>(qkv), out, lse, seq, heads, causal, reinterpret_cast<_Float16*>(out16));
+  const clipfs_attention_launch& l = p.launch[0];
+  const TQ* q = reinterpret_cast<const TQ*>(qkv);
+  _Float16* o16 = reinterpret_cast<_Float16*>(out16);
+  if (p.family == CLIPFS_ATTN_F16_LONG)
+    hipLaunchKernelGGL(attention_f16_long_fwd_kernel<TQ>, dim3(l.grid_x), dim3(l.block), l.lds_bytes, st, q, out, lse, seq, heads,
+                       causal, o16, p.parts, p.ctok);
+  else
+    hipLaunchKernelGGL(attention_f16_fwd_kernel<TQ>, dim3(l.grid_x), dim3(l.block), l.lds_bytes, st, q, out, lse, seq, heads,
+                       causal, o16);
   return launch_status();
 }
 
+// off == NULL: the dense layout; else live rows over dense records (causal, short family: af_plan)
 template <typename TQ, typename TG>
-static int af_bwd(const void* qkv, const void* dout, const float* out, const float* lse, float* dqkv, void* dqkv16,
-                  float* work, int batch, int seq, int heads, int causal, hipStream_t st) {
-  const int threads = af_threads(seq, 9);
-  const size_t lds_q = af_lds_bytes(seq, 2, 1);
-  const size_t lds_kv = af_lds_bytes(seq, 2, 2) + 2 * (size_t)((seq + 31) & ~31) * sizeof(float);
+static int af_run_bwd(const AttnPlan& p, const void* qkv, const void* dout, const float* out, const float* lse, float* dqkv,
+                      void* dqkv16, float* work, const int32_t* off, int seq, int heads, int causal, hipStream_t st) {
   static bool attr = false;  // per instantiation
   if (!attr) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attention_f16_bwd_q_kernel<TQ, TG>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attention_f16_bwd_kv_kernel<TQ, TG>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attention_f16_long_bwd_q_kernel<TQ, TG>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attention_f16_long_bwd_kv_kernel<TQ, TG>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    af_allow_lds(&attention_f16_bwd_q_kernel<TQ, TG>);
+    af_allow_lds(&attention_f16_bwd_kv_kernel<TQ, TG>);
+    af_allow_lds(&attention_f16_bwd_q_kernel<TQ, TG, true, const int32_t*>);
+    af_allow_lds(&attention_f16_bwd_kv_kernel<TQ, TG, true, const int32_t*>);
+    af_allow_lds(&attention_f16_long_bwd_q_kernel<TQ, TG>);
+    af_allow_lds(&attention_f16_long_bwd_kv_kernel<TQ, TG>);
     attr = true;
   }
-  if (seq > AF_MAXL) {  // one workgroup per run of own tiles (dQ: queries, dK/dV: keys); the other side in chunks
-    const AfRuns own = af_runs(seq, AF_LONG_WAVES), oc = af_runs(seq, AF_MAXL / 32);
-    const int ctok = 32 * oc.tiles;
-    const dim3 grid(batch * heads * own.parts), block(64 * own.tiles);
-    hipLaunchKernelGGL((attention_f16_long_bwd_q_kernel<TQ, TG>), grid, block, af_lds_bytes(ctok, 2, 1), st,
-                       reinterpret_cast<const TQ*>(qkv), reinterpret_cast<const TG*>(dout), out, lse, dqkv, work, seq, heads,
-                       causal, reinterpret_cast<_Float16*>(dqkv16), own.parts, ctok);
+  const TQ* q = reinterpret_cast<const TQ*>(qkv);
+  const TG* g = reinterpret_cast<const TG*>(dout);
+  _Float16* d16 = reinterpret_cast<_Float16*>(dqkv16);
+  // the two passes of every family; `tail`: what the family's kernels take after the common arguments
+  auto passes = [&](auto q_kernel, auto kv_kernel, auto... tail) -> int {
+    const clipfs_attention_launch &a = p.launch[0], &b = p.launch[1];
+    hipLaunchKernelGGL(q_kernel, dim3(a.grid_x), dim3(a.block), a.lds_bytes, st, q, g, out, lse, dqkv, work, seq, heads, causal,
+                       d16, tail...);
     CLIPFS_CHECK(launch_status());
-    hipLaunchKernelGGL((attention_f16_long_bwd_kv_kernel<TQ, TG>), grid, block,
-                       af_lds_bytes(ctok, 2, 2) + 2 * (size_t)ctok * sizeof(float), st, reinterpret_cast<const TQ*>(qkv),
-                       reinterpret_cast<const TG*>(dout), lse, work, dqkv, seq, heads, causal,
-                       reinterpret_cast<_Float16*>(dqkv16), own.parts, ctok);
+    hipLaunchKernelGGL(kv_kernel, dim3(b.grid_x), dim3(b.block), b.lds_bytes, st, q, g, lse, work, dqkv, seq, heads, causal, d16,
+                       tail...);
     return launch_status();
-  }
-  hipLaunchKernelGGL((attention_f16_bwd_q_kernel<TQ, TG>), dim3(batch * heads), dim3(threads), lds_q, st,
-                     reinterpret_cast<const TQ*>(qkv), reinterpret_cast<const TG*>(dout), out, lse, dqkv, work, seq, heads, causal,
-                     reinterpret_cast<_Float16*>(dqkv16));
-  CLIPFS_CHECK(launch_status());
-  hipLaunchKernelGGL((attention_f16_bwd_kv_kernel<TQ, TG>), dim3(batch * heads), dim3(threads), lds_kv, st,
-                     reinterpret_cast<const TQ*>(qkv), reinterpret_cast<const TG*>(dout), lse, work, dqkv, seq, heads, causal,
-                     reinterpret_cast<_Float16*>(dqkv16));
-  return launch_status();
+  };
+  if (off)
+    return passes(&attention_f16_bwd_q_kernel<TQ, TG, true, const int32_t*>,
+                  &attention_f16_bwd_kv_kernel<TQ, TG, true, const int32_t*>, off);
+  if (p.family == CLIPFS_ATTN_F16_LONG)
+    return passes(&attention_f16_long_bwd_q_kernel<TQ, TG>, &attention_f16_long_bwd_kv_kernel<TQ, TG>, p.parts, p.ctok);
+  return passes(&attention_f16_bwd_q_kernel<TQ, TG>, &attention_f16_bwd_kv_kernel<TQ, TG>);
 }
 
-// live rows over dense records (causal only): the launch geometry is the dense one for `seq`
-template <typename TQ, typename TG>
-static int af_bwd_packed(const void* qkv, const void* dout, const float* out, const float* lse, float* dqkv, void* dqkv16,
-                         float* work, const int32_t* off, int batch, int seq, int heads, hipStream_t st) {
-  const int threads = af_threads(seq, 9);
-  const size_t lds_q = af_lds_bytes(seq, 2, 1);
-  const size_t lds_kv = af_lds_bytes(seq, 2, 2) + 2 * (size_t)((seq + 31) & ~31) * sizeof(float);
-  static bool attr = false;  // per instantiation
-  if (!attr) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attention_f16_bwd_q_kernel<TQ, TG, true, const int32_t*>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attention_f16_bwd_kv_kernel<TQ, TG, true, const int32_t*>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    attr = true;
+// validate, make the plan, execute it: the dense and the packed backward
+static int af_bwd(int dir, const void* qkv, int qkv_f16, const void* dout, int dout_f16, const float* out, const float* lse,
+                  float* dqkv, void* dqkv16, float* work, const int32_t* off, int batch, int seq, int heads, int causal,
+                  hipStream_t st) {
+  // the fp32 result is optional beside the f16 one
+  CLIPFS_REQUIRE(qkv && dout && (dqkv || dqkv16) && (off || dir == CLIPFS_ATTN_F16_BWD), "%s: null pointer", kAfName[dir]);
+  const bool aligned = aligned16(qkv) && aligned16(dout) && aligned16(out) && aligned16(dqkv) && aligned16(dqkv16);
+  AttnPlan p;
+  CLIPFS_CHECK(af_plan(dir, batch, seq, heads, causal,
+                       (out && lse && work ? CLIPFS_ATTN_STATS : 0) | (aligned ? CLIPFS_ATTN_ALIGNED : 0), p));
+  switch ((qkv_f16 ? 1 : 0) | (dout_f16 ? 2 : 0)) {
+    case 0: return af_run_bwd<float, float>(p, qkv, dout, out, lse, dqkv, dqkv16, work, off, seq, heads, causal, st);
+    case 1: return af_run_bwd<_Float16, float>(p, qkv, dout, out, lse, dqkv, dqkv16, work, off, seq, heads, causal, st);
+    case 2: return af_run_bwd<float, _Float16>(p, qkv, dout, out, lse, dqkv, dqkv16, work, off, seq, heads, causal, st);
+    default: return af_run_bwd<_Float16, _Float16>(p, qkv, dout, out, lse, dqkv, dqkv16, work, off, seq, heads, causal, st);
   }
-  hipLaunchKernelGGL((attention_f16_bwd_q_kernel<TQ, TG, true, const int32_t*>), dim3(batch * heads), dim3(threads), lds_q, st,
-                     reinterpret_cast<const TQ*>(qkv), reinterpret_cast<const TG*>(dout), out, lse, dqkv, work, seq, heads, 1,
-                     reinterpret_cast<_Float16*>(dqkv16), off);
-  CLIPFS_CHECK(launch_status());
-  hipLaunchKernelGGL((attention_f16_bwd_kv_kernel<TQ, TG, true, const int32_t*>), dim3(batch * heads), dim3(threads), lds_kv, st,
-                     reinterpret_cast<const TQ*>(qkv), reinterpret_cast<const TG*>(dout), lse, work, dqkv, seq, heads, 1,
-                     reinterpret_cast<_Float16*>(dqkv16), off);
-  return launch_status();
+}
+
+}  // namespace clipfs
+
+using namespace clipfs;
+
+extern "C" int clipfs_attention_f16_max_seq(void) { return AF_LONG_MAXL; }
+
+extern "C" int clipfs_attention_f16_plan(int direction, int batch, int seq, int heads, int causal, int flags,
+                                         struct clipfs_attention_plan* plan) {
+  CLIPFS_REQUIRE(plan, "attention_f16_plan: null plan");
+  AttnPlan p;
+  CLIPFS_CHECK(af_plan(direction, batch, seq, heads, causal, flags, p));
+  *plan = p;
+  return CLIPFS_OK;
 }
 
 extern "C" int clipfs_attention_f16_fwd(const void* qkv, int qkv_f16, float* out, void* out16, float* lse, int batch, int seq,
                                         int heads, int causal, void* stream) {
-  CLIPFS_CHECK(check_af(qkv, out, batch, seq, heads));
-  CLIPFS_REQUIRE(aligned16(qkv) && aligned16(out), "attention_f16_fwd: misaligned pointer");
-  return qkv_f16 ? af_fwd<_Float16>(qkv, out, out16, lse, batch, seq, heads, causal, (hipStream_t)stream)
-                 : af_fwd<float>(qkv, out, out16, lse, batch, seq, heads, causal, (hipStream_t)stream);
+  CLIPFS_REQUIRE(qkv && out, "attention_f16_fwd: null pointer");
+  AttnPlan p;
+  CLIPFS_CHECK(af_plan(CLIPFS_ATTN_F16_FWD, batch, seq, heads, causal,
+                       (lse ? CLIPFS_ATTN_STATS : 0) | (aligned16(qkv) && aligned16(out) ? CLIPFS_ATTN_ALIGNED : 0), p));
+  return qkv_f16 ? af_run_fwd<_Float16>(p, qkv, out, out16, lse, seq, heads, causal, (hipStream_t)stream)
+                 : af_run_fwd<float>(p, qkv, out, out16, lse, seq, heads, causal, (hipStream_t)stream);
 }
 
 extern "C" int clipfs_attention_f16_bwd(const void* qkv, int qkv_f16, const void* dout, int dout_f16, const float* out,
                                         const float* lse, float* dqkv, void* dqkv16, float* work, int batch, int seq, int heads,
                                         int causal, void* stream) {
-  CLIPFS_CHECK(check_af(qkv, dqkv ? (const void*)dqkv : dqkv16, batch, seq, heads));  // the fp32 result is optional beside the f16 one
-  CLIPFS_REQUIRE(dout && out && lse && work, "attention_f16_bwd: null pointer");
-  CLIPFS_REQUIRE(aligned16(qkv) && aligned16(dout) && aligned16(out) && aligned16(dqkv) && aligned16(dqkv16),
-                 "attention_f16_bwd: misaligned pointer");
-  hipStream_t st = (hipStream_t)stream;
-  if (dout_f16)
-    return qkv_f16 ? af_bwd<_Float16, _Float16>(qkv, dout, out, lse, dqkv, dqkv16, work, batch, seq, heads, causal, st)
-                   : af_bwd<float, _Float16>(qkv, dout, out, lse, dqkv, dqkv16, work, batch, seq, heads, causal, st);
-  return qkv_f16 ? af_bwd<_Float16, float>(qkv, dout, out, lse, dqkv, dqkv16, work, batch, seq, heads, causal, st)
-                 : af_bwd<float, float>(qkv, dout, out, lse, dqkv, dqkv16, work, batch, seq, heads, causal, st);
+  return af_bwd(CLIPFS_ATTN_F16_BWD, qkv, qkv_f16, dout, dout_f16, out, lse, dqkv, dqkv16, work, nullptr, batch, seq, heads, causal,
+                (hipStream_t)stream);
 }
 
 extern "C" int clipfs_attention_f16_bwd_packed_ok(int seq, int causal) {
-  return (causal && seq > 0 && seq <= AF_MAXL) ? 1 : 0;  // the short kernels: one workgroup per (sequence, head)
+  AttnPlan p;
+  return af_plan(CLIPFS_ATTN_F16_BWD_PACKED, 1, seq, 1, causal, CLIPFS_ATTN_STATS | CLIPFS_ATTN_ALIGNED, p) == CLIPFS_OK;
 }
 
 extern "C" int clipfs_attention_f16_bwd_packed(const void* qkv, int qkv_f16, const void* dout, int dout_f16, const float* out,
                                                const float* lse, float* dqkv, void* dqkv16, float* work, const int32_t* off,
                                                int batch, int seq, int heads, void* stream) {
-  CLIPFS_REQUIRE(qkv && dout && out && lse && work && off && (dqkv || dqkv16), "attention_f16_bwd_packed: null pointer");
-  CLIPFS_REQUIRE(batch > 0 && heads > 0 && seq > 0, "attention_f16_bwd_packed: batch %d seq %d heads %d", batch, seq, heads);
-  CLIPFS_REQUIRE(clipfs_attention_f16_bwd_packed_ok(seq, 1), "attention_f16_bwd_packed: seq %d has no packed kernel (1..%d)",
-                 seq, AF_MAXL);
-  CLIPFS_REQUIRE((long long)batch * heads <= 0x7fffffffLL, "attention_f16_bwd_packed: batch %d x heads %d too large", batch,
-                 heads);
-  CLIPFS_REQUIRE(aligned16(qkv) && aligned16(dout) && aligned16(out) && aligned16(dqkv) && aligned16(dqkv16),
-                 "attention_f16_bwd_packed: misaligned pointer");
-  hipStream_t st = (hipStream_t)stream;
-  if (dout_f16)
-    return qkv_f16 ? af_bwd_packed<_Float16, _Float16>(qkv, dout, out, lse, dqkv, dqkv16, work, off, batch, seq, heads, st)
-                   : af_bwd_packed<float, _Float16>(qkv, dout, out, lse, dqkv, dqkv16, work, off, batch, seq, heads, st);
-  return qkv_f16 ? af_bwd_packed<_Float16, float>(qkv, dout, out, lse, dqkv, dqkv16, work, off, batch, seq, heads, st)
-                 : af_bwd_packed<float, float>(qkv, dout, out, lse, dqkv, dqkv16, work, off, batch, seq, heads, st);
+  return af_bwd(CLIPFS_ATTN_F16_BWD_PACKED, qkv, qkv_f16, dout, dout_f16, out, lse, dqkv, dqkv16, work, off, batch, seq, heads, 1,
+                (hipStream_t)stream);
 }

@@ -339,6 +339,25 @@ struct RowView {
   bool saved_packed() const { return map && !gather; }
 };
 
+// Which attention a block runs: decided here alone, read by fwd_block, bwd_attn_half and pack_ok.
+enum class AttnRoute {
+  Fp32Dense,     // clipfs_attention_fwd / _bwd
+  Fp32Packed,    // live rows over dense records: clipfs_attention_bwd_packed
+  Fp32PackedIo,  // live rows over packed records: clipfs_attention_fwd_packed / _bwd_packed_io
+  F16Dense,      // fp16 storage mode: clipfs_attention_f16_fwd / _bwd
+  F16Packed,     // ... live rows over dense records: clipfs_attention_f16_bwd_packed
+  Fp32Fallback,  // fp16 storage mode past the f16 kernels' bound: the dense fp32 pair (never packed: pack_ok)
+};
+static AttnRoute attn_route(const clipfs_tower* t, bool packed, bool saved_packed) {
+  if (t->weight_format == 2) {  // (the live-row forward is exact fp32 only, pack_fwd_ok: no packed records here)
+    if (!f16_attention(t)) return AttnRoute::Fp32Fallback;
+    return packed ? AttnRoute::F16Packed : AttnRoute::F16Dense;
+  }
+  if (saved_packed) return AttnRoute::Fp32PackedIo;
+  return packed ? AttnRoute::Fp32Packed : AttnRoute::Fp32Dense;
+}
+static AttnRoute attn_route(const clipfs_tower* t, const RowView& v) { return attn_route(t, v.packed(), v.saved_packed()); }
+
 // One call's state, built by begin_pass
 struct Pass {
   const clipfs_tower* t;
@@ -609,13 +628,18 @@ static int fwd_block(const Pass& p, int l, float* x, const int32_t* rows, float*
                            .lora = {ad.qkv_mask ? t_qkv : nullptr, b.lora_b_qkv, r, 3, d, t->lora_scale},
                            .a16_ready = h16, .c16_only = q16 ? (void*)qkv : nullptr}, st));
   const void* att16 = nullptr;
-  if (v.packed()) {
-    CLIPFS_CHECK(clipfs_attention_fwd_packed(qkv, att, lse, v.off, p.batch, t->seq, t->heads, st));
-  } else if (f16_attention(t)) {
-    CLIPFS_CHECK(clipfs_attention_f16_fwd(qkv, q16, att, h16, lse, p.batch, t->seq, t->heads, t->causal, st));
-    att16 = h16;
-  } else {
-    CLIPFS_CHECK(clipfs_attention_fwd(qkv, att, lse, p.batch, t->seq, t->heads, t->causal, st));
+  switch (attn_route(t, v)) {
+    case AttnRoute::Fp32Packed:
+    case AttnRoute::Fp32PackedIo:
+    case AttnRoute::F16Packed:  // every live-row forward (exact fp32 only: pack_fwd_ok)
+      CLIPFS_CHECK(clipfs_attention_fwd_packed(qkv, att, lse, v.off, p.batch, t->seq, t->heads, st));
+      break;
+    case AttnRoute::F16Dense:
+      CLIPFS_CHECK(clipfs_attention_f16_fwd(qkv, q16, att, h16, lse, p.batch, t->seq, t->heads, t->causal, st));
+      att16 = h16;
+      break;
+    default:  // Fp32Dense, Fp32Fallback
+      CLIPFS_CHECK(clipfs_attention_fwd(qkv, att, lse, p.batch, t->seq, t->heads, t->causal, st));
   }
   if (rows && l == t->layers - 1) return fwd_tail(p, b, sv, att, x_in, rows, x);
   if (ad.o)  // (packed rows: no dropout here, pack_fwd_ok)
@@ -822,23 +846,29 @@ static int bwd_attn_half(const Pass& p, int l, const float* sv, float* dx, void*
   // attention backward does not write the fp32 tensor at all (404 MB per ViT-L/14 block at 128 images)
   const bool f16a = f16_attention(t);
   const bool dy16 = f16a && p.dqkv16 && (!qkv_mask || clipfs_lora_bwd_f16dy_ok(d, d, r, 3));
-  if (v.saved_packed())  // packed q/k/v and O; packed dO and dqkv either way
-    CLIPFS_CHECK(clipfs_attention_bwd_packed_io(sv + SL.qkv, datt, sv + SL.att, sv + SL.lse, dqkv, v.off, p.batch, t->seq,
-                                                t->heads, p.st));
-  else if (v.packed() && f16a)  // fp16 storage mode: the dense flags, dqkv16 at the packed rows of its slot
-    CLIPFS_CHECK(clipfs_attention_f16_bwd_packed(sv + SL.qkv, qkv_f16(t), datt, datt_f16(t, b, h16) ? 1 : 0, sv + SL.att,
-                                                 sv + SL.lse, dy16 ? nullptr : dqkv, p.dqkv16, dh, v.off, p.batch, t->seq,
-                                                 t->heads, p.st));
-  else if (v.packed())
-    CLIPFS_CHECK(clipfs_attention_bwd_packed(sv + SL.qkv, datt, sv + SL.att, sv + SL.lse, dqkv, v.off, p.batch, t->seq,
-                                             t->heads, p.st));
-  else if (f16a)
-    CLIPFS_CHECK(clipfs_attention_f16_bwd(sv + SL.qkv, qkv_f16(t), datt, datt_f16(t, b, h16) ? 1 : 0, sv + SL.att,
-                                          sv + SL.lse, dy16 ? nullptr : dqkv, p.dqkv16, dh, p.batch, t->seq, t->heads,
-                                          t->causal, p.st));
-  else
-    CLIPFS_CHECK(clipfs_attention_bwd(sv + SL.qkv, datt, sv + SL.att, sv + SL.lse, dqkv, dh, p.batch, t->seq, t->heads,
-                                      t->causal, p.st));
+  switch (attn_route(t, v)) {
+    case AttnRoute::Fp32PackedIo:  // packed q/k/v and O; packed dO and dqkv either way
+      CLIPFS_CHECK(clipfs_attention_bwd_packed_io(sv + SL.qkv, datt, sv + SL.att, sv + SL.lse, dqkv, v.off, p.batch, t->seq,
+                                                  t->heads, p.st));
+      break;
+    case AttnRoute::F16Packed:  // fp16 storage mode: the dense flags, dqkv16 at the packed rows of its slot
+      CLIPFS_CHECK(clipfs_attention_f16_bwd_packed(sv + SL.qkv, qkv_f16(t), datt, datt_f16(t, b, h16) ? 1 : 0, sv + SL.att,
+                                                   sv + SL.lse, dy16 ? nullptr : dqkv, p.dqkv16, dh, v.off, p.batch, t->seq,
+                                                   t->heads, p.st));
+      break;
+    case AttnRoute::Fp32Packed:
+      CLIPFS_CHECK(clipfs_attention_bwd_packed(sv + SL.qkv, datt, sv + SL.att, sv + SL.lse, dqkv, v.off, p.batch, t->seq,
+                                               t->heads, p.st));
+      break;
+    case AttnRoute::F16Dense:
+      CLIPFS_CHECK(clipfs_attention_f16_bwd(sv + SL.qkv, qkv_f16(t), datt, datt_f16(t, b, h16) ? 1 : 0, sv + SL.att,
+                                            sv + SL.lse, dy16 ? nullptr : dqkv, p.dqkv16, dh, p.batch, t->seq, t->heads,
+                                            t->causal, p.st));
+      break;
+    default:  // Fp32Dense, Fp32Fallback
+      CLIPFS_CHECK(clipfs_attention_bwd(sv + SL.qkv, datt, sv + SL.att, sv + SL.lse, dqkv, dh, p.batch, t->seq, t->heads,
+                                        t->causal, p.st));
+  }
   CLIPFS_CHECK(bias_sum(p, dqkv, n, 3 * d, d, b.g_b_q, b.g_b_k, b.g_b_v));
   const bool need_dx = needs_dx(t, l, stop_at_input);
   // dh1 (the gradient wrt LayerNorm 1's output) is also needed for ln_1's bias gradient, even where dx is not
@@ -1009,14 +1039,18 @@ static bool pack_ok(const clipfs_tower* t, int batch, int R) {
   // MLP adapters keep the dense rows in both directions: their down-projections and backward products are not carried
   // through the row map (the masks would have to be drawn at the full-layout row)
   if (tower_has_mlp_lora(t)) return false;
-  if (t->weight_format == 2) {
-    if (!f16_attention(t) || !clipfs_attention_f16_bwd_packed_ok(t->seq, 1)) return false;
-    for (int l = t->grad_lo; l < t->layers; ++l) {
-      const clipfs_block& b = t->blocks[l];
-      if (!b.w_qkv_t_p || !b.w_o_t_p || !b.w_fc_t_p || !b.w_pr_t_p) return false;
-    }
-  } else if (!clipfs_attention_bwd_packed_ok(t->seq, 1)) {
-    return false;
+  switch (attn_route(t, true, false)) {  // of the live rows over dense records: is there a kernel for it?
+    case AttnRoute::F16Packed:
+      if (!clipfs_attention_f16_bwd_packed_ok(t->seq, 1)) return false;
+      for (int l = t->grad_lo; l < t->layers; ++l) {
+        const clipfs_block& b = t->blocks[l];
+        if (!b.w_qkv_t_p || !b.w_o_t_p || !b.w_fc_t_p || !b.w_pr_t_p) return false;
+      }
+      break;
+    case AttnRoute::Fp32Packed:
+      if (!clipfs_attention_bwd_packed_ok(t->seq, 1)) return false;
+      break;
+    default: return false;  // Fp32Fallback
   }
   if (R < batch || 2 * (size_t)R > (size_t)M || (d % 8) != 0) return false;
   if (!pack_dropout_ok(t)) return false;

@@ -45,8 +45,9 @@ def test_max_seq_is_past_vit_l14_336():
 def test_attention_f16_long_fwd(batch, seq, heads, causal):
     """Forward vs an fp64 reference on the SAME f16-rounded q, k, v: 2e-3 absolute on the output, 1e-3 on the log-sum-exp;
     qkv passed as an f16 tensor gives the same bits."""
-    from clipfs import ops
+    from clipfs import _lib, ops
     seq = _seq(seq)
+    assert _lib.attention_f16_plan("fwd", batch, seq, heads, causal)["family"] == "f16_long"
     g = torch.Generator().manual_seed(seq)
     qkv = torch.randn(batch * seq, 3 * heads * 64, generator=g).half().float().cuda()
     out, lse = ops.attention_f16_fwd(qkv, batch, seq, heads, causal)
@@ -78,8 +79,9 @@ def test_attention_f16_long_bwd(batch, seq, heads, causal):
     """Backward vs fp64 autograd on the same f16-rounded inputs: 1e-2 of the largest gradient entry.  The four storage
     combinations (qkv fp32 / f16 x dO fp32 / f16) give the same bits, and the f16-only result (no fp32 dqkv) is the
     rounded fp32 result."""
-    from clipfs import ops
+    from clipfs import _lib, ops
     seq = _seq(seq)
+    assert _lib.attention_f16_plan("bwd", batch, seq, heads, causal)["family"] == "f16_long"
     g = torch.Generator().manual_seed(seq + 7)
     qkv = torch.randn(batch * seq, 3 * heads * 64, generator=g).half().float().cuda()
     dout = torch.randn(batch * seq, heads * 64, generator=g).half().float().cuda()
@@ -104,8 +106,10 @@ def test_attention_f16_long_bwd(batch, seq, heads, causal):
 def test_reproducible_and_heads_independent():
     """Two calls give equal bits, and head (b, h) of a (3, 577, 2) call equals the same head computed alone as a (1, 577, 1)
     call bit for bit: a wrong run, chunk or grid index mixes heads or tokens."""
-    from clipfs import ops
+    from clipfs import _lib, ops
     batch, seq, heads = 3, 577, 2
+    for d, b, h in (("fwd", batch, heads), ("bwd", batch, heads), ("fwd", 1, 1), ("bwd", 1, 1)):
+        assert _lib.attention_f16_plan(d, b, seq, h, False)["family"] == "f16_long"
     g = torch.Generator().manual_seed(seq + 13)
     qkv = torch.randn(batch * seq, 3 * heads * 64, generator=g).half().float().cuda()
     dout = torch.randn(batch * seq, heads * 64, generator=g).half().float().cuda()

@@ -60,7 +60,9 @@ def test_rows_under_a_cached_aid(aid):
 def test_table_covers_what_it_is_there_for():
     from clipfs import _lib
     plans = [c.plan for c in TABLE if not isinstance(c.plan, str)]
-    assert {p["family"] for p in plans} == set(_lib.ATTN_FAMILIES)
+    # every family clipfs_attention_plan can return: the first seven names (the last two are clipfs_attention_f16_plan's)
+    assert _lib.ATTN_FAMILIES[7:] == ("f16_short", "f16_long")
+    assert {p["family"] for p in plans} == set(_lib.ATTN_FAMILIES[:7])
     assert {p["nt"] for p in plans if p["family"] == "mfma16"} == {1, 2, 4, 5, 6}
     assert {p["lmax"] for p in plans if p["family"] == "recompute"} == {64, 80, 96}
     assert all(l[3] <= LDS_LIMIT for p in plans for l in p["launches"]), "every dynamic LDS size fits the 160 KiB of a CU"

@@ -678,7 +678,8 @@ def test_attention_f16_fwd(batch, seq, heads, causal):
     """fp16-mode MFMA attention forward vs an fp64 reference on the SAME f16-rounded q, k, v: what remains is the f16
     rounding of the probabilities (2^-11 relative per term) and fp32 accumulation: 2e-3 absolute on outputs of
     unit scale, 1e-3 on the log-sum-exp."""
-    from clipfs import ops
+    from clipfs import _lib, ops
+    assert _lib.attention_f16_plan("fwd", batch, seq, heads, causal)["family"] == "f16_short"
     g = torch.Generator().manual_seed(seq)
     qkv = torch.randn(batch * seq, 3 * heads * 64, generator=g).half().float().cuda()
     out, lse = ops.attention_f16_fwd(qkv, batch, seq, heads, causal)
@@ -697,7 +698,8 @@ def test_attention_f16_bwd(batch, seq, heads, causal):
     """fp16-mode MFMA attention backward vs fp64 autograd on the same f16-rounded inputs.  P, dS and the staged
     operands are rounded to f16 (2^-11 relative each), accumulation is fp32: 1e-2 relative to the largest gradient
     entry, stated here (the exact-fp32 kernels are held to 1e-5 in test_attention)."""
-    from clipfs import ops
+    from clipfs import _lib, ops
+    assert _lib.attention_f16_plan("bwd", batch, seq, heads, causal)["family"] == "f16_short"
     g = torch.Generator().manual_seed(seq + 7)
     qkv = torch.randn(batch * seq, 3 * heads * 64, generator=g).half().float().cuda()
     dout = torch.randn(batch * seq, heads * 64, generator=g).half().float().cuda()

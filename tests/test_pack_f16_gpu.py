@@ -67,6 +67,9 @@ def _attention_pair(dev, seq, L, qkv_f16, dout_f16, want_fp32=True):
     lib = _lib.load()
     d = 64 * H
     qkv, dout, live, ref, off = _att_inputs(seq, L)
+    # the packed backward is the short backward of this length on the live rows, the dense records its forward's
+    packed, dense = (_lib.attention_f16_plan(d, B, seq, H, True) for d in ("bwd_packed", "bwd"))
+    assert packed == dense and packed["family"] == _lib.attention_f16_plan("fwd", B, seq, H, True)["family"] == "f16_short"
     qkv_d = qkv.to(dev)
     out, lse = ops.attention_f16_fwd(qkv_d, B, seq, H, True)  # the dense forward's records
     q_in = qkv_d.half() if qkv_f16 else qkv_d
