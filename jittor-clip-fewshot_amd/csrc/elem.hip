@@ -336,24 +336,15 @@ __device__ __forceinline__ void cross_entropy_rows(const float* __restrict__ log
     }
   }
 }
+// state = a scaler record (clipfs.h: "loss scaling") whose loss scale is folded into the gradient scale, or NULL; the
+// per-row losses and hit flags do not depend on it
 __global__ __launch_bounds__(256) void cross_entropy_kernel(const float* __restrict__ logits,
                                                             const int64_t* __restrict__ target,
                                                             float* __restrict__ dlogits, float* __restrict__ loss_rows,
                                                             int32_t* __restrict__ correct_rows, int rows, int classes,
-                                                            float grad_scale) {
-  cross_entropy_rows(logits, target, dlogits, loss_rows, correct_rows, rows, classes, grad_scale);
-}
-// the same with the loss scale of a scaler record (clipfs.h: "loss scaling") folded into the gradient scale; the
-// per-row losses and hit flags are those of the plain kernel
-__global__ __launch_bounds__(256) void cross_entropy_scaled_kernel(const float* __restrict__ logits,
-                                                                   const int64_t* __restrict__ target,
-                                                                   float* __restrict__ dlogits,
-                                                                   float* __restrict__ loss_rows,
-                                                                   int32_t* __restrict__ correct_rows, int rows,
-                                                                   int classes, float grad_scale,
-                                                                   const float* __restrict__ state) {
+                                                            float grad_scale, const float* __restrict__ state) {
   cross_entropy_rows(logits, target, dlogits, loss_rows, correct_rows, rows, classes,
-                     grad_scale * state[CLIPFS_SCALER_SCALE]);
+                     state ? grad_scale * state[CLIPFS_SCALER_SCALE] : grad_scale);
 }
 
 // deterministic final reduction of the per-row losses / hit flags (single wave, fixed order)
@@ -545,13 +536,27 @@ __device__ __forceinline__ void adamw_element(float* __restrict__ p, const float
   m[i] = mi;
   v[i] = vi;
 }
+// The one AdamW kernel, with three optional records (each NULL or given, uniform over the launch): bias corrections,
+// gradient scale and the skip decision from the loss-scaling record sf when there is one (below), the gradient
+// multiplier from the clip record cs when there is one, and the EMA shadow updated from the parameter just computed.
+// With all three NULL it is the plain update at the arguments' inv_sqrt_bc2 / step_size / grad_scale.
 __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                     float* __restrict__ m, float* __restrict__ v, size_t n, float lr,
                                                     float b1, float b2, float eps, float wd, float inv_sqrt_bc2,
-                                                    float step_size, float grad_scale) {
+                                                    float step_size, float grad_scale,
+                                                    const float* __restrict__ sf, const float* __restrict__ cs,
+                                                    float* __restrict__ shadow, float decay, float one_minus_decay) {
   const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
+  if (sf) {
+    if (reinterpret_cast<const int32_t*>(sf)[CLIPFS_SCALER_SKIP] != 0) return;
+    inv_sqrt_bc2 = sf[CLIPFS_SCALER_INV_SQRT_BC2];
+    step_size = sf[CLIPFS_SCALER_STEP_SIZE];
+    grad_scale = sf[CLIPFS_SCALER_INV_SCALE];
+  }
+  if (cs) grad_scale = cs[CLIPFS_CLIP_MULT];
   adamw_element(p, g, m, v, i, lr, b1, b2, eps, wd, inv_sqrt_bc2, step_size, grad_scale);
+  if (shadow) shadow[i] = fmaf(decay, shadow[i], one_minus_decay * p[i]);
 }
 
 // ---- loss scaling for f16 gradient storage: the scaler record is CLIPFS_SCALER_WORDS 32-bit words (clipfs.h) ----
@@ -606,17 +611,6 @@ __global__ __launch_bounds__(64) void scaler_decide_kernel(float* __restrict__ s
     si[CLIPFS_SCALER_TRACKER] = 0;
   }
   si[CLIPFS_SCALER_FOUND] = 0;
-}
-
-// adamw_kernel with the gradient scale, the bias corrections and the skip decision of the scaler record
-__global__ __launch_bounds__(256) void adamw_scaled_kernel(float* __restrict__ p, const float* __restrict__ g,
-                                                           float* __restrict__ m, float* __restrict__ v, size_t n,
-                                                           float lr, float b1, float b2, float eps, float wd,
-                                                           const float* __restrict__ sf) {
-  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n || reinterpret_cast<const int32_t*>(sf)[CLIPFS_SCALER_SKIP] != 0) return;
-  adamw_element(p, g, m, v, i, lr, b1, b2, eps, wd, sf[CLIPFS_SCALER_INV_SQRT_BC2], sf[CLIPFS_SCALER_STEP_SIZE],
-                sf[CLIPFS_SCALER_INV_SCALE]);
 }
 
 // ---- gradient clipping by global norm + EMA shadow (clipfs.h: "optimiser step options") ----
@@ -698,28 +692,6 @@ __global__ __launch_bounds__(256) void clip_decide_kernel(const double* __restri
   cs[CLIPFS_CLIP_NORM] = norm;
   cs[CLIPFS_CLIP_COEF] = coef;
   cs[CLIPFS_CLIP_MULT] = inv_scale * coef;
-}
-
-// adamw_kernel / adamw_scaled_kernel with the optional records: bias corrections and the skip decision from the
-// loss-scaling record when there is one, the gradient multiplier from the clip record when there is one, and the EMA
-// shadow updated from the parameter just computed.
-__global__ __launch_bounds__(256) void adamw_ext_kernel(float* __restrict__ p, const float* __restrict__ g,
-                                                        float* __restrict__ m, float* __restrict__ v, size_t n, float lr,
-                                                        float b1, float b2, float eps, float wd, float inv_sqrt_bc2,
-                                                        float step_size, float grad_scale,
-                                                        const float* __restrict__ sf, const float* __restrict__ cs,
-                                                        float* __restrict__ shadow, float decay, float one_minus_decay) {
-  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  if (sf) {
-    if (reinterpret_cast<const int32_t*>(sf)[CLIPFS_SCALER_SKIP] != 0) return;
-    inv_sqrt_bc2 = sf[CLIPFS_SCALER_INV_SQRT_BC2];
-    step_size = sf[CLIPFS_SCALER_STEP_SIZE];
-    grad_scale = sf[CLIPFS_SCALER_INV_SCALE];
-  }
-  if (cs) grad_scale = cs[CLIPFS_CLIP_MULT];
-  adamw_element(p, g, m, v, i, lr, b1, b2, eps, wd, inv_sqrt_bc2, step_size, grad_scale);
-  if (shadow) shadow[i] = fmaf(decay, shadow[i], one_minus_decay * p[i]);
 }
 
 // C[m,n] = alpha * sum_k A[m*sam + k*sak] * B[k*sbk + n*sbn]   (tiny products whose reduction dim is
@@ -1126,18 +1098,27 @@ extern "C" int clipfs_class_mean_bwd(const float* emb, const float* dout, float*
   return launch_status();
 }
 
-extern "C" int clipfs_cross_entropy(const float* logits, const int64_t* target, float* dlogits, float* loss_rows,
-                                    float* loss_sum, int32_t* correct, int rows, int classes, float grad_scale,
-                                    void* stream) {
-  CLIPFS_REQUIRE(logits && target && loss_rows && loss_sum && rows > 0 && classes > 0, "cross_entropy: bad args");
+// The two launches of both cross-entropy entry points: the rows kernel, then the fixed-order reduction.  scaler_state
+// = NULL for the unscaled gradient.
+static int launch_cross_entropy(const float* logits, const int64_t* target, float* dlogits, float* loss_rows,
+                                float* loss_sum, int32_t* correct, int rows, int classes, float grad_scale,
+                                const float* scaler_state, void* stream) {
   // loss_rows is [2 * rows]: per-row losses, then per-row hit flags (int32) when correct != NULL
   int32_t* flags = correct ? reinterpret_cast<int32_t*>(loss_rows + rows) : nullptr;
   hipLaunchKernelGGL(cross_entropy_kernel, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, logits, target,
-                     dlogits, loss_rows, flags, rows, classes, grad_scale);
+                     dlogits, loss_rows, flags, rows, classes, grad_scale, scaler_state);
   CLIPFS_CHECK(launch_status());
   hipLaunchKernelGGL(ce_finish_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, loss_rows, flags, loss_sum, correct,
                      rows);
   return launch_status();
+}
+
+extern "C" int clipfs_cross_entropy(const float* logits, const int64_t* target, float* dlogits, float* loss_rows,
+                                    float* loss_sum, int32_t* correct, int rows, int classes, float grad_scale,
+                                    void* stream) {
+  CLIPFS_REQUIRE(logits && target && loss_rows && loss_sum && rows > 0 && classes > 0, "cross_entropy: bad args");
+  return launch_cross_entropy(logits, target, dlogits, loss_rows, loss_sum, correct, rows, classes, grad_scale, nullptr,
+                              stream);
 }
 
 extern "C" int clipfs_cross_entropy_scaled(const float* logits, const int64_t* target, float* dlogits, float* loss_rows,
@@ -1145,13 +1126,8 @@ extern "C" int clipfs_cross_entropy_scaled(const float* logits, const int64_t* t
                                            const float* scaler_state, void* stream) {
   CLIPFS_REQUIRE(logits && target && loss_rows && loss_sum && rows > 0 && classes > 0, "cross_entropy_scaled: bad args");
   CLIPFS_REQUIRE(scaler_state && aligned16(scaler_state), "cross_entropy_scaled: null or misaligned scaler state");
-  int32_t* flags = correct ? reinterpret_cast<int32_t*>(loss_rows + rows) : nullptr;
-  hipLaunchKernelGGL(cross_entropy_scaled_kernel, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, logits, target,
-                     dlogits, loss_rows, flags, rows, classes, grad_scale, scaler_state);
-  CLIPFS_CHECK(launch_status());
-  hipLaunchKernelGGL(ce_finish_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, loss_rows, flags, loss_sum, correct,
-                     rows);
-  return launch_status();
+  return launch_cross_entropy(logits, target, dlogits, loss_rows, loss_sum, correct, rows, classes, grad_scale,
+                              scaler_state, stream);
 }
 
 extern "C" int clipfs_topk(const float* logits, int32_t* labels, int rows, int classes, int k, void* stream) {
@@ -1188,14 +1164,30 @@ extern "C" int clipfs_colsum(const float* x, const float* y, float* out, int row
   return launch_status();
 }
 
+// The one AdamW launch behind clipfs_adamw / clipfs_adamw_scaled / clipfs_adamw_ext (each checks its own arguments
+// first).  Without a scaler record the bias corrections come from `step` (>= 1) here; with one the kernel reads them
+// from the record and neither `step` nor `grad_scale` is used.
+static int launch_adamw(float* p, const float* g, float* m, float* v, size_t n, int step, float lr, float beta1,
+                        float beta2, float eps, float weight_decay, float grad_scale, const float* scaler_state,
+                        const float* clip_state, float* ema_shadow, float ema_decay, void* stream) {
+  float inv_sqrt_bc2 = 0.f, step_size = 0.f;  // read from the record when there is one
+  if (!scaler_state) {
+    const double bc1 = 1.0 - pow((double)beta1, step);
+    const double bc2 = 1.0 - pow((double)beta2, step);
+    inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2));
+    step_size = (float)((double)lr / bc1);
+  }
+  hipLaunchKernelGGL(adamw_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, lr,
+                     beta1, beta2, eps, weight_decay, inv_sqrt_bc2, step_size, grad_scale, scaler_state, clip_state,
+                     ema_shadow, ema_decay, 1.f - ema_decay);
+  return launch_status();
+}
+
 extern "C" int clipfs_adamw(float* p, const float* g, float* m, float* v, size_t n, int step, float lr, float beta1,
                             float beta2, float eps, float weight_decay, float grad_scale, void* stream) {
   CLIPFS_REQUIRE(p && g && m && v && n > 0 && step >= 1, "adamw: bad args");
-  const double bc1 = 1.0 - pow((double)beta1, step);
-  const double bc2 = 1.0 - pow((double)beta2, step);
-  hipLaunchKernelGGL(adamw_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, lr,
-                     beta1, beta2, eps, weight_decay, (float)(1.0 / sqrt(bc2)), (float)((double)lr / bc1), grad_scale);
-  return launch_status();
+  return launch_adamw(p, g, m, v, n, step, lr, beta1, beta2, eps, weight_decay, grad_scale, nullptr, nullptr, nullptr, 0.f,
+                      stream);
 }
 
 static inline bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
@@ -1228,9 +1220,8 @@ extern "C" int clipfs_adamw_scaled(float* p, const float* g, float* m, float* v,
   CLIPFS_REQUIRE(p && g && m && v && aligned4(p) && aligned4(g) && aligned4(m) && aligned4(v),
                  "adamw_scaled: null or misaligned pointer");
   CLIPFS_REQUIRE(n > 0, "adamw_scaled: n = 0");
-  hipLaunchKernelGGL(adamw_scaled_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, p, g, m,
-                     v, n, lr, beta1, beta2, eps, weight_decay, scaler_state);
-  return launch_status();
+  return launch_adamw(p, g, m, v, n, 0, lr, beta1, beta2, eps, weight_decay, 1.f, scaler_state, nullptr, nullptr, 0.f,
+                      stream);
 }
 
 extern "C" size_t clipfs_grad_sumsq_work_doubles(size_t n) { return sumsq_chunks(n); }
@@ -1271,17 +1262,8 @@ extern "C" int clipfs_adamw_ext(float* p, const float* g, float* m, float* v, si
                  (double)ema_decay);
   CLIPFS_REQUIRE(n > 0, "adamw_ext: n = 0");
   CLIPFS_REQUIRE(scaler_state || step >= 1, "adamw_ext: step %d must be >= 1 without a scaler state", step);
-  float inv_sqrt_bc2 = 0.f, step_size = 0.f;  // read from the record when there is one
-  if (!scaler_state) {
-    const double bc1 = 1.0 - pow((double)beta1, step);
-    const double bc2 = 1.0 - pow((double)beta2, step);
-    inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2));
-    step_size = (float)((double)lr / bc1);
-  }
-  hipLaunchKernelGGL(adamw_ext_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n,
-                     lr, beta1, beta2, eps, weight_decay, inv_sqrt_bc2, step_size, grad_scale, scaler_state, clip_state,
-                     ema_shadow, ema_decay, 1.f - ema_decay);
-  return launch_status();
+  return launch_adamw(p, g, m, v, n, step, lr, beta1, beta2, eps, weight_decay, grad_scale, scaler_state, clip_state,
+                      ema_shadow, ema_decay, stream);
 }
 
 extern "C" int clipfs_l1_loss(const float* a, const float* b, size_t n, float* loss, float* da, float grad_scale,

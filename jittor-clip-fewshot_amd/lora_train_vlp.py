@@ -769,9 +769,27 @@ def _check_step_options(max_grad_norm, ema_decay):
         raise ValueError(f"ema_decay must be None or lie in (0, 1) as an fp32 number, not {ema_decay!r}")
 
 
-class OptimizerStepOptions:
-    """What ``LoRATrainer`` and the fused ``Stage2Trainer`` share around their one AdamW launch over ``flat``: gradient
-    clipping by global norm, an EMA shadow of the parameters, and handing the whole optimiser state out and back.
+class FlatStepTrainer:
+    """Base of the trainers that step ONE flat buffer (``LoRATrainer``, ``slow_pace.FusedStage2Trainer``): everything
+    around the forward / backward that does not depend on the objective.
+
+    Contract.  A subclass's ``__init__`` (explicit arguments, no ``**kwargs``) first validates with ``_check_loss_scale``
+    and ``_check_step_options`` -- before it touches the model -- then sets ``self.model`` (a model with an ``engine``),
+    builds ``self.flat`` (``FlatTrainables``) and, if it has one, ``self.sched`` (a scheduler with ``step()`` and
+    ``base_lr`` / ``T_max`` / ``eta_min`` / ``last_epoch``), and then calls ``_init_flat_step`` once, with its
+    collective counts per step (class-sharded text tower, replicated).  It implements ``_after_update`` (what
+    follows the AdamW launch) and its own ``forward_backward`` / ``step``, which call ``_refuse_sharded_dropout``.
+
+    The base then guarantees: the hyper-parameters ``lr`` / ``wd`` / ``betas`` / ``eps`` and the call counter ``t``; the
+    data-parallel attributes ``pg`` / ``rank`` / ``world`` / ``live`` / ``shard_text`` / ``collectives_per_step``, the
+    exchange buffers, the side stream and the collective timers (``time_collectives``, ``collective_times_ms``);
+    ``overlap_towers`` and ``last_plan``; the loss-scaling state (``loss_scaling``, ``scale_state``, ``_scaler_rule``) with
+    its host views ``loss_scale_value`` / ``skipped_steps`` / ``optimizer_steps``; the clipping and EMA state below;
+    ``optimizer_step`` (shadow refusal, all-reduce when ``live``, ``t += 1``, ``_apply_update``, ``_after_update``); and
+    ``state_dict`` / ``load_state_dict`` over all of it.
+
+    Loss scaling (``loss_scale`` ...): see ``LoRATrainer``.  ``scale_state`` is the device record (clipfs.h
+    CLIPFS_SCALER_*), None = off; ``_scaler_rule`` the scaler's constants (growth, backoff, interval).
 
     ``max_grad_norm``: ``torch.nn.utils.clip_grad_norm_``'s rule on the UNSCALED gradient, on the device: after the
     all-reduce (every rank forms the same norm from the same bytes: no new collective) and after the scaler's decision,
@@ -787,8 +805,34 @@ class OptimizerStepOptions:
 
     With both None the step is the launches it was without them."""
 
-    def _init_step_options(self, max_grad_norm, ema_decay):
+    def _init_flat_step(self, lr, weight_decay, betas, eps, process_group, shard_text, collectives, loss_scale,
+                        init_scale, growth_factor, backoff_factor, growth_interval, max_grad_norm, ema_decay):
+        """Everything of the contract above; called once, after ``self.model`` and ``self.flat`` are in place.
+        ``collectives``: the subclass's collectives per step, (class-sharded text tower, replicated)."""
+        from clipfs import dist as D
         dev = self.flat.params.device
+        self.lr, self.wd, self.betas, self.eps = lr, weight_decay, betas, eps
+        self.t = 0
+        self.pg = process_group
+        self.rank, self.world = D.world_info(process_group)
+        self.shard_text = shard_text and self.live
+        self.collectives_per_step = collectives[0 if self.shard_text else 1] if self.live else 0
+        self.overlap_towers = True  # text tower on a side HIP stream (set False to serialise, e.g. for per-kernel timing)
+        # class-sharded text tower: fixed exchange buffers (allocated on first use, never re-zeroed: padding rows of
+        # the send block / the gradient table are written by nobody and stay zero)
+        self._xbuf = {}
+        self.last_plan = None  # gradient floors of the last forward_backward: {"text": lo or None, "vision": lo or None}
+        self.time_collectives = False      # bench: bracket every collective with HIP events on the launch stream
+        self._coll_events = []
+        # loss scaling: the device record (clipfs.h CLIPFS_SCALER_*) and the scaler's constants; None = off
+        self.loss_scaling = _check_loss_scale(loss_scale, init_scale, growth_factor, backoff_factor, growth_interval)
+        self.scale_state = None
+        if self.loss_scaling == "dynamic":
+            self._scaler_rule = (float(growth_factor), float(backoff_factor), int(growth_interval))
+            self.scale_state = ops.new_scaler_state(float(init_scale), dev)
+        elif self.loss_scaling == "static":
+            self._scaler_rule = (1.0, 1.0, 0)  # never grows, never backs off; still skips a non-finite step
+            self.scale_state = ops.new_scaler_state(float(loss_scale), dev)
         self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
         self.ema_decay = None if ema_decay is None else float(ema_decay)
         self.clip_state = self._sumsq_work = self.ema_shadow = self._ema_backup = None
@@ -798,8 +842,40 @@ class OptimizerStepOptions:
         if self.ema_decay is not None:
             self.ema_shadow = self.flat.params.clone()
 
+    @property
+    def live(self) -> bool:
+        """Whether the collectives run: more than one rank, or ``clipfs.dist.FORCE_COLLECTIVES`` (read at each use)."""
+        from clipfs import dist as D
+        return self.world > 1 or D.FORCE_COLLECTIVES
+
+    def _refuse_sharded_dropout(self):
+        """Every ``forward_backward`` calls this before it launches anything."""
+        eng = self.model.engine
+        if self.shard_text and eng.trim_text and self.model.training and eng.txt.lora_dropout_rate() > 0:
+            # dropout masks are indexed by token row = caption * seq + position; trimming makes `seq` the local shard's
+            # last EOT, so ranks would index different (and overlapping) rows than the one-process run
+            raise ValueError("trim_text cannot be combined with a class-sharded text tower and LoRA dropout > 0: the "
+                             "Philox rows would depend on each rank's trimmed length (use trim_text=False or shard_text=False)")
+
+    def optimizer_step(self):
+        from clipfs import dist as D
+        if self.shadow_applied:
+            raise RuntimeError("optimizer_step while the EMA shadow is applied: call restore() first")
+        if self.live:
+            # replicated text tower (shard_text=False): every rank back-propagated the text gradient of ITS images
+            # only, so this same sum is already the batch total (d_txt is linear in the local dlogits)
+            self._timed("all_reduce", lambda: D.allreduce_sum_(self.flat.grads, self.pg))
+        self.t += 1
+        self._apply_update()  # AdamW, behind the scaler's and the clip's launches when those are on
+        self._after_update()
+
+    def _after_update(self):
+        """What a subclass does after the AdamW launch of ``optimizer_step``."""
+        raise NotImplementedError
+
     def _apply_update(self):
-        """The launches of one optimiser step after the all-reduce (``self.t`` already counts this step)."""
+        """The launches of one optimiser step after the all-reduce (``self.t`` already counts this step): the one AdamW
+        launch, which takes every record that is on (None = off), behind the scaler's and the clip's own launches."""
         f = self.flat
         if self.scale_state is not None:
             growth, backoff, interval = self._scaler_rule
@@ -808,13 +884,67 @@ class OptimizerStepOptions:
         if self.clip_state is not None:
             ops.grad_sumsq(f.grads, self._sumsq_work)
             ops.clip_decide(self._sumsq_work, f.numel, self.max_grad_norm, self.clip_state, self.scale_state)
-        if self.clip_state is not None or self.ema_shadow is not None:
-            ops.adamw_ext(f.params, f.grads, f.m, f.v, self.t, self.lr, self.betas, self.eps, self.wd, 1.0,
-                          self.scale_state, self.clip_state, self.ema_shadow, self.ema_decay or 0.0)
-        elif self.scale_state is not None:
-            ops.adamw_scaled(f.params, f.grads, f.m, f.v, self.scale_state, self.lr, self.betas, self.eps, self.wd)
-        else:
-            ops.adamw(f.params, f.grads, f.m, f.v, self.t, self.lr, self.betas, self.eps, self.wd, 1.0)
+        ops.adamw_ext(f.params, f.grads, f.m, f.v, self.t, self.lr, self.betas, self.eps, self.wd, 1.0,
+                      self.scale_state, self.clip_state, self.ema_shadow, self.ema_decay or 0.0)
+
+    # -- loss scaling: host views of the device record (each one synchronises) -------------------------
+    def _scaler_word(self, index: int, as_int: bool):
+        if self.scale_state is None:
+            return None
+        st = self.scale_state.cpu()
+        return int(st.view(torch.int32)[index]) if as_int else float(st[index])
+
+    @property
+    def loss_scale_value(self) -> Optional[float]:
+        """The scale the next ``forward_backward`` applies (None with loss scaling off)."""
+        return self._scaler_word(ops._lib.SCALER_SCALE, False)
+
+    @property
+    def skipped_steps(self) -> int:
+        """``optimizer_step`` calls that changed nothing because a gradient was NaN / inf (0 with loss scaling off)."""
+        return self._scaler_word(ops._lib.SCALER_SKIPPED, True) or 0
+
+    @property
+    def optimizer_steps(self) -> int:
+        """AdamW steps applied: ``t`` minus the skipped steps."""
+        return self.t if self.scale_state is None else self._scaler_word(ops._lib.SCALER_STEP, True)
+
+    # -- collectives ---------------------------------------------------------------------------------
+    def _exchange_buffers(self, classes: int, width: int):
+        from clipfs import dist as D
+        key = (classes, width)
+        b = self._xbuf.get(key)
+        if b is None:
+            s = D.block_rows(classes, self.world)
+            dev = self.flat.params.device
+            b = dict(S=s, send=torch.zeros(s, width, device=dev), full=torch.empty(self.world * s, width, device=dev),
+                     dfull=torch.zeros(self.world * s, width, device=dev), dmine=torch.empty(s, width, device=dev))
+            self._xbuf = {key: b}
+        return b
+
+    def _timed(self, name, fn):
+        if not self.time_collectives:
+            return fn()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        out = fn()
+        e1.record()
+        self._coll_events.append((name, e0, e1))
+        return out
+
+    def collective_times_ms(self):
+        """{name: [ms, ...]} of the collectives bracketed since the last call (needs a prior synchronize)."""
+        out = {}
+        for name, e0, e1 in self._coll_events:
+            out.setdefault(name, []).append(e0.elapsed_time(e1))
+        self._coll_events = []
+        return out
+
+    def _side_stream(self):
+        # one per device for everything in the process (clipfs/streams.py: HIP maps streams onto a handful of hardware
+        # queues, and a fresh stream per user ends up sharing a queue with another one)
+        from clipfs import streams
+        return streams.side_stream(self.model.device)
 
     # -- clipping: host views of the device record (each one synchronises) ----------------------------
     @property
@@ -926,7 +1056,7 @@ class OptimizerStepOptions:
         f.sync_packed()
 
 
-class LoRATrainer(OptimizerStepOptions):
+class LoRATrainer(FlatStepTrainer):
     """One object = the state of run_lora (:921-1023) that matters for the hot path: model with adapters,
     flat trainables, AdamW moments, step counter.  ``step`` is the loop body :956-1002:
 
@@ -952,15 +1082,14 @@ class LoRATrainer(OptimizerStepOptions):
     through ``slow_pace.Stage2Trainer(..., fused=True)``); bias training still needs a non-fp16 mode.
 
     ``max_grad_norm`` / ``ema_decay`` (both off by default) and ``state_dict`` / ``load_state_dict``: see
-    ``OptimizerStepOptions``."""
+    ``FlatStepTrainer``."""
 
     def __init__(self, model, lr: float = 2e-4, weight_decay: float = 1e-2, betas=(0.9, 0.999), eps: float = 1e-8,
                  logit_scale: float = 100.0, prompt_ctx: Optional[nn.Parameter] = None, process_group=None,
                  shard_text: bool = True, loss_scale=None, growth_factor: float = 2.0, backoff_factor: float = 0.5,
                  growth_interval: int = 2000, init_scale: float = 65536.0, max_grad_norm: Optional[float] = None,
                  ema_decay: Optional[float] = None):
-        from clipfs import dist as D
-        self.loss_scaling = _check_loss_scale(loss_scale, init_scale, growth_factor, backoff_factor, growth_interval)
+        _check_loss_scale(loss_scale, init_scale, growth_factor, backoff_factor, growth_interval)
         _check_step_options(max_grad_norm, ema_decay)
         self.model = model
         extra = []
@@ -980,82 +1109,10 @@ class LoRATrainer(OptimizerStepOptions):
             raise ValueError("bias training is not supported in the fp16 storage mode (dqkv and the MLP gradient exist "
                              "only as f16 images there): use precision 'fp32' or 'bf16x3'")
         self.prompt_ctx = prompt_ctx
-        self.lr, self.wd, self.betas, self.eps = lr, weight_decay, betas, eps
         self.logit_scale = logit_scale
-        self.t = 0
-        self.pg = process_group
-        self.rank, self.world = D.world_info(process_group)
-        self.shard_text = shard_text and (self.world > 1 or D.FORCE_COLLECTIVES)
-        self.overlap_towers = True  # text tower on a side HIP stream (set False to serialise, e.g. for per-kernel timing)
-        # class-sharded text tower: fixed exchange buffers (allocated on first use, never re-zeroed: padding rows of
-        # the send block / the gradient table are written by nobody and stay zero)
-        self._xbuf = {}
-        self.collectives_per_step = (3 if self.shard_text else 1) if (self.world > 1 or D.FORCE_COLLECTIVES) else 0
-        self.last_plan = None  # gradient floors of the last forward_backward: {"text": lo or None, "vision": lo or None}
-        self.time_collectives = False      # bench: bracket every collective with HIP events on the launch stream
-        self._coll_events = []
-        # loss scaling: the device record (clipfs.h CLIPFS_SCALER_*) and the scaler's constants; None = off
-        self.scale_state = None
-        if self.loss_scaling == "dynamic":
-            self._scaler_rule = (float(growth_factor), float(backoff_factor), int(growth_interval))
-            self.scale_state = ops.new_scaler_state(float(init_scale), self.flat.params.device)
-        elif self.loss_scaling == "static":
-            self._scaler_rule = (1.0, 1.0, 0)  # never grows, never backs off; still skips a non-finite step
-            self.scale_state = ops.new_scaler_state(float(loss_scale), self.flat.params.device)
-        self._init_step_options(max_grad_norm, ema_decay)
-
-    # -- loss scaling: host views of the device record (each one synchronises) -------------------------
-    def _scaler_word(self, index: int, as_int: bool):
-        if self.scale_state is None:
-            return None
-        st = self.scale_state.cpu()
-        return int(st.view(torch.int32)[index]) if as_int else float(st[index])
-
-    @property
-    def loss_scale_value(self) -> Optional[float]:
-        """The scale the next ``forward_backward`` applies (None with loss scaling off)."""
-        return self._scaler_word(ops._lib.SCALER_SCALE, False)
-
-    @property
-    def skipped_steps(self) -> int:
-        """``optimizer_step`` calls that changed nothing because a gradient was NaN / inf (0 with loss scaling off)."""
-        return self._scaler_word(ops._lib.SCALER_SKIPPED, True) or 0
-
-    @property
-    def optimizer_steps(self) -> int:
-        """AdamW steps applied: ``t`` minus the skipped steps."""
-        return self.t if self.scale_state is None else self._scaler_word(ops._lib.SCALER_STEP, True)
-
-    # -- collectives ---------------------------------------------------------------------------------
-    def _exchange_buffers(self, classes: int, width: int):
-        from clipfs import dist as D
-        key = (classes, width)
-        b = self._xbuf.get(key)
-        if b is None:
-            s = D.block_rows(classes, self.world)
-            dev = self.flat.params.device
-            b = dict(S=s, send=torch.zeros(s, width, device=dev), full=torch.empty(self.world * s, width, device=dev),
-                     dfull=torch.zeros(self.world * s, width, device=dev), dmine=torch.empty(s, width, device=dev))
-            self._xbuf = {key: b}
-        return b
-
-    def _timed(self, name, fn):
-        if not self.time_collectives:
-            return fn()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        out = fn()
-        e1.record()
-        self._coll_events.append((name, e0, e1))
-        return out
-
-    def collective_times_ms(self):
-        """{name: [ms, ...]} of the collectives bracketed since the last call (needs a prior synchronize)."""
-        out = {}
-        for name, e0, e1 in self._coll_events:
-            out.setdefault(name, []).append(e0.elapsed_time(e1))
-        self._coll_events = []
-        return out
+        # all_gather + reduce_scatter + all_reduce, or the all_reduce alone (forward_backward recounts from text_lo)
+        self._init_flat_step(lr, weight_decay, betas, eps, process_group, shard_text, (3, 1), loss_scale, init_scale,
+                             growth_factor, backoff_factor, growth_interval, max_grad_norm, ema_decay)
 
     def forward_backward(self, images, captions, target, templates_per_class: int = 1, global_batch: Optional[int] = None,
                          row_offset: int = 0):
@@ -1081,16 +1138,12 @@ class LoRATrainer(OptimizerStepOptions):
         classes = captions.shape[0] // t
         d = m.embed_dim
         c_lo, c_hi = D.block_bounds(classes, self.rank, self.world) if self.shard_text else (0, classes)
-        if self.shard_text and eng.trim_text and m.training and eng.txt.lora_dropout_rate() > 0:
-            # dropout masks are indexed by token row = caption * seq + position; trimming makes `seq` the local shard's
-            # last EOT, so ranks would index different (and overlapping) rows than the one-process run
-            raise ValueError("trim_text cannot be combined with a class-sharded text tower and LoRA dropout > 0: the "
-                             "Philox rows would depend on each rank's trimmed length (use trim_text=False or shard_text=False)")
+        self._refuse_sharded_dropout()
         xb = self._exchange_buffers(classes, d) if self.shard_text else None
         text_lo = eng.text_plan(self.prompt_ctx is not None)
         vis_lo = eng.image_plan()
         self.last_plan = {"text": text_lo, "vision": vis_lo}
-        if self.world > 1 or D.FORCE_COLLECTIVES:
+        if self.live:
             self.collectives_per_step = (3 if text_lo is not None else 2) if self.shard_text else 1
         # The two towers are independent until the logits: the text tower runs on a side HIP stream so that
         # its kernels fill the CUs the image tower's launches leave idle (small per-rank batches) and vice versa.
@@ -1133,22 +1186,7 @@ class LoRATrainer(OptimizerStepOptions):
         main.wait_stream(side)
         return loss_sum, correct, logits
 
-    def _side_stream(self):
-        # one per device for everything in the process (clipfs/streams.py: HIP maps streams onto a handful of hardware
-        # queues, and a fresh stream per user ends up sharing a queue with another one)
-        from clipfs import streams
-        return streams.side_stream(self.model.device)
-
-    def optimizer_step(self):
-        from clipfs import dist as D
-        if self.shadow_applied:
-            raise RuntimeError("optimizer_step while the EMA shadow is applied: call restore() first")
-        if self.world > 1 or D.FORCE_COLLECTIVES:
-            # replicated text tower (shard_text=False): every rank back-propagated the text gradient of ITS images
-            # only, so this same sum is already the batch total (d_txt is linear in the local dlogits)
-            self._timed("all_reduce", lambda: D.allreduce_sum_(self.flat.grads, self.pg))
-        self.t += 1
-        self._apply_update()  # AdamW, behind the scaler's and the clip's launches when those are on
+    def _after_update(self):
         self.flat.sync_packed()
 
     def step(self, images, captions, target, templates_per_class: int = 1, global_batch: Optional[int] = None,

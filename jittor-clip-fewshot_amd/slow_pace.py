@@ -31,8 +31,7 @@ from torch import nn
 from clipfs import engine as E
 from clipfs import ops
 from jclip import clip
-from lora_train_vlp import (FlatTrainables, LoRATrainer, OptimizerStepOptions, _check_loss_scale, _check_step_options,
-                            trainable_biases)
+from lora_train_vlp import FlatStepTrainer, FlatTrainables, _check_loss_scale, _check_step_options, trainable_biases
 from lora_train_vlp import clip_classifier  # noqa: F401  (re-exported like the reference's copy)
 
 
@@ -589,7 +588,7 @@ class Stage2Trainer:
         return loss.detach(), terms, cos.detach()
 
 
-class FusedStage2Trainer(Stage2Trainer, OptimizerStepOptions):
+class FusedStage2Trainer(Stage2Trainer, FlatStepTrainer):
     """``Stage2Trainer(..., fused=True)``: the same loop body (slow_pace.py:1622-1697, without the MoCo branch) built the
     way ``LoRATrainer`` builds stage 1 instead of through autograd.
 
@@ -622,7 +621,7 @@ class FusedStage2Trainer(Stage2Trainer, OptimizerStepOptions):
 
     Gradient clipping (``max_grad_norm``), averaged weights (``ema_decay``, ``apply_shadow`` / ``restore``) and the
     resumable state (``state_dict`` / ``load_state_dict``, which carries the cosine schedule's position) are
-    ``lora_train_vlp.OptimizerStepOptions``, as in ``LoRATrainer``; ``apply_shadow`` swaps every trainable of the flat
+    ``lora_train_vlp.FlatStepTrainer``, as in ``LoRATrainer``; ``apply_shadow`` swaps every trainable of the flat
     buffer, the head's included.
 
     ``step`` returns ``(loss, terms, cos)``: device tensors holding this rank's SHARE of the loss and of each term
@@ -643,8 +642,7 @@ class FusedStage2Trainer(Stage2Trainer, OptimizerStepOptions):
                  ema_decay: Optional[float] = None, fused: bool = True, process_group=None,
                  shard_text: bool = True, loss_scale=None, growth_factor: float = 2.0, backoff_factor: float = 0.5,
                  growth_interval: int = 2000, init_scale: float = 65536.0):
-        from clipfs import dist as D
-        self.loss_scaling = _check_loss_scale(loss_scale, init_scale, growth_factor, backoff_factor, growth_interval)
+        _check_loss_scale(loss_scale, init_scale, growth_factor, backoff_factor, growth_interval)
         _check_step_options(max_grad_norm, ema_decay)
         if not fused:
             raise ValueError("FusedStage2Trainer is the fused step: pass fused=True (or build a Stage2Trainer)")
@@ -684,37 +682,10 @@ class FusedStage2Trainer(Stage2Trainer, OptimizerStepOptions):
         n_tok = len(extra) - 4
         self.params: List[nn.Parameter] = extra[:n_tok] + list(self.flat.deep_prompts) + extra[n_tok:]  # each has .grad_slot
         self.sched = CosineAnnealingLR(lr, total_epoch)
-        self.lr, self.wd, self.betas, self.eps = lr, weight_decay, betas, eps
-        self.t = 0
-        self.pg = process_group
-        self.rank, self.world = D.world_info(process_group)
-        live = self.world > 1 or D.FORCE_COLLECTIVES
-        self.shard_text = shard_text and live
-        self.collectives_per_step = (4 if self.shard_text else 2) if live else 0
-        self.overlap_towers = True  # text tower on the side HIP stream (False serialises, e.g. for per-kernel timing)
-        self._xbuf, self._hbuf = {}, {}
+        self._hbuf = {}
         self._arange = None
-        self.last_plan = None
-        self.time_collectives = False
-        self._coll_events = []
-        self.scale_state = None
-        if self.loss_scaling == "dynamic":
-            self._scaler_rule = (float(growth_factor), float(backoff_factor), int(growth_interval))
-            self.scale_state = ops.new_scaler_state(float(init_scale), dev)
-        elif self.loss_scaling == "static":
-            self._scaler_rule = (1.0, 1.0, 0)  # never grows, never backs off; still skips a non-finite step
-            self.scale_state = ops.new_scaler_state(float(loss_scale), dev)
-        self._init_step_options(max_grad_norm, ema_decay)
-
-    # the device record's host views, the exchange buffers and the collective timers are LoRATrainer's own
-    _scaler_word = LoRATrainer._scaler_word
-    loss_scale_value = LoRATrainer.loss_scale_value
-    skipped_steps = LoRATrainer.skipped_steps
-    optimizer_steps = LoRATrainer.optimizer_steps
-    _exchange_buffers = LoRATrainer._exchange_buffers
-    _side_stream = LoRATrainer._side_stream
-    _timed = LoRATrainer._timed
-    collective_times_ms = LoRATrainer.collective_times_ms
+        self._init_flat_step(lr, weight_decay, betas, eps, process_group, shard_text, (4, 2), loss_scale, init_scale,
+                             growth_factor, backoff_factor, growth_interval, max_grad_norm, ema_decay)
 
     def loss(self, *args, **kwargs):
         raise NotImplementedError("the fused trainer evaluates the objective inside step(); use fused=False for loss()")
@@ -764,7 +735,6 @@ class FusedStage2Trainer(Stage2Trainer, OptimizerStepOptions):
         dev = m.device
         ctx = self.prompt_learner.ctx
         ids = self.prompt_learner.tokenized_prompts
-        live = self.world > 1 or D.FORCE_COLLECTIVES
         images = images.to(device=dev, dtype=torch.float32)
         target = target.to(dev).long().contiguous()
         B = images.shape[0]
@@ -780,9 +750,7 @@ class FusedStage2Trainer(Stage2Trainer, OptimizerStepOptions):
         s_txt, s_img, s_lp = (eng.next_seed(), eng.next_seed(), eng.next_seed()) if m.training else (0, 0, 0)
         c_lo, c_hi = D.block_bounds(C, self.rank, self.world) if self.shard_text else (0, C)
         n_loc = c_hi - c_lo
-        if self.shard_text and eng.trim_text and m.training and eng.txt.lora_dropout_rate() > 0:
-            raise ValueError("trim_text cannot be combined with a class-sharded text tower and LoRA dropout > 0: the "
-                             "Philox rows would depend on each rank's trimmed length (use trim_text=False or shard_text=False)")
+        self._refuse_sharded_dropout()
         xb = self._exchange_buffers(C, d) if self.shard_text else None
         text_lo, vis_lo = eng.text_plan(True), eng.image_plan()
         self.last_plan = {"text": text_lo, "vision": vis_lo}
@@ -801,7 +769,7 @@ class FusedStage2Trainer(Stage2Trainer, OptimizerStepOptions):
         zs_logits = ops.gemm_nt(zs_img, self.zs_txt, alpha=100.0)                         # :1650
         out = torch.zeros(5, device=dev)  # sim_ce, scl_logits, scl_image, scl_text, lp_ce: this rank's shares
         # head branch: on the gathered batch, by rank 0 alone (every rank takes part in the gather)
-        if live:
+        if self.live:
             hb = self._head_buffers(gb, d)
             hb["send"][:B, :d].copy_(lp_img)
             hb["send"][:B, d].copy_(target)
@@ -844,15 +812,8 @@ class FusedStage2Trainer(Stage2Trainer, OptimizerStepOptions):
         terms = {"sim_ce": out[0], "scl_text": out[3], "scl_image": out[2], "scl_logits": out[1], "lp_ce": out[4]}
         return out.sum(), terms, cos
 
-    def optimizer_step(self):
-        from clipfs import dist as D
-        if self.shadow_applied:
-            raise RuntimeError("optimizer_step while the EMA shadow is applied: call restore() first")
-        if self.world > 1 or D.FORCE_COLLECTIVES:
-            self._timed("all_reduce", lambda: D.allreduce_sum_(self.flat.grads, self.pg))
-        self.t += 1
-        self._apply_update()  # AdamW at the pre-step rate, behind the scaler's and the clip's launches when those are on
-        self.lr = self.sched.step()                                                       # :1697 (counts iterations)
+    def _after_update(self):
+        self.lr = self.sched.step()  # :1697 (counts iterations); the AdamW launch before it ran at the pre-step rate
 
     def step(self, images, target, index, template_choice: int = 0, global_batch: Optional[int] = None,
              row_offset: int = 0):

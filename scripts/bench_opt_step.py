@@ -5,7 +5,8 @@
 (a) The launches of one optimiser step on flat buffers of n = 370 688 floats (bench.py's cfg-2: rank-4 q/k/v adapters of
 12 + 12 blocks and the prompt ctx) and n = 3 934 208 (cfg-2 with ``q k v c_fc c_proj`` at r = 16), random contents, no
 model: plain AdamW (1 launch), clip (3), EMA (1), clip + EMA (3), and the same four behind dynamic loss scaling (3, 5,
-3, 5 launches).  Per arm --iters back-to-back steps between two HIP events, --rounds times, the arms alternating;
+3, 5 launches).  The last launch of every arm is the one AdamW kernel through ``ops.adamw_ext``, with the records that are
+off passed as None.  Per arm --iters back-to-back steps between two HIP events, --rounds times, the arms alternating;
 microseconds per step: median, minimum and maximum over the rounds.  Back-to-back steps never wait for the host, as
 inside a training step; what comes out is the larger of the device time and the time to issue the launches, so at the
 small size (1.5 MB per buffer) expect a multiple of the per-launch issue time rather than a bandwidth figure.
@@ -41,7 +42,7 @@ def stats(xs, digits=3):
 
 
 class FlatStep:
-    """The launch sequence of ``OptimizerStepOptions._apply_update`` on bare buffers."""
+    """The launch sequence of ``FlatStepTrainer._apply_update`` on bare buffers."""
 
     def __init__(self, dev, n, clip, ema, scaled):
         from clipfs import ops
@@ -67,13 +68,8 @@ class FlatStep:
         if self.clip is not None:
             ops.grad_sumsq(self.g, self.work)
             ops.clip_decide(self.work, self.g.numel(), 1.0, self.clip, self.scale)
-        if self.clip is not None or self.shadow is not None:
-            ops.adamw_ext(self.p, self.g, self.m, self.v, self.t, LR, BETAS, EPS, WD, 1.0, self.scale, self.clip,
-                          self.shadow, 0.999)
-        elif self.scale is not None:
-            ops.adamw_scaled(self.p, self.g, self.m, self.v, self.scale, LR, BETAS, EPS, WD)
-        else:
-            ops.adamw(self.p, self.g, self.m, self.v, self.t, LR, BETAS, EPS, WD, 1.0)
+        ops.adamw_ext(self.p, self.g, self.m, self.v, self.t, LR, BETAS, EPS, WD, 1.0, self.scale, self.clip, self.shadow,
+                      0.999 if self.shadow is not None else 0.0)
 
 
 def alone(dev, n, args):
