@@ -760,6 +760,51 @@ int clipfs_crop_batch(const uint8_t* pool, size_t pool_bytes, const int64_t* src
                       const int32_t* recs, const int32_t* recs_dev, int n, int out_size, const float* mean,
                       const float* stdv, float* out_norm, float* out_raw, void* stream);
 
+/* ------------------------------------------------------ merged weights --
+ * Folds LoRA adapters into COPIES of the frozen weights: out = W + scale * B A, the weight the reference runs a plain
+ * linear on once a layer is in eval mode (LoRALayer.merge_BA / add_lora_data, lora_train_vlp.py:218-234).  W itself is
+ * read only.  ONE launch folds a whole table of projections (a tower's adapted matrices are a few MB each: a launch per
+ * matrix would spend more on kernel boundaries than on bytes).
+ *
+ * One job = one projection:
+ *   w [n, k] fp32, the master weight (read only; out must not be w);
+ *   a [nseg * r, k], b [n, r]: the tower's stacked adapter layouts (qkv: nseg 3, A [3r, k], B [3d, r]; o / c_fc / c_proj:
+ *     nseg 1);
+ *   seg_mask: bit g set = rows g * n / nseg ... (g + 1) * n / nseg - 1 have an adapter; a clear bit = those rows of out
+ *     are a bitwise copy of w;
+ *   out [n, k] fp32;  planes: NULL, or the 16-bit image of out in `plane_format` (2: f16 [n, k], bit for bit what
+ *     clipfs_convert_f16 makes of out; 1: bf16 hi [n, k] then lo [n, k], bit for bit clipfs_split_bf16 of out);
+ *   tile0: the index of the job's first tile in the launch = the tile counts of the jobs before it, where a job has
+ *     nseg * ceil(n / nseg / CLIPFS_LORA_MERGE_TILE_ROWS) * ceil(k / CLIPFS_LORA_MERGE_TILE_COLS) tiles (a tile never
+ *     crosses a segment).
+ * r (1 ... 64), scale and plane_format (0: no planes anywhere) are per call: one tower shares them.
+ *
+ * Arithmetic, fixed: for row n of segment g and column k,  acc = sum_j B[n, j] * A[g r + j, k]  in fp32, ascending j,
+ * each step one fused multiply-add;  out = fma(scale, acc, W[n, k]).  No atomics, no split over j: results are
+ * deterministic and  |out - (W + s B A)| <= (r + 3) 2^-24 (|W| + |s| sum_j |B A|)  elementwise.
+ *
+ * h_jobs is the HOST table, validated here before anything is enqueued; jobs_dev is its device copy (the same bytes,
+ * uploaded by the caller), which the kernel reads.  struct_size = sizeof(clipfs_lora_merge_job) of the caller.
+ * CLIPFS_EINVAL (nothing launched), the message naming the job index and the field: a struct_size this library does not
+ * know, njobs <= 0, a NULL or not 16-byte aligned pointer, k % 8 != 0, nseg other than 1 or 3, n % nseg != 0, seg_mask
+ * zero or outside nseg bits, out == w, planes given with plane_format 0, a wrong tile0, r outside [1, 64]. */
+#define CLIPFS_LORA_MERGE_TILE_ROWS 32
+#define CLIPFS_LORA_MERGE_TILE_COLS 256
+typedef struct clipfs_lora_merge_job {
+  const float* w;
+  const float* a;
+  const float* b;
+  float* out;
+  void* planes;
+  int n, k;
+  int nseg;
+  unsigned seg_mask;
+  int tile0;
+  int reserved; /* zero */
+} clipfs_lora_merge_job;
+int clipfs_lora_merge(const clipfs_lora_merge_job* h_jobs, const clipfs_lora_merge_job* jobs_dev, int njobs,
+                      size_t struct_size, int r, float scale, int plane_format, void* stream);
+
 /* --------------------------------------------------------- tower drivers --
  * C++ sequencing of the kernels above for one transformer tower, so that one call
  * from Python enqueues a whole forward or backward (no per-kernel interpreter cost).

@@ -95,6 +95,22 @@ F16_KERNELS = ("64x128", "64x128_s2", "128x128", "256x128", "pp_reg", "pp_lds", 
 GEMM_KERNELS = ("nt64", "nt64_reg", "nt32", "mixed", "patch32", "generic", "planes64", "planes128")
 
 
+class MergeJob(C.Structure):
+    """struct clipfs_lora_merge_job: one projection of a clipfs_lora_merge table."""
+    _fields_ = [("w", C.c_void_p), ("a", C.c_void_p), ("b", C.c_void_p), ("out", C.c_void_p), ("planes", C.c_void_p),
+                ("n", C.c_int), ("k", C.c_int), ("nseg", C.c_int), ("seg_mask", C.c_uint), ("tile0", C.c_int),
+                ("reserved", C.c_int)]
+
+
+# CLIPFS_LORA_MERGE_TILE_ROWS / _COLS of include/clipfs.h
+MERGE_TILE_ROWS, MERGE_TILE_COLS = 32, 256
+
+
+def merge_job_tiles(n: int, k: int, nseg: int) -> int:
+    """Tiles of one clipfs_lora_merge job (a tile never crosses a segment); the table's ``tile0`` is their prefix sum."""
+    return nseg * (-(-(n // nseg) // MERGE_TILE_ROWS)) * (-(-k // MERGE_TILE_COLS))
+
+
 class Block(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in (
         "ln1_g", "ln1_b", "ln2_g", "ln2_b",
@@ -213,6 +229,7 @@ SIGNATURES = {
     "clipfs_mta": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _p]),
     "clipfs_tta_views": (_i, [_p, _i, _i, _p, _i, _i, _p, _p, _p, _p]),
     "clipfs_crop_batch": (_i, [_p, _sz, _p, _p, _i, _p, _p, _i, _i, _p, _p, _p, _p, _p]),
+    "clipfs_lora_merge": (_i, [C.POINTER(MergeJob), _p, _i, _sz, _i, _f, _i, _p]),
     "clipfs_bpe_create": (C.c_void_p, [C.c_char_p, _sz, _i]),
     "clipfs_bpe_destroy": (None, [C.c_void_p]),
     "clipfs_bpe_encode": (C.c_long, [C.c_void_p, _p, _p, _i, _p, _p, C.c_long]),

@@ -92,6 +92,69 @@ class _TowerRT:
         self.lora_r = 0
         self.lora_scale = 0.0
         self.lora_dropout = 0.0
+        # merged-weight cache (``merge``): {block: {"qkv" | "o" | "fc" | "pr": W + scale * B A, fp32}} for the ADAPTED
+        # projections only; None = the additive form (every path as if this cache did not exist)
+        self._merged: Optional[Dict[int, Dict[str, torch.Tensor]]] = None
+
+    # -- merged weights --------------------------------------------------------------------------
+    def _adapted(self):
+        """([(block, name, w, a, b, nseg, seg_mask)], r, scale) of the tower's adapted projections in the stacked layouts
+        the tower kernels read (qkv: A [3r, d], B [3d, r], one bit per segment; o / fc / pr: one segment)."""
+        out, r, scale = [], 0, 0.0
+
+        def shared(m):
+            nonlocal r, scale
+            if r and (m.r != r or abs(m.scaling - scale) > 0):
+                raise ValueError("all LoRA layers of one tower must share r / alpha / dropout")
+            r, scale = m.r, float(m.scaling)
+
+        for i, blk in enumerate(self.mod.resblocks):
+            a = blk.attn
+            if getattr(a, "is_lora_mha", False) and a.r > 0 and a.lora_mask:
+                shared(a)
+                if a.lora_mask & 7:
+                    out.append((i, "qkv", a.qkv_weight, a.lora_A_qkv, a.lora_B_qkv, 3, a.lora_mask & 7))
+                if a.lora_mask & 8:
+                    out.append((i, "o", a.proj.weight.data, a.lora_A_o, a.lora_B_o, 1, 1))
+            for tok, m in _mlp_adapters(blk):
+                shared(m)
+                out.append((i, "fc" if tok == "c_fc" else "pr", m.weight.data, m.w_lora_A.data, m.w_lora_B.data, 1, 1))
+        return out, r, scale
+
+    def merge(self) -> int:
+        """Fold every adapter of the tower into copies of its weights with ONE clipfs_lora_merge launch (the 16-bit
+        planes of the current precision in the same pass); the master weights are only read.  Returns the number of
+        projections folded (q, k and v count one each); 0 = nothing to fold, the tower stays unmerged."""
+        jobs, r, scale = self._adapted()
+        self.unmerge()
+        if not jobs:
+            return 0
+        fmt = ops.PLANE_FORMATS[self.precision]
+        merged: Dict[int, Dict[str, torch.Tensor]] = {}
+        table = []
+        for i, name, w, a, b, nseg, mask in jobs:
+            out = torch.empty_like(w)
+            planes = ops.empty_planes(out, fmt)
+            table.append((w, a.contiguous(), b.contiguous(), nseg, mask, out, planes))
+            merged.setdefault(i, {})[name] = out
+            if planes is not None:
+                self._planes[(i, "m_" + name, self.precision)] = planes
+        ops.lora_merge(table, r, scale, fmt)
+        self._merged = merged
+        return sum(bin(mask).count("1") for *_, mask in jobs)
+
+    def unmerge(self) -> None:
+        self._merged = None
+        for key in [k for k in self._planes if k[1].startswith("m_")]:
+            del self._planes[key]
+
+    def _point_merged(self, b, i: int, m: Dict[str, torch.Tensor]) -> None:
+        """Block pointers of the folded projections of block i (planes of another precision than the merge's are built
+        from the folded fp32 copy on first use: bitwise what the merge kernel writes)."""
+        for name, w in m.items():
+            setattr(b, "w_" + name, _ptr(w))
+            if self.precision != "fp32":
+                setattr(b, "w_" + name + "_p", _ptr(self._plane(i, "m_" + name, w)))
 
     # -- descriptor ------------------------------------------------------------------------------
     def _transposed(self, i: int, blk) -> Dict[str, torch.Tensor]:
@@ -137,6 +200,17 @@ class _TowerRT:
         return self.layers - 1 if head_trains else None
 
     def descriptor(self, train: bool, seed: int, seq: Optional[int] = None, row0: int = 0, grad_lo: int = 0) -> Tower:
+        merged = self._merged
+        if merged is not None:
+            # a merged tower is forward-only and dropout-free: nothing was saved for a backward through W + s B A, and a
+            # train-mode forward of the additive form would drop
+            if train:
+                raise ValueError(f"{self.name} tower: its LoRA adapters are merged into the weights (merge_lora), which "
+                                 "is forward-only -- call unmerge_lora before a forward that keeps activations")
+            if seed and self.lora_dropout_rate() > 0:
+                raise ValueError(f"{self.name} tower: a train-mode forward with adapter dropout "
+                                 f"{self.lora_dropout_rate():g} cannot run on merged weights -- call unmerge_lora (or "
+                                 "model.eval()) first")
         blocks = (Block * self.layers)()
         r, scale, p = 0, 0.0, 0.0
         # deep prompts: the vision tower's last prompt_rows rows (its VPT rows), the text tower's rows 1 ... prompt_rows
@@ -197,6 +271,10 @@ class _TowerRT:
                     b.w_fc_t_p = _ptr(self._plane(i, "fc_t", wt["fc"]))
                     b.w_pr_t_p = _ptr(self._plane(i, "pr_t", wt["pr"]))
             b.lora_mask = 0
+            if merged is not None:  # an ordinary model to every kernel and mode query: no adapter pointers, lora_r 0
+                if i in merged:
+                    self._point_merged(b, i, merged[i])
+                continue
             if lora and a.r > 0:
                 if r and (a.r != r or abs(a.scaling - scale) > 0 or abs(a.dropout_rate - p) > 0):
                     raise ValueError("all LoRA layers of one tower must share r / alpha / dropout")
@@ -439,6 +517,33 @@ class Engine:
         if not self.resnet:
             self.vis.precision = mode
         self.txt.precision = mode
+
+    # -- merged weights -------------------------------------------------------------------------------
+    def _towers(self) -> List[_TowerRT]:
+        return [self.txt] if self.resnet else [self.txt, self.vis]
+
+    @property
+    def merged(self) -> bool:
+        """Whether the towers run on folded copies of their weights (``merge``): then every forward is the one of a model
+        that never had adapters, and anything that needs the additive form (a backward, adapter dropout) is refused."""
+        return any(t._merged is not None for t in self._towers())
+
+    def merge(self) -> int:
+        """Fold the adapters of both towers (one launch per tower that has any); the number of projections folded."""
+        try:
+            return sum(t.merge() for t in self._towers())
+        except Exception:
+            self.unmerge()  # never one tower merged and the other not
+            raise
+
+    def unmerge(self) -> None:
+        for t in self._towers():
+            t.unmerge()
+
+    def refuse_merged(self, what: str) -> None:
+        if self.merged:
+            raise ValueError(f"{what}: the LoRA adapters are merged into the weights (merge_lora), which is forward-only "
+                             "-- call unmerge_lora first")
 
     # -- backward plan --------------------------------------------------------------------------------
     def image_plan(self) -> Optional[int]:
@@ -784,6 +889,7 @@ def encode_image(model, images: torch.Tensor) -> torch.Tensor:
         _ensure_slot(model.visual.VPT)
         params.append(model.visual.VPT)
     if torch.is_grad_enabled() and any(p.requires_grad for p in params):
+        model.engine.refuse_merged("encode_image with trainable parameters")
         return _EncodeImage.apply(model, images, *params)
     # no-grad route: dropout still follows model.training (reference: a second encode_image under jt.no_grad() in
     # train mode, slow_pace.py:1612,1659-1661, is dropout-on)
@@ -796,6 +902,7 @@ def encode_text(model, ids: torch.Tensor, prompt_ctx: Optional[torch.Tensor] = N
     params = [p for p, _ in pairs]
     needs = any(p.requires_grad for p in params) or (prompt_ctx is not None and prompt_ctx.requires_grad)
     if torch.is_grad_enabled() and needs:
+        model.engine.refuse_merged("encode_text with trainable parameters")
         return _EncodeText.apply(model, ids, prompt_ctx, *params)
     feat, _ = model.engine.text_forward(ids, prompt_ctx, False, model.engine.next_seed() if model.training else 0)
     return feat

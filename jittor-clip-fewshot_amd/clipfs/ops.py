@@ -116,6 +116,45 @@ def to_f16(w: torch.Tensor) -> torch.Tensor:
     return out
 
 
+PLANE_FORMATS = {"fp32": 0, "bf16x3": 1, "fp16": 2}  # clipfs_tower.weight_format / clipfs_lora_merge plane_format
+
+
+def empty_planes(w: torch.Tensor, fmt: int) -> Optional[torch.Tensor]:
+    """An unwritten 16-bit image of ``w`` in plane format ``fmt``, shaped as ``split_bf16`` / ``to_f16`` return it."""
+    if fmt == 1:
+        return torch.empty((2,) + tuple(w.shape), device=w.device, dtype=torch.int16)
+    if fmt == 2:
+        return torch.empty(w.shape, device=w.device, dtype=torch.float16)
+    return None
+
+
+def lora_merge(jobs, r: int, scale: float, fmt: int = 0) -> None:
+    """ONE clipfs_lora_merge launch over ``jobs`` = [(w [n,k], a [nseg*r,k], b [n,r], nseg, seg_mask, out [n,k], planes |
+    None)]: out = w + scale * b a per segment (segments outside ``seg_mask``: the bits of w), ``planes`` = the 16-bit
+    image of out in plane format ``fmt`` (``empty_planes``).  w is read only.  The host table is validated by the library;
+    its device copy is uploaded here."""
+    table = (_lib.MergeJob * len(jobs))()
+    tile0 = 0
+    dev = None
+    for rec, (w, a, b, nseg, seg_mask, out, planes) in zip(table, jobs):
+        _f32(w), _f32(a), _f32(b), _f32(out)
+        n, k = w.shape
+        assert tuple(out.shape) == (n, k) and tuple(a.shape) == (nseg * r, k) and tuple(b.shape) == (n, r), \
+            (tuple(w.shape), tuple(a.shape), tuple(b.shape), tuple(out.shape), nseg, r)
+        if planes is not None:
+            assert planes.is_contiguous() and planes.numel() * planes.element_size() == (4 if fmt == 1 else 2) * n * k
+        rec.w, rec.a, rec.b, rec.out, rec.planes = _p(w), _p(a), _p(b), _p(out), _p(planes)
+        rec.n, rec.k, rec.nseg, rec.seg_mask, rec.tile0 = n, k, nseg, seg_mask, tile0
+        tile0 += _lib.merge_job_tiles(n, k, nseg)
+        dev = w.device
+    if not jobs:
+        raise ValueError("lora_merge: empty job table")
+    table_dev = torch.frombuffer(bytearray(bytes(table)), dtype=torch.uint8).to(dev)
+    check(_lib.load().clipfs_lora_merge(table, _p(table_dev), len(jobs), C.sizeof(_lib.MergeJob), r, float(scale), fmt,
+                                        _stream()), "lora_merge")
+    # table_dev was allocated on this stream: its storage is handed out again only to work ordered behind the launch
+
+
 def patch_embed(images: torch.Tensor, conv_w: torch.Tensor, pos: torch.Tensor, x: torch.Tensor, tokens: int) -> None:
     """x[b, 1+p, :] = conv(images)[b, :, p] + pos[1+p]  (im2col-free GEMM on the NCHW batch)."""
     _f32(images), _f32(conv_w), _f32(pos), _f32(x)

@@ -15,31 +15,15 @@
 //   * block tile BM x BN x 32, 4 waves (2 x 2), double-buffered, one barrier per K-step; epilogue and tile order are
 //     shared with the fp32 kernel (gemm_common.h).
 #include "gemm_common.h"
+#include "convert16.h"
 
 #include <stdlib.h>
 
 namespace clipfs {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 __device__ __forceinline__ void glds16b(const void* gsrc, void* lds_wave_base) {
   __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gsrc,
                                    (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
-}
-
-__device__ __forceinline__ void split8(const f32x4& x0, const f32x4& x1, bf16x8& hi, bf16x8& lo) {
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    hi[j] = (__bf16)x0[j];
-    hi[4 + j] = (__bf16)x1[j];
-  }
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    lo[j] = (__bf16)(x0[j] - (float)hi[j]);
-    lo[4 + j] = (__bf16)(x1[j] - (float)hi[4 + j]);
-  }
 }
 
 __global__ __launch_bounds__(256) void split_bf16_kernel(const float* __restrict__ src, __bf16* __restrict__ hi,
@@ -59,16 +43,6 @@ struct Bf16Params {
   const void* b_hi;  // [N, K] 16-bit plane (bf16 hi, or the single f16 plane)
   const void* b_lo;  // bf16 lo plane (unused for f16)
 };
-
-__device__ __forceinline__ f16x8 to_f16x8(const f32x4& x0, const f32x4& x1) {
-  f16x8 h;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    h[j] = (_Float16)x0[j];
-    h[4 + j] = (_Float16)x1[j];
-  }
-  return h;
-}
 
 __global__ __launch_bounds__(256) void convert_f16_kernel(const float* __restrict__ src, _Float16* __restrict__ dst,
                                                           size_t n8) {

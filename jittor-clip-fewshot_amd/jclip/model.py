@@ -300,6 +300,7 @@ class CLIP(nn.Module):
 
     def load(self, path: str) -> None:
         from clipfs import module_io
+        self.invalidate_engine()  # merged-weight copies (merge_lora) go first: the adapters are about to change
         module_io.load_module(self, path)
         if hasattr(self.visual, "invalidate"):
             self.visual.invalidate()  # a ModifiedResNet's runner holds BatchNorm-folded copies
@@ -307,10 +308,15 @@ class CLIP(nn.Module):
 
     def invalidate_engine(self):
         """Called when the module tree changes (apply_lora, FlatTrainables) so pointers are re-collected.  The
-        engine's user-visible settings (precision mode, text trimming) carry over to the rebuilt engine."""
+        engine's user-visible settings (precision mode, text trimming) carry over to the rebuilt engine.  Merged-weight
+        copies (``lora_train_vlp.merge_lora``) live in the engine and go with it: the model is unmerged afterwards."""
         if self._engine is not None:
             self._engine_opts = (self._engine.precision, self._engine.trim_text, self._engine.sparse_backward,
                                  self._engine.prune_backward)
+            if self._engine.merged:  # the merged-weight copies go with the engine: the model is unmerged again
+                for m in self.modules():
+                    if getattr(m, "merged", False):
+                        m.merged = False
         self._engine = None
 
     @property

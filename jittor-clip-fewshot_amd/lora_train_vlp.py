@@ -14,10 +14,12 @@ model are re-homed into one flat fp32 buffer so the data-parallel gradient excha
 all-reduce and the optimiser a single fused launch."""
 from __future__ import annotations
 
+import contextlib
 import math
 import numbers
 import os
 import pickle
+import weakref
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -124,8 +126,11 @@ def lora_state_dict(model, bias: str = 'none'):
 # ----------------------------------------------------------------------------------------------
 
 class LoRALayer:
-    """lora_train_vlp.py:185-245 (state only; merging is never needed: the engine always applies the
-    additive form, which is the branch the reference executes)."""
+    """lora_train_vlp.py:185-245 (state only).  Training always runs the additive form, the branch the reference
+    executes in train mode.  ``merged`` is the reference's flag with a narrower trigger: it is True
+    exactly while ``merge_lora`` has folded this layer's adapter into a COPY of its weight (``merged_lora`` /
+    ``evaluate_lora(merged=True)``), never because of ``eval()``; ``weight`` itself is never written, so
+    ``unmerge_lora`` restores the model bit for bit (the reference's ``sub_lora_data``, :236-245, subtracts in fp32)."""
 
     def __init__(self, r: int, lora_alpha: int, fan_in_fan_out: bool = False, dropout_rate: float = 0):
         self.r = r
@@ -136,6 +141,7 @@ class LoRALayer:
         self.merged = False
         self.fan_in_fan_out = fan_in_fan_out
         self.params_with_lora = {}
+        self._merge_owner = None  # the CLIP model whose ``merge_lora`` set ``merged`` (a weak reference)
 
 
 class LinearLoRA(nn.Module, LoRALayer):
@@ -154,7 +160,7 @@ class LinearLoRA(nn.Module, LoRALayer):
         self.w_lora_B = nn.Parameter(b_view)
 
     def merge_BA(self, param_name: str = 'weight') -> torch.Tensor:
-        """B @ A (:218-221); host-side helper for inspection / merged-weight checks."""
+        """B @ A (:218-221); host-side helper for inspection (``merge_lora`` folds on the GPU, clipfs_lora_merge)."""
         return (self.w_lora_B.data @ self.w_lora_A.data).reshape(self.weight.shape)
 
 
@@ -435,6 +441,7 @@ def load_lora(args, list_lora_layers, load_path):
     if md['position'] != args.position:
         raise ValueError(f"Position mismatch: expected {args.position}, found {md['position']}")
     weights = loaded['weights']
+    _unmerge_layers(list_lora_layers)  # merged copies (merge_lora) of the values about to change are dropped first
     with torch.no_grad():
         for i, layer in enumerate(list_lora_layers):
             lw = weights[f'layer_{i}']
@@ -450,6 +457,117 @@ def load_lora(args, list_lora_layers, load_path):
                     m.w_lora_A.data.copy_(torch.from_numpy(np.ascontiguousarray(lw[tok]['w_lora_A'])))
                     m.w_lora_B.data.copy_(torch.from_numpy(np.ascontiguousarray(lw[tok]['w_lora_B'])))
     print(f'LoRA weights loaded from {load_path}')
+
+
+# ----------------------------------------------------------------------------------------------
+# merged-weight evaluation and export (LoRALayer.merge_BA / add_lora_data / sub_lora_data / lora_train, :218-245)
+# ----------------------------------------------------------------------------------------------
+
+def _lora_layers(clip_model) -> List[LoRALayer]:
+    return [m for m in clip_model.modules() if isinstance(m, LoRALayer)]
+
+
+def is_merged(clip_model) -> bool:
+    """Whether ``merge_lora`` is in effect (no engine is built to answer)."""
+    eng = getattr(clip_model, '_engine', None)
+    return eng is not None and eng.merged
+
+
+def merge_lora(clip_model) -> int:
+    """Fold every adapter of both towers (attention q / k / v / o, MLP c_fc / c_proj; a ModifiedResNet model: the text
+    tower) into COPIES of the weights, W + scaling * B A, with one clipfs_lora_merge launch per tower, and run every
+    later forward on them: the towers then see a model without adapters, so an MLP adapter no longer costs the live-row
+    text forward, the one-row last block or the fp16 storage mode.  The master weights and the adapters are only read.
+    Sets ``merged`` on every ``LoRALayer`` and returns the number of projections folded; called again it refreshes the
+    copies from the current adapter values; a model without adapters returns 0 and changes nothing.  While merged the
+    model is forward-only and dropout-free: the autograd route, the trainers and a train-mode forward with adapter
+    dropout raise ValueError (``unmerge_lora``)."""
+    n = clip_model.engine.merge()
+    if n:
+        owner = weakref.ref(clip_model)
+        for m in _lora_layers(clip_model):
+            m.merged, m._merge_owner = True, owner
+    return n
+
+
+def unmerge_lora(clip_model) -> None:
+    """Drop the merged copies and clear the flags.  The master weights were never written: the model is bit for bit the
+    one before ``merge_lora``."""
+    eng = getattr(clip_model, '_engine', None)
+    if eng is not None:
+        eng.unmerge()
+    for m in _lora_layers(clip_model):
+        m.merged, m._merge_owner = False, None
+
+
+def _unmerge_layers(list_lora_layers) -> None:
+    """``unmerge_lora`` of the model(s) the given layers were merged in: the writers of adapter values call this first, so
+    a stale merged copy can never be evaluated."""
+    for layer in list_lora_layers:
+        owner = getattr(layer, '_merge_owner', None)
+        model = owner() if (owner is not None and getattr(layer, 'merged', False)) else None
+        if model is not None:
+            unmerge_lora(model)
+
+
+@contextlib.contextmanager
+def merged_lora(clip_model):
+    """``with merged_lora(model): ...`` evaluates on merged weights and restores the previous state on exit (also on an
+    exception): unmerged again, or, inside an outer merge, merged afresh."""
+    was = is_merged(clip_model)
+    merge_lora(clip_model)
+    try:
+        yield clip_model
+    finally:
+        if was:
+            merge_lora(clip_model)
+        else:
+            unmerge_lora(clip_model)
+
+
+def merged_state_dict(clip_model, prompt_ctx=None) -> Dict[str, torch.Tensor]:
+    """The model as a PLAIN CLIP checkpoint: CPU fp32 tensors under the keys ``jclip.model.build_model`` reads
+    (``...attn.in_proj_weight``, ``...attn.out_proj.weight``, ``...mlp.c_fc.weight``, ...), adapters folded in
+    (clipfs_lora_merge, the weights ``merge_lora`` evaluates on), current biases, no ``lora`` key.  The model's merge state
+    is left as found.  Learned prompts have no place in a plain checkpoint: a model with VPT tokens or deep prompts, or
+    a ``prompt_ctx``, is refused by name."""
+    if prompt_ctx is not None:
+        raise ValueError("merged_state_dict: prompt ctx tokens cannot be stored in a plain CLIP checkpoint")
+    if getattr(clip_model.visual, 'VPT', None) is not None:
+        raise ValueError("merged_state_dict: the model has VPT tokens (visual.VPT), which a plain CLIP checkpoint cannot hold")
+    for tname, tower in towers(clip_model):
+        if any(getattr(blk, 'VPT_shallow', None) is not None for blk in tower.resblocks):
+            raise ValueError(f"merged_state_dict: the {tname} tower has deep prompts (VPT_shallow), which a plain CLIP "
+                             "checkpoint cannot hold")
+    eng = clip_model.engine
+    was = eng.merged
+    eng.merge()  # engine state only: the LoRALayer flags keep saying what the caller set
+    try:
+        sd = {}
+        for name, t in clip_model.state_dict().items():
+            if 'lora_' in name or '.attn.q_proj.' in name or '.attn.k_proj.' in name or '.attn.v_proj.' in name \
+                    or '.attn.proj.' in name:
+                continue
+            sd[name] = t
+        rts = {'text': eng.txt} if eng.resnet else {'text': eng.txt, 'vision': eng.vis}
+        for tname, tower in towers(clip_model):
+            prefix = 'transformer' if tname == 'text' else 'visual.transformer'
+            folded = rts[tname]._merged or {}
+            for i, blk in enumerate(tower.resblocks):
+                a, f, p = blk.attn, folded.get(i, {}), f'{prefix}.resblocks.{i}.'
+                if getattr(a, 'is_lora_mha', False):
+                    sd[p + 'attn.in_proj_weight'] = f.get('qkv', a.qkv_weight)
+                    sd[p + 'attn.in_proj_bias'] = a.qkv_bias
+                    sd[p + 'attn.out_proj.weight'] = f.get('o', a.proj.weight.data)
+                    sd[p + 'attn.out_proj.bias'] = a.proj.bias.data
+                if 'fc' in f:
+                    sd[p + 'mlp.c_fc.weight'] = f['fc']
+                if 'pr' in f:
+                    sd[p + 'mlp.c_proj.weight'] = f['pr']
+        return {k: v.detach().to(device='cpu', dtype=torch.float32).contiguous().clone() for k, v in sd.items()}
+    finally:
+        if not was:
+            eng.unmerge()
 
 
 # ----------------------------------------------------------------------------------------------
@@ -515,11 +633,16 @@ def evaluate_views(clip_model, views, target, textual_features):
 
 
 @torch.no_grad()
-def evaluate_lora(args, clip_model, loader, templates=None, textual_features=None):
+def evaluate_lora(args, clip_model, loader, templates=None, textual_features=None, merged: bool = False):
     """lora_train_vlp.py:813-846: MTA / centre-view / view-ensemble top-1 accuracy (in %) over a loader that yields
     ``(image [n,1,3,R,R] | [n,3,R,R], images [n,1,N,3,R,R] | [n,N,3,R,R], target, impath)`` -- the centre view and the N
     random crops of each image.  The text classifier comes from ``templates`` ({class: [captions]}, the reference reads
-    them from the 'text_template' folder, :816-817) or is passed in as ``textual_features`` [d, C]."""
+    them from the 'text_template' folder, :816-817) or is passed in as ``textual_features`` [d, C].  ``merged=True``
+    evaluates under ``merged_lora``: the adapters folded into copies of the weights (what the reference's eval mode
+    does in place, :236-245), the model's merge state left as found."""
+    if merged:
+        with merged_lora(clip_model):
+            return evaluate_lora(args, clip_model, loader, templates, textual_features)
     clip_model.eval()
     if textual_features is None:
         if templates is None:
@@ -619,6 +742,9 @@ class FlatTrainables:
 
     def __init__(self, model, extra: Sequence[nn.Parameter] = ()):
         from clipfs.engine import _lora_trains, _mlp_lora_trains
+        if is_merged(model):  # re-homing the adapters rebuilds the engine, which would silently drop the merged copies
+            raise ValueError("the LoRA adapters are merged into the weights (merge_lora), which is forward-only -- call "
+                             "unmerge_lora before building a trainer")
         self.model = model
         bias_names = [n for n, _ in trainable_biases(model)]
         entries = []
@@ -1130,6 +1256,7 @@ class LoRATrainer(FlatStepTrainer):
         from clipfs import dist as D
         m = self.model
         eng = m.engine
+        eng.refuse_merged("LoRATrainer.forward_backward")  # merged weights (merge_lora) are forward-only
         self.flat.sync_packed()  # packed q/k/v biases of partially trained blocks (no-op otherwise)
         seed = eng.next_seed() if m.training else 0
         B = images.shape[0]

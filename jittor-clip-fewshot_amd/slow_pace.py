@@ -236,6 +236,8 @@ def load_lora_swa(args, list_lora_layers, swa_weights_folder: str) -> int:
         count += 1
     if count == 0:
         raise ValueError(f"no LoRA files in {swa_weights_folder}")
+    from lora_train_vlp import _unmerge_layers
+    _unmerge_layers(list_lora_layers)  # merged copies (merge_lora) of the values about to change are dropped first
     with torch.no_grad():
         for i, layer in enumerate(list_lora_layers):
             lw = acc[f"layer_{i}"]
@@ -575,6 +577,7 @@ class Stage2Trainer:
                            self.zs_sets[template_choice % len(self.zs_sets)], self.moco_adapter, moco_feats)
 
     def step(self, images, target, index, template_choice: int = 0, raw_images: Optional[torch.Tensor] = None):
+        self.model.engine.refuse_merged("Stage2Trainer.step")  # merged weights (merge_lora) are forward-only
         for p in self.params:
             p.grad = None
         loss, terms, cos = self.loss(images, target, index, template_choice, raw_images)
@@ -732,6 +735,7 @@ class FusedStage2Trainer(Stage2Trainer, FlatStepTrainer):
         from clipfs import dist as D
         m = self.model
         eng = m.engine
+        eng.refuse_merged("Stage2Trainer(fused=True).forward_backward")  # merged weights (merge_lora) are forward-only
         dev = m.device
         ctx = self.prompt_learner.ctx
         ids = self.prompt_learner.tokenized_prompts
