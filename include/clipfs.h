@@ -957,6 +957,59 @@ int clipfs_tower_fwd_packed(const clipfs_tower* t, float* x, const int32_t* rows
 int clipfs_tower_bwd_packed_saved(const clipfs_tower* t, const float* dxs, const int32_t* rows, const int32_t* plan, int R,
                                   float* dx, int batch, const float* saved, float* scratch, int stop_at_input, void* stream);
 
+/* ------------------------------------------------------------- cache head --
+ * A Tip-Adapter key-value cache over few-shot features with one-hot values (Zhang et al., ECCV 2022), fp32 in every
+ * engine precision mode:
+ *   a[b,k] = f[b,:] . K[k,:]      E[b,k] = exp(-beta (1 - a[b,k]))      S[b,c] = sum_{k in [off[c], off[c+1])} E[b,k]
+ *   logits[b,c] = base[b,c] + alpha S[b,c]
+ * f [B, d] query rows (the caller passes unit rows; nothing is normalised or clamped: a > 1 is legal), K [NK, d] keys
+ * SORTED BY CLASS, off [C + 1] int32 ascending class offsets into K (off[0] = 0, off[C] = NK; a class may own no key:
+ * S = 0), base [B, C] with leading dimension ldbase >= C (NULL: 0), alpha, beta >= 0.  The [B, NK] affinity and E never
+ * reach HBM; no float atomics; every sum runs in an order fixed by the shapes and `off` (a class run in ascending key
+ * order), every output element is written by one thread: results are bitwise equal run to run.
+ *
+ * clipfs_cache_plan IS the function the three entry points execute: host-only (no GPU is opened, nothing is launched,
+ * nothing written to `plan` on refusal).  CLIPFS_EINVAL, the message naming the argument, for B, NK or C < 1, d not a
+ * multiple of 4 in [4, 4096], nA or nB outside [1, 1024] (pass 1 where the operation has no grid), an unknown op or a
+ * NULL plan.  The entry points refuse the same before anything is launched, and also: f, K, out or dK NULL or not
+ * 16-byte aligned, a leading dimension below C, out == base, alpha or beta negative or not finite. */
+#define CLIPFS_CACHE_OP_LOGITS 0 /* clipfs_cache_logits: grid (32-query tiles, chunks of class_chunk classes) */
+#define CLIPFS_CACHE_OP_BWD_DK 1 /* clipfs_cache_bwd, the dK launch: grid (32-key tiles, chunks of feat_chunk features) */
+#define CLIPFS_CACHE_OP_BWD_DF 2 /*   ... the df launch: grid (32-query tiles, chunks of feat_chunk features) */
+#define CLIPFS_CACHE_OP_SEARCH 3 /* clipfs_cache_search: grid (32-query tiles, beta chunks, alpha chunks) */
+struct clipfs_cache_plan {
+  unsigned grid_x, grid_y, grid_z, block;
+  unsigned lds_bytes;     /* static + dynamic LDS of a workgroup (at most 160 KB) */
+  int class_chunk;        /* logits: classes per workgroup (0 otherwise) */
+  int feat_chunk;         /* backward: features per workgroup, 512, or 128 where 512 would leave compute units idle */
+  int beta_chunk;         /* search: betas per workgroup; the affinity is recomputed per chunk (0 otherwise) */
+  int alpha_chunk;        /* search: alphas per workgroup (0 otherwise) */
+  size_t work_floats;     /* scratch the call needs: 0, no sum is cut over workgroups */
+};
+int clipfs_cache_plan(int op, int B, int NK, int C, int d, int nA, int nB, struct clipfs_cache_plan* plan);
+/* out [B, C] (leading dimension ldout >= C; columns past C and rows past B are not touched) = the logits above, one
+ * launch.  out must not alias base. */
+int clipfs_cache_logits(const float* f, const float* K, const int32_t* off, const float* base, float* out, int B, int NK,
+                        int C, int d, int ldbase, int ldout, float alpha, float beta, void* stream);
+/* Backward for key training given dlogits [B, C] (leading dimension lddl >= C), G[b,k] = alpha beta E[b,k] dlogits[b, class(k)]:
+ *   dK[k,:] += sum_b G[b,k] f[b,:]   (accumulate-into, like the adapter gradient slots)
+ *   df[b,:]  = sum_k G[b,k] K[k,:]   (df may be NULL; written, not accumulated)
+ * E is recomputed per 32 x 32 tile; one workgroup owns 32 rows of dK (df) and feat_chunk features and walks the queries (keys)
+ * in ascending tiles, so no sum is cut over workgroups: no scratch, one launch per output.  dK and df must not alias
+ * f, K or each other.  alpha and beta get no gradient. */
+int clipfs_cache_bwd(const float* f, const float* K, const int32_t* off, const float* dlogits, float* dK, float* df, int B,
+                     int NK, int C, int d, int lddl, float alpha, float beta, void* stream);
+/* The hyper-parameter search in one launch: for the grids alphas [nA], betas [nB] (device, fp32) and targets y [B]
+ *   hits[j, i] += #{ b : argmax_c (base[b,c] + alphas[i] S_betas[j][b,c]) == y[b] }        (int32 [nB, nA])
+ * ties towards the smaller class index (the rule of clipfs_topk).  Neither the affinity nor S reaches HBM: the keys
+ * being class-sorted, classes complete in ascending order along the key walk, and a running (best value, best class)
+ * per (query, beta, alpha), updated with a strict > when a class's run ends (with base alone for an empty class), is
+ * all that is kept.  Each cell's logits are bitwise those of clipfs_cache_logits.  hits is ADDED to with integer
+ * atomics (order-free: deterministic); the caller zeroes it. */
+int clipfs_cache_search(const float* f, const float* K, const int32_t* off, const float* base, const int64_t* y,
+                        const float* alphas, const float* betas, int32_t* hits, int B, int NK, int C, int d, int ldbase,
+                        int nA, int nB, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

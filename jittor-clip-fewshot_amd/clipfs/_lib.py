@@ -95,6 +95,16 @@ F16_KERNELS = ("64x128", "64x128_s2", "128x128", "256x128", "pp_reg", "pp_lds", 
 GEMM_KERNELS = ("nt64", "nt64_reg", "nt32", "mixed", "patch32", "generic", "planes64", "planes128")
 
 
+class CachePlan(C.Structure):
+    """struct clipfs_cache_plan: what a cache-head entry point launches."""
+    _fields_ = [("grid_x", C.c_uint), ("grid_y", C.c_uint), ("grid_z", C.c_uint), ("block", C.c_uint), ("lds_bytes", C.c_uint),
+                ("class_chunk", C.c_int), ("feat_chunk", C.c_int), ("beta_chunk", C.c_int), ("alpha_chunk", C.c_int), ("work_floats", C.c_size_t)]
+
+
+# CLIPFS_CACHE_OP_* of include/clipfs.h, by value
+CACHE_OPS = ("logits", "bwd_dk", "bwd_df", "search")
+
+
 class MergeJob(C.Structure):
     """struct clipfs_lora_merge_job: one projection of a clipfs_lora_merge table."""
     _fields_ = [("w", C.c_void_p), ("a", C.c_void_p), ("b", C.c_void_p), ("out", C.c_void_p), ("planes", C.c_void_p),
@@ -267,6 +277,10 @@ SIGNATURES = {
     "clipfs_attention_f16_bwd_packed_ok": (_i, [_i, _i]),
     "clipfs_attention_f16_bwd_packed": (_i, [_p, _i, _p, _i, _p, _p, _p, _p, _p, _p, _i, _i, _i, _p]),
     "clipfs_layernorm_bwd_rows_f16": (_i, [_p, _p, _i, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _p]),
+    "clipfs_cache_plan": (_i, [_i, _i, _i, _i, _i, _i, _i, C.POINTER(CachePlan)]),
+    "clipfs_cache_logits": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _f, _f, _p]),
+    "clipfs_cache_bwd": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _f, _p]),
+    "clipfs_cache_search": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p]),
 }
 
 # word indices of the loss-scaling record (CLIPFS_SCALER_* of include/clipfs.h)
@@ -336,6 +350,14 @@ def lora_plan(op: str, rows: int, width: int, segw: int, r: int, nseg: int, x_ac
     check(load().clipfs_lora_plan(LORA_OPS.index(op), rows, width, segw, r, nseg, flags, C.byref(plan)), "lora_plan")
     d = {k: getattr(plan, k) for k, _ in LoraPlan._fields_[1:-2]}
     return dict(family=LORA_FAMILIES[plan.family], **d, launches=tuple((l.grid_x, l.grid_y, l.block) for l in plan.launch[:plan.launches]))
+
+
+def cache_plan(op: str, B: int, NK: int, C_: int, d: int, nA: int = 1, nB: int = 1):
+    """The plan clipfs_cache_logits / _bwd / _search execute for these shapes (host-only), as a dict of the fields of struct
+    clipfs_cache_plan with grid = (x, y, z).  A refusal raises ClipfsError with its message."""
+    plan = CachePlan()
+    check(load().clipfs_cache_plan(CACHE_OPS.index(op), B, NK, C_, d, nA, nB, C.byref(plan)), "cache_plan")
+    return dict(grid=(plan.grid_x, plan.grid_y, plan.grid_z), **{k: getattr(plan, k) for k, _ in CachePlan._fields_[3:]})
 
 
 def new_tower() -> Tower:

@@ -698,3 +698,78 @@ def stage2_objective(cos, zs_logits, target, img, zs_img, txt, zs_txt, classes: 
                                               None if scale_state is None else _p(_scaler(scale_state)), _stream()),
           "stage2_objective")
     return terms, correct, dcos, dimg, dtxt
+
+
+# ------------------------------------------------------------------------------------------------ cache head
+def _cache_shapes(f, keys, offsets):
+    B, d = f.shape
+    NK = keys.shape[0]
+    assert keys.shape[1] == d and offsets.dtype == torch.int32 and offsets.is_contiguous() and offsets.dim() == 1
+    return B, NK, offsets.numel() - 1, d
+
+
+def cache_plan(op: str, B: int, NK: int, C_: int, d: int, nA: int = 1, nB: int = 1):
+    """What ``cache_logits`` ("logits"), ``cache_bwd`` ("bwd_dk", "bwd_df") or ``cache_search`` ("search") launch for these
+    shapes (host-only): grid, block, lds_bytes, class_chunk, feat_chunk, beta_chunk, alpha_chunk, work_floats."""
+    return _lib.cache_plan(op, B, NK, C_, d, nA, nB)
+
+
+def cache_logits(f, keys, offsets, base=None, alpha=1.0, beta=5.5, out=None):
+    """logits [B, C] = base + alpha * (per-class sums of exp(-beta (1 - f keys^T))): the Tip-Adapter cache head in one
+    launch.  ``keys`` [NK, d] sorted by class, ``offsets`` int32 [C + 1]; ``base`` and ``out`` may be column slices (row
+    stride >= C, unit column stride).  ``out`` must not alias ``base``."""
+    B, NK, Cn, d = _cache_shapes(f, keys, offsets)
+    if out is None:
+        out = torch.empty(B, Cn, device=f.device, dtype=torch.float32)
+    for t in (base, out):
+        assert t is None or (t.dtype == torch.float32 and tuple(t.shape) == (B, Cn) and t.stride(1) == 1), "base / out"
+    check(_lib.load().clipfs_cache_logits(_p(_f32(f)), _p(_f32(keys)), _p(offsets), _p(base), _p(out), B, NK, Cn, d,
+                                          0 if base is None else (base.stride(0) if B > 1 else max(base.stride(0), Cn)),
+                                          out.stride(0) if B > 1 else max(out.stride(0), Cn), alpha, beta, _stream()),
+          "cache_logits")
+    return out
+
+
+def cache_bwd(f, keys, offsets, dlogits, dkeys, alpha=1.0, beta=5.5, want_df=False):
+    """Adds the key gradient of ``cache_logits`` for ``dlogits`` [B, C] into ``dkeys`` [NK, d]; returns df [B, d] when
+    ``want_df`` (else None)."""
+    B, NK, Cn, d = _cache_shapes(f, keys, offsets)
+    assert tuple(dlogits.shape) == (B, Cn) and tuple(dkeys.shape) == (NK, d)
+    df = torch.empty_like(f) if want_df else None
+    check(_lib.load().clipfs_cache_bwd(_p(_f32(f)), _p(_f32(keys)), _p(offsets), _p(_f32(dlogits)), _p(_f32(dkeys)), _p(df),
+                                       B, NK, Cn, d, Cn, alpha, beta, _stream()), "cache_bwd")
+    return df
+
+
+def cache_search(f, keys, offsets, base, target, alphas, betas):
+    """hits int32 [nB, nA]: per (beta, alpha) cell the rows whose top-1 of ``cache_logits`` equals ``target`` (int64 [B]),
+    one launch; ``alphas`` / ``betas`` are fp32 device vectors."""
+    B, NK, Cn, d = _cache_shapes(f, keys, offsets)
+    assert target.dtype == torch.int64 and target.is_contiguous() and target.numel() == B
+    assert base is None or (base.dtype == torch.float32 and tuple(base.shape) == (B, Cn) and base.stride(1) == 1)
+    nA, nB = alphas.numel(), betas.numel()
+    hits = torch.zeros(nB, nA, device=f.device, dtype=torch.int32)
+    check(_lib.load().clipfs_cache_search(_p(_f32(f)), _p(_f32(keys)), _p(offsets), _p(base), _p(target), _p(_f32(alphas)),
+                                          _p(_f32(betas)), _p(hits), B, NK, Cn, d,
+                                          0 if base is None else (base.stride(0) if B > 1 else max(base.stride(0), Cn)),
+                                          nA, nB, _stream()), "cache_search")
+    return hits
+
+
+class CacheLogitsFn(torch.autograd.Function):
+    """``cache_logits`` differentiable w.r.t. the keys, the base logits and (when they require grad) the queries."""
+
+    @staticmethod
+    def forward(ctx, f, keys, offsets, base, alpha, beta):
+        f, keys = f.contiguous(), keys.contiguous()
+        ctx.save_for_backward(f, keys, offsets)
+        ctx.alpha, ctx.beta = float(alpha), float(beta)
+        return cache_logits(f, keys, offsets, base, alpha, beta)
+
+    @staticmethod
+    def backward(ctx, dlogits):
+        f, keys, offsets = ctx.saved_tensors
+        dlogits = dlogits.contiguous()
+        dkeys = torch.zeros_like(keys)
+        df = cache_bwd(f, keys, offsets, dlogits, dkeys, ctx.alpha, ctx.beta, want_df=ctx.needs_input_grad[0])
+        return df, dkeys if ctx.needs_input_grad[1] else None, None, dlogits if ctx.needs_input_grad[3] else None, None, None
