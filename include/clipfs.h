@@ -1010,6 +1010,37 @@ int clipfs_cache_search(const float* f, const float* K, const int32_t* off, cons
                         const float* alphas, const float* betas, int32_t* hits, int B, int NK, int C, int d, int ldbase,
                         int nA, int nB, void* stream);
 
+/* ---------------------------------------------------------- TPT objective --
+ * The objective of test-time prompt tuning (Shu et al., NeurIPS 2022) for n_img independent images, fp32 in every
+ * engine precision mode.  Per image, with F [V, d] the unit view features, T [C, d] the unit class features, s the
+ * logit scale:
+ *   z_v = s F_v T^T      p_v = softmax(z_v)      H_v = -sum_c p_vc log p_vc
+ *   S    = the K views of lowest H_v, ties to the lower view index: rank_v = #{u : H_u < H_v or (H_u == H_v and u < v)},
+ *          v in S iff rank_v < K (rank counting, no sort)
+ *   pbar = (1/K) sum_{v in S} p_v (ascending view index)      loss = -sum_c pbar_c log pbar_c
+ *   dT   = s sum_{v in S} dz_v^T F_v,   dz_v = (1/K) p_v (g - <p_v, g>),   g_c = -log pbar_c
+ * (0 log 0 = 0 where pbar underflows).  A view's entropy does not depend on its index: identical rows of F give
+ * bitwise equal H, which makes the tie rule exact.  classes == 1 gives loss 0 and a zero gradient.
+ *
+ * feats [n_img, V, d]; text [C, d], or [n_img, C, d] when text_per_image != 0; selected [n_img, K] int32, ascending
+ * view index per image: WRITTEN, or READ when reuse_selection != 0 (the selection is a constant of an episode: later
+ * steps reuse the first step's; indices outside [0, V) are clamped); loss [n_img]; entropy [n_img, V] or NULL; dtext
+ * [n_img, C, d] = grad_scale * dT or NULL (loss only; grad_scale reaches nothing else); work >=
+ * clipfs_tpt_work_floats(n_img, views, width, classes) = n_img * (2 * views * classes + classes) floats.
+ *
+ * At most three launches whatever n_img (logits tiles on the fp32 matrix cores; one workgroup per image for softmax
+ * statistics, entropies, selection, pbar, loss and dz; the rank-K product dz^T F), two when dtext is NULL; nothing is
+ * launched per image and nothing returns to the host.  No float atomics: results are bitwise equal run to run, and an
+ * image's results do not depend on n_img or on its position in the batch.
+ *
+ * CLIPFS_EINVAL before anything is enqueued, the message naming the argument: feats, text, selected, loss or work NULL,
+ * n_img outside [1, 65535], views outside [1, 1024], width not a multiple of 4 in [4, 1024], classes < 1, K outside
+ * [1, views], feats / text / dtext not 16-byte aligned, a scale that is not finite. */
+size_t clipfs_tpt_work_floats(int n_img, int views, int width, int classes);
+int clipfs_tpt_objective(const float* feats, const float* text, int text_per_image, int32_t* selected, int reuse_selection,
+                         int K, float logit_scale, float grad_scale, float* loss, float* entropy, float* dtext, float* work,
+                         int n_img, int views, int width, int classes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

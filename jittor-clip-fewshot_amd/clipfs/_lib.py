@@ -281,6 +281,8 @@ SIGNATURES = {
     "clipfs_cache_logits": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _f, _f, _p]),
     "clipfs_cache_bwd": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _f, _p]),
     "clipfs_cache_search": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p]),
+    "clipfs_tpt_work_floats": (_sz, [_i, _i, _i, _i]),
+    "clipfs_tpt_objective": (_i, [_p, _p, _i, _p, _i, _i, _f, _f, _p, _p, _p, _p, _i, _i, _i, _i, _p]),
 }
 
 # word indices of the loss-scaling record (CLIPFS_SCALER_* of include/clipfs.h)

@@ -773,3 +773,33 @@ class CacheLogitsFn(torch.autograd.Function):
         dkeys = torch.zeros_like(keys)
         df = cache_bwd(f, keys, offsets, dlogits, dkeys, ctx.alpha, ctx.beta, want_df=ctx.needs_input_grad[0])
         return df, dkeys if ctx.needs_input_grad[1] else None, None, dlogits if ctx.needs_input_grad[3] else None, None, None
+
+
+# ------------------------------------------------------------------------------------------------ TPT objective
+def tpt_objective(feats, text, K, logit_scale=100.0, selected=None, want_grad=True, grad_scale=1.0, want_entropy=False):
+    """The test-time prompt tuning objective for ``feats`` [n_img, V, d] (unit view features) and ``text`` [C, d] shared by
+    the images or [n_img, C, d] one per image (unit class features): per image the entropy of the softmax averaged over
+    the ``K`` views of lowest entropy (ties to the lower view index) and its gradient with respect to ``text``, in at most
+    three launches for the whole batch.  ``selected`` (int32 [n_img, K], ascending view index): given, it IS the
+    selection (a later step of an episode reuses the first step's); None, it is made and returned.  Returns
+    (loss [n_img], selected [n_img, K], dtext [n_img, C, d] = ``grad_scale`` * d loss / d text or None, entropy
+    [n_img, V] or None)."""
+    assert feats.dim() == 3 and text.dim() in (2, 3), "feats [n_img, V, d], text [C, d] or [n_img, C, d]"
+    n_img, V, d = feats.shape
+    Cn = text.shape[-2]
+    assert text.shape[-1] == d and (text.dim() == 2 or text.shape[0] == n_img), (tuple(feats.shape), tuple(text.shape))
+    dev = feats.device
+    reuse = selected is not None
+    if reuse:
+        assert selected.dtype == torch.int32 and selected.is_contiguous() and tuple(selected.shape) == (n_img, K)
+    else:
+        selected = torch.empty(n_img, max(K, 0), device=dev, dtype=torch.int32)
+    lib = _lib.load()
+    loss = torch.empty(n_img, device=dev, dtype=torch.float32)
+    entropy = torch.empty(n_img, V, device=dev, dtype=torch.float32) if want_entropy else None
+    dtext = torch.empty(n_img, Cn, d, device=dev, dtype=torch.float32) if want_grad else None
+    work = torch.empty(max(lib.clipfs_tpt_work_floats(n_img, V, d, Cn), 4), device=dev, dtype=torch.float32)
+    check(lib.clipfs_tpt_objective(_p(_f32(feats)), _p(_f32(text)), int(text.dim() == 3), _p(selected), int(reuse), K,
+                                   logit_scale, grad_scale, _p(loss), _p(entropy), _p(dtext), _p(work), n_img, V, d, Cn,
+                                   _stream()), "tpt_objective")
+    return loss, selected, dtext, entropy
