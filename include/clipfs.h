@@ -1041,6 +1041,60 @@ int clipfs_tpt_objective(const float* feats, const float* text, int text_per_ima
                          int K, float logit_scale, float grad_scale, float* loss, float* entropy, float* dtext, float* work,
                          int n_img, int views, int width, int classes, void* stream);
 
+/* --------------------------------------------------- contrastive objective --
+ * The one-directional multi-positive InfoNCE loss (CLIP's contrastive objective with group ids: the UniCL /
+ * supervised-contrastive form), fp32 in every engine precision mode.  Both directions of the symmetric loss, and both
+ * halves of a data-parallel step, are calls of it.  q [R, d] queries and k [N, d] keys (the caller passes unit rows),
+ * q_group [R] / k_group [N] int32, s = logit_scale, w = weight, S = word CLIPFS_SCALER_SCALE of scaler_state (a
+ * loss-scaling record, see "loss scaling") or 1 when it is NULL:
+ *   z_ij   = s q_i . k_j
+ *   a key with k_group[j] < 0 does not exist: it is masked out of the softmax and never positive (padding rows of
+ *   gathered blocks); "live" = k_group[j] >= 0
+ *   P_i    = { j live : k_group[j] == q_group[i] }      n_i = |P_i|
+ *   a row with q_group[i] < 0 or n_i = 0 contributes nothing: loss_i = 0, G_i: = 0; otherwise
+ *   loss_i = logsumexp_{j live} z_ij - (1/n_i) sum_{j in P_i} z_ij
+ *   loss_rows [R] (may be NULL) = loss_i      loss_sum [1] = w sum_i loss_i
+ *   correct [1] (int32, may be NULL) = #{ i : q_group[i] >= 0, n_i > 0, argmax_{j live} z_ij in P_i }, ties to the lower j
+ *                                      (the rule of clipfs_topk)
+ *   G_ij   = w S (softmax_ij - [j in P_i] / n_i)   for live j, 0 otherwise
+ *   dq_i   = s sum_j G_ij k_j   [R, d]             dk_j = s sum_i G_ij q_i   [N, d]
+ * dq and dk are each optional (NULL: not formed, one launch fewer).  With its accumulate flag set the finished sum is
+ * added ONCE to what is there (bitwise old + fresh); otherwise it is written.  S multiplies the gradients only, never
+ * loss_rows, loss_sum or correct.  Plain paired CLIP is group = pair index on both sides.
+ *
+ * Neither z nor G reaches HBM; no float atomics; every sum runs in an order fixed by (R, N, d), every output element is
+ * written by one thread: results are bitwise equal run to run.  Nothing outside the stated extents is touched and
+ * nothing returns to the host.  Four launches at most, three when one gradient is NULL:
+ *   stats    grid (32-query tiles, chunks of col_chunk keys): per (query, chunk) max, sum of exponentials, sum of
+ *            positive z, positive count, best (value, index) into `work`
+ *   combine  one workgroup: lse_i, 1 / n_i, loss_i, the hit flag; loss_sum and correct by a fixed-order tree
+ *   dq, dk   grid (32 own-row tiles, chunks of feat_chunk features): the other side walked in ascending 32-row tiles,
+ *            z recomputed, G formed from lse_i and contracted in the same workgroup
+ * work >= work_floats = 6 * chunks * R + 2 * R floats (the same for every op of a shape); no initialisation needed.
+ *
+ * clipfs_contrastive_plan IS the function the entry point executes: host-only (no GPU is opened, nothing is launched,
+ * nothing written to `plan` on refusal).  CLIPFS_EINVAL, the message naming the argument, for R or N < 1, d not a
+ * multiple of 4 in [4, 1024], an unknown op or a NULL plan.  clipfs_contrastive_objective refuses the same before
+ * anything is enqueued, and also: q, k, q_group, k_group, loss_sum or work NULL; q, k, dq or dk not 16-byte aligned; dq
+ * or dk overlapping q, k or each other; a logit_scale or weight that is not finite. */
+#define CLIPFS_CONTRASTIVE_OP_STATS 0
+#define CLIPFS_CONTRASTIVE_OP_COMBINE 1
+#define CLIPFS_CONTRASTIVE_OP_DQ 2
+#define CLIPFS_CONTRASTIVE_OP_DK 3
+struct clipfs_contrastive_plan {
+  unsigned grid_x, grid_y, grid_z, block;
+  unsigned lds_bytes;     /* LDS of a workgroup (at most 160 KB) */
+  int col_chunk;          /* keys per stats workgroup: a multiple of 128, at most 1024 */
+  int chunks;             /* key chunks = ceil(N / col_chunk) */
+  int feat_chunk;         /* dq / dk: features per workgroup, 512, or 128 where 512 would leave compute units idle (0 otherwise) */
+  size_t work_floats;     /* scratch the call needs */
+};
+int clipfs_contrastive_plan(int op, int R, int N, int d, struct clipfs_contrastive_plan* plan);
+int clipfs_contrastive_objective(const float* q, const float* k, const int32_t* q_group, const int32_t* k_group,
+                                 float logit_scale, float weight, const float* scaler_state, float* loss_rows,
+                                 float* loss_sum, int32_t* correct, float* dq, int dq_accumulate, float* dk,
+                                 int dk_accumulate, float* work, int R, int N, int d, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -105,6 +105,16 @@ class CachePlan(C.Structure):
 CACHE_OPS = ("logits", "bwd_dk", "bwd_df", "search")
 
 
+class ContrastivePlan(C.Structure):
+    """struct clipfs_contrastive_plan: what clipfs_contrastive_objective launches."""
+    _fields_ = [("grid_x", C.c_uint), ("grid_y", C.c_uint), ("grid_z", C.c_uint), ("block", C.c_uint), ("lds_bytes", C.c_uint),
+                ("col_chunk", C.c_int), ("chunks", C.c_int), ("feat_chunk", C.c_int), ("work_floats", C.c_size_t)]
+
+
+# CLIPFS_CONTRASTIVE_OP_* of include/clipfs.h, by value
+CONTRASTIVE_OPS = ("stats", "combine", "dq", "dk")
+
+
 class MergeJob(C.Structure):
     """struct clipfs_lora_merge_job: one projection of a clipfs_lora_merge table."""
     _fields_ = [("w", C.c_void_p), ("a", C.c_void_p), ("b", C.c_void_p), ("out", C.c_void_p), ("planes", C.c_void_p),
@@ -283,6 +293,8 @@ SIGNATURES = {
     "clipfs_cache_search": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p]),
     "clipfs_tpt_work_floats": (_sz, [_i, _i, _i, _i]),
     "clipfs_tpt_objective": (_i, [_p, _p, _i, _p, _i, _i, _f, _f, _p, _p, _p, _p, _i, _i, _i, _i, _p]),
+    "clipfs_contrastive_plan": (_i, [_i, _i, _i, _i, C.POINTER(ContrastivePlan)]),
+    "clipfs_contrastive_objective": (_i, [_p, _p, _p, _p, _f, _f, _p, _p, _p, _p, _p, _i, _p, _i, _p, _i, _i, _i, _p]),
 }
 
 # word indices of the loss-scaling record (CLIPFS_SCALER_* of include/clipfs.h)
@@ -360,6 +372,14 @@ def cache_plan(op: str, B: int, NK: int, C_: int, d: int, nA: int = 1, nB: int =
     plan = CachePlan()
     check(load().clipfs_cache_plan(CACHE_OPS.index(op), B, NK, C_, d, nA, nB, C.byref(plan)), "cache_plan")
     return dict(grid=(plan.grid_x, plan.grid_y, plan.grid_z), **{k: getattr(plan, k) for k, _ in CachePlan._fields_[3:]})
+
+
+def contrastive_plan(op: str, R: int, N: int, d: int):
+    """The plan clipfs_contrastive_objective executes for these shapes (host-only), as a dict of the fields of struct
+    clipfs_contrastive_plan with grid = (x, y, z).  A refusal raises ClipfsError with its message."""
+    plan = ContrastivePlan()
+    check(load().clipfs_contrastive_plan(CONTRASTIVE_OPS.index(op), R, N, d, C.byref(plan)), "contrastive_plan")
+    return dict(grid=(plan.grid_x, plan.grid_y, plan.grid_z), **{k: getattr(plan, k) for k, _ in ContrastivePlan._fields_[3:]})
 
 
 def new_tower() -> Tower:

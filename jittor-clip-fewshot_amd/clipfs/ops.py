@@ -803,3 +803,86 @@ def tpt_objective(feats, text, K, logit_scale=100.0, selected=None, want_grad=Tr
                                    logit_scale, grad_scale, _p(loss), _p(entropy), _p(dtext), _p(work), n_img, V, d, Cn,
                                    _stream()), "tpt_objective")
     return loss, selected, dtext, entropy
+
+
+# ------------------------------------------------------------------------------------------------ contrastive objective
+def contrastive_plan(op: str, R: int, N: int, d: int):
+    """What ``contrastive_objective`` launches for these shapes ("stats", "combine", "dq", "dk"; host-only): grid, block,
+    lds_bytes, col_chunk, chunks, feat_chunk, work_floats."""
+    return _lib.contrastive_plan(op, R, N, d)
+
+
+def contrastive_objective(q, k, q_group, k_group, logit_scale=100.0, weight=1.0, scale_state=None, dq=None, dk=None,
+                          want_dq=True, want_dk=True, *, accumulate=True):
+    """The one-directional multi-positive InfoNCE loss of unit queries ``q`` [R, d] against unit keys ``k`` [N, d] with
+    int32 group ids (a key whose group equals the query's is a positive; a negative key group masks the key out, a
+    negative query group or a query without positives contributes nothing): at most four launches, the [R, N] logits and
+    their gradient never reach memory.  Returns (loss_sum [1] = weight * sum of the row losses, loss_rows [R], correct [1]
+    int32, dq [R, d] or None, dk [N, d] or None).  A passed ``dq`` / ``dk`` is ACCUMULATED into (bitwise old + fresh) and
+    returned (``accumulate=False``, or a (dq, dk) pair of flags: overwritten instead); otherwise the gradient is made
+    when ``want_dq`` / ``want_dk``.  ``scale_state`` (a loss-scaling record) multiplies the gradients only."""
+    R, d = q.shape
+    N = k.shape[0]
+    assert k.shape[1] == d, (tuple(q.shape), tuple(k.shape))
+    for g, n in ((q_group, R), (k_group, N)):
+        assert g.dtype == torch.int32 and g.is_contiguous() and g.numel() == n, "groups are contiguous int32 [R] / [N]"
+    dev = q.device
+    acc_q, acc_k = accumulate if isinstance(accumulate, tuple) else (accumulate, accumulate)
+    acc_q, acc_k = acc_q and dq is not None, acc_k and dk is not None
+    if dq is None and want_dq:
+        dq = torch.empty(R, d, device=dev, dtype=torch.float32)
+    if dk is None and want_dk:
+        dk = torch.empty(N, d, device=dev, dtype=torch.float32)
+    assert dq is None or tuple(dq.shape) == (R, d), "dq is [R, d]"
+    assert dk is None or tuple(dk.shape) == (N, d), "dk is [N, d]"
+    lib = _lib.load()
+    work = torch.empty(_lib.contrastive_plan("stats", R, N, d)["work_floats"], device=dev, dtype=torch.float32)
+    loss_rows = torch.empty(R, device=dev, dtype=torch.float32)
+    loss_sum = torch.empty(1, device=dev, dtype=torch.float32)
+    correct = torch.empty(1, device=dev, dtype=torch.int32)
+    check(lib.clipfs_contrastive_objective(_p(_f32(q)), _p(_f32(k)), _p(q_group), _p(k_group), logit_scale, weight,
+                                           None if scale_state is None else _p(_scaler(scale_state)), _p(loss_rows),
+                                           _p(loss_sum), _p(correct), None if dq is None else _p(_f32(dq)), int(acc_q),
+                                           None if dk is None else _p(_f32(dk)), int(acc_k), _p(work), R, N, d, _stream()),
+          "contrastive_objective")
+    return loss_sum, loss_rows, correct, dq, dk
+
+
+class ClipLossFn(torch.autograd.Function):
+    """``clip_loss``: both directions of the symmetric loss are calls of ``contrastive_objective``; the second call
+    accumulates into the first one's gradients."""
+
+    @staticmethod
+    def forward(ctx, img, txt, img_group, txt_group, logit_scale):
+        img, txt = img.contiguous(), txt.contiguous()
+        B, M = img.shape[0], txt.shape[0]
+        need_i, need_t = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        l_it, _, _, dimg, dtxt = contrastive_objective(img, txt, img_group, txt_group, logit_scale, 0.5 / B,
+                                                       want_dq=need_i, want_dk=need_t)
+        l_ti, _, _, dtxt, dimg = contrastive_objective(txt, img, txt_group, img_group, logit_scale, 0.5 / M, dq=dtxt, dk=dimg,
+                                                       want_dq=False, want_dk=False)
+        ctx.save_for_backward(*(t for t in (dimg, dtxt) if t is not None))
+        ctx.have = (dimg is not None, dtxt is not None)
+        return (l_it + l_ti).reshape(())
+
+    @staticmethod
+    def backward(ctx, dloss):
+        saved = list(ctx.saved_tensors)
+        dimg = saved.pop(0) * dloss if ctx.have[0] else None
+        dtxt = saved.pop(0) * dloss if ctx.have[1] else None
+        return dimg, dtxt, None, None, None
+
+
+def clip_loss(img, txt, img_group=None, txt_group=None, logit_scale=100.0):
+    """CLIP's symmetric contrastive loss of unit image rows ``img`` [B, d] and unit caption rows ``txt`` [M, d], a scalar
+    with autograd: 1/2 (mean over images of the image -> text loss + mean over captions of the text -> image loss), every
+    caption whose group equals an image's being its positive (``contrastive_objective``).  With both groups None the rows
+    are pairs (M == B, group = row index).  The means divide by B and M, not by the number of rows that have a positive."""
+    if img_group is None and txt_group is None:
+        if img.shape[0] != txt.shape[0]:
+            raise ValueError(f"clip_loss without groups pairs row i with row i: {img.shape[0]} images, {txt.shape[0]} captions")
+        img_group = txt_group = torch.arange(img.shape[0], device=img.device, dtype=torch.int32)
+    elif img_group is None or txt_group is None:
+        raise ValueError("clip_loss needs both img_group and txt_group, or neither")
+    return ClipLossFn.apply(img, txt, img_group.to(torch.int32).contiguous(), txt_group.to(torch.int32).contiguous(),
+                            float(logit_scale))

@@ -671,6 +671,35 @@ def evaluate_lora(args, clip_model, loader, templates=None, textual_features=Non
     return 100.0 * acc / tot, 100.0 * acc1 / tot, 100.0 * acc2 / tot
 
 
+@torch.no_grad()
+def evaluate_retrieval(model, images, captions, image_groups=None, caption_groups=None, ks=(1, 5, 10)):
+    """Recall@k of image -> text and text -> image retrieval over ``images`` [B, 3, R, R] and ``captions`` [M, 77]: a
+    query is a hit at k when ANY of its positives (the rows of the other side whose group equals its own; with both
+    groups None, M == B and row i pairs with row i) is among its k best matches (ties to the lower index, ``ops.topk``).
+    Returns {"i2t": {k: recall}, "t2i": {k: recall}} as fractions of B and of M (k is capped at the other side's size).
+    Synchronises (it returns Python floats)."""
+    eng = model.engine
+    dev = model.device
+    B, M = images.shape[0], captions.shape[0]
+    if (image_groups is None) != (caption_groups is None):
+        raise ValueError("evaluate_retrieval needs both image_groups and caption_groups, or neither")
+    if image_groups is None:
+        if B != M:
+            raise ValueError(f"evaluate_retrieval without groups pairs image i with caption i: {B} images, {M} captions")
+        image_groups = caption_groups = torch.arange(B)
+    ig, cg = image_groups.to(dev).long(), caption_groups.to(dev).long()
+    feat, _ = eng.vit_forward(images.to(dev), False, 0)
+    emb, _ = eng.text_forward(captions, None, False, 0)
+    img, txt = ops.l2norm_fwd(feat), ops.class_mean_fwd(emb, M, 1)
+    out = {}
+    for name, q, k, qg, kg in (("i2t", img, txt, ig, cg), ("t2i", txt, img, cg, ig)):
+        n = k.shape[0]
+        top = ops.topk(ops.gemm_nt(q, k, alpha=100.0), min(max(ks), n)).long()
+        hit = (kg[top] == qg[:, None]) & (qg[:, None] >= 0)
+        out[name] = {kk: int(hit[:, :min(kk, n)].any(dim=1).sum()) / q.shape[0] for kk in ks}
+    return out
+
+
 # ----------------------------------------------------------------------------------------------
 # flat trainable buffer + stage-1 step (lora_train_vlp.py:946,956-1002)
 # ----------------------------------------------------------------------------------------------
@@ -1236,6 +1265,7 @@ class LoRATrainer(FlatStepTrainer):
                              "only as f16 images there): use precision 'fp32' or 'bf16x3'")
         self.prompt_ctx = prompt_ctx
         self.logit_scale = logit_scale
+        self._pbuf = {}  # exchange buffers of forward_backward_pairs
         # all_gather + reduce_scatter + all_reduce, or the all_reduce alone (forward_backward recounts from text_lo)
         self._init_flat_step(lr, weight_decay, betas, eps, process_group, shard_text, (3, 1), loss_scale, init_scale,
                              growth_factor, backoff_factor, growth_interval, max_grad_norm, ema_decay)
@@ -1320,6 +1350,168 @@ class LoRATrainer(FlatStepTrainer):
              row_offset: int = 0):
         self.flat.zero_grad()
         out = self.forward_backward(images, captions, target, templates_per_class, global_batch, row_offset)
+        self.optimizer_step()
+        return out
+
+    # -- contrastive (image, caption) pairs ----------------------------------------------------------------
+    def _pair_buffers(self, images: int, captions: int, width: int):
+        """The fixed exchange buffers of ``forward_backward_pairs`` under data parallelism, per side ("img", "cap"): the
+        send block (padding rows written by nobody: they stay zero), the gathered table, its gradient table, this rank's
+        block of the reduced gradient; and one int32 pair for both group vectors."""
+        from clipfs import dist as D
+        key = (images, captions, width)
+        b = self._pbuf.get(key)
+        if b is None:
+            dev = self.flat.params.device
+            b = {}
+            for side, n in (("img", images), ("cap", captions)):
+                s = D.block_rows(n, self.world)
+                b[side] = dict(S=s, send=torch.zeros(s, width, device=dev), full=torch.empty(self.world * s, width, device=dev),
+                               dfull=torch.empty(self.world * s, width, device=dev), dmine=torch.empty(s, width, device=dev))
+            s2 = b["img"]["S"] + b["cap"]["S"]
+            b["gsend"] = torch.full((1, s2), -1, device=dev, dtype=torch.int32)
+            b["gfull"] = torch.empty(self.world, s2, device=dev, dtype=torch.int32)
+            self._pbuf = {key: b}
+        return b
+
+    def forward_backward_pairs(self, images, captions, image_groups=None, caption_groups=None,
+                               global_batch: Optional[int] = None, global_captions: Optional[int] = None,
+                               row_offset: int = 0, caption_offset: int = 0):
+        """CLIP's own objective over (image, caption) pairs with group ids: every caption whose group equals an image's is
+        its positive (the UniCL / supervised-contrastive form), in both directions:
+
+            loss = 1/2 ( (1/B_g) sum over images of loss_i  +  (1/M_g) sum over captions of loss_j )
+
+        with loss_i the multi-positive InfoNCE row loss of ``ops.contrastive_objective``.  The sums are divided by the
+        ROW COUNTS B_g and M_g, not by the number of rows that have a positive: the latter would need a device -> host
+        read, and this method never synchronises.
+
+        ``images`` [B, 3, R, R] and ``captions`` [M, 77] are THIS RANK's rows (``row_offset`` / ``caption_offset`` of
+        the global batch of ``global_batch`` images and ``global_captions`` captions); M need not equal B (unique class
+        captions, several captions per image).  ``image_groups`` [B] / ``caption_groups`` [M] are integer ids >= 0 (a
+        negative id masks the row out); with both None the rows are pairs: M_g == B_g and group = global row index.
+        Accumulates gradients into the flat buffer; returns (loss_sum_local [1], correct_i2t_local [1],
+        correct_t2i_local [1]): this rank's share of the loss above and the local images / captions whose best match is
+        a positive.
+
+        Towers, side stream, gradient floors (``last_plan``), dropout rows by global row, loss scaling: as
+        ``forward_backward``.  A tower with nothing to train gets no feature gradient formed and no backward.
+
+        Data parallel (class-sharded text only: ``shard_text=False`` is refused): rank r holds image rows
+        ``block_bounds(B_g, r, world)`` and caption rows ``block_bounds(M_g, r, world)``.  Its unit image block and unit
+        caption block are all-gathered (padding rows zero, group -1), given groups are gathered as one int32 vector;
+        the objective runs twice (local images x all captions, local captions x all images); the two gathered-feature
+        gradient tables are reduce-scattered; ``optimizer_step`` all-reduces the flat gradient.  Collectives per step:
+        2 all_gather (+ 1 with given groups) + 1 reduce_scatter per trained tower + 1 all_reduce -- 5 for plain pairs,
+        6 with groups (``collectives_per_step``)."""
+        from clipfs import dist as D
+        m = self.model
+        eng = m.engine
+        eng.refuse_merged("LoRATrainer.forward_backward_pairs")
+        live = self.live
+        if live and not self.shard_text:
+            raise ValueError("forward_backward_pairs: shard_text=False is not supported for pairs (every rank would encode "
+                             "every caption): build the trainer with shard_text=True")
+        if (image_groups is None) != (caption_groups is None):
+            raise ValueError("forward_backward_pairs needs both image_groups and caption_groups, or neither")
+        B, M = images.shape[0], captions.shape[0]
+        Bg, Mg = global_batch or B * self.world, global_captions or M * self.world
+        paired = image_groups is None
+        if paired and Mg != Bg:
+            raise ValueError(f"forward_backward_pairs without groups pairs image i with caption i: {Bg} images, {Mg} captions")
+        b_lo, b_hi = D.block_bounds(Bg, self.rank, self.world) if live else (row_offset, row_offset + B)
+        c_lo, c_hi = D.block_bounds(Mg, self.rank, self.world) if live else (caption_offset, caption_offset + M)
+        if B < 1 or M < 1 or (live and (B, M, row_offset, caption_offset) != (b_hi - b_lo, c_hi - c_lo, b_lo, c_lo)):
+            raise ValueError(f"forward_backward_pairs: rank {self.rank} of {self.world} takes image rows [{b_lo}, {b_hi}) and "
+                             f"caption rows [{c_lo}, {c_hi}) (block_bounds, at least one of each), got {B} images at "
+                             f"{row_offset} and {M} captions at {caption_offset}")
+        self.flat.sync_packed()
+        seed = eng.next_seed() if m.training else 0
+        d = m.embed_dim
+        dev = self.flat.params.device
+        self._refuse_sharded_dropout()
+        xb = self._pair_buffers(Bg, Mg, d) if live else None
+        text_lo = eng.text_plan(self.prompt_ctx is not None)
+        vis_lo = eng.image_plan()
+        want_i, want_t = vis_lo is not None, text_lo is not None
+        self.last_plan = {"text": text_lo, "vision": vis_lo}
+        if live:
+            self.collectives_per_step = 2 + (0 if paired else 1) + int(want_i) + int(want_t) + 1
+        main = torch.cuda.current_stream()
+        side = self._side_stream() if self.overlap_towers else main
+        side.wait_stream(main)
+        with torch.cuda.stream(side):
+            emb, tctx = eng.text_forward(captions, self.prompt_ctx, True, seed, row0=caption_offset)
+            txt = ops.class_mean_fwd(emb, M, 1, out=None if xb is None else xb["cap"]["send"][:M])  # unit rows
+        feat, ictx = eng.vit_forward(images, True, seed, row0=row_offset)
+        img_n, inv = ops.l2norm_fwd(feat, save_inv=True, out=None if xb is None else xb["img"]["send"][:B])
+        if paired:
+            ig = torch.arange(row_offset, row_offset + B, device=dev, dtype=torch.int32)
+            cg = torch.arange(caption_offset, caption_offset + M, device=dev, dtype=torch.int32)
+        else:
+            ig = image_groups.to(device=dev, dtype=torch.int32).contiguous()
+            cg = caption_groups.to(device=dev, dtype=torch.int32).contiguous()
+        main.wait_stream(side)
+        if live:
+            si, sc = xb["img"]["S"], xb["cap"]["S"]
+            img_all = self._timed("all_gather", lambda: D.allgather_blocks(xb["img"]["send"], xb["img"]["full"], self.pg))
+            txt_all = self._timed("all_gather", lambda: D.allgather_blocks(xb["cap"]["send"], xb["cap"]["full"], self.pg))
+            if paired:  # global row g carries group g, padding rows -1: nothing to exchange
+                ig_all = torch.arange(self.world * si, device=dev, dtype=torch.int32)
+                cg_all = torch.arange(self.world * sc, device=dev, dtype=torch.int32)
+                ig_all[Bg:] = -1
+                cg_all[Mg:] = -1
+            else:
+                xb["gsend"][0, :B] = ig
+                xb["gsend"][0, si:si + M] = cg
+                g_all = self._timed("all_gather", lambda: D.allgather_blocks(xb["gsend"], xb["gfull"], self.pg))
+                ig_all, cg_all = g_all[:, :si].reshape(-1), g_all[:, si:].reshape(-1)
+            d_txt_all, d_img_all = (xb["cap"]["dfull"] if want_t else None), (xb["img"]["dfull"] if want_i else None)
+            my_img, my_cap = self.rank * si, self.rank * sc
+        else:
+            img_all, txt_all, ig_all, cg_all = img_n, txt, ig, cg
+            d_txt_all = torch.empty(M, d, device=dev) if want_t else None
+            d_img_all = None
+            my_img = my_cap = 0
+        self.last_features = (img_n, txt)
+        s = self.logit_scale
+        # local images x all captions: the images' own gradient, and the caption-gradient table written afresh
+        l_it, _, c_it, d_img_own, _ = ops.contrastive_objective(img_n, txt_all, ig, cg_all, s, 0.5 / Bg, self.scale_state,
+                                                                dk=d_txt_all, want_dq=want_i, want_dk=False, accumulate=False)
+        # local captions x all images: added into this rank's rows of the caption table; the image side is added to the
+        # images' own gradient (one process) or written afresh into the image-gradient table (data parallel)
+        l_ti, _, c_ti, _, _ = ops.contrastive_objective(txt, img_all, cg, ig_all, s, 0.5 / Mg, self.scale_state,
+                                                        dq=d_txt_all[my_cap:my_cap + M] if want_t else None,
+                                                        dk=d_img_all if live else d_img_own, want_dq=False, want_dk=False,
+                                                        accumulate=(True, not live))
+        loss_sum = l_it + l_ti
+        if want_t:
+            if live:
+                mine = self._timed("reduce_scatter", lambda: D.reduce_scatter_blocks(xb["cap"]["dfull"], xb["cap"]["dmine"], self.pg))
+                d_txt_local = mine[:M]
+            else:
+                d_txt_local = d_txt_all
+            side.wait_stream(main)
+            with torch.cuda.stream(side):
+                d_emb = ops.class_mean_bwd(emb, d_txt_local, M, 1)
+                eng.text_backward(tctx, d_emb, None if self.prompt_ctx is None else self.prompt_ctx.grad_slot)
+        if want_i:
+            if live:
+                d_img_all[my_img:my_img + B].add_(d_img_own)
+                mine = self._timed("reduce_scatter", lambda: D.reduce_scatter_blocks(xb["img"]["dfull"], xb["img"]["dmine"], self.pg))
+                d_img_n = mine[:B]
+            else:
+                d_img_n = d_img_own
+            eng.vit_backward(ictx, ops.l2norm_bwd(d_img_n.contiguous(), img_n, inv))
+        main.wait_stream(side)
+        return loss_sum, c_it, c_ti
+
+    def step_pairs(self, images, captions, image_groups=None, caption_groups=None, global_batch: Optional[int] = None,
+                   global_captions: Optional[int] = None, row_offset: int = 0, caption_offset: int = 0):
+        """``zero_grad``, ``forward_backward_pairs``, ``optimizer_step``: one training step on (image, caption) pairs."""
+        self.flat.zero_grad()
+        out = self.forward_backward_pairs(images, captions, image_groups, caption_groups, global_batch, global_captions,
+                                          row_offset, caption_offset)
         self.optimizer_step()
         return out
 
