@@ -16,6 +16,8 @@ CSRC = os.path.join(HERE, "csrc")
 INCLUDE = os.path.join(os.path.dirname(HERE), "include")
 OUT = os.path.join(HERE, "clipfs", "libclipfs_hip.so")
 SOURCES = ["common.hip", "gemm.hip", "gemm_bf16.hip", "gemm_f16.hip", "norm.hip", "attention.hip", "attention_f16.hip", "attention_mfma.hip", "attention_mfma16.hip", "lora.hip", "lora_mfma.hip", "lora_merge.hip", "elem.hip", "mta.hip", "views.hip", "crops.hip", "resnet.hip", "bpe.hip", "bias_grad.hip", "prompts.hip", "tower.hip", "cache_head.hip", "tpt.hip", "contrastive.hip"]
+# every header a source may include: an edit to one rebuilds every object and changes the whole-library stamp
+HEADERS = tuple(os.path.join(CSRC, h) for h in ("common.h", "gemm_common.h", "lora.h", "convert16.h", "logits_tile.h")) + (os.path.join(INCLUDE, "clipfs.h"),)
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-I", INCLUDE, "-I", CSRC, "-Wall",
          "-Wno-unused-function", "-ffp-contract=off"] + os.environ.get("HIPCC_EXTRA", "").split()
@@ -39,10 +41,9 @@ def _stamp(paths) -> str:
 def source_stamps():
     """(whole-library stamp, fp32-GEMM stamp) of the sources in the tree -- what clipfs_source_stamp() /
     clipfs_gemm_source_stamp() of a library built from them return."""
-    headers = [os.path.join(CSRC, h) for h in ("common.h", "gemm_common.h", "lora.h", "convert16.h")] + [os.path.join(INCLUDE, "clipfs.h")]
     # common.hip only carries the stamps themselves: leave it out so that a stamp does not depend on itself
     srcs = [os.path.join(CSRC, s) for s in SOURCES if s != "common.hip" and os.path.exists(os.path.join(CSRC, s))]
-    return (_stamp(sorted(srcs) + headers),
+    return (_stamp(sorted(srcs) + list(HEADERS)),
             _stamp([os.path.join(CSRC, "gemm.hip"), os.path.join(CSRC, "gemm_common.h"), os.path.join(CSRC, "common.h")]))
 
 
@@ -52,7 +53,6 @@ def build(force: bool = False, verbose: bool = True, tag: str = "") -> str:
     bdir = os.path.join(CSRC, "build", tag) if tag else os.path.join(CSRC, "build")
     out = OUT.replace(".so", f"_{tag}.so") if tag else OUT
     os.makedirs(bdir, exist_ok=True)
-    headers = [os.path.join(CSRC, h) for h in ("common.h", "gemm_common.h", "lora.h", "convert16.h")] + [os.path.join(INCLUDE, "clipfs.h")]
     srcs = [s for s in SOURCES if os.path.exists(os.path.join(CSRC, s))]
     lib_stamp, gemm_stamp = source_stamps()
     stamp_file = os.path.join(bdir, "stamp.txt")
@@ -66,7 +66,7 @@ def build(force: bool = False, verbose: bool = True, tag: str = "") -> str:
         extra = []
         if s == "common.hip":  # carries the source stamps: rebuilt whenever any source changed
             extra = [f'-DCLIPFS_SOURCE_STAMP="{lib_stamp}"', f'-DCLIPFS_GEMM_STAMP="{gemm_stamp}"']
-        if force or _newer(obj, [src] + headers) or (extra and stamp_now != stamp_old):
+        if force or _newer(obj, [src, *HEADERS]) or (extra and stamp_now != stamp_old):
             jobs.append([HIPCC, *FLAGS, *extra, "-c", src, "-o", obj])
 
     def run(cmd):

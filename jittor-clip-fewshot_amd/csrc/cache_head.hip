@@ -4,49 +4,31 @@
 //   a[b,k] = f[b,:] . K[k,:]     E[b,k] = exp(-beta (1 - a[b,k]))     S[b,c] = sum of E over the keys of class c
 //   logits[b,c] = base[b,c] + alpha S[b,c]
 //
-// The [B, NK] affinity never leaves the chip.  Every kernel forms 32 x 32 affinity tiles on v_mfma_f32_32x32x2_f32 the
-// way attention_mfma.hip forms its scores: in the logits and search kernels both operands are row-major rows read
-// straight from global memory / L2 (a lane reads 128 contiguous bytes of its row per 64-feature step; the K-slot <->
-// feature assignment of an MFMA sum is free as long as A and B agree, so each half-wave takes one contiguous half of the
-// step), in the backward they pass through LDS; the product comes out with a lane holding 16 rows of the A side for ONE
-// row of the B side.  No float atomics anywhere: every float output
+// The [B, NK] affinity never leaves the chip.  Every kernel forms 32 x 32 affinity tiles on v_mfma_f32_32x32x2_f32
+// (logits_tile.h): in the logits and search kernels both operands are rows read straight from global memory / L2
+// (tile_dots), in the backward they pass through LDS (tile_grad_walk).  No float atomics anywhere: every float output
 // element is written by one thread of one workgroup, and the order of every sum depends on the shapes and `off` only.
 //
 //   logits  one workgroup per (32 queries, chunk of classes) walks the chunk's keys in tiles of 128 (one wave per 32
 //           keys), stages E in LDS and lets one thread add each (query, class) run in ascending key order; a run that
 //           straddles tiles travels in a per-query carry.
 //   bwd     one workgroup per (32 own rows, 512 features): own = keys for dK, queries for df.  It walks the other side
-//           in tiles of 32 ascending: both tiles pass through LDS in 128-feature chunks (the next chunk in flight while
-//           this one is multiplied), the four waves split each chunk for the affinity tile (partials added in wave
-//           order), G is formed once in LDS, then every wave contracts G with the other side's rows into its 128 features.
+//           in tiles of 32 ascending (tile_grad_walk) with G = alpha beta E dlogits.
 //   search  one workgroup per (32 queries, beta chunk, alpha chunk) walks ALL keys; because the keys are class-sorted,
 //           classes complete in ascending order, so per (query, beta, alpha) a running (best value, best class) in LDS
 //           is all that is kept.  The affinity is recomputed per chunk.
-#include "common.h"
+#include "logits_tile.h"
 
 #include <math.h>
 
 namespace clipfs {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
 namespace {
 
 constexpr int CH_THREADS = 256;      // 4 waves
 constexpr int CH_QT = 32;            // queries (own rows) per workgroup
 constexpr int CH_KT = 128;           // keys per tile of the logits / search walk: 32 per wave
-constexpr int CH_FEAT = 512;         // most features per backward workgroup: 4 waves x 4 accumulators x 32
-constexpr int CH_PS = 33;            // row stride of the backward's affinity partials (conflict-free transposed read)
 constexpr int CH_SEARCH_STATE = 120 * 1024;  // bytes of LDS the search gives its (best value, best class) records
 constexpr int CH_MAX_AC = 256;       // alphas per search workgroup
-constexpr float CH_LOG2E = 1.4426950408889634f;
-
-__device__ __forceinline__ f32x16 ch_mfma(float a, float b, f32x16 c) {
-  return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0);
-}
-// row of the A side that register r of lane (half h) holds
-__device__ __forceinline__ int ch_row(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
 
 // the class of key k: the largest c in [0, C) with off[c] <= k (the empty classes before it share its offset)
 __device__ __forceinline__ int ch_class_of(const int* __restrict__ off, int C, int k) {
@@ -56,91 +38,6 @@ __device__ __forceinline__ int ch_class_of(const int* __restrict__ off, int C, i
     if (off[mid] <= k) lo = mid; else hi = mid - 1;
   }
   return lo;
-}
-
-// acc[A row a0 + ch_row(r, h)][B row b0 + (lane & 31)] += sum over the 64-feature steps s0, s0 + sstep, ... < d.  Rows
-// past the end are clamped to the last row (their products are discarded by the caller), features >= d read as 0.
-__device__ __forceinline__ f32x16 ch_affinity(const float* __restrict__ A, int a0, int na, const float* __restrict__ Bm,
-                                              int b0, int nb, int d, int s0, int sstep, int lane) {
-  const int li = lane & 31, h = lane >> 5;
-  f32x16 acc;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-  const float* pa = A + (size_t)min(a0 + li, na - 1) * d + 32 * h;
-  const float* pb = Bm + (size_t)min(b0 + li, nb - 1) * d + 32 * h;
-  for (int s = s0; s < d; s += sstep) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      f32x4 va, vb;
-      va[0] = va[1] = va[2] = va[3] = 0.f;
-      vb = va;
-      if (s + 32 * h + 4 * j < d) {
-        va = *reinterpret_cast<const f32x4*>(pa + s + 4 * j);
-        vb = *reinterpret_cast<const f32x4*>(pb + s + 4 * j);
-      }
-#pragma unroll
-      for (int e = 0; e < 4; ++e) acc = ch_mfma(va[e], vb[e], acc);
-    }
-  }
-  return acc;
-}
-
-// The backward's affinity tile: 32 x 32 over the whole of d, the operands passing through LDS in chunks of CH_KC features
-// (16-byte global loads with a row's 128 features contiguous over 32 threads, where ch_affinity's lanes each walk a row
-// of their own).  Wave w takes features [32 w, 32 w + 32) of every chunk, half h 16 of them.  The next chunk -- after a
-// tile's last one, the first chunk of the tile at (a0n, b0n) -- is fetched into registers while this one is multiplied.
-constexpr int CH_KC = 128, CH_KST = CH_KC + 4;  // + 4: 16-byte rows, conflict-free ds_read_b128 over consecutive rows
-struct ChStage {
-  f32x4 ra[4], rb[4];
-  __device__ __forceinline__ void load(const float* __restrict__ A, int a0, int na, const float* __restrict__ Bm, int b0, int nb,
-                                       int d, int s, int tid) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int e = tid + CH_THREADS * i, row = e >> 5, c = s + 4 * (e & 31);
-      f32x4 z;
-      z[0] = z[1] = z[2] = z[3] = 0.f;
-      ra[i] = rb[i] = z;
-      if (c < d) {
-        ra[i] = *reinterpret_cast<const f32x4*>(A + (size_t)min(a0 + row, na - 1) * d + c);
-        rb[i] = *reinterpret_cast<const f32x4*>(Bm + (size_t)min(b0 + row, nb - 1) * d + c);
-      }
-    }
-  }
-  __device__ __forceinline__ void store(float* sA, float* sB, int tid) const {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int e = tid + CH_THREADS * i, at = (e >> 5) * CH_KST + 4 * (e & 31);
-      *reinterpret_cast<f32x4*>(sA + at) = ra[i];
-      *reinterpret_cast<f32x4*>(sB + at) = rb[i];
-    }
-  }
-};
-// `st` holds chunk 0 of this tile on entry and chunk 0 of the next tile (if any) on return.  Every thread of the
-// workgroup calls it (it synchronises).
-__device__ __forceinline__ f32x16 ch_affinity_staged(ChStage& st, const float* __restrict__ A, int a0, int na,
-                                                     const float* __restrict__ Bm, int b0, int nb, int d, int a0n, int b0n,
-                                                     bool has_next, float* sA, float* sB, int tid) {
-  const int lane = tid & 63, w = tid >> 6, li = lane & 31, h = lane >> 5;
-  f32x16 acc;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-  const float* pa = sA + li * CH_KST + 32 * w + 16 * h;
-  const float* pb = sB + li * CH_KST + 32 * w + 16 * h;
-  for (int s = 0; s < d; s += CH_KC) {
-    __syncthreads();  // the last chunk's reads are done
-    st.store(sA, sB, tid);
-    __syncthreads();
-    if (s + CH_KC < d) st.load(A, a0, na, Bm, b0, nb, d, s + CH_KC, tid);
-    else if (has_next) st.load(A, a0n, na, Bm, b0n, nb, d, 0, tid);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const f32x4 va = *reinterpret_cast<const f32x4*>(pa + 4 * j);
-      const f32x4 vb = *reinterpret_cast<const f32x4*>(pb + 4 * j);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) acc = ch_mfma(va[e], vb[e], acc);
-    }
-  }
-  return acc;
 }
 
 __device__ __forceinline__ float ch_exp(float a, float bl2) { return __builtin_amdgcn_exp2f((a - 1.f) * bl2); }
@@ -156,7 +53,7 @@ __global__ __launch_bounds__(CH_THREADS) void cache_logits_kernel(const float* _
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, li = lane & 31, h = lane >> 5;
   const int q0 = blockIdx.x * CH_QT;
   const int c0 = blockIdx.y * cchunk, c1 = min(C, c0 + cchunk);
-  const float bl2 = beta * CH_LOG2E;
+  const float bl2 = beta * TILE_LOG2E;
   const int kb = min(max(off[c0], 0), NK), ke = min(max(off[c1], kb), NK);
   // empty classes: S = 0
   for (int p = tid; p < 32 * (c1 - c0); p += CH_THREADS) {
@@ -168,9 +65,9 @@ __global__ __launch_bounds__(CH_THREADS) void cache_logits_kernel(const float* _
     const int k1 = min(k0 + CH_KT, ke);
     const int kw = k0 + 32 * w;
     if (kw < k1) {  // wave-uniform
-      const f32x16 a = ch_affinity(K, kw, NK, f, q0, B, d, 0, 64, lane);
+      const f32x16 a = tile_dots(K, kw, NK, f, q0, B, d, 0, 64, lane);
 #pragma unroll
-      for (int r = 0; r < 16; ++r) Es[(32 * w + ch_row(r, h)) * 32 + li] = ch_exp(a[r], bl2);
+      for (int r = 0; r < 16; ++r) Es[(32 * w + tile_row(r, h)) * 32 + li] = ch_exp(a[r], bl2);
     }
     if (tid == 0) {
       s_rng[0] = ch_class_of(off, C, k0);
@@ -198,86 +95,32 @@ __global__ __launch_bounds__(CH_THREADS) void cache_logits_kernel(const float* _
 // ------------------------------------------------------------------------------------------------- backward
 // out[x, :] (+)= sum_y G(x, y) Y[y, :], G = alpha beta E[b,k] dlogits[b, class(k)], (b, k) = (y, x) for OWN_KEY (dK), (x, y)
 // otherwise (df).
-// NACC: 32-feature accumulators per wave, a workgroup owning 128 NACC features: 4 where the own tiles alone fill the
-// machine, 1 (four times the workgroups, each forming the affinity tile again) where they do not.
+// NACC: 32-feature accumulators per wave (logits_tile.h).
+template <bool OWN_KEY>
+struct ChGrad {
+  const int* off;
+  const float* dlog;
+  int* cls_s;  // [32] class of the key tile's keys
+  int C, NY, ldd;
+  float bl2, ab;
+  __device__ __forceinline__ void tile(int y0, int tid) const {
+    if (!OWN_KEY && tid < 32) cls_s[tid] = ch_class_of(off, C, min(y0 + tid, NY - 1));
+  }
+  __device__ __forceinline__ float g(float a, int xi, int yi, int own, int oth) const {
+    const int b = OWN_KEY ? yi : xi, c = cls_s[OWN_KEY ? own : oth];
+    return ab * ch_exp(a, bl2) * dlog[(size_t)b * ldd + c];
+  }
+};
 template <bool OWN_KEY, bool ACCUM, int NACC>
 __global__ __launch_bounds__(CH_THREADS) __attribute__((amdgpu_waves_per_eu(2, NACC == 4 ? 2 : 8))) void cache_bwd_kernel(const float* __restrict__ X, const float* __restrict__ Y,
                                                                const int* __restrict__ off, const float* __restrict__ dlog,
                                                                float* __restrict__ out, int NX, int NY, int C, int d, int ldd,
                                                                float alpha, float beta) {
-  __shared__ __attribute__((aligned(16))) float sX[32 * CH_KST];  // a chunk of the own rows
-  __shared__ __attribute__((aligned(16))) float sY[32 * CH_KST];  //   ... of the other side's tile
-  __shared__ float Ps[4][32 * CH_PS];  // per wave: [own][other] partial affinity over its features of every chunk
-  __shared__ float Gs[32 * 32];        // [other][own]
-  __shared__ int cls_s[32];            // class of the key tile's keys
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, li = lane & 31, h = lane >> 5;
-  const int x0 = blockIdx.x * 32;
-  const int fw = (blockIdx.y * 4 + w) * 32 * NACC;  // this wave's first feature
-  const float bl2 = beta * CH_LOG2E, ab = alpha * beta;
-  f32x16 acc[NACC];
-#pragma unroll
-  for (int a = 0; a < NACC; ++a)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[a][r] = 0.f;
+  __shared__ int cls_s[32];
+  const int tid = threadIdx.x, x0 = blockIdx.x * 32;
   if (OWN_KEY && tid < 32) cls_s[tid] = ch_class_of(off, C, min(x0 + tid, NX - 1));
-  ChStage st;
-  st.load(X, x0, NX, Y, 0, NY, d, 0, tid);
-  for (int y0 = 0; y0 < NY; y0 += 32) {
-    const f32x16 s = ch_affinity_staged(st, X, x0, NX, Y, y0, NY, d, x0, y0 + 32, y0 + 32 < NY, sX, sY, tid);
-    // the first accumulator's operands of the other side: in flight while G is formed
-    float y0v[16];
-    {
-      const int ft = fw + li;
-#pragma unroll
-      for (int i = 0; i < 16; ++i) y0v[i] = ft < d ? Y[(size_t)min(y0 + 16 * h + i, NY - 1) * d + ft] : 0.f;
-    }
-#pragma unroll
-    for (int r = 0; r < 16; ++r) Ps[w][ch_row(r, h) * CH_PS + li] = s[r];
-    if (!OWN_KEY && tid < 32) cls_s[tid] = ch_class_of(off, C, min(y0 + tid, NY - 1));
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int e = tid + CH_THREADS * i, own = e & 31, oth = e >> 5;
-      const int at = own * CH_PS + oth;
-      const float a = ((Ps[0][at] + Ps[1][at]) + Ps[2][at]) + Ps[3][at];
-      const int xi = x0 + own, yi = y0 + oth;
-      float g = 0.f;
-      if (xi < NX && yi < NY) {
-        const int b = OWN_KEY ? yi : xi, c = cls_s[OWN_KEY ? own : oth];
-        g = ab * ch_exp(a, bl2) * dlog[(size_t)b * ldd + c];
-      }
-      Gs[oth * 32 + own] = g;
-    }
-    __syncthreads();
-    float ga[16];
-#pragma unroll
-    for (int i = 0; i < 16; ++i) ga[i] = Gs[(16 * h + i) * 32 + li];
-#pragma unroll
-    for (int a = 0; a < NACC; ++a) {
-      if (fw + 32 * a < d) {  // wave-uniform
-        const int ft = fw + 32 * a + li;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-          const float yv = a == 0 ? y0v[i] : (ft < d ? Y[(size_t)min(y0 + 16 * h + i, NY - 1) * d + ft] : 0.f);
-          acc[a] = ch_mfma(ga[i], yv, acc[a]);
-        }
-      }
-    }
-  }
-#pragma unroll
-  for (int a = 0; a < NACC; ++a) {
-    const int ft = fw + 32 * a + li;
-    if (ft < d) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int xi = x0 + ch_row(r, h);
-        if (xi < NX) {
-          float* p = out + (size_t)xi * d + ft;
-          *p = ACCUM ? *p + acc[a][r] : acc[a][r];
-        }
-      }
-    }
-  }
+  const ChGrad<OWN_KEY> fn = {off, dlog, cls_s, C, NY, ldd, beta * TILE_LOG2E, alpha * beta};
+  tile_grad_walk<ACCUM, NACC>(X, Y, out, NX, NY, d, fn);
 }
 
 // ------------------------------------------------------------------------------------------------- search
@@ -312,7 +155,7 @@ __global__ __launch_bounds__(CH_THREADS) void cache_search_kernel(const float* _
   }
   for (int p = tid; p < JB * 32; p += CH_THREADS) carry[p] = 0.f;
   for (int p = tid; p < na; p += CH_THREADS) s_al[p] = alphas[i0 + p];
-  for (int p = tid; p < nj; p += CH_THREADS) s_bl2[p] = betas[j0 + p] * CH_LOG2E;
+  for (int p = tid; p < nj; p += CH_THREADS) s_bl2[p] = betas[j0 + p] * TILE_LOG2E;
   if (tid == 0) {
     int e0 = C;
     while (e0 > 0 && off[e0 - 1] >= NK) --e0;
@@ -323,9 +166,9 @@ __global__ __launch_bounds__(CH_THREADS) void cache_search_kernel(const float* _
   for (int k0 = 0; k0 < NK; k0 += CH_KT) {
     const int kn = min(CH_KT, NK - k0);
     if (32 * w < kn) {  // wave-uniform
-      const f32x16 a = ch_affinity(K, k0 + 32 * w, NK, f, q0, B, d, 0, 64, lane);
+      const f32x16 a = tile_dots(K, k0 + 32 * w, NK, f, q0, B, d, 0, 64, lane);
 #pragma unroll
-      for (int r = 0; r < 16; ++r) As[(32 * w + ch_row(r, h)) * 32 + li] = a[r];
+      for (int r = 0; r < 16; ++r) As[(32 * w + tile_row(r, h)) * 32 + li] = a[r];
     }
     if (tid < kn) {
       const int k = k0 + tid, c = ch_class_of(off, C, k);
@@ -450,12 +293,9 @@ extern "C" int clipfs_cache_plan(int op, int B, int NK, int C, int d, int nA, in
     p.lds_bytes = (unsigned)((CH_KT * 32 + 2 * 32 + 2) * sizeof(float));
   } else if (op == CLIPFS_CACHE_OP_BWD_DK || op == CLIPFS_CACHE_OP_BWD_DF) {
     const int own = op == CLIPFS_CACHE_OP_BWD_DK ? NK : B;
-    p.grid_x = (unsigned)((own + 31) / 32);
-    // 512 features per workgroup where that gives every compute unit one; else 128: four times the workgroups
-    p.feat_chunk = (long long)p.grid_x * ((d + CH_FEAT - 1) / CH_FEAT) >= 256 ? CH_FEAT : CH_FEAT / 4;
-    p.grid_y = (unsigned)((d + p.feat_chunk - 1) / p.feat_chunk);
+    tile_grad_plan(p, own, d);
     p.grid_z = 1;
-    p.lds_bytes = (unsigned)((2 * 32 * CH_KST + 4 * 32 * CH_PS + 32 * 32 + 32) * sizeof(float));
+    p.lds_bytes = tile_grad_lds_bytes(32);  // + cls_s
   } else {
     const int ac = nA < CH_MAX_AC ? nA : CH_MAX_AC;
     int jb = CH_SEARCH_STATE / (ac * 32 * 8 + 32 * 4 + 4);  // per beta: the records, its carry row, its factor
@@ -504,20 +344,12 @@ extern "C" int clipfs_cache_bwd(const float* f, const float* K, const int32_t* o
   CLIPFS_REQUIRE(lddl >= C, "clipfs_cache_bwd: lddl = %d below C = %d", lddl, C);
   CLIPFS_REQUIRE(dK != K && dK != f && df != f && df != K && (!df || df != dK), "clipfs_cache_bwd: dK / df alias an input");
   CLIPFS_CHECK(ch_check_scalars(alpha, beta));
-  if (pk.feat_chunk == CH_FEAT)
-    hipLaunchKernelGGL((cache_bwd_kernel<true, true, 4>), dim3(pk.grid_x, pk.grid_y), dim3(pk.block), 0, (hipStream_t)stream, K,
-                       f, off, dlogits, dK, NK, B, C, d, lddl, alpha, beta);
-  else
-    hipLaunchKernelGGL((cache_bwd_kernel<true, true, 1>), dim3(pk.grid_x, pk.grid_y), dim3(pk.block), 0, (hipStream_t)stream, K,
-                       f, off, dlogits, dK, NK, B, C, d, lddl, alpha, beta);
+  TILE_GRAD_LAUNCH_NACC(cache_bwd_kernel, true, true, pk, (hipStream_t)stream, K, f, off, dlogits, dK, NK, B, C, d, lddl, alpha,
+                        beta);
   CLIPFS_CHECK(launch_status());
   if (df) {
-    if (pf.feat_chunk == CH_FEAT)
-      hipLaunchKernelGGL((cache_bwd_kernel<false, false, 4>), dim3(pf.grid_x, pf.grid_y), dim3(pf.block), 0, (hipStream_t)stream,
-                         f, K, off, dlogits, df, B, NK, C, d, lddl, alpha, beta);
-    else
-      hipLaunchKernelGGL((cache_bwd_kernel<false, false, 1>), dim3(pf.grid_x, pf.grid_y), dim3(pf.block), 0, (hipStream_t)stream,
-                         f, K, off, dlogits, df, B, NK, C, d, lddl, alpha, beta);
+    TILE_GRAD_LAUNCH_NACC(cache_bwd_kernel, false, false, pf, (hipStream_t)stream, f, K, off, dlogits, df, B, NK, C, d, lddl,
+                          alpha, beta);
     CLIPFS_CHECK(launch_status());
   }
   return CLIPFS_OK;

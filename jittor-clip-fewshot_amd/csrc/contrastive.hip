@@ -6,10 +6,9 @@
 //   loss_i = logsumexp_{j live} z[i,j] - (1/n_i) sum_{j in P_i} z[i,j]
 //   G[i,j] = w S (softmax_ij - [j in P_i] / n_i)      dq_i = s sum_j G[i,j] k_j      dk_j = s sum_i G[i,j] q_i
 //
-// Neither z nor G leaves the chip.  Every kernel forms 32 x 32 logits tiles on v_mfma_f32_32x32x2_f32 the way
-// cache_head.hip forms its affinity tiles (operands straight from global memory / L2 in the stats kernel, through LDS in
-// the gradient kernels).  No float atomics: every output element is written by one thread of one workgroup and the order
-// of every sum depends on the shapes alone.
+// Neither z nor G leaves the chip.  Every kernel forms 32 x 32 logits tiles on v_mfma_f32_32x32x2_f32 (logits_tile.h:
+// operands straight from global memory / L2 in the stats kernel, through LDS in the gradient kernels).  No float atomics:
+// every output element is written by one thread of one workgroup and the order of every sum depends on the shapes alone.
 //
 //   stats    one workgroup per (32 queries, chunk of keys) walks the chunk in tiles of 128 keys (one wave per 32); a lane
 //            keeps the running (max, sum of exponentials, sum of positive z, positive count, best value, best index) of
@@ -19,119 +18,22 @@
 //            its G exactly 0 in the gradient kernels.
 //   grad     one workgroup per (32 own rows, chunk of features): own = queries for dq, keys for dk.  It walks the other
 //            side in tiles of 32 ascending, recomputes z, forms G from lse in LDS and contracts it with the other side's
-//            rows (cache_bwd_kernel's structure).
-#include "common.h"
+//            rows (tile_grad_walk).
+#include "logits_tile.h"
 
 #include <limits.h>
 #include <math.h>
 
 namespace clipfs {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
 namespace {
 
 constexpr int CT_THREADS = 256;   // 4 waves
 constexpr int CT_QT = 32;         // queries (own rows) per workgroup
 constexpr int CT_KT = 128;        // keys per tile of the stats walk: 32 per wave
 constexpr int CT_MAX_CHUNK = 1024;  // most keys per stats workgroup
-constexpr int CT_FEAT = 512;      // most features per gradient workgroup: 4 waves x 4 accumulators x 32
-constexpr int CT_PS = 33;         // row stride of the gradient kernels' logits partials (conflict-free transposed read)
 constexpr int CT_FIELDS = 6;      // per (query, chunk): max, sum of exponentials, positive sum, positive count, best value, best index
-constexpr float CT_LOG2E = 1.4426950408889634f;
 
-__device__ __forceinline__ f32x16 ct_mfma(float a, float b, f32x16 c) {
-  return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0);
-}
-// row of the A side that register r of lane (half h) holds
-__device__ __forceinline__ int ct_row(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
-
-// acc[A row a0 + ct_row(r, h)][B row b0 + (lane & 31)] = the dot products over d.  Rows past the end are clamped to the
-// last row (their products are discarded by the caller), features >= d read as 0.
-__device__ __forceinline__ f32x16 ct_dots(const float* __restrict__ A, int a0, int na, const float* __restrict__ Bm, int b0,
-                                          int nb, int d, int lane) {
-  const int li = lane & 31, h = lane >> 5;
-  f32x16 acc;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-  const float* pa = A + (size_t)min(a0 + li, na - 1) * d + 32 * h;
-  const float* pb = Bm + (size_t)min(b0 + li, nb - 1) * d + 32 * h;
-  for (int s = 0; s < d; s += 64) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      f32x4 va, vb;
-      va[0] = va[1] = va[2] = va[3] = 0.f;
-      vb = va;
-      if (s + 32 * h + 4 * j < d) {
-        va = *reinterpret_cast<const f32x4*>(pa + s + 4 * j);
-        vb = *reinterpret_cast<const f32x4*>(pb + s + 4 * j);
-      }
-#pragma unroll
-      for (int e = 0; e < 4; ++e) acc = ct_mfma(va[e], vb[e], acc);
-    }
-  }
-  return acc;
-}
-
-// The gradient kernels' tile: 32 x 32 over the whole of d, the operands passing through LDS in chunks of CT_KC features.
-// Wave w takes features [32 w, 32 w + 32) of every chunk, half h 16 of them.  The next chunk -- after a tile's last one,
-// the first chunk of the next tile -- is fetched into registers while this one is multiplied.
-constexpr int CT_KC = 128, CT_KST = CT_KC + 4;  // + 4: 16-byte rows, conflict-free ds_read_b128 over consecutive rows
-struct CtStage {
-  f32x4 ra[4], rb[4];
-  __device__ __forceinline__ void load(const float* __restrict__ A, int a0, int na, const float* __restrict__ Bm, int b0, int nb,
-                                       int d, int s, int tid) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int e = tid + CT_THREADS * i, row = e >> 5, c = s + 4 * (e & 31);
-      f32x4 z;
-      z[0] = z[1] = z[2] = z[3] = 0.f;
-      ra[i] = rb[i] = z;
-      if (c < d) {
-        ra[i] = *reinterpret_cast<const f32x4*>(A + (size_t)min(a0 + row, na - 1) * d + c);
-        rb[i] = *reinterpret_cast<const f32x4*>(Bm + (size_t)min(b0 + row, nb - 1) * d + c);
-      }
-    }
-  }
-  __device__ __forceinline__ void store(float* sA, float* sB, int tid) const {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int e = tid + CT_THREADS * i, at = (e >> 5) * CT_KST + 4 * (e & 31);
-      *reinterpret_cast<f32x4*>(sA + at) = ra[i];
-      *reinterpret_cast<f32x4*>(sB + at) = rb[i];
-    }
-  }
-};
-// `st` holds chunk 0 of this tile on entry and chunk 0 of the next tile (if any) on return.  Every thread of the
-// workgroup calls it (it synchronises).
-__device__ __forceinline__ f32x16 ct_dots_staged(CtStage& st, const float* __restrict__ A, int a0, int na,
-                                                 const float* __restrict__ Bm, int b0, int nb, int d, int b0n, bool has_next,
-                                                 float* sA, float* sB, int tid) {
-  const int lane = tid & 63, w = tid >> 6, li = lane & 31, h = lane >> 5;
-  f32x16 acc;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-  const float* pa = sA + li * CT_KST + 32 * w + 16 * h;
-  const float* pb = sB + li * CT_KST + 32 * w + 16 * h;
-  for (int s = 0; s < d; s += CT_KC) {
-    __syncthreads();  // the last chunk's reads are done
-    st.store(sA, sB, tid);
-    __syncthreads();
-    if (s + CT_KC < d) st.load(A, a0, na, Bm, b0, nb, d, s + CT_KC, tid);
-    else if (has_next) st.load(A, a0, na, Bm, b0n, nb, d, 0, tid);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const f32x4 va = *reinterpret_cast<const f32x4*>(pa + 4 * j);
-      const f32x4 vb = *reinterpret_cast<const f32x4*>(pb + 4 * j);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) acc = ct_mfma(va[e], vb[e], acc);
-    }
-  }
-  return acc;
-}
-
-__device__ __forceinline__ float ct_exp(float x) { return __builtin_amdgcn_exp2f(x * CT_LOG2E); }
+__device__ __forceinline__ float ct_exp(float x) { return __builtin_amdgcn_exp2f(x * TILE_LOG2E); }
 
 // work: CT_FIELDS planes of [chunks][R] partials, then lse [R] and 1 / n [R]
 __device__ __forceinline__ float* ct_field(float* work, int f, int chunks, int R) { return work + (size_t)f * chunks * R; }
@@ -152,10 +54,10 @@ __global__ __launch_bounds__(CT_THREADS) void contrastive_stats_kernel(const flo
   for (int k0 = c0; k0 < c1; k0 += CT_KT) {
     const int kw = k0 + 32 * w;
     if (kw < c1) {  // wave-uniform
-      const f32x16 a = ct_dots(k, kw, N, q, q0, R, d, lane);
+      const f32x16 a = tile_dots(k, kw, N, q, q0, R, d, 0, 64, lane);
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int j = kw + ct_row(r, h);  // ascending in r: a strict > keeps the lowest index of a tie
+        const int j = kw + tile_row(r, h);  // ascending in r: a strict > keeps the lowest index of a tie
         if (j < c1) {
           const int g = kg[j];
           if (g >= 0) {
@@ -268,100 +170,26 @@ __global__ __launch_bounds__(CT_THREADS) void contrastive_combine_kernel(float* 
 
 // ------------------------------------------------------------------------------------------------- gradients
 // out[x, :] (+)= sum_y g(x, y) Y[y, :], g = s w S (exp(z - lse_i) - [groups equal] / n_i) with (i, j) = (x, y) for OWN_Q
-// (dq: X = q, Y = k), (y, x) otherwise (dk: X = k, Y = q).  NACC: 32-feature accumulators per wave, a workgroup owning
-// 128 NACC features.
+// (dq: X = q, Y = k), (y, x) otherwise (dk: X = k, Y = q).  NACC: 32-feature accumulators per wave (logits_tile.h).
+template <bool OWN_Q>
+struct CtGrad {
+  const int *qg, *kg;
+  const float *lse, *invn;
+  float s, gs;
+  __device__ __forceinline__ void tile(int, int) const {}
+  __device__ __forceinline__ float g(float a, int xi, int yi, int, int) const {
+    const int qi = OWN_Q ? xi : yi, kj = OWN_Q ? yi : xi;
+    const int gk = kg[kj];
+    return gk >= 0 ? gs * (ct_exp(s * a - lse[qi]) - (gk == qg[qi] ? invn[qi] : 0.f)) : 0.f;
+  }
+};
 template <bool OWN_Q, bool ACCUM, int NACC>
 __global__ __launch_bounds__(CT_THREADS) __attribute__((amdgpu_waves_per_eu(2, NACC == 4 ? 2 : 8))) void contrastive_grad_kernel(
     const float* __restrict__ X, const float* __restrict__ Y, const int* __restrict__ qg, const int* __restrict__ kg,
     const float* __restrict__ lse, const float* __restrict__ invn, float* __restrict__ out, int NX, int NY, int d, float s,
     float weight, const float* __restrict__ state) {
-  __shared__ __attribute__((aligned(16))) float sX[32 * CT_KST];  // a chunk of the own rows
-  __shared__ __attribute__((aligned(16))) float sY[32 * CT_KST];  //   ... of the other side's tile
-  __shared__ float Ps[4][32 * CT_PS];  // per wave: [own][other] partial dot products over its features of every chunk
-  __shared__ float Gs[32 * 32];        // [other][own]
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, li = lane & 31, h = lane >> 5;
-  const int x0 = blockIdx.x * 32;
-  const int fw = (blockIdx.y * 4 + w) * 32 * NACC;  // this wave's first feature
-  const float gs = (weight * (state ? state[CLIPFS_SCALER_SCALE] : 1.f)) * s;
-  f32x16 acc[NACC];
-#pragma unroll
-  for (int a = 0; a < NACC; ++a)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[a][r] = 0.f;
-  CtStage st;
-  st.load(X, x0, NX, Y, 0, NY, d, 0, tid);
-  for (int y0 = 0; y0 < NY; y0 += 32) {
-    const f32x16 dots = ct_dots_staged(st, X, x0, NX, Y, y0, NY, d, y0 + 32, y0 + 32 < NY, sX, sY, tid);
-    // the first accumulator's operands of the other side: in flight while G is formed
-    float y0v[16];
-    {
-      const int ft = fw + li;
-#pragma unroll
-      for (int i = 0; i < 16; ++i) y0v[i] = ft < d ? Y[(size_t)min(y0 + 16 * h + i, NY - 1) * d + ft] : 0.f;
-    }
-#pragma unroll
-    for (int r = 0; r < 16; ++r) Ps[w][ct_row(r, h) * CT_PS + li] = dots[r];
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int e = tid + CT_THREADS * i, own = e & 31, oth = e >> 5;
-      const int at = own * CT_PS + oth;
-      const float a = ((Ps[0][at] + Ps[1][at]) + Ps[2][at]) + Ps[3][at];
-      const int xi = x0 + own, yi = y0 + oth;
-      float g = 0.f;
-      if (xi < NX && yi < NY) {
-        const int qi = OWN_Q ? xi : yi, kj = OWN_Q ? yi : xi;
-        const int gk = kg[kj];
-        if (gk >= 0) g = gs * (ct_exp(s * a - lse[qi]) - (gk == qg[qi] ? invn[qi] : 0.f));
-      }
-      Gs[oth * 32 + own] = g;
-    }
-    __syncthreads();
-    float ga[16];
-#pragma unroll
-    for (int i = 0; i < 16; ++i) ga[i] = Gs[(16 * h + i) * 32 + li];
-#pragma unroll
-    for (int a = 0; a < NACC; ++a) {
-      if (fw + 32 * a < d) {  // wave-uniform
-        const int ft = fw + 32 * a + li;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-          const float yv = a == 0 ? y0v[i] : (ft < d ? Y[(size_t)min(y0 + 16 * h + i, NY - 1) * d + ft] : 0.f);
-          acc[a] = ct_mfma(ga[i], yv, acc[a]);
-        }
-      }
-    }
-  }
-#pragma unroll
-  for (int a = 0; a < NACC; ++a) {
-    const int ft = fw + 32 * a + li;
-    if (ft < d) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int xi = x0 + ct_row(r, h);
-        if (xi < NX) {
-          float* p = out + (size_t)xi * d + ft;
-          *p = ACCUM ? *p + acc[a][r] : acc[a][r];
-        }
-      }
-    }
-  }
-}
-
-template <bool OWN_Q>
-void ct_launch_grad(const struct clipfs_contrastive_plan& p, bool accum, hipStream_t stream, const float* X, const float* Y,
-                    const int* qg, const int* kg, const float* lse, const float* invn, float* out, int NX, int NY, int d,
-                    float s, float weight, const float* state) {
-  const dim3 grid(p.grid_x, p.grid_y), block(p.block);
-#define CT_GO(ACC, NACC)                                                                                                  \
-  hipLaunchKernelGGL((contrastive_grad_kernel<OWN_Q, ACC, NACC>), grid, block, 0, stream, X, Y, qg, kg, lse, invn, out, NX, \
-                     NY, d, s, weight, state)
-  if (p.feat_chunk == CT_FEAT) {
-    if (accum) CT_GO(true, 4); else CT_GO(false, 4);
-  } else {
-    if (accum) CT_GO(true, 1); else CT_GO(false, 1);
-  }
-#undef CT_GO
+  const CtGrad<OWN_Q> fn = {qg, kg, lse, invn, s, (weight * (state ? state[CLIPFS_SCALER_SCALE] : 1.f)) * s};
+  tile_grad_walk<ACCUM, NACC>(X, Y, out, NX, NY, d, fn);
 }
 
 int ct_check_shape(int R, int N, int d) {
@@ -407,11 +235,8 @@ extern "C" int clipfs_contrastive_plan(int op, int R, int N, int d, struct clipf
     p.lds_bytes = (unsigned)(2 * CT_THREADS * sizeof(float));
   } else {
     const int own = op == CLIPFS_CONTRASTIVE_OP_DQ ? R : N;
-    p.grid_x = (unsigned)((own + 31) / 32);
-    // 512 features per workgroup where that gives every compute unit one; else 128: four times the workgroups
-    p.feat_chunk = (long long)p.grid_x * ((d + CT_FEAT - 1) / CT_FEAT) >= 256 ? CT_FEAT : CT_FEAT / 4;
-    p.grid_y = (unsigned)((d + p.feat_chunk - 1) / p.feat_chunk);
-    p.lds_bytes = (unsigned)((2 * 32 * CT_KST + 4 * 32 * CT_PS + 32 * 32) * sizeof(float));
+    tile_grad_plan(p, own, d);
+    p.lds_bytes = tile_grad_lds_bytes();
   }
   *plan = p;
   return CLIPFS_OK;
@@ -451,13 +276,13 @@ extern "C" int clipfs_contrastive_objective(const float* q, const float* k, cons
   const float* lse = work + (size_t)CT_FIELDS * ps.chunks * R;
   const float* invn = lse + R;
   if (dq) {
-    ct_launch_grad<true>(pq, dq_accumulate != 0, st, q, k, q_group, k_group, lse, invn, dq, R, N, d, logit_scale, weight,
-                         scaler_state);
+    TILE_GRAD_LAUNCH(contrastive_grad_kernel, true, dq_accumulate != 0, pq, st, q, k, q_group, k_group, lse, invn, dq, R, N, d,
+                     logit_scale, weight, scaler_state);
     CLIPFS_CHECK(launch_status());
   }
   if (dk) {
-    ct_launch_grad<false>(pk, dk_accumulate != 0, st, k, q, q_group, k_group, lse, invn, dk, N, R, d, logit_scale, weight,
-                          scaler_state);
+    TILE_GRAD_LAUNCH(contrastive_grad_kernel, false, dk_accumulate != 0, pk, st, k, q, q_group, k_group, lse, invn, dk, N, R, d,
+                     logit_scale, weight, scaler_state);
     CLIPFS_CHECK(launch_status());
   }
   return CLIPFS_OK;

@@ -10,36 +10,28 @@
 // every float is written by one thread and every sum runs in an order fixed by the shapes, so results are bitwise equal
 // run to run and an image's results do not depend on the batch around it.
 //
-//   logits  one workgroup per (32 classes, 32 views, image) forms its tile on v_mfma_f32_32x32x2_f32 the way
-//           cache_head.hip forms its affinity tiles (rows read straight from global memory / L2, 128 contiguous bytes per
-//           lane and 64-feature step); the four waves split the 64-feature steps and their partials are added in wave
-//           order.  Every element of a tile sums the same features in the same order: a row's logits do not depend on
-//           where the row sits, which is what makes the tie rule exact.
+//   logits  one workgroup per (32 classes, 32 views, image) forms its tile on v_mfma_f32_32x32x2_f32 (tile_dots of
+//           logits_tile.h: rows read straight from global memory / L2, 128 contiguous bytes per lane and 64-feature
+//           step); the four waves split the 64-feature steps and their partials are added in wave order.  Every element
+//           of a tile sums the same features in the same order: a row's logits do not depend on where the row sits,
+//           which is what makes the tie rule exact.
 //   reduce  one 1024-thread workgroup per image, in the manner of mta_kernel: a wave per row for max / sum / entropy,
 //           a thread per view for the rank count, a thread per class for pbar, g and the loss, a wave per selected row for
 //           dz.  Softmax probabilities are recomputed as exp(z - max) / sum wherever they are needed.
 //   grad    the rank-K product dz^T F on the VALU, a thread per (class, 4 features), the K terms added in ascending view
 //           index.  K is about 6: twelve flops per output element, the launch is bound by its stores.
-#include "common.h"
+#include "logits_tile.h"
 
 #include <math.h>
 
 namespace clipfs {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
 namespace {
 
 constexpr int TPT_MAX_V = 1024;
 constexpr int TPT_MAX_D = 1024;
 constexpr int TPT_THREADS = 256;       // logits and gradient workgroups: 4 waves
 constexpr int TPT_RED_THREADS = 1024;  // the reduction workgroup: one thread per view
-constexpr int TPT_PS = 33;             // row stride of the logits partials (conflict-free)
 constexpr int TPT_GC = 8;              // classes per gradient workgroup
-
-// row of the A side that register r of lane (half h) holds after v_mfma_f32_32x32x2_f32
-__device__ __forceinline__ int tpt_row(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
 
 __device__ __forceinline__ float tpt_block_sum(float v, float* red, int tid) {
   v = wave_sum(v);
@@ -58,40 +50,20 @@ __global__ __launch_bounds__(TPT_THREADS) void tpt_logits_kernel(const float* __
                                                                  const float* __restrict__ text, size_t text_stride,
                                                                  float* __restrict__ work, size_t work_stride, int V, int d,
                                                                  int C, float s) {
-  __shared__ float Ps[4][32 * TPT_PS];  // per wave: [view][class] partial over its 64-feature steps
+  __shared__ float Ps[4][32 * TILE_PS];  // per wave: [view][class] partial over its 64-feature steps
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, li = lane & 31, h = lane >> 5;
   const int c0 = blockIdx.x * 32, v0 = blockIdx.y * 32, img = blockIdx.z;
   const float* F = feats + (size_t)img * V * d;
   const float* T = text + (size_t)img * text_stride;
   float* z = work + (size_t)img * work_stride;
-  f32x16 acc;
+  const f32x16 acc = tile_dots(F, v0, V, T, c0, C, d, 64 * w, 256, lane);  // this wave's steps; edge products are never stored
 #pragma unroll
-  for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-  // rows past the end are clamped to the last row (their products are never stored); d is a multiple of 4, so a float4
-  // that starts below d ends inside the row
-  const float* pa = F + (size_t)min(v0 + li, V - 1) * d + 32 * h;
-  const float* pb = T + (size_t)min(c0 + li, C - 1) * d + 32 * h;
-  for (int k0 = 64 * w; k0 < d; k0 += 256) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      f32x4 va, vb;
-      va[0] = va[1] = va[2] = va[3] = 0.f;
-      vb = va;
-      if (k0 + 32 * h + 4 * j < d) {
-        va = *reinterpret_cast<const f32x4*>(pa + k0 + 4 * j);
-        vb = *reinterpret_cast<const f32x4*>(pb + k0 + 4 * j);
-      }
-#pragma unroll
-      for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(va[e], vb[e], acc, 0, 0, 0);
-    }
-  }
-#pragma unroll
-  for (int r = 0; r < 16; ++r) Ps[w][tpt_row(r, h) * TPT_PS + li] = acc[r];
+  for (int r = 0; r < 16; ++r) Ps[w][tile_row(r, h) * TILE_PS + li] = acc[r];
   __syncthreads();
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
-    const int e = tid + TPT_THREADS * i, row = e >> 5, col = e & 31, at = row * TPT_PS + col;
-    const float a = ((Ps[0][at] + Ps[1][at]) + Ps[2][at]) + Ps[3][at];
+    const int e = tid + TPT_THREADS * i, row = e >> 5, col = e & 31;
+    const float a = tile_sum4(Ps, row * TILE_PS + col);
     if (v0 + row < V && c0 + col < C) z[(size_t)(v0 + row) * C + c0 + col] = s * a;
   }
 }

@@ -12,9 +12,14 @@ import torch
 
 PULL = 0.2
 
-# (R, N, d, kind) of the kernel parity test
+# (R, N, d, kind) of the kernel parity test.  The last two reach the gradient kernel's 512-feature workgroups (four
+# accumulators per wave): 4081 is the smallest own side at which a d in (512, 1024] selects them, the first for dq with a
+# ragged second feature chunk (600 = 512 + 88), the second for dk.
 CASES = [(1, 1, 64, "paired"), (32, 32, 64, "paired"), (33, 65, 64, "groups"), (37, 83, 192, "groups"),
-         (256, 256, 512, "paired"), (256, 403, 512, "groups"), (96, 1100, 1024, "groups"), (300, 40, 128, "groups")]
+         (256, 256, 512, "paired"), (256, 403, 512, "groups"), (96, 1100, 1024, "groups"), (300, 40, 128, "groups"),
+         (4081, 40, 600, "groups"), (40, 4081, 600, "groups")]
+# (case, op) pairs whose gradient plan must say feat_chunk == 512
+WIDE_GRAD = [((4081, 40, 600, "groups"), "dq"), ((40, 4081, 600, "groups"), "dk")]
 
 
 def _unit(t):

@@ -4,9 +4,7 @@ every refusal of clipfs_contrastive_objective (fake device addresses, a NULL str
 import pytest
 import torch
 
-from contrastive_ref import CASES, contrastive_case, contrastive_inputs, contrastive_ref
-
-SMALL = [c for c in CASES if c[0] * c[1] <= 256 * 403]
+from contrastive_ref import CASES, WIDE_GRAD, contrastive_case, contrastive_inputs, contrastive_ref
 
 
 def _autograd(q, k, qg, kg, s, w):
@@ -81,7 +79,7 @@ def test_a_masked_key_changes_nothing_but_its_own_column():
 
 @pytest.mark.parametrize("s", [100.0, 1.0])
 def test_case_table_satisfies_the_helper_conditions(s):
-    for case in SMALL:
+    for case in CASES:
         contrastive_case(*case, s)
 
 
@@ -112,6 +110,17 @@ def test_plan_covers_the_shape(R, N, d):
         assert p["block"] == 256 and 0 < p["lds_bytes"] <= 160 * 1024
         assert p["work_floats"] == 6 * st["chunks"] * R + 2 * R
         assert (p["col_chunk"], p["chunks"]) == (st["col_chunk"], st["chunks"])
+
+
+@pytest.mark.parametrize("case,op", WIDE_GRAD)
+def test_wide_gradient_cases_reach_the_512_feature_workgroups(case, op):
+    """The two cases that exist to run the four-accumulator gradient kernels must keep selecting them."""
+    from clipfs import ops
+    assert case in CASES
+    R, N, d, _ = case
+    other = "dk" if op == "dq" else "dq"
+    assert ops.contrastive_plan(op, R, N, d)["feat_chunk"] == 512
+    assert ops.contrastive_plan(other, R, N, d)["feat_chunk"] == 128
 
 
 def test_plan_refusals():

@@ -9,8 +9,8 @@ test prints its figures before it asserts.
 
     quantity                                                        worst measured   bound
     loss_sum (w = 1/R; kernel cases and clip_loss), absolute        8.52e-7          3.5e-6
-    loss_rows, absolute                                             1.51e-5          6.1e-5
-    kernel dq / dk, share of the reference's largest entry          1.77e-5          7.1e-5
+    loss_rows, absolute                                             1.82e-5          7.3e-5
+    kernel dq / dk, share of the reference's largest entry          2.25e-5          9.0e-5
     clip_loss gradients, share of the largest entry                 1.16e-5          4.7e-5
     step_pairs loss against the fp64 oracle, absolute               1.10e-6          4.4e-6
     step_pairs adapter gradients (the whole flat buffer), share     4.27e-6          1.8e-5
@@ -20,6 +20,8 @@ test prints its figures before it asserts.
 The last bound is not 4 x a measurement (that would be 0): the two ranks add the same fp32 row losses in another order than
 one process does, which may move a loss of ~2.8 by a few units in its last place (2.4e-7); 1e-6 is four of them.  For
 orientation, a torch fp32 CPU evaluation of the kernel cases is within 7.5e-7 on the loss and 3.9e-6 on the gradients.
+The loss_rows and dq / dk figures are those of (4081, 40, 600, groups) at s = 100, measured on the kernels as they stood
+before logits_tile.h (the older cases gave 1.51e-5 and 1.77e-5).
 """
 import os
 import socket
@@ -36,8 +38,8 @@ from contrastive_ref import CASES, contrastive_case, contrastive_inputs, contras
 pytestmark = pytest.mark.gpu
 
 BOUND_LOSS = 3.5e-6
-BOUND_ROWS = 6.1e-5
-BOUND_GRAD = 7.1e-5
+BOUND_ROWS = 7.3e-5
+BOUND_GRAD = 9.0e-5
 BOUND_CLIP = 4.7e-5
 BOUND_TLOSS = 4.4e-6
 BOUND_TGRAD = 1.8e-5
