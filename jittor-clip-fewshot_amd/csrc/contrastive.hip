@@ -7,8 +7,10 @@
 //   G[i,j] = w S (softmax_ij - [j in P_i] / n_i)      dq_i = s sum_j G[i,j] k_j      dk_j = s sum_i G[i,j] q_i
 //
 // Neither z nor G leaves the chip.  Every kernel forms 32 x 32 logits tiles on v_mfma_f32_32x32x2_f32 (logits_tile.h:
-// operands straight from global memory / L2 in the stats kernel, through LDS in the gradient kernels).  No float atomics:
-// every output element is written by one thread of one workgroup and the order of every sum depends on the shapes alone.
+// operands straight from global memory / L2 in the stats kernel, through LDS in the gradient kernels, summed in ONE
+// order, so that the z behind lse and the z of the gradient are the same fp32 number; the build does not contract s * a).
+// No float atomics: every output element is written by one thread of one workgroup and the order of every sum depends on
+// the shapes alone.
 //
 //   stats    one workgroup per (32 queries, chunk of keys) walks the chunk in tiles of 128 keys (one wave per 32); a lane
 //            keeps the running (max, sum of exponentials, sum of positive z, positive count, best value, best index) of
@@ -54,7 +56,7 @@ __global__ __launch_bounds__(CT_THREADS) void contrastive_stats_kernel(const flo
   for (int k0 = c0; k0 < c1; k0 += CT_KT) {
     const int kw = k0 + 32 * w;
     if (kw < c1) {  // wave-uniform
-      const f32x16 a = tile_dots(k, kw, N, q, q0, R, d, 0, 64, lane);
+      const f32x16 a = tile_dots_as_staged(k, kw, N, q, q0, R, d, lane);  // the gradient kernels' z, bit for bit
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int j = kw + tile_row(r, h);  // ascending in r: a strict > keeps the lowest index of a tie

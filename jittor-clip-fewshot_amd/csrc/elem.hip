@@ -476,12 +476,15 @@ __global__ __launch_bounds__(1024) void logit_normalize_bwd_kernel(const float* 
     for (int w = 0; w < 16; ++w) t += red[w];
     return t;
   };
+  // every mean is taken of z - z[0]: a sum of logits that all sit near 300 rounds to an ulp of n * 300, and the centred
+  // values it leaves behind carry that error at full size
+  const float z0 = z[0];
   float s = 0.f;
-  for (size_t i = tid; i < n; i += 1024) s += z[i];
-  const float mean = block_total(s) / (float)n;
+  for (size_t i = tid; i < n; i += 1024) s += z[i] - z0;
+  const float mean = block_total(s) / (float)n;  // of z - z0
   float q = 0.f;
   for (size_t i = tid; i < n; i += 1024) {
-    const float d = z[i] - mean;
+    const float d = (z[i] - z0) - mean;
     q = fmaf(d, d, q);
   }
   const float var = block_total(q) / (float)(n - 1);
@@ -491,9 +494,9 @@ __global__ __launch_bounds__(1024) void logit_normalize_bwd_kernel(const float* 
   float g = 0.f;
   for (int r = wave; r < rows; r += 16) {
     float rs = 0.f;
-    for (int c = lane; c < classes; c += 64) rs += z[(size_t)r * classes + c];
-    const float rm = wave_sum(rs) / (float)classes;
-    for (int c = lane; c < classes; c += 64) g = fmaf(dzn[(size_t)r * classes + c], z[(size_t)r * classes + c] - rm, g);
+    for (int c = lane; c < classes; c += 64) rs += z[(size_t)r * classes + c] - z0;
+    const float rm = wave_sum(rs) / (float)classes;  // of z - z0
+    for (int c = lane; c < classes; c += 64) g = fmaf(dzn[(size_t)r * classes + c], (z[(size_t)r * classes + c] - z0) - rm, g);
   }
   g = block_total(g);  // = sigma * sum(dzn * zn)
   const float coef = clamped ? 0.f : g / (sd * sd * sd * (float)(n - 1));
@@ -503,7 +506,7 @@ __global__ __launch_bounds__(1024) void logit_normalize_bwd_kernel(const float* 
     const float dm = wave_sum(ds) / (float)classes;
     for (int c = lane; c < classes; c += 64) {
       const size_t i = (size_t)r * classes + c;
-      dz[i] = (dzn[i] - dm) / sd - coef * (z[i] - mean);
+      dz[i] = (dzn[i] - dm) / sd - coef * ((z[i] - z0) - mean);
     }
   }
 }
@@ -739,7 +742,10 @@ __global__ __launch_bounds__(1024) void l1_loss_kernel(const float* __restrict__
 }
 
 // KL(softmax(t) || softmax(x)) per row:  loss_rows[r] = sum_j q_j (log q_j - log p_j),  dx = (p - q) * grad_scale.
-// One wave per row (403 classes); both log-softmaxes with max subtraction.
+// One wave per row (403 classes); both log-softmaxes with max subtraction, and the maximum subtracted FIRST: log p =
+// (x - max) - log(sum), never x - (max + log(sum)), which rounds log(sum) to an ulp of the maximum (3e-5 at logits of
+// 300) and shifts every log p of the row by it.  exp / log are the precise ones: q (b - a) multiplies q's error by
+// log-ratios of a hundred and more.
 __global__ __launch_bounds__(256) void kl_logits_kernel(const float* __restrict__ x, const float* __restrict__ t,
                                                         float* __restrict__ loss_rows, float* __restrict__ dx, int rows,
                                                         int cols, float gscale) {
@@ -757,18 +763,18 @@ __global__ __launch_bounds__(256) void kl_logits_kernel(const float* __restrict_
   mt = wave_max(mt);
   float sx = 0.f, st = 0.f;
   for (int j = lane; j < cols; j += 64) {
-    sx += __expf(xr[j] - mx);
-    st += __expf(tr[j] - mt);
+    sx += expf(xr[j] - mx);
+    st += expf(tr[j] - mt);
   }
   sx = wave_sum(sx);
   st = wave_sum(st);
-  const float lx = mx + __logf(sx), lt = mt + __logf(st);
+  const float lsx = logf(sx), lst = logf(st);
   float acc = 0.f;
   for (int j = lane; j < cols; j += 64) {
-    const float a = xr[j] - lx, b = tr[j] - lt;  // log p, log q
-    const float q = __expf(b);
+    const float a = (xr[j] - mx) - lsx, b = (tr[j] - mt) - lst;  // log p, log q
+    const float q = expf(b);
     acc += q * (b - a);
-    if (dx) dx[(size_t)row * cols + j] = (__expf(a) - q) * gscale;
+    if (dx) dx[(size_t)row * cols + j] = (expf(a) - q) * gscale;
   }
   acc = wave_sum(acc);
   if (lane == 0) loss_rows[row] = acc;

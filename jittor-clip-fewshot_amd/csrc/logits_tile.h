@@ -64,6 +64,47 @@ __device__ __forceinline__ f32x16 tile_dots(const float* __restrict__ A, int a0,
   return acc;
 }
 
+// tile_dots' products (operands straight from global memory) summed in the ORDER of the staged tile below: per chunk of
+// TILE_KC features four partial sums, the staged waves' shares of 32 features with half h taking 16 of them, added in wave
+// order as tile_sum4 adds them.  A statistic made from these products (a log-sum-exp) and a gradient kernel that forms
+// the products again through tile_dots_staged then hold the SAME fp32 number for every pair of rows.  With two orders the
+// two differ by the rounding of a d-term fp32 sum, ~1e-7 of |a| |b|; a logit scale s multiplies that, and
+// exp(s a - lse) of a row's dominant key, where s a and lse cancel, is off by s 1e-7: 1e-4 of the gradient at s = 1000.
+__device__ __forceinline__ f32x16 tile_dots_as_staged(const float* __restrict__ A, int a0, int na, const float* __restrict__ Bm,
+                                                      int b0, int nb, int d, int lane) {
+  const int li = lane & 31, h = lane >> 5;
+  f32x16 acc[4];
+#pragma unroll
+  for (int w = 0; w < 4; ++w)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[w][r] = 0.f;
+  const float* pa = A + (size_t)min(a0 + li, na - 1) * d + 16 * h;
+  const float* pb = Bm + (size_t)min(b0 + li, nb - 1) * d + 16 * h;
+  for (int s = 0; s < d; s += TILE_KC) {
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+      if (s + 32 * w < d) {  // wave-uniform; a share wholly past d is zeros in the staged tile too
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          f32x4 va, vb;
+          va[0] = va[1] = va[2] = va[3] = 0.f;
+          vb = va;
+          if (s + 32 * w + 16 * h + 4 * j < d) {
+            va = *reinterpret_cast<const f32x4*>(pa + s + 32 * w + 4 * j);
+            vb = *reinterpret_cast<const f32x4*>(pb + s + 32 * w + 4 * j);
+          }
+#pragma unroll
+          for (int e = 0; e < 4; ++e) acc[w] = tile_mfma(va[e], vb[e], acc[w]);
+        }
+      }
+    }
+  }
+  f32x16 sum;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) sum[r] = ((acc[0][r] + acc[1][r]) + acc[2][r]) + acc[3][r];
+  return sum;
+}
+
 // The staged tile: 32 x 32 over the whole of d, the operands passing through LDS in chunks of TILE_KC features (16-byte
 // global loads with a row's 128 features contiguous over 32 threads, where tile_dots' lanes each walk a row of their own).
 // Wave w takes features [32 w, 32 w + 32) of every chunk, half h 16 of them.  The next chunk -- after a tile's last one,

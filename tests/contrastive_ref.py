@@ -53,10 +53,11 @@ def contrastive_inputs(R, N, d, kind, seed=1):
     return q.float(), k.float(), qg.clone(), kg.clone()
 
 
-def contrastive_ref(q, k, q_group, k_group, s, w, scale=1.0):
+def contrastive_ref(q, k, q_group, k_group, s, w, scale=1.0, dtype=torch.float64):
     """The definition in fp64, closed form: dict of loss (w * sum), loss_rows [R], dq, dk, n [R], correct and gap (the
-    smallest top-1 minus top-2 logit over the rows that have a positive; inf where no row has two live keys)."""
-    q, k = q.detach().double().cpu(), k.detach().double().cpu()
+    smallest top-1 minus top-2 logit over the rows that have a positive; inf where no row has two live keys).
+    ``dtype=torch.float32``: the same expressions evaluated in fp32, the yardstick of the range tests."""
+    q, k = q.detach().to(dtype).cpu(), k.detach().to(dtype).cpu()
     qg, kg = q_group.cpu().long(), k_group.cpu().long()
     live = kg >= 0
     pos = positives(qg, kg)
@@ -68,7 +69,7 @@ def contrastive_ref(q, k, q_group, k_group, s, w, scale=1.0):
     possum = (z * pos).sum(1)
     loss_rows = torch.where(alive, lse - possum / n.clamp(min=1), torch.zeros_like(lse))
     soft = torch.exp(zl - lse[:, None])
-    G = w * scale * (soft - pos.double() / n.clamp(min=1)[:, None].double())
+    G = w * scale * (soft - pos.to(dtype) / n.clamp(min=1)[:, None].to(dtype))
     G[~alive] = 0
     G[:, ~live] = 0
     is_max = zl == zl.max(dim=1, keepdim=True).values  # ties to the lower j, spelled out: argmax does not promise it

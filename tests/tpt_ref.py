@@ -24,11 +24,12 @@ def tpt_inputs(V, C, d, seed):
     return F.float(), T.float()
 
 
-def tpt_ref(F, T, K, s, selected=None):
+def tpt_ref(F, T, K, s, selected=None, dtype=torch.float64):
     """loss, dT [C, d], H [V], selected [K] (int64, ascending) in fp64 with autograd.  The selection is the K views of
-    lowest entropy by a stable sort (ties to the lower index), or ``selected`` when given."""
-    F = F.detach().double().cpu()
-    T = T.detach().double().cpu().clone().requires_grad_()
+    lowest entropy by a stable sort (ties to the lower index), or ``selected`` when given.  ``dtype=torch.float32``: the
+    same expressions evaluated in fp32, the yardstick of the range tests."""
+    F = F.detach().to(dtype).cpu()
+    T = T.detach().to(dtype).cpu().clone().requires_grad_()
     lp = torch.log_softmax(s * F @ T.t(), dim=-1)
     H = -(lp.exp() * lp).sum(-1)
     if selected is None:
