@@ -1095,6 +1095,65 @@ int clipfs_contrastive_objective(const float* q, const float* k, const int32_t* 
                                  float* loss_sum, int32_t* correct, float* dq, int dq_accumulate, float* dk,
                                  int dk_accumulate, float* work, int R, int N, int d, void* stream);
 
+/* ------------------------------------------------------- sigmoid objective --
+ * The pairwise sigmoid (SigLIP) loss with group ids, fp32 in every engine precision mode: every (query, key) cell is an
+ * independent binary problem, so the loss is one-directional in form and symmetric in effect (one call serves both
+ * directions), a batch that repeats classes needs nothing special, and under data parallelism a rank scores ITS
+ * queries against all keys.  q [R, d] queries and k [N, d] keys (the caller passes unit rows), q_group [R] / k_group [N]
+ * int32, head a DEVICE pointer to two floats (log t, b) -- the scale and bias are trainable, so they never pass
+ * through the host --, w = weight, S = word CLIPFS_SCALER_SCALE of scaler_state or 1 when it is NULL:
+ *   t = expf(head[0])      a_ij = q_i . k_j      z_ij = t a_ij + head[1]
+ *   live(i,j) = q_group[i] >= 0 and k_group[j] >= 0      (a dead cell contributes nothing, anywhere)
+ *   pos(i,j)  = live and q_group[i] == k_group[j]
+ *   l_ij      = softplus(-z_ij) if pos else softplus(z_ij)      loss_i = sum_j live l_ij
+ *   loss_sum [1] = w sum_i loss_i
+ *   G_ij      = w S (sigmoid(z_ij) - [pos])   on live cells, 0 elsewhere
+ *   dq_i = t sum_j G_ij k_j   [R, d]      dk_j = t sum_i G_ij q_i   [N, d]
+ *   dhead [2]: dhead[0] = t sum_ij G_ij a_ij  (d / d log t)      dhead[1] = sum_ij G_ij
+ *   correct [1] (int32, may be NULL) = #{ i live with at least one positive : argmax_{j live} z_ij is a positive }, ties
+ *                                      to the lower j (the rule of clipfs_topk)
+ * UNLIKE the contrastive objective above, a live query WITHOUT a positive still contributes its negative terms to the
+ * loss and to every gradient (there, such a row contributes nothing): there is no row normaliser to leave it out of.
+ * softplus keeps its tail (max(x, 0) + log1p(exp(-|x|))): at SigLIP's initial point (t, b) = (10, -10) a negative
+ * term is 1e-5 ... 1e-7 and there are R N of them; sigmoid does not overflow at any z.
+ *
+ * dq, dk and dhead are each optional (NULL: not formed).  With its accumulate flag set the finished sum is added ONCE
+ * to what is there (bitwise old + fresh); otherwise it is written.  S multiplies the three gradients only.
+ *
+ * row_stats [4, R] is an OUTPUT, not scratch (the entry point takes none: the gradient kernels need nothing from an
+ * earlier pass), and every element of it is written: row 0 loss_i, row 1 sum_j (sigmoid - [pos]), row 2
+ * sum_j (sigmoid - [pos]) a_ij (all three 0 for a dead query), row 3 the best live key index as int32 bits, -1 for a
+ * dead query or when there is no live key.  The combine kernel reads it, so it must be given.
+ *
+ * Neither z nor G reaches HBM; no float atomics; every sum runs in an order fixed by (R, N, d), every output element is
+ * written by one thread: results are bitwise equal run to run.  Nothing outside the stated extents is touched and
+ * nothing returns to the host.  Four launches at most:
+ *   rows     grid (32-query tiles): ALL keys walked in tiles of 128, the row statistics into row_stats
+ *   combine  one workgroup: loss_sum, correct and dhead from row_stats by a fixed-order tree
+ *   dq, dk   grid (32 own-row tiles, chunks of feat_chunk features): the other side walked in ascending 32-row tiles,
+ *            z recomputed (the same fp32 number as in the rows kernel), G formed and contracted in the same workgroup
+ *
+ * clipfs_sigmoid_plan IS the function the entry point executes: host-only (no GPU is opened, nothing is launched,
+ * nothing written to `plan` on refusal).  CLIPFS_EINVAL, the message naming the argument, for R or N < 1, d not a
+ * multiple of 4 in [4, 1024], an unknown op or a NULL plan.  clipfs_sigmoid_objective refuses the same before anything
+ * is enqueued, and also: q, k, q_group, k_group, head, row_stats or loss_sum NULL; q, k, dq or dk not 16-byte aligned;
+ * dq or dk overlapping q, k or each other; head overlapping q, k, dq or dk; dhead overlapping q, k, dq, dk or head; a
+ * weight that is not finite; a scaler_state that is not 16-byte aligned. */
+#define CLIPFS_SIGMOID_OP_ROWS 0
+#define CLIPFS_SIGMOID_OP_COMBINE 1
+#define CLIPFS_SIGMOID_OP_DQ 2
+#define CLIPFS_SIGMOID_OP_DK 3
+struct clipfs_sigmoid_plan {
+  unsigned grid_x, grid_y, grid_z, block;
+  unsigned lds_bytes;     /* LDS of a workgroup (at most 160 KB) */
+  int feat_chunk;         /* dq / dk: features per workgroup, 512, or 128 where 512 would leave compute units idle (0 otherwise) */
+};
+int clipfs_sigmoid_plan(int op, int R, int N, int d, struct clipfs_sigmoid_plan* plan);
+int clipfs_sigmoid_objective(const float* q, const float* k, const int32_t* q_group, const int32_t* k_group,
+                             const float* head, float weight, const float* scaler_state, float* row_stats,
+                             float* loss_sum, int32_t* correct, float* dq, int dq_accumulate, float* dk,
+                             int dk_accumulate, float* dhead, int dhead_accumulate, int R, int N, int d, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

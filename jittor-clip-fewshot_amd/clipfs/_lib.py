@@ -115,6 +115,16 @@ class ContrastivePlan(C.Structure):
 CONTRASTIVE_OPS = ("stats", "combine", "dq", "dk")
 
 
+class SigmoidPlan(C.Structure):
+    """struct clipfs_sigmoid_plan: what clipfs_sigmoid_objective launches."""
+    _fields_ = [("grid_x", C.c_uint), ("grid_y", C.c_uint), ("grid_z", C.c_uint), ("block", C.c_uint), ("lds_bytes", C.c_uint),
+                ("feat_chunk", C.c_int)]
+
+
+# CLIPFS_SIGMOID_OP_* of include/clipfs.h, by value
+SIGMOID_OPS = ("rows", "combine", "dq", "dk")
+
+
 class MergeJob(C.Structure):
     """struct clipfs_lora_merge_job: one projection of a clipfs_lora_merge table."""
     _fields_ = [("w", C.c_void_p), ("a", C.c_void_p), ("b", C.c_void_p), ("out", C.c_void_p), ("planes", C.c_void_p),
@@ -295,6 +305,8 @@ SIGNATURES = {
     "clipfs_tpt_objective": (_i, [_p, _p, _i, _p, _i, _i, _f, _f, _p, _p, _p, _p, _i, _i, _i, _i, _p]),
     "clipfs_contrastive_plan": (_i, [_i, _i, _i, _i, C.POINTER(ContrastivePlan)]),
     "clipfs_contrastive_objective": (_i, [_p, _p, _p, _p, _f, _f, _p, _p, _p, _p, _p, _i, _p, _i, _p, _i, _i, _i, _p]),
+    "clipfs_sigmoid_plan": (_i, [_i, _i, _i, _i, C.POINTER(SigmoidPlan)]),
+    "clipfs_sigmoid_objective": (_i, [_p, _p, _p, _p, _p, _f, _p, _p, _p, _p, _p, _i, _p, _i, _p, _i, _i, _i, _i, _p]),
 }
 
 # word indices of the loss-scaling record (CLIPFS_SCALER_* of include/clipfs.h)
@@ -380,6 +392,14 @@ def contrastive_plan(op: str, R: int, N: int, d: int):
     plan = ContrastivePlan()
     check(load().clipfs_contrastive_plan(CONTRASTIVE_OPS.index(op), R, N, d, C.byref(plan)), "contrastive_plan")
     return dict(grid=(plan.grid_x, plan.grid_y, plan.grid_z), **{k: getattr(plan, k) for k, _ in ContrastivePlan._fields_[3:]})
+
+
+def sigmoid_plan(op: str, R: int, N: int, d: int):
+    """The plan clipfs_sigmoid_objective executes for these shapes (host-only), as a dict of the fields of struct
+    clipfs_sigmoid_plan with grid = (x, y, z).  A refusal raises ClipfsError with its message."""
+    plan = SigmoidPlan()
+    check(load().clipfs_sigmoid_plan(SIGMOID_OPS.index(op), R, N, d, C.byref(plan)), "sigmoid_plan")
+    return dict(grid=(plan.grid_x, plan.grid_y, plan.grid_z), **{k: getattr(plan, k) for k, _ in SigmoidPlan._fields_[3:]})
 
 
 def new_tower() -> Tower:

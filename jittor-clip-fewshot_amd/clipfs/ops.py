@@ -886,3 +886,87 @@ def clip_loss(img, txt, img_group=None, txt_group=None, logit_scale=100.0):
         raise ValueError("clip_loss needs both img_group and txt_group, or neither")
     return ClipLossFn.apply(img, txt, img_group.to(torch.int32).contiguous(), txt_group.to(torch.int32).contiguous(),
                             float(logit_scale))
+
+
+# ---------------------------------------------------------------------------------------------------- sigmoid objective
+def sigmoid_plan(op: str, R: int, N: int, d: int):
+    """What ``sigmoid_objective`` launches for these shapes ("rows", "combine", "dq", "dk"; host-only): grid, block,
+    lds_bytes, feat_chunk.  There is no scratch size: the entry point takes none."""
+    return _lib.sigmoid_plan(op, R, N, d)
+
+
+def sigmoid_objective(q, k, q_group, k_group, head, weight=1.0, scale_state=None, dq=None, dk=None, dhead=None, want_dq=True,
+                      want_dk=True, want_dhead=True, accumulate=True):
+    """The pairwise sigmoid (SigLIP) loss of unit queries ``q`` [R, d] against unit keys ``k`` [N, d] with int32 group ids
+    (a cell whose two groups are equal is a positive, a negative group on either side takes the cell out; a live query
+    without a positive still pays its negative terms, unlike ``contrastive_objective``): at most four launches, the
+    [R, N] logits and their gradient never reach memory.  ``head``: a DEVICE tensor of two floats (log t, b), read by the
+    kernels (nothing passes through the host).  Returns (loss_sum [1] = weight * sum of the cell losses, row_stats [4, R]
+    (row loss, sum of sigmoid - [pos], the same times q . k, best live key index as int32 bits), correct [1] int32,
+    dq [R, d] or None, dk [N, d] or None, dhead [2] = d / d (log t, b) or None).  A passed ``dq`` / ``dk`` / ``dhead`` is
+    ACCUMULATED into (bitwise old + fresh) and returned (``accumulate=False``, or a (dq, dk, dhead) triple of flags:
+    overwritten instead); otherwise the gradient is made when ``want_dq`` / ``want_dk`` / ``want_dhead``.
+    ``scale_state`` (a loss-scaling record) multiplies the three gradients only."""
+    R, d = q.shape
+    N = k.shape[0]
+    assert k.shape[1] == d, (tuple(q.shape), tuple(k.shape))
+    for g, n in ((q_group, R), (k_group, N)):
+        assert g.dtype == torch.int32 and g.is_contiguous() and g.numel() == n, "groups are contiguous int32 [R] / [N]"
+    assert head.dtype == torch.float32 and head.numel() == 2 and head.is_contiguous(), "head is two contiguous floats (log t, b)"
+    dev = q.device
+    acc_q, acc_k, acc_h = accumulate if isinstance(accumulate, tuple) else (accumulate,) * 3
+    acc_q, acc_k, acc_h = acc_q and dq is not None, acc_k and dk is not None, acc_h and dhead is not None
+    if dq is None and want_dq:
+        dq = torch.empty(R, d, device=dev, dtype=torch.float32)
+    if dk is None and want_dk:
+        dk = torch.empty(N, d, device=dev, dtype=torch.float32)
+    if dhead is None and want_dhead:
+        dhead = torch.empty(2, device=dev, dtype=torch.float32)
+    assert dq is None or tuple(dq.shape) == (R, d), "dq is [R, d]"
+    assert dk is None or tuple(dk.shape) == (N, d), "dk is [N, d]"
+    assert dhead is None or (dhead.numel() == 2 and dhead.is_contiguous()), "dhead is two contiguous floats"
+    lib = _lib.load()
+    row_stats = torch.empty(4, R, device=dev, dtype=torch.float32)
+    loss_sum = torch.empty(1, device=dev, dtype=torch.float32)
+    correct = torch.empty(1, device=dev, dtype=torch.int32)
+    check(lib.clipfs_sigmoid_objective(_p(_f32(q)), _p(_f32(k)), _p(q_group), _p(k_group), _p(_f32(head)), weight,
+                                       None if scale_state is None else _p(_scaler(scale_state)), _p(row_stats), _p(loss_sum),
+                                       _p(correct), None if dq is None else _p(_f32(dq)), int(acc_q),
+                                       None if dk is None else _p(_f32(dk)), int(acc_k),
+                                       None if dhead is None else _p(_f32(dhead)), int(acc_h), R, N, d, _stream()),
+          "sigmoid_objective")
+    return loss_sum, row_stats, correct, dq, dk, dhead
+
+
+class SiglipLossFn(torch.autograd.Function):
+    """``siglip_loss``: one call of ``sigmoid_objective`` serves both directions."""
+
+    @staticmethod
+    def forward(ctx, img, txt, head, img_group, txt_group):
+        img, txt, head = img.contiguous(), txt.contiguous(), head.contiguous()
+        need = ctx.needs_input_grad[:3]
+        loss, _, _, dimg, dtxt, dhead = sigmoid_objective(img, txt, img_group, txt_group, head, 1.0 / img.shape[0],
+                                                          want_dq=need[0], want_dk=need[1], want_dhead=need[2])
+        ctx.save_for_backward(*(t for t in (dimg, dtxt, dhead) if t is not None))
+        ctx.have = (dimg is not None, dtxt is not None, dhead is not None)
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, dloss):
+        saved = list(ctx.saved_tensors)
+        return (*(saved.pop(0) * dloss if have else None for have in ctx.have), None, None)
+
+
+def siglip_loss(img, txt, img_group=None, txt_group=None, *, head):
+    """The sigmoid (SigLIP) loss of unit image rows ``img`` [B, d] and unit caption rows ``txt`` [M, d], a scalar with
+    autograd to ``img``, ``txt`` and ``head``: (1/B) sum over all live (image, caption) cells of the binary loss of
+    ``sigmoid_objective``, a cell being positive where the two groups are equal.  ``head``: a device tensor of two floats
+    (log t, b) (SigLIP starts at t = 10, b = -10).  With both groups None the rows are pairs (M == B, group = row
+    index)."""
+    if img_group is None and txt_group is None:
+        if img.shape[0] != txt.shape[0]:
+            raise ValueError(f"siglip_loss without groups pairs row i with row i: {img.shape[0]} images, {txt.shape[0]} captions")
+        img_group = txt_group = torch.arange(img.shape[0], device=img.device, dtype=torch.int32)
+    elif img_group is None or txt_group is None:
+        raise ValueError("siglip_loss needs both img_group and txt_group, or neither")
+    return SiglipLossFn.apply(img, txt, head, img_group.to(torch.int32).contiguous(), txt_group.to(torch.int32).contiguous())

@@ -941,7 +941,8 @@ class FlatStepTrainer:
     ``overlap_towers`` and ``last_plan``; the loss-scaling state (``loss_scaling``, ``scale_state``, ``_scaler_rule``) with
     its host views ``loss_scale_value`` / ``skipped_steps`` / ``optimizer_steps``; the clipping and EMA state below;
     ``optimizer_step`` (shadow refusal, all-reduce when ``live``, ``t += 1``, ``_apply_update``, ``_after_update``); and
-    ``state_dict`` / ``load_state_dict`` over all of it.
+    ``state_dict`` / ``load_state_dict`` over all of it.  A subclass with state of its own does not override those two:
+    it implements ``_own_state`` / ``_check_own_state`` / ``_load_own_state`` (all three do nothing here).
 
     Loss scaling (``loss_scale`` ...): see ``LoRATrainer``.  ``scale_state`` is the device record (clipfs.h
     CLIPFS_SCALER_*), None = off; ``_scaler_rule`` the scaler's constants (growth, backoff, interval).
@@ -1147,11 +1148,13 @@ class FlatStepTrainer:
         ``torch.save``; adapter files of ``save_lora`` are another matter): the flat parameters and AdamW moments, the EMA
         shadow (and the live values set aside while it is applied), the loss-scaling and clip records, ``t``, ``lr``, the
         scheduler position (stage 2), the engine's dropout seed state, the hyper-parameters and the layout of the flat
-        buffer.  Synchronises."""
+        buffer; and what the subclass adds (``_own_state``: ``LoRATrainer``'s ``pair_loss`` and sigmoid head).
+        Synchronises."""
         cpu = lambda x: None if x is None else x.detach().cpu().clone()
         eng = self.model.engine
         sched = getattr(self, "sched", None)
         return {
+            **self._own_state(),
             "layout": [(n, k) for n, k in self.flat.segments],
             "switches": self._switches(),
             "params": cpu(self.flat.params), "m": cpu(self.flat.m), "v": cpu(self.flat.v),
@@ -1172,7 +1175,9 @@ class FlatStepTrainer:
     def load_state_dict(self, sd: dict) -> None:
         """Take back a ``state_dict()``.  The trainer must have been built like the one that wrote it: the same flat
         layout and the same of loss scaling, clipping and EMA switched on -- a ``ValueError`` names what differs and
-        nothing is changed.  Everything else (hyper-parameters included) is restored from ``sd``."""
+        nothing is changed; a subclass refuses the same way what does not fit its own additions (``LoRATrainer``: a
+        state written under the other ``pair_loss``).  Everything else (hyper-parameters included) is restored from
+        ``sd``."""
         mine, theirs = [(n, k) for n, k in self.flat.segments], [(n, int(k)) for n, k in sd["layout"]]
         if mine != theirs:
             a, b = dict(theirs), dict(mine)
@@ -1190,6 +1195,7 @@ class FlatStepTrainer:
         if (sched is None) != (sd["scheduler"] is None):
             raise ValueError("the saved state " + ("has no" if sched is not None else "carries a")
                              + " scheduler position: it was written by the other kind of trainer")
+        self._check_own_state(sd)
         f = self.flat
         for dst, key in ((f.params, "params"), (f.m, "m"), (f.v, "v"), (self.ema_shadow, "ema_shadow"),
                          (self.scale_state, "scale_state"), (self.clip_state, "clip_state")):
@@ -1208,7 +1214,18 @@ class FlatStepTrainer:
         self.max_grad_norm, self.ema_decay, self.loss_scaling = h["max_grad_norm"], h["ema_decay"], h["loss_scaling"]
         if self.scale_state is not None:
             self._scaler_rule = tuple(h["scaler_rule"])
+        self._load_own_state(sd)
         f.sync_packed()
+
+    def _own_state(self) -> dict:
+        """What a subclass's ``state_dict`` adds to the base's (plain Python values and CPU tensors)."""
+        return {}
+
+    def _check_own_state(self, sd: dict) -> None:
+        """Raise ``ValueError`` where ``sd`` does not fit what the subclass added; nothing has been changed yet."""
+
+    def _load_own_state(self, sd: dict) -> None:
+        """Take back what ``_own_state`` added."""
 
 
 class LoRATrainer(FlatStepTrainer):
@@ -1237,7 +1254,16 @@ class LoRATrainer(FlatStepTrainer):
     through ``slow_pace.Stage2Trainer(..., fused=True)``); bias training still needs a non-fp16 mode.
 
     ``max_grad_norm`` / ``ema_decay`` (both off by default) and ``state_dict`` / ``load_state_dict``: see
-    ``FlatStepTrainer``."""
+    ``FlatStepTrainer``.
+
+    ``pair_loss`` / ``pair_head`` / ``train_pair_head``: the objective of ``step_pairs``.  On this class they are the
+    constants "infonce" / None / False: the multi-positive InfoNCE loss at the host constant ``logit_scale``.  The
+    constructor of ``LoRAPairTrainer`` (below) is where they are chosen; ``state_dict`` records ``pair_loss`` and the
+    head, and ``load_state_dict`` refuses a state written under the other ``pair_loss``."""
+
+    pair_loss = "infonce"
+    pair_head = None
+    train_pair_head = False
 
     def __init__(self, model, lr: float = 2e-4, weight_decay: float = 1e-2, betas=(0.9, 0.999), eps: float = 1e-8,
                  logit_scale: float = 100.0, prompt_ctx: Optional[nn.Parameter] = None, process_group=None,
@@ -1252,6 +1278,8 @@ class LoRATrainer(FlatStepTrainer):
             extra.append(prompt_ctx)
         if model.visual.VPT is not None and model.visual.VPT.requires_grad:
             extra.append(model.visual.VPT)
+        if self.train_pair_head:  # LoRAPairTrainer: the sigmoid head, after the prompt ctx and VPT
+            extra.append(self.pair_head)
         self.flat = FlatTrainables(model, extra)
         if model.engine.precision == "fp16":
             for tname, tower in towers(model):
@@ -1403,7 +1431,16 @@ class LoRATrainer(FlatStepTrainer):
         the objective runs twice (local images x all captions, local captions x all images); the two gathered-feature
         gradient tables are reduce-scattered; ``optimizer_step`` all-reduces the flat gradient.  Collectives per step:
         2 all_gather (+ 1 with given groups) + 1 reduce_scatter per trained tower + 1 all_reduce -- 5 for plain pairs,
-        6 with groups (``collectives_per_step``)."""
+        6 with groups (``collectives_per_step``).
+
+        ``pair_loss="sigmoid"``: loss = (1/B_g) sum over all live (image, caption) cells of the binary loss of
+        ``ops.sigmoid_objective`` -- ONE objective call, local images x all captions, which covers every cell once.  A
+        live image without a positive caption still pays its negative terms.  Returns (loss_sum_local,
+        correct_i2t_local, None): a text -> image hit count would need a second walk and is not formed.  Data parallel:
+        only the caption block is all-gathered (and the caption groups when given); image features and image groups
+        stay local, the caption-gradient table is written afresh and reduce-scattered, and the flat all-reduce sums the
+        ranks' shares of the head's gradient: 3 collectives for plain pairs, 4 with groups, one fewer with the text tower
+        frozen.  Everything else is as above."""
         from clipfs import dist as D
         m = self.model
         eng = m.engine
@@ -1435,7 +1472,10 @@ class LoRATrainer(FlatStepTrainer):
         vis_lo = eng.image_plan()
         want_i, want_t = vis_lo is not None, text_lo is not None
         self.last_plan = {"text": text_lo, "vision": vis_lo}
-        if live:
+        sigmoid = self.pair_loss == "sigmoid"
+        if live and sigmoid:
+            self.collectives_per_step = 1 + (0 if paired else 1) + int(want_t) + 1
+        elif live:
             self.collectives_per_step = 2 + (0 if paired else 1) + int(want_i) + int(want_t) + 1
         main = torch.cuda.current_stream()
         side = self._side_stream() if self.overlap_towers else main
@@ -1452,39 +1492,46 @@ class LoRATrainer(FlatStepTrainer):
             ig = image_groups.to(device=dev, dtype=torch.int32).contiguous()
             cg = caption_groups.to(device=dev, dtype=torch.int32).contiguous()
         main.wait_stream(side)
-        if live:
-            si, sc = xb["img"]["S"], xb["cap"]["S"]
-            img_all = self._timed("all_gather", lambda: D.allgather_blocks(xb["img"]["send"], xb["img"]["full"], self.pg))
-            txt_all = self._timed("all_gather", lambda: D.allgather_blocks(xb["cap"]["send"], xb["cap"]["full"], self.pg))
-            if paired:  # global row g carries group g, padding rows -1: nothing to exchange
-                ig_all = torch.arange(self.world * si, device=dev, dtype=torch.int32)
-                cg_all = torch.arange(self.world * sc, device=dev, dtype=torch.int32)
-                ig_all[Bg:] = -1
-                cg_all[Mg:] = -1
-            else:
-                xb["gsend"][0, :B] = ig
-                xb["gsend"][0, si:si + M] = cg
-                g_all = self._timed("all_gather", lambda: D.allgather_blocks(xb["gsend"], xb["gfull"], self.pg))
-                ig_all, cg_all = g_all[:, :si].reshape(-1), g_all[:, si:].reshape(-1)
-            d_txt_all, d_img_all = (xb["cap"]["dfull"] if want_t else None), (xb["img"]["dfull"] if want_i else None)
-            my_img, my_cap = self.rank * si, self.rank * sc
-        else:
-            img_all, txt_all, ig_all, cg_all = img_n, txt, ig, cg
-            d_txt_all = torch.empty(M, d, device=dev) if want_t else None
-            d_img_all = None
-            my_img = my_cap = 0
         self.last_features = (img_n, txt)
-        s = self.logit_scale
-        # local images x all captions: the images' own gradient, and the caption-gradient table written afresh
-        l_it, _, c_it, d_img_own, _ = ops.contrastive_objective(img_n, txt_all, ig, cg_all, s, 0.5 / Bg, self.scale_state,
-                                                                dk=d_txt_all, want_dq=want_i, want_dk=False, accumulate=False)
-        # local captions x all images: added into this rank's rows of the caption table; the image side is added to the
-        # images' own gradient (one process) or written afresh into the image-gradient table (data parallel)
-        l_ti, _, c_ti, _, _ = ops.contrastive_objective(txt, img_all, cg, ig_all, s, 0.5 / Mg, self.scale_state,
-                                                        dq=d_txt_all[my_cap:my_cap + M] if want_t else None,
-                                                        dk=d_img_all if live else d_img_own, want_dq=False, want_dk=False,
-                                                        accumulate=(True, not live))
-        loss_sum = l_it + l_ti
+        if sigmoid:
+            loss_sum, c_it, d_img_own, d_txt_all = self._sigmoid_pairs(img_n, txt, ig, cg, xb, Mg, Bg, paired, want_i, want_t)
+            c_ti = None
+            scatter_images = False  # the images' gradient is complete on its rank: every cell of a row was scored here
+        else:
+            if live:
+                si, sc = xb["img"]["S"], xb["cap"]["S"]
+                img_all = self._timed("all_gather", lambda: D.allgather_blocks(xb["img"]["send"], xb["img"]["full"], self.pg))
+                txt_all = self._timed("all_gather", lambda: D.allgather_blocks(xb["cap"]["send"], xb["cap"]["full"], self.pg))
+                if paired:  # global row g carries group g, padding rows -1: nothing to exchange
+                    ig_all = torch.arange(self.world * si, device=dev, dtype=torch.int32)
+                    cg_all = torch.arange(self.world * sc, device=dev, dtype=torch.int32)
+                    ig_all[Bg:] = -1
+                    cg_all[Mg:] = -1
+                else:
+                    xb["gsend"][0, :B] = ig
+                    xb["gsend"][0, si:si + M] = cg
+                    g_all = self._timed("all_gather", lambda: D.allgather_blocks(xb["gsend"], xb["gfull"], self.pg))
+                    ig_all, cg_all = g_all[:, :si].reshape(-1), g_all[:, si:].reshape(-1)
+                d_txt_all, d_img_all = (xb["cap"]["dfull"] if want_t else None), (xb["img"]["dfull"] if want_i else None)
+                my_img, my_cap = self.rank * si, self.rank * sc
+            else:
+                img_all, txt_all, ig_all, cg_all = img_n, txt, ig, cg
+                d_txt_all = torch.empty(M, d, device=dev) if want_t else None
+                d_img_all = None
+                my_img = my_cap = 0
+            s = self.logit_scale
+            # local images x all captions: the images' own gradient, and the caption-gradient table written afresh
+            l_it, _, c_it, d_img_own, _ = ops.contrastive_objective(img_n, txt_all, ig, cg_all, s, 0.5 / Bg, self.scale_state,
+                                                                    dk=d_txt_all, want_dq=want_i, want_dk=False,
+                                                                    accumulate=False)
+            # local captions x all images: added into this rank's rows of the caption table; the image side is added to
+            # the images' own gradient (one process) or written afresh into the image-gradient table (data parallel)
+            l_ti, _, c_ti, _, _ = ops.contrastive_objective(txt, img_all, cg, ig_all, s, 0.5 / Mg, self.scale_state,
+                                                            dq=d_txt_all[my_cap:my_cap + M] if want_t else None,
+                                                            dk=d_img_all if live else d_img_own, want_dq=False, want_dk=False,
+                                                            accumulate=(True, not live))
+            loss_sum = l_it + l_ti
+            scatter_images = live  # each rank holds a share of every image's gradient from the captions' direction
         if want_t:
             if live:
                 mine = self._timed("reduce_scatter", lambda: D.reduce_scatter_blocks(xb["cap"]["dfull"], xb["cap"]["dmine"], self.pg))
@@ -1496,7 +1543,7 @@ class LoRATrainer(FlatStepTrainer):
                 d_emb = ops.class_mean_bwd(emb, d_txt_local, M, 1)
                 eng.text_backward(tctx, d_emb, None if self.prompt_ctx is None else self.prompt_ctx.grad_slot)
         if want_i:
-            if live:
+            if scatter_images:
                 d_img_all[my_img:my_img + B].add_(d_img_own)
                 mine = self._timed("reduce_scatter", lambda: D.reduce_scatter_blocks(xb["img"]["dfull"], xb["img"]["dmine"], self.pg))
                 d_img_n = mine[:B]
@@ -1506,6 +1553,58 @@ class LoRATrainer(FlatStepTrainer):
         main.wait_stream(side)
         return loss_sum, c_it, c_ti
 
+    def _sigmoid_pairs(self, img_n, txt, ig, cg, xb, Mg, Bg, paired, want_i, want_t):
+        """The sigmoid objective of ``forward_backward_pairs``: this rank's unit images against ALL unit captions in one
+        call.  Returns (loss_sum_local, correct_i2t_local, the images' gradient or None, the caption-gradient table
+        (written afresh; data parallel: the gathered table, to be reduce-scattered) or None)."""
+        from clipfs import dist as D
+        dev = self.flat.params.device
+        M, d = txt.shape
+        if self.live:
+            si, sc = xb["img"]["S"], xb["cap"]["S"]
+            txt_all = self._timed("all_gather", lambda: D.allgather_blocks(xb["cap"]["send"], xb["cap"]["full"], self.pg))
+            if paired:  # global row g carries group g, padding rows -1: nothing to exchange
+                cg_all = torch.arange(self.world * sc, device=dev, dtype=torch.int32)
+                cg_all[Mg:] = -1
+            else:  # the caption half of the group vector alone: image groups stay local
+                xb["gsend"][0, si:si + M] = cg
+                g_all = self._timed("all_gather", lambda: D.allgather_blocks(xb["gsend"], xb["gfull"], self.pg))
+                cg_all = g_all[:, si:].reshape(-1)
+            d_txt_all = xb["cap"]["dfull"] if want_t else None
+        else:
+            txt_all, cg_all = txt, cg
+            d_txt_all = torch.empty(M, d, device=dev) if want_t else None
+        dhead = self.pair_head.grad_slot if self.train_pair_head else None
+        loss_sum, _, c_it, d_img_own, _, _ = ops.sigmoid_objective(
+            img_n, txt_all, ig, cg_all, self.pair_head.data, 1.0 / Bg, self.scale_state, dk=d_txt_all, dhead=dhead,
+            want_dq=want_i, want_dk=False, want_dhead=False, accumulate=(False, False, True))
+        return loss_sum, c_it, d_img_own, d_txt_all
+
+    @property
+    def pair_scale_value(self) -> Optional[float]:
+        """t = exp(pair_head[0]) of the sigmoid objective (None under ``pair_loss="infonce"``).  Synchronises."""
+        return None if self.pair_head is None else float(math.exp(self.pair_head.data[0].item()))
+
+    @property
+    def pair_bias_value(self) -> Optional[float]:
+        """b = pair_head[1] of the sigmoid objective (None under ``pair_loss="infonce"``).  Synchronises."""
+        return None if self.pair_head is None else float(self.pair_head.data[1].item())
+
+    def _own_state(self) -> dict:
+        """``pair_loss`` and the sigmoid head (None under "infonce"; a trained head is also part of ``params``)."""
+        return {"pair_loss": self.pair_loss,
+                "pair_head": None if self.pair_head is None else self.pair_head.data.detach().cpu().clone()}
+
+    def _check_own_state(self, sd: dict) -> None:
+        theirs = sd.get("pair_loss", "infonce")  # a state without the key was written before the argument existed
+        if theirs != self.pair_loss:
+            raise ValueError(f"the saved state was written with pair_loss={theirs!r} and this trainer was built with "
+                             f"pair_loss={self.pair_loss!r}")
+
+    def _load_own_state(self, sd: dict) -> None:
+        if self.pair_head is not None and not self.train_pair_head:  # a trained head came back with ``params``
+            self.pair_head.data.copy_(sd["pair_head"])
+
     def step_pairs(self, images, captions, image_groups=None, caption_groups=None, global_batch: Optional[int] = None,
                    global_captions: Optional[int] = None, row_offset: int = 0, caption_offset: int = 0):
         """``zero_grad``, ``forward_backward_pairs``, ``optimizer_step``: one training step on (image, caption) pairs."""
@@ -1514,6 +1613,47 @@ class LoRATrainer(FlatStepTrainer):
                                           row_offset, caption_offset)
         self.optimizer_step()
         return out
+
+
+class LoRAPairTrainer(LoRATrainer):
+    """``LoRATrainer`` with the objective of ``step_pairs`` chosen at construction: the four arguments ``pair_loss``,
+    ``pair_scale``, ``pair_bias`` and ``train_pair_head`` after ``LoRATrainer``'s own, everything else inherited
+    (``LoRATrainer``'s constructor keeps its parameter list, which the suite pins).
+
+    ``pair_loss="infonce"`` (the default) builds exactly a ``LoRATrainer``: the same flat layout, the same launches.
+    ``"sigmoid"`` is the pairwise sigmoid (SigLIP) loss of ``ops.sigmoid_objective`` with ``pair_head``, a two-float DEVICE
+    parameter (log ``pair_scale``, ``pair_bias``) that the kernels read (SigLIP's initial point is t = 10, b = -10).  With
+    ``train_pair_head=True`` it is the LAST extra tensor of the flat buffer (after the prompt ctx and VPT), its
+    ``grad_slot`` is where the objective accumulates d loss / d (log t, b), the flat all-reduce sums the ranks' shares,
+    and AdamW moves it like every other entry -- INCLUDING the buffer's uniform weight decay, which pulls log t and b
+    towards 0 (there is no per-parameter decay).  Otherwise it stays outside the buffer (the flat layout is the default
+    trainer's) and its gradient is not formed.  ``pair_scale_value`` / ``pair_bias_value`` read it back (they
+    synchronise; ``step_pairs`` never uses them)."""
+
+    def __init__(self, model, lr: float = 2e-4, weight_decay: float = 1e-2, betas=(0.9, 0.999), eps: float = 1e-8,
+                 logit_scale: float = 100.0, prompt_ctx: Optional[nn.Parameter] = None, process_group=None,
+                 shard_text: bool = True, loss_scale=None, growth_factor: float = 2.0, backoff_factor: float = 0.5,
+                 growth_interval: int = 2000, init_scale: float = 65536.0, max_grad_norm: Optional[float] = None,
+                 ema_decay: Optional[float] = None, pair_loss: str = "infonce", pair_scale: float = 10.0,
+                 pair_bias: float = -10.0, train_pair_head: bool = False):
+        _check_loss_scale(loss_scale, init_scale, growth_factor, backoff_factor, growth_interval)
+        _check_step_options(max_grad_norm, ema_decay)
+        if pair_loss not in ("infonce", "sigmoid"):
+            raise ValueError(f"pair_loss must be 'infonce' or 'sigmoid', not {pair_loss!r}")
+        if pair_loss == "sigmoid":
+            for name, x in (("pair_scale", pair_scale), ("pair_bias", pair_bias)):
+                if isinstance(x, bool) or not isinstance(x, numbers.Real) or not math.isfinite(x):
+                    raise ValueError(f"{name} must be a finite number, not {x!r}")
+            if pair_scale <= 0:
+                raise ValueError(f"pair_scale must be positive (the head holds its logarithm), not {pair_scale!r}")
+            self.pair_loss = pair_loss
+            self.train_pair_head = bool(train_pair_head)
+            self.pair_head = nn.Parameter(torch.tensor([math.log(pair_scale), pair_bias], device=model.device,
+                                                       dtype=torch.float32), requires_grad=self.train_pair_head)
+        elif train_pair_head:
+            raise ValueError("train_pair_head needs pair_loss='sigmoid' (the InfoNCE logit_scale is a host constant)")
+        super().__init__(model, lr, weight_decay, betas, eps, logit_scale, prompt_ctx, process_group, shard_text, loss_scale,
+                         growth_factor, backoff_factor, growth_interval, init_scale, max_grad_norm, ema_decay)
 
 
 def gpu_train_loader(root: str, split: str = 'train', image_dir: str = '', batch_size: int = 256, scale=(0.05, 1.0),
