@@ -721,6 +721,17 @@ int clipfs_adamw_ext(float* p, const float* g, float* m, float* v, size_t n, int
                      float eps, float weight_decay, float grad_scale, const float* scaler_state, const float* clip_state,
                      float* ema_shadow, float ema_decay, void* stream);
 
+/* clipfs_adamw_ext with a TAIL: the last tail_n elements of the flat buffer (i >= n - tail_n) take tail_weight_decay
+ * in place of weight_decay and are clamped to [tail_min, tail_max] after the update (-inf / +inf: no bound on that
+ * side); the EMA shadow sees the clamped value.  This is what a trained log-temperature needs: free of weight decay,
+ * held at or below ln 100.  Same launch, same kernel; a step the scaler skips leaves the tail untouched too.
+ * tail_n = 0 is bitwise clipfs_adamw_ext.  CLIPFS_EINVAL for what clipfs_adamw_ext refuses, and for tail_n > n,
+ * tail_min > tail_max or a NaN bound. */
+int clipfs_adamw_tail(float* p, const float* g, float* m, float* v, size_t n, int step, float lr, float beta1, float beta2,
+                      float eps, float weight_decay, float grad_scale, const float* scaler_state, const float* clip_state,
+                      float* ema_shadow, float ema_decay, size_t tail_n, float tail_weight_decay, float tail_min,
+                      float tail_max, void* stream);
+
 /* -------------------------------------------------------------------- MTA --
  * solve_mta (lora_train_vlp.py:742-811; slow_pace.py:1363-1433), one workgroup per image.
  * feats [n_img, V, d] unit rows (row 0 = centre view), text [C, d] (unit rows; the reference
@@ -1153,6 +1164,61 @@ int clipfs_sigmoid_objective(const float* q, const float* k, const int32_t* q_gr
                              const float* head, float weight, const float* scaler_state, float* row_stats,
                              float* loss_sum, int32_t* correct, float* dq, int dq_accumulate, float* dk,
                              int dk_accumulate, float* dhead, int dhead_accumulate, int R, int N, int d, void* stream);
+
+/* --------------------------------------------------- clip pairs objective --
+ * CLIP's symmetric pair loss in ONE call with the logit scale on the device: head is a DEVICE pointer to one float,
+ * head[0] = log s, so the temperature is trainable and never passes through the host.  With s = expf(head[0]) let
+ * C(q, k, qg, kg, s, w) be the contrastive objective above (its live keys, P_i, n_i, dead rows, G and the hit count's
+ * ties to the lower index).  S = word CLIPFS_SCALER_SCALE of scaler_state, or 1 when it is NULL:
+ *   loss_sum [1] = C(q, k, .., weight_q).loss_sum + C(k, q, .., weight_k).loss_sum
+ *   dq [R, d]    = C(q, k).dq + C(k, q).dk            dk [N, d] = C(q, k).dk + C(k, q).dq
+ *   correct [2]  (int32, may be NULL) = the hit counts of C(q, k) and C(k, q)
+ *   dhead [1]    = sum over both directions of sum_ij G_ij z_ij = d loss / d log s   (S and the weights are inside G)
+ * i.e. one G for a cell, with lse_q / n_i the query rows' and lse_k / m_j the key rows' statistics:
+ *   G_ij = S (w_q (exp(z_ij - lse_q[i]) - [pos] / n_i) live_k[j] + w_k (exp(z_ij - lse_k[j]) - [pos] / m_j) live_q[i])
+ * weight_k == 0 means the second direction DOES NOT EXIST (it is not a multiplication by zero): no key-side statistics
+ * are computed, k_stats must be NULL, correct[1] = 0, and the call is C(q, k, .., weight_q) with dhead: the
+ * one-directional call a data-parallel rank makes.
+ *
+ * dq, dk and dhead are each optional (NULL: not formed).  With its accumulate flag set the finished sum is added ONCE
+ * to what is there (bitwise old + fresh); otherwise it is written.  S multiplies the three gradients only.
+ *
+ * q_stats [5, R] and k_stats [5, N] are OUTPUTS, not scratch (the entry point takes none), and every element is
+ * written: per row  0 lse,  1 1 / n,  2 the row loss,  3 E_softmax[z] - mean_P z (the row's share of dhead before the
+ * weight),  4 the best live index of the other side as int32 bits, -1 for a dead row or when nothing is live.  A row
+ * that contributes nothing (dead, or without a positive) has lse = +inf, 1 / n = 0 and rows 2, 3 = 0, which makes its G
+ * exactly 0 without a branch.  The gradient launches read rows 0 and 1, the combine launch rows 2 to 4.
+ *
+ * Neither z nor G reaches HBM; no float atomics; every sum runs in an order fixed by (R, N, d), every output element is
+ * written by one thread: results are bitwise equal run to run.  A cell has one fp32 z in every kernel and in both
+ * roles.  Nothing outside the stated extents is touched and nothing returns to the host.  Four launches at most:
+ *   rows     grid ceil(R / 32) + (both ? ceil(N / 32) : 0): a workgroup walks ALL of the other side in tiles of 128
+ *            (no key chunks: their partials would be scratch); the trailing workgroups are the key side
+ *   combine  one workgroup: loss_sum, correct and dhead by a fixed-order tree
+ *   dq, dk   grid (32 own-row tiles, chunks of feat_chunk features): ONE walk of the other side carries both
+ *            directions' G
+ *
+ * clipfs_clip_pairs_plan IS the function the entry point executes (both = weight_k != 0): host-only.  CLIPFS_EINVAL,
+ * the message naming the argument, for R or N < 1, d not a multiple of 4 in [4, 1024], both outside {0, 1}, an unknown
+ * op or a NULL plan.  clipfs_clip_pairs_objective refuses the same before anything is enqueued, and also: q, k,
+ * q_group, k_group, head, q_stats or loss_sum NULL; k_stats given with weight_k == 0 or NULL with weight_k != 0; q, k,
+ * dq or dk not 16-byte aligned; dq or dk overlapping q, k or each other; head, dhead or a statistics array overlapping
+ * another array of the call; a weight that is not finite; a scaler_state that is not 16-byte aligned. */
+#define CLIPFS_PAIRS_OP_ROWS 0
+#define CLIPFS_PAIRS_OP_COMBINE 1
+#define CLIPFS_PAIRS_OP_DQ 2
+#define CLIPFS_PAIRS_OP_DK 3
+struct clipfs_clip_pairs_plan {
+  unsigned grid_x, grid_y, grid_z, block;
+  unsigned lds_bytes;     /* LDS of a workgroup (at most 160 KB) */
+  int feat_chunk;         /* dq / dk: features per workgroup, 512, or 128 where 512 would leave compute units idle (0 otherwise) */
+};
+int clipfs_clip_pairs_plan(int op, int R, int N, int d, int both, struct clipfs_clip_pairs_plan* plan);
+int clipfs_clip_pairs_objective(const float* q, const float* k, const int32_t* q_group, const int32_t* k_group,
+                                const float* head, float weight_q, float weight_k, const float* scaler_state,
+                                float* q_stats, float* k_stats, float* loss_sum, int32_t* correct, float* dq,
+                                int dq_accumulate, float* dk, int dk_accumulate, float* dhead, int dhead_accumulate,
+                                int R, int N, int d, void* stream);
 
 #ifdef __cplusplus
 }

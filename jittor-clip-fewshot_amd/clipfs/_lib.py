@@ -125,6 +125,16 @@ class SigmoidPlan(C.Structure):
 SIGMOID_OPS = ("rows", "combine", "dq", "dk")
 
 
+class ClipPairsPlan(C.Structure):
+    """struct clipfs_clip_pairs_plan: what clipfs_clip_pairs_objective launches."""
+    _fields_ = [("grid_x", C.c_uint), ("grid_y", C.c_uint), ("grid_z", C.c_uint), ("block", C.c_uint), ("lds_bytes", C.c_uint),
+                ("feat_chunk", C.c_int)]
+
+
+# CLIPFS_PAIRS_OP_* of include/clipfs.h, by value
+CLIP_PAIRS_OPS = ("rows", "combine", "dq", "dk")
+
+
 class MergeJob(C.Structure):
     """struct clipfs_lora_merge_job: one projection of a clipfs_lora_merge table."""
     _fields_ = [("w", C.c_void_p), ("a", C.c_void_p), ("b", C.c_void_p), ("out", C.c_void_p), ("planes", C.c_void_p),
@@ -255,6 +265,7 @@ SIGNATURES = {
     "clipfs_grad_sumsq": (_i, [_p, _sz, _p, _p]),
     "clipfs_clip_decide": (_i, [_p, _sz, _f, _p, _p, _p]),
     "clipfs_adamw_ext": (_i, [_p, _p, _p, _p, _sz, _i, _f, _f, _f, _f, _f, _f, _p, _p, _p, _f, _p]),
+    "clipfs_adamw_tail": (_i, [_p, _p, _p, _p, _sz, _i, _f, _f, _f, _f, _f, _f, _p, _p, _p, _f, _sz, _f, _f, _f, _p]),
     "clipfs_mta_work_floats": (_sz, [_i, _i, _i, _i]),
     "clipfs_mta": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _p]),
     "clipfs_tta_views": (_i, [_p, _i, _i, _p, _i, _i, _p, _p, _p, _p]),
@@ -307,6 +318,8 @@ SIGNATURES = {
     "clipfs_contrastive_objective": (_i, [_p, _p, _p, _p, _f, _f, _p, _p, _p, _p, _p, _i, _p, _i, _p, _i, _i, _i, _p]),
     "clipfs_sigmoid_plan": (_i, [_i, _i, _i, _i, C.POINTER(SigmoidPlan)]),
     "clipfs_sigmoid_objective": (_i, [_p, _p, _p, _p, _p, _f, _p, _p, _p, _p, _p, _i, _p, _i, _p, _i, _i, _i, _i, _p]),
+    "clipfs_clip_pairs_plan": (_i, [_i, _i, _i, _i, _i, C.POINTER(ClipPairsPlan)]),
+    "clipfs_clip_pairs_objective": (_i, [_p, _p, _p, _p, _p, _f, _f, _p, _p, _p, _p, _p, _p, _i, _p, _i, _p, _i, _i, _i, _i, _p]),
 }
 
 # word indices of the loss-scaling record (CLIPFS_SCALER_* of include/clipfs.h)
@@ -400,6 +413,14 @@ def sigmoid_plan(op: str, R: int, N: int, d: int):
     plan = SigmoidPlan()
     check(load().clipfs_sigmoid_plan(SIGMOID_OPS.index(op), R, N, d, C.byref(plan)), "sigmoid_plan")
     return dict(grid=(plan.grid_x, plan.grid_y, plan.grid_z), **{k: getattr(plan, k) for k, _ in SigmoidPlan._fields_[3:]})
+
+
+def clip_pairs_plan(op: str, R: int, N: int, d: int, both: bool = True):
+    """The plan clipfs_clip_pairs_objective executes for these shapes (host-only; ``both``: weight_k != 0), as a dict of
+    the fields of struct clipfs_clip_pairs_plan with grid = (x, y, z).  A refusal raises ClipfsError with its message."""
+    plan = ClipPairsPlan()
+    check(load().clipfs_clip_pairs_plan(CLIP_PAIRS_OPS.index(op), R, N, d, int(both), C.byref(plan)), "clip_pairs_plan")
+    return dict(grid=(plan.grid_x, plan.grid_y, plan.grid_z), **{k: getattr(plan, k) for k, _ in ClipPairsPlan._fields_[3:]})
 
 
 def new_tower() -> Tower:

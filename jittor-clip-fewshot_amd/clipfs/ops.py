@@ -629,6 +629,21 @@ def adamw_ext(p, g, m, v, step, lr=2e-4, betas=(0.9, 0.999), eps=1e-8, weight_de
                                        _stream()), "adamw_ext")
 
 
+def adamw_tail(p, g, m, v, step, lr=2e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, grad_scale=1.0,
+               scale_state=None, clip_state=None, ema_shadow=None, ema_decay=0.999, *, tail_n=0, tail_weight_decay=0.0,
+               tail_min=float("-inf"), tail_max=float("inf")):
+    """``adamw_ext`` whose last ``tail_n`` elements take ``tail_weight_decay`` in place of ``weight_decay`` and are clamped
+    to [tail_min, tail_max] after the update (the EMA shadow sees the clamped value): a trained log-temperature at the
+    end of the flat buffer, free of decay and held below its cap.  ``tail_n=0`` is bitwise ``adamw_ext``."""
+    if ema_shadow is not None:
+        assert ema_shadow.shape == p.shape and ema_shadow.device == p.device
+        _f32(ema_shadow)
+    check(_lib.load().clipfs_adamw_tail(_p(p), _p(g), _p(m), _p(v), p.numel(), step, lr, betas[0], betas[1], eps,
+                                        weight_decay, grad_scale, None if scale_state is None else _p(_scaler(scale_state)),
+                                        None if clip_state is None else _p(_clip(clip_state)), _p(ema_shadow), ema_decay,
+                                        tail_n, tail_weight_decay, tail_min, tail_max, _stream()), "adamw_tail")
+
+
 def mta(feats, text, want_mode=True, want_logits=True):
     """feats [n_img, V, d] unit rows, text [C, d] unit rows -> (mode [n_img,d], logits [n_img,C])"""
     n_img, V, d = feats.shape
@@ -970,3 +985,87 @@ def siglip_loss(img, txt, img_group=None, txt_group=None, *, head):
     elif img_group is None or txt_group is None:
         raise ValueError("siglip_loss needs both img_group and txt_group, or neither")
     return SiglipLossFn.apply(img, txt, head, img_group.to(torch.int32).contiguous(), txt_group.to(torch.int32).contiguous())
+
+
+# ------------------------------------------------------------------------------------------------- clip pairs objective
+def clip_pairs_plan(op: str, R: int, N: int, d: int, both: bool = True):
+    """What ``clip_pairs_objective`` launches for these shapes ("rows", "combine", "dq", "dk"; host-only; ``both``:
+    weight_k != 0): grid, block, lds_bytes, feat_chunk.  There is no scratch size: the entry point takes none."""
+    return _lib.clip_pairs_plan(op, R, N, d, both)
+
+
+def clip_pairs_objective(q, k, q_group, k_group, head, weight_q, weight_k=0.0, scale_state=None, dq=None, dk=None, dhead=None,
+                         want_dq=True, want_dk=True, want_dhead=True, accumulate=False):
+    """CLIP's symmetric pair loss in one call, the logit scale on the device: ``contrastive_objective`` of ``q`` [R, d]
+    against ``k`` [N, d] with weight ``weight_q`` PLUS the same with the roles swapped and weight ``weight_k``, both at
+    s = exp(head[0]); at most four launches, one walk of the logits per gradient carrying both directions.  ``head``: a
+    DEVICE tensor of one float, log s, read by the kernels (nothing passes through the host).  ``weight_k == 0``: the
+    second direction does not exist (no key statistics; the one-directional call of a data-parallel rank).  Returns
+    (loss_sum [1], q_stats [5, R], k_stats [5, N] or None, correct [2] int32 (q -> k, k -> q), dq [R, d] or None,
+    dk [N, d] or None, dhead [1] = d loss / d log s or None); a statistics array holds per row lse, 1 / n, the row loss,
+    E_softmax[z] - mean_P z and the best live index of the other side as int32 bits.  A passed ``dq`` / ``dk`` / ``dhead``
+    is overwritten and returned (``accumulate=True``, or a (dq, dk, dhead) triple of flags: ACCUMULATED into instead,
+    bitwise old + fresh); otherwise the gradient is made when ``want_dq`` / ``want_dk`` / ``want_dhead``.
+    ``scale_state`` (a loss-scaling record) multiplies the three gradients only."""
+    R, d = q.shape
+    N = k.shape[0]
+    assert k.shape[1] == d, (tuple(q.shape), tuple(k.shape))
+    for g, n in ((q_group, R), (k_group, N)):
+        assert g.dtype == torch.int32 and g.is_contiguous() and g.numel() == n, "groups are contiguous int32 [R] / [N]"
+    assert head.dtype == torch.float32 and head.numel() == 1 and head.is_contiguous(), "head is one float, log s"
+    dev = q.device
+    acc_q, acc_k, acc_h = accumulate if isinstance(accumulate, tuple) else (accumulate,) * 3
+    acc_q, acc_k, acc_h = acc_q and dq is not None, acc_k and dk is not None, acc_h and dhead is not None
+    if dq is None and want_dq:
+        dq = torch.empty(R, d, device=dev, dtype=torch.float32)
+    if dk is None and want_dk:
+        dk = torch.empty(N, d, device=dev, dtype=torch.float32)
+    if dhead is None and want_dhead:
+        dhead = torch.empty(1, device=dev, dtype=torch.float32)
+    assert dq is None or tuple(dq.shape) == (R, d), "dq is [R, d]"
+    assert dk is None or tuple(dk.shape) == (N, d), "dk is [N, d]"
+    assert dhead is None or (dhead.numel() == 1 and dhead.is_contiguous()), "dhead is one float"
+    q_stats = torch.empty(5, R, device=dev, dtype=torch.float32)
+    k_stats = torch.empty(5, N, device=dev, dtype=torch.float32) if weight_k != 0.0 else None
+    loss_sum = torch.empty(1, device=dev, dtype=torch.float32)
+    correct = torch.empty(2, device=dev, dtype=torch.int32)
+    check(_lib.load().clipfs_clip_pairs_objective(
+        _p(_f32(q)), _p(_f32(k)), _p(q_group), _p(k_group), _p(_f32(head)), weight_q, weight_k,
+        None if scale_state is None else _p(_scaler(scale_state)), _p(q_stats), _p(k_stats), _p(loss_sum), _p(correct),
+        None if dq is None else _p(_f32(dq)), int(acc_q), None if dk is None else _p(_f32(dk)), int(acc_k),
+        None if dhead is None else _p(_f32(dhead)), int(acc_h), R, N, d, _stream()), "clip_pairs_objective")
+    return loss_sum, q_stats, k_stats, correct, dq, dk, dhead
+
+
+class ClipPairsLossFn(torch.autograd.Function):
+    """``clip_pairs_loss``: ONE symmetric call of ``clip_pairs_objective``."""
+
+    @staticmethod
+    def forward(ctx, img, txt, head, img_group, txt_group):
+        img, txt, head = img.contiguous(), txt.contiguous(), head.contiguous()
+        need = ctx.needs_input_grad[:3]
+        loss, _, _, _, dimg, dtxt, dhead = clip_pairs_objective(img, txt, img_group, txt_group, head, 0.5 / img.shape[0],
+                                                                0.5 / txt.shape[0], want_dq=need[0], want_dk=need[1],
+                                                                want_dhead=need[2])
+        ctx.save_for_backward(*(t for t in (dimg, dtxt, dhead) if t is not None))
+        ctx.have = (dimg is not None, dtxt is not None, dhead is not None)
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, dloss):
+        saved = list(ctx.saved_tensors)
+        return (*(saved.pop(0) * dloss if have else None for have in ctx.have), None, None)
+
+
+def clip_pairs_loss(img, txt, img_group=None, txt_group=None, *, head):
+    """``clip_loss`` with a trainable temperature: CLIP's symmetric contrastive loss of unit image rows ``img`` [B, d] and
+    unit caption rows ``txt`` [M, d] at the logit scale exp(head[0]), a scalar with autograd to ``img``, ``txt`` and
+    ``head`` (a device tensor of one float, log s), from one symmetric call with the weights 0.5 / B and 0.5 / M.  With
+    both groups None the rows are pairs (M == B, group = row index)."""
+    if img_group is None and txt_group is None:
+        if img.shape[0] != txt.shape[0]:
+            raise ValueError(f"clip_pairs_loss without groups pairs row i with row i: {img.shape[0]} images, {txt.shape[0]} captions")
+        img_group = txt_group = torch.arange(img.shape[0], device=img.device, dtype=torch.int32)
+    elif img_group is None or txt_group is None:
+        raise ValueError("clip_pairs_loss needs both img_group and txt_group, or neither")
+    return ClipPairsLossFn.apply(img, txt, head, img_group.to(torch.int32).contiguous(), txt_group.to(torch.int32).contiguous())

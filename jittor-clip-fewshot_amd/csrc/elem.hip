@@ -542,13 +542,15 @@ __device__ __forceinline__ void adamw_element(float* __restrict__ p, const float
 // The one AdamW kernel, with three optional records (each NULL or given, uniform over the launch): bias corrections,
 // gradient scale and the skip decision from the loss-scaling record sf when there is one (below), the gradient
 // multiplier from the clip record cs when there is one, and the EMA shadow updated from the parameter just computed.
-// With all three NULL it is the plain update at the arguments' inv_sqrt_bc2 / step_size / grad_scale.
+// With all three NULL it is the plain update at the arguments' inv_sqrt_bc2 / step_size / grad_scale.  Elements from
+// tail_start on (n: none) take the decay tail_wd and are clamped to [tail_min, tail_max] before the shadow reads them.
 __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                     float* __restrict__ m, float* __restrict__ v, size_t n, float lr,
                                                     float b1, float b2, float eps, float wd, float inv_sqrt_bc2,
                                                     float step_size, float grad_scale,
                                                     const float* __restrict__ sf, const float* __restrict__ cs,
-                                                    float* __restrict__ shadow, float decay, float one_minus_decay) {
+                                                    float* __restrict__ shadow, float decay, float one_minus_decay,
+                                                    size_t tail_start, float tail_wd, float tail_min, float tail_max) {
   const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
   if (sf) {
@@ -558,7 +560,9 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const
     grad_scale = sf[CLIPFS_SCALER_INV_SCALE];
   }
   if (cs) grad_scale = cs[CLIPFS_CLIP_MULT];
-  adamw_element(p, g, m, v, i, lr, b1, b2, eps, wd, inv_sqrt_bc2, step_size, grad_scale);
+  const bool tail = i >= tail_start;
+  adamw_element(p, g, m, v, i, lr, b1, b2, eps, tail ? tail_wd : wd, inv_sqrt_bc2, step_size, grad_scale);
+  if (tail) p[i] = fminf(fmaxf(p[i], tail_min), tail_max);
   if (shadow) shadow[i] = fmaf(decay, shadow[i], one_minus_decay * p[i]);
 }
 
@@ -1170,12 +1174,13 @@ extern "C" int clipfs_colsum(const float* x, const float* y, float* out, int row
   return launch_status();
 }
 
-// The one AdamW launch behind clipfs_adamw / clipfs_adamw_scaled / clipfs_adamw_ext (each checks its own arguments
-// first).  Without a scaler record the bias corrections come from `step` (>= 1) here; with one the kernel reads them
+// The one AdamW launch behind clipfs_adamw / clipfs_adamw_scaled / clipfs_adamw_ext / clipfs_adamw_tail (each checks
+// its own arguments first; the first three pass tail_n = 0).  Without a scaler record the bias corrections come from `step` (>= 1) here; with one the kernel reads them
 // from the record and neither `step` nor `grad_scale` is used.
 static int launch_adamw(float* p, const float* g, float* m, float* v, size_t n, int step, float lr, float beta1,
                         float beta2, float eps, float weight_decay, float grad_scale, const float* scaler_state,
-                        const float* clip_state, float* ema_shadow, float ema_decay, void* stream) {
+                        const float* clip_state, float* ema_shadow, float ema_decay, void* stream, size_t tail_n = 0,
+                        float tail_wd = 0.f, float tail_min = -INFINITY, float tail_max = INFINITY) {
   float inv_sqrt_bc2 = 0.f, step_size = 0.f;  // read from the record when there is one
   if (!scaler_state) {
     const double bc1 = 1.0 - pow((double)beta1, step);
@@ -1185,7 +1190,7 @@ static int launch_adamw(float* p, const float* g, float* m, float* v, size_t n, 
   }
   hipLaunchKernelGGL(adamw_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, lr,
                      beta1, beta2, eps, weight_decay, inv_sqrt_bc2, step_size, grad_scale, scaler_state, clip_state,
-                     ema_shadow, ema_decay, 1.f - ema_decay);
+                     ema_shadow, ema_decay, 1.f - ema_decay, n - tail_n, tail_wd, tail_min, tail_max);
   return launch_status();
 }
 
@@ -1270,6 +1275,27 @@ extern "C" int clipfs_adamw_ext(float* p, const float* g, float* m, float* v, si
   CLIPFS_REQUIRE(scaler_state || step >= 1, "adamw_ext: step %d must be >= 1 without a scaler state", step);
   return launch_adamw(p, g, m, v, n, step, lr, beta1, beta2, eps, weight_decay, grad_scale, scaler_state, clip_state,
                       ema_shadow, ema_decay, stream);
+}
+
+extern "C" int clipfs_adamw_tail(float* p, const float* g, float* m, float* v, size_t n, int step, float lr, float beta1,
+                                 float beta2, float eps, float weight_decay, float grad_scale, const float* scaler_state,
+                                 const float* clip_state, float* ema_shadow, float ema_decay, size_t tail_n,
+                                 float tail_weight_decay, float tail_min, float tail_max, void* stream) {
+  CLIPFS_REQUIRE(p && g && m && v && aligned4(p) && aligned4(g) && aligned4(m) && aligned4(v),
+                 "adamw_tail: null or misaligned pointer");
+  CLIPFS_REQUIRE(!scaler_state || aligned16(scaler_state), "adamw_tail: misaligned scaler state");
+  CLIPFS_REQUIRE(!clip_state || aligned16(clip_state), "adamw_tail: misaligned clip state");
+  CLIPFS_REQUIRE(!ema_shadow || (aligned4(ema_shadow) && ema_shadow != p && ema_shadow != m && ema_shadow != v),
+                 "adamw_tail: misaligned or aliased ema shadow");
+  CLIPFS_REQUIRE(!ema_shadow || (ema_decay > 0.f && ema_decay < 1.f), "adamw_tail: ema_decay %g must lie in (0, 1)",
+                 (double)ema_decay);
+  CLIPFS_REQUIRE(n > 0, "adamw_tail: n = 0");
+  CLIPFS_REQUIRE(scaler_state || step >= 1, "adamw_tail: step %d must be >= 1 without a scaler state", step);
+  CLIPFS_REQUIRE(tail_n <= n, "adamw_tail: tail_n = %zu exceeds n = %zu", tail_n, n);
+  CLIPFS_REQUIRE(tail_min == tail_min && tail_max == tail_max, "adamw_tail: tail_min or tail_max is NaN");
+  CLIPFS_REQUIRE(tail_min <= tail_max, "adamw_tail: tail_min = %g exceeds tail_max = %g", (double)tail_min, (double)tail_max);
+  return launch_adamw(p, g, m, v, n, step, lr, beta1, beta2, eps, weight_decay, grad_scale, scaler_state, clip_state,
+                      ema_shadow, ema_decay, stream, tail_n, tail_weight_decay, tail_min, tail_max);
 }
 
 extern "C" int clipfs_l1_loss(const float* a, const float* b, size_t n, float* loss, float* da, float grad_scale,

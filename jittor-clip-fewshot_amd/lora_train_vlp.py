@@ -1029,6 +1029,10 @@ class FlatStepTrainer:
         """What a subclass does after the AdamW launch of ``optimizer_step``."""
         raise NotImplementedError
 
+    # (tail_n, weight decay, lower bound, upper bound) of the flat buffer's last entries where a subclass gives them an
+    # update that differs from plain AdamW (``LoRAPairTrainer``'s trained log-temperature); None: the plain launch
+    tail_update = None
+
     def _apply_update(self):
         """The launches of one optimiser step after the all-reduce (``self.t`` already counts this step): the one AdamW
         launch, which takes every record that is on (None = off), behind the scaler's and the clip's own launches."""
@@ -1040,8 +1044,14 @@ class FlatStepTrainer:
         if self.clip_state is not None:
             ops.grad_sumsq(f.grads, self._sumsq_work)
             ops.clip_decide(self._sumsq_work, f.numel, self.max_grad_norm, self.clip_state, self.scale_state)
-        ops.adamw_ext(f.params, f.grads, f.m, f.v, self.t, self.lr, self.betas, self.eps, self.wd, 1.0,
-                      self.scale_state, self.clip_state, self.ema_shadow, self.ema_decay or 0.0)
+        if self.tail_update is None:
+            ops.adamw_ext(f.params, f.grads, f.m, f.v, self.t, self.lr, self.betas, self.eps, self.wd, 1.0,
+                          self.scale_state, self.clip_state, self.ema_shadow, self.ema_decay or 0.0)
+        else:  # the buffer's last entries with a decay and bounds of their own: the same one launch
+            tail_n, tail_wd, tail_min, tail_max = self.tail_update
+            ops.adamw_tail(f.params, f.grads, f.m, f.v, self.t, self.lr, self.betas, self.eps, self.wd, 1.0,
+                           self.scale_state, self.clip_state, self.ema_shadow, self.ema_decay or 0.0, tail_n=tail_n,
+                           tail_weight_decay=tail_wd, tail_min=tail_min, tail_max=tail_max)
 
     # -- loss scaling: host views of the device record (each one synchronises) -------------------------
     def _scaler_word(self, index: int, as_int: bool):
@@ -1440,7 +1450,12 @@ class LoRATrainer(FlatStepTrainer):
         only the caption block is all-gathered (and the caption groups when given); image features and image groups
         stay local, the caption-gradient table is written afresh and reduce-scattered, and the flat all-reduce sums the
         ranks' shares of the head's gradient: 3 collectives for plain pairs, 4 with groups, one fewer with the text tower
-        frozen.  Everything else is as above."""
+        frozen.  Everything else is as above.
+
+        ``pair_loss="clip"``: the first loss above at the logit scale exp(pair_head[0]), read on the device (and trained
+        with ``train_pair_head``).  One process: ONE symmetric call of ``ops.clip_pairs_objective`` (four launches, one
+        walk of the logits per gradient).  Data parallel: the exchange above unchanged, the two calls one-directional
+        (``weight_k = 0``); the head's gradient accumulates over both and the flat all-reduce sums the ranks' shares."""
         from clipfs import dist as D
         m = self.model
         eng = m.engine
@@ -1520,17 +1535,37 @@ class LoRATrainer(FlatStepTrainer):
                 d_img_all = None
                 my_img = my_cap = 0
             s = self.logit_scale
-            # local images x all captions: the images' own gradient, and the caption-gradient table written afresh
-            l_it, _, c_it, d_img_own, _ = ops.contrastive_objective(img_n, txt_all, ig, cg_all, s, 0.5 / Bg, self.scale_state,
-                                                                    dk=d_txt_all, want_dq=want_i, want_dk=False,
-                                                                    accumulate=False)
-            # local captions x all images: added into this rank's rows of the caption table; the image side is added to
-            # the images' own gradient (one process) or written afresh into the image-gradient table (data parallel)
-            l_ti, _, c_ti, _, _ = ops.contrastive_objective(txt, img_all, cg, ig_all, s, 0.5 / Mg, self.scale_state,
-                                                            dq=d_txt_all[my_cap:my_cap + M] if want_t else None,
-                                                            dk=d_img_all if live else d_img_own, want_dq=False, want_dk=False,
-                                                            accumulate=(True, not live))
-            loss_sum = l_it + l_ti
+            if self.pair_loss == "clip":
+                head = self.pair_head.data
+                dhead = self.pair_head.grad_slot if self.train_pair_head else None
+            if self.pair_loss == "clip" and not live:
+                # ONE symmetric call: both directions' statistics, one walk of the logits per gradient
+                loss_sum, _, _, hits, d_img_own, _, _ = ops.clip_pairs_objective(
+                    img_n, txt, ig, cg, head, 0.5 / Bg, 0.5 / Mg, self.scale_state, dk=d_txt_all, dhead=dhead,
+                    want_dq=want_i, want_dk=False, want_dhead=False, accumulate=(False, False, True))
+                c_it, c_ti = hits[:1], hits[1:]
+            elif self.pair_loss == "clip":
+                # the exchange below, call for call, with the scale read on the device; dhead accumulates over both
+                l_it, _, _, hits, d_img_own, _, _ = ops.clip_pairs_objective(
+                    img_n, txt_all, ig, cg_all, head, 0.5 / Bg, 0.0, self.scale_state, dk=d_txt_all, dhead=dhead,
+                    want_dq=want_i, want_dk=False, want_dhead=False, accumulate=(False, False, True))
+                l_ti, _, _, hits_t, _, _, _ = ops.clip_pairs_objective(
+                    txt, img_all, cg, ig_all, head, 0.5 / Mg, 0.0, self.scale_state,
+                    dq=d_txt_all[my_cap:my_cap + M] if want_t else None, dk=d_img_all, dhead=dhead,
+                    want_dq=False, want_dk=False, want_dhead=False, accumulate=(True, False, True))
+                loss_sum, c_it, c_ti = l_it + l_ti, hits[:1], hits_t[:1]
+            else:
+                # local images x all captions: the images' own gradient, and the caption-gradient table written afresh
+                l_it, _, c_it, d_img_own, _ = ops.contrastive_objective(img_n, txt_all, ig, cg_all, s, 0.5 / Bg,
+                                                                        self.scale_state, dk=d_txt_all, want_dq=want_i,
+                                                                        want_dk=False, accumulate=False)
+                # local captions x all images: added into this rank's rows of the caption table; the image side is added
+                # to the images' own gradient (one process) or written afresh into the image-gradient table (data parallel)
+                l_ti, _, c_ti, _, _ = ops.contrastive_objective(txt, img_all, cg, ig_all, s, 0.5 / Mg, self.scale_state,
+                                                                dq=d_txt_all[my_cap:my_cap + M] if want_t else None,
+                                                                dk=d_img_all if live else d_img_own, want_dq=False,
+                                                                want_dk=False, accumulate=(True, not live))
+                loss_sum = l_it + l_ti
             scatter_images = live  # each rank holds a share of every image's gradient from the captions' direction
         if want_t:
             if live:
@@ -1582,13 +1617,14 @@ class LoRATrainer(FlatStepTrainer):
 
     @property
     def pair_scale_value(self) -> Optional[float]:
-        """t = exp(pair_head[0]) of the sigmoid objective (None under ``pair_loss="infonce"``).  Synchronises."""
+        """t = exp(pair_head[0]) of the sigmoid objective, s of the "clip" one (None under ``pair_loss="infonce"``).
+        Synchronises."""
         return None if self.pair_head is None else float(math.exp(self.pair_head.data[0].item()))
 
     @property
     def pair_bias_value(self) -> Optional[float]:
-        """b = pair_head[1] of the sigmoid objective (None under ``pair_loss="infonce"``).  Synchronises."""
-        return None if self.pair_head is None else float(self.pair_head.data[1].item())
+        """b = pair_head[1] of the sigmoid objective (None under the other two).  Synchronises."""
+        return None if self.pair_head is None or self.pair_head.numel() < 2 else float(self.pair_head.data[1].item())
 
     def _own_state(self) -> dict:
         """``pair_loss`` and the sigmoid head (None under "infonce"; a trained head is also part of ``params``)."""
@@ -1616,9 +1652,18 @@ class LoRATrainer(FlatStepTrainer):
 
 
 class LoRAPairTrainer(LoRATrainer):
-    """``LoRATrainer`` with the objective of ``step_pairs`` chosen at construction: the four arguments ``pair_loss``,
-    ``pair_scale``, ``pair_bias`` and ``train_pair_head`` after ``LoRATrainer``'s own, everything else inherited
+    """``LoRATrainer`` with the objective of ``step_pairs`` chosen at construction: the arguments ``pair_loss``,
+    ``pair_scale``, ``pair_bias``, ``train_pair_head``, ``pair_scale_max`` and ``pair_head_weight_decay`` after
+    ``LoRATrainer``'s own, everything else inherited
     (``LoRATrainer``'s constructor keeps its parameter list, which the suite pins).
+
+    ``pair_loss="clip"`` is the InfoNCE loss with CLIP's own temperature: ``pair_head`` is ONE float on the device,
+    log(``logit_scale``), read by ``ops.clip_pairs_objective`` (``pair_scale`` / ``pair_bias`` belong to "sigmoid" and are
+    refused).  With ``train_pair_head=True`` it is trained as CLIP and OpenCLIP train it: the buffer's last entry, free of
+    weight decay (``pair_head_weight_decay``: None = 0 here, the buffer's decay under "sigmoid") and clamped at
+    log(``pair_scale_max``) after every update (100, CLIP's ln 100; None: no clamp; under the other two it must stay at
+    its default and does nothing).  The decay and the clamp ride in the one AdamW launch (``ops.adamw_tail``), issued
+    only where they differ from plain AdamW.
 
     ``pair_loss="infonce"`` (the default) builds exactly a ``LoRATrainer``: the same flat layout, the same launches.
     ``"sigmoid"`` is the pairwise sigmoid (SigLIP) loss of ``ops.sigmoid_objective`` with ``pair_head``, a two-float DEVICE
@@ -1626,21 +1671,45 @@ class LoRAPairTrainer(LoRATrainer):
     ``train_pair_head=True`` it is the LAST extra tensor of the flat buffer (after the prompt ctx and VPT), its
     ``grad_slot`` is where the objective accumulates d loss / d (log t, b), the flat all-reduce sums the ranks' shares,
     and AdamW moves it like every other entry -- INCLUDING the buffer's uniform weight decay, which pulls log t and b
-    towards 0 (there is no per-parameter decay).  Otherwise it stays outside the buffer (the flat layout is the default
-    trainer's) and its gradient is not formed.  ``pair_scale_value`` / ``pair_bias_value`` read it back (they
-    synchronise; ``step_pairs`` never uses them)."""
+    towards 0, unless ``pair_head_weight_decay`` says otherwise.  A head that is not trained stays outside the buffer (the
+    flat layout is the default trainer's) and its gradient is not formed.  ``pair_scale_value`` / ``pair_bias_value`` read
+    it back (they synchronise; ``step_pairs`` never uses them)."""
 
     def __init__(self, model, lr: float = 2e-4, weight_decay: float = 1e-2, betas=(0.9, 0.999), eps: float = 1e-8,
                  logit_scale: float = 100.0, prompt_ctx: Optional[nn.Parameter] = None, process_group=None,
                  shard_text: bool = True, loss_scale=None, growth_factor: float = 2.0, backoff_factor: float = 0.5,
                  growth_interval: int = 2000, init_scale: float = 65536.0, max_grad_norm: Optional[float] = None,
                  ema_decay: Optional[float] = None, pair_loss: str = "infonce", pair_scale: float = 10.0,
-                 pair_bias: float = -10.0, train_pair_head: bool = False):
+                 pair_bias: float = -10.0, train_pair_head: bool = False, pair_scale_max: Optional[float] = 100.0,
+                 pair_head_weight_decay: Optional[float] = None):
         _check_loss_scale(loss_scale, init_scale, growth_factor, backoff_factor, growth_interval)
         _check_step_options(max_grad_norm, ema_decay)
-        if pair_loss not in ("infonce", "sigmoid"):
-            raise ValueError(f"pair_loss must be 'infonce' or 'sigmoid', not {pair_loss!r}")
-        if pair_loss == "sigmoid":
+        if pair_loss not in ("infonce", "sigmoid", "clip"):
+            raise ValueError(f"pair_loss must be 'infonce', 'sigmoid' or 'clip', not {pair_loss!r}")
+        if pair_head_weight_decay is not None and (isinstance(pair_head_weight_decay, bool)
+                                                   or not isinstance(pair_head_weight_decay, numbers.Real)
+                                                   or not math.isfinite(pair_head_weight_decay) or pair_head_weight_decay < 0):
+            raise ValueError(f"pair_head_weight_decay must be None or a finite number >= 0, not {pair_head_weight_decay!r}")
+        if pair_scale_max is not None and (isinstance(pair_scale_max, bool) or not isinstance(pair_scale_max, numbers.Real)
+                                           or not math.isfinite(pair_scale_max) or pair_scale_max <= 0):
+            raise ValueError(f"pair_scale_max must be None or a positive finite number, not {pair_scale_max!r}")
+        if pair_loss != "clip" and pair_scale_max != 100.0:
+            raise ValueError(f"pair_scale_max needs pair_loss='clip' (under {pair_loss!r} nothing is clamped): leave it at its "
+                             "default")
+        if pair_loss == "clip":
+            for name, x, default in (("pair_scale", pair_scale, 10.0), ("pair_bias", pair_bias, -10.0)):
+                if x != default:
+                    raise ValueError(f"{name} belongs to pair_loss='sigmoid': under 'clip' the scale starts at logit_scale "
+                                     "and there is no bias")
+            if isinstance(logit_scale, bool) or not isinstance(logit_scale, numbers.Real) or not math.isfinite(logit_scale) \
+                    or logit_scale <= 0:
+                raise ValueError(f"logit_scale must be a positive finite number under pair_loss='clip' (the head holds its "
+                                 f"logarithm), not {logit_scale!r}")
+            self.pair_loss = pair_loss
+            self.train_pair_head = bool(train_pair_head)
+            self.pair_head = nn.Parameter(torch.tensor([math.log(logit_scale)], device=model.device, dtype=torch.float32),
+                                          requires_grad=self.train_pair_head)
+        elif pair_loss == "sigmoid":
             for name, x in (("pair_scale", pair_scale), ("pair_bias", pair_bias)):
                 if isinstance(x, bool) or not isinstance(x, numbers.Real) or not math.isfinite(x):
                     raise ValueError(f"{name} must be a finite number, not {x!r}")
@@ -1651,9 +1720,19 @@ class LoRAPairTrainer(LoRATrainer):
             self.pair_head = nn.Parameter(torch.tensor([math.log(pair_scale), pair_bias], device=model.device,
                                                        dtype=torch.float32), requires_grad=self.train_pair_head)
         elif train_pair_head:
-            raise ValueError("train_pair_head needs pair_loss='sigmoid' (the InfoNCE logit_scale is a host constant)")
+            raise ValueError("train_pair_head needs pair_loss='sigmoid' or 'clip' (under 'infonce' the logit_scale is a "
+                             "host constant)")
         super().__init__(model, lr, weight_decay, betas, eps, logit_scale, prompt_ctx, process_group, shard_text, loss_scale,
                          growth_factor, backoff_factor, growth_interval, init_scale, max_grad_norm, ema_decay)
+        self.pair_scale_max = pair_scale_max if pair_loss == "clip" else None
+        self.pair_head_weight_decay = pair_head_weight_decay
+        if self.train_pair_head:
+            # the head is the buffer's tail: its decay (None: the buffer's under "sigmoid", 0 under "clip") and the clamp
+            # of log s; where both are what plain AdamW does anyway, the plain launch is issued
+            tail_wd = pair_head_weight_decay if pair_head_weight_decay is not None else (0.0 if pair_loss == "clip" else self.wd)
+            tail_max = math.log(self.pair_scale_max) if self.pair_scale_max is not None else math.inf
+            if tail_wd != self.wd or tail_max != math.inf:
+                self.tail_update = (self.pair_head.numel(), float(tail_wd), -math.inf, tail_max)
 
 
 def gpu_train_loader(root: str, split: str = 'train', image_dir: str = '', batch_size: int = 256, scale=(0.05, 1.0),
