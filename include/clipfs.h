@@ -1220,6 +1220,125 @@ int clipfs_clip_pairs_objective(const float* q, const float* k, const int32_t* q
                                 int dq_accumulate, float* dk, int dk_accumulate, float* dhead, int dhead_accumulate,
                                 int R, int N, int d, void* stream);
 
+/* --------------------------------------------------------------------- TDA --
+ * The training-free dynamic adapter (Karmanov et al., "Efficient Test-Time Adaptation of Vision-Language Models",
+ * CVPR 2024): a zero-shot classifier adapted at test time by two caches of test features, with no labels, no backward
+ * and no extra views; fp32 in every engine precision mode.  The published form handles one image at a time on the
+ * host; here one call adapts B samples on the device and IS B applications of the sequential rule in row order.
+ *
+ * THE RULE.  Fixed: unit class features T [C, d], logit scale s, capacities Sp and Sn (0 disables that cache),
+ * pos_alpha, pos_beta, neg_alpha, neg_beta, the entropy band (ent_lo, ent_hi), the mask band (mask_lo, mask_hi).  For
+ * one sample with unit feature f at global sample number t:
+ *   1. z = s T f      2. lse = logsumexp(z)      3. p_c = exp(z_c - lse)
+ *   4. H = -sum_c p_c (z_c - lse) in nats (never the log of an underflowed p; >= 0)
+ *   5. pred = argmax z, ties to the lower index (the rule of clipfs_topk)
+ *   6. h = H / log2(C) (the published normaliser, although H is in nats; C == 1: h = 0)
+ *   7. positive cache, queue of class pred: with fewer than Sp slots occupied take the lowest free slot; otherwise let
+ *      w be the occupied slot of largest stored entropy, ties to the most recently inserted, and replace w iff
+ *      H < ent[w] (strict, fp32 as stored); else nothing.  An entry is (f, H, t).
+ *   8. negative cache, only if ent_lo < h < ent_hi (both strict): the same insertion on the negative queue of class
+ *      pred; the entry is (f, H, t, m), m_c = 1 iff mask_lo < p_c < mask_hi.
+ *   9. AFTER both updates (a sample sees itself if it was inserted):
+ *      out = z + pos_alpha sum_{e in pos} exp(-pos_beta (1 - f . k_e)) onehot(class_e)
+ *              - neg_alpha sum_{e in neg} exp(-neg_beta (1 - f . k_e)) m_e
+ * update == 0 evaluates step 9 against the state as it stands and changes nothing.  z, H, pred, h and m of a sample
+ * are bitwise independent of B and of its row, so the state after any split of a stream into calls is bitwise the
+ * same.  At s = 100 confident samples have H near 0 and many comparisons of step 7 are between rounding noise: the
+ * fp32 compare and the tie rule make the outcome deterministic all the same.
+ *
+ * HOW.  Steps 7 and 8 depend only on (pred, H, h) of earlier samples, never on a cache logit, and the queues of
+ * different classes are independent.  A scan with one thread per class turns the batch into intervals: entry j (an old
+ * slot or a batch row) is in its cache exactly for the batch rows born_j <= i < evict_j, and step 9 is a dense masked
+ * sum over (old slots + batch rows).  Five launches at most, whatever B and C: z tiles on the fp32 matrix cores into
+ * `out`; per-row statistics; the scan; the masked logits (32 x 32 affinity tiles, contracted on the matrix cores with
+ * one-hot class rows or mask rows; the affinity never reaches memory; tiles with no live entry are skipped); the
+ * write-back of the survivors (after the logits launch has read the old state; a slot with several occupants within
+ * the batch receives the last).  The logits launch is absent when both capacities are 0 (out is then bitwise z), the
+ * write-back when update == 0.  No float atomics; every output element is written by one thread.  Summation order of
+ * an output element: positive old slots, positive batch rows, negative old slots, negative batch rows, each in
+ * ascending tiles of 32 entries, within a tile entries (i, 16 + i) for i = 0 .. 15; then out = z + sum.  Nothing
+ * returns to the host.
+ *
+ * state (all device memory, fixed shapes): pos_keys [C, Sp, d], pos_ent [C, Sp] (+inf = empty), pos_seq [C, Sp] int64
+ * (-1 = empty: a slot is occupied iff seq >= 0), the same three for the negative cache, neg_mask [C, Sn, C] bytes,
+ * counter [1] int64 = the number of samples seen (t of row b is counter + b; the write-back adds B).  The members of a
+ * cache of capacity 0 may be NULL.
+ *
+ * record: the per-sample OUTPUTS of the call, every element written (none is scratch, none is read before it is
+ * written): pred [B] int32, entropy [B] = H, hnorm [B] = h, band [B] int32 (1 iff in the entropy band), seq [B] int64
+ * = t, mask [B, C] bytes = m, pos_slot / neg_slot [B] int32 (the slot the sample was inserted into, -1 if it was not),
+ * pos_born / pos_evict [C Sp + B] and neg_born / neg_evict [C Sn + B] int32: the interval of old slot (c, k) at index
+ * c S + k and of batch row b at index C S + b (born = evict = 0: never in the cache; evict = B: in it when the call
+ * ends).
+ *
+ * out [B, C] with leading dimension ldout >= C; columns past C are not touched.
+ *
+ * clipfs_tda_plan IS the function the entry point executes: host-only (no GPU is opened, nothing is launched, nothing
+ * written to `plan` on refusal).  CLIPFS_EINVAL before anything is enqueued, the message naming the argument: params,
+ * state, record or plan NULL or of another struct_size; d not a multiple of 4 in [4, 4096]; C outside [1, 4096]; B
+ * outside [1, 8192]; pos_cap or neg_cap outside [0, 8]; an alpha or beta that is negative or not finite; a
+ * logit_scale that is not finite; feats, text, out or a key tensor NULL or not 16-byte aligned; ldout below C; a NULL
+ * member of record or of an enabled cache; out overlapping feats, text or a key tensor. */
+struct clipfs_tda_params {
+  unsigned struct_size; /* sizeof(struct clipfs_tda_params) */
+  int C, d;
+  int pos_cap, neg_cap; /* Sp, Sn */
+  float logit_scale;
+  float pos_alpha, pos_beta, neg_alpha, neg_beta;
+  float ent_lo, ent_hi, mask_lo, mask_hi;
+};
+struct clipfs_tda_state {
+  unsigned struct_size;
+  float* pos_keys;
+  float* pos_ent;
+  int64_t* pos_seq;
+  float* neg_keys;
+  float* neg_ent;
+  int64_t* neg_seq;
+  uint8_t* neg_mask;
+  int64_t* counter;
+};
+struct clipfs_tda_record {
+  unsigned struct_size;
+  int32_t* pred;
+  float* entropy;
+  float* hnorm;
+  int32_t* band;
+  int64_t* seq;
+  uint8_t* mask;
+  int32_t* pos_slot;
+  int32_t* neg_slot;
+  int32_t* pos_born;
+  int32_t* pos_evict;
+  int32_t* neg_born;
+  int32_t* neg_evict;
+};
+#define CLIPFS_TDA_LAUNCH_Z 0      /* grid (32-class tiles, 32-row tiles) */
+#define CLIPFS_TDA_LAUNCH_STATS 1  /* grid (4-row groups): one wave per row */
+#define CLIPFS_TDA_LAUNCH_SCAN 2   /* grid (64-class groups): one thread per class */
+#define CLIPFS_TDA_LAUNCH_LOGITS 3 /* grid (32-row tiles, chunks of class_chunk classes) */
+#define CLIPFS_TDA_LAUNCH_WRITE 4  /* grid (rows) */
+#define CLIPFS_TDA_LAUNCHES 5
+struct clipfs_tda_launch {
+  unsigned grid_x, grid_y, block, lds_bytes; /* grid_x == 0: the launch is absent */
+};
+struct clipfs_tda_plan {
+  int launches;                 /* launches present: the same for every B and C */
+  struct clipfs_tda_launch launch[CLIPFS_TDA_LAUNCHES];
+  unsigned lds_bytes;           /* the largest LDS of a workgroup (at most 160 KB) */
+  int class_chunk;              /* classes per logits workgroup */
+  size_t pos_entries;           /* C Sp + B: elements of pos_born / pos_evict */
+  size_t neg_entries;           /* C Sn + B */
+  size_t pos_key_floats;        /* C Sp d */
+  size_t neg_key_floats;        /* C Sn d */
+  size_t neg_mask_bytes;        /* C Sn C */
+  size_t mask_bytes;            /* B C: record.mask */
+};
+int clipfs_tda_plan(const struct clipfs_tda_params* params, int B, int update, struct clipfs_tda_plan* plan);
+int clipfs_tda_adapt(const struct clipfs_tda_params* params, const float* feats, const float* text,
+                     const struct clipfs_tda_state* state, float* out, int ldout, const struct clipfs_tda_record* record,
+                     int B, int update, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

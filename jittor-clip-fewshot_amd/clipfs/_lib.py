@@ -135,6 +135,43 @@ class ClipPairsPlan(C.Structure):
 CLIP_PAIRS_OPS = ("rows", "combine", "dq", "dk")
 
 
+class TdaParams(C.Structure):
+    """struct clipfs_tda_params: the fixed inputs of the TDA rule."""
+    _fields_ = [("struct_size", C.c_uint), ("C", C.c_int), ("d", C.c_int), ("pos_cap", C.c_int), ("neg_cap", C.c_int),
+                ("logit_scale", C.c_float), ("pos_alpha", C.c_float), ("pos_beta", C.c_float), ("neg_alpha", C.c_float),
+                ("neg_beta", C.c_float), ("ent_lo", C.c_float), ("ent_hi", C.c_float), ("mask_lo", C.c_float), ("mask_hi", C.c_float)]
+
+
+TDA_STATE_FIELDS = ("pos_keys", "pos_ent", "pos_seq", "neg_keys", "neg_ent", "neg_seq", "neg_mask", "counter")
+TDA_RECORD_FIELDS = ("pred", "entropy", "hnorm", "band", "seq", "mask", "pos_slot", "neg_slot", "pos_born", "pos_evict",
+                     "neg_born", "neg_evict")
+
+
+class TdaState(C.Structure):
+    """struct clipfs_tda_state: device pointers of the two caches and the sample counter."""
+    _fields_ = [("struct_size", C.c_uint)] + [(n, C.c_void_p) for n in TDA_STATE_FIELDS]
+
+
+class TdaRecord(C.Structure):
+    """struct clipfs_tda_record: device pointers of the per-sample outputs of clipfs_tda_adapt."""
+    _fields_ = [("struct_size", C.c_uint)] + [(n, C.c_void_p) for n in TDA_RECORD_FIELDS]
+
+
+class TdaLaunch(C.Structure):
+    _fields_ = [("grid_x", C.c_uint), ("grid_y", C.c_uint), ("block", C.c_uint), ("lds_bytes", C.c_uint)]
+
+
+# CLIPFS_TDA_LAUNCH_* of include/clipfs.h, by value
+TDA_LAUNCHES = ("z", "stats", "scan", "logits", "write")
+
+
+class TdaPlan(C.Structure):
+    """struct clipfs_tda_plan: what clipfs_tda_adapt launches, and the sizes of its state and record."""
+    _fields_ = [("launches", C.c_int), ("launch", TdaLaunch * 5), ("lds_bytes", C.c_uint), ("class_chunk", C.c_int),
+                ("pos_entries", C.c_size_t), ("neg_entries", C.c_size_t), ("pos_key_floats", C.c_size_t),
+                ("neg_key_floats", C.c_size_t), ("neg_mask_bytes", C.c_size_t), ("mask_bytes", C.c_size_t)]
+
+
 class MergeJob(C.Structure):
     """struct clipfs_lora_merge_job: one projection of a clipfs_lora_merge table."""
     _fields_ = [("w", C.c_void_p), ("a", C.c_void_p), ("b", C.c_void_p), ("out", C.c_void_p), ("planes", C.c_void_p),
@@ -320,6 +357,8 @@ SIGNATURES = {
     "clipfs_sigmoid_objective": (_i, [_p, _p, _p, _p, _p, _f, _p, _p, _p, _p, _p, _i, _p, _i, _p, _i, _i, _i, _i, _p]),
     "clipfs_clip_pairs_plan": (_i, [_i, _i, _i, _i, _i, C.POINTER(ClipPairsPlan)]),
     "clipfs_clip_pairs_objective": (_i, [_p, _p, _p, _p, _p, _f, _f, _p, _p, _p, _p, _p, _p, _i, _p, _i, _p, _i, _i, _i, _i, _p]),
+    "clipfs_tda_plan": (_i, [C.POINTER(TdaParams), _i, _i, C.POINTER(TdaPlan)]),
+    "clipfs_tda_adapt": (_i, [C.POINTER(TdaParams), _p, _p, C.POINTER(TdaState), _p, _i, C.POINTER(TdaRecord), _i, _i, _p]),
 }
 
 # word indices of the loss-scaling record (CLIPFS_SCALER_* of include/clipfs.h)
@@ -421,6 +460,25 @@ def clip_pairs_plan(op: str, R: int, N: int, d: int, both: bool = True):
     plan = ClipPairsPlan()
     check(load().clipfs_clip_pairs_plan(CLIP_PAIRS_OPS.index(op), R, N, d, int(both), C.byref(plan)), "clip_pairs_plan")
     return dict(grid=(plan.grid_x, plan.grid_y, plan.grid_z), **{k: getattr(plan, k) for k, _ in ClipPairsPlan._fields_[3:]})
+
+
+def new_tda_params(**fields) -> TdaParams:
+    p = TdaParams()
+    p.struct_size = C.sizeof(TdaParams)
+    for k, v in fields.items():
+        setattr(p, k, v)
+    return p
+
+
+def tda_plan(params: TdaParams, B: int, update: bool = True):
+    """The plan clipfs_tda_adapt executes (host-only), as a dict: launches (a count that does not depend on B or C), launch
+    = {name: (grid_x, grid_y, block, lds_bytes)} of the launches present, lds_bytes, class_chunk and the state / record
+    sizes of struct clipfs_tda_plan.  A refusal raises ClipfsError with its message."""
+    plan = TdaPlan()
+    check(load().clipfs_tda_plan(C.byref(params), B, int(update), C.byref(plan)), "tda_plan")
+    d = {k: getattr(plan, k) for k, _ in TdaPlan._fields_ if k != "launch"}
+    d["launch"] = {TDA_LAUNCHES[i]: (l.grid_x, l.grid_y, l.block, l.lds_bytes) for i, l in enumerate(plan.launch) if l.grid_x}
+    return d
 
 
 def new_tower() -> Tower:

@@ -820,6 +820,90 @@ def tpt_objective(feats, text, K, logit_scale=100.0, selected=None, want_grad=Tr
     return loss, selected, dtext, entropy
 
 
+# ------------------------------------------------------------------------------------------------ TDA
+TDA_DEFAULTS = dict(logit_scale=100.0, pos_cap=3, neg_cap=2, pos_alpha=2.0, pos_beta=5.0, neg_alpha=0.117, neg_beta=1.0,
+                    ent_lo=0.2, ent_hi=0.5, mask_lo=0.03, mask_hi=1.0)
+TDA_MAX_BATCH = 8192  # of clipfs_tda_adapt
+
+
+def tda_params(C_: int, d: int, **hyper):
+    """struct clipfs_tda_params for C classes of d features; ``hyper`` overrides TDA_DEFAULTS (unknown names: KeyError)."""
+    unknown = sorted(set(hyper) - set(TDA_DEFAULTS))
+    if unknown:
+        raise KeyError(f"tda_params: unknown hyper-parameter(s) {', '.join(unknown)}")
+    return _lib.new_tda_params(C=C_, d=d, **{**TDA_DEFAULTS, **hyper})
+
+
+def tda_plan(C_: int, d: int, B: int, update: bool = True, **hyper):
+    """What ``tda_adapt`` launches for B samples (host-only): launches (the same for every B and C), launch = {name: (grid_x,
+    grid_y, block, lds_bytes)}, lds_bytes, class_chunk, and the element counts of the state and record tensors."""
+    return _lib.tda_plan(tda_params(C_, d, **hyper), B, update)
+
+
+def tda_new_state(C_: int, d: int, pos_cap: int, neg_cap: int, device):
+    """An empty TDA state: the fixed-shape device tensors of struct clipfs_tda_state, by name."""
+    f32, i64 = torch.float32, torch.int64
+    return dict(pos_keys=torch.zeros(C_, pos_cap, d, device=device, dtype=f32),
+                pos_ent=torch.full((C_, pos_cap), float("inf"), device=device, dtype=f32),
+                pos_seq=torch.full((C_, pos_cap), -1, device=device, dtype=i64),
+                neg_keys=torch.zeros(C_, neg_cap, d, device=device, dtype=f32),
+                neg_ent=torch.full((C_, neg_cap), float("inf"), device=device, dtype=f32),
+                neg_seq=torch.full((C_, neg_cap), -1, device=device, dtype=i64),
+                neg_mask=torch.zeros(C_, neg_cap, C_, device=device, dtype=torch.uint8),
+                counter=torch.zeros(1, device=device, dtype=i64))
+
+
+_TDA_STATE_DTYPES = dict(pos_keys=torch.float32, pos_ent=torch.float32, pos_seq=torch.int64, neg_keys=torch.float32,
+                         neg_ent=torch.float32, neg_seq=torch.int64, neg_mask=torch.uint8, counter=torch.int64)
+
+
+def tda_new_record(C_: int, B: int, pos_cap: int, neg_cap: int, device):
+    """The per-sample record of one ``tda_adapt`` call (struct clipfs_tda_record): every element is written by the call."""
+    i32 = torch.int32
+    e = lambda n, dt: torch.empty(n, device=device, dtype=dt)
+    return dict(pred=e(B, i32), entropy=e(B, torch.float32), hnorm=e(B, torch.float32), band=e(B, i32),
+                seq=e(B, torch.int64), mask=torch.empty(B, C_, device=device, dtype=torch.uint8), pos_slot=e(B, i32),
+                neg_slot=e(B, i32), pos_born=e(C_ * pos_cap + B, i32), pos_evict=e(C_ * pos_cap + B, i32),
+                neg_born=e(C_ * neg_cap + B, i32), neg_evict=e(C_ * neg_cap + B, i32))
+
+
+def tda_adapt(feats, text, state, update=True, out=None, record=None, **hyper):
+    """The training-free dynamic adapter (TDA) for ``feats`` [B, d] (unit rows, B <= 8192) against unit class features
+    ``text`` [C, d] and the cache ``state`` (``tda_new_state``): B applications of the sequential rule of include/clipfs.h
+    in row order, in at most five launches and without a host synchronisation.  ``update=False`` scores against the
+    state as it stands and changes nothing; otherwise ``state`` is updated in place.  Returns (logits [B, C], record): the
+    record (``tda_new_record``) holds pred, entropy, hnorm, band, seq, mask, pos_slot / neg_slot (-1: not inserted) and the
+    born / evict intervals.  ``out`` may be a column slice (row stride >= C, unit column stride); ``hyper`` overrides
+    TDA_DEFAULTS except the capacities, which are read off ``state``."""
+    assert feats.dim() == 2 and text.dim() == 2 and feats.shape[1] == text.shape[1], (tuple(feats.shape), tuple(text.shape))
+    B, d = feats.shape
+    Cn = text.shape[0]
+    Sp, Sn = state["pos_keys"].shape[1], state["neg_keys"].shape[1]
+    shapes = dict(pos_keys=(Cn, Sp, d), pos_ent=(Cn, Sp), pos_seq=(Cn, Sp), neg_keys=(Cn, Sn, d), neg_ent=(Cn, Sn),
+                  neg_seq=(Cn, Sn), neg_mask=(Cn, Sn, Cn), counter=(1,))
+    for name, shape in shapes.items():
+        t = state[name]
+        assert t.is_cuda and t.is_contiguous() and t.dtype == _TDA_STATE_DTYPES[name] and tuple(t.shape) == shape, \
+            f"tda_adapt: state[{name!r}] must be a contiguous {_TDA_STATE_DTYPES[name]} device tensor of shape {shape}"
+    params = tda_params(Cn, d, pos_cap=Sp, neg_cap=Sn, **hyper)
+    if out is None:
+        out = torch.empty(B, Cn, device=feats.device, dtype=torch.float32)
+    assert out.dtype == torch.float32 and tuple(out.shape) == (B, Cn) and out.stride(1) == 1, "out"
+    if record is None:
+        record = tda_new_record(Cn, B, Sp, Sn, feats.device)
+    st, rec = _lib.TdaState(), _lib.TdaRecord()
+    st.struct_size, rec.struct_size = C.sizeof(_lib.TdaState), C.sizeof(_lib.TdaRecord)
+    for name in _lib.TDA_STATE_FIELDS:
+        setattr(st, name, _p(state[name]) if state[name].numel() else None)
+    for name in _lib.TDA_RECORD_FIELDS:
+        assert record[name].is_contiguous()
+        setattr(rec, name, _p(record[name]))
+    check(_lib.load().clipfs_tda_adapt(C.byref(params), _p(_f32(feats)), _p(_f32(text)), C.byref(st), _p(out),
+                                       out.stride(0) if B > 1 else max(out.stride(0), Cn), C.byref(rec), B, int(bool(update)),
+                                       _stream()), "tda_adapt")
+    return out, record
+
+
 # ------------------------------------------------------------------------------------------------ contrastive objective
 def contrastive_plan(op: str, R: int, N: int, d: int):
     """What ``contrastive_objective`` launches for these shapes ("stats", "combine", "dq", "dk"; host-only): grid, block,
