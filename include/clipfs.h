@@ -1339,6 +1339,159 @@ int clipfs_tda_adapt(const struct clipfs_tda_params* params, const float* feats,
                      const struct clipfs_tda_state* state, float* out, int ldout, const struct clipfs_tda_record* record,
                      int B, int update, void* stream);
 
+/* --------------------------------------------------------------- TRANSDUCT --
+ * Transductive zero-/few-shot inference (TransCLIP: Zanella, Gerin and Ben Ayed, "Boosting Vision-Language Models with
+ * Transduction", NeurIPS 2024): the whole unlabelled test set is classified at once, and its own neighbourhood and
+ * cluster structure corrects the zero-shot (or few-shot) predictions.  No labels, no backward, no tower pass; fp32 in
+ * every engine precision mode.  Where the published code differs from the rule below, the rule holds.
+ *
+ * THE RULE.  Inputs: test features F [N, d] (unit rows are assumed, not checked), class features T [C, d], optional
+ * labelled shots S [M, d] with labels y [M] (M_c shots of class c; M = 0 is the zero-shot form).  Scalars: logit scale
+ * s, neighbours k, init_top m, lam, shot_weight gamma, outer, inner, n_min, var_floor.
+ *   1. logy = log_softmax_rows(s F T^T).  The zero-shot label of row i is argmax_c logy_ic, ties to the lower class.
+ *   2. nbr_i = the k indices j != i of largest a_ij = f_i . f_j, ties to the lower j (the exclusion is by index: a
+ *      duplicate of a feature is a legitimate neighbour), stored in descending a, ties in ascending j, with
+ *      w_ir = a_{i, nbr_ir}.  Not symmetrised, not clamped.
+ *   3. z = exp(logy); var_d = 1 / d; I_c = the m rows of largest logy_ic (the log-probability, not the probability,
+ *      which saturates and ties at s = 100), ties to the lower row, in that order;
+ *      mu_c = (sum_{i in I_c} f_i + gamma sum_{y_j = c} s_j) / (m + gamma M_c).
+ *   4. `outer` times:
+ *      4.1 mu'_c = mu_c / var, b_c = -1/2 sum_d mu_cd mu'_cd, u_ic = lam logy_ic + f_i . mu'_c + b_c.  (Under one
+ *          shared diagonal covariance the Gaussian log-likelihood -1/2 sum_d (f_d - mu_cd)^2 / var_d is affine in f up
+ *          to a term that does not depend on c, and the softmax removes that term.)
+ *      4.2 `inner` times, Jacobi (every row reads the previous sweep's z):
+ *          z_i <- softmax_c(u_ic + sum_r w_ir z_{nbr_ir, c}).
+ *      4.3 n_c = sum_i z_ic + gamma M_c; G_c = sum_i z_ic f_i + gamma sum_{y_j = c} s_j; mu_c <- G_c / n_c if
+ *          n_c > n_min, else mu_c stays.
+ *      4.4 var_d <- max(var_floor, (Q_d - 2 sum_c mu_cd G_cd + sum_c n_c mu_cd^2) / (N + gamma M)) with
+ *          Q_d = sum_i f_id^2 + gamma sum_j s_jd^2 computed once.
+ *   5. Outputs: z, labels_i = argmax_c z_ic (ties low), the zero-shot labels, mu, var, nbr, w.
+ *
+ * HOW.  Launches of a fit, whatever N, C, d and M: 6 + (knn_chunks > 1) + outer (inner + 4):
+ *   logits  s F T^T in 32 x 32 tiles on the fp32 matrix cores into logy
+ *   logsm   one wave per row: logy in place, the zero-shot label, z0 = exp(logy)
+ *   knn     one workgroup per (32 query rows, column chunk) walks the chunk's key tiles; the N x N similarities never
+ *           reach memory; an element's dot is summed in one order wherever it falls, and a row's list is the top k of
+ *           a total order (value descending, index ascending), so the result is bitwise independent of the chunking
+ *   merge   only with more than one chunk: one thread per row combines the chunks' lists
+ *   shots   gamma M_c and gamma sum_{y_j = c} s_j (shots in ascending j); runs (and writes zeros) when M = 0
+ *   q       Q_d, in double
+ *   init    per class the top m rows of logy (8 row groups, combined in group order), mu, var = 1 / d, mu' = mu / var
+ *   per outer iteration:
+ *   bias    b_c, one wave per class
+ *   u       u = lam logy + F mu'^T + b in the tile kernel of `logits`: lam logy is added HERE, once per outer
+ *           iteration, not inside the sweeps; an element is (lam logy + dot) + b
+ *   z_step  `inner` launches, one wave per row, the row's t in registers; the sweep reads one z buffer and writes the
+ *           other; the last sweep of the fit writes `labels`
+ *   stats   G = z^T F on the matrix cores, the rows cut into stat_splits ranges whose partial sums go to stat_work
+ *   muvar   combines the partials in range order, then adds the shots' constants; mu, var (its terms summed in double
+ *           over 8 class groups combined in group order), mu' for the next iteration
+ * bias and muvar are two small launches where one would need a grid-wide barrier (var needs every class, b every
+ * feature).  No float atomics; every output element is written by one thread; every sum runs in an order fixed by the
+ * shapes; nothing returns to the host; all launches go to `stream`.
+ *
+ * buffers (all device memory except shot_labels_host; the stages check only the members they use):
+ *   inputs   feats [N, d], text [C, d], shots [M, d], shot_labels [M] int32 (both may be NULL when M = 0),
+ *            shot_labels_host: an optional HOST copy of the labels, checked for range before anything is enqueued (a
+ *            device label outside [0, C) matches no class and cannot send a kernel anywhere)
+ *   outputs  z [N, C], labels [N] int32, zs_labels [N] int32, mu [C, d], var [d], nbr [N, k] int32, w [N, k]
+ *   state    logy [N, C], u [N, C], z2 [N, C] (the other z buffer), mup [C, d] = mu', bias [C], n [C], G [C, d], Q [d],
+ *            shot_n [C], shot_G [C, d], sel [C, m] int32 = I_c
+ *   work     stat_work [plan.stat_work_floats], knn_work [plan.knn_work_bytes] (NULL with one chunk)
+ * Every element of every state and work buffer is written before it is read.  The O(N C) state is the method's; the
+ * workspace of the affinity is knn_work alone: knn_chunks N k 8 bytes.
+ *
+ * Stages (each runs alone, on the members named): logy (feats, text -> logy, zs_labels, z); knn (feats -> nbr, w);
+ * init (feats, logy, shots -> shot_n, shot_G, Q, sel, mu, mup, var); u (feats, logy, mu, mup -> bias, u);
+ * z_step (u, nbr, w, z_in -> z_out and, if not NULL, labels); stats (feats, z_in, shot_n, shot_G, Q, mu -> n, G, mu,
+ * var, mup).  clipfs_transduct_fit IS these calls in the order of the rule, bit for bit.
+ *
+ * clipfs_transduct_plan is host-only (no GPU is opened, nothing written to `plan` on refusal).  CLIPFS_EINVAL before
+ * anything is enqueued, the message naming the argument: params, buffers or plan NULL or of another struct_size; d not a
+ * multiple of 4 in [4, 4096]; C outside [1, 4096]; k outside [1, 8]; init_top outside [1, 16]; N outside
+ * [max(k + 1, init_top), 131072]; M outside [0, 65536]; outer or inner below 1; knn_chunks outside [0, 64] (0: the
+ * plan decides); logit_scale, lam, shot_weight, n_min or var_floor negative or not finite (var_floor: not positive); a
+ * used member NULL or misaligned (16 bytes for the matrices, 4 for the vectors); a written member overlapping another
+ * member; a label of shot_labels_host outside [0, C); z_out overlapping z_in, u, nbr or w. */
+struct clipfs_transduct_params {
+  unsigned struct_size; /* sizeof(struct clipfs_transduct_params) */
+  int N, C, d, M;
+  int k, init_top, outer, inner;
+  int knn_chunks; /* 0: the plan decides; else forced */
+  float logit_scale, lam, shot_weight, n_min, var_floor;
+};
+struct clipfs_transduct_buffers {
+  unsigned struct_size;
+  const float* feats;
+  const float* text;
+  const float* shots;
+  const int32_t* shot_labels;
+  const int32_t* shot_labels_host;
+  float* z;
+  int32_t* labels;
+  int32_t* zs_labels;
+  float* mu;
+  float* var;
+  int32_t* nbr;
+  float* w;
+  float* logy;
+  float* u;
+  float* z2;
+  float* mup;
+  float* bias;
+  float* n;
+  float* G;
+  float* Q;
+  float* shot_n;
+  float* shot_G;
+  int32_t* sel;
+  float* stat_work;
+  void* knn_work;
+};
+#define CLIPFS_TRANSDUCT_LAUNCH_LOGITS 0    /* grid (32-class tiles, 32-row tiles) */
+#define CLIPFS_TRANSDUCT_LAUNCH_LOGSM 1     /* grid (4-row groups): one wave per row */
+#define CLIPFS_TRANSDUCT_LAUNCH_KNN 2       /* grid (32-row tiles, column chunks) */
+#define CLIPFS_TRANSDUCT_LAUNCH_KNN_MERGE 3 /* grid (256-row groups); absent with one chunk */
+#define CLIPFS_TRANSDUCT_LAUNCH_SHOTS 4     /* grid (classes) */
+#define CLIPFS_TRANSDUCT_LAUNCH_Q 5         /* grid (64-feature groups) */
+#define CLIPFS_TRANSDUCT_LAUNCH_INIT 6      /* grid (32-class tiles) */
+#define CLIPFS_TRANSDUCT_LAUNCH_BIAS 7      /* grid (4-class groups): one wave per class */
+#define CLIPFS_TRANSDUCT_LAUNCH_U 8         /* grid (32-class tiles, 32-row tiles) */
+#define CLIPFS_TRANSDUCT_LAUNCH_Z_STEP 9    /* grid (4-row groups): one wave per row */
+#define CLIPFS_TRANSDUCT_LAUNCH_STATS 10    /* grid (32-class tiles, 128-feature chunks, row ranges) */
+#define CLIPFS_TRANSDUCT_LAUNCH_MUVAR 11    /* grid (32-feature groups) */
+#define CLIPFS_TRANSDUCT_LAUNCHES 12
+struct clipfs_transduct_launch {
+  unsigned grid_x, grid_y, grid_z, block, lds_bytes; /* grid_x == 0: the launch is absent */
+};
+struct clipfs_transduct_plan {
+  int launches;    /* of a fit: 6 + (knn_chunks > 1) + outer (inner + 4) */
+  int knn_chunks;  /* column chunks of the kNN walk */
+  int class_chunk; /* classes a z_step wave holds in registers: 256, 1024 or 4096 */
+  int stat_splits; /* row ranges of the stats launch */
+  int stat_rows;   /* rows per range (a multiple of 16) */
+  struct clipfs_transduct_launch launch[CLIPFS_TRANSDUCT_LAUNCHES];
+  unsigned lds_bytes;      /* the largest LDS of a workgroup (at most 160 KB) */
+  size_t knn_work_bytes;   /* knn_chunks N k 8, 0 with one chunk */
+  size_t stat_work_floats; /* stat_splits C (d + 1) */
+  size_t nc_floats;        /* N C: elements of z, z2, logy and u each */
+};
+int clipfs_transduct_plan(const struct clipfs_transduct_params* params, struct clipfs_transduct_plan* plan);
+int clipfs_transduct_logy(const struct clipfs_transduct_params* params, const struct clipfs_transduct_buffers* buffers,
+                          void* stream);
+int clipfs_transduct_knn(const struct clipfs_transduct_params* params, const struct clipfs_transduct_buffers* buffers,
+                         void* stream);
+int clipfs_transduct_init(const struct clipfs_transduct_params* params, const struct clipfs_transduct_buffers* buffers,
+                          void* stream);
+int clipfs_transduct_u(const struct clipfs_transduct_params* params, const struct clipfs_transduct_buffers* buffers,
+                       void* stream);
+int clipfs_transduct_z_step(const struct clipfs_transduct_params* params, const struct clipfs_transduct_buffers* buffers,
+                            const float* z_in, float* z_out, int32_t* labels, void* stream);
+int clipfs_transduct_stats(const struct clipfs_transduct_params* params, const struct clipfs_transduct_buffers* buffers,
+                           const float* z_in, void* stream);
+int clipfs_transduct_fit(const struct clipfs_transduct_params* params, const struct clipfs_transduct_buffers* buffers,
+                         void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -172,6 +172,40 @@ class TdaPlan(C.Structure):
                 ("neg_key_floats", C.c_size_t), ("neg_mask_bytes", C.c_size_t), ("mask_bytes", C.c_size_t)]
 
 
+class TransductParams(C.Structure):
+    """struct clipfs_transduct_params: the shapes and hyper-parameters of a transductive fit."""
+    _fields_ = [("struct_size", C.c_uint), ("N", C.c_int), ("C", C.c_int), ("d", C.c_int), ("M", C.c_int), ("k", C.c_int),
+                ("init_top", C.c_int), ("outer", C.c_int), ("inner", C.c_int), ("knn_chunks", C.c_int),
+                ("logit_scale", C.c_float), ("lam", C.c_float), ("shot_weight", C.c_float), ("n_min", C.c_float),
+                ("var_floor", C.c_float)]
+
+
+# members of struct clipfs_transduct_buffers, in order (shot_labels_host is host memory, the rest device memory)
+TRANSDUCT_BUFFER_FIELDS = ("feats", "text", "shots", "shot_labels", "shot_labels_host", "z", "labels", "zs_labels", "mu", "var",
+                           "nbr", "w", "logy", "u", "z2", "mup", "bias", "n", "G", "Q", "shot_n", "shot_G", "sel", "stat_work",
+                           "knn_work")
+
+
+class TransductBuffers(C.Structure):
+    """struct clipfs_transduct_buffers: inputs, outputs, state and work of the transductive stages."""
+    _fields_ = [("struct_size", C.c_uint)] + [(n, C.c_void_p) for n in TRANSDUCT_BUFFER_FIELDS]
+
+
+class TransductLaunch(C.Structure):
+    _fields_ = [("grid_x", C.c_uint), ("grid_y", C.c_uint), ("grid_z", C.c_uint), ("block", C.c_uint), ("lds_bytes", C.c_uint)]
+
+
+# CLIPFS_TRANSDUCT_LAUNCH_* of include/clipfs.h, by value
+TRANSDUCT_LAUNCHES = ("logits", "logsm", "knn", "knn_merge", "shots", "q", "init", "bias", "u", "z_step", "stats", "muvar")
+
+
+class TransductPlan(C.Structure):
+    """struct clipfs_transduct_plan: what a transductive fit launches, and the sizes of its work buffers."""
+    _fields_ = [("launches", C.c_int), ("knn_chunks", C.c_int), ("class_chunk", C.c_int), ("stat_splits", C.c_int),
+                ("stat_rows", C.c_int), ("launch", TransductLaunch * 12), ("lds_bytes", C.c_uint),
+                ("knn_work_bytes", C.c_size_t), ("stat_work_floats", C.c_size_t), ("nc_floats", C.c_size_t)]
+
+
 class MergeJob(C.Structure):
     """struct clipfs_lora_merge_job: one projection of a clipfs_lora_merge table."""
     _fields_ = [("w", C.c_void_p), ("a", C.c_void_p), ("b", C.c_void_p), ("out", C.c_void_p), ("planes", C.c_void_p),
@@ -359,6 +393,14 @@ SIGNATURES = {
     "clipfs_clip_pairs_objective": (_i, [_p, _p, _p, _p, _p, _f, _f, _p, _p, _p, _p, _p, _p, _i, _p, _i, _p, _i, _i, _i, _i, _p]),
     "clipfs_tda_plan": (_i, [C.POINTER(TdaParams), _i, _i, C.POINTER(TdaPlan)]),
     "clipfs_tda_adapt": (_i, [C.POINTER(TdaParams), _p, _p, C.POINTER(TdaState), _p, _i, C.POINTER(TdaRecord), _i, _i, _p]),
+    "clipfs_transduct_plan": (_i, [C.POINTER(TransductParams), C.POINTER(TransductPlan)]),
+    "clipfs_transduct_logy": (_i, [C.POINTER(TransductParams), C.POINTER(TransductBuffers), _p]),
+    "clipfs_transduct_knn": (_i, [C.POINTER(TransductParams), C.POINTER(TransductBuffers), _p]),
+    "clipfs_transduct_init": (_i, [C.POINTER(TransductParams), C.POINTER(TransductBuffers), _p]),
+    "clipfs_transduct_u": (_i, [C.POINTER(TransductParams), C.POINTER(TransductBuffers), _p]),
+    "clipfs_transduct_z_step": (_i, [C.POINTER(TransductParams), C.POINTER(TransductBuffers), _p, _p, _p, _p]),
+    "clipfs_transduct_stats": (_i, [C.POINTER(TransductParams), C.POINTER(TransductBuffers), _p, _p]),
+    "clipfs_transduct_fit": (_i, [C.POINTER(TransductParams), C.POINTER(TransductBuffers), _p]),
 }
 
 # word indices of the loss-scaling record (CLIPFS_SCALER_* of include/clipfs.h)
@@ -478,6 +520,34 @@ def tda_plan(params: TdaParams, B: int, update: bool = True):
     check(load().clipfs_tda_plan(C.byref(params), B, int(update), C.byref(plan)), "tda_plan")
     d = {k: getattr(plan, k) for k, _ in TdaPlan._fields_ if k != "launch"}
     d["launch"] = {TDA_LAUNCHES[i]: (l.grid_x, l.grid_y, l.block, l.lds_bytes) for i, l in enumerate(plan.launch) if l.grid_x}
+    return d
+
+
+def new_transduct_params(**fields) -> TransductParams:
+    p = TransductParams()
+    p.struct_size = C.sizeof(TransductParams)
+    for k, v in fields.items():
+        setattr(p, k, v)
+    return p
+
+
+def new_transduct_buffers(**members) -> TransductBuffers:
+    """struct clipfs_transduct_buffers with the named members set (addresses as integers); the rest stay NULL."""
+    b = TransductBuffers()
+    b.struct_size = C.sizeof(TransductBuffers)
+    for k, v in members.items():
+        setattr(b, k, v)
+    return b
+
+
+def transduct_plan(params: TransductParams):
+    """The plan the transductive entry points execute (host-only), as a dict of the fields of struct clipfs_transduct_plan with
+    launch = {name: (grid_x, grid_y, grid_z, block, lds_bytes)} of the launches present.  A refusal raises ClipfsError."""
+    plan = TransductPlan()
+    check(load().clipfs_transduct_plan(C.byref(params), C.byref(plan)), "transduct_plan")
+    d = {k: getattr(plan, k) for k, _ in TransductPlan._fields_ if k != "launch"}
+    d["launch"] = {TRANSDUCT_LAUNCHES[i]: (l.grid_x, l.grid_y, l.grid_z, l.block, l.lds_bytes)
+                   for i, l in enumerate(plan.launch) if l.grid_x}
     return d
 
 

@@ -904,6 +904,190 @@ def tda_adapt(feats, text, state, update=True, out=None, record=None, **hyper):
     return out, record
 
 
+# ------------------------------------------------------------------------------------------------ transductive inference
+TRANSDUCT_DEFAULTS = dict(logit_scale=100.0, k=3, init_top=8, lam=1.0, shot_weight=1.0, outer=10, inner=5, n_min=1e-6,
+                          var_floor=1e-6)
+# outputs, state and work of a fit (struct clipfs_transduct_buffers without its inputs): name -> dtype
+_TRANSDUCT_OUT = ("z", "labels", "zs_labels", "mu", "var", "nbr", "w")
+_TRANSDUCT_INT = ("labels", "zs_labels", "nbr", "sel", "shot_labels")
+
+
+def transduct_params(N: int, C_: int, d: int, M: int = 0, knn_chunks: int = 0, **hyper):
+    """struct clipfs_transduct_params; ``hyper`` overrides TRANSDUCT_DEFAULTS (unknown names: KeyError).  ``knn_chunks`` 0
+    lets the plan choose the column chunks of the kNN walk; the result does not depend on them bit for bit."""
+    unknown = sorted(set(hyper) - set(TRANSDUCT_DEFAULTS))
+    if unknown:
+        raise KeyError(f"transduct_params: unknown hyper-parameter(s) {', '.join(unknown)}")
+    h = {**TRANSDUCT_DEFAULTS, **hyper}
+    for name in ("k", "init_top", "outer", "inner"):
+        h[name] = int(h[name])
+    return _lib.new_transduct_params(N=N, C=C_, d=d, M=M, knn_chunks=knn_chunks, **h)
+
+
+def transduct_plan(N: int, C_: int, d: int, M: int = 0, knn_chunks: int = 0, **hyper):
+    """What a fit launches (host-only): launches = 6 + (knn_chunks > 1) + outer (inner + 4) whatever N, C, d and M, launch =
+    {name: (grid_x, grid_y, grid_z, block, lds_bytes)}, lds_bytes, knn_chunks, class_chunk, stat_splits, stat_rows and
+    the work sizes knn_work_bytes, stat_work_floats, nc_floats."""
+    return _lib.transduct_plan(transduct_params(N, C_, d, M, knn_chunks, **hyper))
+
+
+def transduct_shapes(N: int, C_: int, d: int, M: int = 0, knn_chunks: int = 0, **hyper):
+    """{member: (shape, dtype)} of the outputs, state and work of struct clipfs_transduct_buffers for these shapes."""
+    plan = transduct_plan(N, C_, d, M, knn_chunks, **hyper)
+    h = {**TRANSDUCT_DEFAULTS, **hyper}
+    k, m = int(h["k"]), int(h["init_top"])
+    f32, i32 = torch.float32, torch.int32
+    return dict(z=((N, C_), f32), labels=((N,), i32), zs_labels=((N,), i32), mu=((C_, d), f32), var=((d,), f32),
+                nbr=((N, k), i32), w=((N, k), f32), logy=((N, C_), f32), u=((N, C_), f32), z2=((N, C_), f32),
+                mup=((C_, d), f32), bias=((C_,), f32), n=((C_,), f32), G=((C_, d), f32), Q=((d,), f32), shot_n=((C_,), f32),
+                shot_G=((C_, d), f32), sel=((C_, m), i32), stat_work=((plan["stat_work_floats"],), f32),
+                knn_work=((plan["knn_work_bytes"] // 4,), f32))
+
+
+def transduct_buffers(N: int, C_: int, d: int, device, M: int = 0, knn_chunks: int = 0, **hyper):
+    """Uninitialised device tensors for every output, state and work member of a fit: every element is written by the fit
+    before it is read."""
+    return {name: torch.empty(shape, device=device, dtype=dt)
+            for name, (shape, dt) in transduct_shapes(N, C_, d, M, knn_chunks, **hyper).items()}
+
+
+def _transduct_members(**tensors):
+    """struct clipfs_transduct_buffers from the named tensors (None and empty tensors stay NULL)."""
+    mem = {}
+    for name, t in tensors.items():
+        if t is None or t.numel() == 0:
+            continue
+        want = torch.int32 if name in _TRANSDUCT_INT else torch.float32
+        assert t.is_cuda and t.is_contiguous() and t.dtype == want, f"transduct: {name} must be a contiguous {want} device tensor"
+        mem[name] = t.data_ptr()
+    return _lib.new_transduct_buffers(**mem)
+
+
+def _transduct_shots(shots, shot_labels, d, device):
+    """(shots [M, d] or None, device labels or None, host labels or None, M).  Labels given on the host are checked for
+    range by the entry point before anything is enqueued; device labels are passed as they are (no host round trip)."""
+    if shots is None or shots.shape[0] == 0:
+        return None, None, None, 0
+    assert shots.dim() == 2 and shots.shape[1] == d and shot_labels is not None and shot_labels.numel() == shots.shape[0], \
+        "transduct: shots [M, d] need shot_labels [M]"
+    host = None
+    if not shot_labels.is_cuda:
+        host = shot_labels.to(torch.int32).contiguous()
+        dev_labels = host.to(device)
+    else:
+        dev_labels = shot_labels.to(torch.int32).contiguous()
+    return _f32(shots), dev_labels, host, int(shots.shape[0])
+
+
+def transduct_logy(feats, text, logit_scale=TRANSDUCT_DEFAULTS["logit_scale"]):
+    """Step 1 of the rule: (logy [N, C] = log_softmax(s F T^T), zero-shot labels [N] int32, z0 = exp(logy))."""
+    (N, d), Cn = feats.shape, text.shape[0]
+    params = transduct_params(N, Cn, d, k=1, init_top=1, logit_scale=logit_scale)
+    logy, z = torch.empty(N, Cn, device=feats.device), torch.empty(N, Cn, device=feats.device)
+    zs = torch.empty(N, device=feats.device, dtype=torch.int32)
+    b = _transduct_members(feats=_f32(feats), text=_f32(text), logy=logy, z=z, zs_labels=zs)
+    check(_lib.load().clipfs_transduct_logy(C.byref(params), C.byref(b), _stream()), "transduct_logy")
+    return logy, zs, z
+
+
+def transduct_knn(feats, k=TRANSDUCT_DEFAULTS["k"], knn_chunks=0, work=None):
+    """Step 2: (nbr [N, k] int32, w [N, k]) -- per row the k most similar OTHER rows, descending, ties to the lower index.
+    The N x N similarities never reach memory; ``knn_chunks`` forces the column chunks (the result is bitwise the same);
+    ``work``: plan["knn_work_bytes"] // 4 floats, used only with more than one chunk."""
+    N, d = feats.shape
+    params = transduct_params(N, 1, d, k=k, init_top=1, knn_chunks=knn_chunks)
+    plan = _lib.transduct_plan(params)
+    if work is None:
+        work = torch.empty(plan["knn_work_bytes"] // 4, device=feats.device, dtype=torch.float32)
+    assert work.numel() * 4 >= plan["knn_work_bytes"], "transduct_knn: work is too small"
+    nbr = torch.empty(N, k, device=feats.device, dtype=torch.int32)
+    w = torch.empty(N, k, device=feats.device, dtype=torch.float32)
+    b = _transduct_members(feats=_f32(feats), nbr=nbr, w=w, knn_work=work)
+    check(_lib.load().clipfs_transduct_knn(C.byref(params), C.byref(b), _stream()), "transduct_knn")
+    return nbr, w
+
+
+def transduct_init(feats, logy, shots=None, shot_labels=None, init_top=TRANSDUCT_DEFAULTS["init_top"],
+                   shot_weight=TRANSDUCT_DEFAULTS["shot_weight"]):
+    """Step 3 and the shots' constants: dict(sel [C, m] int32 = the m rows of largest logy per class in rank order, mu, mup =
+    mu / var, var = 1 / d, shot_n = gamma M_c, shot_G = gamma sum of a class's shots, Q)."""
+    (N, d), Cn = feats.shape, logy.shape[1]
+    S, y, yh, M = _transduct_shots(shots, shot_labels, d, feats.device)
+    params = transduct_params(N, Cn, d, M, k=1, init_top=init_top, shot_weight=shot_weight)
+    e = lambda *s: torch.empty(*s, device=feats.device, dtype=torch.float32)
+    out = dict(sel=torch.empty(Cn, init_top, device=feats.device, dtype=torch.int32), mu=e(Cn, d), mup=e(Cn, d), var=e(d),
+               shot_n=e(Cn), shot_G=e(Cn, d), Q=e(d))
+    b = _transduct_members(feats=_f32(feats), logy=_f32(logy), shots=S, shot_labels=y, **out)
+    if yh is not None:
+        b.shot_labels_host = yh.data_ptr()
+    check(_lib.load().clipfs_transduct_init(C.byref(params), C.byref(b), _stream()), "transduct_init")
+    return out
+
+
+def transduct_u(feats, logy, mu, mup, lam=TRANSDUCT_DEFAULTS["lam"]):
+    """Step 4.1: (u [N, C] = lam logy + F mup^T + bias, bias [C] = -1/2 sum_d mu mup)."""
+    (N, d), Cn = feats.shape, logy.shape[1]
+    params = transduct_params(N, Cn, d, k=1, init_top=1, lam=lam)
+    u, bias = torch.empty(N, Cn, device=feats.device), torch.empty(Cn, device=feats.device)
+    b = _transduct_members(feats=_f32(feats), logy=_f32(logy), mu=_f32(mu), mup=_f32(mup), u=u, bias=bias)
+    check(_lib.load().clipfs_transduct_u(C.byref(params), C.byref(b), _stream()), "transduct_u")
+    return u, bias
+
+
+def transduct_z_step(u, nbr, w, z_in, want_labels=False, out=None):
+    """Step 4.2, one Jacobi sweep: z_out[i] = softmax(u[i] + sum_r w[i, r] z_in[nbr[i, r]]).  Returns z_out, or (z_out,
+    labels [N] int32 = argmax, ties low) with ``want_labels``.  ``out`` must not be ``z_in``."""
+    N, Cn = u.shape
+    k = nbr.shape[1]
+    params = transduct_params(N, Cn, 4, k=k, init_top=1)
+    if out is None:
+        out = torch.empty(N, Cn, device=u.device, dtype=torch.float32)
+    labels = torch.empty(N, device=u.device, dtype=torch.int32) if want_labels else None
+    b = _transduct_members(u=_f32(u), nbr=nbr, w=_f32(w))
+    check(_lib.load().clipfs_transduct_z_step(C.byref(params), C.byref(b), _p(_f32(z_in)), _p(_f32(out)), _p(labels),
+                                              _stream()), "transduct_z_step")
+    return (out, labels) if want_labels else out
+
+
+def transduct_stats(feats, z, mu, shot_n, shot_G, Q, M=0, shot_weight=TRANSDUCT_DEFAULTS["shot_weight"],
+                    n_min=TRANSDUCT_DEFAULTS["n_min"], var_floor=TRANSDUCT_DEFAULTS["var_floor"], work=None):
+    """Steps 4.3 and 4.4 from z [N, C]: dict(n, G, mu (a new tensor: ``mu`` where n_c <= n_min), var, mup = mu / var).
+    ``M`` is the number of shots behind shot_n / shot_G / Q (it enters the variance's denominator N + gamma M)."""
+    (N, d), Cn = feats.shape, z.shape[1]
+    params = transduct_params(N, Cn, d, M, k=1, init_top=1, shot_weight=shot_weight, n_min=n_min, var_floor=var_floor)
+    plan = _lib.transduct_plan(params)
+    if work is None:
+        work = torch.empty(plan["stat_work_floats"], device=feats.device, dtype=torch.float32)
+    assert work.numel() >= plan["stat_work_floats"], "transduct_stats: work is too small"
+    e = lambda *s: torch.empty(*s, device=feats.device, dtype=torch.float32)
+    out = dict(n=e(Cn), G=e(Cn, d), mu=mu.clone(), var=e(d), mup=e(Cn, d))
+    b = _transduct_members(feats=_f32(feats), shot_n=_f32(shot_n), shot_G=_f32(shot_G), Q=_f32(Q), stat_work=work, **out)
+    check(_lib.load().clipfs_transduct_stats(C.byref(params), C.byref(b), _p(_f32(z)), _stream()), "transduct_stats")
+    return out
+
+
+def transduct_fit(feats, text, shots=None, shot_labels=None, knn_chunks=0, buffers=None, **hyper):
+    """TransCLIP-style transductive inference (the rule of include/clipfs.h, "TRANSDUCT") over the whole test set
+    ``feats`` [N, d] (unit rows) against class features ``text`` [C, d], optionally with labelled ``shots`` [M, d] /
+    ``shot_labels`` [M]: 6 + (chunks > 1) + outer (inner + 4) launches on the current stream, no host synchronisation,
+    bitwise equal run to run.  Returns the ``buffers`` dict (``transduct_buffers``): z, labels, zs_labels, mu, var, nbr, w
+    are the outputs of step 5; the rest is state and work.  ``hyper`` overrides TRANSDUCT_DEFAULTS."""
+    assert feats.dim() == 2 and text.dim() == 2 and feats.shape[1] == text.shape[1], (tuple(feats.shape), tuple(text.shape))
+    (N, d), Cn = feats.shape, text.shape[0]
+    S, y, yh, M = _transduct_shots(shots, shot_labels, d, feats.device)
+    params = transduct_params(N, Cn, d, M, knn_chunks, **hyper)
+    if buffers is None:
+        buffers = transduct_buffers(N, Cn, d, feats.device, M, knn_chunks, **hyper)
+    for name, (shape, dt) in transduct_shapes(N, Cn, d, M, knn_chunks, **hyper).items():
+        t = buffers[name]
+        assert tuple(t.shape) == tuple(shape) and t.dtype == dt, f"transduct_fit: buffers[{name!r}] must be {dt} of shape {shape}"
+    b = _transduct_members(feats=_f32(feats), text=_f32(text), shots=S, shot_labels=y, **buffers)
+    if yh is not None:
+        b.shot_labels_host = yh.data_ptr()
+    check(_lib.load().clipfs_transduct_fit(C.byref(params), C.byref(b), _stream()), "transduct_fit")
+    return buffers
+
+
 # ------------------------------------------------------------------------------------------------ contrastive objective
 def contrastive_plan(op: str, R: int, N: int, d: int):
     """What ``contrastive_objective`` launches for these shapes ("stats", "combine", "dq", "dk"; host-only): grid, block,
