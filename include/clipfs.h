@@ -1492,6 +1492,128 @@ int clipfs_transduct_stats(const struct clipfs_transduct_params* params, const s
 int clipfs_transduct_fit(const struct clipfs_transduct_params* params, const struct clipfs_transduct_buffers* buffers,
                          void* stream);
 
+/* --------------------------------------------------------------------- SPD --
+ * Symmetric positive definite systems in fp32: the blocked Cholesky factor A = L L^T and the solve with many right-hand
+ * sides, block 32 on the fp32 matrix cores.  Matrices are row-major with 16-byte-aligned bases; n is a multiple of 4 in
+ * [4, 1024]; leading dimensions are multiples of 4 and at least n.  No atomics, no caller memory besides the arguments,
+ * nothing returns to the host; results are bitwise equal run to run.
+ *
+ * clipfs_spd_factor reads ONLY the lower triangle of A (diagonal included) and writes L into the lower triangle of the
+ * output and L^T into its strict upper triangle: the whole n x n output is defined (columns n .. ldl of a row are not
+ * touched), and the backward substitution reads contiguous rows.  L == A with ldl == lda factors in place (bitwise the
+ * out-of-place result); any other overlap is refused.  `info` is a device int32: 0 on success, else the 1-based index of
+ * the first pivot that is <= 0 or not finite; the columns before that pivot are valid, later columns are unspecified
+ * and may be NaN.  The call always terminates (nothing loops on data) and indexes nothing by a computed value.
+ * ceil(n / 32) launches: launch j factors block column j, one workgroup per 32-row tile at or below the diagonal, each
+ * forming and factoring the updated diagonal tile itself; diagonal tile j is written by one more workgroup of launch
+ * j + 1 (the last one by its own launch), which is what makes the in-place form safe.
+ *
+ * clipfs_spd_solve: X[i, :] = alpha * A^-1 R[i, :] for the rows i < nrhs (nrhs in [1, 65536]) from the output of
+ * clipfs_spd_factor.  X == R with ldx == ldr is allowed; the intermediate of the forward substitution lives in X.  Two
+ * launches, forward and backward; one workgroup owns 32 right-hand-side rows, keeps them in LDS (32 (n + 4) floats) and
+ * walks the block columns itself.  A factor whose info is not 0 gives unspecified (possibly NaN) values, never a fault.
+ *
+ * clipfs_spd_plan is host-only (nothing written to `plan` on refusal).  CLIPFS_EINVAL before anything is enqueued, the
+ * message naming the argument: n not a multiple of 4 in [4, 1024]; nrhs outside [1, 65536]; a matrix NULL or not
+ * 16-byte aligned; lda / ldl / ldr / ldx below n or not a multiple of 4; info NULL or misaligned or inside A or L; L
+ * overlapping A, or X overlapping R, other than as the same matrix; X overlapping L; alpha not finite. */
+struct clipfs_spd_plan {
+  int block;           /* 32 */
+  int factor_launches; /* ceil(n / 32) */
+  int solve_launches;  /* 2 */
+  unsigned factor_grid; /* workgroups of the first factor launch: ceil(n / 32); launch j > 0 has ceil(n / 32) - j + 1 */
+  unsigned solve_grid;  /* ceil(nrhs / 32), both launches */
+  unsigned threads;     /* 256 */
+  unsigned factor_lds_bytes, solve_lds_bytes;
+  unsigned lds_bytes;   /* the larger (at most 160 KB) */
+};
+int clipfs_spd_plan(int n, int nrhs, struct clipfs_spd_plan* plan);
+int clipfs_spd_factor(const float* A, int lda, float* L, int ldl, int n, int32_t* info, void* stream);
+int clipfs_spd_solve(const float* L, int ldl, int n, const float* R, int ldr, float* X, int ldx, int nrhs, float alpha,
+                     void* stream);
+
+/* --------------------------------------------------------------------- GDA --
+ * Training-free Gaussian discriminant head (Wang et al., "A Hard-to-Beat Baseline for Training-Free CLIP-Based
+ * Adaptation", ICLR 2024): one mean per class and ONE shared full covariance of the few-shot features, shrunk towards
+ * its trace; the linear classifier W = Sigma^-1 mu is added to the zero-shot logits with one weight alpha.  No training,
+ * no backward, no tower pass; fp32.  Where the published code differs from the rule below, the rule holds.
+ *
+ * THE RULE.  Inputs: shots S [M, d] with unit rows (assumed, not checked), SORTED BY CLASS; offsets int32 [C + 1]
+ * (class c owns rows offsets[c] .. offsets[c + 1] - 1); every class owns at least one shot and M >= 2.  d is a multiple
+ * of 4 in [4, 1024], C in [1, 4096], M in [2, 65536].
+ *   1. mu_c = the mean of class c's shots: an fp32 sum in row order divided by n_c.
+ *   2. X = S - mu_y, stored transposed as xt [d, Mp], Mp = M rounded up to 32, the tail zero.
+ *   3. G = xt xt^T [d, d]: one clipfs_gemm_nt call (K = Mp takes its K % 32 == 0 path).
+ *   4. tau = trace(G), summed in double in a fixed order; A = G + shrink tau / (M - 1) I (shrink >= 0, 1 by default).
+ *      With Sigma = G / (M - 1) this is the published (M - 1) Sigma + trace(Sigma) I.  No host synchronisation: with
+ *      tau = 0 (or shrink = 0 and a singular G) A is singular and `info` reports it.
+ *   5. A = L L^T (clipfs_spd_factor), Z = A^-1 mu with rows as right-hand sides, W = d Z [C, d] (clipfs_spd_solve with
+ *      alpha = d).
+ *   6. b_c = log pi_c - 1/2 mu_c . W_c; pi_c = 1 / C (CLIPFS_GDA_PRIOR_UNIFORM) or n_c / M (_EMPIRICAL).
+ *   7. logits = base + alpha (F W^T + b) for unit test features F [B, d] and the caller's zero-shot logits base [B, C]
+ *      (NULL: 0): ONE clipfs_gemm_nt call with alpha, bias = alpha b and residual = base; there is no kernel for it here.
+ *   8. The alpha search runs on g = F W^T + b, formed once: hits[a] = the number of rows whose
+ *      argmax_c (base + alphas[a] g) equals the target, the argmax taking the lowest index on ties; all nA in [1, 1024]
+ *      cells in one launch.
+ *
+ * buffers (device memory except offsets_host).  Every intermediate is a named output, written whole before it is read:
+ *   inputs   shots [M, d], offsets [C + 1] int32, offsets_host: an optional HOST copy of the offsets, checked before
+ *            anything is enqueued (a device copy that disagrees cannot send a kernel anywhere: the kernels clamp it)
+ *   outputs  mu [C, d], xt [d, Mp], gram [d, d] (G after step 3, A after step 4), tau [1], chol [d, d] (L below and on
+ *            the diagonal, L^T above), info [1] int32 (clipfs_spd_factor's), W [C, d], b [C]
+ * Stages (each runs alone on the members named): stats (shots, offsets -> mu, xt); shrink (gram -> gram, tau);
+ * bias (mu, W, offsets -> b).  clipfs_gda_fit IS stats, clipfs_gemm_nt (xt -> gram, without a split-K workspace), shrink,
+ * clipfs_spd_factor (gram -> chol, info), clipfs_spd_solve (chol, mu -> W) and bias in this order on `stream`, bit for
+ * bit: 6 + ceil(d / 32) launches, a function of d alone, no host synchronisation, no float atomics.
+ *
+ * clipfs_gda_search(g [B, C], base [B, C] with row stride ldbase or NULL, target int64 [B], alphas [nA], hits int32
+ * [nA]): zeroes `hits` on the stream, then one launch; rows are counted in LDS integers and added with integer atomics.
+ *
+ * clipfs_gda_plan is host-only (nothing written to `plan` on refusal).  CLIPFS_EINVAL before anything is enqueued, the
+ * message naming the argument: params, buffers or plan NULL or of another struct_size; d not a multiple of 4 in
+ * [4, 1024]; C outside [1, 4096]; M outside [2, 65536] or below C; prior unknown; shrink negative or not finite; a used
+ * member NULL or misaligned (16 bytes for the matrices, 4 for the vectors); a written member overlapping another
+ * member; in offsets_host: offsets[0] != 0, a class without a shot, a descending entry, offsets[C] != M; in the search:
+ * B, C or nA out of range, a NULL or misaligned argument, ldbase below C. */
+#define CLIPFS_GDA_PRIOR_UNIFORM 0
+#define CLIPFS_GDA_PRIOR_EMPIRICAL 1
+struct clipfs_gda_params {
+  unsigned struct_size; /* sizeof(struct clipfs_gda_params) */
+  int M, C, d;
+  int prior;    /* CLIPFS_GDA_PRIOR_* */
+  float shrink; /* 1: the published rule */
+};
+struct clipfs_gda_buffers {
+  unsigned struct_size;
+  const float* shots;
+  const int32_t* offsets;
+  const int32_t* offsets_host;
+  float* mu;
+  float* xt;
+  float* gram;
+  float* tau;
+  float* chol;
+  int32_t* info;
+  float* W;
+  float* b;
+};
+struct clipfs_gda_plan {
+  int launches;        /* of a fit: 6 + ceil(d / 32) */
+  int Mp;              /* M rounded up to 32: the row length of xt */
+  int factor_launches; /* ceil(d / 32) */
+  int solve_launches;  /* 2 */
+  unsigned stats_grid, bias_grid, solve_grid, threads;
+  unsigned lds_bytes; /* the largest LDS of a workgroup (the solve's; at most 160 KB) */
+  size_t xt_floats;   /* d Mp */
+};
+int clipfs_gda_plan(const struct clipfs_gda_params* params, struct clipfs_gda_plan* plan);
+int clipfs_gda_stats(const struct clipfs_gda_params* params, const struct clipfs_gda_buffers* buffers, void* stream);
+int clipfs_gda_shrink(const struct clipfs_gda_params* params, const struct clipfs_gda_buffers* buffers, void* stream);
+int clipfs_gda_bias(const struct clipfs_gda_params* params, const struct clipfs_gda_buffers* buffers, void* stream);
+int clipfs_gda_search(const float* g, const float* base, int ldbase, const int64_t* target, const float* alphas,
+                      int32_t* hits, int B, int C, int nA, void* stream);
+int clipfs_gda_fit(const struct clipfs_gda_params* params, const struct clipfs_gda_buffers* buffers, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -206,6 +206,39 @@ class TransductPlan(C.Structure):
                 ("knn_work_bytes", C.c_size_t), ("stat_work_floats", C.c_size_t), ("nc_floats", C.c_size_t)]
 
 
+class SpdPlan(C.Structure):
+    """struct clipfs_spd_plan: what clipfs_spd_factor and clipfs_spd_solve launch."""
+    _fields_ = [("block", C.c_int), ("factor_launches", C.c_int), ("solve_launches", C.c_int), ("factor_grid", C.c_uint),
+                ("solve_grid", C.c_uint), ("threads", C.c_uint), ("factor_lds_bytes", C.c_uint), ("solve_lds_bytes", C.c_uint),
+                ("lds_bytes", C.c_uint)]
+
+
+# CLIPFS_GDA_PRIOR_* of include/clipfs.h, by value
+GDA_PRIORS = ("uniform", "empirical")
+
+
+class GdaParams(C.Structure):
+    """struct clipfs_gda_params: the shapes and hyper-parameters of a GDA fit."""
+    _fields_ = [("struct_size", C.c_uint), ("M", C.c_int), ("C", C.c_int), ("d", C.c_int), ("prior", C.c_int),
+                ("shrink", C.c_float)]
+
+
+# members of struct clipfs_gda_buffers, in order (offsets_host is host memory, the rest device memory)
+GDA_BUFFER_FIELDS = ("shots", "offsets", "offsets_host", "mu", "xt", "gram", "tau", "chol", "info", "W", "b")
+
+
+class GdaBuffers(C.Structure):
+    """struct clipfs_gda_buffers: the inputs and the named outputs of the GDA stages."""
+    _fields_ = [("struct_size", C.c_uint)] + [(n, C.c_void_p) for n in GDA_BUFFER_FIELDS]
+
+
+class GdaPlan(C.Structure):
+    """struct clipfs_gda_plan: what a GDA fit launches."""
+    _fields_ = [("launches", C.c_int), ("Mp", C.c_int), ("factor_launches", C.c_int), ("solve_launches", C.c_int),
+                ("stats_grid", C.c_uint), ("bias_grid", C.c_uint), ("solve_grid", C.c_uint), ("threads", C.c_uint),
+                ("lds_bytes", C.c_uint), ("xt_floats", C.c_size_t)]
+
+
 class MergeJob(C.Structure):
     """struct clipfs_lora_merge_job: one projection of a clipfs_lora_merge table."""
     _fields_ = [("w", C.c_void_p), ("a", C.c_void_p), ("b", C.c_void_p), ("out", C.c_void_p), ("planes", C.c_void_p),
@@ -401,6 +434,15 @@ SIGNATURES = {
     "clipfs_transduct_z_step": (_i, [C.POINTER(TransductParams), C.POINTER(TransductBuffers), _p, _p, _p, _p]),
     "clipfs_transduct_stats": (_i, [C.POINTER(TransductParams), C.POINTER(TransductBuffers), _p, _p]),
     "clipfs_transduct_fit": (_i, [C.POINTER(TransductParams), C.POINTER(TransductBuffers), _p]),
+    "clipfs_spd_plan": (_i, [C.c_int, C.c_int, C.POINTER(SpdPlan)]),
+    "clipfs_spd_factor": (_i, [_p, C.c_int, _p, C.c_int, C.c_int, _p, _p]),
+    "clipfs_spd_solve": (_i, [_p, C.c_int, C.c_int, _p, C.c_int, _p, C.c_int, C.c_int, C.c_float, _p]),
+    "clipfs_gda_plan": (_i, [C.POINTER(GdaParams), C.POINTER(GdaPlan)]),
+    "clipfs_gda_stats": (_i, [C.POINTER(GdaParams), C.POINTER(GdaBuffers), _p]),
+    "clipfs_gda_shrink": (_i, [C.POINTER(GdaParams), C.POINTER(GdaBuffers), _p]),
+    "clipfs_gda_bias": (_i, [C.POINTER(GdaParams), C.POINTER(GdaBuffers), _p]),
+    "clipfs_gda_search": (_i, [_p, _p, C.c_int, _p, _p, _p, C.c_int, C.c_int, C.c_int, _p]),
+    "clipfs_gda_fit": (_i, [C.POINTER(GdaParams), C.POINTER(GdaBuffers), _p]),
 }
 
 # word indices of the loss-scaling record (CLIPFS_SCALER_* of include/clipfs.h)
@@ -549,6 +591,39 @@ def transduct_plan(params: TransductParams):
     d["launch"] = {TRANSDUCT_LAUNCHES[i]: (l.grid_x, l.grid_y, l.grid_z, l.block, l.lds_bytes)
                    for i, l in enumerate(plan.launch) if l.grid_x}
     return d
+
+
+def spd_plan(n: int, nrhs: int = 1):
+    """The plan clipfs_spd_factor / clipfs_spd_solve execute for an n x n system with nrhs right-hand sides (host-only), as a
+    dict of the fields of struct clipfs_spd_plan.  A refusal raises ClipfsError with its message."""
+    plan = SpdPlan()
+    check(load().clipfs_spd_plan(n, nrhs, C.byref(plan)), "spd_plan")
+    return {k: getattr(plan, k) for k, _ in SpdPlan._fields_}
+
+
+def new_gda_params(**fields) -> GdaParams:
+    p = GdaParams()
+    p.struct_size = C.sizeof(GdaParams)
+    for k, v in fields.items():
+        setattr(p, k, v)
+    return p
+
+
+def new_gda_buffers(**members) -> GdaBuffers:
+    """struct clipfs_gda_buffers with the named members set (addresses as integers); the rest stay NULL."""
+    b = GdaBuffers()
+    b.struct_size = C.sizeof(GdaBuffers)
+    for k, v in members.items():
+        setattr(b, k, v)
+    return b
+
+
+def gda_plan(params: GdaParams):
+    """The plan the GDA entry points execute (host-only), as a dict of the fields of struct clipfs_gda_plan.  A refusal raises
+    ClipfsError with its message."""
+    plan = GdaPlan()
+    check(load().clipfs_gda_plan(C.byref(params), C.byref(plan)), "gda_plan")
+    return {k: getattr(plan, k) for k, _ in GdaPlan._fields_}
 
 
 def new_tower() -> Tower:

@@ -1088,6 +1088,163 @@ def transduct_fit(feats, text, shots=None, shot_labels=None, knn_chunks=0, buffe
     return buffers
 
 
+# ------------------------------------------------------------------------------------------------ SPD factor and solve
+def spd_plan(n: int, nrhs: int = 1):
+    """What ``spd_factor`` and ``spd_solve`` launch for an n x n system with nrhs right-hand sides (host-only):
+    factor_launches = ceil(n / 32), solve_launches = 2, the grids, threads and LDS bytes."""
+    return _lib.spd_plan(n, nrhs)
+
+
+def _spd_matrix(t: torch.Tensor, cols: int, what: str) -> torch.Tensor:
+    assert t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and t.shape[1] == cols and t.stride(1) == 1, \
+        f"{what} must be an fp32 device matrix with {cols} columns of unit stride"
+    return t
+
+
+def _ld(t: torch.Tensor) -> int:
+    return t.stride(0) if t.shape[0] > 1 else max(t.stride(0), t.shape[1])
+
+
+def spd_factor(a: torch.Tensor, out: Optional[torch.Tensor] = None):
+    """Cholesky factor of the symmetric positive definite ``a`` [n, n] (only its lower triangle is read): returns
+    (chol, info).  ``chol`` holds L on and below the diagonal and L^T above it; ``info`` is a device int32 [1]: 0, or the
+    1-based index of the first pivot that is <= 0 or not finite (read it when you want to know: nothing synchronises
+    here).  ``a`` and ``out`` may be column slices (row stride >= n, a multiple of 4); ``out=a`` factors in place."""
+    n = a.shape[0]
+    _spd_matrix(a, n, "spd_factor: a")
+    if out is None:
+        out = torch.empty(n, n, device=a.device, dtype=torch.float32)
+    _spd_matrix(out, n, "spd_factor: out")
+    assert out.shape[0] == n
+    info = torch.empty(1, device=a.device, dtype=torch.int32)
+    check(_lib.load().clipfs_spd_factor(_p(a), _ld(a), _p(out), _ld(out), n, _p(info), _stream()), "spd_factor")
+    return out, info
+
+
+def spd_solve(chol: torch.Tensor, rhs: torch.Tensor, alpha: float = 1.0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out[i, :] = alpha * A^-1 rhs[i, :] for the rows of ``rhs`` [nrhs, n], from ``chol`` = ``spd_factor(A)[0]``.
+    ``out=rhs`` solves in place."""
+    n = chol.shape[0]
+    _spd_matrix(chol, n, "spd_solve: chol")
+    _spd_matrix(rhs, n, "spd_solve: rhs")
+    if out is None:
+        out = torch.empty(rhs.shape[0], n, device=rhs.device, dtype=torch.float32)
+    _spd_matrix(out, n, "spd_solve: out")
+    assert out.shape[0] == rhs.shape[0]
+    check(_lib.load().clipfs_spd_solve(_p(chol), _ld(chol), n, _p(rhs), _ld(rhs), _p(out), _ld(out), rhs.shape[0], alpha,
+                                       _stream()), "spd_solve")
+    return out
+
+
+# ------------------------------------------------------------------------------------------------ GDA head
+GDA_DEFAULT_ALPHAS = tuple(10.0 ** e for e in range(-4, 5))
+
+
+def gda_params(M: int, C_: int, d: int, prior: str = "uniform", shrink: float = 1.0):
+    """struct clipfs_gda_params; ``prior`` is "uniform" or "empirical"."""
+    if prior not in _lib.GDA_PRIORS:
+        raise ValueError(f"gda: prior must be one of {_lib.GDA_PRIORS}, not {prior!r}")
+    return _lib.new_gda_params(M=M, C=C_, d=d, prior=_lib.GDA_PRIORS.index(prior), shrink=shrink)
+
+
+def gda_plan(M: int, C_: int, d: int, prior: str = "uniform", shrink: float = 1.0):
+    """What a fit launches (host-only): launches = 6 + ceil(d / 32) whatever M and C, Mp, factor_launches, solve_launches,
+    the grids, lds_bytes and xt_floats."""
+    return _lib.gda_plan(gda_params(M, C_, d, prior, shrink))
+
+
+def gda_shapes(M: int, C_: int, d: int):
+    """{member: (shape, dtype)} of the outputs of struct clipfs_gda_buffers for these shapes."""
+    Mp = (M + 31) // 32 * 32
+    f32, i32 = torch.float32, torch.int32
+    return dict(mu=((C_, d), f32), xt=((d, Mp), f32), gram=((d, d), f32), tau=((1,), f32), chol=((d, d), f32),
+                info=((1,), i32), W=((C_, d), f32), b=((C_,), f32))
+
+
+def gda_buffers(M: int, C_: int, d: int, device):
+    """Uninitialised device tensors for every output of a fit: every element is written before it is read."""
+    return {name: torch.empty(shape, device=device, dtype=dt) for name, (shape, dt) in gda_shapes(M, C_, d).items()}
+
+
+def _gda_members(offsets_host=None, **tensors):
+    mem = {}
+    for name, t in tensors.items():
+        want = torch.int32 if name in ("offsets", "info") else torch.float32
+        assert t.is_cuda and t.is_contiguous() and t.dtype == want, f"gda: {name} must be a contiguous {want} device tensor"
+        mem[name] = t.data_ptr()
+    b = _lib.new_gda_buffers(**mem)
+    if offsets_host is not None:
+        assert not offsets_host.is_cuda and offsets_host.dtype == torch.int32 and offsets_host.is_contiguous()
+        b.offsets_host = offsets_host.data_ptr()
+    return b
+
+
+def _gda_dims(shots, offsets):
+    assert shots.dim() == 2 and offsets.dim() == 1 and offsets.dtype == torch.int32, "gda: shots [M, d], offsets int32 [C + 1]"
+    return shots.shape[0], offsets.numel() - 1, shots.shape[1]
+
+
+def gda_stats(shots, offsets, offsets_host=None):
+    """Steps 1 and 2 of the rule (include/clipfs.h, "GDA"): (mu [C, d], xt [d, Mp]) of ``shots`` [M, d] sorted by class with
+    ``offsets`` int32 [C + 1].  ``offsets_host`` (a CPU int32 copy) is checked before anything is enqueued."""
+    M, Cn, d = _gda_dims(shots, offsets)
+    params = gda_params(M, Cn, d)
+    sh = gda_shapes(M, Cn, d)
+    out = {k: torch.empty(sh[k][0], device=shots.device, dtype=sh[k][1]) for k in ("mu", "xt")}
+    b = _gda_members(offsets_host, shots=_f32(shots), offsets=offsets, **out)
+    check(_lib.load().clipfs_gda_stats(C.byref(params), C.byref(b), _stream()), "gda_stats")
+    return out["mu"], out["xt"]
+
+
+def gda_shrink(gram, M: int, shrink: float = 1.0):
+    """Step 4, in place on ``gram`` [d, d]: adds shrink * trace / (M - 1) to its diagonal; returns (gram, tau [1])."""
+    d = gram.shape[0]
+    params = gda_params(M, 1, d, shrink=shrink)
+    tau = torch.empty(1, device=gram.device, dtype=torch.float32)
+    b = _gda_members(gram=_f32(gram), tau=tau)
+    check(_lib.load().clipfs_gda_shrink(C.byref(params), C.byref(b), _stream()), "gda_shrink")
+    return gram, tau
+
+
+def gda_bias(mu, W, offsets, M: int, prior: str = "uniform", offsets_host=None):
+    """Step 6: b [C] = log pi_c - 1/2 mu_c . W_c."""
+    Cn, d = mu.shape
+    params = gda_params(M, Cn, d, prior)
+    out = torch.empty(Cn, device=mu.device, dtype=torch.float32)
+    b = _gda_members(offsets_host, mu=_f32(mu), W=_f32(W), offsets=offsets, b=out)
+    check(_lib.load().clipfs_gda_bias(C.byref(params), C.byref(b), _stream()), "gda_bias")
+    return out
+
+
+def gda_search(g, base, target, alphas):
+    """hits int32 [nA]: per alpha the rows of ``g`` [B, C] whose argmax_c (base + alpha g), ties to the lower class, equals
+    ``target`` (int64 [B]); one launch.  ``base`` [B, C] may be None (0) or a column slice; ``alphas`` is an fp32 device
+    vector."""
+    B, Cn = g.shape
+    assert target.dtype == torch.int64 and target.is_contiguous() and target.numel() == B and target.is_cuda
+    assert base is None or (base.dtype == torch.float32 and tuple(base.shape) == (B, Cn) and base.stride(1) == 1)
+    hits = torch.empty(alphas.numel(), device=g.device, dtype=torch.int32)
+    check(_lib.load().clipfs_gda_search(_p(_f32(g)), _p(base), 0 if base is None else _ld(base), _p(target), _p(_f32(alphas)),
+                                        _p(hits), B, Cn, alphas.numel(), _stream()), "gda_search")
+    return hits
+
+
+def gda_fit(shots, offsets, prior: str = "uniform", shrink: float = 1.0, offsets_host=None, buffers=None):
+    """Steps 1-6 of the rule on the current stream, 6 + ceil(d / 32) launches, no host synchronisation, bitwise equal run
+    to run and bitwise the stages called one by one.  Returns the ``buffers`` dict (``gda_buffers``): mu, xt, gram (after
+    the shrinkage), tau, chol, info, W, b."""
+    M, Cn, d = _gda_dims(shots, offsets)
+    params = gda_params(M, Cn, d, prior, shrink)
+    if buffers is None:
+        buffers = gda_buffers(M, Cn, d, shots.device)
+    for name, (shape, dt) in gda_shapes(M, Cn, d).items():
+        t = buffers[name]
+        assert tuple(t.shape) == tuple(shape) and t.dtype == dt, f"gda_fit: buffers[{name!r}] must be {dt} of shape {shape}"
+    b = _gda_members(offsets_host, shots=_f32(shots), offsets=offsets, **buffers)
+    check(_lib.load().clipfs_gda_fit(C.byref(params), C.byref(b), _stream()), "gda_fit")
+    return buffers
+
+
 # ------------------------------------------------------------------------------------------------ contrastive objective
 def contrastive_plan(op: str, R: int, N: int, d: int):
     """What ``contrastive_objective`` launches for these shapes ("stats", "combine", "dq", "dk"; host-only): grid, block,

@@ -1,5 +1,6 @@
 // 32 x 32 fp32 tiles of row-by-row dot products on v_mfma_f32_32x32x2_f32, and the gradient walk built on them: the
-// device machinery shared by cache_head.hip, tpt.hip and contrastive.hip (and by them only).
+// device machinery shared by cache_head.hip, tpt.hip and contrastive.hip, and later by sigmoid_pairs.hip, clip_pairs.hip,
+// tda.hip, transduct.hip and spd.hip (gda.hip includes it for the shared types only).
 //
 // A tile is formed the way attention_mfma.hip forms its scores.  Both operands are row-major rows of d floats; the
 // K-slot <-> feature assignment of an MFMA sum is free as long as A and B agree, so each half-wave takes one contiguous
@@ -9,6 +10,7 @@
 //
 //   tile_dots         operands straight from global memory / L2: a lane reads 128 contiguous bytes of its row per
 //                     64-feature step.
+//   tile_dots_ld      tile_dots with a leading dimension per side (rows of a Cholesky factor, an operand in LDS): spd.hip
 //   tile_dots_staged  operands through LDS in chunks of TILE_KC features, the four waves of a workgroup splitting each
 //                     chunk; tile_sum4 adds their partials in wave order.
 //   tile_grad_walk    out[x, :] (+)= sum_y G(x, y) Y[y, :] for one workgroup's 32 own rows and 128 NACC features, G a
@@ -47,6 +49,34 @@ __device__ __forceinline__ f32x16 tile_dots(const float* __restrict__ A, int a0,
   for (int r = 0; r < 16; ++r) acc[r] = 0.f;
   const float* pa = A + (size_t)min(a0 + li, na - 1) * d + 32 * h;
   const float* pb = Bm + (size_t)min(b0 + li, nb - 1) * d + 32 * h;
+  for (int s = s0; s < d; s += sstep) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      f32x4 va, vb;
+      va[0] = va[1] = va[2] = va[3] = 0.f;
+      vb = va;
+      if (s + 32 * h + 4 * j < d) {
+        va = *reinterpret_cast<const f32x4*>(pa + s + 4 * j);
+        vb = *reinterpret_cast<const f32x4*>(pb + s + 4 * j);
+      }
+#pragma unroll
+      for (int e = 0; e < 4; ++e) acc = tile_mfma(va[e], vb[e], acc);
+    }
+  }
+  return acc;
+}
+
+// tile_dots with a leading dimension per side (multiples of 4, rows 16-byte aligned): rows of a matrix, or of two column
+// ranges of one (spd.hip: a row block of a Cholesky factor against another; the sides may be the same memory, so
+// neither is __restrict__).  An operand may live in LDS.  Same clamping, same zero fill past d, same order of the sum.
+__device__ __forceinline__ f32x16 tile_dots_ld(const float* A, int lda, int a0, int na, const float* Bm, int ldb, int b0, int nb,
+                                               int d, int s0, int sstep, int lane) {
+  const int li = lane & 31, h = lane >> 5;
+  f32x16 acc;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+  const float* pa = A + (size_t)min(a0 + li, na - 1) * lda + 32 * h;
+  const float* pb = Bm + (size_t)min(b0 + li, nb - 1) * ldb + 32 * h;
   for (int s = s0; s < d; s += sstep) {
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
