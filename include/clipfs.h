@@ -1614,6 +1614,70 @@ int clipfs_gda_search(const float* g, const float* base, int ldbase, const int64
                       int32_t* hits, int B, int C, int nA, void* stream);
 int clipfs_gda_fit(const struct clipfs_gda_params* params, const struct clipfs_gda_buffers* buffers, void* stream);
 
+/* ------------------------------------------------------------- OT matching --
+ * Optimal-transport matching of M local image features against the N prompt features of every class (PLOT: Chen et al.,
+ * "Prompt Learning with Optimal Transport for Vision-Language Models", ICLR 2023), fp32 in every precision mode.  The
+ * [B, C, M, N] similarity never reaches memory.  Where the published code differs from the rule below, the rule holds.
+ *
+ * THE RULE.  Inputs: X [B, M, d] and P [C, N, d], fp32 rows that the caller has normalised to unit length (assumed, not
+ * checked); marginals mu [B, M] and nu [C, N], positive, each row summing to 1 (NULL: uniform 1/M, 1/N); eps, iters,
+ * scale.
+ *   z[b,c,m,n] = X[b,m,:] . P[c,n,:]
+ *   K = exp((z - 1) / eps)                       (exp2((z - 1) * (log2e / eps)) on the device)
+ *   v = 1
+ *   repeat iters times:   u = mu / (K v)      v = nu / (K^T u)      (this order)
+ *   T = diag(u) K diag(v)
+ *   logits[b,c] = scale * sum_{m,n} T z
+ * Backward: T is a constant, as in PLOT (its Sinkhorn runs under no_grad).  With G = dlogits[b,c] * scale * T[b,c,m,n]:
+ *   dP[c,n,:] = sum_{b,m} G X[b,m,:]             dX[b,m,:] = sum_{c,n} G P[c,n,:]
+ *
+ * DEVIATION FROM THE PAPER.  `iters` is fixed (100 in PLOT's configuration).  PLOT stops early once the batch mean of
+ * |u - u_prev| falls below 1e-2: a loop whose length depends on the data, decided by a host read.  It is not offered.
+ *
+ * Limits: d a multiple of 4 in [4, 1024]; M in [1, 256]; N in [1, 32]; eps in [0.05, 10]; iters in [1, 1000]; scale
+ * finite; B and C in [1, 2^20] with B M <= 2^24, C N <= 2^24 and B C <= 2^28.  The lower eps bound is derived: with unit
+ * rows z >= -1, so K >= exp(-2 / eps) = exp(-40) = 4e-18 at eps = 0.05 and u, v and T stay finite in fp32; at
+ * eps = 0.02 K reaches exp(-100), which is subnormal.
+ *
+ * clipfs_ot_logits (replaces PLOT's `sim = einsum('mbd,ncd->mnbc')`, `Sinkhorn(KK, u, v)` and
+ * `sim_op = sum(T * sim, dim=(0, 1))`): ONE launch.  Outputs logits [B, C] (row stride ldl >= C; the columns past C are
+ * not touched), u [B, C, M] and v [B, C, N]: the scalings after the last iteration, which clipfs_ot_bwd reads.  There is
+ * no caller scratch.  One workgroup owns an image and a chunk of classes, forms the chunk's z on the fp32 matrix cores
+ * into LDS, and each wave then iterates one class at a time with K in registers.
+ *
+ * clipfs_ot_bwd (replaces autograd through `sum(T * sim)` with T detached): one launch for dP [C, N, d] and, with dX
+ * not NULL, one for dX [B, M, d], both walks of 32 x 32 tiles that form z again (the same fp32 number per cell as the
+ * forward held) and G from u, v and dlogits [B, C] (row stride ldd >= C).  accumulate != 0 adds to dP / dX.
+ *
+ * No float atomics; every output element is written by one thread; the order of every sum depends on the shapes alone;
+ * nothing returns to the host; results are bitwise equal run to run, and a (b, c) cell does not depend on which other
+ * images and classes share the call.  A forward workgroup that needs more than 64 KB of LDS (M > 224) asks for it.
+ *
+ * clipfs_ot_plan is host-only (nothing written to `plan` on refusal).  CLIPFS_EINVAL before anything is enqueued, the
+ * message naming the argument: a shape, eps, iters or scale outside the limits; ldl or ldd below C; X, P, logits, u, v,
+ * dlogits or dP NULL; X, P, dP or dX not 16-byte aligned (the others: 4); an output overlapping an input or another
+ * output. */
+struct clipfs_ot_plan {
+  int fwd_launches, dp_launches, dx_launches; /* 1, 1, 1 */
+  int rows_per_lane; /* rows of z a lane of the forward owns: ceil(M / 64) rounded up to 1, 2 or 4 */
+  int prompt_regs;   /* N rounded up to 4, 8, 16 or 32: the forward instantiation */
+  int class_chunk;   /* classes per forward workgroup */
+  int class_chunks;  /* ceil(C / class_chunk) */
+  int z_stride;      /* row stride of z in LDS: 32 ceil(class_chunk N / 32) + 1 */
+  int dp_feat_chunk, dx_feat_chunk; /* features per gradient workgroup: 512 or 128 */
+  unsigned fwd_grid; /* B class_chunks */
+  unsigned dp_grid_x, dp_grid_y; /* (ceil(C N / 32), ceil(d / dp_feat_chunk)) */
+  unsigned dx_grid_x, dx_grid_y; /* (ceil(B M / 32), ceil(d / dx_feat_chunk)) */
+  unsigned threads;  /* 256 */
+  unsigned fwd_lds_bytes; /* 4 * 32 ceil(M / 32) * z_stride (at most 66 560) */
+  unsigned bwd_lds_bytes;
+};
+int clipfs_ot_plan(int B, int M, int C, int N, int d, struct clipfs_ot_plan* plan);
+int clipfs_ot_logits(const float* X, const float* P, const float* mu, const float* nu, float* logits, int ldl, float* u,
+                     float* v, int B, int M, int C, int N, int d, float eps, int iters, float scale, void* stream);
+int clipfs_ot_bwd(const float* X, const float* P, const float* u, const float* v, const float* dlogits, int ldd, float* dP,
+                  float* dX, int B, int M, int C, int N, int d, float eps, float scale, int accumulate, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -239,6 +239,15 @@ class GdaPlan(C.Structure):
                 ("lds_bytes", C.c_uint), ("xt_floats", C.c_size_t)]
 
 
+class OtPlan(C.Structure):
+    """struct clipfs_ot_plan: what clipfs_ot_logits and clipfs_ot_bwd launch."""
+    _fields_ = [("fwd_launches", C.c_int), ("dp_launches", C.c_int), ("dx_launches", C.c_int), ("rows_per_lane", C.c_int),
+                ("prompt_regs", C.c_int), ("class_chunk", C.c_int), ("class_chunks", C.c_int), ("z_stride", C.c_int),
+                ("dp_feat_chunk", C.c_int), ("dx_feat_chunk", C.c_int), ("fwd_grid", C.c_uint), ("dp_grid_x", C.c_uint),
+                ("dp_grid_y", C.c_uint), ("dx_grid_x", C.c_uint), ("dx_grid_y", C.c_uint), ("threads", C.c_uint),
+                ("fwd_lds_bytes", C.c_uint), ("bwd_lds_bytes", C.c_uint)]
+
+
 class MergeJob(C.Structure):
     """struct clipfs_lora_merge_job: one projection of a clipfs_lora_merge table."""
     _fields_ = [("w", C.c_void_p), ("a", C.c_void_p), ("b", C.c_void_p), ("out", C.c_void_p), ("planes", C.c_void_p),
@@ -443,6 +452,11 @@ SIGNATURES = {
     "clipfs_gda_bias": (_i, [C.POINTER(GdaParams), C.POINTER(GdaBuffers), _p]),
     "clipfs_gda_search": (_i, [_p, _p, C.c_int, _p, _p, _p, C.c_int, C.c_int, C.c_int, _p]),
     "clipfs_gda_fit": (_i, [C.POINTER(GdaParams), C.POINTER(GdaBuffers), _p]),
+    "clipfs_ot_plan": (_i, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(OtPlan)]),
+    "clipfs_ot_logits": (_i, [_p, _p, _p, _p, _p, C.c_int, _p, _p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
+                              C.c_int, C.c_float, _p]),
+    "clipfs_ot_bwd": (_i, [_p, _p, _p, _p, _p, C.c_int, _p, _p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
+                           C.c_float, C.c_int, _p]),
 }
 
 # word indices of the loss-scaling record (CLIPFS_SCALER_* of include/clipfs.h)
@@ -624,6 +638,14 @@ def gda_plan(params: GdaParams):
     plan = GdaPlan()
     check(load().clipfs_gda_plan(C.byref(params), C.byref(plan)), "gda_plan")
     return {k: getattr(plan, k) for k, _ in GdaPlan._fields_}
+
+
+def ot_plan(B: int, M: int, C_: int, N: int, d: int):
+    """The plan clipfs_ot_logits / clipfs_ot_bwd execute for B images of M rows against C_ classes of N prompts (host-only), as
+    a dict of the fields of struct clipfs_ot_plan.  A refusal raises ClipfsError with its message."""
+    plan = OtPlan()
+    check(load().clipfs_ot_plan(B, M, C_, N, d, C.byref(plan)), "ot_plan")
+    return {k: getattr(plan, k) for k, _ in OtPlan._fields_}
 
 
 def new_tower() -> Tower:

@@ -614,6 +614,31 @@ class Engine:
                        pre=(x0, mean0, rstd0) if need_pre else None, lo=lo)
         return feat, ctx
 
+    def vit_tokens(self, images: torch.Tensor, seed: int = 0):
+        """Every row of the image tower through ln_post and proj, without a graph: (tokens [B, P, embed] -- the P patch
+        rows; the class row and the VPT rows are dropped -- and the class-row feature [B, embed]).  The tower runs its
+        dense forward: the one-row last block of ``vit_forward`` leaves the patch rows of the last block unfinished."""
+        if self.resnet:
+            raise ValueError("encode_image_tokens: a ModifiedResNet tower has no local tokens here -- its attention-pool head "
+                             "computes the one query row only (ViT towers only)")
+        v = self.model.visual
+        assert images.is_cuda and images.dtype == torch.float32, "images: fp32 device tensor [B,3,R,R]"
+        images = images.contiguous()
+        B = images.shape[0]
+        if images.shape[1] != 3 or images.shape[2] != v.input_resolution or images.shape[3] != v.input_resolution:
+            raise ValueError(f"expected images [B,3,{v.input_resolution},{v.input_resolution}], got {tuple(images.shape)}")
+        L, d = v.tokens, v.width
+        P = (v.input_resolution // v.patch_size) ** 2
+        x0 = torch.empty(B * L, d, device=images.device, dtype=torch.float32)
+        ops.patch_embed(images, v.conv1.weight.data, v.positional_embedding.data, x0, L)
+        ops.vit_fill_special(x0, v.class_embedding.data, v.positional_embedding.data,
+                             None if v.VPT is None else v.VPT.data, B, L, P)
+        x = ops.layernorm_fwd(x0, v.ln_pre.weight.data, v.ln_pre.bias.data)
+        self.vis.forward(x, B, False, seed)
+        y = ops.layernorm_fwd(x, v.ln_post.weight.data, v.ln_post.bias.data)
+        feat = ops.gemm_nt(y, self.vproj_t).view(B, L, -1)
+        return feat[:, 1:1 + P].contiguous(), feat[:, 0].contiguous()
+
     def vit_backward(self, ctx: dict, dfeat: torch.Tensor) -> None:
         """Accumulates into the LoRA gradient slots (and VPT.grad_slot, and the slots of trainable biases)."""
         v = self.model.visual
@@ -895,6 +920,17 @@ def encode_image(model, images: torch.Tensor) -> torch.Tensor:
     # train mode, slow_pace.py:1612,1659-1661, is dropout-on)
     feat, _ = model.engine.vit_forward(images, False, model.engine.next_seed() if model.training else 0)
     return feat
+
+
+@torch.no_grad()
+def encode_image_tokens(model, images: torch.Tensor, with_class: bool = False):
+    """Local image features [B, P, embed]: every patch row of a ViT tower through ln_post and proj (the class row and
+    the VPT rows are dropped), without a graph, in any precision mode.  ``with_class``: (tokens, class-row feature
+    [B, embed]) -- the feature ``encode_image`` returns.  Dropout follows model.training, as in ``encode_image``'s no-grad
+    route.  A ModifiedResNet tower is refused."""
+    images = images.to(device=model.device, dtype=torch.float32)
+    tokens, cls = model.engine.vit_tokens(images, model.engine.next_seed() if model.training else 0)
+    return (tokens, cls) if with_class else tokens
 
 
 def encode_text(model, ids: torch.Tensor, prompt_ctx: Optional[torch.Tensor] = None) -> torch.Tensor:

@@ -1494,3 +1494,80 @@ def clip_pairs_loss(img, txt, img_group=None, txt_group=None, *, head):
     elif img_group is None or txt_group is None:
         raise ValueError("clip_pairs_loss needs both img_group and txt_group, or neither")
     return ClipPairsLossFn.apply(img, txt, head, img_group.to(torch.int32).contiguous(), txt_group.to(torch.int32).contiguous())
+
+
+# ------------------------------------------------------------------------------------------------ OT matching (PLOT)
+def _ot_shapes(x, p):
+    assert x.dim() == 3 and p.dim() == 3 and x.shape[2] == p.shape[2], "ot: x is [B, M, d], p is [C, N, d]"
+    return x.shape[0], x.shape[1], p.shape[0], p.shape[1], x.shape[2]
+
+
+def ot_plan(B: int, M: int, C_: int, N: int, d: int):
+    """What ``ot_logits`` and ``ot_bwd`` launch for B images of M local rows against C_ classes of N prompts (host-only):
+    fwd_launches = dp_launches = dx_launches = 1, the grids, the class chunk, LDS bytes."""
+    return _lib.ot_plan(B, M, C_, N, d)
+
+
+def ot_logits(x, p, mu=None, nu=None, eps=0.1, iters=100, scale=100.0, out=None):
+    """(logits [B, C], u [B, C, M], v [B, C, N]): the optimal-transport matching score of include/clipfs.h ("OT
+    matching") for unit rows ``x`` [B, M, d] and ``p`` [C, N, d] in one launch.  ``mu`` [B, M] and ``nu`` [C, N] are the
+    marginals (None: uniform).  ``u`` and ``v`` are the Sinkhorn scalings ``ot_bwd`` reads.  ``out`` may be a column slice
+    (row stride >= C, unit column stride)."""
+    B, M, Cn, N, d = _ot_shapes(x, p)
+    assert mu is None or tuple(mu.shape) == (B, M), "ot: mu is [B, M]"
+    assert nu is None or tuple(nu.shape) == (Cn, N), "ot: nu is [C, N]"
+    if out is None:
+        out = torch.empty(B, Cn, device=x.device, dtype=torch.float32)
+    assert out.dtype == torch.float32 and tuple(out.shape) == (B, Cn) and out.stride(1) == 1, "ot: out"
+    u = torch.empty(B, Cn, M, device=x.device, dtype=torch.float32)
+    v = torch.empty(B, Cn, N, device=x.device, dtype=torch.float32)
+    check(_lib.load().clipfs_ot_logits(_p(_f32(x)), _p(_f32(p)), _p(None if mu is None else _f32(mu)),
+                                       _p(None if nu is None else _f32(nu)), _p(out), _ld(out), _p(u), _p(v), B, M, Cn, N, d,
+                                       eps, iters, scale, _stream()), "ot_logits")
+    return out, u, v
+
+
+def ot_bwd(x, p, u, v, dlogits, eps=0.1, scale=100.0, dp=None, dx=None, want_dx=False, accumulate=False):
+    """(dp [C, N, d], dx [B, M, d] or None): the gradients of ``ot_logits`` for ``dlogits`` [B, C] with the transport plan
+    held constant, one launch each.  ``dp`` / ``dx`` given: written, or added to with ``accumulate``; ``dx`` is computed
+    when given or ``want_dx``."""
+    B, M, Cn, N, d = _ot_shapes(x, p)
+    assert tuple(u.shape) == (B, Cn, M) and tuple(v.shape) == (B, Cn, N), "ot: u is [B, C, M], v is [B, C, N]"
+    assert dlogits.dtype == torch.float32 and tuple(dlogits.shape) == (B, Cn) and dlogits.stride(1) == 1, "ot: dlogits"
+    assert not accumulate or (dp is not None and (dx is not None or not want_dx)), "ot: accumulate needs dp (and dx)"
+    if dp is None:
+        dp = torch.empty_like(p)
+    if dx is None and want_dx:
+        dx = torch.empty_like(x)
+    assert dp.shape == p.shape and (dx is None or dx.shape == x.shape)
+    check(_lib.load().clipfs_ot_bwd(_p(_f32(x)), _p(_f32(p)), _p(_f32(u)), _p(_f32(v)), _p(dlogits), _ld(dlogits), _p(_f32(dp)),
+                                    _p(None if dx is None else _f32(dx)), B, M, Cn, N, d, eps, scale, int(bool(accumulate)),
+                                    _stream()), "ot_bwd")
+    return dp, dx
+
+
+class OtMatchFn(torch.autograd.Function):
+    """``ot_logits`` differentiable w.r.t. ``x`` and ``p`` with the transport plan a constant (PLOT's rule)."""
+
+    @staticmethod
+    def forward(ctx, x, p, mu, nu, eps, iters, scale):
+        x, p = x.contiguous(), p.contiguous()
+        mu = None if mu is None else mu.contiguous()
+        nu = None if nu is None else nu.contiguous()
+        logits, u, v = ot_logits(x, p, mu, nu, eps, iters, scale)
+        ctx.save_for_backward(x, p, u, v)
+        ctx.eps, ctx.scale = float(eps), float(scale)
+        return logits
+
+    @staticmethod
+    def backward(ctx, dlogits):
+        x, p, u, v = ctx.saved_tensors
+        dp, dx = ot_bwd(x, p, u, v, dlogits.contiguous(), ctx.eps, ctx.scale, want_dx=ctx.needs_input_grad[0])
+        return dx, dp if ctx.needs_input_grad[1] else None, None, None, None, None, None
+
+
+def ot_match(x, p, mu=None, nu=None, eps=0.1, iters=100, scale=100.0):
+    """logits [B, C] = scale * <T, z>: the optimal-transport matching of unit local rows ``x`` [B, M, d] against unit
+    prompt rows ``p`` [C, N, d], T from ``iters`` Sinkhorn iterations at ``eps`` between the marginals ``mu`` [B, M] and
+    ``nu`` [C, N] (None: uniform).  Autograd reaches ``x`` and ``p`` only, with T held constant."""
+    return OtMatchFn.apply(x, p, mu, nu, eps, iters, scale)

@@ -334,6 +334,10 @@ class CLIP(nn.Module):
         from clipfs.engine import encode_image
         return encode_image(self, image)
 
+    def encode_image_tokens(self, image: torch.Tensor, with_class: bool = False):
+        from clipfs.engine import encode_image_tokens
+        return encode_image_tokens(self, image, with_class)
+
     def encode_text(self, text: torch.Tensor) -> torch.Tensor:
         from clipfs.engine import encode_text
         return encode_text(self, text)
