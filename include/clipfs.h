@@ -1532,6 +1532,50 @@ int clipfs_spd_factor(const float* A, int lda, float* L, int ldl, int n, int32_t
 int clipfs_spd_solve(const float* L, int ldl, int n, const float* R, int ldr, float* X, int ldx, int nrhs, float alpha,
                      void* stream);
 
+/* The panelled pair: the same contract for n a multiple of 4 in [4, 16384], built right-looking over panels of `panel`
+ * columns (a multiple of 32 in [32, 1024]) from the kernels above and clipfs_gemm_nt.  WHICH TO CALL: clipfs_spd_factor /
+ * clipfs_spd_solve for n <= 1024 (fewer, fused launches; a right-hand side's whole row stays in LDS); the panelled pair
+ * above that.  With n <= panel clipfs_spd_factor_panels IS clipfs_spd_factor, launch for launch and bit for bit.
+ *
+ * clipfs_spd_factor_panels, per panel [c0, c1): (1) the diagonal block by the block-32 factor kernel (ceil(pn / 32)
+ * launches, its `info` reports carried to GLOBAL 1-based columns and never overwritten by a later panel: `info` is the
+ * FIRST pivot that is <= 0 or not finite); (2) L21 = A21 L11^-T, the forward substitution alone with the rows of A21 as
+ * right-hand sides; (3) L21 mirrored into the strict upper triangle; (4) the trailing update A22 -= L21 L21^T in row
+ * bands of 4 panels, band b one clipfs_gemm_nt call (alpha = -1, residual = C = the band, sub-matrix views by leading
+ * dimension, never split along K) over the columns up to its own last row, so that 1/2 + 2 panel / n of the square's
+ * products are formed.  The first panel reads A, every later one L; only the lower triangle of A reaches the result
+ * (elements above the diagonal of a band's last block are read and overwritten, their values never used), the whole
+ * n x n output is L below and L^T above, L == A with ldl == lda is bitwise the out-of-place result, and columns before a
+ * reported pivot are valid.  clipfs_gemm_nt with C == residual (ldc == ldres) is allowed: every element is read and then
+ * written by the one thread that owns it.
+ *
+ * clipfs_spd_solve_panels: X[i, :] = alpha * A^-1 R[i, :].  Forward over the panels: the substitution on the diagonal
+ * block (the right-hand sides' panel columns in LDS), then one clipfs_gemm_nt call that takes the panel's part out of
+ * all later columns (the panel's rows of L, contiguous); backward from the last panel with the rows of the transposed
+ * copy; one last launch scales by alpha.  The right-hand sides live in X (panel 0 reads R), X == R with ldx == ldr is
+ * allowed.  This schedule needs no caller scratch, so the call takes none.
+ *
+ * Launches (clipfs_spd_panels_plan, host-only), P = ceil(n / panel), pn_k = panel k's columns, rest_k = the rows below it:
+ *   factor   sum_k ceil(pn_k / 32) + 2 (P - 1) kernel launches and sum_{k < P - 1} ceil(rest_k / (4 panel)) GEMM calls
+ *   solve    2 P + 1 kernel launches and 2 (P - 1) GEMM calls
+ * No float atomics, nothing returns to the host, results are bitwise equal run to run.  Refusals are those of the pair
+ * above with n in [4, 16384], plus: panel not a multiple of 32 in [32, 1024]. */
+struct clipfs_spd_panels_plan {
+  int panel;           /* as given */
+  int panels;          /* P = ceil(n / panel) */
+  int band;            /* rows of one trailing-update GEMM call: 4 panel */
+  int factor_launches; /* kernel launches of the factor, GEMM calls not counted */
+  int factor_gemms;    /* clipfs_gemm_nt calls of the factor */
+  int solve_launches;  /* 2 P + 1 */
+  int solve_gemms;     /* 2 (P - 1) */
+  unsigned threads;    /* 256 */
+  unsigned lds_bytes;  /* the largest LDS of a workgroup: the substitution's 32 (min(n, panel) + 4) floats + 25 KB */
+};
+int clipfs_spd_panels_plan(int n, int nrhs, int panel, struct clipfs_spd_panels_plan* plan);
+int clipfs_spd_factor_panels(const float* A, int lda, float* L, int ldl, int n, int panel, int32_t* info, void* stream);
+int clipfs_spd_solve_panels(const float* L, int ldl, int n, int panel, const float* R, int ldr, float* X, int ldx, int nrhs,
+                            float alpha, void* stream);
+
 /* --------------------------------------------------------------------- GDA --
  * Training-free Gaussian discriminant head (Wang et al., "A Hard-to-Beat Baseline for Training-Free CLIP-Based
  * Adaptation", ICLR 2024): one mean per class and ONE shared full covariance of the few-shot features, shrunk towards
@@ -1613,6 +1657,85 @@ int clipfs_gda_bias(const struct clipfs_gda_params* params, const struct clipfs_
 int clipfs_gda_search(const float* g, const float* base, int ldbase, const int64_t* target, const float* alphas,
                       int32_t* hits, int B, int C, int nA, void* stream);
 int clipfs_gda_fit(const struct clipfs_gda_params* params, const struct clipfs_gda_buffers* buffers, void* stream);
+
+/* --------------------------------------------------------------------- KRR --
+ * Kernel ridge regression head (ProKeR: Bendou et al., "ProKeR: A Kernel Perspective on Few-Shot Adaptation of Large
+ * Vision-Language Models", CVPR 2025): the Tip-Adapter kernel k(x, s) = exp(-beta (1 - x . s)) with the global closed-form
+ * solution of the ridge problem in its RKHS, regularised towards a base predictor.  Training-free, fp32, no backward.
+ * More general than the paper in two places: the base predictor is whatever logits the caller supplies (for the shots
+ * and for the queries; NULL: 0), and the one-hot targets carry a scale t.
+ *
+ * THE RULE.  Inputs: shots S [n, d] with unit rows (assumed, not checked) in ANY label order, labels int32 [n], base_S
+ * [n, C] (row stride ldbs) or NULL.  d a multiple of 4 in [4, 1024], n in [1, 16384], C in [1, 4096], beta in (0, 100],
+ * lambda > 0 and finite, t finite.  n4 = 4 ceil(n / 4).
+ *   1. A [n4, n4] = exp(-beta (1 - S S^T)) + lambda I: one clipfs_gemm_nt call (S S^T into A) and one map launch in
+ *      place, exp as exp2((a - 1) (beta log2 e)), the diagonal computed like any other element, then + lambda.  Pad rows
+ *      and columns (n .. n4) are the identity, written by the map; the whole n4 x n4 matrix is defined.
+ *   2. Et [C, n4]: Et[c, j] = t [labels[j] == c] - base_S[j, c]; pad columns are 0.  One class per row: the layout the
+ *      solves take as right-hand sides.  A label outside [0, C) matches no class (labels are compared, never used as an
+ *      index); labels_host, an optional HOST copy, is checked before anything is enqueued.
+ *   3. A = L L^T and At = Et A^-1 (rows as right-hand sides): clipfs_spd_factor / clipfs_spd_solve when n4 <= 1024, the
+ *      panelled pair with `panel` above that.  At [C, n4] has the contraction index contiguous; its pad columns are 0.
+ *   4. out[b, c] = base[b, c] + sum_{j < n} exp(-beta (1 - x_b . s_j)) At[c, j] for queries X [B, d] (clipfs_krr_apply).
+ *
+ * clipfs_krr_apply: one workgroup per 32 query rows and class chunk, grid (ceil(B / 32), ceil(C / class_chunk)).  It walks
+ * the keys in tiles of 32: both operands pass through LDS, the four waves' partial dot products are added in wave order,
+ * g is formed once in LDS, then every wave contracts g with the rows of At for its share of the 32-class tiles on
+ * v_mfma_f32_32x32x2_f32, the accumulators in registers: tiles_per_wave in {1, 2, 4, 8}, class_chunk = 128 tiles_per_wave
+ * (1024 classes at 8; more classes go over grid.y, each chunk forming g again).  The [B, n] affinity never reaches memory;
+ * no float atomics; a row's result depends on neither B nor the other rows; bitwise equal run to run.  base (NULL: 0) and
+ * out are [B, C] with row strides ldbase, ldo (column slices); out must not overlap base.
+ *
+ * clipfs_krr_fit IS clipfs_krr_system, clipfs_krr_targets, the factor and the solve in this order on `stream`, bit for
+ * bit; every intermediate is a named output.  buffers: inputs shots, labels, labels_host (host, optional), base_S + ldbs
+ * (optional); outputs A [n4, n4], chol [n4, n4] (may be A: the factor runs in place), info [1] int32, Et [C, n4], At
+ * [C, n4] (may be Et); there is no caller scratch.  Launches: 3 (one of them the GEMM call) + the
+ * factor's + the solve's, a closed form of (n, panel) that clipfs_krr_plan returns.
+ *
+ * clipfs_krr_plan(n, C, d, B, panel) is host-only (nothing written on refusal).  CLIPFS_EINVAL before anything is
+ * enqueued, the message naming the argument: d, n, C, B, panel, beta, lambda, t out of range; ld / ldet / ldat / ldbs /
+ * ldbase / ldo too small (or, for A, Et and At, not a multiple of 4); a pointer NULL or misaligned (16 bytes for the
+ * matrices, 4 for labels and info); out overlapping base; a label of labels_host outside [0, C); params or buffers NULL
+ * or of another struct_size; a written member of the fit overlapping another member (other than chol == A, At == Et). */
+struct clipfs_krr_params {
+  unsigned struct_size; /* sizeof(struct clipfs_krr_params) */
+  int n, C, d;
+  int panel;    /* of the panelled factor and solve (used when n4 > 1024) */
+  float beta;   /* kernel sharpness */
+  float lambda; /* ridge */
+  float t;      /* target scale */
+};
+struct clipfs_krr_buffers {
+  unsigned struct_size;
+  const float* shots;
+  const int32_t* labels;
+  const int32_t* labels_host;
+  const float* base_S;
+  int ldbs;
+  float* A;
+  float* chol;
+  int32_t* info;
+  float* Et;
+  float* At;
+};
+struct clipfs_krr_plan {
+  int n4;              /* 4 ceil(n / 4) */
+  int panelled;        /* 1: n4 > 1024, the panelled factor and solve */
+  int fit_launches;    /* kernel launches and GEMM calls of a fit */
+  int factor_launches; /* of these: the factor's ... */
+  int solve_launches;  /* ... and the solve's (GEMM calls included) */
+  int tiles_per_wave;  /* of the apply: 32-class accumulators per wave */
+  int class_chunk;     /* 128 tiles_per_wave */
+  unsigned apply_grid_x, apply_grid_y, threads;
+  unsigned lds_bytes;  /* the largest LDS of a workgroup (at most 160 KB) */
+};
+int clipfs_krr_plan(int n, int C, int d, int B, int panel, struct clipfs_krr_plan* plan);
+int clipfs_krr_system(const float* S, float* A, int n, int d, int ld, float beta, float lambda, void* stream);
+int clipfs_krr_targets(const int32_t* labels, const int32_t* labels_host, const float* base_S, int ldbs, float* Et, int n, int C,
+                       int ldet, float t, void* stream);
+int clipfs_krr_apply(const float* X, const float* S, const float* At, int ldat, const float* base, int ldbase, float* out,
+                     int ldo, int B, int n, int C, int d, float beta, void* stream);
+int clipfs_krr_fit(const struct clipfs_krr_params* params, const struct clipfs_krr_buffers* buffers, void* stream);
 
 /* ------------------------------------------------------------- OT matching --
  * Optimal-transport matching of M local image features against the N prompt features of every class (PLOT: Chen et al.,

@@ -239,6 +239,33 @@ class GdaPlan(C.Structure):
                 ("lds_bytes", C.c_uint), ("xt_floats", C.c_size_t)]
 
 
+class SpdPanelsPlan(C.Structure):
+    """struct clipfs_spd_panels_plan: what clipfs_spd_factor_panels and clipfs_spd_solve_panels launch."""
+    _fields_ = [("panel", C.c_int), ("panels", C.c_int), ("band", C.c_int), ("factor_launches", C.c_int),
+                ("factor_gemms", C.c_int), ("solve_launches", C.c_int), ("solve_gemms", C.c_int), ("threads", C.c_uint),
+                ("lds_bytes", C.c_uint)]
+
+
+class KrrParams(C.Structure):
+    """struct clipfs_krr_params: the shapes and hyper-parameters of a kernel ridge fit."""
+    _fields_ = [("struct_size", C.c_uint), ("n", C.c_int), ("C", C.c_int), ("d", C.c_int), ("panel", C.c_int),
+                ("beta", C.c_float), ("lambda_", C.c_float), ("t", C.c_float)]
+
+
+class KrrBuffers(C.Structure):
+    """struct clipfs_krr_buffers: the inputs and the named outputs of a kernel ridge fit (labels_host is host memory)."""
+    _fields_ = [("struct_size", C.c_uint), ("shots", C.c_void_p), ("labels", C.c_void_p), ("labels_host", C.c_void_p),
+                ("base_S", C.c_void_p), ("ldbs", C.c_int), ("A", C.c_void_p), ("chol", C.c_void_p), ("info", C.c_void_p),
+                ("Et", C.c_void_p), ("At", C.c_void_p)]
+
+
+class KrrPlan(C.Structure):
+    """struct clipfs_krr_plan: what a kernel ridge fit and apply launch."""
+    _fields_ = [("n4", C.c_int), ("panelled", C.c_int), ("fit_launches", C.c_int), ("factor_launches", C.c_int),
+                ("solve_launches", C.c_int), ("tiles_per_wave", C.c_int), ("class_chunk", C.c_int), ("apply_grid_x", C.c_uint),
+                ("apply_grid_y", C.c_uint), ("threads", C.c_uint), ("lds_bytes", C.c_uint)]
+
+
 class OtPlan(C.Structure):
     """struct clipfs_ot_plan: what clipfs_ot_logits and clipfs_ot_bwd launch."""
     _fields_ = [("fwd_launches", C.c_int), ("dp_launches", C.c_int), ("dx_launches", C.c_int), ("rows_per_lane", C.c_int),
@@ -446,12 +473,20 @@ SIGNATURES = {
     "clipfs_spd_plan": (_i, [C.c_int, C.c_int, C.POINTER(SpdPlan)]),
     "clipfs_spd_factor": (_i, [_p, C.c_int, _p, C.c_int, C.c_int, _p, _p]),
     "clipfs_spd_solve": (_i, [_p, C.c_int, C.c_int, _p, C.c_int, _p, C.c_int, C.c_int, C.c_float, _p]),
+    "clipfs_spd_panels_plan": (_i, [C.c_int, C.c_int, C.c_int, C.POINTER(SpdPanelsPlan)]),
+    "clipfs_spd_factor_panels": (_i, [_p, C.c_int, _p, C.c_int, C.c_int, C.c_int, _p, _p]),
+    "clipfs_spd_solve_panels": (_i, [_p, C.c_int, C.c_int, C.c_int, _p, C.c_int, _p, C.c_int, C.c_int, C.c_float, _p]),
     "clipfs_gda_plan": (_i, [C.POINTER(GdaParams), C.POINTER(GdaPlan)]),
     "clipfs_gda_stats": (_i, [C.POINTER(GdaParams), C.POINTER(GdaBuffers), _p]),
     "clipfs_gda_shrink": (_i, [C.POINTER(GdaParams), C.POINTER(GdaBuffers), _p]),
     "clipfs_gda_bias": (_i, [C.POINTER(GdaParams), C.POINTER(GdaBuffers), _p]),
     "clipfs_gda_search": (_i, [_p, _p, C.c_int, _p, _p, _p, C.c_int, C.c_int, C.c_int, _p]),
     "clipfs_gda_fit": (_i, [C.POINTER(GdaParams), C.POINTER(GdaBuffers), _p]),
+    "clipfs_krr_plan": (_i, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(KrrPlan)]),
+    "clipfs_krr_system": (_i, [_p, _p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, _p]),
+    "clipfs_krr_targets": (_i, [_p, _p, _p, C.c_int, _p, C.c_int, C.c_int, C.c_int, C.c_float, _p]),
+    "clipfs_krr_apply": (_i, [_p, _p, _p, C.c_int, _p, C.c_int, _p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, _p]),
+    "clipfs_krr_fit": (_i, [C.POINTER(KrrParams), C.POINTER(KrrBuffers), _p]),
     "clipfs_ot_plan": (_i, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(OtPlan)]),
     "clipfs_ot_logits": (_i, [_p, _p, _p, _p, _p, C.c_int, _p, _p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
                               C.c_int, C.c_float, _p]),
@@ -638,6 +673,39 @@ def gda_plan(params: GdaParams):
     plan = GdaPlan()
     check(load().clipfs_gda_plan(C.byref(params), C.byref(plan)), "gda_plan")
     return {k: getattr(plan, k) for k, _ in GdaPlan._fields_}
+
+
+def spd_panels_plan(n: int, nrhs: int = 1, panel: int = 256):
+    """The plan clipfs_spd_factor_panels / clipfs_spd_solve_panels execute (host-only), as a dict of the fields of struct
+    clipfs_spd_panels_plan.  A refusal raises ClipfsError with its message."""
+    plan = SpdPanelsPlan()
+    check(load().clipfs_spd_panels_plan(n, nrhs, panel, C.byref(plan)), "spd_panels_plan")
+    return {k: getattr(plan, k) for k, _ in SpdPanelsPlan._fields_}
+
+
+def new_krr_params(**fields) -> KrrParams:
+    p = KrrParams()
+    p.struct_size = C.sizeof(KrrParams)
+    for k, v in fields.items():
+        setattr(p, k, v)
+    return p
+
+
+def new_krr_buffers(**members) -> KrrBuffers:
+    """struct clipfs_krr_buffers with the named members set (addresses as integers); the rest stay NULL / 0."""
+    b = KrrBuffers()
+    b.struct_size = C.sizeof(KrrBuffers)
+    for k, v in members.items():
+        setattr(b, k, v)
+    return b
+
+
+def krr_plan(n: int, C_: int, d: int, B: int = 1, panel: int = 256):
+    """The plan clipfs_krr_fit / clipfs_krr_apply execute (host-only), as a dict of the fields of struct clipfs_krr_plan.  A
+    refusal raises ClipfsError with its message."""
+    plan = KrrPlan()
+    check(load().clipfs_krr_plan(n, C_, d, B, panel, C.byref(plan)), "krr_plan")
+    return {k: getattr(plan, k) for k, _ in KrrPlan._fields_}
 
 
 def ot_plan(B: int, M: int, C_: int, N: int, d: int):

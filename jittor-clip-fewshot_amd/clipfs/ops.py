@@ -1136,6 +1136,147 @@ def spd_solve(chol: torch.Tensor, rhs: torch.Tensor, alpha: float = 1.0, out: Op
     return out
 
 
+def spd_panels_plan(n: int, nrhs: int = 1, panel: int = 256):
+    """What ``spd_factor_panels`` and ``spd_solve_panels`` launch (host-only): panels, band, the kernel launches and GEMM
+    calls of the factor and of the solve and lds_bytes."""
+    return _lib.spd_panels_plan(n, nrhs, panel)
+
+
+def spd_factor_panels(a: torch.Tensor, out: Optional[torch.Tensor] = None, panel: int = 256):
+    """``spd_factor`` for n up to 16384, right-looking over panels of ``panel`` columns (a multiple of 32 in [32, 1024]):
+    the same arguments, the same (chol, info) with ``info`` the first bad pivot as a global 1-based index.  Call
+    ``spd_factor`` for n <= 1024; with n <= panel this IS ``spd_factor``, bit for bit."""
+    n = a.shape[0]
+    _spd_matrix(a, n, "spd_factor_panels: a")
+    if out is None:
+        out = torch.empty(n, n, device=a.device, dtype=torch.float32)
+    _spd_matrix(out, n, "spd_factor_panels: out")
+    assert out.shape[0] == n
+    info = torch.empty(1, device=a.device, dtype=torch.int32)
+    check(_lib.load().clipfs_spd_factor_panels(_p(a), _ld(a), _p(out), _ld(out), n, panel, _p(info), _stream()),
+          "spd_factor_panels")
+    return out, info
+
+
+def spd_solve_panels(chol: torch.Tensor, rhs: torch.Tensor, alpha: float = 1.0, out: Optional[torch.Tensor] = None,
+                     panel: int = 256) -> torch.Tensor:
+    """``spd_solve`` for n up to 16384 from ``spd_factor_panels(A)[0]`` (``panel`` need not be the factor's); the
+    right-hand sides live in ``out``, there is no scratch.  ``out=rhs`` solves in place."""
+    n = chol.shape[0]
+    _spd_matrix(chol, n, "spd_solve_panels: chol")
+    _spd_matrix(rhs, n, "spd_solve_panels: rhs")
+    if out is None:
+        out = torch.empty(rhs.shape[0], n, device=rhs.device, dtype=torch.float32)
+    _spd_matrix(out, n, "spd_solve_panels: out")
+    assert out.shape[0] == rhs.shape[0]
+    check(_lib.load().clipfs_spd_solve_panels(_p(chol), _ld(chol), n, panel, _p(rhs), _ld(rhs), _p(out), _ld(out), rhs.shape[0],
+                                              alpha, _stream()),
+          "spd_solve_panels")
+    return out
+
+
+# ------------------------------------------------------------------------------------------------ kernel ridge head
+def krr_plan(n: int, C_: int, d: int, B: int = 1, panel: int = 256):
+    """What ``krr_fit`` and ``krr_apply`` launch (host-only): n4, panelled, fit_launches, factor_launches, solve_launches,
+    tiles_per_wave, class_chunk, the apply's grid, threads and lds_bytes."""
+    return _lib.krr_plan(n, C_, d, B, panel)
+
+
+def _n4(n: int) -> int:
+    return (n + 3) // 4 * 4
+
+
+def krr_system(shots, beta=5.5, lam=1.0, out=None):
+    """A [n4, n4] = exp(-beta (1 - S S^T)) + lam I of unit ``shots`` [n, d]; pad rows and columns are the identity."""
+    n, d = shots.shape
+    if out is None:
+        out = torch.empty(_n4(n), _n4(n), device=shots.device, dtype=torch.float32)
+    _spd_matrix(out, _n4(n), "krr_system: out")
+    check(_lib.load().clipfs_krr_system(_p(_f32(shots)), _p(out), n, d, _ld(out), beta, lam, _stream()), "krr_system")
+    return out
+
+
+def _krr_labels(labels, labels_host, n):
+    assert labels.is_cuda and labels.dtype == torch.int32 and labels.is_contiguous() and labels.numel() == n, \
+        "krr: labels must be a contiguous int32 device vector [n]"
+    if labels_host is not None:
+        assert not labels_host.is_cuda and labels_host.dtype == torch.int32 and labels_host.is_contiguous() \
+            and labels_host.numel() == n
+    return None if labels_host is None else labels_host.data_ptr()
+
+
+def _krr_base(base, rows, cols, what):
+    if base is None:
+        return None, 0
+    assert base.is_cuda and base.dtype == torch.float32 and tuple(base.shape) == (rows, cols) and base.stride(1) == 1, what
+    return _p(base), _ld(base)
+
+
+def krr_targets(labels, n_classes: int, shot_logits=None, target_scale=1.0, labels_host=None, out=None):
+    """Et [C, n4]: Et[c, j] = target_scale [labels[j] == c] - shot_logits[j, c]; ``labels`` int32 [n] in any order,
+    ``shot_logits`` [n, C] (a column slice is fine) or None.  ``labels_host`` (a CPU int32 copy) is checked first."""
+    n = labels.numel()
+    lh = _krr_labels(labels, labels_host, n)
+    if out is None:
+        out = torch.empty(n_classes, _n4(n), device=labels.device, dtype=torch.float32)
+    _spd_matrix(out, _n4(n), "krr_targets: out")
+    bp, ldb = _krr_base(shot_logits, n, n_classes, "krr_targets: shot_logits [n, C]")
+    check(_lib.load().clipfs_krr_targets(_p(labels), lh, bp, ldb, _p(out), n, n_classes, _ld(out), target_scale, _stream()),
+          "krr_targets")
+    return out
+
+
+def krr_apply(features, shots, At, base=None, beta=5.5, out=None):
+    """out [B, C] = base + exp(-beta (1 - features shots^T)) At[:, :n]^T in one launch; the [B, n] affinity never reaches
+    memory.  ``At`` [C, n4] from ``krr_fit``; ``base`` and ``out`` may be column slices; ``out`` must not alias ``base``."""
+    B, d = features.shape
+    n = shots.shape[0]
+    Cn = At.shape[0]
+    assert shots.shape[1] == d
+    _spd_matrix(At, _n4(n), "krr_apply: At")
+    if out is None:
+        out = torch.empty(B, Cn, device=features.device, dtype=torch.float32)
+    bp, ldb = _krr_base(base, B, Cn, "krr_apply: base [B, C]")
+    op, ldo = _krr_base(out, B, Cn, "krr_apply: out [B, C]")
+    check(_lib.load().clipfs_krr_apply(_p(_f32(features)), _p(_f32(shots)), _p(At), _ld(At), bp, ldb, op, ldo, B, n, Cn, d, beta,
+                                       _stream()), "krr_apply")
+    return out
+
+
+def krr_shapes(n: int, C_: int):
+    """{member: (shape, dtype)} of the outputs of struct clipfs_krr_buffers."""
+    n4 = _n4(n)
+    f32, i32 = torch.float32, torch.int32
+    return dict(A=((n4, n4), f32), chol=((n4, n4), f32), info=((1,), i32), Et=((C_, n4), f32), At=((C_, n4), f32))
+
+
+def krr_buffers(n: int, C_: int, device):
+    """Uninitialised device tensors for every output of a fit: every element is written before it is read."""
+    return {name: torch.empty(shape, device=device, dtype=dt) for name, (shape, dt) in krr_shapes(n, C_).items()}
+
+
+def krr_fit(shots, labels, n_classes: int, shot_logits=None, beta=5.5, lam=1.0, target_scale=1.0, panel=256, labels_host=None,
+            buffers=None):
+    """System, targets, factor and solve of the rule (include/clipfs.h, "KRR") on the current stream, no host
+    synchronisation, bitwise the stages called one by one: ``spd_factor`` / ``spd_solve`` when n4 <= 1024, the panelled
+    pair above.  Returns the ``buffers`` dict (``krr_buffers``): A, chol, info, Et, At; ``buffers["chol"]`` may be
+    ``buffers["A"]`` (the factor then runs in place) and ``buffers["At"]`` may be ``buffers["Et"]``."""
+    n, d = shots.shape
+    lh = _krr_labels(labels, labels_host, n)
+    if buffers is None:
+        buffers = krr_buffers(n, n_classes, shots.device)
+    for name, (shape, dt) in krr_shapes(n, n_classes).items():
+        t = buffers[name]
+        assert t.is_cuda and t.is_contiguous() and tuple(t.shape) == tuple(shape) and t.dtype == dt, \
+            f"krr_fit: buffers[{name!r}] must be a contiguous {dt} device tensor of shape {shape}"
+    bp, ldb = _krr_base(shot_logits, n, n_classes, "krr_fit: shot_logits [n, C]")
+    params = _lib.new_krr_params(n=n, C=n_classes, d=d, panel=panel, beta=beta, lambda_=lam, t=target_scale)
+    b = _lib.new_krr_buffers(shots=_p(_f32(shots)), labels=_p(labels), labels_host=lh, base_S=bp, ldbs=ldb, A=_p(buffers["A"]),
+                             chol=_p(buffers["chol"]), info=_p(buffers["info"]), Et=_p(buffers["Et"]), At=_p(buffers["At"]))
+    check(_lib.load().clipfs_krr_fit(C.byref(params), C.byref(b), _stream()), "krr_fit")
+    return buffers
+
+
 # ------------------------------------------------------------------------------------------------ GDA head
 GDA_DEFAULT_ALPHAS = tuple(10.0 ** e for e in range(-4, 5))
 

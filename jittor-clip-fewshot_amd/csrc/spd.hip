@@ -24,6 +24,14 @@
 //            solved times the block's rows of L (forward: the lower triangle; backward: the transposed copy in the strict
 //            upper triangle, so both read contiguous rows) on the matrix cores, then the 32 x 32 substitution in
 //            registers, one lane per row.  The forward launch leaves Y in X.
+//   panels   the same contract for n up to 16384 (clipfs_spd_factor_panels / clipfs_spd_solve_panels, at the end of this
+//            file), right-looking over panels of `panel` <= 1024 columns, built from the kernels above on sub-matrix
+//            views: the diagonal block by the factor kernel (its info reports carried to global columns by `base`, never
+//            overwritten by a later panel under `keep`), L21 = A21 L11^-T by the FORWARD solve launch alone with the rows
+//            of A21 as right-hand sides, L21 mirrored above the diagonal, A22 -= L21 L21^T by clipfs_gemm_nt in row
+//            bands that stop at their own last row.  The solve substitutes on a diagonal block (one-directional launch)
+//            and takes the panel's part out of every remaining column with one clipfs_gemm_nt call; the right-hand sides
+//            live in X, a last launch scales by alpha.
 //
 // No atomics at all; every output element is written by one thread; the order of every sum depends on n alone.
 #include "logits_tile.h"
@@ -102,8 +110,10 @@ __device__ __forceinline__ float spd_sum4(const float* Ps, int at) {
 // ------------------------------------------------------------------------------------------------- factor
 // Launch j: workgroups 0 .. nb - j - 1 own the tiles (j + x, j); with j > 0 workgroup nb - j forms, factors and writes
 // the diagonal tile (j - 1, j - 1).  A and L may be the same memory.
+// `base`, `keep`: the block is the diagonal block of a larger matrix (the panelled factor below) whose first column is
+// `base`, and with `keep` launch 0 leaves an earlier panel's report alone.  (0, 0) is the whole-matrix call.
 __global__ __launch_bounds__(SPD_THREADS) void spd_factor_kernel(const float* A, int lda, float* L, int ldl, int n, int j,
-                                                                 int32_t* info) {
+                                                                 int32_t* info, int base, int keep) {
   __shared__ float PsD[4 * 32 * SPD_TS];
   __shared__ float PsT[4 * 32 * SPD_TS];
   __shared__ float Ds[32 * SPD_TS];
@@ -150,8 +160,8 @@ __global__ __launch_bounds__(SPD_THREADS) void spd_factor_kernel(const float* A,
   if (diag) {
     if (!finish && tid == 0) {
       const int bad = s_bad;
-      if (j == 0) *info = bad;
-      else if (bad != 0 && *info == 0) *info = cj + bad;
+      if (j == 0 && !keep) *info = bad != 0 ? base + bad : 0;
+      else if (bad != 0 && *info == 0) *info = base + cj + bad;
     }
     if (!finish && j != nb - 1) return;  // written by the next launch (workgroup-uniform)
 #pragma unroll
@@ -255,6 +265,39 @@ __global__ __launch_bounds__(SPD_THREADS) void spd_solve_kernel(const float* L, 
   }
 }
 
+// ------------------------------------------------------------------------------------------------- panels
+// L[c0 + a, c1 + b] = L[c1 + b, c0 + a] for the `rows` x pn block below a diagonal block (pn a multiple of 32): one
+// workgroup per 32 x 32 tile, transposed through LDS.
+__global__ __launch_bounds__(SPD_THREADS) void spd_mirror_kernel(float* L, int ldl, int c0, int c1, int rows) {
+  __shared__ float T[32 * SPD_TS];
+  const int tid = threadIdx.x, i0 = 32 * (int)blockIdx.x, j0 = c0 + 32 * (int)blockIdx.y;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const int e = tid + SPD_THREADS * q, a = e >> 5, b = e & 31;
+    if (i0 + a < rows) T[a * SPD_TS + b] = L[(size_t)(c1 + i0 + a) * ldl + j0 + b];
+  }
+  __syncthreads();
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const int e = tid + SPD_THREADS * q, a = e >> 5, b = e & 31;
+    if (i0 + b < rows) L[(size_t)(j0 + a) * ldl + c1 + i0 + b] = T[b * SPD_TS + a];
+  }
+}
+
+// X[i, :n] *= alpha
+__global__ __launch_bounds__(SPD_THREADS) void spd_scale_kernel(float* X, int ldx, int n, int nrhs, float alpha) {
+  const int q4 = n >> 2;
+  const size_t total = (size_t)nrhs * q4;
+  for (size_t e = (size_t)blockIdx.x * SPD_THREADS + threadIdx.x; e < total; e += (size_t)gridDim.x * SPD_THREADS) {
+    const size_t row = e / q4;
+    f32x4* p = reinterpret_cast<f32x4*>(X + row * ldx + 4 * (e - row * q4));
+    f32x4 v = *p;
+#pragma unroll
+    for (int x = 0; x < 4; ++x) v[x] = alpha * v[x];
+    *p = v;
+  }
+}
+
 // ------------------------------------------------------------------------------------------------- host
 typedef struct clipfs_spd_plan SpdPlan;
 
@@ -316,7 +359,7 @@ extern "C" int clipfs_spd_factor(const float* A, int lda, float* L, int ldl, int
   const int nb = (n + SPD_B - 1) / SPD_B;
   for (int j = 0; j < nb; ++j)
     hipLaunchKernelGGL(spd_factor_kernel, dim3((unsigned)(nb - j + (j > 0 ? 1 : 0))), dim3(SPD_THREADS), 0, (hipStream_t)stream,
-                       A, lda, L, ldl, n, j, info);
+                       A, lda, L, ldl, n, j, info, 0, 0);
   return launch_status();
 }
 
@@ -344,5 +387,170 @@ extern "C" int clipfs_spd_solve(const float* L, int ldl, int n, const float* R, 
   hipLaunchKernelGGL(spd_solve_kernel<false>, dim3(grid), dim3(SPD_THREADS), lds, st, L, ldl, n, R, ldr, X, ldx, nrhs, 1.f);
   hipLaunchKernelGGL(spd_solve_kernel<true>, dim3(grid), dim3(SPD_THREADS), lds, st, L, ldl, n, (const float*)X, ldx, X, ldx, nrhs,
                      alpha);
+  return launch_status();
+}
+
+// ------------------------------------------------------------------------------------------------- panelled entry points
+namespace clipfs {
+namespace {
+
+constexpr int SPD_PANELS_MAX_N = 16384, SPD_MIN_PANEL = 32, SPD_MAX_PANEL = 1024;
+constexpr int SPD_BAND_PANELS = 4;  // rows of one trailing-update product, in panels
+
+typedef struct clipfs_spd_panels_plan SpdPanelsPlan;
+
+int spd_check_panels(int n, int panel, const char* who) {
+  CLIPFS_REQUIRE(n >= 4 && n <= SPD_PANELS_MAX_N && n % 4 == 0, "%s: n = %d must be a multiple of 4 in [4, %d]", who, n,
+                 SPD_PANELS_MAX_N);
+  CLIPFS_REQUIRE(panel >= SPD_MIN_PANEL && panel <= SPD_MAX_PANEL && panel % 32 == 0,
+                 "%s: panel = %d must be a multiple of 32 in [%d, %d]", who, panel, SPD_MIN_PANEL, SPD_MAX_PANEL);
+  return CLIPFS_OK;
+}
+
+void spd_allow_solve_lds(unsigned lds) {
+  if (lds > 64 * 1024) {  // per device, so asked for on every such call
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&spd_solve_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                              160 * 1024);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&spd_solve_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                              160 * 1024);
+  }
+}
+
+// C[M, N] = Res[M, N] - A[M, K] B[N, K]^T, every operand a sub-matrix view by its leading dimension; never split along K
+int spd_gemm_sub(const float* A, int lda, const float* B, int ldb, const float* Res, int ldres, float* C, int ldc, int M, int N,
+                 int K, void* stream) {
+  clipfs_gemm_args g = {};
+  g.struct_size = sizeof(g);
+  g.A = A;
+  g.B = B;
+  g.C = C;
+  g.M = M;
+  g.N = N;
+  g.K = K;
+  g.lda = lda;
+  g.ldb = ldb;
+  g.ldc = ldc;
+  g.alpha = -1.f;
+  g.residual = Res;
+  g.ldres = ldres;
+  return clipfs_gemm_nt(&g, stream);
+}
+
+}  // namespace
+}  // namespace clipfs
+
+extern "C" int clipfs_spd_panels_plan(int n, int nrhs, int panel, struct clipfs_spd_panels_plan* plan) {
+  const char* who = "clipfs_spd_panels_plan";
+  CLIPFS_REQUIRE(plan != nullptr, "%s: plan is NULL", who);
+  CLIPFS_CHECK(spd_check_panels(n, panel, who));
+  CLIPFS_REQUIRE(nrhs >= 1 && nrhs <= SPD_MAX_RHS, "%s: nrhs = %d outside [1, %d]", who, nrhs, SPD_MAX_RHS);
+  SpdPanelsPlan p = {};
+  p.panel = panel;
+  p.panels = (n + panel - 1) / panel;
+  p.band = SPD_BAND_PANELS * panel;
+  for (int k = 0; k < p.panels; ++k) {
+    const int c0 = k * panel, pn = n - c0 < panel ? n - c0 : panel, rest = n - c0 - pn;
+    p.factor_launches += (pn + SPD_B - 1) / SPD_B;
+    if (rest > 0) {
+      p.factor_launches += 2;  // L21 and its mirror
+      p.factor_gemms += (rest + p.band - 1) / p.band;
+    }
+  }
+  p.solve_launches = 2 * p.panels + 1;  // a substitution per panel and direction, the scaling
+  p.solve_gemms = 2 * (p.panels - 1);
+  p.threads = SPD_THREADS;
+  const unsigned fl = (unsigned)((10 * 32 * SPD_TS) * sizeof(float) + sizeof(int));
+  const unsigned sl = spd_solve_lds(n < panel ? n : panel);
+  p.lds_bytes = fl > sl ? fl : sl;
+  *plan = p;
+  return CLIPFS_OK;
+}
+
+extern "C" int clipfs_spd_factor_panels(const float* A, int lda, float* L, int ldl, int n, int panel, int32_t* info, void* stream) {
+  const char* who = "clipfs_spd_factor_panels";
+  CLIPFS_CHECK(spd_check_panels(n, panel, who));
+  CLIPFS_CHECK(spd_check_matrix(A, lda, n, "A", "lda", who));
+  CLIPFS_CHECK(spd_check_matrix(L, ldl, n, "L", "ldl", who));
+  CLIPFS_REQUIRE(info != nullptr, "%s: info is NULL", who);
+  CLIPFS_REQUIRE((reinterpret_cast<uintptr_t>(info) & 3u) == 0, "%s: info is not 4-byte aligned", who);
+  const size_t sa = spd_span(n, lda, n), sl = spd_span(n, ldl, n);
+  CLIPFS_REQUIRE((A == L && lda == ldl) || !spd_overlap(A, sa, L, sl),
+                 "%s: L overlaps A (allowed only as L == A with ldl == lda)", who);
+  CLIPFS_REQUIRE(!spd_overlap(info, 4, A, sa) && !spd_overlap(info, 4, L, sl), "%s: info overlaps A or L", who);
+  hipStream_t st = (hipStream_t)stream;
+  const int band = SPD_BAND_PANELS * panel;
+  // Panel 0 reads A; its trailing update writes the rest of the lower triangle into L, which every later panel reads.
+  const float* src = A;
+  int lds = lda;
+  for (int c0 = 0; c0 < n; c0 += panel) {
+    const int pn = n - c0 < panel ? n - c0 : panel, c1 = c0 + pn, rest = n - c1;
+    const int nb = (pn + SPD_B - 1) / SPD_B;
+    const float* sd = src + (size_t)c0 * lds + c0;
+    float* ld = L + (size_t)c0 * ldl + c0;
+    for (int j = 0; j < nb; ++j)
+      hipLaunchKernelGGL(spd_factor_kernel, dim3((unsigned)(nb - j + (j > 0 ? 1 : 0))), dim3(SPD_THREADS), 0, st, sd, lds, ld, ldl,
+                         pn, j, info, c0, c0 > 0 ? 1 : 0);
+    if (rest > 0) {
+      // L21 = A21 L11^-T: the forward substitution with the rows of A21 as right-hand sides
+      const unsigned slds = spd_solve_lds(pn);
+      spd_allow_solve_lds(slds);
+      float* l21 = L + (size_t)c1 * ldl + c0;
+      hipLaunchKernelGGL(spd_solve_kernel<false>, dim3((unsigned)((rest + 31) / 32)), dim3(SPD_THREADS), slds, st, (const float*)ld,
+                         ldl, pn, src + (size_t)c1 * lds + c0, lds, l21, ldl, rest, 1.f);
+      hipLaunchKernelGGL(spd_mirror_kernel, dim3((unsigned)((rest + 31) / 32), (unsigned)(pn / 32)), dim3(SPD_THREADS), 0, st, L, ldl,
+                         c0, c1, rest);
+      // A22 -= L21 L21^T in row bands: band b computes the columns up to its own last row only
+      for (int r0 = 0; r0 < rest; r0 += band) {
+        const int bh = rest - r0 < band ? rest - r0 : band;
+        CLIPFS_CHECK(spd_gemm_sub(l21 + (size_t)r0 * ldl, ldl, l21, ldl, src + (size_t)(c1 + r0) * lds + c1, lds,
+                                  L + (size_t)(c1 + r0) * ldl + c1, ldl, bh, r0 + bh, pn, stream));
+      }
+    }
+    src = L;
+    lds = ldl;
+  }
+  return launch_status();
+}
+
+extern "C" int clipfs_spd_solve_panels(const float* L, int ldl, int n, int panel, const float* R, int ldr, float* X, int ldx,
+                                       int nrhs, float alpha, void* stream) {
+  const char* who = "clipfs_spd_solve_panels";
+  CLIPFS_CHECK(spd_check_panels(n, panel, who));
+  CLIPFS_REQUIRE(nrhs >= 1 && nrhs <= SPD_MAX_RHS, "%s: nrhs = %d outside [1, %d]", who, nrhs, SPD_MAX_RHS);
+  CLIPFS_CHECK(spd_check_matrix(L, ldl, n, "L", "ldl", who));
+  CLIPFS_CHECK(spd_check_matrix(R, ldr, n, "R", "ldr", who));
+  CLIPFS_CHECK(spd_check_matrix(X, ldx, n, "X", "ldx", who));
+  CLIPFS_REQUIRE(isfinite(alpha), "%s: alpha = %g must be finite", who, (double)alpha);
+  const size_t sl = spd_span(n, ldl, n), sr = spd_span(nrhs, ldr, n), sx = spd_span(nrhs, ldx, n);
+  CLIPFS_REQUIRE((R == X && ldr == ldx) || !spd_overlap(R, sr, X, sx), "%s: X overlaps R (allowed only as X == R with ldx == ldr)",
+                 who);
+  CLIPFS_REQUIRE(!spd_overlap(X, sx, L, sl), "%s: X overlaps L", who);
+  hipStream_t st = (hipStream_t)stream;
+  const unsigned grid = (unsigned)((nrhs + 31) / 32);
+  spd_allow_solve_lds(spd_solve_lds(n < panel ? n : panel));
+  // forward, Y L^T = R: substitute on the diagonal block, then take the panel's part out of every later column.  Panel 0
+  // reads R; its update writes the later columns into X, where everything after it lives.
+  const float* src = R;
+  int lds = ldr;
+  for (int c0 = 0; c0 < n; c0 += panel) {
+    const int pn = n - c0 < panel ? n - c0 : panel, c1 = c0 + pn, rest = n - c1;
+    hipLaunchKernelGGL(spd_solve_kernel<false>, dim3(grid), dim3(SPD_THREADS), spd_solve_lds(pn), st, L + (size_t)c0 * ldl + c0, ldl,
+                       pn, src + c0, lds, X + c0, ldx, nrhs, 1.f);
+    if (rest > 0)
+      CLIPFS_CHECK(spd_gemm_sub(X + c0, ldx, L + (size_t)c1 * ldl + c0, ldl, src + c1, lds, X + c1, ldx, nrhs, rest, pn, stream));
+    src = X;
+    lds = ldx;
+  }
+  // backward, X L = Y, from the last panel: the rows of L^T are the strict upper triangle's
+  const int last = (n - 1) / panel * panel;
+  for (int c0 = last; c0 >= 0; c0 -= panel) {
+    const int pn = n - c0 < panel ? n - c0 : panel;
+    hipLaunchKernelGGL(spd_solve_kernel<true>, dim3(grid), dim3(SPD_THREADS), spd_solve_lds(pn), st, L + (size_t)c0 * ldl + c0, ldl,
+                       pn, (const float*)(X + c0), ldx, X + c0, ldx, nrhs, 1.f);
+    if (c0 > 0) CLIPFS_CHECK(spd_gemm_sub(X + c0, ldx, L + c0, ldl, X, ldx, X, ldx, nrhs, c0, pn, stream));
+  }
+  const size_t quads = (size_t)nrhs * (n >> 2);
+  const unsigned sgrid = (unsigned)((quads + SPD_THREADS - 1) / SPD_THREADS < 4096 ? (quads + SPD_THREADS - 1) / SPD_THREADS : 4096);
+  hipLaunchKernelGGL(spd_scale_kernel, dim3(sgrid), dim3(SPD_THREADS), 0, st, X, ldx, n, nrhs, alpha);
   return launch_status();
 }
