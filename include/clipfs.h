@@ -1801,6 +1801,97 @@ int clipfs_ot_logits(const float* X, const float* P, const float* mu, const floa
 int clipfs_ot_bwd(const float* X, const float* P, const float* u, const float* v, const float* dlogits, int ldd, float* dP,
                   float* dX, int B, int M, int C, int N, int d, float eps, float scale, int accumulate, void* stream);
 
+/* ------------------------------------------------------------------ AUGMIX --
+ * AugMix test-time views (Hendrycks et al., "AugMix: A Simple Data Processing Method to Improve Robustness and
+ * Uncertainty", ICLR 2020; the views test-time prompt tuning and TDA are published with) generated on the device from the
+ * uint8 image pool of clipfs_crop_batch, every uint8 image equal to PIL's bit for bit.  The host samples the recipe, the
+ * device does the pixels.  Where the published AugMix or TPT code differs from the rule below, the rule holds.
+ *
+ * THE RULE.  S is the view side.  `base` is the S x S x 3 uint8 image of the view's crop record: its arithmetic and its
+ * record {src, top, left, h, w, flip, out_w, out_h, win_x, win_y, filter, 0} are exactly those of clipfs_crop_batch.  A
+ * view has `width` chains; chain i starts from base and applies depth[i] operations, 0 to 3 of them, each reading a whole
+ * uint8 image and writing a whole uint8 image.  A chain of depth 0 is base itself.  Operations {code, param}:
+ *   NONE (0)          copy.
+ *   AUTOCONTRAST (1)  per channel (ImageOps.autocontrast, cutoff 0): lo and hi are the lowest and highest occupied bins of
+ *                     the channel's histogram.  hi <= lo: the LUT is the identity.  Otherwise in double, every operation
+ *                     rounded on its own: scale = 255.0 / (hi - lo), offset = -lo * scale,
+ *                     lut[i] = clamp(int(i * scale + offset), 0, 255), int() towards zero.
+ *   EQUALIZE (2)      per channel (ImageOps.equalize), all in integers: h the histogram,
+ *                     step = (sum(h) - (last non-zero entry of h)) / 255.  At most one occupied bin, or step == 0: the
+ *                     LUT is the identity.  Otherwise n = step / 2; for i = 0 .. 255: lut[i] = min(n / step, 255), then
+ *                     n += h[i] (the clamp is Image.point's).
+ *   POSTERIZE (3)     param = bits in [1, 8]: v & ~((1 << (8 - bits)) - 1).
+ *   SOLARIZE (4)      param = threshold in [0, 256]: v < threshold ? v : 255 - v.
+ *   AFFINE (5)        six double coefficients a0 .. a5 (Image.transform((S, S), AFFINE, a, BILINEAR)), fill 0.  For output
+ *                     pixel (x, y), in double, every multiply and add rounded on its own (no fma):
+ *                       xin = a0 (x + 0.5) + a1 (y + 0.5) + a2;  yin = a3 (x + 0.5) + a4 (y + 0.5) + a5  (left to right)
+ *                       xin < 0 || xin >= S || yin < 0 || yin >= S: the pixel is 0 in all channels.  Otherwise
+ *                       xin -= 0.5; yin -= 0.5; X = floor(xin); Y = floor(yin); dx = xin - X; dy = yin - Y
+ *                       x0 = clamp(X, 0, S-1), x1 = clamp(X+1, 0, S-1), yc = clamp(Y, 0, S-1)
+ *                       v1 = in[yc][x0] + (in[yc][x1] - in[yc][x0]) * dx
+ *                       v2 = the same on row Y + 1 if 0 <= Y + 1 < S, else v1
+ *                       out = (uint8)(v1 + (v2 - v1) * dy), truncated.
+ * The output view, in fp32, every operation rounded on its own:  t(u) = (u8 - mean * 255) * ((1 / 255) / std), the formula
+ * of clipfs_crop_batch;  acc = 0;  for i ascending: acc = acc + w[i] * t(chain_i);
+ *   out = m * t(base) + (1 - m) * acc,   fp32 [n, 3, S, S].
+ * With m = 1 and all depths 0 this is bitwise clipfs_crop_batch's out_norm for the same record.
+ *
+ * clipfs_augmix_batch: pool, source table and crop records as clipfs_crop_batch takes them (host tables validated, device
+ * copies read and re-checked by the kernels, which write nothing for a view that fails).  The recipe tables, each as a HOST
+ * copy (validated before anything is enqueued) and a device copy (read by the kernels, which execute no chain the host
+ * would have refused): ops int32 [n, width, 3, 2] = {code, param}; coef float64 [n, width, 3, 6] (read for AFFINE steps
+ * only); depth int32 [n, width]; w fp32 [n, width]; m fp32 [n].  Entries of ops and coef at or past a chain's depth are
+ * ignored.  mean, std: device fp32 [3].  base_u8 [n, S, S, 3] and chains_u8 [n, width, S, S, 3] are caller-owned uint8
+ * device buffers, documented OUTPUTS and the only working storage: base_u8 is the crop, chains_u8[v, i] the final image of
+ * chain i (base for depth 0).  Every element of base_u8, chains_u8 and out is written, none is read before it is
+ * written; there is no hidden scratch and no host synchronisation.
+ *
+ * Three launches on `stream`: base (the crop; grid (n, ceil(S / 16)), the resampling of crop_batch_kernel), chains (one
+ * workgroup of 1024 threads per (view, chain), the image resident in LDS for the whole chain: integer LDS histogram, LUT,
+ * in-place apply; AFFINE reads LDS, writes chains_u8 and reads it back if another operation follows), mix (four pixels per
+ * thread).  No float atomics; every output element is written by one thread; results are bitwise equal run to run, and a
+ * view's result does not depend on what shares the call.
+ *
+ * Limits: S in [8, 224] (one view's image, 150 528 bytes at S = 224, with its histograms and LUTs, is one CU's LDS; the
+ * 336-px towers are not offered), width in [1, 4], n in [1, 65 536], sources as clipfs_crop_batch.
+ *
+ * clipfs_augmix_plan(n, S, width) is host-only (no GPU is opened, nothing written on refusal) and IS the function the
+ * entry point executes: the three launches and the byte sizes of the two uint8 buffers.  The base launch's lds_bytes is its
+ * bound at 80 taps; a call asks for what its batch's largest tap count needs.  CLIPFS_EINVAL before anything is enqueued,
+ * the message naming the argument: n, S or width out of range; a NULL or misaligned pointer (base_u8, chains_u8 and out:
+ * 16 bytes; coef and the source table: 8; the other tables: 4); an op code outside 0..5; bits or threshold out of range; a
+ * depth outside 0..3; a non-finite coefficient, weight or m; everything clipfs_crop_batch refuses about a source or a
+ * record; out, base_u8 and chains_u8 overlapping each other or the pool; recipe NULL or of another struct_size. */
+enum { CLIPFS_AUGMIX_LAUNCH_BASE = 0, CLIPFS_AUGMIX_LAUNCH_CHAINS = 1, CLIPFS_AUGMIX_LAUNCH_MIX = 2 };
+enum {
+  CLIPFS_AUGMIX_NONE = 0, CLIPFS_AUGMIX_AUTOCONTRAST = 1, CLIPFS_AUGMIX_EQUALIZE = 2, CLIPFS_AUGMIX_POSTERIZE = 3,
+  CLIPFS_AUGMIX_SOLARIZE = 4, CLIPFS_AUGMIX_AFFINE = 5
+};
+struct clipfs_augmix_recipe {
+  unsigned struct_size; /* sizeof(struct clipfs_augmix_recipe) */
+  const int32_t *ops, *ops_dev;
+  const double *coef, *coef_dev;
+  const int32_t *depth, *depth_dev;
+  const float *w, *w_dev;
+  const float *m, *m_dev;
+};
+struct clipfs_augmix_launch {
+  unsigned grid_x, grid_y, block, lds_bytes;
+};
+struct clipfs_augmix_plan {
+  int launches;                          /* 3 */
+  struct clipfs_augmix_launch launch[3]; /* by CLIPFS_AUGMIX_LAUNCH_* */
+  unsigned lds_bytes;                    /* of a chain workgroup, the largest (at most 160 KB) */
+  size_t base_bytes;                     /* n S S 3 */
+  size_t chains_bytes;                   /* n width S S 3 */
+  size_t out_floats;                     /* n 3 S S */
+};
+int clipfs_augmix_plan(int n, int S, int width, struct clipfs_augmix_plan* plan);
+int clipfs_augmix_batch(const uint8_t* pool, size_t pool_bytes, const int64_t* src, const int64_t* src_dev, int n_src,
+                        const int32_t* recs, const int32_t* recs_dev, int n, int S, int width,
+                        const struct clipfs_augmix_recipe* recipe, const float* mean, const float* stdv, uint8_t* base_u8,
+                        uint8_t* chains_u8, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

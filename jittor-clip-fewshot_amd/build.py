@@ -15,9 +15,9 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 INCLUDE = os.path.join(os.path.dirname(HERE), "include")
 OUT = os.path.join(HERE, "clipfs", "libclipfs_hip.so")
-SOURCES = ["common.hip", "gemm.hip", "gemm_bf16.hip", "gemm_f16.hip", "norm.hip", "attention.hip", "attention_f16.hip", "attention_mfma.hip", "attention_mfma16.hip", "lora.hip", "lora_mfma.hip", "lora_merge.hip", "elem.hip", "mta.hip", "views.hip", "crops.hip", "resnet.hip", "bpe.hip", "bias_grad.hip", "prompts.hip", "tower.hip", "cache_head.hip", "tpt.hip", "contrastive.hip", "sigmoid_pairs.hip", "clip_pairs.hip", "tda.hip", "transduct.hip", "spd.hip", "gda.hip", "ot_match.hip", "krr.hip"]
+SOURCES = ["common.hip", "gemm.hip", "gemm_bf16.hip", "gemm_f16.hip", "norm.hip", "attention.hip", "attention_f16.hip", "attention_mfma.hip", "attention_mfma16.hip", "lora.hip", "lora_mfma.hip", "lora_merge.hip", "elem.hip", "mta.hip", "views.hip", "crops.hip", "resnet.hip", "bpe.hip", "bias_grad.hip", "prompts.hip", "tower.hip", "cache_head.hip", "tpt.hip", "contrastive.hip", "sigmoid_pairs.hip", "clip_pairs.hip", "tda.hip", "transduct.hip", "spd.hip", "gda.hip", "ot_match.hip", "krr.hip", "augmix.hip"]
 # every header a source may include: an edit to one rebuilds every object and changes the whole-library stamp
-HEADERS = tuple(os.path.join(CSRC, h) for h in ("common.h", "gemm_common.h", "lora.h", "convert16.h", "logits_tile.h")) + (os.path.join(INCLUDE, "clipfs.h"),)
+HEADERS = tuple(os.path.join(CSRC, h) for h in ("common.h", "gemm_common.h", "lora.h", "convert16.h", "logits_tile.h", "crops.h")) + (os.path.join(INCLUDE, "clipfs.h"),)
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-I", INCLUDE, "-I", CSRC, "-Wall",
          "-Wno-unused-function", "-ffp-contract=off"] + os.environ.get("HIPCC_EXTRA", "").split()

@@ -275,6 +275,26 @@ class OtPlan(C.Structure):
                 ("fwd_lds_bytes", C.c_uint), ("bwd_lds_bytes", C.c_uint)]
 
 
+class AugmixRecipe(C.Structure):
+    """struct clipfs_augmix_recipe: host and device copies of the five recipe tables of clipfs_augmix_batch."""
+    _fields_ = [("struct_size", C.c_uint)] + [(n + s, C.c_void_p) for n in ("ops", "coef", "depth", "w", "m") for s in ("", "_dev")]
+
+
+class AugmixLaunch(C.Structure):
+    _fields_ = [("grid_x", C.c_uint), ("grid_y", C.c_uint), ("block", C.c_uint), ("lds_bytes", C.c_uint)]
+
+
+# CLIPFS_AUGMIX_LAUNCH_* and the operation codes CLIPFS_AUGMIX_* of include/clipfs.h, by value
+AUGMIX_LAUNCHES = ("base", "chains", "mix")
+AUGMIX_CODES = ("none", "autocontrast", "equalize", "posterize", "solarize", "affine")
+
+
+class AugmixPlan(C.Structure):
+    """struct clipfs_augmix_plan: what clipfs_augmix_batch launches, and the sizes of its two uint8 buffers."""
+    _fields_ = [("launches", C.c_int), ("launch", AugmixLaunch * 3), ("lds_bytes", C.c_uint), ("base_bytes", C.c_size_t),
+                ("chains_bytes", C.c_size_t), ("out_floats", C.c_size_t)]
+
+
 class MergeJob(C.Structure):
     """struct clipfs_lora_merge_job: one projection of a clipfs_lora_merge table."""
     _fields_ = [("w", C.c_void_p), ("a", C.c_void_p), ("b", C.c_void_p), ("out", C.c_void_p), ("planes", C.c_void_p),
@@ -492,6 +512,8 @@ SIGNATURES = {
                               C.c_int, C.c_float, _p]),
     "clipfs_ot_bwd": (_i, [_p, _p, _p, _p, _p, C.c_int, _p, _p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
                            C.c_float, C.c_int, _p]),
+    "clipfs_augmix_plan": (_i, [_i, _i, _i, C.POINTER(AugmixPlan)]),
+    "clipfs_augmix_batch": (_i, [_p, _sz, _p, _p, _i, _p, _p, _i, _i, _i, C.POINTER(AugmixRecipe), _p, _p, _p, _p, _p, _p]),
 }
 
 # word indices of the loss-scaling record (CLIPFS_SCALER_* of include/clipfs.h)
@@ -714,6 +736,17 @@ def ot_plan(B: int, M: int, C_: int, N: int, d: int):
     plan = OtPlan()
     check(load().clipfs_ot_plan(B, M, C_, N, d, C.byref(plan)), "ot_plan")
     return {k: getattr(plan, k) for k, _ in OtPlan._fields_}
+
+
+def augmix_plan(n: int, S: int, width: int):
+    """The plan clipfs_augmix_batch executes for n views of side S with ``width`` chains (host-only), as a dict of the fields
+    of struct clipfs_augmix_plan with launch = {name: (grid_x, grid_y, block, lds_bytes)}.  A refusal raises ClipfsError
+    with its message."""
+    plan = AugmixPlan()
+    check(load().clipfs_augmix_plan(n, S, width, C.byref(plan)), "augmix_plan")
+    d = {k: getattr(plan, k) for k, _ in AugmixPlan._fields_ if k != "launch"}
+    d["launch"] = {AUGMIX_LAUNCHES[i]: (l.grid_x, l.grid_y, l.block, l.lds_bytes) for i, l in enumerate(plan.launch)}
+    return d
 
 
 def new_tower() -> Tower:

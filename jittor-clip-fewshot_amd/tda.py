@@ -17,8 +17,11 @@ the logits into a dense masked sum, at most five launches whatever B and C, no h
 run.  A sample's prediction, entropy and mask do not depend on the batch around it, so a stream gives the same caches
 however it is cut into calls.
 
-Not offered: sharing a cache among data-parallel ranks (each rank's stream adapts on its own), AugMix multi-view selection
-in front of the adapter, hyper-parameter search.
+``adapt_views`` / ``adapt_view_features`` put the paper's multi-view front end before the caches: of the V views of an image
+(``clipfs.augmix.view_groups``: AugMix views made on the device) the ``max(1, int(V rho))`` most confident ones are kept and
+the mean of their unit features is the image's one feature.
+
+Not offered: sharing a cache among data-parallel ranks (each rank's stream adapts on its own), hyper-parameter search.
 """
 from __future__ import annotations
 
@@ -141,6 +144,36 @@ class TestTimeDynamicAdapter:
             raise ValueError("adapt_images: the adapter was built without a clip_model")
         f = self.model.encode_image(images.to(self.model.device))
         return self.adapt_features(ops.l2norm_fwd(f.float().contiguous()), update)
+
+    @torch.no_grad()
+    def adapt_view_features(self, feats: torch.Tensor, rho: float = 0.1, update: bool = True) -> TDAResult:
+        """``feats`` [G, V, d]: the unit features of V views of each of G images, in stream order.  Per image the
+        ``max(1, int(V * rho))`` views of lowest zero-shot entropy are selected (``ops.tpt_objective``'s selection: ties to
+        the lower view index), the mean of their features (NOT renormalised: the logits are linear in it) is the image's
+        feature, and the G means go through ``adapt_features`` in order.  Never synchronises with the host."""
+        if feats.dim() != 3 or feats.shape[2] != self.width or feats.shape[1] < 1:
+            raise ValueError(f"adapt_view_features: expected feats [G, V, {self.width}], got {tuple(feats.shape)}")
+        if not 0.0 < rho <= 1.0:
+            raise ValueError(f"adapt_view_features: rho = {rho} must be in (0, 1]")
+        feats = feats.detach().to(device=self.device, dtype=torch.float32).contiguous()
+        G, V, d = feats.shape
+        K = max(1, int(V * rho))
+        _, selected, _, _ = ops.tpt_objective(feats, self.text, K, logit_scale=self.hyper["logit_scale"], want_grad=False)
+        picked = torch.gather(feats, 1, selected.long().unsqueeze(-1).expand(G, K, d))
+        return self.adapt_features(picked.mean(dim=1), update)
+
+    @torch.no_grad()
+    def adapt_views(self, views: torch.Tensor, rho: float = 0.1, update: bool = True) -> TDAResult:
+        """``views`` [G, V, 3, R, R] (``clipfs.augmix.view_groups``): one image tower pass over the G V views, one
+        normalisation, then ``adapt_view_features``."""
+        if self.model is None:
+            raise ValueError("adapt_views: the adapter was built without a clip_model")
+        if views.dim() != 5:
+            raise ValueError(f"adapt_views: expected views [G, V, 3, R, R], got {tuple(views.shape)}")
+        G, V = views.shape[:2]
+        f = self.model.encode_image(views.to(self.model.device).reshape(G * V, *views.shape[2:]))
+        f = ops.l2norm_fwd(f.float().contiguous())
+        return self.adapt_view_features(f.view(G, V, -1), rho, update)
 
 
 @torch.no_grad()

@@ -29,6 +29,25 @@ def make_tta_views(image, n_crops: int = 512, scale=(0.5, 1.0), seed: int = 0, s
     return views.make_views(image, recs, size, out=out)
 
 
+def make_augmix_views(image, n_views: int = 63, scale=(0.08, 1.0), severity: float = 1, width: int = 3, seed: int = 0,
+                      size: int = 224, device=None, out=None):
+    """The 1 + n_views AugMix views of one image as a device tensor [1 + n_views, 3, size, size], generated ON THE GPU
+    (csrc/augmix.hip, every uint8 image on the way pixel-exact with PIL): view 0 is the plain centre preprocess, bitwise
+    ``make_tta_views``' view 0; the rest are RandomResizedCrop(scale) + flip + AugMix(severity, width), the views test-time
+    prompt tuning and TDA are published with.  The one-image form of ``clipfs.augmix.view_groups`` (a pool of many images
+    makes every image's views in one call).  ``image``: PIL image, uint8 numpy [H, W, 3] or uint8 tensor."""
+    import numpy as np
+    from clipfs import augmix, data
+    if hasattr(image, "convert"):
+        image = np.asarray(image.convert("RGB"))
+    if device is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    pool = data.ImagePool.from_arrays([image], [0], device=device)
+    if out is not None:
+        out = out.view(1, *out.shape)
+    return augmix.view_groups(pool, [0], n_views, scale=scale, severity=severity, width=width, seed=seed, size=size, out=out)[0]
+
+
 @torch.no_grad()
 def fuse_top5(cos: torch.Tensor, cos1: torch.Tensor, cos3: torch.Tensor,
               head_logits: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
